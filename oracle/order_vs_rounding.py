@@ -1,4 +1,5 @@
-"""ORACLE-SIDE EVIDENCE (test infrastructure; needs oracle/_ref, i.e. the unmodified reference staged by oracle/make_ref.py).
+"""ORACLE-SIDE EVIDENCE (test infrastructure): the unmodified reference staged by oracle/make_ref.py (oracle/_ref), or -- where
+that is absent -- its restatement oracle/ctc_oracle.py, which tests/test_oracle_golden.py pins to the reference's beams and order.
 
 Question ("beam order is not bit-exact"): when this package returns the reference's beams in another
 ORDER inside a run of equal or nearly equal lm_scores, is a tie-break rule wrong -- or is that order not a property of the
@@ -43,6 +44,53 @@ def _exact_normaliser(orig):
             return tmp - np.log(s)
 
     return log_softmax
+
+
+def _exact_normalise(orig):
+    """oracle.ctc_oracle.normalise_logits with the same one change as above (float64 logits only)."""
+    from oracle.ctc_oracle import MIN_TOKEN_CLIP_P
+
+    exact = _exact_normaliser(None)
+
+    def normalise_logits(logits, sniff_on=None):
+        probe = logits if sniff_on is None else sniff_on
+        if logits.dtype != np.float64 or logits.size == 0 or math.isclose(probe.sum(axis=1).mean(), 1):
+            return orig(logits, sniff_on)
+        return np.clip(exact(logits, 1), np.log(MIN_TOKEN_CLIP_P), 0)
+
+    return normalise_logits
+
+
+def unstable_cases_oracle(names=None):
+    """unstable_cases() on oracle/ctc_oracle.py instead of the reference: the same experiment on its restatement."""
+    from oracle import ctc_oracle as O
+    from pyctcdecode_amd.alphabet import Alphabet
+    from tests.golden_util import lm_path, load_cases
+
+    cases, inputs = load_cases()
+    orig = O.normalise_logits
+    out = []
+    logging.disable(logging.CRITICAL)
+    try:
+        for case in cases:
+            x = inputs[case["input"]]
+            if x.dtype != np.float64 or x.shape[0] == 0 or (names is not None and case["name"] not in names):
+                continue
+            alpha = Alphabet.build_alphabet(case["labels"])
+            res = []
+            for variant in (orig, _exact_normalise(orig)):
+                O.normalise_logits = variant
+                orc = O.build_oracle(alpha.labels, alpha.is_bpe, lm_path(case["lm"]), case["unigrams"], **case["build"])
+                with np.errstate(all="ignore"):
+                    beams = orc.decode_beams(x, **case["decode"])
+                res.append([(b[0], tuple(b[2])) for b in beams])
+            if res[0] != res[1]:
+                assert sorted(res[0]) == sorted(res[1]), case["name"]  # the same beams, another order
+                out.append(case["name"])
+    finally:
+        O.normalise_logits = orig
+        logging.disable(logging.NOTSET)
+    return out
 
 
 def unstable_cases(names=None):

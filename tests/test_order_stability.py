@@ -37,17 +37,17 @@ def test_sim_returns_every_float64_golden_case_in_exactly_the_reference_order(si
 
 
 def test_cases_whose_order_hinges_on_the_last_bit_are_unstable_in_the_reference_itself():
-    """The four cases in which round 3's kernels (normaliser summed in another order) returned another order."""
+    """The four cases in which round 3's kernels (normaliser summed in another order) returned another order. Run on the
+    staged reference (oracle/_ref) where there is one, else on its restatement oracle/ctc_oracle.py, which the golden vectors
+    pin to the reference's beams and order (tests/test_oracle_golden.py): both name the same float64 golden cases."""
     from oracle import make_ref
-
-    if not make_ref.available():
-        pytest.skip("oracle/_ref (the staged reference) is not here")
-    from oracle.order_vs_rounding import unstable_cases
+    from oracle.order_vs_rounding import unstable_cases, unstable_cases_oracle
 
     suspects = ["toy_nolm_16beams", "toy_history_prune", "toy_lm_unk0_prune20", "toy_lm_autounigrams_prune60"]
     stable_sample = ["libri_char", "toy_lm_default"]
     names = [c["name"] for c in CASES]
-    got = unstable_cases(names=[n for n in suspects + stable_sample if n in names])
+    run = unstable_cases if make_ref.available() else unstable_cases_oracle
+    got = run(names=[n for n in suspects + stable_sample if n in names])
     assert sorted(got) == sorted(suspects)
 
 

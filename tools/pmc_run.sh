@@ -5,6 +5,6 @@ set -u
 out=$1; tag=$2; ctrs=$3; shift 3
 export TMPDIR=/tmp
 mkdir -p "$out"
-rocprofv3 --kernel-trace --pmc $ctrs --output-format csv -d "$out/$tag.d" -o "$tag" -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline "$@" > "$out/$tag.log" 2>&1
+rocprofv3 --kernel-trace --pmc $ctrs --output-format csv -d "$out/$tag.d" -o "$tag" -- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline "$@" > "$out/$tag.log" 2>&1
 python tools/pmc_summary.py "$out/$tag.d" "$out/$tag.json" > /dev/null
 rm -rf "$out/$tag.d"

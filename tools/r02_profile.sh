@@ -10,15 +10,15 @@ if [ "${SKIP_TESTS:-0}" != 1 ]; then
   timeout 1200 python -m pytest tests -m gpu -x -q > $out/pytest_gpu.log 2>&1
   tail -3 $out/pytest_gpu.log
 fi
-timeout 600 python bench.py > $out/bench.json 2> $out/bench.log
+timeout 600 python bench.py --full > $out/bench.json 2> $out/bench.log
 tail -1 $out/bench.json | cut -c1-400
 # 1-GPU rehearsal of the N>1 path (process group, device binding, the one all_gather per step)
 CTC_BENCH_FORCE_DIST=1 timeout 300 python bench.py --batch 1024 --steps 3 > $out/bench_dist1.json 2> $out/bench_dist1.log
 tail -1 $out/bench_dist1.json | cut -c1-200
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats.d -o stats -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-shard --no-peaky > $out/stats.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats.d -o stats -- python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-shard --no-peaky > $out/stats.log 2>&1
 find $out/stats.d -name '*kernel_stats.csv' -exec cp {} $out/kernel_stats_4096.csv \;
 rm -rf $out/stats.d
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats.d -o stats -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-shard --no-peaky --batch 512 > $out/stats512.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats.d -o stats -- python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-shard --no-peaky --batch 512 > $out/stats512.log 2>&1
 find $out/stats.d -name '*kernel_stats.csv' -exec cp {} $out/kernel_stats_512.csv \;
 rm -rf $out/stats.d
 for b in 4096 512; do

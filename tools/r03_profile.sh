@@ -10,7 +10,7 @@ if [ "${SKIP_TESTS:-0}" != 1 ]; then
   timeout 1500 python -m pytest tests -m gpu -x -q > $out/pytest_gpu.log 2>&1
   tail -4 $out/pytest_gpu.log
 fi
-timeout 900 python bench.py > $out/bench.json 2> $out/bench.log
+timeout 900 python bench.py --full > $out/bench.json 2> $out/bench.log
 tail -1 $out/bench.json | cut -c1-300
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats.d -o stats -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-shard --no-peaky --no-extras > $out/stats.log 2>&1
 find $out/stats.d -name '*kernel_stats.csv' -exec cp {} $out/kernel_stats_4096.csv \;

@@ -13,7 +13,7 @@ if [ "${SKIP_TESTS:-0}" != 1 ]; then
   tail -4 $out/pytest_gpu.log
 fi
 if [ "${SKIP_BENCH:-0}" != 1 ]; then
-  timeout 900 python bench.py > $out/bench.json 2> $out/bench.log
+  timeout 900 python bench.py --full > $out/bench.json 2> $out/bench.log
   tail -1 $out/bench.json | cut -c1-300
 fi
 B="--no-cpu-baseline --no-shard --no-peaky --no-extras"

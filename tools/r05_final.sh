@@ -17,5 +17,5 @@ rm -rf $out/stats.d
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats.d -o stats -- python bench.py --steps 5 --warmup 2 $B --batch 512 > $out/stats512.log 2>&1
 find $out/stats.d -name '*kernel_stats.csv' -exec cp {} $out/kernel_stats_512.csv \;
 rm -rf $out/stats.d
-timeout 900 python bench.py > $out/bench.json 2> $out/bench.log
+timeout 900 python bench.py --full > $out/bench.json 2> $out/bench.log
 tail -1 $out/bench.json | cut -c1-200

@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 out=gpurun_out/r05f${TAG:-}
 mkdir -p $out
 timeout 1500 python -m pytest tests -m gpu -x -q --durations=8 > $out/pytest_gpu.log 2>&1; echo "pytest rc=$?"; tail -14 $out/pytest_gpu.log
-timeout 900 python bench.py > $out/bench.json 2> $out/bench.log; echo "bench rc=$?"
+timeout 900 python bench.py --full > $out/bench.json 2> $out/bench.log; echo "bench rc=$?"
 python - <<PY
 import json
 d=json.load(open("$out/bench.json"))
