@@ -159,6 +159,17 @@ int ctcdec_lm_base_score(const ctcdec_decoder* dec, const ctcdec_lm_state* in, u
  * hot-word UNIGRAMS (already stripped and split by the caller) as UTF-8 blob + offsets. */
 int ctcdec_set_hotwords(ctcdec_decoder* dec, const char* blob, const int64_t* off, int64_t n_words);
 
+/* Per-utterance hot words for the NEXT decode call on this handle only (ctcdec_decode_batch, ctcdec_decode_stream_batch,
+ * ctcdec_stream_push, ctcdec_stream_import); that call takes them whatever its outcome, and the call after it is back on
+ * the set of ctcdec_set_hotwords, which keeps its meaning.  Set k = unigrams [set_off[k], set_off[k+1]) of blob / off
+ * (already stripped and split, as for ctcdec_set_hotwords), weight set_weight[k]; utterance / stream u uses set
+ * utt_set[u] (-1: none) in place of the call-wide set and DecodeParams hotword_weight.  A call whose utterance or stream
+ * count differs from n_utts fails (CTCDEC_ERR_ARG).  A backend whose kernels do not take per-utterance sets refuses them
+ * here (CTCDEC_ERR_LIMIT). */
+int ctcdec_set_hotword_sets(ctcdec_decoder* dec, const char* blob, const int64_t* off, int64_t n_words,
+                            const int64_t* set_off, int32_t n_sets, const double* set_weight,
+                            const int32_t* utt_set, int32_t n_utts);
+
 /* ---- the hot path: replaces decode_beams / decode_batch / decode_beams_batch ------------------
  * utt_logits[i] points to a row-major [utt_frames[i], n_labels] matrix of `dtype`; pointers may
  * be device (HBM-resident, no copy) or host memory (copied H2D first), is_device tells which.

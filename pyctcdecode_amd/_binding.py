@@ -109,6 +109,8 @@ _PROTOS = {
     "ctcdec_lm_base_score": (C.c_int, [_VP, C.POINTER(LmState), C.c_uint32, C.POINTER(LmState),
                                        C.POINTER(C.c_float)]),
     "ctcdec_set_hotwords": (C.c_int, [_VP, C.c_char_p, C.POINTER(C.c_int64), C.c_int64]),
+    "ctcdec_set_hotword_sets": (C.c_int, [_VP, C.c_char_p, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int64), C.c_int32,
+                                          C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_int32]),
     "ctcdec_decode_batch": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32,
                                       C.POINTER(Params), C.POINTER(LmState), C.POINTER(_VP)]),
     "ctcdec_decode_stream_batch": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32,

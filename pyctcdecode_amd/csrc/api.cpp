@@ -1,5 +1,6 @@
 // api.cpp -- the C ABI of include/ctcdec.h on top of backend.h + host_tables.h.
 #include <math.h>
+#include <cmath>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -191,6 +192,19 @@ struct ctcdec_decoder {
   int hist_order() const { return multi ? multi->order : lm_ptr->order; }
   HostHotwords hot;
   bool tables_dirty = true, hot_dirty = true;
+  // per-utterance hot words (ctcdec_set_hotword_sets): armed for the next decode call only. That call moves them to
+  // hot_call (HotCallScope) and builds the sets' tables when it first needs them; they are gone when it returns.
+  struct HotSets {
+    bool armed = false;
+    std::vector<std::vector<std::string>> words;  // per set: its unigrams
+    std::vector<double> weight;
+    std::vector<int32_t> utt_set;                 // per utterance / stream: its set (-1: none)
+    bool built = false;
+    std::vector<HostHotwords> sets;               // words.size() sets, plus an empty one when some utterance has none
+  };
+  HotSets hot_next, hot_call;
+  DevBuf d_hsets, d_htab, d_htok, d_hutt;
+  HostBuf h_hot;
   DevBuf d_tok, d_tok_hot, d_uni, d_pref, d_hot;  // (the n-gram tables: NgramStore::device, shared between decoders)
   DevBuf d_xuni[MAX_LMS - 1], d_winfo[MAX_LMS], w_xstate, w_impx;
   HostBuf h_xstate;
@@ -219,6 +233,11 @@ struct ctcdec_decoder {
     for (int k = 0; k < MAX_LMS; ++k) d_winfo[k].drop();
     w_xstate.drop();
     w_impx.drop();
+    d_hsets.drop();
+    d_htab.drop();
+    d_htok.drop();
+    d_hutt.drop();
+    h_hot.drop();
     h_xstate.drop();
     h_tok.drop();
     h_out.drop();
@@ -241,6 +260,81 @@ static int upload_staged(ctcdec_decoder* dec, DevBuf& b, const std::vector<T>& v
   memcpy(src, v.data(), bytes);
   dec->stage_used += (bytes + 63) & ~(size_t)63;
   return be::h2d_async(b.p, src, bytes, err);
+}
+
+// The sets armed by ctcdec_set_hotword_sets belong to the one decode call that takes them: moved into hot_call for
+// the call's duration, dropped when it returns (whatever its outcome).
+struct HotCallScope {
+  ctcdec_decoder* dec;
+  explicit HotCallScope(ctcdec_decoder* d) : dec(d) {
+    if (!dec) return;
+    dec->hot_call = std::move(dec->hot_next);
+    dec->hot_next = ctcdec_decoder::HotSets();
+  }
+  ~HotCallScope() {
+    if (dec) dec->hot_call = ctcdec_decoder::HotSets();
+  }
+};
+
+// the host tables of the call's sets (HostHotwords::build_table: the same hash and min_len / complete rules as the
+// call-wide set); utterances without a set are pointed at a trailing empty one
+static void build_hot_sets(ctcdec_decoder::HotSets& h) {
+  if (h.built) return;
+  h.sets.resize(h.words.size());
+  for (size_t k = 0; k < h.words.size(); ++k) h.sets[k].build_table(h.words[k]);
+  bool none = false;
+  for (int32_t& s : h.utt_set) {
+    if (s < 0) {
+      s = (int32_t)h.words.size();
+      none = true;
+    }
+  }
+  if (none) {
+    h.sets.emplace_back();
+    h.weight.push_back(0.0);
+  }
+  h.built = true;
+}
+
+// hot-word table a streaming import of stream u resolves its beams' words against
+static const HostHotwords& import_hot(const ctcdec_decoder* dec, int64_t u) {
+  const ctcdec_decoder::HotSets& h = dec->hot_call;
+  return h.armed ? h.sets[(size_t)h.utt_set[(size_t)u]] : dec->hot;
+}
+
+// Upload the call's sets: their tables one behind the other, one per-label view of n_labels entries per set (filled by the
+// device: be::launch_beam), the descriptors and each utterance's set index -- copied from page-locked memory on the decode
+// stream without the host waiting (the kernels that read them are queued behind). Sets ba's hot-set fields.
+static int upload_hot_sets(ctcdec_decoder* dec, be::BeamArgs* ba, std::string* err) {
+  ctcdec_decoder::HotSets& h = dec->hot_call;
+  build_hot_sets(h);
+  const size_t K = h.sets.size(), V = dec->alpha.labels.size(), n = h.utt_set.size();
+  std::vector<size_t> toff(K + 1, 0);
+  for (size_t k = 0; k < K; ++k) toff[k + 1] = toff[k] + h.sets[k].table.size();
+  const size_t b_sets = K * sizeof(HotSet), b_utt = n * sizeof(int32_t), b_tab = toff[K] * sizeof(HotEntry);
+  const size_t o_utt = (b_sets + 63) & ~(size_t)63, o_tab = (o_utt + b_utt + 63) & ~(size_t)63;
+  if (dec->d_hsets.ensure(std::max<size_t>(b_sets, 16), err) || dec->d_hutt.ensure(std::max<size_t>(b_utt, 16), err) ||
+      dec->d_htab.ensure(std::max<size_t>(b_tab, 16), err) || dec->d_htok.ensure(std::max<size_t>(K * V * sizeof(TokHot), 16), err) ||
+      dec->h_hot.ensure(o_tab + b_tab + 64, err))
+    return -1;
+  char* stage = (char*)dec->h_hot.p;
+  HotSet* hs = (HotSet*)stage;
+  for (size_t k = 0; k < K; ++k) {
+    const HostHotwords& w = h.sets[k];
+    hs[k].hot = w.table.empty() ? nullptr : (const HotEntry*)dec->d_htab.p + toff[k];
+    hs[k].hot_mask = w.mask;
+    hs[k].tok_hot = (const TokHot*)dec->d_htok.p + k * V;
+    hs[k].weight = h.weight[k];
+    if (!w.table.empty()) memcpy(stage + o_tab + toff[k] * sizeof(HotEntry), w.table.data(), w.table.size() * sizeof(HotEntry));
+  }
+  memcpy(stage + o_utt, h.utt_set.data(), b_utt);
+  if (be::h2d_async(dec->d_hsets.p, stage, b_sets, err) || be::h2d_async(dec->d_hutt.p, stage + o_utt, b_utt, err) ||
+      (b_tab && be::h2d_async(dec->d_htab.p, stage + o_tab, b_tab, err)))
+    return -1;
+  ba->hot_sets = (const HotSet*)dec->d_hsets.p;
+  ba->utt_hot = (const int32_t*)dec->d_hutt.p;
+  ba->n_hot_sets = (int32_t)K;
+  return 0;
 }
 
 struct ctcdec_result {
@@ -614,6 +708,36 @@ int ctcdec_set_hotwords(ctcdec_decoder* dec, const char* blob, const int64_t* of
   return CTCDEC_OK;
 }
 
+int ctcdec_set_hotword_sets(ctcdec_decoder* dec, const char* blob, const int64_t* off, int64_t n_words, const int64_t* set_off,
+                            int32_t n_sets, const double* set_weight, const int32_t* utt_set, int32_t n_utts) {
+  if (!dec) return fail(CTCDEC_ERR_ARG, "bad arguments");
+  dec->hot_next = ctcdec_decoder::HotSets();
+  if (n_words < 0 || n_sets < 0 || n_utts < 0 || (n_words > 0 && (!blob || !off)) || (n_sets > 0 && (!set_off || !set_weight)) ||
+      (n_utts > 0 && !utt_set))
+    return fail(CTCDEC_ERR_ARG, "bad arguments");
+  // the kernels of the HIP backend take each utterance's set; a backend that does not must not decode them with another
+  if (strncmp(be::name(), "hip", 3) != 0)
+    return fail(CTCDEC_ERR_LIMIT, std::string("per-utterance hot words are not supported by the '") + be::name() + "' backend");
+  if (n_sets > 0 && (set_off[0] != 0 || set_off[n_sets] != n_words)) return fail(CTCDEC_ERR_ARG, "set_off must run from 0 to n_words");
+  ctcdec_decoder::HotSets h;
+  h.words.resize((size_t)n_sets);
+  h.weight.assign(set_weight, set_weight + n_sets);
+  for (int32_t k = 0; k < n_sets; ++k) {
+    if (set_off[k + 1] < set_off[k]) return fail(CTCDEC_ERR_ARG, "set_off must not decrease");
+    if (!std::isfinite(set_weight[k])) return fail(CTCDEC_ERR_ARG, "hot-word weights must be finite");
+    for (int64_t i = set_off[k]; i < set_off[k + 1]; ++i) {
+      if (off[i + 1] < off[i]) return fail(CTCDEC_ERR_ARG, "bad word offsets");
+      h.words[(size_t)k].emplace_back(blob + off[i], (size_t)(off[i + 1] - off[i]));
+    }
+  }
+  h.utt_set.assign(utt_set, utt_set + n_utts);
+  for (int32_t s : h.utt_set)
+    if (s < -1 || s >= n_sets) return fail(CTCDEC_ERR_ARG, "utterance set index out of range");
+  h.armed = true;
+  dec->hot_next = std::move(h);
+  return CTCDEC_OK;
+}
+
 // Rebuild text + word frames of one beam from its emission list (root -> leaf). The text is written
 // in place: `open` is where the currently open (partial) word starts. A streaming beam starts from the
 // caller's beam named by its BR_IMPORT root (text so far + open partial word).
@@ -700,9 +824,11 @@ static int host_slices_wanted(const ctcdec_decoder* dec, const int32_t* utt_fram
 int ctcdec_decode_batch(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames,
                         int32_t n_utts, int32_t dtype, int32_t is_device, const ctcdec_params* p,
                         const ctcdec_lm_state* start_states, ctcdec_result** out) {
+  HotCallScope hot_scope(dec);
   // Large HOST batches (the reference's own calling convention: numpy in) go over in time slices, the copy of slice k + 1
-  // under the kernels of slice k (decode_host_sliced); 1 = "decode it in one piece after all" (probability-like rows)
-  if (dec && p && out && !is_device && n_utts > 0 && utt_logits && utt_frames && dtype >= CTCDEC_F32 && dtype <= CTCDEC_BF16) {
+  // under the kernels of slice k (decode_host_sliced); 1 = "decode it in one piece after all" (probability-like rows).
+  // (per-utterance hot words: in one piece)
+  if (dec && p && out && !is_device && !dec->hot_call.armed && n_utts > 0 && utt_logits && utt_frames && dtype >= CTCDEC_F32 && dtype <= CTCDEC_BF16) {
     const int n_slices = host_slices_wanted(dec, utt_frames, n_utts, dtype);
     if (n_slices >= 2) {
       const int rc = decode_host_sliced(dec, utt_logits, utt_frames, n_utts, dtype, p, start_states, n_slices, out);
@@ -724,6 +850,7 @@ int ctcdec_decode_stream_batch(ctcdec_decoder* dec, const void* const* utt_logit
   st.text_blob = text_blob;
   st.fold = (force_next_word || is_end) ? 1 : 0;
   st.eos = is_end ? 1 : 0;
+  HotCallScope hot_scope(dec);
   return decode_impl(dec, utt_logits, utt_frames, n_streams, dtype, is_device, p, nullptr, &st, out);
 }
 
@@ -732,7 +859,7 @@ int ctcdec_decode_stream_batch(ctcdec_decoder* dec, const void* const* utt_logit
 static int64_t shape_bw_limit(int beam_width) { return beam_bucket(beam_width); }
 
 static std::string build_import(const ctcdec_decoder* dec, const StreamIn& st, int64_t k, int beam_width, ImportBeam* m,
-                                LmState* more /* n_lms - 1 entries, or nullptr */) {
+                                LmState* more /* n_lms - 1 entries, or nullptr */, const HostHotwords& hot) {
   const ctcdec_beam_in& in = st.beams[k];
   memset(m, 0, sizeof(*m));
   if (in.text_end < in.text_begin || in.partial_end < in.partial_begin) return "bad beam text range";
@@ -752,7 +879,7 @@ static std::string build_import(const ctcdec_decoder* dec, const StreamIn& st, i
       th = text_push(th, h);
       wh.push_back(h);
       uint32_t ml = 0, cp = 0;
-      if (!dec->hot.table.empty() && hot_lookup(dec->hot.table.data(), dec->hot.mask, h, &ml, &cp) && cp) ++hw;
+      if (!hot.table.empty() && hot_lookup(hot.table.data(), hot.mask, h, &ml, &cp) && cp) ++hw;
     }
     a = b;
   }
@@ -775,7 +902,7 @@ static std::string build_import(const ctcdec_decoder* dec, const StreamIn& st, i
       wid = w;
     }
     uint32_t ml = 0, cp = 0;
-    if (!dec->hot.table.empty() && hot_lookup(dec->hot.table.data(), dec->hot.mask, m->part_h, &ml, &cp))
+    if (!hot.table.empty() && hot_lookup(hot.table.data(), hot.mask, m->part_h, &ml, &cp))
       m2 |= M2_HOT_ON | (cp ? M2_HOT_COMPLETE : 0u) | ((ml & 0xFFFFu) << 8);
   }
   m->m2 = m2;
@@ -835,6 +962,10 @@ static int decode_impl(ctcdec_decoder* dec, const void* const* utt_logits, const
     return CTCDEC_OK;
   }
   const int K = dec->has_lm ? dec->n_lms() : 1;
+  if (dec->hot_call.armed) {
+    if ((int32_t)dec->hot_call.utt_set.size() != n_utts) return fail(CTCDEC_ERR_ARG, "hot-word sets armed for another number of utterances");
+    if (stream && !rs) build_hot_sets(dec->hot_call);  // (the imported beams' words are counted against their stream's set)
+  }
   std::lock_guard<std::mutex> device_lock(g_device_mu);
   if (be::bind_thread(&err)) return fail(CTCDEC_ERR_DEVICE, err);
   if (sync_tables(dec, &err)) return fail(CTCDEC_ERR_DEVICE, err);
@@ -965,7 +1096,7 @@ static int decode_impl(ctcdec_decoder* dec, const void* const* utt_logits, const
       max_import = std::max<int32_t>(max_import, (int32_t)cnt);
       for (int64_t k = ioff[(size_t)u]; k < ioff[(size_t)u + 1]; ++k) {
         std::string e = build_import(dec, *stream, k, B, &imps[(size_t)k],
-                                     K > 1 ? &imps_x[(size_t)k * (size_t)(K - 1)] : nullptr);
+                                     K > 1 ? &imps_x[(size_t)k * (size_t)(K - 1)] : nullptr, import_hot(dec, u));
         if (!e.empty()) return fail(CTCDEC_ERR_ARG, e);
       }
     }
@@ -1185,6 +1316,9 @@ static int decode_impl(ctcdec_decoder* dec, const void* const* utt_logits, const
     if (!by_input && reserve_pay()) return fail(CTCDEC_ERR_DEVICE, err);
     auto run_beam = [&]() -> int {
       if (be::zero(dec->w_head.p, 16, &err)) return -1;
+      // per-utterance hot words: built and sent here, behind the first prune launch -- the host builds the tables while the
+      // prune stage runs
+      if (dec->hot_call.armed && !ba.hot_sets && upload_hot_sets(dec, &ba, &err)) return -1;
       return be::launch_beam(ba, &err);
     };
     // (a resident stream's beam kernel advances persistent state: it is launched once, when the prune stage has
@@ -1434,6 +1568,7 @@ int ctcdec_stream_push(ctcdec_stream* st, const void* const* chunk_logits, const
   sin.fold = (force_next_word || is_end) ? 1 : 0;
   sin.eos = is_end ? 1 : 0;
   ctcdec_result* res = nullptr;
+  HotCallScope hot_scope(st->dec);
   const int rc = decode_impl(st->dec, chunk_logits, chunk_frames, st->n, dtype, is_device, params,
                              st->start_states.empty() ? nullptr : st->start_states.data(), &sin, &res, st,
                              want_result != 0 || is_end != 0);
@@ -1456,6 +1591,11 @@ int ctcdec_stream_import(ctcdec_stream* st, const ctcdec_beam_in* beams, const i
                          int64_t text_bytes) {
   if (!st || !beams || !beam_off || !text_blob || text_bytes < 0) return fail(CTCDEC_ERR_ARG, "bad arguments");
   ctcdec_decoder* dec = st->dec;
+  HotCallScope hot_scope(dec);
+  if (dec->hot_call.armed) {
+    if ((int32_t)dec->hot_call.utt_set.size() != st->n) return fail(CTCDEC_ERR_ARG, "hot-word sets armed for another number of streams");
+    build_hot_sets(dec->hot_call);
+  }
   std::string err;
   std::lock_guard<std::mutex> device_lock(g_device_mu);
   if (be::bind_thread(&err)) return fail(CTCDEC_ERR_DEVICE, err);
@@ -1474,7 +1614,8 @@ int ctcdec_stream_import(ctcdec_stream* st, const ctcdec_beam_in* beams, const i
     if (cnt < 1 || cnt > ctcdec_stream::CAP) return fail(CTCDEC_ERR_ARG, "a stream must carry between 1 and 256 beams");
     for (int64_t k = 0; k < cnt; ++k) {
       const size_t slot = (size_t)u * ctcdec_stream::CAP + (size_t)k;
-      std::string e = build_import(dec, sin, beam_off[u] + k, 0, &imps[slot], K > 1 ? &imps_x[slot * (size_t)(K - 1)] : nullptr);
+      std::string e = build_import(dec, sin, beam_off[u] + k, 0, &imps[slot], K > 1 ? &imps_x[slot * (size_t)(K - 1)] : nullptr,
+                                   import_hot(dec, u));
       if (!e.empty()) return fail(CTCDEC_ERR_ARG, e);
     }
   }

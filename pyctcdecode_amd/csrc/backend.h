@@ -152,6 +152,12 @@ struct BeamArgs {
   float inv_n_utts;
   const float* block_weight;   // [n_utts] (prio_mode 33) expected cost of a frame of the utterance workgroup b decodes, relative to
                                // the launch's mean (utt_weigh / utt_place, backend_hip.hip); the same kernels write `order`
+  // per-utterance hot words (ctcdec_set_hotword_sets), else nullptr / 0: the call-wide tables.tok_hot / hot / hot_mask and
+  // params.hot_weight hold for every utterance. Utterance u (not workgroup u: `order` moves utterances) uses
+  // hot_sets[utt_hot[u]]; launch_beam first fills every set's per-label view, hot_sets[k].tok_hot (n_labels entries each)
+  const HotSet* hot_sets = nullptr;  // [n_hot_sets] (device)
+  const int32_t* utt_hot = nullptr;  // [n_utts] (device), each in [0, n_hot_sets)
+  int32_t n_hot_sets = 0;
 };
 int launch_beam(const BeamArgs& a, std::string* err);
 // Will launch_beam run the wave kernel on these arguments (given payload lines)? THE kernel-selection rule, shared by the

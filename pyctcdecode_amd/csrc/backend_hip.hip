@@ -2214,7 +2214,29 @@ bool wave_kernel_chosen(const BeamArgs& a) {
   return a.n_utts > 0 && !want_group && wave_eligible(a.tables, a.params) && a.max_import <= wave_bucket(a.params.beam_width);
 }
 
+// Per-label hot-word view of every set of a call with per-utterance hot words (what HostHotwords::build does on the host for
+// the call-wide set, host_tables.cpp): one wave per set, lanes over the labels. A label whose clean text is a prefix of one of
+// the set's hot words gets {shortest such word, is itself a hot word}, every other label {0, 0}.
+__global__ __launch_bounds__(64) void hot_tok_build(const HotSet* sets, int32_t n_sets, const TokInfo* tok, uint32_t n_labels) {
+  const int32_t k = (int32_t)blockIdx.x;
+  if (k >= n_sets) return;
+  const HotSet hs = sets[k];
+  TokHot* out = const_cast<TokHot*>(hs.tok_hot);
+  for (uint32_t i = threadIdx.x; i < n_labels; i += 64) {
+    const TokInfo& t = tok[i];
+    uint32_t ml = 0, cp = 0;
+    TokHot v{0u, 0u};
+    if (t.len_clean > 0 && hot_lookup(hs.hot, hs.hot_mask, t.h_clean, &ml, &cp)) v = TokHot{ml, cp};
+    out[i] = v;
+  }
+}
+
 int launch_beam(const BeamArgs& a, std::string* err) {
+  if (a.hot_sets && a.n_hot_sets > 0 && a.n_utts > 0) {
+    hipLaunchKernelGGL(hot_tok_build, dim3((unsigned)a.n_hot_sets), dim3(64), 0, g_stream, a.hot_sets, a.n_hot_sets, a.tables.tok,
+                       a.tables.n_labels);
+    HIP_TRY(hipGetLastError());
+  }
   // Two kernels for the same recursion. A lone utterance's frame takes about the same time in both (measured in round 4 on
   // the bench input: 11.3 us on the workgroup kernel's eight waves, 11.4 us on one wave), but a CU holds two workgroups
   // against sixteen waves and one wave needs an eighth of the issue slots per utterance: the wave kernel wins as soon as

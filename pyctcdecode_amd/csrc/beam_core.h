@@ -267,6 +267,8 @@ struct UttIO {
   StreamState* sstate;
   uint32_t emit_start;
   int32_t want_out;
+  // per-utterance hot words (ctcdec_set_hotword_sets): the utterance's set, nullptr = the call-wide tables and weight
+  const HotSet* hot_set = nullptr;
 };
 
 // (the launch behind the beam kernel when DecodeParams::texts_only is set: backend_hip.hip assemble_texts)
@@ -435,9 +437,10 @@ CTC_HD double div_by_6(double x) {
 }
 
 // language_model.py:141-150 (hot word) / :326-336 (unigram trie) / decoder.py:363-367,397-409
-CTC_HD double partial_score(const DeviceTables& t, const DecodeParams& prm, uint32_t pf_flags,
+// hot_weight: the utterance's (HotSet::weight, or the call-wide DecodeParams::hot_weight)
+CTC_HD double partial_score(const DeviceTables& t, const DecodeParams& prm, double hot_weight, uint32_t pf_flags,
                             uint32_t hot_min_len, uint32_t plen) {
-  if (hot_min_len > 0) return prm.hot_weight * (double)plen / (double)hot_min_len;
+  if (hot_min_len > 0) return hot_weight * (double)plen / (double)hot_min_len;
   if (!t.has_lm) return 0.0;
   bool on_trie = t.has_trie && (pf_flags & PF_UNI_PREFIX);
   double s = prm.unk * (on_trie ? 0.0 : 1.0);
@@ -491,6 +494,7 @@ struct BeamDecoder {
   const DeviceTables& tab;
   const DecodeParams& prm;
   const UttIO& io;
+  const HotSet hs;  // this utterance's hot words: its own set (UttIO::hot_set) or the call-wide tables and weight
   int cur;  // live beam buffer
   int N;    // live beams
   uint32_t pf_cnt = 0, pf_id = 0;  // survivors of the NEXT frame, fetched one frame ahead
@@ -514,7 +518,8 @@ struct BeamDecoder {
 
   CTC_HD BeamDecoder(Ctx& c, LdsView& l, const LdsShape& s, const DeviceTables& t, const DecodeParams& p,
                      const UttIO& i)
-      : ctx(c), L(l), shape(s), tab(t), prm(p), io(i), cur(0), N(1) {}
+      : ctx(c), L(l), shape(s), tab(t), prm(p), io(i),
+        hs(i.hot_set ? *i.hot_set : HotSet{t.hot, t.hot_mask, t.tok_hot, p.hot_weight}), cur(0), N(1) {}
 
   // beam table `which` (0/1) as a by-value bundle of LDS pointers (no run-time indexed struct arrays:
   // those would force the whole view into scratch memory)
@@ -677,7 +682,7 @@ CTC_UNROLL
     const uint64_t wh = b.part_h[i];
     const uint64_t th = text_push(src.text_h, wh);
     const uint32_t cnt = src.hw_cnt + ((m2 & M2_HOT_COMPLETE) ? 1u : 0u);
-    const double lmhw = raw + prm.hot_weight * (double)cnt;
+    const double lmhw = raw + hs.weight * (double)cnt;
     const uint32_t rc = src.ring_cnt + 1 > tab.n_hist ? tab.n_hist : src.ring_cnt + 1;
     // history ring (newest first) and its hash, without run-time indexed temporaries
     uint64_t hh = 0x9E3779B97F4A7C15ull + rc;
@@ -732,8 +737,8 @@ CTC_UNROLL
     CTC_TK_FIELD(uint32_t, flags, d->tab.tok[c].flags)
     CTC_TK_FIELD(uint32_t, start_flags, d->tab.tok[c].start_flags)
     CTC_TK_FIELD(uint32_t, start_word_id, d->tab.tok[c].start_word_id)
-    CTC_TK_FIELD(uint32_t, hot_min, (d->tab.tok_hot ? d->tab.tok_hot[c].min_len : 0u))
-    CTC_TK_FIELD(uint32_t, hot_complete, (d->tab.tok_hot ? d->tab.tok_hot[c].complete : 0u))
+    CTC_TK_FIELD(uint32_t, hot_min, (d->hs.tok_hot ? d->hs.tok_hot[c].min_len : 0u))
+    CTC_TK_FIELD(uint32_t, hot_complete, (d->hs.tok_hot ? d->hs.tok_hot[c].complete : 0u))
 #undef CTC_TK_FIELD
   };
   CTC_HD TkView tok_of(uint32_t s) const { return TkView{this, s}; }
@@ -749,8 +754,8 @@ CTC_UNROLL
     L.stok[s].flags = g.flags;
     L.stok[s].start_flags = g.start_flags;
     L.stok[s].start_word_id = g.start_word_id;
-    L.stok[s].hot_min = tab.tok_hot ? tab.tok_hot[c].min_len : 0u;
-    L.stok[s].hot_complete = tab.tok_hot ? tab.tok_hot[c].complete : 0u;
+    L.stok[s].hot_min = hs.tok_hot ? hs.tok_hot[c].min_len : 0u;
+    L.stok[s].hot_complete = hs.tok_hot ? hs.tok_hot[c].complete : 0u;
   }
 
   // issue the loads of frame t's survivor list; they are consumed by load_survivors(t) one frame later
@@ -777,8 +782,8 @@ CTC_UNROLL
     pf_tok.flags = g.flags;
     pf_tok.start_flags = g.start_flags;
     pf_tok.start_word_id = g.start_word_id;
-    pf_tok.hot_min = tab.tok_hot ? tab.tok_hot[pf_id].min_len : 0u;
-    pf_tok.hot_complete = tab.tok_hot ? tab.tok_hot[pf_id].complete : 0u;
+    pf_tok.hot_min = hs.tok_hot ? hs.tok_hot[pf_id].min_len : 0u;
+    pf_tok.hot_complete = hs.tok_hot ? hs.tok_hot[pf_id].complete : 0u;
   }
 
   CTC_HD void store_tok(uint32_t s) {  // survivor slot s <- the prefetched constants of this thread's label
@@ -1273,19 +1278,19 @@ CTC_UNROLL
       v.pl = tk.len_clean();
       v.m2 = (tk.start_flags() & (PF_PARTIAL_MASK | PF_ON_TABLE)) | (hmin ? M2_HOT_ON : 0u) | (hcomp ? M2_HOT_COMPLETE : 0u) | (hmin << 8);
       v.wid = tk.start_word_id();
-      v.ps = partial_score(tab, prm, tk.start_flags(), hmin, v.pl);
+      v.ps = partial_score(tab, prm, hs.weight, tk.start_flags(), hmin, v.pl);
     } else if (br == BR_APPEND) {
       uint32_t m2 = b.meta2[i];
       uint32_t pf = 0, nw = 0, hmin = 0, hcomp = 0;
       // first probe of both tables issued together (one memory round trip instead of two)
       const bool want_p = (m2 & PF_ON_TABLE) && tab.prefixes && new_part_h != 0;
-      const bool want_h = (m2 & M2_HOT_ON) && tab.hot && new_part_h != 0;
+      const bool want_h = (m2 & M2_HOT_ON) && hs.hot && new_part_h != 0;
       const uint64_t hk = table_slot(new_part_h);
-      uint64_t sp = hk & tab.prefix_mask, sh = hk & tab.hot_mask;
+      uint64_t sp = hk & tab.prefix_mask, sh = hk & hs.hot_mask;
       PrefixEntry ep = {0, 0, 0};
       HotEntry eh = {0, 0, 0};
       if (want_p) ep = have_pre ? pre_p : tab.prefixes[sp];
-      if (want_h) eh = have_pre ? pre_h : tab.hot[sh];
+      if (want_h) eh = have_pre ? pre_h : hs.hot[sh];
       bool on = false, hon = false;
       if (want_p) {
         while (ep.key != new_part_h && ep.key != 0) {
@@ -1298,8 +1303,8 @@ CTC_UNROLL
       }
       if (want_h) {
         while (eh.key != new_part_h && eh.key != 0) {
-          sh = (sh + 1) & tab.hot_mask;
-          eh = tab.hot[sh];
+          sh = (sh + 1) & hs.hot_mask;
+          eh = hs.hot[sh];
         }
         hon = eh.key == new_part_h;
         hmin = eh.min_len;
@@ -1309,7 +1314,7 @@ CTC_UNROLL
       v.m2 = (on ? (PF_ON_TABLE | (pf & PF_PARTIAL_MASK)) : 0u) | (hon ? M2_HOT_ON : 0u) | ((hon && hcomp) ? M2_HOT_COMPLETE : 0u) |
              ((hon ? hmin : 0u) << 8);
       v.wid = on ? nw : 0;
-      v.ps = partial_score(tab, prm, on ? pf : 0u, hon ? hmin : 0u, v.pl);
+      v.ps = partial_score(tab, prm, hs.weight, on ? pf : 0u, hon ? hmin : 0u, v.pl);
     } else {  // space, or a bare boundary mark: the open word is empty
       v.pl = 0;
       v.m2 = EMPTY_PARTIAL_M2;
@@ -1348,7 +1353,7 @@ CTC_UNROLL
           const uint32_t m2 = b.meta2[i];
           const uint64_t hk = table_slot(kp);
           if ((m2 & PF_ON_TABLE) && tab.prefixes) pre_p = tab.prefixes[hk & tab.prefix_mask];
-          if ((m2 & M2_HOT_ON) && tab.hot) pre_h = tab.hot[hk & tab.hot_mask];
+          if ((m2 & M2_HOT_ON) && hs.hot) pre_h = hs.hot[hk & hs.hot_mask];
           have_pre = true;
         }
       }
@@ -1502,7 +1507,7 @@ CTC_UNROLL
       depth += 1;
     }
     double ps = 0.0;
-    if (npl > 0) ps = partial_score(tab, prm, m2 & PF_PARTIAL_MASK, (m2 & M2_HOT_ON) ? ((m2 >> 8) & 0xFFFFu) : 0u, npl);
+    if (npl > 0) ps = partial_score(tab, prm, hs.weight, m2 & PF_PARTIAL_MASK, (m2 & M2_HOT_ON) ? ((m2 >> 8) & 0xFFFFu) : 0u, npl);
     nb.logit[dst] = L.p_logit[idx];
     nb.lm_hw[dst] = lmhw;
     nb.pscore[dst] = ps;
@@ -1820,7 +1825,7 @@ CTC_UNROLL
       TextNode& tn = io.text_nodes[node];
       tn.text_h = m.text_h;
       tn.raw_lm = m.raw_lm;
-      const double lmhw = m.raw_lm + prm.hot_weight * (double)m.hw_cnt;
+      const double lmhw = m.raw_lm + hs.weight * (double)m.hw_cnt;
       tn.lm_hw = lmhw;
       uint64_t hh = 0x9E3779B97F4A7C15ull + m.ring_cnt;
 CTC_UNROLL
@@ -1860,7 +1865,7 @@ CTC_UNROLL
       }
       b.logit[i] = m.logit_score;
       b.lm_hw[i] = lmhw;
-      b.pscore[i] = m.plen > 0 ? partial_score(tab, prm, m.m2 & PF_PARTIAL_MASK, (m.m2 & M2_HOT_ON) ? ((m.m2 >> 8) & 0xFFFFu) : 0u, m.plen) : 0.0;
+      b.pscore[i] = m.plen > 0 ? partial_score(tab, prm, hs.weight, m.m2 & PF_PARTIAL_MASK, (m.m2 & M2_HOT_ON) ? ((m.m2 >> 8) & 0xFFFFu) : 0u, m.plen) : 0.0;
       b.c_lm_hw[i] = 0.0;
       b.text_h[i] = m.text_h;
       b.part_h[i] = m.part_h;
@@ -1947,7 +1952,7 @@ CTC_UNROLL
             const double w = multi_word_score(
                 pl > 0 ? b.word_id[d] : 0u, true, [&](int k, LmState* st) { copy_state(st, src_nodes[k].state); },
                 [&](int, const LmState&) {});
-            lmhw = (src.raw_lm + w) + prm.hot_weight * (double)cnt;
+            lmhw = (src.raw_lm + w) + hs.weight * (double)cnt;
           } else if (tab.has_lm) {
             LmState end;
             uint32_t wid = pl > 0 ? b.word_id[d] : 0u;
@@ -1959,9 +1964,9 @@ CTC_UNROLL
               end_score = (double)lm_base_score(tab, end, tab.eos_id, &tmp);
             }
             double raw = src.raw_lm + lm_word_score(tab, prm, base_s, wfl, end_score, true);
-            lmhw = raw + prm.hot_weight * (double)cnt;
+            lmhw = raw + hs.weight * (double)cnt;
           } else {
-            lmhw = prm.hot_weight * (double)cnt;
+            lmhw = hs.weight * (double)cnt;
           }
         } else {
           lmhw = pl > 0 ? b.c_lm_hw[d] : b.lm_hw[d];  // memo entry (text (+) word, False)

@@ -250,8 +250,9 @@ struct WaveDecoder {
   struct Hot {
     const PrefixEntry* prefixes;
     uint64_t prefix_mask;
-    const HotEntry* hot;
+    const HotEntry* hot;  // (this utterance's hot words: its own set, UttIO::hot_set, or the call-wide ones)
     uint64_t hot_mask;
+    const TokHot* tok_hot;
     double prune_logp, hot_weight, unk;
     uint32_t has_lm, has_trie, prune_history, beam_width;
   } H;
@@ -260,10 +261,12 @@ struct WaveDecoder {
     const DecodeParams& P_ = prm();
     H.prefixes = T_.prefixes;
     H.prefix_mask = T_.prefix_mask;
-    H.hot = T_.hot;
-    H.hot_mask = T_.hot_mask;
+    const HotSet hs = io.hot_set ? *io.hot_set : HotSet{T_.hot, T_.hot_mask, T_.tok_hot, P_.hot_weight};
+    H.hot = hs.hot;
+    H.hot_mask = hs.hot_mask;
+    H.tok_hot = hs.tok_hot;
     H.prune_logp = P_.beam_prune_logp;
-    H.hot_weight = P_.hot_weight;
+    H.hot_weight = hs.weight;
     H.unk = P_.unk;
     H.has_lm = T_.has_lm ? 1u : 0u;
     H.has_trie = T_.has_trie ? 1u : 0u;
@@ -382,8 +385,8 @@ struct WaveDecoder {
     if (!(pf_live && l < pf_cnt)) return;
     if (q < 3u) {
       r.v = ((const u32x4a*)&T_.tok[id])[q];
-    } else if (T_.tok_hot) {
-      const uint64_t h = *(const uint64_t*)&T_.tok_hot[id];
+    } else if (H.tok_hot) {
+      const uint64_t h = *(const uint64_t*)&H.tok_hot[id];
       r.v[3] = ((uint32_t)h & 0xFFFFu) | ((uint32_t)(h >> 32) ? 0x80000000u : 0u);
     }
   }
@@ -465,7 +468,7 @@ CTC_UNROLL
         raw = raw + lm_word_score(T_, P_, base, m2, 0.0, false);
       }
       const uint32_t cnt = sn.hw_cnt + ((m2 & M2_HOT_COMPLETE) ? 1u : 0u);
-      const double lmhw = raw + P_.hot_weight * (double)cnt;
+      const double lmhw = raw + H.hot_weight * (double)cnt;
       const uint32_t rc0 = sn.ring_cnt;
       const uint32_t rc = rc0 + 1 > T_.n_hist ? T_.n_hist : rc0 + 1;
       // history ring, newest first: the closed word, then the source node's (its last entry drops out when the ring is full)
@@ -1343,7 +1346,7 @@ CTC_UNROLL
           lp = io.surv_lp[(size_t)t * prm().max_surv + s];
           const TokInfo& g = tab().tok[id];
           fl = g.flags;
-          const uint32_t hot = tab().tok_hot ? ((tab().tok_hot[id].min_len & 0xFFFFu) | (tab().tok_hot[id].complete ? 0x80000000u : 0u)) : 0u;
+          const uint32_t hot = H.tok_hot ? ((H.tok_hot[id].min_len & 0xFFFFu) | (H.tok_hot[id].complete ? 0x80000000u : 0u)) : 0u;
           L.lab[lane * 4 + 1] = mk4q(g.h_raw, g.pow_raw);
           L.lab[lane * 4 + 2] = mk4((uint32_t)g.h_clean, (uint32_t)(g.h_clean >> 32), g.len_raw, g.len_clean);
           L.lab[lane * 4 + 3] = mk4(g.flags, g.start_flags, g.start_word_id, hot);
@@ -1626,7 +1629,7 @@ CTC_UNROLL
       const uint32_t node = 1u + (uint32_t)i;  // node 0 is the empty text
       Node tn;
       tn.raw = m.raw_lm;
-      const double lmhw = m.raw_lm + P_.hot_weight * (double)m.hw_cnt;
+      const double lmhw = m.raw_lm + H.hot_weight * (double)m.hw_cnt;
       const uint64_t hh = wave_hist_fold(m.ring, m.ring_cnt);
 CTC_UNROLL
       for (int k = 0; k < MAX_CTX; ++k) tn.ring[k] = m.ring[k];
@@ -1654,7 +1657,7 @@ CTC_UNROLL
         }
         io.emit_nodes[enode] = en;
       }
-      const double ps = m.plen > 0 ? partial_score(T_, P_, m.m2 & PF_PARTIAL_MASK, (m.m2 & M2_HOT_ON) ? ((m.m2 >> 8) & 0xFFFFu) : 0u, m.plen) : 0.0;
+      const double ps = m.plen > 0 ? partial_score(T_, P_, H.hot_weight, m.m2 & PF_PARTIAL_MASK, (m.m2 & M2_HOT_ON) ? ((m.m2 >> 8) & 0xFFFFu) : 0u, m.plen) : 0.0;
       write_beam(i, m.text_h, m.part_h, m.logit_score, (m.last_char & 0xFFFFu) | (m.plen << 16),
                  m.plen > 0 ? m.m2 : EMPTY_PARTIAL_M2, lmhw, ps, hh, node, enode, m.word_id, m.pstart, m.pend, depth);
     }
@@ -1752,9 +1755,9 @@ CTC_UNROLL
               end_score = (double)lm_base_score<ORD>(tab(), end, tab().eos_id, &tmp);
             }
             const double raw = src.raw + lm_word_score(tab(), prm(), base_s, wfl, end_score, true);
-            lmhw = raw + prm().hot_weight * (double)cnt;
+            lmhw = raw + H.hot_weight * (double)cnt;
           } else {
-            lmhw = prm().hot_weight * (double)cnt;
+            lmhw = H.hot_weight * (double)cnt;
           }
         } else {
           lmhw = pl > 0 ? cold_cur()[d].c_lmhw : bits_f64(q_lo(d2));  // memo entry (text (+) word, False)

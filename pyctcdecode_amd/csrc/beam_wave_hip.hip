@@ -206,6 +206,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BW <= 100 ? 
   io.sstate = a.sstate ? a.sstate + u : nullptr;
   io.emit_start = a.sstate ? a.sstate[u].emit_next : 0u;
   io.want_out = a.want_out;
+  io.hot_set = a.utt_hot ? a.hot_sets + a.utt_hot[u] : nullptr;
   if (a.resident_in) {
     io.imports = a.imports + (size_t)u * a.carry_stride;
     io.n_import = (int32_t)a.sstate[u].n_carry;

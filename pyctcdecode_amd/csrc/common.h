@@ -201,6 +201,15 @@ struct TokHot {  // per call (hot words change per call): hot-word view of the C
   uint32_t complete;
 };
 
+// one hot-word set of a call with per-utterance hot words (ctcdec_set_hotword_sets): it stands in for the call-wide
+// DeviceTables::hot / hot_mask / tok_hot and DecodeParams::hot_weight for the utterances that use it
+struct HotSet {  // 32 B
+  const HotEntry* hot;    // nullptr: an empty set
+  uint64_t hot_mask;
+  const TokHot* tok_hot;  // [n_labels], filled on the device (backend_hip.hip: hot_tok_build)
+  double weight;
+};
+
 constexpr int MAX_CTX = 5;  // CTCDEC_MAX_LM_ORDER - 1
 
 struct LmState {

@@ -494,6 +494,19 @@ void HostLM::tables(DeviceTables* t) const {
 }
 
 void HostHotwords::build(const std::vector<std::string>& uni, const HostAlphabet& alpha) {
+  build_table(uni);
+  tok_hot.assign(alpha.tok.size(), TokHot{0, 0});
+  if (!table.empty()) {
+    for (size_t i = 0; i < alpha.tok.size(); ++i) {
+      const TokInfo& t = alpha.tok[i];
+      uint32_t ml = 0, cp = 0;
+      if (t.len_clean > 0 && hot_lookup(table.data(), mask, t.h_clean, &ml, &cp)) tok_hot[i] = TokHot{ml, cp};
+    }
+  }
+}
+
+void HostHotwords::build_table(const std::vector<std::string>& uni) {
+  tok_hot.clear();
   std::unordered_map<uint64_t, HotEntry> m;
   std::vector<size_t> bounds;
   for (const std::string& w : uni) {
@@ -526,14 +539,6 @@ void HostHotwords::build(const std::vector<std::string>& uni, const HostAlphabet
       uint64_t s = table_slot(kv.first) & mask;
       while (table[s].key != 0) s = (s + 1) & mask;
       table[s] = kv.second;
-    }
-  }
-  tok_hot.assign(alpha.tok.size(), TokHot{0, 0});
-  if (!table.empty()) {
-    for (size_t i = 0; i < alpha.tok.size(); ++i) {
-      const TokInfo& t = alpha.tok[i];
-      uint32_t ml = 0, cp = 0;
-      if (t.len_clean > 0 && hot_lookup(table.data(), mask, t.h_clean, &ml, &cp)) tok_hot[i] = TokHot{ml, cp};
     }
   }
 }

@@ -103,6 +103,9 @@ struct HostHotwords {
   std::vector<TokHot> tok_hot;
   // unigrams: already stripped/split hot-word unigrams
   void build(const std::vector<std::string>& unigrams, const HostAlphabet& alpha);
+  // the table alone (tok_hot is left empty): a set of a call with per-utterance hot words, whose per-label view the
+  // device fills in
+  void build_table(const std::vector<std::string>& unigrams);
 };
 
 }  // namespace ctc

@@ -126,6 +126,34 @@ def _frames_of(logits_list) -> List[int]:
     return [int(x.shape[0]) for x in logits_list]
 
 
+def _hot_kwargs(kwargs, n: int) -> dict:
+    """kwargs of a batch call made fit to be split: a hot-word iterable that is not a list (a generator: it cannot be pickled,
+    and only one shard could consume it) becomes a list; per-utterance forms are checked against the batch size."""
+    from pyctcdecode_amd.decoder import _per_utt_hot
+
+    kw = dict(kwargs)
+    hw = kw.get("hotwords")
+    if hw is not None and not isinstance(hw, (list, tuple, str)):
+        kw["hotwords"] = list(hw)
+    w = kw.get("hotword_weight")
+    if w is not None and not isinstance(w, (int, float, np.number)) and hasattr(w, "__len__"):
+        kw["hotword_weight"] = [float(x) for x in w]
+    _per_utt_hot(kw.get("hotwords"), kw.get("hotword_weight", 0.0), n)  # (the refusals, before any shard is sent)
+    return kw
+
+
+def _slice_kwargs(kw: dict, lo: int, hi: int) -> dict:
+    """kwargs of the shard [lo, hi): per-utterance hotwords / hotword_weight go with their utterances (kw: _hot_kwargs)."""
+    from pyctcdecode_amd.decoder import _is_per_utt_hotwords
+
+    out = dict(kw)
+    if _is_per_utt_hotwords(kw.get("hotwords")):
+        out["hotwords"] = list(kw["hotwords"][lo:hi])
+    if isinstance(kw.get("hotword_weight"), list):
+        out["hotword_weight"] = kw["hotword_weight"][lo:hi]
+    return out
+
+
 def decode_batch_sharded(decoder, logits_list, group=None, **kwargs) -> List[str]:
     """Each rank decodes its contiguous slice of `logits_list` (balanced by frames) on its own GPU; all ranks return
     the texts of the whole batch in input order. One collective."""
@@ -137,7 +165,7 @@ def decode_batch_sharded(decoder, logits_list, group=None, **kwargs) -> List[str
     frames = _frames_of(logits_list)
     spans = [shard_bounds_by_frames(frames, world, r) for r in range(world)]
     lo, hi = spans[rank]
-    local = decoder.decode_batch(None, logits_list[lo:hi], **kwargs)
+    local = decoder.decode_batch(None, logits_list[lo:hi], **_slice_kwargs(_hot_kwargs(kwargs, len(frames)), lo, hi))
     cap = max(text_capacity(b - a, 0) + sum(frames[a:b]) // 2 for a, b in spans)  # the same on every rank
     return gather_texts(local, group=group, capacity=cap)
 
@@ -150,8 +178,9 @@ def decode_beams_batch_sharded(decoder, logits_list, group=None, **kwargs) -> Li
     if not dist.is_available() or not dist.is_initialized():
         return decoder.decode_beams_batch(None, logits_list, **kwargs)
     world, rank = dist.get_world_size(group), dist.get_rank(group)
-    lo, hi = shard_bounds_by_frames(_frames_of(logits_list), world, rank)
-    local = decoder.decode_beams_batch(None, logits_list[lo:hi], **kwargs)
+    frames = _frames_of(logits_list)
+    lo, hi = shard_bounds_by_frames(frames, world, rank)
+    local = decoder.decode_beams_batch(None, logits_list[lo:hi], **_slice_kwargs(_hot_kwargs(kwargs, len(frames)), lo, hi))
     return gather_objects(local, group=group)
 
 
@@ -240,11 +269,12 @@ class DevicePool:
     def _map(self, method: str, logits_list, kwargs):
         logits_list = [np.asarray(x.detach().cpu().numpy() if hasattr(x, "detach") else x) for x in logits_list]
         n, world = len(logits_list), len(self._workers)
+        kwargs = _hot_kwargs(kwargs, n)
         spans = [shard_bounds_by_frames(_frames_of(logits_list), world, r) for r in range(world)]
         busy = []
         for (lo, hi), (_p, conn) in zip(spans, self._workers):
             if hi > lo:
-                conn.send((method, logits_list[lo:hi], kwargs))
+                conn.send((method, logits_list[lo:hi], _slice_kwargs(kwargs, lo, hi)))
                 busy.append(conn)
         out: List[Any] = []
         err = None
