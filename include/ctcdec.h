@@ -62,7 +62,8 @@ typedef struct ctcdec_params {
   int32_t texts_only;        /* 0/1 (ctcdec_decode_batch with n_best = 1): only the best beam's TEXT is wanted
                                 (decode_batch, decoder.py:895-945) -- it is assembled on the device and the result holds
                                 one beam per utterance with its text and scores, no word frames and no LM state */
-  int32_t reserved;
+  int32_t token_frames;      /* 0/1: also keep every returned beam's tokens with their frames for
+                                ctcdec_result_token_frames (takes precedence over texts_only); was a reserved 0 */
 } ctcdec_params;
 
 /* LM start state for one utterance (decode_beams(lm_start_state=...), decoder.py:621-625):
@@ -290,6 +291,18 @@ int ctcdec_result_texts_joined(ctcdec_result* r, char sep, const char** blob_out
  * Pointers stay valid until ctcdec_result_free. */
 int ctcdec_result_text_blocks(ctcdec_result* r, const char** pool_out, const int64_t** off_out, const int64_t** len_out,
                               int64_t* n_out);
+
+/* Per-token frames of every beam of a result decoded with params.token_frames = 1, in the order of ctcdec_result_pack:
+ * beam k's tokens are [tok_off[k], tok_off[k+1]) (tok_off has n_beams + 1 entries) in label / start / end. A token is a
+ * non-blank emission on the beam's path that is not a space label of a character alphabet: label is its alphabet index,
+ * start the absolute frame at which the beam took it after a blank or another label, end 1 + the last frame of the run
+ * of that label which follows it. This is the reference's partial_frames bookkeeping (decoder.py:449-534) applied to one
+ * token instead of one word: each word of ctcdec_result_frames is a run of consecutive tokens, from its first token's
+ * start to its last token's end. Streaming results (ctcdec_decode_stream_batch, ctcdec_stream_*) list only the tokens
+ * decoded on the device since the caller's beam was imported. Pointers stay valid until ctcdec_result_free; a result
+ * decoded without params.token_frames returns CTCDEC_ERR_ARG. */
+int ctcdec_result_token_frames(ctcdec_result* r, const int64_t** tok_off, const int32_t** label, const int32_t** start,
+                               const int32_t** end, int64_t* n_tokens);
 
 /* timing of the last call's device stages in milliseconds (HIP events on the decode stream):
  * [0] frame-prune kernel, [1] beam kernel, [2] total device time incl. result copy */

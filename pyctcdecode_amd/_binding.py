@@ -34,7 +34,7 @@ class Params(C.Structure):
         ("lm_score_boundary", C.c_int32),
         ("first_frame", C.c_int32),
         ("texts_only", C.c_int32),
-        ("reserved", C.c_int32),
+        ("token_frames", C.c_int32),
     ]
 
 
@@ -139,6 +139,9 @@ _PROTOS = {
     "ctcdec_result_texts_joined": (C.c_int, [_VP, C.c_char, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "ctcdec_result_text_blocks": (C.c_int, [_VP, C.POINTER(C.c_void_p), C.POINTER(C.POINTER(C.c_int64)),
                                            C.POINTER(C.POINTER(C.c_int64)), C.POINTER(C.c_int64)]),
+    "ctcdec_result_token_frames": (C.c_int, [_VP, C.POINTER(C.POINTER(C.c_int64)), C.POINTER(C.POINTER(C.c_int32)),
+                                            C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_int32)),
+                                            C.POINTER(C.c_int64)]),
     "ctcdec_result_timing": (C.c_int, [_VP, C.POINTER(C.c_double)]),
     "ctcdec_result_beam_kernel": (C.c_int, [_VP]),
     "ctcdec_device": (C.c_int, []),

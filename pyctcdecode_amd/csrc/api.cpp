@@ -95,6 +95,8 @@ struct BeamResult {
   std::string partial;
   int32_t src = -1, last_char = -1, pstart = -1, pend = -1;
   double raw_lm = 0;
+  // params.token_frames: (label, start, end) of every token of the beam, root to leaf (replay())
+  std::vector<int32_t> tok;
 };
 
 // what a streaming call adds to a plain batch decode
@@ -363,6 +365,10 @@ struct ctcdec_result {
   std::vector<int64_t> partial_off;
   std::vector<int32_t> src_beam, last_char, pstart, pend;
   std::vector<double> raw_lm;
+  // token frames (params.token_frames; packed by ctcdec_result_token_frames in the order of ctcdec_result_pack)
+  bool has_tokens = false, tok_packed = false;
+  std::vector<int64_t> tk_off;
+  std::vector<int32_t> tk_label, tk_start, tk_end;
 };
 
 // A batch of device-resident streams (ctcdec_stream_*): what survives between chunks lives in device memory owned by
@@ -741,8 +747,20 @@ int ctcdec_set_hotword_sets(ctcdec_decoder* dec, const char* blob, const int64_t
 // Rebuild text + word frames of one beam from its emission list (root -> leaf). The text is written
 // in place: `open` is where the currently open (partial) word starts. A streaming beam starts from the
 // caller's beam named by its BR_IMPORT root (text so far + open partial word).
+// want_tok: the same pass also lists the beam's tokens with their frames ("Token frames"). An APPEND node
+// holds 1 + its own start frame; a BOUNDARY token's start is the start of the word it opens, which the next word-closing
+// node carries (or, for the last word, open_s: the beam's open-word frames the kernel leaves in OutBeam::pad). Every
+// node holds the end of the token before it in wend (partial_frames[1], decoder.py:449-534); the last token's end is
+// open_e. Space labels of a character alphabet (BR_SPACE) are separators and are not listed.
 static void replay(const ctcdec_decoder* d, const EmitNode* toks, uint32_t n, const StreamIn* st, int64_t imp0,
-                   BeamResult* r) {
+                   BeamResult* r, bool want_tok = false, int32_t open_s = -1, int32_t open_e = -1) {
+  constexpr size_t NONE = ~(size_t)0;
+  std::vector<int32_t>& tk = r->tok;
+  size_t last = NONE, opener = NONE;  // the token whose end / BOUNDARY token whose start the next node gives
+  if (want_tok) {
+    tk.clear();
+    tk.reserve((size_t)n * 3);
+  }
   std::string& text = r->text;
   text.clear();
   text.reserve((size_t)n * 3 + 8);
@@ -757,6 +775,25 @@ static void replay(const ctcdec_decoder* d, const EmitNode* toks, uint32_t n, co
   };
   for (uint32_t k = 0; k < n; ++k) {
     const uint32_t br = toks[k].tok_branch >> 16, tok = toks[k].tok_branch & 0xFFFFu;
+    if (want_tok) {
+      if (br == BR_IMPORT) {  // (streaming: the tokens before the caller's beam are not on this chain)
+        last = opener = NONE;
+      } else {
+        if (last != NONE) tk[last * 3 + 2] = toks[k].wend;
+        last = NONE;
+        if (br != BR_APPEND && opener != NONE) {
+          tk[opener * 3 + 1] = toks[k].wstart;
+          opener = NONE;
+        }
+        if (br == BR_BOUNDARY || br == BR_APPEND) {
+          last = tk.size() / 3;
+          if (br == BR_BOUNDARY) opener = last;
+          tk.push_back((int32_t)tok);
+          tk.push_back(br == BR_APPEND ? toks[k].wstart - 1 : -1);
+          tk.push_back(-1);
+        }
+      }
+    }
     if (br == BR_BOUNDARY) {
       close_word(toks[k].wstart, toks[k].wend, true);
       text += d->alpha.clean[tok];
@@ -776,6 +813,10 @@ static void replay(const ctcdec_decoder* d, const EmitNode* toks, uint32_t n, co
       open = text.size();
       text.append(st->text_blob + in.partial_begin, (size_t)(in.partial_end - in.partial_begin));
     }
+  }
+  if (want_tok) {
+    if (last != NONE) tk[last * 3 + 2] = open_e;
+    if (opener != NONE) tk[opener * 3 + 1] = open_s;
   }
   // split off the still open word (streaming without force_next_word / is_end)
   r->partial.assign(text, open, std::string::npos);
@@ -1168,7 +1209,7 @@ static int decode_impl(ctcdec_decoder* dec, const void* const* utt_logits, const
   dp.no_label_runs = getenv("CTCDEC_NO_LABEL_RUNS") != nullptr ? 1 : 0;
   // decode_batch: the kernels assemble the best beam's text themselves (CTCDEC_HOST_REPLAY=1: the emission lists come
   // back and the host replays them, as for every other call)
-  const bool device_texts = p->texts_only != 0 && n_best == 1 && !stream && getenv("CTCDEC_HOST_REPLAY") == nullptr;
+  const bool device_texts = p->texts_only != 0 && p->token_frames == 0 && n_best == 1 && !stream && getenv("CTCDEC_HOST_REPLAY") == nullptr;
   dp.texts_only = device_texts ? 1 : 0;
   ba.n_utts = n_utts;
   ba.utt_row0 = (const int64_t*)dec->w_row0.p;
@@ -1492,6 +1533,8 @@ static int decode_impl(ctcdec_decoder* dec, const void* const* utt_logits, const
       const OutBeam& ob = obs[(size_t)u * n_best + k];
       if ((unsigned long long)ob.tok_off + ob.tok_cnt > head) return fail(CTCDEC_ERR_INTERNAL, "token pool range");
     }
+  const bool want_tok = p->token_frames != 0;
+  res->has_tokens = want_tok;
   auto replay_range = [&](int32_t u0, int32_t u1) {
     for (int32_t u = u0; u < u1; ++u) {
       auto& beams = res->utts[(size_t)u];
@@ -1500,7 +1543,8 @@ static int decode_impl(ctcdec_decoder* dec, const void* const* utt_logits, const
         const OutBeam& ob = obs[(size_t)u * n_best + k];
         BeamResult& r = beams[k];
         fill_result(ob, xst ? &xst[((size_t)u * n_best + k) * (size_t)(K - 1)] : nullptr, K, &r);
-        replay(dec, toks + ob.tok_off, ob.tok_cnt, stream, stream ? stream->beam_off[u] : 0, &r);
+        replay(dec, toks + ob.tok_off, ob.tok_cnt, stream, stream ? stream->beam_off[u] : 0, &r, want_tok, (int32_t)ob.pad[0],
+               (int32_t)ob.pad[1]);
       }
     }
   };
@@ -2098,6 +2142,43 @@ int ctcdec_result_pack(ctcdec_result* r, ctcdec_packed* out) {
   out->partial_start = r->pstart.data();
   out->partial_end = r->pend.data();
   out->raw_lm_score = r->raw_lm.data();
+  return CTCDEC_OK;
+}
+
+int ctcdec_result_token_frames(ctcdec_result* r, const int64_t** tok_off_out, const int32_t** label_out, const int32_t** start_out,
+                               const int32_t** end_out, int64_t* n_tokens_out) {
+  if (!r || !tok_off_out || !label_out || !start_out || !end_out || !n_tokens_out) return fail(CTCDEC_ERR_ARG, "no result");
+  if (!r->has_tokens) return fail(CTCDEC_ERR_ARG, "the result was decoded without params.token_frames");
+  if (!r->tok_packed) {
+    size_t nb = 0, nt = 0;
+    for (const auto& beams : r->utts)
+      for (const BeamResult& b : beams) {
+        ++nb;
+        nt += b.tok.size() / 3;
+      }
+    r->tk_off.resize(nb + 1);
+    r->tk_label.resize(nt);
+    r->tk_start.resize(nt);
+    r->tk_end.resize(nt);
+    size_t j = 0, o = 0;
+    r->tk_off[0] = 0;
+    for (const auto& beams : r->utts)
+      for (const BeamResult& b : beams) {
+        const int32_t* t = b.tok.data();
+        for (size_t k = 0, n = b.tok.size() / 3; k < n; ++k, ++o, t += 3) {
+          r->tk_label[o] = t[0];
+          r->tk_start[o] = t[1];
+          r->tk_end[o] = t[2];
+        }
+        r->tk_off[++j] = (int64_t)o;
+      }
+    r->tok_packed = true;
+  }
+  *tok_off_out = r->tk_off.data();
+  *label_out = r->tk_label.data();
+  *start_out = r->tk_start.data();
+  *end_out = r->tk_end.data();
+  *n_tokens_out = (int64_t)r->tk_label.size();
   return CTCDEC_OK;
 }
 

@@ -1500,7 +1500,9 @@ CTC_UNROLL
       EmitNode en;
       en.parent = enode;
       en.tok_branch = c | (br << 16);
-      en.wstart = wst;
+      // a word-closing node carries the frames of the word it closes, an APPEND node 1 + its own frame (its new pen: the
+      // token frames of a chain); wen is the end of the token before it in either case
+      en.wstart = br == BR_APPEND ? pen : wst;
       en.wend = wen;
       io.emit_nodes[e] = en;
       enode = e;
@@ -2081,6 +2083,8 @@ CTC_UNROLL
         }
       }
       if (tok_ok) {
+        ob.pad[0] = (uint32_t)b.pstart[d];  // the open word's frames even when folded: the last token's
+        ob.pad[1] = (uint32_t)b.pend[d];
         uint32_t pos = off + len;
         if (closes) {
           EmitNode fin;

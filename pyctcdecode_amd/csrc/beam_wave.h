@@ -1476,7 +1476,10 @@ CTC_UNROLL
         status |= ST_EMIT_OVERFLOW;
         e = io.emit_cap - 1;
       }
-      *(u32x4a*)&io.emit_nodes[e] = mk4(enode, c | (b << 16), (uint32_t)wst, (uint32_t)wen);
+      // a word-closing node carries the frames of the word it closes, an APPEND node 1 + its own frame (its new pen: the
+      // token frames of a chain); wen is the end of the token before it in either case. (pen rather than
+      // frame: the SGPR spills of the bench kernel stay where they were)
+      *(u32x4a*)&io.emit_nodes[e] = mk4(enode, c | (b << 16), (uint32_t)(b == BR_APPEND ? pen : wst), (uint32_t)wen);
       enode = e;
       depth += 1;
     }
@@ -1854,8 +1857,8 @@ CTC_UNROLL
       const uint32_t o = (uint32_t)(base + off[j]);
       ob.tok_off = o;
       ob.tok_cnt = tok_ok ? len[j] : 0;
-      ob.pad[0] = 0;
-      ob.pad[1] = 0;
+      ob.pad[0] = (uint32_t)cr.pstart;  // the open word's frames even when folded: the last token's
+      ob.pad[1] = (uint32_t)cr.pend;
       ob.last_char = fold ? NO_CHAR : (meta1 & 0xFFFFu);
       ob.pstart = fold ? -1 : cr.pstart;
       ob.pend = fold ? -1 : cr.pend;

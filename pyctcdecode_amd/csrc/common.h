@@ -237,7 +237,8 @@ enum : uint32_t { BR_BOUNDARY = 1u, BR_SPACE = 2u, BR_APPEND = 3u, BR_FINAL = 4u
 struct EmitNode {  // 16 B
   uint32_t parent;
   uint32_t tok_branch;  // token | branch << 16
-  int32_t wstart, wend; // frames of the word closed by this emission (BOUNDARY/SPACE/FINAL)
+  int32_t wstart, wend; // frames of the word closed by this emission (BOUNDARY/SPACE/FINAL); APPEND: 1 + the frame of
+                        // the emission, and the end of the token before it ("Token frames")
 };
 
 // per-beam result record written by the beam kernel

@@ -99,6 +99,51 @@ class OutputBeam:
         return dataclasses.replace(self, last_lm_state=state.get_mp_safe_state() if state is not None else None)
 
 
+@dataclasses.dataclass(frozen=True)
+class TokenOutputBeam(OutputBeam):
+    """An OutputBeam with the frames of its tokens (decode_beams(..., token_frames=True)): every non-blank emission on the
+    beam's path except the space label of a character alphabet, in order, as (label, (start, end)). ``label`` is the
+    alphabet label, ``start`` the frame at which the beam took it after a blank or another label, ``end`` 1 + the last
+    frame of the run of that label which follows. Each word of ``text_frames`` spans a run of consecutive tokens."""
+
+    token_frames: List[Tuple[str, Frames]]
+
+
+class TokenFrames:
+    """The token frames of a decode_batch(..., token_frames=True) call as arrays: utterance i's tokens are
+    ``[offsets[i], offsets[i + 1])`` of ``label`` (alphabet index), ``start`` and ``end`` (int32); ``offsets`` is int64
+    ``[B + 1]``. ``of(i)`` lists them as TokenOutputBeam.token_frames does."""
+
+    __slots__ = ("label", "start", "end", "offsets", "labels")
+
+    def __init__(self, label: np.ndarray, start: np.ndarray, end: np.ndarray, offsets: np.ndarray, labels: Sequence[str]):
+        self.label, self.start, self.end, self.offsets = label, start, end, offsets
+        self.labels = list(labels)
+
+    def __len__(self) -> int:
+        return len(self.offsets) - 1
+
+    def of(self, i: int) -> List[Tuple[str, Frames]]:
+        lo, hi = int(self.offsets[i]), int(self.offsets[i + 1])
+        labels = self.labels
+        return [(labels[c], (s, e)) for c, s, e in zip(self.label[lo:hi].tolist(), self.start[lo:hi].tolist(),
+                                                        self.end[lo:hi].tolist())]
+
+    @classmethod
+    def join(cls, parts: Sequence["TokenFrames"], labels: Sequence[str]) -> "TokenFrames":
+        """The parts of consecutive slices of a batch as one (offsets rebased)."""
+        offs = [np.zeros(1, dtype=np.int64)]
+        base = 0
+        for t in parts:
+            offs.append(t.offsets[1:] + base)
+            base += int(t.offsets[-1])
+        cat = lambda name: np.concatenate([getattr(t, name) for t in parts]) if parts else np.zeros(0, np.int32)  # noqa: E731
+        return cls(cat("label"), cat("start"), cat("end"), np.concatenate(offs), labels)
+
+    def __reduce__(self):
+        return TokenFrames, (self.label, self.start, self.end, self.offsets, self.labels)
+
+
 NULL_FRAMES: Frames = (-1, -1)
 EMPTY_START_BEAM = Beam("", "", "", None, [], NULL_FRAMES, 0.0)
 
@@ -984,7 +1029,7 @@ class BeamSearchDecoderCTC:
         p.lm_score_boundary = int(bool(lm.score_boundary)) if lm is not None else 0
         p.first_frame = 0
         p.texts_only = 0
-        p.reserved = 0
+        p.token_frames = 0
         return p
 
     def _run(self, logits_list: Sequence[Any], params: B.Params, hotwords, start_states=None, hot_sets=None):
@@ -1109,12 +1154,16 @@ class BeamSearchDecoderCTC:
         hotwords: Optional[Iterable[str]] = None,
         hotword_weight: float = DEFAULT_HOTWORD_WEIGHT,
         lm_start_state: Optional[AbstractLMState] = None,
+        token_frames: bool = False,
     ) -> List[OutputBeam]:
+        """token_frames=True: TokenOutputBeams, which also carry the frames of every token of the beam."""
         self._check_logits_dimension(logits)
         params = self._params(beam_width, beam_prune_logp, token_min_logp, prune_history, hotword_weight, 0)
+        params.token_frames = int(bool(token_frames))
         res = self._run([logits], params, hotwords, [lm_start_state])
         try:
-            return self._unpack(res, True)[0]
+            beams = self._unpack(res, True)
+            return (self._with_tokens(res, beams) if token_frames else beams)[0]
         finally:
             self._lib.dll.ctcdec_result_free(res)
 
@@ -1146,45 +1195,86 @@ class BeamSearchDecoderCTC:
         token_min_logp: float = DEFAULT_MIN_TOKEN_LOGP,
         hotwords: Optional[Iterable[str]] = None,
         hotword_weight: float = DEFAULT_HOTWORD_WEIGHT,
-    ) -> List[str]:
+        token_frames: bool = False,
+    ) -> Any:
         """decoder.py:895-945. One device launch decodes the whole batch: a multiprocessing pool is ignored. A
-        `pyctcdecode_amd.parallel.DevicePool` -- one worker process per GPU -- shards the batch over its devices."""
+        `pyctcdecode_amd.parallel.DevicePool` -- one worker process per GPU -- shards the batch over its devices.
+        token_frames=True: returns (texts, TokenFrames), the frames of every token of each text as arrays."""
         if getattr(logits_list, "ndim", 0) != 3:
             logits_list = list(logits_list)
         if len(logits_list) == 0:
-            return []
+            return ([], self._empty_token_frames()) if token_frames else []
         if type(pool).__name__ == "DevicePool":
+            kw = dict(token_frames=True) if token_frames else {}
             return pool.decode_batch(logits_list, beam_width=beam_width, beam_prune_logp=beam_prune_logp,
-                                     token_min_logp=token_min_logp, hotwords=hotwords, hotword_weight=hotword_weight)
+                                     token_min_logp=token_min_logp, hotwords=hotwords, hotword_weight=hotword_weight, **kw)
         hotwords, hotword_weight, hot_sets = self._resolve_hot(hotwords, hotword_weight, len(logits_list))
         params = self._params(beam_width, beam_prune_logp, token_min_logp, True, hotword_weight, 1)
-        params.texts_only = 1  # (the kernels write the texts themselves: no emission lists to copy back and replay)
+        if token_frames:  # (the best beam's emission list comes back: one host pass gives its text and its tokens)
+            params.token_frames = 1
+        else:
+            params.texts_only = 1  # (the kernels write the texts themselves: no emission lists to copy back and replay)
         res = self._run(logits_list, params, hotwords, hot_sets=hot_sets)
         try:
-            texts = B.texts_of(self._lib, res)  # (one str per block of the library's memory, built in C)
-            if texts is not None:
-                return texts
-            if self._texts_sep is not None:  # one split instead of one slice per utterance (0.7 -> 0.15 ms at 4096)
-                blob_p, nbytes, n = C.c_void_p(), C.c_int64(), C.c_int64()
-                self._lib.check(self._lib.dll.ctcdec_result_texts_joined(res, self._texts_sep, C.byref(blob_p), C.byref(nbytes),
-                                                                         C.byref(n)))
-                if n.value == 0:
-                    return []
-                parts = B.split_texts(blob_p, int(nbytes.value), int(n.value), self._texts_sep)
-                if len(parts) == n.value:
-                    return parts
-            blob_p, off_p, n = C.c_void_p(), C.POINTER(C.c_int64)(), C.c_int64()
-            self._lib.check(self._lib.dll.ctcdec_result_texts(res, C.byref(blob_p), C.byref(off_p), C.byref(n)))
-            nb = int(n.value)
-            text_off = np.ctypeslib.as_array(off_p, shape=(nb + 1,))
-            blob = C.string_at(blob_p, int(text_off[nb])) if text_off[nb] else b""
-            off = text_off.tolist()
-            if blob.isascii():  # byte offsets == character offsets: decode once, slice the str
-                text = blob.decode("ascii")
-                return [text[off[k] : off[k + 1]] for k in range(nb)]
-            return [blob[off[k] : off[k + 1]].decode("utf-8") for k in range(nb)]
+            texts = self._texts(res)
+            return (texts, self._token_frames(res, len(texts))) if token_frames else texts
         finally:
             self._lib.dll.ctcdec_result_free(res)
+
+    def _empty_token_frames(self) -> TokenFrames:
+        z = np.zeros(0, dtype=np.int32)
+        return TokenFrames(z, z.copy(), z.copy(), np.zeros(1, dtype=np.int64), self._alphabet.labels)
+
+    def _token_frames(self, res, n_beams: int) -> TokenFrames:
+        """The token frames of all beams of a result (ctcdec_result_token_frames), copied into numpy arrays."""
+        off_p, lab_p, st_p, en_p = (C.POINTER(C.c_int64)(), C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)(),
+                                    C.POINTER(C.c_int32)())
+        n = C.c_int64()
+        self._lib.check(self._lib.dll.ctcdec_result_token_frames(res, C.byref(off_p), C.byref(lab_p), C.byref(st_p),
+                                                                 C.byref(en_p), C.byref(n)))
+        nt = int(n.value)
+        offsets = np.ctypeslib.as_array(off_p, shape=(n_beams + 1,)).copy()
+        if nt:
+            arrs = [np.ctypeslib.as_array(q, shape=(nt,)).copy() for q in (lab_p, st_p, en_p)]
+        else:
+            arrs = [np.zeros(0, dtype=np.int32) for _ in range(3)]
+        return TokenFrames(arrs[0], arrs[1], arrs[2], offsets, self._alphabet.labels)
+
+    def _with_tokens(self, res, beams: List[List[OutputBeam]]) -> List[List[TokenOutputBeam]]:
+        tf = self._token_frames(res, sum(len(bs) for bs in beams))
+        out, k = [], 0
+        for bs in beams:
+            row = []
+            for b in bs:
+                row.append(TokenOutputBeam(b.text, b.last_lm_state, b.text_frames, b.logit_score, b.lm_score, tf.of(k)))
+                k += 1
+            out.append(row)
+        return out
+
+    def _texts(self, res) -> List[str]:
+        """The texts of all beams of a result (utterance-major)."""
+        texts = B.texts_of(self._lib, res)  # (one str per block of the library's memory, built in C)
+        if texts is not None:
+            return texts
+        if self._texts_sep is not None:  # one split instead of one slice per utterance (0.7 -> 0.15 ms at 4096)
+            blob_p, nbytes, n = C.c_void_p(), C.c_int64(), C.c_int64()
+            self._lib.check(self._lib.dll.ctcdec_result_texts_joined(res, self._texts_sep, C.byref(blob_p), C.byref(nbytes),
+                                                                     C.byref(n)))
+            if n.value == 0:
+                return []
+            parts = B.split_texts(blob_p, int(nbytes.value), int(n.value), self._texts_sep)
+            if len(parts) == n.value:
+                return parts
+        blob_p, off_p, n = C.c_void_p(), C.POINTER(C.c_int64)(), C.c_int64()
+        self._lib.check(self._lib.dll.ctcdec_result_texts(res, C.byref(blob_p), C.byref(off_p), C.byref(n)))
+        nb = int(n.value)
+        text_off = np.ctypeslib.as_array(off_p, shape=(nb + 1,))
+        blob = C.string_at(blob_p, int(text_off[nb])) if text_off[nb] else b""
+        off = text_off.tolist()
+        if blob.isascii():  # byte offsets == character offsets: decode once, slice the str
+            text = blob.decode("ascii")
+            return [text[off[k] : off[k + 1]] for k in range(nb)]
+        return [blob[off[k] : off[k + 1]].decode("utf-8") for k in range(nb)]
 
     def decode_beams_batch(
         self,
@@ -1196,22 +1286,27 @@ class BeamSearchDecoderCTC:
         prune_history: bool = DEFAULT_PRUNE_BEAMS,
         hotwords: Optional[Iterable[str]] = None,
         hotword_weight: float = DEFAULT_HOTWORD_WEIGHT,
+        token_frames: bool = False,
     ) -> List[List[OutputBeam]]:
-        """decoder.py:801-857. Beams carry ``last_lm_state=None`` like the reference's mp-safe beams. ``pool``: see decode_batch."""
+        """decoder.py:801-857. Beams carry ``last_lm_state=None`` like the reference's mp-safe beams. ``pool``: see decode_batch.
+        token_frames=True: TokenOutputBeams, which also carry the frames of every token of the beam."""
         logits_list = list(logits_list)
         for logits in logits_list:
             self._check_logits_dimension(logits)
         if len(logits_list) == 0:
             return []
         if type(pool).__name__ == "DevicePool":
+            kw = dict(token_frames=True) if token_frames else {}
             return pool.decode_beams_batch(logits_list, beam_width=beam_width, beam_prune_logp=beam_prune_logp,
                                            token_min_logp=token_min_logp, prune_history=prune_history, hotwords=hotwords,
-                                           hotword_weight=hotword_weight)
+                                           hotword_weight=hotword_weight, **kw)
         hotwords, hotword_weight, hot_sets = self._resolve_hot(hotwords, hotword_weight, len(logits_list))
         params = self._params(beam_width, beam_prune_logp, token_min_logp, prune_history, hotword_weight, 0)
+        params.token_frames = int(bool(token_frames))
         res = self._run(logits_list, params, hotwords, hot_sets=hot_sets)
         try:
-            return self._unpack(res, False)
+            beams = self._unpack(res, False)
+            return self._with_tokens(res, beams) if token_frames else beams
         finally:
             self._lib.dll.ctcdec_result_free(res)
 

@@ -159,6 +159,8 @@ def decode_batch_sharded(decoder, logits_list, group=None, **kwargs) -> List[str
     the texts of the whole batch in input order. One collective."""
     import torch.distributed as dist
 
+    if kwargs.get("token_frames"):
+        raise NotImplementedError("token_frames=True is not gathered over ranks: decode_batch each rank's slice itself")
     if not dist.is_available() or not dist.is_initialized():
         return decoder.decode_batch(None, logits_list, **kwargs)
     world, rank = dist.get_world_size(group), dist.get_rank(group)
@@ -175,6 +177,8 @@ def decode_beams_batch_sharded(decoder, logits_list, group=None, **kwargs) -> Li
     input order (beams carry last_lm_state=None, as in the reference's pool path)."""
     import torch.distributed as dist
 
+    if kwargs.get("token_frames"):
+        raise NotImplementedError("token_frames=True is not gathered over ranks: decode_beams_batch each rank's slice itself")
     if not dist.is_available() or not dist.is_initialized():
         return decoder.decode_beams_batch(None, logits_list, **kwargs)
     world, rank = dist.get_world_size(group), dist.get_rank(group)
@@ -214,6 +218,10 @@ def _device_worker(conn, device: int, decoder_dir: str, library: Optional[str]) 
         try:
             if method == "decode_batch":
                 conn.send(("ok", dec.decode_batch(None, logits, **kwargs)))
+            elif kwargs.get("token_frames"):
+                beams = dec.decode_beams_batch(None, logits, **kwargs)
+                conn.send(("ok", [[(b.text, list(b.text_frames), b.logit_score, b.lm_score, b.token_frames) for b in bs]
+                                  for bs in beams]))
             else:
                 beams = dec.decode_beams_batch(None, logits, **kwargs)
                 conn.send(("ok", [[(b.text, list(b.text_frames), b.logit_score, b.lm_score) for b in bs] for bs in beams]))
@@ -267,6 +275,14 @@ class DevicePool:
                 raise RuntimeError("a DevicePool worker failed to start:\n%s" % what)
 
     def _map(self, method: str, logits_list, kwargs):
+        out: List[Any] = []
+        for part in self._parts(method, logits_list, kwargs):
+            out.extend(part)
+        assert len(out) == len(logits_list)
+        return out
+
+    def _parts(self, method: str, logits_list, kwargs) -> List[Any]:
+        """What each busy worker returned for its slice, in slice order."""
         logits_list = [np.asarray(x.detach().cpu().numpy() if hasattr(x, "detach") else x) for x in logits_list]
         n, world = len(logits_list), len(self._workers)
         kwargs = _hot_kwargs(kwargs, n)
@@ -276,25 +292,35 @@ class DevicePool:
             if hi > lo:
                 conn.send((method, logits_list[lo:hi], _slice_kwargs(kwargs, lo, hi)))
                 busy.append(conn)
-        out: List[Any] = []
+        parts: List[Any] = []
         err = None
         for conn in busy:  # (every answer is collected before anything is raised: the workers stay in step)
             kind, what = conn.recv()
             if kind == "ok":
-                out.extend(what)
+                parts.append(what)
             elif err is None:
                 err = what
         if err is not None:
             raise err
-        assert len(out) == n
-        return out
+        return parts
 
     def decode_batch(self, logits_list, **kwargs) -> List[str]:
+        if kwargs.get("token_frames"):  # (texts, TokenFrames) per slice -> one of each, offsets rebased
+            from pyctcdecode_amd.decoder import TokenFrames
+
+            parts = self._parts("decode_batch", logits_list, kwargs)
+            texts = [t for p in parts for t in p[0]]
+            assert len(texts) == len(logits_list)
+            labels = parts[0][1].labels if parts else []
+            return texts, TokenFrames.join([p[1] for p in parts], labels)
         return self._map("decode_batch", logits_list, kwargs)
 
     def decode_beams_batch(self, logits_list, **kwargs):
-        from pyctcdecode_amd.decoder import OutputBeam
+        from pyctcdecode_amd.decoder import OutputBeam, TokenOutputBeam
 
+        if kwargs.get("token_frames"):
+            return [[TokenOutputBeam(t, None, f, lg, lm, tf) for t, f, lg, lm, tf in beams]
+                    for beams in self._map("decode_beams_batch", logits_list, kwargs)]
         return [[OutputBeam(t, None, f, lg, lm) for t, f, lg, lm in beams] for beams in self._map("decode_beams_batch", logits_list, kwargs)]
 
     def close(self) -> None:
