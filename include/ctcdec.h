@@ -63,8 +63,13 @@ typedef struct ctcdec_params {
                                 (decode_batch, decoder.py:895-945) -- it is assembled on the device and the result holds
                                 one beam per utterance with its text and scores, no word frames and no LM state */
   int32_t token_frames;      /* 0/1: also keep every returned beam's tokens with their frames for
-                                ctcdec_result_token_frames (takes precedence over texts_only); was a reserved 0 */
+                                ctcdec_result_token_frames (takes precedence over texts_only); was a reserved 0.
+                                CTCDEC_TOKEN_LOGP_MEAN / _MIN / _MAX: the same, plus each token's confidence for
+                                ctcdec_result_token_logp (ctcdec_decode_batch only) */
 } ctcdec_params;
+
+/* ctcdec_params.token_frames beyond 0/1: the fold of a token's per-frame log-probabilities (ctcdec_result_token_logp) */
+enum ctcdec_token_logp { CTCDEC_TOKEN_LOGP_MEAN = 2, CTCDEC_TOKEN_LOGP_MIN = 3, CTCDEC_TOKEN_LOGP_MAX = 4 };
 
 /* LM start state for one utterance (decode_beams(lm_start_state=...), decoder.py:621-625):
  * context words newest first, as vocabulary indices of THIS decoder's LM, with the back-off
@@ -303,6 +308,16 @@ int ctcdec_result_text_blocks(ctcdec_result* r, const char** pool_out, const int
  * decoded without params.token_frames returns CTCDEC_ERR_ARG. */
 int ctcdec_result_token_frames(ctcdec_result* r, const int64_t** tok_off, const int32_t** label, const int32_t** start,
                                const int32_t** end, int64_t* n_tokens);
+
+/* Per-token confidences of a result decoded with params.token_frames = CTCDEC_TOKEN_LOGP_MEAN / _MIN / _MAX, in the order
+ * of ctcdec_result_token_frames (n_tokens is the same): logp[i] folds, over the frames [start, end) of token i, the natural-log
+ * probability of the token's label at that frame -- the clipped log-softmax (or log(clip(p))) the token prune looked at
+ * (decoder.py:180-197, 444-445, 762-765) -- as the arithmetic mean (summed in frame order; the log of the geometric mean), the
+ * minimum or the maximum. The values are computed on the device inside the decode call, from the survivor lists of its
+ * frame-prune stage: a token's label survived the prune at every frame of its run. Pointers stay valid until
+ * ctcdec_result_free; a result decoded without a fold returns CTCDEC_ERR_ARG, and streaming calls refuse the fold.
+ * decode_beams(..., confidence="mean") / decode_batch(..., confidence=...) */
+int ctcdec_result_token_logp(ctcdec_result* r, const double** logp, int64_t* n_tokens);
 
 /* timing of the last call's device stages in milliseconds (HIP events on the decode stream):
  * [0] frame-prune kernel, [1] beam kernel, [2] total device time incl. result copy */

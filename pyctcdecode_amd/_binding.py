@@ -142,6 +142,7 @@ _PROTOS = {
     "ctcdec_result_token_frames": (C.c_int, [_VP, C.POINTER(C.POINTER(C.c_int64)), C.POINTER(C.POINTER(C.c_int32)),
                                             C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_int32)),
                                             C.POINTER(C.c_int64)]),
+    "ctcdec_result_token_logp": (C.c_int, [_VP, C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.c_int64)]),
     "ctcdec_result_timing": (C.c_int, [_VP, C.POINTER(C.c_double)]),
     "ctcdec_result_beam_kernel": (C.c_int, [_VP]),
     "ctcdec_device": (C.c_int, []),

@@ -213,11 +213,11 @@ struct ctcdec_decoder {
   // per-call workspace (grow only)
   DevBuf w_logits, w_ptrs, w_row0, w_rowsum, w_isprob, w_scnt, w_sid, w_slp, w_flags, w_text, w_emit, w_toff,
       w_eoff, w_start, w_out, w_nout, w_status, w_tok, w_head, w_prof, w_imp, w_impoff, w_ff, w_cold, w_pay, w_tscr, w_tsoff, w_tpool,
-      d_toktext, d_tokbytes, w_slow, w_order, w_side;
+      d_toktext, d_tokbytes, w_slow, w_order, w_side, w_truns, w_tlogp, w_tmiss;
   bool slicing = false;  // a time-sliced host ingest is under way (decode_host_sliced): the prune stage notes each slice's side of 1
   uint32_t max_label_bytes = 1;
   bool arenas_worst_case = false;  // a call has outgrown the usual reservation of the node arenas: reserve the worst case from now on
-  HostBuf h_tok, h_out, h_small;
+  HostBuf h_tok, h_out, h_small, h_truns;
   int dense_calls = 0;      // calls left that skip the 64-rows-per-wave prune kernel (most rows of a recent call overflowed it)
   HostBuf h_stage;          // page-locked staging of a call's small uploads (upload_staged): they go over without the host waiting
   size_t stage_used = 0;
@@ -227,7 +227,8 @@ struct ctcdec_decoder {
     DevBuf* all[] = {&d_tok,  &d_tok_hot, &d_uni,  &d_pref,  &d_hot,  &w_logits, &w_ptrs, &w_row0,
                      &w_rowsum, &w_isprob, &w_scnt, &w_sid,  &w_slp,   &w_flags, &w_text,   &w_emit, &w_toff,
                      &w_eoff,  &w_start,  &w_out,  &w_nout, &w_status, &w_tok,  &w_head, &w_prof, &w_imp, &w_impoff, &w_ff, &w_cold, &w_pay,
-                     &w_tscr,  &w_tsoff, &w_tpool, &d_toktext, &d_tokbytes, &w_slow, &w_order, &w_side};
+                     &w_tscr,  &w_tsoff, &w_tpool, &d_toktext, &d_tokbytes, &w_slow, &w_order, &w_side,
+                     &w_truns, &w_tlogp, &w_tmiss};
     for (DevBuf* b : all) b->drop();
     for (int k = 0; k < MAX_LMS - 1; ++k) {
       d_xuni[k].drop();
@@ -244,6 +245,7 @@ struct ctcdec_decoder {
     h_tok.drop();
     h_out.drop();
     h_small.drop();
+    h_truns.drop();
     h_stage.drop();
   }
 };
@@ -369,6 +371,9 @@ struct ctcdec_result {
   bool has_tokens = false, tok_packed = false;
   std::vector<int64_t> tk_off;
   std::vector<int32_t> tk_label, tk_start, tk_end;
+  // token confidences (params.token_frames = CTCDEC_TOKEN_LOGP_*), in the same order: filled by the decode call itself
+  bool has_logp = false;
+  std::vector<double> tk_logp;
 };
 
 // A batch of device-resident streams (ctcdec_stream_*): what survives between chunks lives in device memory owned by
@@ -850,6 +855,12 @@ static void fill_result(const OutBeam& ob, const LmState* xs, int K, BeamResult*
   r->raw_lm = ob.raw_lm;
 }
 
+// the fold of a call that asks for token confidences (ctcdec_params.token_frames = CTCDEC_TOKEN_LOGP_*), else 0
+static_assert(LOGP_MEAN == CTCDEC_TOKEN_LOGP_MEAN && LOGP_MIN == CTCDEC_TOKEN_LOGP_MIN && LOGP_MAX == CTCDEC_TOKEN_LOGP_MAX, "token_logp.h");
+static int32_t logp_fold(const ctcdec_params* p) {
+  return p && p->token_frames >= LOGP_MEAN && p->token_frames <= LOGP_MAX ? p->token_frames : 0;
+}
+
 // after_launch: called once the kernels of this call are queued and before the host waits for them (time-sliced host ingest:
 // the next slice's copy runs under this slice's kernels)
 typedef std::function<int(std::string*)> AfterLaunch;
@@ -869,7 +880,8 @@ int ctcdec_decode_batch(ctcdec_decoder* dec, const void* const* utt_logits, cons
   // Large HOST batches (the reference's own calling convention: numpy in) go over in time slices, the copy of slice k + 1
   // under the kernels of slice k (decode_host_sliced); 1 = "decode it in one piece after all" (probability-like rows).
   // (per-utterance hot words: in one piece)
-  if (dec && p && out && !is_device && !dec->hot_call.armed && n_utts > 0 && utt_logits && utt_frames && dtype >= CTCDEC_F32 && dtype <= CTCDEC_BF16) {
+  // (token confidences: in one piece too -- a slice's survivor lists are overwritten by the next slice's)
+  if (dec && p && out && !is_device && !dec->hot_call.armed && !logp_fold(p) && n_utts > 0 && utt_logits && utt_frames && dtype >= CTCDEC_F32 && dtype <= CTCDEC_BF16) {
     const int n_slices = host_slices_wanted(dec, utt_frames, n_utts, dtype);
     if (n_slices >= 2) {
       const int rc = decode_host_sliced(dec, utt_logits, utt_frames, n_utts, dtype, p, start_states, n_slices, out);
@@ -994,6 +1006,8 @@ static int decode_impl(ctcdec_decoder* dec, const void* const* utt_logits, const
   if (p->beam_width < 1) return fail(CTCDEC_ERR_ARG, "beam_width must be >= 1");
   if (p->beam_width > CTCDEC_MAX_BEAM_WIDTH)
     return fail(CTCDEC_ERR_LIMIT, "beam_width above the supported maximum of 256");
+  const int32_t fold = logp_fold(p);
+  if (fold && stream) return fail(CTCDEC_ERR_ARG, "token confidences are not available to streaming decodes");
   std::string err;
   auto t_begin = std::chrono::steady_clock::now();
   std::unique_ptr<ctcdec_result> res(new ctcdec_result());
@@ -1560,6 +1574,73 @@ static int decode_impl(ctcdec_decoder* dec, const void* const* utt_logits, const
     dec->replay_pool->run(n_utts, 4, job);
   } else {
     replay_range(0, n_utts);
+  }
+  // Token confidences: the tokens replay() has just listed go to the device as runs of rows of the survivor arrays, which
+  // this call's prune stage left there (whatever max_surv the overflow redo ended with), one kernel folds each run and one
+  // float64 per token comes back -- in the order of ctcdec_result_token_frames. A label that is missing from a frame's
+  // survivors is a broken invariant ("Token confidences"): the call fails, there is no substitute value.
+  double logp_ms[3] = {0, 0, 0};  // pack + upload, kernel, download
+  if (fold) {
+    auto t0 = std::chrono::steady_clock::now();
+    if (R > (int64_t)UINT32_MAX) return fail(CTCDEC_ERR_LIMIT, "token confidences: more than 2^32 frames in one call");
+    size_t nt = 0;
+    for (const auto& beams : res->utts)
+      for (const BeamResult& b : beams) nt += b.tok.size() / 3;
+    // (packed in page-locked memory that the decoder keeps: a fresh 20 MB of pageable memory costs more than the kernel)
+    if (dec->h_truns.ensure(std::max<size_t>(nt, 1) * sizeof(TokRun), &err)) return fail(CTCDEC_ERR_DEVICE, err);
+    TokRun* runs = (TokRun*)dec->h_truns.p;
+    size_t o = 0;
+    for (int32_t u = 0; u < n_utts; ++u)
+      for (const BeamResult& b : res->utts[(size_t)u]) {
+        const int32_t* t = b.tok.data();
+        for (size_t k = 0, n = b.tok.size() / 3; k < n; ++k, ++o, t += 3) {
+          const int64_t s = (int64_t)t[1] - p->first_frame, e = (int64_t)t[2] - p->first_frame;
+          if (t[0] < 0 || t[0] >= V || s < 0 || e <= s || e > utt_frames[u]) return fail(CTCDEC_ERR_INTERNAL, "token frames out of range");
+          runs[o] = TokRun{(uint32_t)(row0[(size_t)u] + s), (uint32_t)(e - s), (uint32_t)t[0]};
+        }
+      }
+    res->tk_logp.resize(nt);
+    uint32_t missing = 0;
+#ifdef CTC_SIM  // (the simulator's device memory is host memory: the kernel's body, token by token)
+    for (size_t i = 0; i < nt; ++i) {
+      const uint32_t* cnt = (const uint32_t*)dec->w_scnt.p;
+      const uint16_t* sid = (const uint16_t*)dec->w_sid.p;
+      const double* slp = (const double*)dec->w_slp.p;
+      missing += fold == LOGP_MEAN  ? token_logp_of<LOGP_MEAN>(runs[i], cnt, sid, slp, (uint32_t)max_surv, &res->tk_logp[i])
+                 : fold == LOGP_MIN ? token_logp_of<LOGP_MIN>(runs[i], cnt, sid, slp, (uint32_t)max_surv, &res->tk_logp[i])
+                                    : token_logp_of<LOGP_MAX>(runs[i], cnt, sid, slp, (uint32_t)max_surv, &res->tk_logp[i]);
+    }
+#else
+    if (nt) {
+      if (dec->w_truns.ensure(nt * sizeof(TokRun), &err) || be::h2d(dec->w_truns.p, runs, nt * sizeof(TokRun), &err) ||
+          dec->w_tlogp.ensure(nt * 8, &err) || dec->w_tmiss.ensure(16, &err) || be::zero(dec->w_tmiss.p, 16, &err))
+        return fail(CTCDEC_ERR_DEVICE, err);
+      be::TokenLogpArgs ta;
+      ta.runs = (const TokRun*)dec->w_truns.p;
+      ta.n_tokens = (int64_t)nt;
+      ta.fold = fold;
+      ta.surv_cnt = (const uint32_t*)dec->w_scnt.p;
+      ta.surv_id = (const uint16_t*)dec->w_sid.p;
+      ta.surv_lp = (const double*)dec->w_slp.p;
+      ta.max_surv = max_surv;
+      ta.out = (double*)dec->w_tlogp.p;
+      ta.missing = (uint32_t*)dec->w_tmiss.p;
+      auto t1 = std::chrono::steady_clock::now();
+      if (be::launch_token_logp(ta, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+      if (host_timing) logp_ms[1] = be::last_token_logp_ms();
+      auto t2 = std::chrono::steady_clock::now();
+      if (be::d2h(res->tk_logp.data(), dec->w_tlogp.p, nt * 8, &err) || be::d2h(&missing, dec->w_tmiss.p, 4, &err))
+        return fail(CTCDEC_ERR_DEVICE, err);
+      logp_ms[0] = std::chrono::duration<double, std::milli>(t1 - t0).count();
+      logp_ms[2] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t2).count();
+    }
+#endif
+    if (missing)
+      return fail(CTCDEC_ERR_INTERNAL, "token confidences: " + std::to_string(missing) + " token frames whose label is not among the frame's survivors");
+    res->has_logp = true;
+    if (host_timing)
+      fprintf(stderr, "[ctcdec host] token confidences: %zu tokens, pack + upload %.3f ms, kernel %.3f ms, download %.3f ms\n", nt,
+              logp_ms[0], logp_ms[1], logp_ms[2]);
   }
   auto t_end = std::chrono::steady_clock::now();
   res->ms[2] = std::chrono::duration<double, std::milli>(t_end - t_begin).count();
@@ -2179,6 +2260,14 @@ int ctcdec_result_token_frames(ctcdec_result* r, const int64_t** tok_off_out, co
   *start_out = r->tk_start.data();
   *end_out = r->tk_end.data();
   *n_tokens_out = (int64_t)r->tk_label.size();
+  return CTCDEC_OK;
+}
+
+int ctcdec_result_token_logp(ctcdec_result* r, const double** logp_out, int64_t* n_tokens_out) {
+  if (!r || !logp_out || !n_tokens_out) return fail(CTCDEC_ERR_ARG, "no result");
+  if (!r->has_logp) return fail(CTCDEC_ERR_ARG, "the result was decoded without a token confidence fold (params.token_frames = CTCDEC_TOKEN_LOGP_*)");
+  *logp_out = r->tk_logp.data();
+  *n_tokens_out = (int64_t)r->tk_logp.size();
   return CTCDEC_OK;
 }
 

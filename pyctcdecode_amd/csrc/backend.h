@@ -9,6 +9,7 @@
 #include <string>
 
 #include "beam_core.h"
+#include "token_logp.h"
 
 namespace ctc {
 namespace be {
@@ -167,6 +168,22 @@ bool wave_kernel_chosen(const BeamArgs& a);
 // Is this batch small enough for the choice to depend on the input (then the caller reads the prune stage's survivor count
 // before it launches the beam stage -- one small read-back between the two stages)?
 bool beam_kernel_depends_on_input(const BeamArgs& a);
+
+// Token confidences (token_logp.h): one lane per token folds the log-probabilities of the token's label over the frames of its
+// run, read from the survivor lists of this call's prune stage. `missing` counts the frames whose list does not hold the label.
+struct TokenLogpArgs {
+  const TokRun* runs;  // [n_tokens] (device)
+  int64_t n_tokens;
+  int32_t fold;        // LOGP_MEAN / LOGP_MIN / LOGP_MAX
+  const uint32_t* surv_cnt;
+  const uint16_t* surv_id;
+  const double* surv_lp;
+  int32_t max_surv;
+  double* out;         // [n_tokens] (device)
+  uint32_t* missing;   // [1] (device), zeroed by the caller
+};
+int launch_token_logp(const TokenLogpArgs& a, std::string* err);
+double last_token_logp_ms();  // the last launch_token_logp's kernel time (HIP events); waits for the kernel
 
 // stage timing (ms) of the last launch_prune / launch_beam pair, measured on the decode stream
 void last_timing(double* prune_ms, double* beam_ms);

@@ -2359,5 +2359,42 @@ int launch_beam(const BeamArgs& a, std::string* err) {
   return 0;
 }
 
+// Token confidences: one token per lane. A token's frames are consecutive rows of the survivor arrays (mostly one or two; the
+// lists hold a handful of labels), and the tokens of a beam come in frame order, so neighbouring lanes read neighbouring rows:
+// scattered 2- and 8-byte reads that the L2 still holds from the beam stage. Nothing to share between lanes, no LDS.
+template <int FOLD>
+__global__ __launch_bounds__(256) void token_logp(TokenLogpArgs a) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.n_tokens) return;
+  double v;
+  const uint32_t missing = token_logp_of<FOLD>(a.runs[i], a.surv_cnt, a.surv_id, a.surv_lp, (uint32_t)a.max_surv, &v);
+  a.out[i] = v;
+  if (missing) atomicAdd(a.missing, missing);
+}
+
+static hipEvent_t g_logp_ev[2] = {nullptr, nullptr};
+int launch_token_logp(const TokenLogpArgs& a, std::string* err) {
+  if (a.n_tokens <= 0) return 0;
+  if (!g_logp_ev[0])
+    for (int k = 0; k < 2; ++k) HIP_TRY(hipEventCreate(&g_logp_ev[k]));
+  const dim3 grid((unsigned)((a.n_tokens + 255) / 256)), block(256);
+  HIP_TRY(hipEventRecord(g_logp_ev[0], g_stream));
+  if (a.fold == LOGP_MEAN) hipLaunchKernelGGL(token_logp<LOGP_MEAN>, grid, block, 0, g_stream, a);
+  else if (a.fold == LOGP_MIN) hipLaunchKernelGGL(token_logp<LOGP_MIN>, grid, block, 0, g_stream, a);
+  else if (a.fold == LOGP_MAX) hipLaunchKernelGGL(token_logp<LOGP_MAX>, grid, block, 0, g_stream, a);
+  else {
+    if (err) *err = "unknown token_logp fold";
+    return -1;
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(g_logp_ev[1], g_stream));
+  return 0;
+}
+double last_token_logp_ms() {
+  float ms = 0.f;
+  if (!g_logp_ev[1] || hipEventSynchronize(g_logp_ev[1]) != hipSuccess) return 0.0;
+  return hipEventElapsedTime(&ms, g_logp_ev[0], g_logp_ev[1]) == hipSuccess ? (double)ms : 0.0;
+}
+
 }  // namespace be
 }  // namespace ctc

@@ -109,16 +109,60 @@ class TokenOutputBeam(OutputBeam):
     token_frames: List[Tuple[str, Frames]]
 
 
+@dataclasses.dataclass(frozen=True)
+class ConfidenceOutputBeam(TokenOutputBeam):
+    """A TokenOutputBeam with confidences (decode_beams(..., confidence="mean" | "min" | "max")), as natural-log
+    probabilities (<= 0; ``exp()`` gives the [0, 1] form). ``token_logp`` is parallel to ``token_frames``: the fold, over the
+    frames ``start .. end - 1`` of the token, of the log-probability the acoustic model gave the token's label at that
+    frame (the clipped log-softmax the token prune looks at); "mean" is the arithmetic mean, the log of the geometric mean
+    of the probabilities. ``word_logp`` is parallel to ``text_frames``: the smallest ``token_logp`` among the word's tokens."""
+
+    token_logp: List[float]
+    word_logp: List[float]
+
+
+CONFIDENCE_FOLDS = {"mean": 2, "min": 3, "max": 4}  # ctcdec_params.token_frames: CTCDEC_TOKEN_LOGP_MEAN / _MIN / _MAX
+
+
+def _confidence_fold(confidence: Optional[str]) -> int:
+    """The native fold of a ``confidence`` argument (0: none asked for)."""
+    if confidence is None:
+        return 0
+    if not isinstance(confidence, str) or confidence not in CONFIDENCE_FOLDS:
+        raise ValueError("confidence must be None, 'mean', 'min' or 'max', not %r" % (confidence,))
+    return CONFIDENCE_FOLDS[confidence]
+
+
+def _word_logps(text_frames: Sequence[WordFrames], token_frames: Sequence[Tuple[str, Frames]],
+                token_logp: Sequence[float]) -> List[float]:
+    """Per word the smallest token_logp of its run of tokens: those with ``ws <= start`` and ``end <= we``."""
+    out, k, n = [], 0, len(token_frames)
+    for _, (ws, we) in text_frames:
+        while k < n and token_frames[k][1][0] < ws:
+            k += 1
+        lo = k
+        while k < n and token_frames[k][1][1] <= we:
+            k += 1
+        if k == lo:
+            raise RuntimeError("a word of text_frames spans no token of token_frames")
+        out.append(min(token_logp[lo:k]))
+    return out
+
+
 class TokenFrames:
     """The token frames of a decode_batch(..., token_frames=True) call as arrays: utterance i's tokens are
     ``[offsets[i], offsets[i + 1])`` of ``label`` (alphabet index), ``start`` and ``end`` (int32); ``offsets`` is int64
-    ``[B + 1]``. ``of(i)`` lists them as TokenOutputBeam.token_frames does."""
+    ``[B + 1]``. ``of(i)`` lists them as TokenOutputBeam.token_frames does. ``logp`` is None, or after
+    decode_batch(..., confidence=...) the tokens' confidences as a float64 array aligned with ``label``
+    (ConfidenceOutputBeam.token_logp; ``logp_of(i)`` lists utterance i's)."""
 
-    __slots__ = ("label", "start", "end", "offsets", "labels")
+    __slots__ = ("label", "start", "end", "offsets", "labels", "logp")
 
-    def __init__(self, label: np.ndarray, start: np.ndarray, end: np.ndarray, offsets: np.ndarray, labels: Sequence[str]):
+    def __init__(self, label: np.ndarray, start: np.ndarray, end: np.ndarray, offsets: np.ndarray, labels: Sequence[str],
+                 logp: Optional[np.ndarray] = None):
         self.label, self.start, self.end, self.offsets = label, start, end, offsets
         self.labels = list(labels)
+        self.logp = logp
 
     def __len__(self) -> int:
         return len(self.offsets) - 1
@@ -129,6 +173,11 @@ class TokenFrames:
         return [(labels[c], (s, e)) for c, s, e in zip(self.label[lo:hi].tolist(), self.start[lo:hi].tolist(),
                                                         self.end[lo:hi].tolist())]
 
+    def logp_of(self, i: int) -> List[float]:
+        if self.logp is None:
+            raise ValueError("these token frames were decoded without confidence=...")
+        return self.logp[int(self.offsets[i]):int(self.offsets[i + 1])].tolist()
+
     @classmethod
     def join(cls, parts: Sequence["TokenFrames"], labels: Sequence[str]) -> "TokenFrames":
         """The parts of consecutive slices of a batch as one (offsets rebased)."""
@@ -138,10 +187,13 @@ class TokenFrames:
             offs.append(t.offsets[1:] + base)
             base += int(t.offsets[-1])
         cat = lambda name: np.concatenate([getattr(t, name) for t in parts]) if parts else np.zeros(0, np.int32)  # noqa: E731
-        return cls(cat("label"), cat("start"), cat("end"), np.concatenate(offs), labels)
+        logp = None
+        if parts and all(t.logp is not None for t in parts):
+            logp = np.concatenate([t.logp for t in parts])
+        return cls(cat("label"), cat("start"), cat("end"), np.concatenate(offs), labels, logp)
 
     def __reduce__(self):
-        return TokenFrames, (self.label, self.start, self.end, self.offsets, self.labels)
+        return TokenFrames, (self.label, self.start, self.end, self.offsets, self.labels, self.logp)
 
 
 NULL_FRAMES: Frames = (-1, -1)
@@ -1155,15 +1207,19 @@ class BeamSearchDecoderCTC:
         hotword_weight: float = DEFAULT_HOTWORD_WEIGHT,
         lm_start_state: Optional[AbstractLMState] = None,
         token_frames: bool = False,
+        confidence: Optional[str] = None,
     ) -> List[OutputBeam]:
-        """token_frames=True: TokenOutputBeams, which also carry the frames of every token of the beam."""
+        """token_frames=True: TokenOutputBeams, which also carry the frames of every token of the beam.
+        confidence="mean" | "min" | "max" (implies token_frames): ConfidenceOutputBeams, which also carry the confidence of
+        every token -- that fold of its label's log-probability over its frames -- and of every word."""
         self._check_logits_dimension(logits)
+        fold = _confidence_fold(confidence)
         params = self._params(beam_width, beam_prune_logp, token_min_logp, prune_history, hotword_weight, 0)
-        params.token_frames = int(bool(token_frames))
+        params.token_frames = fold or int(bool(token_frames))
         res = self._run([logits], params, hotwords, [lm_start_state])
         try:
             beams = self._unpack(res, True)
-            return (self._with_tokens(res, beams) if token_frames else beams)[0]
+            return (self._with_tokens(res, beams, bool(fold)) if params.token_frames else beams)[0]
         finally:
             self._lib.dll.ctcdec_result_free(res)
 
@@ -1196,37 +1252,44 @@ class BeamSearchDecoderCTC:
         hotwords: Optional[Iterable[str]] = None,
         hotword_weight: float = DEFAULT_HOTWORD_WEIGHT,
         token_frames: bool = False,
+        confidence: Optional[str] = None,
     ) -> Any:
         """decoder.py:895-945. One device launch decodes the whole batch: a multiprocessing pool is ignored. A
         `pyctcdecode_amd.parallel.DevicePool` -- one worker process per GPU -- shards the batch over its devices.
-        token_frames=True: returns (texts, TokenFrames), the frames of every token of each text as arrays."""
+        token_frames=True: returns (texts, TokenFrames), the frames of every token of each text as arrays.
+        confidence="mean" | "min" | "max" (implies token_frames): the TokenFrames also carry ``logp``, the confidence of
+        every token (ConfidenceOutputBeam.token_logp) as a float64 array."""
+        fold = _confidence_fold(confidence)
+        token_frames = bool(token_frames) or bool(fold)
         if getattr(logits_list, "ndim", 0) != 3:
             logits_list = list(logits_list)
         if len(logits_list) == 0:
-            return ([], self._empty_token_frames()) if token_frames else []
+            return ([], self._empty_token_frames(bool(fold))) if token_frames else []
         if type(pool).__name__ == "DevicePool":
-            kw = dict(token_frames=True) if token_frames else {}
+            kw = dict(confidence=confidence) if fold else dict(token_frames=True) if token_frames else {}
             return pool.decode_batch(logits_list, beam_width=beam_width, beam_prune_logp=beam_prune_logp,
                                      token_min_logp=token_min_logp, hotwords=hotwords, hotword_weight=hotword_weight, **kw)
         hotwords, hotword_weight, hot_sets = self._resolve_hot(hotwords, hotword_weight, len(logits_list))
         params = self._params(beam_width, beam_prune_logp, token_min_logp, True, hotword_weight, 1)
         if token_frames:  # (the best beam's emission list comes back: one host pass gives its text and its tokens)
-            params.token_frames = 1
+            params.token_frames = fold or 1
         else:
             params.texts_only = 1  # (the kernels write the texts themselves: no emission lists to copy back and replay)
         res = self._run(logits_list, params, hotwords, hot_sets=hot_sets)
         try:
             texts = self._texts(res)
-            return (texts, self._token_frames(res, len(texts))) if token_frames else texts
+            return (texts, self._token_frames(res, len(texts), bool(fold))) if token_frames else texts
         finally:
             self._lib.dll.ctcdec_result_free(res)
 
-    def _empty_token_frames(self) -> TokenFrames:
+    def _empty_token_frames(self, with_logp: bool = False) -> TokenFrames:
         z = np.zeros(0, dtype=np.int32)
-        return TokenFrames(z, z.copy(), z.copy(), np.zeros(1, dtype=np.int64), self._alphabet.labels)
+        return TokenFrames(z, z.copy(), z.copy(), np.zeros(1, dtype=np.int64), self._alphabet.labels,
+                           np.zeros(0, dtype=np.float64) if with_logp else None)
 
-    def _token_frames(self, res, n_beams: int) -> TokenFrames:
-        """The token frames of all beams of a result (ctcdec_result_token_frames), copied into numpy arrays."""
+    def _token_frames(self, res, n_beams: int, with_logp: bool = False) -> TokenFrames:
+        """The token frames of all beams of a result (ctcdec_result_token_frames), copied into numpy arrays; with_logp: and
+        their confidences (ctcdec_result_token_logp)."""
         off_p, lab_p, st_p, en_p = (C.POINTER(C.c_int64)(), C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)(),
                                     C.POINTER(C.c_int32)())
         n = C.c_int64()
@@ -1238,15 +1301,33 @@ class BeamSearchDecoderCTC:
             arrs = [np.ctypeslib.as_array(q, shape=(nt,)).copy() for q in (lab_p, st_p, en_p)]
         else:
             arrs = [np.zeros(0, dtype=np.int32) for _ in range(3)]
-        return TokenFrames(arrs[0], arrs[1], arrs[2], offsets, self._alphabet.labels)
+        logp = None
+        if with_logp:
+            logp = self._token_logp(res)
+            if len(logp) != nt:
+                raise B.NativeError("token confidences and token frames differ in number")
+        return TokenFrames(arrs[0], arrs[1], arrs[2], offsets, self._alphabet.labels, logp)
 
-    def _with_tokens(self, res, beams: List[List[OutputBeam]]) -> List[List[TokenOutputBeam]]:
-        tf = self._token_frames(res, sum(len(bs) for bs in beams))
+    def _token_logp(self, res) -> np.ndarray:
+        """The token confidences of all beams of a result (ctcdec_result_token_logp), copied into a float64 array."""
+        lp_p, n = C.POINTER(C.c_double)(), C.c_int64()
+        self._lib.check(self._lib.dll.ctcdec_result_token_logp(res, C.byref(lp_p), C.byref(n)))
+        nt = int(n.value)
+        return np.ctypeslib.as_array(lp_p, shape=(nt,)).copy() if nt else np.zeros(0, dtype=np.float64)
+
+    def _with_tokens(self, res, beams: List[List[OutputBeam]], with_logp: bool = False) -> List[List[TokenOutputBeam]]:
+        tf = self._token_frames(res, sum(len(bs) for bs in beams), with_logp)
         out, k = [], 0
         for bs in beams:
             row = []
             for b in bs:
-                row.append(TokenOutputBeam(b.text, b.last_lm_state, b.text_frames, b.logit_score, b.lm_score, tf.of(k)))
+                toks = tf.of(k)
+                if with_logp:
+                    lps = tf.logp_of(k)
+                    row.append(ConfidenceOutputBeam(b.text, b.last_lm_state, b.text_frames, b.logit_score, b.lm_score, toks,
+                                                    lps, _word_logps(b.text_frames, toks, lps)))
+                else:
+                    row.append(TokenOutputBeam(b.text, b.last_lm_state, b.text_frames, b.logit_score, b.lm_score, toks))
                 k += 1
             out.append(row)
         return out
@@ -1287,26 +1368,30 @@ class BeamSearchDecoderCTC:
         hotwords: Optional[Iterable[str]] = None,
         hotword_weight: float = DEFAULT_HOTWORD_WEIGHT,
         token_frames: bool = False,
+        confidence: Optional[str] = None,
     ) -> List[List[OutputBeam]]:
         """decoder.py:801-857. Beams carry ``last_lm_state=None`` like the reference's mp-safe beams. ``pool``: see decode_batch.
-        token_frames=True: TokenOutputBeams, which also carry the frames of every token of the beam."""
+        token_frames=True: TokenOutputBeams, which also carry the frames of every token of the beam.
+        confidence="mean" | "min" | "max" (implies token_frames): ConfidenceOutputBeams, see decode_beams."""
+        fold = _confidence_fold(confidence)
+        token_frames = bool(token_frames) or bool(fold)
         logits_list = list(logits_list)
         for logits in logits_list:
             self._check_logits_dimension(logits)
         if len(logits_list) == 0:
             return []
         if type(pool).__name__ == "DevicePool":
-            kw = dict(token_frames=True) if token_frames else {}
+            kw = dict(confidence=confidence) if fold else dict(token_frames=True) if token_frames else {}
             return pool.decode_beams_batch(logits_list, beam_width=beam_width, beam_prune_logp=beam_prune_logp,
                                            token_min_logp=token_min_logp, prune_history=prune_history, hotwords=hotwords,
                                            hotword_weight=hotword_weight, **kw)
         hotwords, hotword_weight, hot_sets = self._resolve_hot(hotwords, hotword_weight, len(logits_list))
         params = self._params(beam_width, beam_prune_logp, token_min_logp, prune_history, hotword_weight, 0)
-        params.token_frames = int(bool(token_frames))
+        params.token_frames = fold or int(token_frames)
         res = self._run(logits_list, params, hotwords, hot_sets=hot_sets)
         try:
             beams = self._unpack(res, False)
-            return self._with_tokens(res, beams) if token_frames else beams
+            return self._with_tokens(res, beams, bool(fold)) if token_frames else beams
         finally:
             self._lib.dll.ctcdec_result_free(res)
 

@@ -159,8 +159,8 @@ def decode_batch_sharded(decoder, logits_list, group=None, **kwargs) -> List[str
     the texts of the whole batch in input order. One collective."""
     import torch.distributed as dist
 
-    if kwargs.get("token_frames"):
-        raise NotImplementedError("token_frames=True is not gathered over ranks: decode_batch each rank's slice itself")
+    if kwargs.get("token_frames") or kwargs.get("confidence") is not None:
+        raise NotImplementedError("token_frames=True / confidence=... is not gathered over ranks: decode_batch each rank's slice itself")
     if not dist.is_available() or not dist.is_initialized():
         return decoder.decode_batch(None, logits_list, **kwargs)
     world, rank = dist.get_world_size(group), dist.get_rank(group)
@@ -177,8 +177,8 @@ def decode_beams_batch_sharded(decoder, logits_list, group=None, **kwargs) -> Li
     input order (beams carry last_lm_state=None, as in the reference's pool path)."""
     import torch.distributed as dist
 
-    if kwargs.get("token_frames"):
-        raise NotImplementedError("token_frames=True is not gathered over ranks: decode_beams_batch each rank's slice itself")
+    if kwargs.get("token_frames") or kwargs.get("confidence") is not None:
+        raise NotImplementedError("token_frames=True / confidence=... is not gathered over ranks: decode_beams_batch each rank's slice itself")
     if not dist.is_available() or not dist.is_initialized():
         return decoder.decode_beams_batch(None, logits_list, **kwargs)
     world, rank = dist.get_world_size(group), dist.get_rank(group)
@@ -218,6 +218,10 @@ def _device_worker(conn, device: int, decoder_dir: str, library: Optional[str]) 
         try:
             if method == "decode_batch":
                 conn.send(("ok", dec.decode_batch(None, logits, **kwargs)))
+            elif kwargs.get("confidence") is not None:
+                beams = dec.decode_beams_batch(None, logits, **kwargs)
+                conn.send(("ok", [[(b.text, list(b.text_frames), b.logit_score, b.lm_score, b.token_frames, b.token_logp,
+                                    b.word_logp) for b in bs] for bs in beams]))
             elif kwargs.get("token_frames"):
                 beams = dec.decode_beams_batch(None, logits, **kwargs)
                 conn.send(("ok", [[(b.text, list(b.text_frames), b.logit_score, b.lm_score, b.token_frames) for b in bs]
@@ -305,7 +309,7 @@ class DevicePool:
         return parts
 
     def decode_batch(self, logits_list, **kwargs) -> List[str]:
-        if kwargs.get("token_frames"):  # (texts, TokenFrames) per slice -> one of each, offsets rebased
+        if kwargs.get("token_frames") or kwargs.get("confidence") is not None:  # (texts, TokenFrames) per slice -> one of each, offsets rebased
             from pyctcdecode_amd.decoder import TokenFrames
 
             parts = self._parts("decode_batch", logits_list, kwargs)
@@ -316,8 +320,11 @@ class DevicePool:
         return self._map("decode_batch", logits_list, kwargs)
 
     def decode_beams_batch(self, logits_list, **kwargs):
-        from pyctcdecode_amd.decoder import OutputBeam, TokenOutputBeam
+        from pyctcdecode_amd.decoder import ConfidenceOutputBeam, OutputBeam, TokenOutputBeam
 
+        if kwargs.get("confidence") is not None:
+            return [[ConfidenceOutputBeam(t, None, f, lg, lm, tf, tl, wl) for t, f, lg, lm, tf, tl, wl in beams]
+                    for beams in self._map("decode_beams_batch", logits_list, kwargs)]
         if kwargs.get("token_frames"):
             return [[TokenOutputBeam(t, None, f, lg, lm, tf) for t, f, lg, lm, tf in beams]
                     for beams in self._map("decode_beams_batch", logits_list, kwargs)]
