@@ -14,6 +14,7 @@
 #include <memory>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "../../include/ctcdec.h"
@@ -35,47 +36,38 @@ static int fail(int code, const std::string& msg) {
 
 namespace {
 
-struct DevBuf {
+// Grow-only device (HOST: page-locked staging) memory, owned: released with the buffer, handed over by a move.
+template <bool HOST>
+struct Buf {
   void* p = nullptr;
   size_t cap = 0;
+  Buf() = default;
+  Buf(const Buf&) = delete;
+  Buf& operator=(const Buf&) = delete;
+  Buf(Buf&& o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}
+  Buf& operator=(Buf&& o) noexcept {  // (what this held goes to `o`, and away with it)
+    std::swap(p, o.p);
+    std::swap(cap, o.cap);
+    return *this;
+  }
+  ~Buf() { drop(); }
   int ensure(size_t bytes, std::string* err) {
     if (bytes <= cap && p) return 0;
-    if (p) be::release(p);
-    p = nullptr;
-    cap = 0;
-    size_t want = bytes + bytes / 8 + 256;
-    p = be::alloc(want, err);
+    drop();
+    const size_t want = HOST ? bytes + bytes / 4 + 4096 : bytes + bytes / 8 + 256;
+    p = HOST ? be::alloc_host(want, err) : be::alloc(want, err);
     if (!p) return -1;
     cap = want;
     return 0;
   }
   void drop() {
-    if (p) be::release(p);
+    if (p) HOST ? be::release_host(p) : be::release(p);
     p = nullptr;
     cap = 0;
   }
 };
-
-struct HostBuf {  // grow-only page-locked staging buffer
-  void* p = nullptr;
-  size_t cap = 0;
-  int ensure(size_t bytes, std::string* err) {
-    if (bytes <= cap && p) return 0;
-    if (p) be::release_host(p);
-    p = nullptr;
-    cap = 0;
-    size_t want = bytes + bytes / 4 + 4096;
-    p = be::alloc_host(want, err);
-    if (!p) return -1;
-    cap = want;
-    return 0;
-  }
-  void drop() {
-    if (p) be::release_host(p);
-    p = nullptr;
-    cap = 0;
-  }
-};
+using DevBuf = Buf<false>;
+using HostBuf = Buf<true>;
 
 template <class T>
 int upload(DevBuf& b, const std::vector<T>& v, std::string* err) {
@@ -223,31 +215,6 @@ struct ctcdec_decoder {
   size_t stage_used = 0;
   bool profile = false;
   unsigned long long prof[N_PROF] = {0};
-  ~ctcdec_decoder() {
-    DevBuf* all[] = {&d_tok,  &d_tok_hot, &d_uni,  &d_pref,  &d_hot,  &w_logits, &w_ptrs, &w_row0,
-                     &w_rowsum, &w_isprob, &w_scnt, &w_sid,  &w_slp,   &w_flags, &w_text,   &w_emit, &w_toff,
-                     &w_eoff,  &w_start,  &w_out,  &w_nout, &w_status, &w_tok,  &w_head, &w_prof, &w_imp, &w_impoff, &w_ff, &w_cold, &w_pay,
-                     &w_tscr,  &w_tsoff, &w_tpool, &d_toktext, &d_tokbytes, &w_slow, &w_order, &w_side,
-                     &w_truns, &w_tlogp, &w_tmiss};
-    for (DevBuf* b : all) b->drop();
-    for (int k = 0; k < MAX_LMS - 1; ++k) {
-      d_xuni[k].drop();
-    }
-    for (int k = 0; k < MAX_LMS; ++k) d_winfo[k].drop();
-    w_xstate.drop();
-    w_impx.drop();
-    d_hsets.drop();
-    d_htab.drop();
-    d_htok.drop();
-    d_hutt.drop();
-    h_hot.drop();
-    h_xstate.drop();
-    h_tok.drop();
-    h_out.drop();
-    h_small.drop();
-    h_truns.drop();
-    h_stage.drop();
-  }
 };
 
 // A call's small per-utterance tables (pointers, row offsets, arena offsets, start states): copied into the decoder's page-locked
@@ -396,13 +363,6 @@ struct ctcdec_stream {
   std::vector<ctcdec_beam_in> imp_beams;
   std::vector<int64_t> imp_off;
   std::string imp_blob;
-  ~ctcdec_stream() {
-    carry.drop();
-    carry_x.drop();
-    sstate.drop();
-    emit.drop();
-    eoff.drop();
-  }
 };
 
 // the device copy of a model's n-gram table: uploaded once per NgramStore, shared by every decoder that holds the model
@@ -412,10 +372,7 @@ static const NgramEntry* device_ngrams(const HostLM& lm) {
 }
 static int upload_ngrams(const HostLM& lm, std::string* err) {
   if (lm.ngr->device) return 0;
-  std::shared_ptr<DevBuf> buf(new DevBuf(), [](DevBuf* b) {
-    b->drop();
-    delete b;
-  });
+  auto buf = std::make_shared<DevBuf>();
   if (upload(*buf, lm.ngr->table, err)) return -1;
   lm.ngr->device = buf;
   return 0;
@@ -469,6 +426,15 @@ static int sync_tables(ctcdec_decoder* d, std::string* err) {
     d->hot_dirty = false;
   }
   return 0;
+}
+
+// a kernel-side LM state as the ABI hands it out
+static void export_lm_state(const LmState& s, ctcdec_lm_state* out) {
+  out->length = s.len;
+  for (int k = 0; k < MAX_CTX; ++k) {
+    out->words[k] = s.words[k];
+    out->backoff[k] = s.backoff[k];
+  }
 }
 
 static void device_tables(const ctcdec_decoder* d, DeviceTables* t) {
@@ -677,11 +643,7 @@ int ctcdec_lm_start_state(const ctcdec_decoder* dec, int32_t begin_sentence, ctc
   if (!dec || !dec->has_lm || !out) return fail(CTCDEC_ERR_ARG, "no language model loaded");
   LmState st;
   dec->lm_ref().start_state(begin_sentence != 0, &st);
-  out->length = st.len;
-  for (int k = 0; k < MAX_CTX; ++k) {
-    out->words[k] = st.words[k];
-    out->backoff[k] = st.backoff[k];
-  }
+  export_lm_state(st, out);
   return CTCDEC_OK;
 }
 
@@ -699,11 +661,7 @@ int ctcdec_lm_base_score(const ctcdec_decoder* dec, const ctcdec_lm_state* in, u
     a.backoff[k] = in->backoff[k];
   }
   *log10_prob_out = lm_base_score(t, a, word_index, &b);
-  out->length = b.len;
-  for (int k = 0; k < MAX_CTX; ++k) {
-    out->words[k] = b.words[k];
-    out->backoff[k] = b.backoff[k];
-  }
+  export_lm_state(b, out);
   return CTCDEC_OK;
 }
 
@@ -834,20 +792,10 @@ static void replay(const ctcdec_decoder* d, const EmitNode* toks, uint32_t n, co
 static void fill_result(const OutBeam& ob, const LmState* xs, int K, BeamResult* r) {
   r->logit = ob.logit_score;
   r->lm = ob.lm_score;
-  r->state.length = ob.state.len;
-  for (int j = 0; j < MAX_CTX; ++j) {
-    r->state.words[j] = ob.state.words[j];
-    r->state.backoff[j] = ob.state.backoff[j];
-  }
+  export_lm_state(ob.state, &r->state);
   if (xs) {
     r->xstates.resize((size_t)(K - 1));
-    for (int x = 0; x < K - 1; ++x) {
-      r->xstates[(size_t)x].length = xs[x].len;
-      for (int j = 0; j < MAX_CTX; ++j) {
-        r->xstates[(size_t)x].words[j] = xs[x].words[j];
-        r->xstates[(size_t)x].backoff[j] = xs[x].backoff[j];
-      }
-    }
+    for (int x = 0; x < K - 1; ++x) export_lm_state(xs[x], &r->xstates[(size_t)x]);
   }
   r->last_char = ob.last_char == NO_CHAR ? -1 : (int32_t)ob.last_char;
   r->pstart = ob.pstart;
@@ -861,13 +809,38 @@ static int32_t logp_fold(const ctcdec_params* p) {
   return p && p->token_frames >= LOGP_MEAN && p->token_frames <= LOGP_MAX ? p->token_frames : 0;
 }
 
-// after_launch: called once the kernels of this call are queued and before the host waits for them (time-sliced host ingest:
-// the next slice's copy runs under this slice's kernels)
+using Clock = std::chrono::steady_clock;
+static double ms(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
+static size_t dtype_size(int32_t dtype) { return dtype == CTCDEC_F32 ? 4 : dtype == CTCDEC_F64 ? 8 : 2; }
+
+// A caller's LM state into the kernels' form: its length must lie in [0, MAX_CTX], every word index below the model's word count.
+enum LmStateErr { LM_STATE_OK = 0, LM_STATE_LENGTH, LM_STATE_WORD };
+static LmStateErr copy_lm_state(const ctcdec_lm_state& in, size_t n_words, LmState* out) {
+  memset(out, 0, sizeof(*out));
+  if (in.length < 0 || in.length > MAX_CTX) return LM_STATE_LENGTH;
+  out->len = in.length;
+  for (int j = 0; j < out->len; ++j) {
+    if (in.words[j] >= n_words) return LM_STATE_WORD;
+    out->words[j] = in.words[j];
+    out->backoff[j] = in.backoff[j];
+  }
+  return LM_STATE_OK;
+}
+
 typedef std::function<int(std::string*)> AfterLaunch;
+// How a decode call is run. Neither pointer: a plain batch. `stream` alone: host imports. `rs`: the streams are device-
+// resident (`stream` then only carries first_frame / fold / eos and, below an import, the caller's beams for the replay).
+struct DecodeMode {
+  const StreamIn* stream = nullptr;
+  ctcdec_stream* rs = nullptr;
+  bool want_result = true;  // materialise beams at all (a resident stream between reads: no)
+  // called once the kernels of this call are queued and before the host waits for them (time-sliced host ingest: the next
+  // slice's copy runs under this slice's kernels)
+  const AfterLaunch* after_launch = nullptr;
+};
 static int decode_impl(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts,
                        int32_t dtype, int32_t is_device, const ctcdec_params* p, const ctcdec_lm_state* start_states,
-                       const StreamIn* stream, ctcdec_result** out, ctcdec_stream* rs = nullptr, bool want_result = true,
-                       const AfterLaunch* after_launch = nullptr);
+                       const DecodeMode& mode, ctcdec_result** out);
 static int decode_host_sliced(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts,
                               int32_t dtype, const ctcdec_params* p, const ctcdec_lm_state* start_states, int n_slices,
                               ctcdec_result** out);
@@ -888,7 +861,7 @@ int ctcdec_decode_batch(ctcdec_decoder* dec, const void* const* utt_logits, cons
       if (rc != 1) return rc;
     }
   }
-  return decode_impl(dec, utt_logits, utt_frames, n_utts, dtype, is_device, p, start_states, nullptr, out);
+  return decode_impl(dec, utt_logits, utt_frames, n_utts, dtype, is_device, p, start_states, DecodeMode(), out);
 }
 
 int ctcdec_decode_stream_batch(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames,
@@ -896,22 +869,14 @@ int ctcdec_decode_stream_batch(ctcdec_decoder* dec, const void* const* utt_logit
                                const int32_t* first_frame, const ctcdec_beam_in* beams, const int64_t* beam_off,
                                const char* text_blob, int32_t force_next_word, int32_t is_end, ctcdec_result** out) {
   if (!first_frame || !beams || !beam_off || !text_blob) return fail(CTCDEC_ERR_ARG, "bad arguments");
-  StreamIn st;
-  st.first_frame = first_frame;
-  st.beams = beams;
-  st.beam_off = beam_off;
-  st.text_blob = text_blob;
-  st.fold = (force_next_word || is_end) ? 1 : 0;
-  st.eos = is_end ? 1 : 0;
+  const StreamIn st{first_frame, beams, beam_off, text_blob, (force_next_word || is_end) ? 1 : 0, is_end ? 1 : 0};
   HotCallScope hot_scope(dec);
-  return decode_impl(dec, utt_logits, utt_frames, n_streams, dtype, is_device, p, nullptr, &st, out);
+  return decode_impl(dec, utt_logits, utt_frames, n_streams, dtype, is_device, p, nullptr, DecodeMode{&st}, out);
 }
 
 // host side of a streaming import: strings -> hashes, table views, history ring (the kernel rebuilds
 // the beam row and its TextNode from this)
-static int64_t shape_bw_limit(int beam_width) { return beam_bucket(beam_width); }
-
-static std::string build_import(const ctcdec_decoder* dec, const StreamIn& st, int64_t k, int beam_width, ImportBeam* m,
+static std::string build_import(const ctcdec_decoder* dec, const StreamIn& st, int64_t k, ImportBeam* m,
                                 LmState* more /* n_lms - 1 entries, or nullptr */, const HostHotwords& hot) {
   const ctcdec_beam_in& in = st.beams[k];
   memset(m, 0, sizeof(*m));
@@ -966,249 +931,323 @@ static std::string build_import(const ctcdec_decoder* dec, const StreamIn& st, i
   m->pend = in.partial_end_frame;
   m->logit_score = in.logit_score;
   m->raw_lm = dec->has_lm ? in.raw_lm_score : 0.0;
+  const char* const bad_state[] = {nullptr, "bad LM state in beam", "bad LM state word in beam"};
   if (dec->has_lm) {
-    if (in.lm_state.length < 0 || in.lm_state.length > MAX_CTX) return "bad LM state in beam";
-    m->state.len = in.lm_state.length;
-    for (int j = 0; j < m->state.len; ++j) {
-      if (in.lm_state.words[j] >= dec->lm_ref().words.size()) return "bad LM state word in beam";
-      m->state.words[j] = in.lm_state.words[j];
-      m->state.backoff[j] = in.lm_state.backoff[j];
-    }
+    if (const LmStateErr e = copy_lm_state(in.lm_state, dec->lm_ref().words.size(), &m->state)) return bad_state[e];
   }
   if (dec->multi) {
     if (!in.more_states) return "beam lacks the states of the further language models";
-    for (int x = 1; x < dec->n_lms(); ++x) {
-      const ctcdec_lm_state& g = in.more_states[x - 1];
-      LmState& o = more[x - 1];
-      memset(&o, 0, sizeof(o));
-      if (g.length < 0 || g.length > MAX_CTX) return "bad LM state in beam";
-      o.len = g.length;
-      for (int j = 0; j < o.len; ++j) {
-        if (g.words[j] >= dec->multi->lms[(size_t)x]->words.size()) return "bad LM state word in beam";
-        o.words[j] = g.words[j];
-        o.backoff[j] = g.backoff[j];
-      }
-    }
+    for (int x = 1; x < dec->n_lms(); ++x)
+      if (const LmStateErr e = copy_lm_state(in.more_states[x - 1], dec->multi->lms[(size_t)x]->words.size(), &more[x - 1]))
+        return bad_state[e];
   }
-  (void)beam_width;
   return "";
 }
 
-// rs: the streams are device-resident (`stream` then only carries first_frame / fold / eos and, below an import, the
-// caller's beams for the replay); want_result: materialise beams at all
-static int decode_impl(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts,
-                       int32_t dtype, int32_t is_device, const ctcdec_params* p, const ctcdec_lm_state* start_states,
-                       const StreamIn* stream, ctcdec_result** out, ctcdec_stream* rs, bool want_result,
-                       const AfterLaunch* after_launch) {
-  if (!dec || !p || !out || n_utts < 0 || (n_utts > 0 && (!utt_logits || !utt_frames)))
+// ---- one decode call, stage by stage: decode_impl is a short driver over the stages below, which share one DecodeCall ----
+
+// The frame-prune stage of a call: what it runs on, and what it reports.
+struct PruneStage {
+  ctcdec_decoder* dec = nullptr;
+  const std::vector<const void*>* ptrs = nullptr;  // the utterances' device pointers (already uploaded to w_ptrs, like w_row0)
+  int32_t n_utts = 0, dtype = 0;
+  int64_t R = 0;  // frames of all utterances
+  int V = 0;
+  double token_min_logp = 0;
+  bool resident = false;   // resident streams do not take the dense_calls hint (nor does the diagnostic, which leaves it alone)
+  int max_surv = 0;        // out: the width of the survivor lists the stage ended with
+  uint32_t flags[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // out: PruneArgs::overflow as last read
+  uint32_t surv_total = 0;                       // out: flags[4] of the last pass
+  Clock::time_point t_setup, t_queued, t_flags;  // (CTCDEC_HOST_TIMING: where the host side of a call goes)
+};
+
+struct DecodeCall : DecodeMode {
+  ctcdec_decoder* dec = nullptr;
+  const ctcdec_params* p = nullptr;
+  const void* const* utt_logits = nullptr;
+  const int32_t* utt_frames = nullptr;
+  const ctcdec_lm_state* start_states = nullptr;
+  ctcdec_result** out = nullptr;
+  int32_t n_utts = 0, dtype = 0, is_device = 0, fold = 0;
+  int V = 0, K = 1, B = 0, n_best = 0;
+  int64_t R = 0;
+  std::vector<int64_t> row0;
+  std::vector<const void*> ptrs;
+  std::vector<uint64_t> toff, eoff;  // node offsets of the text / emission arenas
+  bool arenas_full = false;
+  unsigned long long tok_cap = 0;
+  size_t xstate_bytes = 0;
+  bool device_texts = false, by_input = false, late_beam = false;
+  be::BeamArgs ba{};
+  PruneStage prune;
+  // the counters of the beam stage, in page-locked memory (h_small)
+  uint32_t *n_out = nullptr, *status = nullptr;
+  unsigned long long* heads_pinned = nullptr;
+  unsigned long long head = 0;
+  bool outgrown_redone = false;
+  bool host_timing = false;
+  Clock::time_point t_begin, t_launch, t_kernel, t_end;
+  std::string err;
+  std::unique_ptr<ctcdec_result> res;
+  std::unique_lock<std::mutex> device_lock;  // (last: released first)
+};
+
+// 1a. Argument checks; the (still empty) result.
+static int check_call(DecodeCall& c) {
+  const ctcdec_params* p = c.p;
+  if (!c.dec || !p || !c.out || c.n_utts < 0 || (c.n_utts > 0 && (!c.utt_logits || !c.utt_frames)))
     return fail(CTCDEC_ERR_ARG, "bad arguments");
-  if (dtype < CTCDEC_F32 || dtype > CTCDEC_BF16) return fail(CTCDEC_ERR_ARG, "dtype must be f32, f64, f16 or bf16");
+  if (c.dtype < CTCDEC_F32 || c.dtype > CTCDEC_BF16) return fail(CTCDEC_ERR_ARG, "dtype must be f32, f64, f16 or bf16");
   if (p->beam_width < 1) return fail(CTCDEC_ERR_ARG, "beam_width must be >= 1");
   if (p->beam_width > CTCDEC_MAX_BEAM_WIDTH)
     return fail(CTCDEC_ERR_LIMIT, "beam_width above the supported maximum of 256");
-  const int32_t fold = logp_fold(p);
-  if (fold && stream) return fail(CTCDEC_ERR_ARG, "token confidences are not available to streaming decodes");
-  std::string err;
-  auto t_begin = std::chrono::steady_clock::now();
-  std::unique_ptr<ctcdec_result> res(new ctcdec_result());
-  res->utts.resize((size_t)n_utts);
-  if (n_utts == 0) {
-    *out = res.release();
-    return CTCDEC_OK;
-  }
-  const int K = dec->has_lm ? dec->n_lms() : 1;
+  c.fold = logp_fold(p);
+  if (c.fold && c.stream) return fail(CTCDEC_ERR_ARG, "token confidences are not available to streaming decodes");
+  c.t_begin = Clock::now();
+  c.res.reset(new ctcdec_result());
+  c.res->utts.resize((size_t)c.n_utts);
+  return CTCDEC_OK;
+}
+
+// 1b. The hand-over of armed hot-word sets, the device, the tables, the staging block, the row offsets.
+static int open_call(DecodeCall& c) {
+  ctcdec_decoder* dec = c.dec;
+  const int32_t n_utts = c.n_utts;
+  std::string& err = c.err;
+  c.K = dec->has_lm ? dec->n_lms() : 1;
   if (dec->hot_call.armed) {
     if ((int32_t)dec->hot_call.utt_set.size() != n_utts) return fail(CTCDEC_ERR_ARG, "hot-word sets armed for another number of utterances");
-    if (stream && !rs) build_hot_sets(dec->hot_call);  // (the imported beams' words are counted against their stream's set)
+    if (c.stream && !c.rs) build_hot_sets(dec->hot_call);  // (the imported beams' words are counted against their stream's set)
   }
-  std::lock_guard<std::mutex> device_lock(g_device_mu);
+  c.device_lock = std::unique_lock<std::mutex>(g_device_mu);
   if (be::bind_thread(&err)) return fail(CTCDEC_ERR_DEVICE, err);
   if (sync_tables(dec, &err)) return fail(CTCDEC_ERR_DEVICE, err);
-  const int V = (int)dec->alpha.labels.size();
-  const size_t esz = dtype == CTCDEC_F32 ? 4 : dtype == CTCDEC_F64 ? 8 : 2;
+  c.V = (int)dec->alpha.labels.size();
+  c.B = c.p->beam_width;
+  c.n_best = c.p->n_best > 0 ? std::min(c.p->n_best, c.B) : c.B;
+  c.host_timing = getenv("CTCDEC_HOST_TIMING") != nullptr;
   // staging for this call's small uploads (every earlier call has synchronised: nothing is in flight from the block)
   dec->stage_used = 0;
-  if (dec->h_stage.ensure((size_t)n_utts * (64 + sizeof(LmState) * (size_t)K) + 4096, &err)) return fail(CTCDEC_ERR_DEVICE, err);
-
-  std::vector<int64_t> row0((size_t)n_utts + 1, 0);
+  if (dec->h_stage.ensure((size_t)n_utts * (64 + sizeof(LmState) * (size_t)c.K) + 4096, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+  c.row0.assign((size_t)n_utts + 1, 0);
   for (int32_t u = 0; u < n_utts; ++u) {
-    if (utt_frames[u] < 0) return fail(CTCDEC_ERR_ARG, "negative frame count");
-    row0[(size_t)u + 1] = row0[(size_t)u] + utt_frames[u];
+    if (c.utt_frames[u] < 0) return fail(CTCDEC_ERR_ARG, "negative frame count");
+    c.row0[(size_t)u + 1] = c.row0[(size_t)u] + c.utt_frames[u];
   }
-  const int64_t R = row0[(size_t)n_utts];
+  c.R = c.row0[(size_t)n_utts];
+  return CTCDEC_OK;
+}
 
-  // logits: device pointers are used in place, host matrices are staged
-  std::vector<const void*> ptrs((size_t)n_utts);
-  if (is_device) {
-    for (int32_t u = 0; u < n_utts; ++u) ptrs[(size_t)u] = utt_logits[u];
+// 2. Logits: device pointers are used in place, host matrices are staged.
+static int stage_logits(DecodeCall& c) {
+  ctcdec_decoder* dec = c.dec;
+  std::string& err = c.err;
+  const int32_t n_utts = c.n_utts;
+  const size_t row_bytes = (size_t)c.V * dtype_size(c.dtype);
+  c.ptrs.resize((size_t)n_utts);
+  if (c.is_device) {
+    for (int32_t u = 0; u < n_utts; ++u) c.ptrs[(size_t)u] = c.utt_logits[u];
   } else {
-    if (dec->w_logits.ensure((size_t)std::max<int64_t>(R, 1) * V * esz, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+    if (dec->w_logits.ensure((size_t)std::max<int64_t>(c.R, 1) * row_bytes, &err)) return fail(CTCDEC_ERR_DEVICE, err);
     // (utterances that follow each other in host memory -- one [B, T, V] array -- go over in one copy)
     for (int32_t u = 0; u < n_utts;) {
-      char* dst = (char*)dec->w_logits.p + (size_t)row0[(size_t)u] * V * esz;
-      const char* src = (const char*)utt_logits[u];
-      size_t bytes = (size_t)utt_frames[u] * V * esz;
-      ptrs[(size_t)u] = dst;
+      char* dst = (char*)dec->w_logits.p + (size_t)c.row0[(size_t)u] * row_bytes;
+      const char* src = (const char*)c.utt_logits[u];
+      size_t bytes = (size_t)c.utt_frames[u] * row_bytes;
+      c.ptrs[(size_t)u] = dst;
       int32_t v = u + 1;
-      while (v < n_utts && (const char*)utt_logits[v] == src + bytes) {
-        ptrs[(size_t)v] = dst + bytes;
-        bytes += (size_t)utt_frames[v] * V * esz;
+      while (v < n_utts && (const char*)c.utt_logits[v] == src + bytes) {
+        c.ptrs[(size_t)v] = dst + bytes;
+        bytes += (size_t)c.utt_frames[v] * row_bytes;
         ++v;
       }
       if (bytes && be::h2d(dst, src, bytes, &err)) return fail(CTCDEC_ERR_DEVICE, err);
       u = v;
     }
   }
-  if (upload_staged(dec, dec->w_ptrs, ptrs, &err) || upload_staged(dec, dec->w_row0, row0, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+  if (upload_staged(dec, dec->w_ptrs, c.ptrs, &err) || upload_staged(dec, dec->w_row0, c.row0, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+  return CTCDEC_OK;
+}
 
-  // survivor bound: rows are normalised log-probabilities, so at most floor(e^-min) labels pass
-  int max_surv = V;
-  if (p->token_min_logp > log(1e-15)) {  // frames are clipped at ln(MIN_TOKEN_CLIP_P) (constants.py:17)
-    double bound = floor(exp(-p->token_min_logp)) + 2.0;
-    if (bound < (double)V) max_surv = (int)bound;
+// 3. Arenas of text nodes (one per completed-words prefix that is scored) and emission nodes (one per non-blank,
+// non-repeat step of a kept beam). The worst case is beam_width of each per frame; what a frame really takes is a
+// handful, so the usual reservation is 16 per frame (+ 2 beam_widths): an utterance that
+// outgrows it reports ST_TEXT_OVERFLOW / ST_EMIT_OVERFLOW and the beam stage is redone with the worst case, which
+// this decoder then keeps reserving. A resident stream's kernel cannot be redone: always the worst case (per chunk).
+static void size_arenas(DecodeCall& c, bool full) {
+  const uint64_t B = (uint64_t)c.B, K = (uint64_t)c.K;
+  const uint64_t per_frame = full ? B : std::min<uint64_t>(B, 16);
+  c.toff.assign((size_t)c.n_utts + 1, 0);
+  c.eoff.assign((size_t)c.n_utts + 1, 0);
+  for (int32_t u = 0; u < c.n_utts; ++u) {
+    const uint64_t T = (uint64_t)c.utt_frames[u];
+    const uint64_t n_imp = c.rs ? (uint64_t)c.rs->mirror[(size_t)u].n_carry
+                                : c.stream ? (uint64_t)(c.stream->beam_off[u + 1] - c.stream->beam_off[u]) : 0;
+    c.toff[(size_t)u + 1] = c.toff[(size_t)u] + ((T + 1) * per_frame + 2 * B + 2 + n_imp) * K;
+    c.eoff[(size_t)u + 1] = c.eoff[(size_t)u] + T * per_frame + 2 * B + 2 + n_imp;
   }
-  if (max_surv < 1) max_surv = 1;
+}
 
-  const int B = p->beam_width;
+// 4a. Resident streams: the chunk's first frames, and room for it in the streams' own emission arena (kept from their start).
+static int stage_resident_input(DecodeCall& c) {
+  ctcdec_stream* rs = c.rs;
+  std::string& err = c.err;
+  const int32_t n_utts = c.n_utts;
+  for (int32_t u = 0; u < n_utts; ++u) c.ba.max_import = std::max<int32_t>(c.ba.max_import, (int32_t)rs->mirror[(size_t)u].n_carry);
+  std::vector<int32_t> ff(c.stream->first_frame, c.stream->first_frame + n_utts);
+  if (upload(c.dec->w_ff, ff, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+  uint64_t need = 0;
+  for (int32_t u = 0; u < n_utts; ++u)
+    need = std::max<uint64_t>(need, (uint64_t)rs->mirror[(size_t)u].emit_next + (uint64_t)c.utt_frames[u] * (uint64_t)c.B +
+                                        (uint64_t)ctcdec_stream::CAP + 2);
+  if (need <= rs->emit_cap) return CTCDEC_OK;
+  // (sized for the worst case -- one node per frame and beam --, of which a real stream uses a few per cent: grow
+  // in big steps so that a long stream reallocates a handful of times)
+  const uint64_t cap = std::max<uint64_t>(std::max<uint64_t>(4 * need, 2 * rs->emit_cap), 4096);
+  DevBuf grown;  // (a failure below releases it: the stream keeps its old arena)
+  if (grown.ensure((size_t)n_utts * cap * sizeof(EmitNode), &err)) return fail(CTCDEC_ERR_DEVICE, err);
+  for (int32_t u = 0; u < n_utts && rs->emit.p; ++u) {
+    const size_t used = (size_t)rs->mirror[(size_t)u].emit_next * sizeof(EmitNode);
+    if (used && be::d2d((char*)grown.p + (size_t)u * cap * sizeof(EmitNode), (const char*)rs->emit.p + (size_t)u * rs->emit_cap * sizeof(EmitNode), used, &err))
+      return fail(CTCDEC_ERR_DEVICE, err);
+  }
+  // the new offsets first: a failure here leaves the stream on its old arena with its old stride
+  std::vector<uint64_t> eo((size_t)n_utts + 1);
+  for (int32_t u = 0; u <= n_utts; ++u) eo[(size_t)u] = (uint64_t)u * cap;
+  if (upload(rs->eoff, eo, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+  rs->emit = std::move(grown);
+  rs->emit_cap = cap;
+  return CTCDEC_OK;
+}
 
-  // Arenas of text nodes (one per completed-words prefix that is scored) and emission nodes (one per non-blank,
-  // non-repeat step of a kept beam). The worst case is beam_width of each per frame; what a frame really takes is a
-  // handful, so the usual reservation is 16 per frame (+ 2 beam_widths): an utterance that
-  // outgrows it reports ST_TEXT_OVERFLOW / ST_EMIT_OVERFLOW and the beam stage is redone with the worst case, which
-  // this decoder then keeps reserving. A resident stream's kernel cannot be redone: always the worst case (per chunk).
-  std::vector<uint64_t> toff((size_t)n_utts + 1, 0), eoff((size_t)n_utts + 1, 0);
-  bool arenas_full = rs != nullptr || dec->arenas_worst_case || getenv("CTCDEC_WORST_CASE_ARENAS") != nullptr;
-  auto size_arenas = [&](bool full) {
-    const uint64_t per_frame = full ? (uint64_t)B : std::min<uint64_t>((uint64_t)B, 16);
-    for (int32_t u = 0; u < n_utts; ++u) {
-      uint64_t T = (uint64_t)utt_frames[u];
-      uint64_t n_imp = rs ? (uint64_t)rs->mirror[(size_t)u].n_carry
-                          : stream ? (uint64_t)(stream->beam_off[u + 1] - stream->beam_off[u]) : 0;
-      toff[(size_t)u + 1] = toff[(size_t)u] + ((T + 1) * per_frame + 2 * (uint64_t)B + 2 + n_imp) * (uint64_t)K;
-      eoff[(size_t)u + 1] = eoff[(size_t)u] + T * per_frame + 2 * (uint64_t)B + 2 + n_imp;
+// 4b. Streams whose beams the caller hands in: every stream's carried-over beams, resolved on the host (build_import).
+static int stage_imports(DecodeCall& c) {
+  ctcdec_decoder* dec = c.dec;
+  const StreamIn* stream = c.stream;
+  std::string& err = c.err;
+  const int32_t n_utts = c.n_utts;
+  const int K = c.K;
+  const int64_t n_imp_total = stream->beam_off[n_utts];
+  std::vector<ImportBeam> imps((size_t)std::max<int64_t>(n_imp_total, 1));
+  std::vector<LmState> imps_x(K > 1 ? (size_t)std::max<int64_t>(n_imp_total, 1) * (size_t)(K - 1) : 0);
+  std::vector<int64_t> ioff(stream->beam_off, stream->beam_off + n_utts + 1);
+  std::vector<int32_t> ff(stream->first_frame, stream->first_frame + n_utts);
+  for (int32_t u = 0; u < n_utts; ++u) {
+    int64_t cnt = ioff[(size_t)u + 1] - ioff[(size_t)u];
+    if (cnt < 1 || cnt > beam_bucket(c.B))
+      return fail(CTCDEC_ERR_ARG, "a stream must carry between 1 and beam-capacity beams");
+    c.ba.max_import = std::max<int32_t>(c.ba.max_import, (int32_t)cnt);
+    for (int64_t k = ioff[(size_t)u]; k < ioff[(size_t)u + 1]; ++k) {
+      std::string e = build_import(dec, *stream, k, &imps[(size_t)k], K > 1 ? &imps_x[(size_t)k * (size_t)(K - 1)] : nullptr,
+                                   import_hot(dec, u));
+      if (!e.empty()) return fail(CTCDEC_ERR_ARG, e);
     }
-  };
-  size_arenas(arenas_full);
-  int n_best = p->n_best > 0 ? std::min(p->n_best, B) : B;
+  }
+  if (upload(dec->w_imp, imps, &err) || upload(dec->w_impoff, ioff, &err) || upload(dec->w_ff, ff, &err))
+    return fail(CTCDEC_ERR_DEVICE, err);
+  if (K > 1 && upload(dec->w_impx, imps_x, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+  return CTCDEC_OK;
+}
+
+// The arenas, the output records and the emission-list pool of the beam stage.
+static int reserve_beam_workspace(DecodeCall& c) {
+  ctcdec_decoder* dec = c.dec;
+  std::string& err = c.err;
+  const int32_t n_utts = c.n_utts;
   // emission lists: at most one entry per frame plus the import root and the closing entry
-  unsigned long long tok_cap = (unsigned long long)n_best * (unsigned long long)(R + 2 * (int64_t)n_utts);
-  if (rs) {
+  c.tok_cap = (unsigned long long)c.n_best * (unsigned long long)(c.R + 2 * (int64_t)n_utts);
+  if (c.rs) {
     // A resident stream's lists reach back to its start, but a beam's chain holds at most one entry per frame pushed so
     // far, one per chunk (a word closed by force_next_word) and its root -- NOT the stream's whole emission arena (every
     // beam's nodes: ten minutes of audio on 64 streams would ask for gigabytes here; round-3 advisor finding).
     unsigned long long depth = 0;
     for (int32_t u = 0; u < n_utts; ++u)
-      depth += (unsigned long long)(rs->frames[(size_t)u] + utt_frames[u] + rs->pushes + 3);
-    tok_cap = want_result ? (unsigned long long)n_best * depth : 1ull;
+      depth += (unsigned long long)(c.rs->frames[(size_t)u] + c.utt_frames[u] + c.rs->pushes + 3);
+    c.tok_cap = c.want_result ? (unsigned long long)c.n_best * depth : 1ull;
   }
-  // streaming: carried-over beams of every stream
-  const ImportBeam* d_imports = nullptr;
-  const LmState* d_import_x = nullptr;
-  int32_t max_import = 0;
-  if (rs) {
-    for (int32_t u = 0; u < n_utts; ++u) max_import = std::max<int32_t>(max_import, (int32_t)rs->mirror[(size_t)u].n_carry);
-    std::vector<int32_t> ff(stream->first_frame, stream->first_frame + n_utts);
-    if (upload(dec->w_ff, ff, &err)) return fail(CTCDEC_ERR_DEVICE, err);
-    // the emission arena of a resident stream is its own and reaches back to the start of the stream: room for this chunk
-    uint64_t need = 0;
-    for (int32_t u = 0; u < n_utts; ++u)
-      need = std::max<uint64_t>(need, (uint64_t)rs->mirror[(size_t)u].emit_next + (uint64_t)utt_frames[u] * (uint64_t)B +
-                                          (uint64_t)ctcdec_stream::CAP + 2);
-    if (need > rs->emit_cap) {
-      // (sized for the worst case -- one node per frame and beam --, of which a real stream uses a few per cent: grow
-      // in big steps so that a long stream reallocates a handful of times)
-      const uint64_t cap = std::max<uint64_t>(std::max<uint64_t>(4 * need, 2 * rs->emit_cap), 4096);
-      DevBuf grown;
-      if (grown.ensure((size_t)n_utts * cap * sizeof(EmitNode), &err)) return fail(CTCDEC_ERR_DEVICE, err);
-      for (int32_t u = 0; u < n_utts && rs->emit.p; ++u) {
-        const size_t used = (size_t)rs->mirror[(size_t)u].emit_next * sizeof(EmitNode);
-        if (used && be::d2d((char*)grown.p + (size_t)u * cap * sizeof(EmitNode), (const char*)rs->emit.p + (size_t)u * rs->emit_cap * sizeof(EmitNode), used, &err)) {
-          grown.drop();  // (the stream keeps its old arena)
-          return fail(CTCDEC_ERR_DEVICE, err);
-        }
-      }
-      // the new offsets first: a failure here leaves the stream on its old arena with its old stride
-      std::vector<uint64_t> eo((size_t)n_utts + 1);
-      for (int32_t u = 0; u <= n_utts; ++u) eo[(size_t)u] = (uint64_t)u * cap;
-      if (upload(rs->eoff, eo, &err)) {
-        grown.drop();
-        return fail(CTCDEC_ERR_DEVICE, err);
-      }
-      rs->emit.drop();
-      rs->emit = grown;
-      rs->emit_cap = cap;
-    }
-  } else if (stream) {
-    const int64_t n_imp_total = stream->beam_off[n_utts];
-    std::vector<ImportBeam> imps((size_t)std::max<int64_t>(n_imp_total, 1));
-    std::vector<LmState> imps_x(K > 1 ? (size_t)std::max<int64_t>(n_imp_total, 1) * (size_t)(K - 1) : 0);
-    std::vector<int64_t> ioff(stream->beam_off, stream->beam_off + n_utts + 1);
-    std::vector<int32_t> ff(stream->first_frame, stream->first_frame + n_utts);
-    for (int32_t u = 0; u < n_utts; ++u) {
-      int64_t cnt = ioff[(size_t)u + 1] - ioff[(size_t)u];
-      if (cnt < 1 || cnt > shape_bw_limit(B))
-        return fail(CTCDEC_ERR_ARG, "a stream must carry between 1 and beam-capacity beams");
-      max_import = std::max<int32_t>(max_import, (int32_t)cnt);
-      for (int64_t k = ioff[(size_t)u]; k < ioff[(size_t)u + 1]; ++k) {
-        std::string e = build_import(dec, *stream, k, B, &imps[(size_t)k],
-                                     K > 1 ? &imps_x[(size_t)k * (size_t)(K - 1)] : nullptr, import_hot(dec, u));
-        if (!e.empty()) return fail(CTCDEC_ERR_ARG, e);
-      }
-    }
-    if (upload(dec->w_imp, imps, &err) || upload(dec->w_impoff, ioff, &err) || upload(dec->w_ff, ff, &err))
-      return fail(CTCDEC_ERR_DEVICE, err);
-    d_imports = (const ImportBeam*)dec->w_imp.p;
-    if (K > 1) {
-      if (upload(dec->w_impx, imps_x, &err)) return fail(CTCDEC_ERR_DEVICE, err);
-      d_import_x = (const LmState*)dec->w_impx.p;
-    }
-  }
-  if (dec->w_text.ensure(toff[(size_t)n_utts] * sizeof(TextNode), &err) ||
-      (!rs && (dec->w_emit.ensure(eoff[(size_t)n_utts] * sizeof(EmitNode), &err) || upload_staged(dec, dec->w_eoff, eoff, &err))) ||
-      upload_staged(dec, dec->w_toff, toff, &err) || dec->w_out.ensure((size_t)n_utts * n_best * sizeof(OutBeam), &err) ||
+  if (dec->w_text.ensure(c.toff[(size_t)n_utts] * sizeof(TextNode), &err) ||
+      (!c.rs && (dec->w_emit.ensure(c.eoff[(size_t)n_utts] * sizeof(EmitNode), &err) || upload_staged(dec, dec->w_eoff, c.eoff, &err))) ||
+      upload_staged(dec, dec->w_toff, c.toff, &err) || dec->w_out.ensure((size_t)n_utts * c.n_best * sizeof(OutBeam), &err) ||
       dec->w_nout.ensure((size_t)n_utts * 4, &err) || dec->w_status.ensure((size_t)n_utts * 4, &err) ||
-      dec->w_tok.ensure((size_t)std::max<unsigned long long>(tok_cap, 1) * sizeof(EmitNode), &err) ||
+      dec->w_tok.ensure((size_t)std::max<unsigned long long>(c.tok_cap, 1) * sizeof(EmitNode), &err) ||
       dec->w_head.ensure(16, &err) || dec->w_cold.ensure((size_t)n_utts * 2 * COLD_STRIDE * sizeof(ColdRec), &err))
     return fail(CTCDEC_ERR_DEVICE, err);
-  const LmState* d_start = nullptr;
-  if (stream && !rs) {
-    d_start = nullptr;  // every imported beam carries its own LM state
-  } else if (dec->has_lm) {  // (resident streams: used by the streams that are at their starting state)
-    // per utterance one state per model; a negative length (or no array) asks for the model's own default
-    std::vector<LmState> st((size_t)n_utts * K);
-    for (int32_t u = 0; u < n_utts; ++u) {
+  return CTCDEC_OK;
+}
+
+// 5. Start states: per utterance one state per model; a negative length (or no array) asks for the model's own default.
+// (Host imports: none, every beam carries its own. Resident streams: used by the streams that are at their starting state.)
+static int stage_start_states(DecodeCall& c) {
+  ctcdec_decoder* dec = c.dec;
+  const int K = c.K;
+  c.xstate_bytes = K > 1 ? (size_t)c.n_utts * c.n_best * (size_t)(K - 1) * sizeof(LmState) : 0;
+  if (!(c.stream && !c.rs) && dec->has_lm) {
+    std::vector<LmState> st((size_t)c.n_utts * K);
+    for (int32_t u = 0; u < c.n_utts; ++u) {
       for (int k = 0; k < K; ++k) {
         LmState& s = st[(size_t)u * K + k];
-        memset(&s, 0, sizeof(s));
         const HostLM& lm = K > 1 ? *dec->multi->lms[(size_t)k] : dec->lm_ref();
-        const ctcdec_lm_state* given = start_states ? &start_states[(size_t)u * K + k] : nullptr;
+        const ctcdec_lm_state* given = c.start_states ? &c.start_states[(size_t)u * K + k] : nullptr;
         if (!given || given->length < 0) {
-          const bool boundary = k == 0 ? p->lm_score_boundary != 0 : dec->x_boundary[k] != 0;
+          const bool boundary = k == 0 ? c.p->lm_score_boundary != 0 : dec->x_boundary[k] != 0;
+          memset(&s, 0, sizeof(s));
           lm.start_state(boundary, &s);
-        } else {
-          if (given->length > MAX_CTX) return fail(CTCDEC_ERR_ARG, "LM start state too long");
-          s.len = given->length;
-          for (int j = 0; j < s.len; ++j) {
-            if (given->words[j] >= lm.words.size()) return fail(CTCDEC_ERR_ARG, "bad LM state word");
-            s.words[j] = given->words[j];
-            s.backoff[j] = given->backoff[j];
-          }
+        } else if (const LmStateErr e = copy_lm_state(*given, lm.words.size(), &s)) {
+          return fail(CTCDEC_ERR_ARG, e == LM_STATE_LENGTH ? "LM start state too long" : "bad LM state word");
         }
       }
     }
-    if (upload_staged(dec, dec->w_start, st, &err)) return fail(CTCDEC_ERR_DEVICE, err);
-    d_start = (const LmState*)dec->w_start.p;
+    if (upload_staged(dec, dec->w_start, st, &c.err)) return fail(CTCDEC_ERR_DEVICE, c.err);
+    c.ba.start_states = (const LmState*)dec->w_start.p;
   }
-  const size_t xstate_bytes = K > 1 ? (size_t)n_utts * n_best * (size_t)(K - 1) * sizeof(LmState) : 0;
-  if (xstate_bytes && dec->w_xstate.ensure(xstate_bytes, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+  if (c.xstate_bytes && dec->w_xstate.ensure(c.xstate_bytes, &c.err)) return fail(CTCDEC_ERR_DEVICE, c.err);
+  return CTCDEC_OK;
+}
 
-  be::BeamArgs ba;
+// device texts: scratch per utterance -- at most one emission per frame, each a label and a separator
+static int reserve_device_texts(DecodeCall& c) {
+  ctcdec_decoder* dec = c.dec;
+  std::vector<uint64_t> soff((size_t)c.n_utts + 1, 0);
+  for (int32_t u = 0; u < c.n_utts; ++u)
+    soff[(size_t)u + 1] = soff[(size_t)u] + (((uint64_t)c.utt_frames[u] + 2) * (uint64_t)(dec->max_label_bytes + 1) + 15) / 16 * 16;
+  if (dec->w_tscr.ensure((size_t)soff[(size_t)c.n_utts] + 16, &c.err) || dec->w_tpool.ensure((size_t)soff[(size_t)c.n_utts] + 16, &c.err) ||
+      upload_staged(dec, dec->w_tsoff, soff, &c.err))
+    return fail(CTCDEC_ERR_DEVICE, c.err);
+  c.ba.text_scratch = (uint8_t*)dec->w_tscr.p;
+  c.ba.text_soff = (const uint64_t*)dec->w_tsoff.p;
+  c.ba.text_pool = (uint8_t*)dec->w_tpool.p;
+  c.ba.text_pool_cap = soff[(size_t)c.n_utts];
+  return CTCDEC_OK;
+}
+
+// ragged batches of more utterances than fit the device at once: longest first (BeamArgs::order)
+static int stage_longest_first(DecodeCall& c) {
+  const int32_t* utt_frames = c.utt_frames;
+  if (c.n_utts <= be::cus() * 2 || getenv("CTCDEC_NO_LPT_ORDER")) return CTCDEC_OK;
+  bool ragged = false;
+  for (int32_t u = 1; u < c.n_utts; ++u) ragged = ragged || utt_frames[u] != utt_frames[0];
+  if (!ragged) return CTCDEC_OK;
+  std::vector<int32_t> order((size_t)c.n_utts);
+  for (int32_t u = 0; u < c.n_utts; ++u) order[(size_t)u] = u;
+  std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return utt_frames[x] > utt_frames[y]; });
+  if (upload(c.dec->w_order, order, &c.err)) return fail(CTCDEC_ERR_DEVICE, c.err);
+  c.ba.order = (const int32_t*)c.dec->w_order.p;
+  return CTCDEC_OK;
+}
+
+// 6. The beam stage's arguments (the survivor lists and the wave kernel's payload follow per prune attempt: beam_ready).
+static int fill_beam_args(DecodeCall& c) {
+  ctcdec_decoder* dec = c.dec;
+  const ctcdec_params* p = c.p;
+  const StreamIn* stream = c.stream;
+  ctcdec_stream* rs = c.rs;
+  be::BeamArgs& ba = c.ba;
   device_tables(dec, &ba.tables);
   DecodeParams& dp = ba.params;
   memset(&dp, 0, sizeof(dp));
-  dp.beam_width = B;
+  dp.beam_width = c.B;
   dp.prune_history = p->prune_history ? 1 : 0;
-  dp.n_best = n_best;
+  dp.n_best = c.n_best;
   dp.first_frame = p->first_frame;
   dp.beam_prune_logp = p->beam_prune_logp;
   dp.token_min_logp = p->token_min_logp;
@@ -1223,101 +1262,118 @@ static int decode_impl(ctcdec_decoder* dec, const void* const* utt_logits, const
   dp.no_label_runs = getenv("CTCDEC_NO_LABEL_RUNS") != nullptr ? 1 : 0;
   // decode_batch: the kernels assemble the best beam's text themselves (CTCDEC_HOST_REPLAY=1: the emission lists come
   // back and the host replays them, as for every other call)
-  const bool device_texts = p->texts_only != 0 && p->token_frames == 0 && n_best == 1 && !stream && getenv("CTCDEC_HOST_REPLAY") == nullptr;
-  dp.texts_only = device_texts ? 1 : 0;
-  ba.n_utts = n_utts;
+  c.device_texts = p->texts_only != 0 && p->token_frames == 0 && c.n_best == 1 && !stream && getenv("CTCDEC_HOST_REPLAY") == nullptr;
+  dp.texts_only = c.device_texts ? 1 : 0;
+  ba.n_utts = c.n_utts;
   ba.utt_row0 = (const int64_t*)dec->w_row0.p;
-  ba.surv_cnt = (const uint32_t*)dec->w_scnt.p;
-  ba.surv_id = (const uint16_t*)dec->w_sid.p;
-  ba.surv_lp = (const double*)dec->w_slp.p;
   ba.text_nodes = (TextNode*)dec->w_text.p;
-  ba.emit_nodes = (EmitNode*)dec->w_emit.p;
   ba.text_off = (const uint64_t*)dec->w_toff.p;
-  ba.emit_off = (const uint64_t*)dec->w_eoff.p;
-  ba.start_states = d_start;
-  ba.out_xstates = xstate_bytes ? (LmState*)dec->w_xstate.p : nullptr;
+  ba.out_xstates = c.xstate_bytes ? (LmState*)dec->w_xstate.p : nullptr;
   ba.out = (OutBeam*)dec->w_out.p;
-  ba.out_stride = n_best;
+  ba.out_stride = c.n_best;
   ba.n_out = (uint32_t*)dec->w_nout.p;
   ba.status = (uint32_t*)dec->w_status.p;
   ba.tok_pool = (EmitNode*)dec->w_tok.p;
   ba.tok_pool_head = (unsigned long long*)dec->w_head.p;
-  ba.tok_pool_cap = tok_cap;
-  ba.prof = nullptr;
-  ba.imports = d_imports;
-  ba.import_xstates = d_import_x;
-  ba.import_off = (stream && !rs) ? (const int64_t*)dec->w_impoff.p : nullptr;
+  ba.tok_pool_cap = c.tok_cap;
   ba.first_frames = stream ? (const int32_t*)dec->w_ff.p : nullptr;
   ba.cold = (ColdRec*)dec->w_cold.p;
-  ba.max_import = max_import;
-  ba.text_scratch = nullptr;
-  ba.text_soff = nullptr;
-  ba.text_pool = nullptr;
-  ba.text_pool_cap = 0;
-  if (device_texts) {
-    // scratch per utterance: at most one emission per frame, each a label and a separator
-    std::vector<uint64_t> soff((size_t)n_utts + 1, 0);
-    for (int32_t u = 0; u < n_utts; ++u)
-      soff[(size_t)u + 1] = soff[(size_t)u] + (((uint64_t)utt_frames[u] + 2) * (uint64_t)(dec->max_label_bytes + 1) + 15) / 16 * 16;
-    if (dec->w_tscr.ensure((size_t)soff[(size_t)n_utts] + 16, &err) || dec->w_tpool.ensure((size_t)soff[(size_t)n_utts] + 16, &err) ||
-        upload_staged(dec, dec->w_tsoff, soff, &err))
-      return fail(CTCDEC_ERR_DEVICE, err);
-    ba.text_scratch = (uint8_t*)dec->w_tscr.p;
-    ba.text_soff = (const uint64_t*)dec->w_tsoff.p;
-    ba.text_pool = (uint8_t*)dec->w_tpool.p;
-    ba.text_pool_cap = soff[(size_t)n_utts];
-  }
-  ba.carry_out = nullptr;
-  ba.carry_xstates = nullptr;
-  ba.sstate = nullptr;
-  ba.carry_stride = 0;
   ba.want_out = 1;
-  ba.resident_in = 0;
-  // ragged batches of more utterances than fit the device at once: longest first (BeamArgs::order)
-  ba.order = nullptr;
-  if (n_utts > be::cus() * 2 && !getenv("CTCDEC_NO_LPT_ORDER")) {
-    bool ragged = false;
-    for (int32_t u = 1; u < n_utts; ++u) ragged = ragged || utt_frames[u] != utt_frames[0];
-    if (ragged) {
-      std::vector<int32_t> order((size_t)n_utts);
-      for (int32_t u = 0; u < n_utts; ++u) order[(size_t)u] = u;
-      std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return utt_frames[x] > utt_frames[y]; });
-      if (upload(dec->w_order, order, &err)) return fail(CTCDEC_ERR_DEVICE, err);
-      ba.order = (const int32_t*)dec->w_order.p;
-    }
-  }
+  ba.total_rows = c.R;
+  if (c.device_texts)
+    if (int rc = reserve_device_texts(c)) return rc;
+  if (int rc = stage_longest_first(c)) return rc;
+  // where the emission nodes go and where the carried-over beams come from
   if (rs) {
     ba.emit_nodes = (EmitNode*)rs->emit.p;
     ba.emit_off = (const uint64_t*)rs->eoff.p;
     ba.imports = (const ImportBeam*)rs->carry.p;
-    ba.import_xstates = K > 1 ? (const LmState*)rs->carry_x.p : nullptr;
-    ba.import_off = nullptr;
+    ba.import_xstates = c.K > 1 ? (const LmState*)rs->carry_x.p : nullptr;
     ba.resident_in = 1;
     ba.carry_out = (ImportBeam*)rs->carry.p;
-    ba.carry_xstates = K > 1 ? (LmState*)rs->carry_x.p : nullptr;
+    ba.carry_xstates = c.K > 1 ? (LmState*)rs->carry_x.p : nullptr;
     ba.sstate = (StreamState*)rs->sstate.p;
     ba.carry_stride = ctcdec_stream::CAP;
-    ba.want_out = want_result ? 1 : 0;
+    ba.want_out = c.want_result ? 1 : 0;
+  } else {
+    ba.emit_nodes = (EmitNode*)dec->w_emit.p;
+    ba.emit_off = (const uint64_t*)dec->w_eoff.p;
+    if (stream) {
+      ba.imports = (const ImportBeam*)dec->w_imp.p;
+      ba.import_xstates = c.K > 1 ? (const LmState*)dec->w_impx.p : nullptr;
+      ba.import_off = (const int64_t*)dec->w_impoff.p;
+    }
   }
   if (dec->profile) {
-    if (dec->w_prof.ensure(N_PROF * 8, &err) || be::zero(dec->w_prof.p, N_PROF * 8, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+    if (dec->w_prof.ensure(N_PROF * 8, &c.err) || be::zero(dec->w_prof.p, N_PROF * 8, &c.err)) return fail(CTCDEC_ERR_DEVICE, c.err);
     ba.prof = (unsigned long long*)dec->w_prof.p;
   }
-  // Everything the beam stage needs is staged BEFORE the prune stage is launched, and the beam kernel is
-  // queued right behind it on the same stream: the host never sits between the two kernels. The two
-  // rare events the prune stage can report (probability-like input, survivor overflow) are read back
-  // afterwards and simply redo the affected stage(s).
-  if (dec->w_flags.ensure(32, &err) || dec->w_head.ensure(16, &err)) return fail(CTCDEC_ERR_DEVICE, err);
-  ba.surv_x16 = 0;
-  ba.total_rows = R;
+  if (dec->w_flags.ensure(32, &c.err) || dec->w_head.ensure(16, &c.err)) return fail(CTCDEC_ERR_DEVICE, c.err);
   // Small batches choose their beam kernel by the input (backend: wave_kernel_chosen): their beam stage is launched when the
   // prune stage has reported -- like a resident stream's --, one small read-back between the two stages.
-  auto t_setup = t_begin, t_queued = t_begin, t_flags = t_begin;  // (CTCDEC_HOST_TIMING: where the host side of a call goes)
-  const bool by_input = !rs && be::beam_kernel_depends_on_input(ba);
-  const bool late_beam = rs != nullptr || by_input;
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    size_t rows = (size_t)std::max<int64_t>(R, 1);
-    if (dec->w_rowsum.ensure(rows * 8, &err) || dec->w_isprob.ensure((size_t)n_utts * 4, &err) ||
+  c.by_input = !rs && be::beam_kernel_depends_on_input(ba);
+  c.late_beam = rs != nullptr || c.by_input;
+  return CTCDEC_OK;
+}
+
+// the wave kernel's payload lines (one per candidate a frame can push into its pool)
+static int reserve_pay(DecodeCall& c) {
+  be::BeamArgs& ba = c.ba;
+  ba.pay = nullptr;
+  ba.pay_stride = 0;
+  if (be::wave_kernel_chosen(ba)) {  // reserved only for launches that will use it (2 GB at the bench size)
+    ba.pay_stride = (uint64_t)wave_pay_stride(ba.params);
+    if (c.dec->w_pay.ensure((size_t)c.n_utts * (size_t)ba.pay_stride * sizeof(PoolPay), &c.err)) return fail(CTCDEC_ERR_DEVICE, c.err);
+    ba.pay = (PoolPay*)c.dec->w_pay.p;
+  }
+  return CTCDEC_OK;
+}
+
+static int run_beam(DecodeCall& c) {
+  if (be::zero(c.dec->w_head.p, 16, &c.err)) return fail(CTCDEC_ERR_DEVICE, c.err);
+  // per-utterance hot words: built and sent here, behind the first prune launch -- the host builds the tables while the
+  // prune stage runs
+  if (c.dec->hot_call.armed && !c.ba.hot_sets && upload_hot_sets(c.dec, &c.ba, &c.err)) return fail(CTCDEC_ERR_DEVICE, c.err);
+  if (be::launch_beam(c.ba, &c.err)) return fail(CTCDEC_ERR_DEVICE, c.err);
+  return CTCDEC_OK;
+}
+
+// A prune attempt's survivor lists are reserved, max_surv wide: the beam stage reads them (and sizes its payload by them).
+static int beam_ready(DecodeCall& c, int max_surv) {
+  c.ba.surv_cnt = (const uint32_t*)c.dec->w_scnt.p;
+  c.ba.surv_id = (const uint16_t*)c.dec->w_sid.p;
+  c.ba.surv_lp = (const double*)c.dec->w_slp.p;
+  c.ba.params.max_surv = max_surv;
+  return c.by_input ? CTCDEC_OK : reserve_pay(c);
+}
+
+// survivor bound: rows are normalised log-probabilities, so at most floor(e^-min) labels pass
+static int max_surv_bound(double token_min_logp, int V) {
+  int max_surv = V;
+  if (token_min_logp > log(1e-15)) {  // frames are clipped at ln(MIN_TOKEN_CLIP_P) (constants.py:17)
+    double bound = floor(exp(-token_min_logp)) + 2.0;
+    if (bound < (double)V) max_surv = (int)bound;
+  }
+  return max_surv < 1 ? 1 : max_surv;
+}
+
+// The frame-prune stage: pass 0 (every utterance as logits), the exact probability test for the utterances pass 0 marked
+// ambiguous, pass 1 for the probability-like ones, and -- un-normalised probability rows can exceed the survivor bound -- all
+// of it again at full width. `beam`: the decode whose beam stage reads the lists, or nullptr (ctcdec_frame_survivors).
+// Everything the beam stage needs is staged BEFORE the prune launch and the beam kernel is queued right behind it on the same
+// stream: the host never sits between the two kernels. The two rare events (probability-like input, survivor overflow) are read
+// back afterwards and simply redo the affected stage(s). (late_beam -- resident streams, whose kernel advances persistent state,
+// and small batches, whose kernel is chosen by what the prune stage counted -- launch it once the stage has reported.)
+static int prune_stage(PruneStage& s, DecodeCall* beam) {
+  ctcdec_decoder* dec = s.dec;
+  std::string err;
+  const int V = s.V;
+  const size_t rows = (size_t)std::max<int64_t>(s.R, 1);
+  uint32_t* flags = s.flags;
+  s.max_surv = max_surv_bound(s.token_min_logp, V);
+  for (int attempt = 0;; ++attempt) {
+    const size_t max_surv = (size_t)s.max_surv;
+    if (dec->w_rowsum.ensure(rows * 8, &err) || dec->w_isprob.ensure((size_t)s.n_utts * 4, &err) ||
         dec->w_scnt.ensure(rows * 4, &err) || dec->w_sid.ensure(rows * max_surv * 2, &err) ||
         dec->w_slp.ensure(rows * max_surv * 8, &err) || dec->w_flags.ensure(32, &err) || dec->w_slow.ensure(rows * 4, &err))
       return fail(CTCDEC_ERR_DEVICE, err);
@@ -1325,12 +1381,12 @@ static int decode_impl(ctcdec_decoder* dec, const void* const* utt_logits, const
     be::PruneArgs pa;
     pa.utt_logits = (const void* const*)dec->w_ptrs.p;
     pa.utt_row0 = (const int64_t*)dec->w_row0.p;
-    pa.n_utts = n_utts;
-    pa.n_rows = R;
+    pa.n_utts = s.n_utts;
+    pa.n_rows = s.R;
     pa.n_labels = V;
-    pa.dtype = dtype;
-    pa.token_min_logp = p->token_min_logp;
-    pa.max_surv = max_surv;
+    pa.dtype = s.dtype;
+    pa.token_min_logp = s.token_min_logp;
+    pa.max_surv = s.max_surv;
     pa.row_sum = (double*)dec->w_rowsum.p;
     pa.utt_is_prob = (uint32_t*)dec->w_isprob.p;
     pa.surv_cnt = (uint32_t*)dec->w_scnt.p;
@@ -1340,55 +1396,34 @@ static int decode_impl(ctcdec_decoder* dec, const void* const* utt_logits, const
     pa.pass = 0;
     pa.row_base = 0;
     pa.slow_rows = (uint32_t*)dec->w_slow.p;
-    pa.utt_side = dec->slicing ? (uint32_t*)dec->w_side.p : nullptr;
-    pa.utt_sum = dec->slicing ? (double*)((char*)dec->w_side.p + (((size_t)n_utts * 4 + 15) & ~(size_t)15)) : nullptr;
+    const bool sliced = beam && dec->slicing;  // (time-sliced host ingest: each slice's side of 1 is noted for decode_host_sliced)
+    pa.utt_side = sliced ? (uint32_t*)dec->w_side.p : nullptr;
+    pa.utt_sum = sliced ? (double*)((char*)dec->w_side.p + (((size_t)s.n_utts * 4 + 15) & ~(size_t)15)) : nullptr;
     pa.dense_hint = 0;
-    if (dec->dense_calls > 0 && !rs) {
+    if (beam && dec->dense_calls > 0 && !s.resident) {
       pa.dense_hint = 1;
       if (attempt == 0) --dec->dense_calls;
     }
     pa.rows_aligned16 = 1;
     pa.rows_aligned4 = 1;
-    for (const void* q : ptrs) {
+    for (const void* q : *s.ptrs) {
       if (((uintptr_t)q & 15u) != 0) pa.rows_aligned16 = 0;
       if (((uintptr_t)q & 3u) != 0) pa.rows_aligned4 = 0;
     }
-    ba.surv_cnt = (const uint32_t*)dec->w_scnt.p;
-    ba.surv_id = (const uint16_t*)dec->w_sid.p;
-    ba.surv_lp = (const double*)dec->w_slp.p;
-    dp.max_surv = max_surv;
-    // the wave kernel's payload lines (one per candidate a frame can push into its pool)
-    auto reserve_pay = [&]() -> int {
-      ba.pay = nullptr;
-      ba.pay_stride = 0;
-      if (be::wave_kernel_chosen(ba)) {  // reserved only for launches that will use it (2 GB at the bench size)
-        ba.pay_stride = (uint64_t)wave_pay_stride(dp);
-        if (dec->w_pay.ensure((size_t)n_utts * (size_t)ba.pay_stride * sizeof(PoolPay), &err)) return -1;
-        ba.pay = (PoolPay*)dec->w_pay.p;
-      }
-      return 0;
-    };
-    if (!by_input && reserve_pay()) return fail(CTCDEC_ERR_DEVICE, err);
-    auto run_beam = [&]() -> int {
-      if (be::zero(dec->w_head.p, 16, &err)) return -1;
-      // per-utterance hot words: built and sent here, behind the first prune launch -- the host builds the tables while the
-      // prune stage runs
-      if (dec->hot_call.armed && !ba.hot_sets && upload_hot_sets(dec, &ba, &err)) return -1;
-      return be::launch_beam(ba, &err);
-    };
-    // (a resident stream's beam kernel advances persistent state: it is launched once, when the prune stage has
-    // reported -- and so is a small batch's, whose kernel is chosen by what the prune stage counted; everything else
-    // launches it right behind the first prune pass and redoes it in the two rare cases)
-    t_setup = std::chrono::steady_clock::now();
-    if (be::launch_prune(pa, &err) || (!late_beam && run_beam())) return fail(CTCDEC_ERR_DEVICE, err);
-    t_queued = std::chrono::steady_clock::now();
-    uint32_t flags[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (beam)
+      if (int rc = beam_ready(*beam, s.max_surv)) return rc;
+    const bool early_beam = beam && !beam->late_beam;
+    s.t_setup = Clock::now();
+    if (be::launch_prune(pa, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+    if (early_beam)
+      if (int rc = run_beam(*beam)) return rc;
+    s.t_queued = Clock::now();
     if (be::d2h(flags, dec->w_flags.p, 32, &err)) return fail(CTCDEC_ERR_DEVICE, err);
-    t_flags = std::chrono::steady_clock::now();
-    uint32_t surv_total = flags[4];  // (pass 0 counted every row as logits)
+    s.t_flags = Clock::now();
+    s.surv_total = flags[4];  // (pass 0 counted every row as logits)
     // small vocabularies fed flat logits: nearly every row overflows the 64-rows-per-wave kernel's sixteen candidates and is done
     // again by the per-row kernel -- the next sixteen calls go there directly (then the fast kernel is tried again)
-    if (V <= 128 && R >= 1024 && (uint64_t)flags[3] * 2 > (uint64_t)R) dec->dense_calls = 16;
+    if (beam && V <= 128 && s.R >= 1024 && (uint64_t)flags[3] * 2 > (uint64_t)s.R) dec->dense_calls = 16;
     if (flags[2]) {  // rows that sum to about 1: the reference's test in its own dtype and summation order (decoder.py:760)
       if (be::launch_sniff_exact(pa, &err) || be::d2h(flags, dec->w_flags.p, 16, &err)) return fail(CTCDEC_ERR_DEVICE, err);
     }
@@ -1396,134 +1431,249 @@ static int decode_impl(ctcdec_decoder* dec, const void* const* utt_logits, const
       pa.pass = 1;
       // pass-0 overflows of those rows are void, and so is its survivor count (flags[4]: the pass counts them again)
       if (be::zero(dec->w_flags.p, 4, &err) || be::zero((char*)dec->w_flags.p + 16, 4, &err)) return fail(CTCDEC_ERR_DEVICE, err);
-      if (be::launch_prune(pa, &err) || (!late_beam && run_beam())) return fail(CTCDEC_ERR_DEVICE, err);
+      if (be::launch_prune(pa, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+      if (early_beam)
+        if (int rc = run_beam(*beam)) return rc;
       if (be::d2h(flags, dec->w_flags.p, 32, &err)) return fail(CTCDEC_ERR_DEVICE, err);
-      surv_total = flags[4];
+      s.surv_total = flags[4];
     }
-    const uint32_t ovf = flags[0];
-    if (!ovf) {
-      if (by_input) {
-        const double mean = R > 0 ? (double)surv_total / (double)R : 0.0;
-        ba.surv_x16 = (int32_t)std::min(1.0e6, std::max(1.0, mean * 16.0 + 0.5));
-        if (reserve_pay()) return fail(CTCDEC_ERR_DEVICE, err);
-      }
-      if (late_beam && run_beam()) return fail(CTCDEC_ERR_DEVICE, err);
-      break;
-    }
-    if (max_surv == V) return fail(CTCDEC_ERR_INTERNAL, "survivor overflow at full vocabulary");
-    max_surv = V;  // un-normalised probability rows can exceed the bound: redo at full width
+    if (!flags[0]) return CTCDEC_OK;
+    if (s.max_surv == V) return fail(CTCDEC_ERR_INTERNAL, "survivor overflow at full vocabulary");
+    s.max_surv = V;  // un-normalised probability rows can exceed the bound: redo at full width
   }
+}
 
-  if (after_launch && *after_launch && (*after_launch)(&err)) return fail(CTCDEC_ERR_DEVICE, err);
-  // results back (page-locked staging: the token pool is a few MB per batch)
-  const bool host_timing = getenv("CTCDEC_HOST_TIMING") != nullptr;
-  auto t_launch = std::chrono::steady_clock::now();
-  if (dec->h_small.ensure((size_t)n_utts * 8 + 16, &err) ||
-      dec->h_out.ensure((size_t)n_utts * n_best * sizeof(OutBeam), &err))
+// 7. Prune and launch: the prune stage with the beam stage queued right behind it, or -- late_beam -- once it has reported.
+static int prune_and_launch(DecodeCall& c) {
+  PruneStage& s = c.prune;
+  s = PruneStage{c.dec, &c.ptrs, c.n_utts, c.dtype, c.R, c.V, c.p->token_min_logp, c.rs != nullptr};
+  s.t_setup = s.t_queued = s.t_flags = c.t_begin;
+  if (int rc = prune_stage(s, &c)) return rc;
+  if (c.by_input) {
+    const double mean = c.R > 0 ? (double)s.surv_total / (double)c.R : 0.0;
+    c.ba.surv_x16 = (int32_t)std::min(1.0e6, std::max(1.0, mean * 16.0 + 0.5));
+    if (int rc = reserve_pay(c)) return rc;
+  }
+  return c.late_beam ? run_beam(c) : CTCDEC_OK;
+}
+
+// (rare: flat posteriors that complete a word for every beam in every frame) the beam stage again, with the worst case reserved
+static int redo_outgrown(DecodeCall& c) {
+  ctcdec_decoder* dec = c.dec;
+  std::string& err = c.err;
+  const int32_t n_utts = c.n_utts;
+  if (getenv("CTCDEC_ARENA_TRACE")) fprintf(stderr, "[ctcdec host] node arenas outgrown: beam stage redone with the worst case\n");
+  dec->arenas_worst_case = true;
+  c.arenas_full = true;
+  c.outgrown_redone = true;
+  size_arenas(c, true);
+  if (dec->w_text.ensure(c.toff[(size_t)n_utts] * sizeof(TextNode), &err) ||
+      dec->w_emit.ensure(c.eoff[(size_t)n_utts] * sizeof(EmitNode), &err) || upload(dec->w_toff, c.toff, &err) ||
+      upload(dec->w_eoff, c.eoff, &err))
     return fail(CTCDEC_ERR_DEVICE, err);
-  uint32_t* n_out = (uint32_t*)dec->h_small.p;
-  uint32_t* status = n_out + n_utts;
-  unsigned long long head = 0;
+  c.ba.text_nodes = (TextNode*)dec->w_text.p;
+  c.ba.emit_nodes = (EmitNode*)dec->w_emit.p;
+  c.ba.text_off = (const uint64_t*)dec->w_toff.p;
+  c.ba.emit_off = (const uint64_t*)dec->w_eoff.p;
+  if (be::zero(dec->w_head.p, 16, &err) || be::launch_beam(c.ba, &err) ||
+      be::d2h(c.n_out, dec->w_nout.p, (size_t)n_utts * 4, &err) || be::d2h(c.status, dec->w_status.p, (size_t)n_utts * 4, &err) ||
+      be::d2h(&c.head, dec->w_head.p, 8, &err))
+    return fail(CTCDEC_ERR_DEVICE, err);
+  return CTCDEC_OK;
+}
+
+// the streams have moved on, whatever the chunk's outcome: the host mirrors of their counters
+static int refresh_stream_mirrors(DecodeCall& c) {
+  ctcdec_stream* rs = c.rs;
+  if (be::d2h(rs->mirror.data(), rs->sstate.p, (size_t)c.n_utts * sizeof(StreamState), &c.err)) return fail(CTCDEC_ERR_DEVICE, c.err);
+  for (int32_t u = 0; u < c.n_utts; ++u) rs->frames[(size_t)u] += c.utt_frames[u];
+  rs->pushes += 1;
+  if (c.stream->eos) {  // decoder.py:681-728 with is_end: the next chunk starts a new utterance
+    for (auto& m : rs->mirror) {
+      m.n_carry = 0;
+      m.emit_next = 1;
+      m.status = 0;
+    }
+    if (be::h2d(rs->sstate.p, rs->mirror.data(), (size_t)c.n_utts * sizeof(StreamState), &c.err)) return fail(CTCDEC_ERR_DEVICE, c.err);
+    rs->has_import = false;
+    std::fill(rs->frames.begin(), rs->frames.end(), 0);
+    rs->pushes = 0;
+  }
+  return CTCDEC_OK;
+}
+
+// 8. The beam stage's counters back (page-locked staging), the outgrown-arena redo, the streams' mirrors, the refusals.
+static int collect_counters(DecodeCall& c) {
+  ctcdec_decoder* dec = c.dec;
+  std::string& err = c.err;
+  const int32_t n_utts = c.n_utts;
+  c.t_launch = Clock::now();
+  if (dec->h_small.ensure((size_t)n_utts * 8 + 16, &err) ||
+      dec->h_out.ensure((size_t)n_utts * c.n_best * sizeof(OutBeam), &err))
+    return fail(CTCDEC_ERR_DEVICE, err);
+  c.n_out = (uint32_t*)dec->h_small.p;
+  c.status = c.n_out + n_utts;
   // (one wait for the three: the targets are page-locked, `heads` rides in the spare 16 bytes behind the status words)
-  unsigned long long* heads_pinned = (unsigned long long*)(status + n_utts);
-  if (be::d2h_async(n_out, dec->w_nout.p, (size_t)n_utts * 4, &err) ||
-      be::d2h_async(status, dec->w_status.p, (size_t)n_utts * 4, &err) || be::d2h_async(heads_pinned, dec->w_head.p, 16, &err) ||
+  c.heads_pinned = (unsigned long long*)(c.status + n_utts);
+  if (be::d2h_async(c.n_out, dec->w_nout.p, (size_t)n_utts * 4, &err) ||
+      be::d2h_async(c.status, dec->w_status.p, (size_t)n_utts * 4, &err) || be::d2h_async(c.heads_pinned, dec->w_head.p, 16, &err) ||
       be::sync(&err))
     return fail(CTCDEC_ERR_DEVICE, err);
-  head = heads_pinned[0];
-  bool outgrown_redone = false;
-  if (!arenas_full) {
+  c.head = c.heads_pinned[0];
+  if (!c.arenas_full) {
     bool outgrown = false;
-    for (int32_t u = 0; u < n_utts; ++u) outgrown = outgrown || (status[u] & (ST_TEXT_OVERFLOW | ST_EMIT_OVERFLOW)) != 0;
-    if (outgrown) {  // (rare: flat posteriors that complete a word for every beam in every frame) the beam stage again,
-      // with the worst case reserved
-      if (getenv("CTCDEC_ARENA_TRACE")) fprintf(stderr, "[ctcdec host] node arenas outgrown: beam stage redone with the worst case\n");
-      dec->arenas_worst_case = true;
-      arenas_full = true;
-      outgrown_redone = true;
-      size_arenas(true);
-      if (dec->w_text.ensure(toff[(size_t)n_utts] * sizeof(TextNode), &err) ||
-          dec->w_emit.ensure(eoff[(size_t)n_utts] * sizeof(EmitNode), &err) || upload(dec->w_toff, toff, &err) ||
-          upload(dec->w_eoff, eoff, &err))
-        return fail(CTCDEC_ERR_DEVICE, err);
-      ba.text_nodes = (TextNode*)dec->w_text.p;
-      ba.emit_nodes = (EmitNode*)dec->w_emit.p;
-      ba.text_off = (const uint64_t*)dec->w_toff.p;
-      ba.emit_off = (const uint64_t*)dec->w_eoff.p;
-      if (be::zero(dec->w_head.p, 16, &err) || be::launch_beam(ba, &err) ||
-          be::d2h(n_out, dec->w_nout.p, (size_t)n_utts * 4, &err) || be::d2h(status, dec->w_status.p, (size_t)n_utts * 4, &err) ||
-          be::d2h(&head, dec->w_head.p, 8, &err))
-        return fail(CTCDEC_ERR_DEVICE, err);
-    }
+    for (int32_t u = 0; u < n_utts; ++u) outgrown = outgrown || (c.status[u] & (ST_TEXT_OVERFLOW | ST_EMIT_OVERFLOW)) != 0;
+    if (outgrown)
+      if (int rc = redo_outgrown(c)) return rc;
   }
-  auto t_kernel = std::chrono::steady_clock::now();
-  if (rs) {  // the streams have moved on, whatever the chunk's outcome: refresh the mirrors first
-    if (be::d2h(rs->mirror.data(), rs->sstate.p, (size_t)n_utts * sizeof(StreamState), &err)) return fail(CTCDEC_ERR_DEVICE, err);
-    for (int32_t u = 0; u < n_utts; ++u) rs->frames[(size_t)u] += utt_frames[u];
-    rs->pushes += 1;
-    if (stream->eos) {  // decoder.py:681-728 with is_end: the next chunk starts a new utterance
-      for (auto& m : rs->mirror) {
-        m.n_carry = 0;
-        m.emit_next = 1;
-        m.status = 0;
-      }
-      if (be::h2d(rs->sstate.p, rs->mirror.data(), (size_t)n_utts * sizeof(StreamState), &err)) return fail(CTCDEC_ERR_DEVICE, err);
-      rs->has_import = false;
-      std::fill(rs->frames.begin(), rs->frames.end(), 0);
-      rs->pushes = 0;
-    }
-  }
+  c.t_kernel = Clock::now();
+  if (c.rs)
+    if (int rc = refresh_stream_mirrors(c)) return rc;
   for (int32_t u = 0; u < n_utts; ++u)
-    if (status[u] & ST_NO_BEAMS)  // the reference: ValueError from max([]) (decoder.py:545 / :585)
+    if (c.status[u] & ST_NO_BEAMS)  // the reference: ValueError from max([]) (decoder.py:545 / :585)
       return fail(CTCDEC_ERR_ARG, "max() arg is an empty sequence (utterance " + std::to_string(u) +
                                       ": no beam survived -- non-finite scores or a positive beam_prune_logp)");
   for (int32_t u = 0; u < n_utts; ++u)
-    if (status[u]) return fail(CTCDEC_ERR_INTERNAL, "beam kernel status " + std::to_string(status[u]) +
-                                                        " for utterance " + std::to_string(u));
-  if (device_texts) {  // one block of text per utterance, written by the kernels
-    unsigned long long heads[2] = {heads_pinned[0], heads_pinned[1]};  // (read back with the counters above)
-    if (outgrown_redone && be::d2h(heads, dec->w_head.p, 16, &err)) return fail(CTCDEC_ERR_DEVICE, err);
-    res->device_texts = true;
-    res->dev_out.resize((size_t)n_utts);
-    res->dev_texts.resize((size_t)heads[1]);
-    if (be::d2h(res->dev_out.data(), dec->w_out.p, (size_t)n_utts * sizeof(OutBeam), &err) ||
-        (heads[1] && be::d2h(&res->dev_texts[0], dec->w_tpool.p, (size_t)heads[1], &err)))
+    if (c.status[u]) return fail(CTCDEC_ERR_INTERNAL, "beam kernel status " + std::to_string(c.status[u]) +
+                                                          " for utterance " + std::to_string(u));
+  return CTCDEC_OK;
+}
+
+// The closing step of every result form. When the beam stage's output is back: the kernels' times, the profile counters ...
+static int kernel_stats(DecodeCall& c) {
+  ctcdec_result* res = c.res.get();
+  be::last_timing(&res->ms[0], &res->ms[1]);
+  res->beam_kernel = be::last_beam_kernel();
+  if (c.dec->profile && be::d2h(c.dec->prof, c.dec->w_prof.p, N_PROF * 8, &c.err)) return fail(CTCDEC_ERR_DEVICE, c.err);
+  return CTCDEC_OK;
+}
+// ... and at the end of the host's work the call's own time; the result is the caller's from here on.
+static void close_call(DecodeCall& c) {
+  c.t_end = Clock::now();
+  c.res->ms[2] = ms(c.t_begin, c.t_end);
+  *c.out = c.res.release();
+}
+
+// 9a. One block of text per utterance, written by the kernels.
+static int finish_device_texts(DecodeCall& c) {
+  ctcdec_result* res = c.res.get();
+  std::string& err = c.err;
+  unsigned long long heads[2] = {c.heads_pinned[0], c.heads_pinned[1]};  // (read back with the counters)
+  if (c.outgrown_redone && be::d2h(heads, c.dec->w_head.p, 16, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+  res->device_texts = true;
+  res->dev_out.resize((size_t)c.n_utts);
+  res->dev_texts.resize((size_t)heads[1]);
+  if (be::d2h(res->dev_out.data(), c.dec->w_out.p, (size_t)c.n_utts * sizeof(OutBeam), &err) ||
+      (heads[1] && be::d2h(&res->dev_texts[0], c.dec->w_tpool.p, (size_t)heads[1], &err)))
+    return fail(CTCDEC_ERR_DEVICE, err);
+  for (int32_t u = 0; u < c.n_utts; ++u) {
+    const OutBeam& ob = res->dev_out[(size_t)u];
+    if (c.n_out[u] != 1 || (unsigned long long)ob.tok_off + ob.tok_cnt > heads[1]) return fail(CTCDEC_ERR_INTERNAL, "text pool range");
+  }
+  if (int rc = kernel_stats(c)) return rc;
+  close_call(c);
+  if (c.host_timing) {
+    const PruneStage& s = c.prune;
+    fprintf(stderr, "[ctcdec host] texts from the device: %llu bytes, native call %.3f ms (kernels %.3f + %.3f): setup %.3f, launches %.3f, "
+                    "wait for the kernels %.3f, counters back %.3f, records + texts back %.3f\n", heads[1], res->ms[2], res->ms[0], res->ms[1],
+            ms(c.t_begin, s.t_setup), ms(s.t_setup, s.t_queued), ms(s.t_queued, s.t_flags), ms(s.t_flags, c.t_kernel), ms(c.t_kernel, Clock::now()));
+  }
+  return CTCDEC_OK;
+}
+
+// 9b. A resident stream between reads: nothing to bring back.
+static int finish_stream_push(DecodeCall& c) {
+  const ctcdec_result* res = c.res.get();
+  if (int rc = kernel_stats(c)) return rc;
+  close_call(c);
+  if (c.host_timing)
+    fprintf(stderr, "[ctcdec host] stream push: setup+prune+launch %.3f ms, wait beam kernel %.3f ms, total %.3f ms (prune kernel %.3f, beam kernel %.3f)\n",
+            ms(c.t_begin, c.t_launch), ms(c.t_launch, c.t_kernel), ms(c.t_begin, Clock::now()), res->ms[0], res->ms[1]);
+  return CTCDEC_OK;
+}
+
+// 10. Token confidences: the tokens replay() has just listed go to the device as runs of rows of the survivor arrays, which
+// this call's prune stage left there (whatever max_surv the overflow redo ended with), one kernel folds each run and one
+// float64 per token comes back -- in the order of ctcdec_result_token_frames. A label that is missing from a frame's
+// survivors is a broken invariant ("Token confidences"): the call fails, there is no substitute value.
+static int token_confidences(DecodeCall& c) {
+  ctcdec_decoder* dec = c.dec;
+  ctcdec_result* res = c.res.get();
+  std::string& err = c.err;
+  const int max_surv = c.prune.max_surv;
+  double logp_ms[3] = {0, 0, 0};  // pack + upload, kernel, download
+  auto t0 = Clock::now();
+  if (c.R > (int64_t)UINT32_MAX) return fail(CTCDEC_ERR_LIMIT, "token confidences: more than 2^32 frames in one call");
+  size_t nt = 0;
+  for (const auto& beams : res->utts)
+    for (const BeamResult& b : beams) nt += b.tok.size() / 3;
+  // (packed in page-locked memory that the decoder keeps: a fresh 20 MB of pageable memory costs more than the kernel)
+  if (dec->h_truns.ensure(std::max<size_t>(nt, 1) * sizeof(TokRun), &err)) return fail(CTCDEC_ERR_DEVICE, err);
+  TokRun* runs = (TokRun*)dec->h_truns.p;
+  size_t o = 0;
+  for (int32_t u = 0; u < c.n_utts; ++u)
+    for (const BeamResult& b : res->utts[(size_t)u]) {
+      const int32_t* t = b.tok.data();
+      for (size_t k = 0, n = b.tok.size() / 3; k < n; ++k, ++o, t += 3) {
+        const int64_t s = (int64_t)t[1] - c.p->first_frame, e = (int64_t)t[2] - c.p->first_frame;
+        if (t[0] < 0 || t[0] >= c.V || s < 0 || e <= s || e > c.utt_frames[u]) return fail(CTCDEC_ERR_INTERNAL, "token frames out of range");
+        runs[o] = TokRun{(uint32_t)(c.row0[(size_t)u] + s), (uint32_t)(e - s), (uint32_t)t[0]};
+      }
+    }
+  res->tk_logp.resize(nt);
+  uint32_t missing = 0;
+#ifdef CTC_SIM  // (the simulator's device memory is host memory: the kernel's body, token by token)
+  for (size_t i = 0; i < nt; ++i) {
+    const uint32_t* cnt = (const uint32_t*)dec->w_scnt.p;
+    const uint16_t* sid = (const uint16_t*)dec->w_sid.p;
+    const double* slp = (const double*)dec->w_slp.p;
+    missing += c.fold == LOGP_MEAN  ? token_logp_of<LOGP_MEAN>(runs[i], cnt, sid, slp, (uint32_t)max_surv, &res->tk_logp[i])
+               : c.fold == LOGP_MIN ? token_logp_of<LOGP_MIN>(runs[i], cnt, sid, slp, (uint32_t)max_surv, &res->tk_logp[i])
+                                    : token_logp_of<LOGP_MAX>(runs[i], cnt, sid, slp, (uint32_t)max_surv, &res->tk_logp[i]);
+  }
+  (void)t0;
+#else
+  if (nt) {
+    if (dec->w_truns.ensure(nt * sizeof(TokRun), &err) || be::h2d(dec->w_truns.p, runs, nt * sizeof(TokRun), &err) ||
+        dec->w_tlogp.ensure(nt * 8, &err) || dec->w_tmiss.ensure(16, &err) || be::zero(dec->w_tmiss.p, 16, &err))
       return fail(CTCDEC_ERR_DEVICE, err);
-    for (int32_t u = 0; u < n_utts; ++u) {
-      const OutBeam& ob = res->dev_out[(size_t)u];
-      if (n_out[u] != 1 || (unsigned long long)ob.tok_off + ob.tok_cnt > heads[1]) return fail(CTCDEC_ERR_INTERNAL, "text pool range");
-    }
-    be::last_timing(&res->ms[0], &res->ms[1]);
-    res->beam_kernel = be::last_beam_kernel();
-    if (dec->profile && be::d2h(dec->prof, dec->w_prof.p, N_PROF * 8, &err)) return fail(CTCDEC_ERR_DEVICE, err);
-    res->ms[2] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-    if (host_timing) {
-      auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-        return std::chrono::duration<double, std::milli>(b - a).count();
-      };
-      fprintf(stderr, "[ctcdec host] texts from the device: %llu bytes, native call %.3f ms (kernels %.3f + %.3f): setup %.3f, launches %.3f, "
-                      "wait for the kernels %.3f, counters back %.3f, records + texts back %.3f\n", heads[1], res->ms[2], res->ms[0], res->ms[1],
-              ms(t_begin, t_setup), ms(t_setup, t_queued), ms(t_queued, t_flags), ms(t_flags, t_kernel), ms(t_kernel, std::chrono::steady_clock::now()));
-    }
-    *out = res.release();
-    return CTCDEC_OK;
+    be::TokenLogpArgs ta;
+    ta.runs = (const TokRun*)dec->w_truns.p;
+    ta.n_tokens = (int64_t)nt;
+    ta.fold = c.fold;
+    ta.surv_cnt = (const uint32_t*)dec->w_scnt.p;
+    ta.surv_id = (const uint16_t*)dec->w_sid.p;
+    ta.surv_lp = (const double*)dec->w_slp.p;
+    ta.max_surv = max_surv;
+    ta.out = (double*)dec->w_tlogp.p;
+    ta.missing = (uint32_t*)dec->w_tmiss.p;
+    auto t1 = Clock::now();
+    if (be::launch_token_logp(ta, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+    if (c.host_timing) logp_ms[1] = be::last_token_logp_ms();
+    auto t2 = Clock::now();
+    if (be::d2h(res->tk_logp.data(), dec->w_tlogp.p, nt * 8, &err) || be::d2h(&missing, dec->w_tmiss.p, 4, &err))
+      return fail(CTCDEC_ERR_DEVICE, err);
+    logp_ms[0] = ms(t0, t1);
+    logp_ms[2] = ms(t2, Clock::now());
   }
-  if (!want_result) {  // a resident stream between reads: nothing to bring back
-    if (host_timing) {
-      auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-        return std::chrono::duration<double, std::milli>(b - a).count();
-      };
-      double pm = 0, bm = 0;
-      be::last_timing(&pm, &bm);
-      fprintf(stderr, "[ctcdec host] stream push: setup+prune+launch %.3f ms, wait beam kernel %.3f ms, total %.3f ms (prune kernel %.3f, beam kernel %.3f)\n",
-              ms(t_begin, t_launch), ms(t_launch, t_kernel), ms(t_begin, std::chrono::steady_clock::now()), pm, bm);
-    }
-    be::last_timing(&res->ms[0], &res->ms[1]);
-    res->beam_kernel = be::last_beam_kernel();
-    res->ms[2] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-    *out = res.release();
-    return CTCDEC_OK;
-  }
+#endif
+  if (missing)
+    return fail(CTCDEC_ERR_INTERNAL, "token confidences: " + std::to_string(missing) + " token frames whose label is not among the frame's survivors");
+  res->has_logp = true;
+  if (c.host_timing)
+    fprintf(stderr, "[ctcdec host] token confidences: %zu tokens, pack + upload %.3f ms, kernel %.3f ms, download %.3f ms\n", nt,
+            logp_ms[0], logp_ms[1], logp_ms[2]);
+  return CTCDEC_OK;
+}
+
+// 9c. The full result: output records, emission lists and the further models' states back, then the host replay.
+static int finish_beams(DecodeCall& c) {
+  ctcdec_decoder* dec = c.dec;
+  ctcdec_result* res = c.res.get();
+  std::string& err = c.err;
+  const int32_t n_utts = c.n_utts;
+  const int n_best = c.n_best, K = c.K;
+  const unsigned long long head = c.head;
   const OutBeam* obs = (const OutBeam*)dec->h_out.p;
   if (be::d2h(dec->h_out.p, dec->w_out.p, (size_t)n_utts * n_best * sizeof(OutBeam), &err))
     return fail(CTCDEC_ERR_DEVICE, err);
@@ -1532,28 +1682,26 @@ static int decode_impl(ctcdec_decoder* dec, const void* const* utt_logits, const
   if (head && be::d2h(dec->h_tok.p, dec->w_tok.p, (size_t)head * sizeof(EmitNode), &err))
     return fail(CTCDEC_ERR_DEVICE, err);
   const LmState* xst = nullptr;
-  if (xstate_bytes) {
-    if (dec->h_xstate.ensure(xstate_bytes, &err) || be::d2h(dec->h_xstate.p, dec->w_xstate.p, xstate_bytes, &err))
+  if (c.xstate_bytes) {
+    if (dec->h_xstate.ensure(c.xstate_bytes, &err) || be::d2h(dec->h_xstate.p, dec->w_xstate.p, c.xstate_bytes, &err))
       return fail(CTCDEC_ERR_DEVICE, err);
     xst = (const LmState*)dec->h_xstate.p;
   }
-  auto t_copy = std::chrono::steady_clock::now();
-  be::last_timing(&res->ms[0], &res->ms[1]);
-  res->beam_kernel = be::last_beam_kernel();
-  if (dec->profile && be::d2h(dec->prof, dec->w_prof.p, N_PROF * 8, &err)) return fail(CTCDEC_ERR_DEVICE, err);
-
+  auto t_copy = Clock::now();
+  if (int rc = kernel_stats(c)) return rc;
   for (int32_t u = 0; u < n_utts; ++u)
-    for (uint32_t k = 0; k < n_out[u]; ++k) {
+    for (uint32_t k = 0; k < c.n_out[u]; ++k) {
       const OutBeam& ob = obs[(size_t)u * n_best + k];
       if ((unsigned long long)ob.tok_off + ob.tok_cnt > head) return fail(CTCDEC_ERR_INTERNAL, "token pool range");
     }
-  const bool want_tok = p->token_frames != 0;
+  const bool want_tok = c.p->token_frames != 0;
+  const StreamIn* stream = c.stream;
   res->has_tokens = want_tok;
   auto replay_range = [&](int32_t u0, int32_t u1) {
     for (int32_t u = u0; u < u1; ++u) {
       auto& beams = res->utts[(size_t)u];
-      beams.resize(n_out[u]);
-      for (uint32_t k = 0; k < n_out[u]; ++k) {
+      beams.resize(c.n_out[u]);
+      for (uint32_t k = 0; k < c.n_out[u]; ++k) {
         const OutBeam& ob = obs[(size_t)u * n_best + k];
         BeamResult& r = beams[k];
         fill_result(ob, xst ? &xst[((size_t)u * n_best + k) * (size_t)(K - 1)] : nullptr, K, &r);
@@ -1575,84 +1723,36 @@ static int decode_impl(ctcdec_decoder* dec, const void* const* utt_logits, const
   } else {
     replay_range(0, n_utts);
   }
-  // Token confidences: the tokens replay() has just listed go to the device as runs of rows of the survivor arrays, which
-  // this call's prune stage left there (whatever max_surv the overflow redo ended with), one kernel folds each run and one
-  // float64 per token comes back -- in the order of ctcdec_result_token_frames. A label that is missing from a frame's
-  // survivors is a broken invariant ("Token confidences"): the call fails, there is no substitute value.
-  double logp_ms[3] = {0, 0, 0};  // pack + upload, kernel, download
-  if (fold) {
-    auto t0 = std::chrono::steady_clock::now();
-    if (R > (int64_t)UINT32_MAX) return fail(CTCDEC_ERR_LIMIT, "token confidences: more than 2^32 frames in one call");
-    size_t nt = 0;
-    for (const auto& beams : res->utts)
-      for (const BeamResult& b : beams) nt += b.tok.size() / 3;
-    // (packed in page-locked memory that the decoder keeps: a fresh 20 MB of pageable memory costs more than the kernel)
-    if (dec->h_truns.ensure(std::max<size_t>(nt, 1) * sizeof(TokRun), &err)) return fail(CTCDEC_ERR_DEVICE, err);
-    TokRun* runs = (TokRun*)dec->h_truns.p;
-    size_t o = 0;
-    for (int32_t u = 0; u < n_utts; ++u)
-      for (const BeamResult& b : res->utts[(size_t)u]) {
-        const int32_t* t = b.tok.data();
-        for (size_t k = 0, n = b.tok.size() / 3; k < n; ++k, ++o, t += 3) {
-          const int64_t s = (int64_t)t[1] - p->first_frame, e = (int64_t)t[2] - p->first_frame;
-          if (t[0] < 0 || t[0] >= V || s < 0 || e <= s || e > utt_frames[u]) return fail(CTCDEC_ERR_INTERNAL, "token frames out of range");
-          runs[o] = TokRun{(uint32_t)(row0[(size_t)u] + s), (uint32_t)(e - s), (uint32_t)t[0]};
-        }
-      }
-    res->tk_logp.resize(nt);
-    uint32_t missing = 0;
-#ifdef CTC_SIM  // (the simulator's device memory is host memory: the kernel's body, token by token)
-    for (size_t i = 0; i < nt; ++i) {
-      const uint32_t* cnt = (const uint32_t*)dec->w_scnt.p;
-      const uint16_t* sid = (const uint16_t*)dec->w_sid.p;
-      const double* slp = (const double*)dec->w_slp.p;
-      missing += fold == LOGP_MEAN  ? token_logp_of<LOGP_MEAN>(runs[i], cnt, sid, slp, (uint32_t)max_surv, &res->tk_logp[i])
-                 : fold == LOGP_MIN ? token_logp_of<LOGP_MIN>(runs[i], cnt, sid, slp, (uint32_t)max_surv, &res->tk_logp[i])
-                                    : token_logp_of<LOGP_MAX>(runs[i], cnt, sid, slp, (uint32_t)max_surv, &res->tk_logp[i]);
-    }
-#else
-    if (nt) {
-      if (dec->w_truns.ensure(nt * sizeof(TokRun), &err) || be::h2d(dec->w_truns.p, runs, nt * sizeof(TokRun), &err) ||
-          dec->w_tlogp.ensure(nt * 8, &err) || dec->w_tmiss.ensure(16, &err) || be::zero(dec->w_tmiss.p, 16, &err))
-        return fail(CTCDEC_ERR_DEVICE, err);
-      be::TokenLogpArgs ta;
-      ta.runs = (const TokRun*)dec->w_truns.p;
-      ta.n_tokens = (int64_t)nt;
-      ta.fold = fold;
-      ta.surv_cnt = (const uint32_t*)dec->w_scnt.p;
-      ta.surv_id = (const uint16_t*)dec->w_sid.p;
-      ta.surv_lp = (const double*)dec->w_slp.p;
-      ta.max_surv = max_surv;
-      ta.out = (double*)dec->w_tlogp.p;
-      ta.missing = (uint32_t*)dec->w_tmiss.p;
-      auto t1 = std::chrono::steady_clock::now();
-      if (be::launch_token_logp(ta, &err)) return fail(CTCDEC_ERR_DEVICE, err);
-      if (host_timing) logp_ms[1] = be::last_token_logp_ms();
-      auto t2 = std::chrono::steady_clock::now();
-      if (be::d2h(res->tk_logp.data(), dec->w_tlogp.p, nt * 8, &err) || be::d2h(&missing, dec->w_tmiss.p, 4, &err))
-        return fail(CTCDEC_ERR_DEVICE, err);
-      logp_ms[0] = std::chrono::duration<double, std::milli>(t1 - t0).count();
-      logp_ms[2] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t2).count();
-    }
-#endif
-    if (missing)
-      return fail(CTCDEC_ERR_INTERNAL, "token confidences: " + std::to_string(missing) + " token frames whose label is not among the frame's survivors");
-    res->has_logp = true;
-    if (host_timing)
-      fprintf(stderr, "[ctcdec host] token confidences: %zu tokens, pack + upload %.3f ms, kernel %.3f ms, download %.3f ms\n", nt,
-              logp_ms[0], logp_ms[1], logp_ms[2]);
-  }
-  auto t_end = std::chrono::steady_clock::now();
-  res->ms[2] = std::chrono::duration<double, std::milli>(t_end - t_begin).count();
-  if (host_timing) {
-    auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-      return std::chrono::duration<double, std::milli>(b - a).count();
-    };
+  if (c.fold)
+    if (int rc = token_confidences(c)) return rc;
+  close_call(c);
+  if (c.host_timing)
     fprintf(stderr, "[ctcdec host] setup+launch %.3f ms, wait kernels %.3f ms, copy back %.3f ms (%llu tokens), replay %.3f ms\n",
-            ms(t_begin, t_launch), ms(t_launch, t_kernel), ms(t_kernel, t_copy), head, ms(t_copy, t_end));
-  }
-  *out = res.release();
+            ms(c.t_begin, c.t_launch), ms(c.t_launch, c.t_kernel), ms(c.t_kernel, t_copy), head, ms(t_copy, c.t_end));
   return CTCDEC_OK;
+}
+
+static int decode_impl(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts,
+                       int32_t dtype, int32_t is_device, const ctcdec_params* p, const ctcdec_lm_state* start_states,
+                       const DecodeMode& mode, ctcdec_result** out) {
+  DecodeCall c{mode, dec, p, utt_logits, utt_frames, start_states, out, n_utts, dtype, is_device};
+  if (int rc = check_call(c)) return rc;
+  if (n_utts == 0) {  // (nothing to decode: no device lock, no tables)
+    *out = c.res.release();
+    return CTCDEC_OK;
+  }
+  if (int rc = open_call(c)) return rc;
+  if (int rc = stage_logits(c)) return rc;
+  c.arenas_full = c.rs != nullptr || dec->arenas_worst_case || getenv("CTCDEC_WORST_CASE_ARENAS") != nullptr;
+  size_arenas(c, c.arenas_full);
+  if (int rc = c.rs ? stage_resident_input(c) : c.stream ? stage_imports(c) : CTCDEC_OK) return rc;
+  if (int rc = reserve_beam_workspace(c)) return rc;
+  if (int rc = stage_start_states(c)) return rc;
+  if (int rc = fill_beam_args(c)) return rc;
+  if (int rc = prune_and_launch(c)) return rc;
+  if (c.after_launch && *c.after_launch && (*c.after_launch)(&c.err)) return fail(CTCDEC_ERR_DEVICE, c.err);
+  if (int rc = collect_counters(c)) return rc;
+  return c.device_texts ? finish_device_texts(c) : c.want_result ? finish_beams(c) : finish_stream_push(c);
 }
 
 // ---- device-resident streams ------------------------------------------------------------------------------------
@@ -1685,18 +1785,13 @@ int ctcdec_stream_push(ctcdec_stream* st, const void* const* chunk_logits, const
   if ((want_result || is_end) && !out) return fail(CTCDEC_ERR_ARG, "a result is wanted but there is nowhere to put it");
   std::vector<int32_t> ff((size_t)st->n);
   for (int32_t u = 0; u < st->n; ++u) ff[(size_t)u] = first_frame ? first_frame[u] : (int32_t)st->frames[(size_t)u];
-  StreamIn sin;
-  sin.first_frame = ff.data();
-  sin.beams = st->has_import ? st->imp_beams.data() : nullptr;
-  sin.beam_off = st->imp_off.data();
-  sin.text_blob = st->imp_blob.data();
-  sin.fold = (force_next_word || is_end) ? 1 : 0;
-  sin.eos = is_end ? 1 : 0;
+  const StreamIn sin{ff.data(), st->has_import ? st->imp_beams.data() : nullptr, st->imp_off.data(), st->imp_blob.data(),
+                     (force_next_word || is_end) ? 1 : 0, is_end ? 1 : 0};
   ctcdec_result* res = nullptr;
   HotCallScope hot_scope(st->dec);
   const int rc = decode_impl(st->dec, chunk_logits, chunk_frames, st->n, dtype, is_device, params,
-                             st->start_states.empty() ? nullptr : st->start_states.data(), &sin, &res, st,
-                             want_result != 0 || is_end != 0);
+                             st->start_states.empty() ? nullptr : st->start_states.data(),
+                             DecodeMode{&sin, st, want_result != 0 || is_end != 0}, &res);
   if (rc != CTCDEC_OK) return rc;
   if (out) *out = res;
   else ctcdec_result_free(res);
@@ -1726,12 +1821,7 @@ int ctcdec_stream_import(ctcdec_stream* st, const ctcdec_beam_in* beams, const i
   if (be::bind_thread(&err)) return fail(CTCDEC_ERR_DEVICE, err);
   if (sync_tables(dec, &err)) return fail(CTCDEC_ERR_DEVICE, err);  // (the hot-word view of the partial words)
   const int K = st->K;
-  StreamIn sin;
-  sin.first_frame = nullptr;
-  sin.beams = beams;
-  sin.beam_off = beam_off;
-  sin.text_blob = text_blob;
-  sin.fold = sin.eos = 0;
+  const StreamIn sin{nullptr, beams, beam_off, text_blob, 0, 0};
   std::vector<ImportBeam> imps((size_t)st->n * ctcdec_stream::CAP);
   std::vector<LmState> imps_x(K > 1 ? imps.size() * (size_t)(K - 1) : 0);
   for (int32_t u = 0; u < st->n; ++u) {
@@ -1739,7 +1829,7 @@ int ctcdec_stream_import(ctcdec_stream* st, const ctcdec_beam_in* beams, const i
     if (cnt < 1 || cnt > ctcdec_stream::CAP) return fail(CTCDEC_ERR_ARG, "a stream must carry between 1 and 256 beams");
     for (int64_t k = 0; k < cnt; ++k) {
       const size_t slot = (size_t)u * ctcdec_stream::CAP + (size_t)k;
-      std::string e = build_import(dec, sin, beam_off[u] + k, 0, &imps[slot], K > 1 ? &imps_x[slot * (size_t)(K - 1)] : nullptr,
+      std::string e = build_import(dec, sin, beam_off[u] + k, &imps[slot], K > 1 ? &imps_x[slot * (size_t)(K - 1)] : nullptr,
                                    import_hot(dec, u));
       if (!e.empty()) return fail(CTCDEC_ERR_ARG, e);
     }
@@ -1772,7 +1862,7 @@ int ctcdec_stream_import(ctcdec_stream* st, const ctcdec_beam_in* beams, const i
 static int host_slices_wanted(const ctcdec_decoder* dec, const int32_t* utt_frames, int32_t n_utts, int32_t dtype) {
   const char* env = getenv("CTCDEC_HOST_SLICES");  // 0: never; n >= 2: always, in n slices (tests); unset: by size
   if (env && atoi(env) < 2) return 0;
-  const size_t esz = dtype == CTCDEC_F32 ? 4 : dtype == CTCDEC_F64 ? 8 : 2;
+  const size_t esz = dtype_size(dtype);
   int64_t rows = 0, tmax = 0;
   for (int32_t u = 0; u < n_utts; ++u) {
     if (utt_frames[u] < 0) return 0;
@@ -1790,7 +1880,7 @@ static int decode_host_sliced(ctcdec_decoder* dec, const void* const* utt_logits
                               ctcdec_result** out) {
   if (p->beam_width < 1 || p->beam_width > CTCDEC_MAX_BEAM_WIDTH) return 1;  // (the one-piece path words the refusal)
   const size_t V = dec->alpha.labels.size();
-  const size_t esz = dtype == CTCDEC_F32 ? 4 : dtype == CTCDEC_F64 ? 8 : 2;
+  const size_t esz = dtype_size(dtype);
   int64_t tmax = 0;
   for (int32_t u = 0; u < n_utts; ++u) tmax = std::max<int64_t>(tmax, utt_frames[u]);
   const int64_t C = (tmax + n_slices - 1) / n_slices;  // frames per slice
@@ -1848,18 +1938,12 @@ static int decode_host_sliced(ctcdec_decoder* dec, const void* const* utt_logits
     }
     std::vector<int32_t> ff((size_t)n_utts);
     for (int32_t u = 0; u < n_utts; ++u) ff[(size_t)u] = (int32_t)st->frames[(size_t)u];
-    StreamIn sin;
-    sin.first_frame = ff.data();
-    sin.beams = nullptr;
-    sin.beam_off = st->imp_off.data();
-    sin.text_blob = st->imp_blob.data();
-    sin.fold = last ? 1 : 0;
-    sin.eos = last ? 1 : 0;
+    const StreamIn sin{ff.data(), nullptr, st->imp_off.data(), st->imp_blob.data(), last ? 1 : 0, last ? 1 : 0};
     const AfterLaunch next = [&, k](std::string* e) -> int { return copy_slice(k + 1, e); };
     res = nullptr;
     rc = decode_impl(dec, ptrs.data(), frames.data(), n_utts, dtype, /*is_device=*/1, p,
-                     st->start_states.empty() ? nullptr : st->start_states.data(), &sin, &res, st, /*want_result=*/last,
-                     last ? nullptr : &next);
+                     st->start_states.empty() ? nullptr : st->start_states.data(),
+                     DecodeMode{&sin, st, /*want_result=*/last, last ? nullptr : &next}, &res);
     if (rc != CTCDEC_OK) return rc;
     if (!last) ctcdec_result_free(res);
   }
@@ -1913,7 +1997,7 @@ int ctcdec_frame_survivors(ctcdec_decoder* dec, const void* logits, int32_t n_fr
   std::lock_guard<std::mutex> device_lock(g_device_mu);
   if (be::bind_thread(&err)) return fail(CTCDEC_ERR_DEVICE, err);
   const int V = (int)dec->alpha.labels.size();
-  const size_t esz = dtype == CTCDEC_F32 ? 4 : dtype == CTCDEC_F64 ? 8 : 2;
+  const size_t esz = dtype_size(dtype);
   const size_t rows = (size_t)n_frames;
   std::vector<const void*> ptrs(1, logits);
   if (!is_device) {
@@ -1922,58 +2006,21 @@ int ctcdec_frame_survivors(ctcdec_decoder* dec, const void* logits, int32_t n_fr
     ptrs[0] = dec->w_logits.p;
   }
   std::vector<int64_t> row0 = {0, (int64_t)n_frames};
-  int max_surv = V;  // the decode path's bound: rows are normalised, at most floor(e^-min) labels pass
-  if (token_min_logp > log(1e-15)) {
-    double bound = floor(exp(-token_min_logp)) + 2.0;
-    if (bound < (double)V) max_surv = (int)bound;
-  }
-  if (upload(dec->w_ptrs, ptrs, &err) || upload(dec->w_row0, row0, &err) || dec->w_rowsum.ensure(rows * 8, &err) ||
-      dec->w_isprob.ensure(4, &err) || dec->w_scnt.ensure(rows * 4, &err) || dec->w_sid.ensure(rows * max_surv * 2, &err) ||
-      dec->w_slp.ensure(rows * max_surv * 8, &err) || dec->w_flags.ensure(32, &err) || be::zero(dec->w_flags.p, 32, &err) ||
-      dec->w_slow.ensure(rows * 4, &err))
-    return fail(CTCDEC_ERR_DEVICE, err);
-  be::PruneArgs pa;
-  pa.utt_logits = (const void* const*)dec->w_ptrs.p;
-  pa.utt_row0 = (const int64_t*)dec->w_row0.p;
-  pa.n_utts = 1;
-  pa.n_rows = n_frames;
-  pa.n_labels = V;
-  pa.dtype = dtype;
-  pa.token_min_logp = token_min_logp;
-  pa.max_surv = max_surv;
-  pa.row_sum = (double*)dec->w_rowsum.p;
-  pa.utt_is_prob = (uint32_t*)dec->w_isprob.p;
-  pa.surv_cnt = (uint32_t*)dec->w_scnt.p;
-  pa.surv_id = (uint16_t*)dec->w_sid.p;
-  pa.surv_lp = (double*)dec->w_slp.p;
-  pa.overflow = (uint32_t*)dec->w_flags.p;
-  pa.row_base = 0;
-  pa.pass = 0;
-  pa.slow_rows = (uint32_t*)dec->w_slow.p;
-  pa.utt_side = nullptr;
-  pa.utt_sum = nullptr;
-  pa.dense_hint = 0;
-  pa.rows_aligned16 = (((uintptr_t)ptrs[0]) & 15u) == 0 ? 1 : 0;
-  pa.rows_aligned4 = (((uintptr_t)ptrs[0]) & 3u) == 0 ? 1 : 0;
-  if (be::launch_prune(pa, &err)) return fail(CTCDEC_ERR_DEVICE, err);
-  uint32_t flags[4] = {0, 0, 0, 0};
-  if (be::d2h(flags, dec->w_flags.p, 16, &err)) return fail(CTCDEC_ERR_DEVICE, err);
-  if (flags[2] && (be::launch_sniff_exact(pa, &err) || be::d2h(flags, dec->w_flags.p, 16, &err))) return fail(CTCDEC_ERR_DEVICE, err);
-  if (flags[1]) {
-    pa.pass = 1;
-    if (be::launch_prune(pa, &err)) return fail(CTCDEC_ERR_DEVICE, err);
-  }
+  if (upload(dec->w_ptrs, ptrs, &err) || upload(dec->w_row0, row0, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+  PruneStage s{dec, &ptrs, 1, dtype, n_frames, V, token_min_logp};  // the decode's own prune stage, no beam stage behind it
+  if (int rc = prune_stage(s, nullptr)) return rc;
+  const size_t max_surv = (size_t)s.max_surv;
   std::vector<uint32_t> cnt(rows);
-  std::vector<uint16_t> sid(rows * (size_t)max_surv);
-  std::vector<double> slp(rows * (size_t)max_surv);
+  std::vector<uint16_t> sid(rows * max_surv);
+  std::vector<double> slp(rows * max_surv);
   if (be::d2h(cnt.data(), dec->w_scnt.p, rows * 4, &err) || be::d2h(sid.data(), dec->w_sid.p, sid.size() * 2, &err) ||
       be::d2h(slp.data(), dec->w_slp.p, slp.size() * 8, &err))
     return fail(CTCDEC_ERR_DEVICE, err);
   for (size_t t = 0; t < rows; ++t) {
     counts[t] = (int32_t)cnt[t];
     for (uint32_t k = 0; k < cnt[t] && k < (uint32_t)stride; ++k) {
-      ids[t * (size_t)stride + k] = sid[t * (size_t)max_surv + k];
-      logps[t * (size_t)stride + k] = slp[t * (size_t)max_surv + k];
+      ids[t * (size_t)stride + k] = sid[t * max_surv + k];
+      logps[t * (size_t)stride + k] = slp[t * max_surv + k];
     }
   }
   return CTCDEC_OK;

@@ -30,20 +30,12 @@ int sync(std::string* err);
 // `height` rows of `width` bytes, host (pitch spitch) -> device (pitch dpitch), on the COPY stream (its own non-blocking stream:
 // the kernels queued on the decode stream keep running while the host waits here). Returns when the copy has landed.
 int h2d_2d_overlapped(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t height, std::string* err);
-// streams and events for the chunked pipeline of large batches (api.cpp: decode_pipelined). Every call above and the
-// launches below act on the current stream; stream 0 is the default.
-void use_stream(int idx);
-int n_events();
-int ev_record(int id, std::string* err);
-int ev_wait(int id, std::string* err);
-int ev_sync(int id, std::string* err);
-double ev_elapsed_ms(int a, int b);
+// Every call above except h2d_2d_overlapped, and every launch below, acts on the one decode stream.
+// device -> host on the decode stream WITHOUT waiting: `dst` is page-locked memory, valid after the next sync()
 int d2h_async(void* dst, const void* src, size_t bytes, std::string* err);
-// host -> device on the current stream WITHOUT waiting: `src` is page-locked memory the caller leaves alone until the stream has passed it
+// host -> device on the decode stream WITHOUT waiting: `src` is page-locked memory the caller leaves alone until the stream has passed it
 int h2d_async(void* dst, const void* src, size_t bytes, std::string* err);
-int sync_all(std::string* err);
 int cus();  // compute units of the device
-void set_last_timing(double prune_ms, double beam_ms);
 
 // Frame-prune stage: input normalisation (decoder.py:759-765), token prune (decoder.py:444-445)
 // and CPython-set ordering of the survivors, for every frame of every utterance.

@@ -1551,7 +1551,7 @@ class BeamSearchDecoderCTC:
                 raise ValueError("a stream needs at least one beam (use get_starting_state())")
         params = self._params(beam_width, beam_prune_logp, token_min_logp, prune_history, weight, 0)
         # refused here, before any stream is opened, imported into or retired: the lists of the previous chunk stay readable
-        # (the library refuses the same values with the same exceptions, api.cpp: decode_impl)
+        # (the library refuses the same values with the same exceptions, api.cpp: check_call)
         if params.beam_width < 1:
             raise ValueError("beam_width must be >= 1")
         if params.beam_width > B.MAX_BEAM_WIDTH:

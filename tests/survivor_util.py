@@ -19,6 +19,32 @@ def survivors(dec, x, token_min_logp):
     return [([ids[t * V + k] for k in range(counts[t])], [lps[t * V + k] for k in range(counts[t])]) for t in range(T)]
 
 
+def probability_rows(rng, T=6, V=32):
+    """Softmax outputs (float64): every row sums to 1, so the prune stage reads them as log(clip(p)) (decoder.py:760-762)."""
+    e = np.exp(rng.standard_normal((T, V)) * 2)
+    return e / e.sum(axis=1, keepdims=True)
+
+
+OVERFLOW_TMIN = -2.0
+OVERFLOW_BOUND = int(np.floor(np.exp(-OVERFLOW_TMIN))) + 2  # 9: what normalised rows can keep, the width the prune stage first reserves
+
+
+def overflow_rows(rng, T=6, V=32):
+    """Un-normalised non-negative rows whose mean sum is EXACTLY 1 -- read as probabilities -- but whose even rows hold
+    more labels above e^OVERFLOW_TMIN = 0.1353 than normalised rows could: ten at 9/64 (row sum 90/64); odd rows four of
+    them and one 1/32 (row sum 38/64). Every value and sum is exact in binary floating point."""
+    x = np.zeros((T + T % 2, V))
+    for t in range(x.shape[0]):
+        at = rng.permutation(V)
+        if t % 2 == 0:
+            x[t, at[:OVERFLOW_BOUND + 1]] = 9 / 64
+        else:
+            x[t, at[:4]] = 9 / 64
+            x[t, at[4]] = 1 / 32
+    assert x.sum(axis=1).mean() == 1.0
+    return x
+
+
 def check_against_cpython(dec, x, token_min_logp, tol):
     got = survivors(dec, x, token_min_logp)
     import os

@@ -536,7 +536,7 @@ def test_hip_frame_survivors_in_cpython_set_order():
     """The prune kernels' per-frame label order against a REAL CPython set (the wave-distributed table for
     up to 18 survivors, the lane-0 LDS walk above that; register-resident and generic kernels; fp32/fp64/fp16)."""
     from pyctcdecode_amd import build_ctcdecoder
-    from tests.survivor_util import check_against_cpython
+    from tests.survivor_util import OVERFLOW_BOUND, OVERFLOW_TMIN, check_against_cpython, overflow_rows, probability_rows, survivors
 
     _loaded_native()
     rng = np.random.default_rng(11)
@@ -553,6 +553,13 @@ def test_hip_frame_survivors_in_cpython_set_order():
         border += check_against_cpython(dec, x, tmin, _tol(x)["tol"])
         frames += 300
     assert border < frames // 20
+    # the lists are what the DECODE's prune stage leaves: probability-like rows as log(clip(p)) under a bound below V, and
+    # un-normalised rows that pass more labels than the bound come back whole (the stage redoes them at full width)
+    dec = build_ctcdecoder([chr(0x4E00 + i) for i in range(31)])
+    assert check_against_cpython(dec, probability_rows(rng), -2.5, 1e-9) == 0
+    x = overflow_rows(rng)
+    assert check_against_cpython(dec, x, OVERFLOW_TMIN, 1e-9) == 0
+    assert [len(ids) for ids, _ in survivors(dec, x, OVERFLOW_TMIN)] == [OVERFLOW_BOUND + 1, 4] * (len(x) // 2)
 
 
 def test_hip_rows64_prune_kernel_shapes(monkeypatch):

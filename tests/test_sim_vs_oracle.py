@@ -208,7 +208,7 @@ def test_non_finite_logits_follow_the_reference(sim_library):  # noqa: F811
 def test_frame_survivors_in_cpython_set_order(sim_library):  # noqa: F811
     """The prune stage's per-frame label order IS the iteration order of a real CPython set."""
     from pyctcdecode_amd import build_ctcdecoder
-    from tests.survivor_util import check_against_cpython
+    from tests.survivor_util import OVERFLOW_BOUND, OVERFLOW_TMIN, check_against_cpython, overflow_rows, probability_rows, survivors
 
     rng = np.random.default_rng(11)
     # (the near-uniform rows keep every label: 16-18, 64-76 and 256-306 members are the sizes whose union copy
@@ -218,6 +218,13 @@ def test_frame_survivors_in_cpython_set_order(sim_library):  # noqa: F811
         dec = build_ctcdecoder([chr(0x4E00 + i) for i in range(V - 1)])
         x = (rng.standard_normal((40, V)) * scale).astype(np.float32)
         check_against_cpython(dec, x, tmin, 1e-9)
+    # the lists are what the DECODE's prune stage leaves: probability-like rows as log(clip(p)) under a bound below V, and
+    # un-normalised rows that pass more labels than the bound come back whole (the stage redoes them at full width)
+    dec = build_ctcdecoder([chr(0x4E00 + i) for i in range(31)])
+    assert check_against_cpython(dec, probability_rows(rng), -2.5, 1e-9) == 0
+    x = overflow_rows(rng)
+    assert check_against_cpython(dec, x, OVERFLOW_TMIN, 1e-9) == 0
+    assert [len(ids) for ids, _ in survivors(dec, x, OVERFLOW_TMIN)] == [OVERFLOW_BOUND + 1, 4] * (len(x) // 2)
 
 
 def test_decode_calls_from_several_host_threads(sim_library):  # noqa: F811
