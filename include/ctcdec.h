@@ -65,7 +65,8 @@ typedef struct ctcdec_params {
   int32_t token_frames;      /* 0/1: also keep every returned beam's tokens with their frames for
                                 ctcdec_result_token_frames (takes precedence over texts_only); was a reserved 0.
                                 CTCDEC_TOKEN_LOGP_MEAN / _MIN / _MAX: the same, plus each token's confidence for
-                                ctcdec_result_token_logp (ctcdec_decode_batch only) */
+                                ctcdec_result_token_logp (ctcdec_decode_batch, and ctcdec_stream_push / _read of streams
+                                whose first chunk asked for the fold; not ctcdec_decode_stream_batch) */
 } ctcdec_params;
 
 /* ctcdec_params.token_frames beyond 0/1: the fold of a token's per-frame log-probabilities (ctcdec_result_token_logp) */
@@ -231,6 +232,7 @@ int ctcdec_decode_stream_batch(ctcdec_decoder* dec, const void* const* utt_logit
  *          next import (they are copied).
  * One handle belongs to one decoder; its calls are serialised with that decoder's other calls. */
 typedef struct ctcdec_stream ctcdec_stream;
+/* (tokens and confidences of a stream: below ctcdec_stream_import) */
 int ctcdec_stream_open(ctcdec_decoder* dec, int32_t n_streams, const ctcdec_lm_state* start_states, ctcdec_stream** out);
 int ctcdec_stream_push(ctcdec_stream* st, const void* const* chunk_logits, const int32_t* chunk_frames, int32_t dtype,
                        int32_t is_device, const ctcdec_params* params, const int32_t* first_frame,
@@ -238,8 +240,20 @@ int ctcdec_stream_push(ctcdec_stream* st, const void* const* chunk_logits, const
 int ctcdec_stream_read(ctcdec_stream* st, const ctcdec_params* params, ctcdec_result** out);
 int ctcdec_stream_import(ctcdec_stream* st, const ctcdec_beam_in* beams, const int64_t* beam_off /* [n_streams+1] */,
                          const char* text_blob, int64_t text_bytes);
+/* Tokens and confidences (params.token_frames): a stream's emission chains reach back to its start, so a push or read
+ * with token_frames = 1 lists the tokens of every word closed so far (a word closed by force_next_word included) and then
+ * those of the open partial word, with absolute frames -- at any chunk. A fold (CTCDEC_TOKEN_LOGP_*) needs the per-frame
+ * survivors of EARLIER chunks, which the handle then keeps in a device-side ledger (compact, grow-only: a few entries per
+ * frame): it has to be asked for by the stream's FIRST push (the first after open or after is_end) and every later push
+ * or read may ask for that fold, for token_frames = 1 or for nothing. Such a stream numbers its frames from its first
+ * chunk's first_frame: every later first_frame[u] has to equal it plus the frames pushed so far. CTCDEC_ERR_ARG, before
+ * the stream is touched: a fold the first push did not ask for (or another one), a first_frame that does not continue the
+ * stream, token_frames != 0 on a stream that holds imported beams (their chains start at the import). A streamed token's
+ * confidence is the same float64 as ctcdec_decode_batch's for the same frames. */
 /* frames pushed so far per stream ([n_streams]) */
 int ctcdec_stream_frames(const ctcdec_stream* st, int64_t* frames_out);
+/* device bytes the handle's survivor ledger holds (0: no push of it has asked for a confidence fold) */
+int ctcdec_stream_ledger_bytes(const ctcdec_stream* st, int64_t* bytes_out);
 void ctcdec_stream_close(ctcdec_stream* st);
 
 /* ---- results (OutputBeam fields, decoder.py:102-110, assembled as decoder.py:653-667) --------- */
@@ -303,8 +317,9 @@ int ctcdec_result_text_blocks(ctcdec_result* r, const char** pool_out, const int
  * start the absolute frame at which the beam took it after a blank or another label, end 1 + the last frame of the run
  * of that label which follows it. This is the reference's partial_frames bookkeeping (decoder.py:449-534) applied to one
  * token instead of one word: each word of ctcdec_result_frames is a run of consecutive tokens, from its first token's
- * start to its last token's end. Streaming results (ctcdec_decode_stream_batch, ctcdec_stream_*) list only the tokens
- * decoded on the device since the caller's beam was imported. Pointers stay valid until ctcdec_result_free; a result
+ * start to its last token's end. A device-resident stream (ctcdec_stream_push / _read) lists the tokens from the start of
+ * the stream, the open partial word's last; ctcdec_decode_stream_batch lists only the tokens decoded on the device since
+ * the caller's beams were imported. Pointers stay valid until ctcdec_result_free; a result
  * decoded without params.token_frames returns CTCDEC_ERR_ARG. */
 int ctcdec_result_token_frames(ctcdec_result* r, const int64_t** tok_off, const int32_t** label, const int32_t** start,
                                const int32_t** end, int64_t* n_tokens);
@@ -314,9 +329,10 @@ int ctcdec_result_token_frames(ctcdec_result* r, const int64_t** tok_off, const 
  * probability of the token's label at that frame -- the clipped log-softmax (or log(clip(p))) the token prune looked at
  * (decoder.py:180-197, 444-445, 762-765) -- as the arithmetic mean (summed in frame order; the log of the geometric mean), the
  * minimum or the maximum. The values are computed on the device inside the decode call, from the survivor lists of its
- * frame-prune stage: a token's label survived the prune at every frame of its run. Pointers stay valid until
- * ctcdec_result_free; a result decoded without a fold returns CTCDEC_ERR_ARG, and streaming calls refuse the fold.
- * decode_beams(..., confidence="mean") / decode_batch(..., confidence=...) */
+ * frame-prune stage: a token's label survived the prune at every frame of its run. A device-resident stream folds over its
+ * survivor ledger instead, which holds the same values for every frame pushed so far (ctcdec_stream_push). Pointers stay
+ * valid until ctcdec_result_free; a result decoded without a fold returns CTCDEC_ERR_ARG, and ctcdec_decode_stream_batch
+ * refuses the fold. decode_beams(..., confidence="mean") / decode_batch / partial_decode_beams(..., confidence=...) */
 int ctcdec_result_token_logp(ctcdec_result* r, const double** logp, int64_t* n_tokens);
 
 /* timing of the last call's device stages in milliseconds (HIP events on the decode stream):

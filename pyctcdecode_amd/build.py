@@ -24,7 +24,7 @@ HIP_FLAGS = {"backend_hip.hip": _MAX_ILP,
              # (the workgroup kernel: 238 -> 195 registers, 255 -> 138 scalar registers spilled to vector lanes)
              "beam_group_hip.hip": ["-mllvm", "-disable-machine-licm"]}
 HEADERS = ["common.h", "beam_core.h", "beam_wave.h", "set_order.h", "set_order_small.h", "backend.h", "host_tables.h", "np_sum.h",
-           "np_f32.h", "wave_ops_hip.h", "text_wave.h", "token_logp.h"]
+           "np_f32.h", "wave_ops_hip.h", "text_wave.h", "token_logp.h", "surv_ledger.h"]
 
 
 def hipcc() -> str:

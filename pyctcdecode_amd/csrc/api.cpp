@@ -205,7 +205,7 @@ struct ctcdec_decoder {
   // per-call workspace (grow only)
   DevBuf w_logits, w_ptrs, w_row0, w_rowsum, w_isprob, w_scnt, w_sid, w_slp, w_flags, w_text, w_emit, w_toff,
       w_eoff, w_start, w_out, w_nout, w_status, w_tok, w_head, w_prof, w_imp, w_impoff, w_ff, w_cold, w_pay, w_tscr, w_tsoff, w_tpool,
-      d_toktext, d_tokbytes, w_slow, w_order, w_side, w_truns, w_tlogp, w_tmiss;
+      d_toktext, d_tokbytes, w_slow, w_order, w_side, w_truns, w_tlogp, w_tmiss, w_ledrow;
   bool slicing = false;  // a time-sliced host ingest is under way (decode_host_sliced): the prune stage notes each slice's side of 1
   uint32_t max_label_bytes = 1;
   bool arenas_worst_case = false;  // a call has outgrown the usual reservation of the node arenas: reserve the worst case from now on
@@ -363,6 +363,18 @@ struct ctcdec_stream {
   std::vector<ctcdec_beam_in> imp_beams;
   std::vector<int64_t> imp_off;
   std::string imp_blob;
+  // The survivor ledger (surv_ledger.h), only for streams whose first push asked for a confidence fold (led_fold != 0):
+  // what the frame prune left for every frame pushed so far, CSR per stream, grow-only like the emission arena. The
+  // entries each stream holds come back with the counters after every push (they ride behind them in `sstate`:
+  // n StreamStates, n entry counts, the overrun word).
+  int32_t led_fold = 0;
+  DevBuf led_off, led_id, led_lp;
+  uint64_t led_row_cap = 0, led_ent_cap = 0;  // rows / entries per stream
+  std::vector<uint64_t> led_used;             // entries per stream after the last push
+  std::vector<int32_t> led_first;             // first_frame of each stream's first chunk: ledger row = frame - led_first
+  std::vector<uint64_t> led_back;             // host side of the widened counter read
+  size_t sstate_bytes() const { return (size_t)n * sizeof(StreamState); }
+  size_t led_bytes() const { return led_off.cap + led_id.cap + led_lp.cap; }
 };
 
 // the device copy of a model's n-gram table: uploaded once per NgramStore, shared by every decoder that holds the model
@@ -985,12 +997,37 @@ struct DecodeCall : DecodeMode {
   unsigned long long* heads_pinned = nullptr;
   unsigned long long head = 0;
   bool outgrown_redone = false;
+  // resident streams: the fold of the streams' survivor ledger when this call appends to it (0: the streams keep none),
+  // the rows each stream's ledger holds once this chunk is in, the streams' first frames
+  int32_t led = 0;
+  std::vector<int64_t> led_rows;
   bool host_timing = false;
   Clock::time_point t_begin, t_launch, t_kernel, t_end;
   std::string err;
   std::unique_ptr<ctcdec_result> res;
   std::unique_lock<std::mutex> device_lock;  // (last: released first)
 };
+
+// Tokens and confidences of a device-resident stream, refused before anything moves. The chains of a stream reach back to its
+// start unless the host imported its beams; the survivor ledger exists only when the stream's first push asked for a fold, and
+// its rows are numbered from the first frame of that push, so every later chunk has to continue where the last one ended.
+static int check_stream_tokens(DecodeCall& c) {
+  const ctcdec_stream* rs = c.rs;
+  if (c.p->token_frames != 0 && rs->has_import)
+    return fail(CTCDEC_ERR_ARG, "token frames are not available to a stream that holds imported beams: their chains do not reach back");
+  const bool first = rs->pushes == 0;  // (a new stream, or the first chunk after is_end)
+  if (c.fold && !first && rs->led_fold != c.fold)
+    return fail(CTCDEC_ERR_ARG, rs->led_fold ? "a stream keeps the confidence fold its first chunk asked for"
+                                             : "token confidences have to be asked for from a stream's first chunk on");
+  c.led = first ? c.fold : rs->led_fold;
+  if (c.led && !first)
+    for (int32_t u = 0; u < c.n_utts; ++u)
+      if ((int64_t)c.stream->first_frame[u] != (int64_t)rs->led_first[(size_t)u] + rs->frames[(size_t)u])
+        return fail(CTCDEC_ERR_ARG, "stream " + std::to_string(u) + ": first_frame " + std::to_string(c.stream->first_frame[u]) +
+                                        " does not continue the stream (token confidences: expected " +
+                                        std::to_string((int64_t)rs->led_first[(size_t)u] + rs->frames[(size_t)u]) + ")");
+  return CTCDEC_OK;
+}
 
 // 1a. Argument checks; the (still empty) result.
 static int check_call(DecodeCall& c) {
@@ -1002,7 +1039,10 @@ static int check_call(DecodeCall& c) {
   if (p->beam_width > CTCDEC_MAX_BEAM_WIDTH)
     return fail(CTCDEC_ERR_LIMIT, "beam_width above the supported maximum of 256");
   c.fold = logp_fold(p);
-  if (c.fold && c.stream) return fail(CTCDEC_ERR_ARG, "token confidences are not available to streaming decodes");
+  if (c.fold && c.stream && !c.rs)
+    return fail(CTCDEC_ERR_ARG, "token confidences are not available to streaming decodes whose beams the caller hands in");
+  if (c.rs)
+    if (int rc = check_stream_tokens(c)) return rc;
   c.t_begin = Clock::now();
   c.res.reset(new ctcdec_result());
   c.res->utts.resize((size_t)c.n_utts);
@@ -1443,6 +1483,105 @@ static int prune_stage(PruneStage& s, DecodeCall* beam) {
   }
 }
 
+// Resident streams with a survivor ledger: room for this chunk. The host knows the entries each stream held after the last push
+// exactly and this chunk's worst case (frames x the width the prune stage ended with); like the emission arena the ledger
+// grows in big steps with a device-to-device copy of the used part, and a failure leaves the stream on its old ledger.
+static int reserve_ledger(DecodeCall& c) {
+  ctcdec_stream* rs = c.rs;
+  std::string& err = c.err;
+  const int32_t n = c.n_utts;
+  const bool first = rs->pushes == 0;
+  if (first) {
+    rs->led_used.assign((size_t)n, 0);
+    rs->led_first.assign(c.stream->first_frame, c.stream->first_frame + n);
+  }
+  uint64_t need_rows = 0, need_ent = 0;
+  for (int32_t u = 0; u < n; ++u) {
+    const uint64_t chunk = (uint64_t)c.utt_frames[u] * (uint64_t)c.prune.max_surv;
+    if (chunk > UINT32_MAX || (uint64_t)rs->frames[(size_t)u] + (uint64_t)c.utt_frames[u] > UINT32_MAX)
+      return fail(CTCDEC_ERR_LIMIT, "token confidences: a chunk of more than 2^32 survivor entries, or a stream of more than 2^32 frames");
+    need_rows = std::max<uint64_t>(need_rows, (uint64_t)rs->frames[(size_t)u] + (uint64_t)c.utt_frames[u]);
+    need_ent = std::max<uint64_t>(need_ent, rs->led_used[(size_t)u] + chunk);
+  }
+  if (need_rows > rs->led_row_cap || need_ent > rs->led_ent_cap || !rs->led_off.p) {
+    const uint64_t row_cap = std::max<uint64_t>(std::max<uint64_t>(2 * need_rows, 2 * rs->led_row_cap), 1024);
+    const uint64_t ent_cap = std::max<uint64_t>(std::max<uint64_t>(2 * need_ent, 2 * rs->led_ent_cap), 4096);
+    DevBuf off, id, lp;  // (a failure below releases them: the stream keeps its old ledger)
+    if (off.ensure((size_t)n * (row_cap + 1) * 8, &err) || id.ensure((size_t)n * ent_cap * 2, &err) || lp.ensure((size_t)n * ent_cap * 8, &err))
+      return fail(CTCDEC_ERR_DEVICE, err);
+    for (int32_t u = 0; u < n && rs->led_off.p && !first; ++u) {
+      const size_t rows = (size_t)rs->frames[(size_t)u], used = (size_t)rs->led_used[(size_t)u];
+      if (be::d2d((char*)off.p + (size_t)u * (row_cap + 1) * 8, (const char*)rs->led_off.p + (size_t)u * (rs->led_row_cap + 1) * 8, (rows + 1) * 8, &err) ||
+          (used && (be::d2d((char*)id.p + (size_t)u * ent_cap * 2, (const char*)rs->led_id.p + (size_t)u * rs->led_ent_cap * 2, used * 2, &err) ||
+                    be::d2d((char*)lp.p + (size_t)u * ent_cap * 8, (const char*)rs->led_lp.p + (size_t)u * rs->led_ent_cap * 8, used * 8, &err))))
+        return fail(CTCDEC_ERR_DEVICE, err);
+    }
+    rs->led_off = std::move(off);
+    rs->led_id = std::move(id);
+    rs->led_lp = std::move(lp);
+    rs->led_row_cap = row_cap;
+    rs->led_ent_cap = ent_cap;
+  }
+  if (first && be::zero((char*)rs->sstate.p + rs->sstate_bytes(), (size_t)n * 8 + 8, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+  rs->led_fold = c.led;
+  return CTCDEC_OK;
+}
+
+// ... and the chunk's rows into it: once per push, behind the beam kernel on the decode stream.
+static int append_ledger(DecodeCall& c) {
+  ctcdec_stream* rs = c.rs;
+  ctcdec_decoder* dec = c.dec;
+  const int32_t n = c.n_utts;
+  const uint32_t max_surv = (uint32_t)c.prune.max_surv;
+#ifdef CTC_SIM  // (the simulator's device memory is host memory: the kernel's body, row by row)
+  const uint32_t* cnt = (const uint32_t*)dec->w_scnt.p;
+  const uint16_t* sid = (const uint16_t*)dec->w_sid.p;
+  const double* slp = (const double*)dec->w_slp.p;
+  uint64_t* used_out = (uint64_t*)((char*)rs->sstate.p + rs->sstate_bytes());
+  for (int32_t u = 0; u < n; ++u) {
+    uint64_t* ro = (uint64_t*)rs->led_off.p + (size_t)u * (rs->led_row_cap + 1);
+    uint16_t* did = (uint16_t*)rs->led_id.p + (size_t)u * rs->led_ent_cap;
+    double* dlp = (double*)rs->led_lp.p + (size_t)u * rs->led_ent_cap;
+    const size_t r0 = (size_t)rs->frames[(size_t)u];
+    if (r0 == 0) ro[0] = 0;
+    uint64_t base = ro[r0];
+    for (int32_t t = 0; t < c.utt_frames[u]; ++t) {
+      const size_t src = (size_t)c.row0[(size_t)u] + (size_t)t;
+      const uint32_t k = ledger_row_count(cnt[src], max_surv);
+      if (base + k > rs->led_ent_cap || r0 + (size_t)t + 1 > rs->led_row_cap) {
+        used_out[n] = 1;
+        break;
+      }
+      ledger_put_row(sid + src * max_surv, slp + src * max_surv, k, did + base, dlp + base);
+      base += k;
+      ro[r0 + (size_t)t + 1] = base;
+    }
+    used_out[u] = base;
+  }
+#else
+  std::vector<uint32_t> r0((size_t)n);
+  for (int32_t u = 0; u < n; ++u) r0[(size_t)u] = (uint32_t)rs->frames[(size_t)u];
+  if (upload_staged(dec, dec->w_ledrow, r0, &c.err)) return fail(CTCDEC_ERR_DEVICE, c.err);
+  be::LedgerAppendArgs la;
+  la.n_streams = n;
+  la.utt_row0 = (const int64_t*)dec->w_row0.p;
+  la.surv_cnt = (const uint32_t*)dec->w_scnt.p;
+  la.surv_id = (const uint16_t*)dec->w_sid.p;
+  la.surv_lp = (const double*)dec->w_slp.p;
+  la.max_surv = (int32_t)max_surv;
+  la.led_row0 = (const uint32_t*)dec->w_ledrow.p;
+  la.row_off = (uint64_t*)rs->led_off.p;
+  la.id = (uint16_t*)rs->led_id.p;
+  la.lp = (double*)rs->led_lp.p;
+  la.row_cap = rs->led_row_cap;
+  la.ent_cap = rs->led_ent_cap;
+  la.used_out = (uint64_t*)((char*)rs->sstate.p + rs->sstate_bytes());
+  la.overrun = la.used_out + n;
+  if (be::launch_ledger_append(la, &c.err)) return fail(CTCDEC_ERR_DEVICE, c.err);
+#endif
+  return CTCDEC_OK;
+}
+
 // 7. Prune and launch: the prune stage with the beam stage queued right behind it, or -- late_beam -- once it has reported.
 static int prune_and_launch(DecodeCall& c) {
   PruneStage& s = c.prune;
@@ -1454,7 +1593,13 @@ static int prune_and_launch(DecodeCall& c) {
     c.ba.surv_x16 = (int32_t)std::min(1.0e6, std::max(1.0, mean * 16.0 + 0.5));
     if (int rc = reserve_pay(c)) return rc;
   }
-  return c.late_beam ? run_beam(c) : CTCDEC_OK;
+  // (a stream with a ledger: room for the chunk first -- a failed growth leaves the stream where it was --, the append behind
+  // the beam kernel. The lists are final here: every redo of the prune stage is over.)
+  if (c.led)
+    if (int rc = reserve_ledger(c)) return rc;
+  if (c.late_beam)
+    if (int rc = run_beam(c)) return rc;
+  return c.led && c.R > 0 ? append_ledger(c) : CTCDEC_OK;  // (a read pushes no rows)
 }
 
 // (rare: flat posteriors that complete a word for every beam in every frame) the beam stage again, with the worst case reserved
@@ -1485,9 +1630,20 @@ static int redo_outgrown(DecodeCall& c) {
 // the streams have moved on, whatever the chunk's outcome: the host mirrors of their counters
 static int refresh_stream_mirrors(DecodeCall& c) {
   ctcdec_stream* rs = c.rs;
-  if (be::d2h(rs->mirror.data(), rs->sstate.p, (size_t)c.n_utts * sizeof(StreamState), &c.err)) return fail(CTCDEC_ERR_DEVICE, c.err);
+  const size_t n = (size_t)c.n_utts;
+  bool overrun = false;
+  if (c.led) {  // (the ledger's entry counts ride behind the counters: one read for both)
+    rs->led_back.resize(2 * n + n + 1);
+    if (be::d2h(rs->led_back.data(), rs->sstate.p, rs->sstate_bytes() + n * 8 + 8, &c.err)) return fail(CTCDEC_ERR_DEVICE, c.err);
+    memcpy(rs->mirror.data(), rs->led_back.data(), rs->sstate_bytes());
+    for (size_t u = 0; u < n; ++u) rs->led_used[u] = rs->led_back[2 * n + u];
+    overrun = rs->led_back[3 * n] != 0;
+  } else if (be::d2h(rs->mirror.data(), rs->sstate.p, rs->sstate_bytes(), &c.err)) {
+    return fail(CTCDEC_ERR_DEVICE, c.err);
+  }
   for (int32_t u = 0; u < c.n_utts; ++u) rs->frames[(size_t)u] += c.utt_frames[u];
   rs->pushes += 1;
+  if (c.led) c.led_rows.assign(rs->frames.begin(), rs->frames.end());
   if (c.stream->eos) {  // decoder.py:681-728 with is_end: the next chunk starts a new utterance
     for (auto& m : rs->mirror) {
       m.n_carry = 0;
@@ -1498,7 +1654,9 @@ static int refresh_stream_mirrors(DecodeCall& c) {
     rs->has_import = false;
     std::fill(rs->frames.begin(), rs->frames.end(), 0);
     rs->pushes = 0;
+    rs->led_fold = 0;  // (the next utterance chooses anew; this call's own fold still reads the rows: c.led_rows)
   }
+  if (overrun) return fail(CTCDEC_ERR_INTERNAL, "survivor ledger: a chunk ran past the room reserved for it");
   return CTCDEC_OK;
 }
 
@@ -1542,6 +1700,11 @@ static int collect_counters(DecodeCall& c) {
 // The closing step of every result form. When the beam stage's output is back: the kernels' times, the profile counters ...
 static int kernel_stats(DecodeCall& c) {
   ctcdec_result* res = c.res.get();
+#ifndef CTC_SIM
+  if (c.led && c.R > 0 && c.host_timing)
+    fprintf(stderr, "[ctcdec host] survivor ledger: surv_ledger_append kernel %.4f ms, %zu bytes reserved\n", be::last_ledger_append_ms(),
+            c.rs->led_bytes());
+#endif
   be::last_timing(&res->ms[0], &res->ms[1]);
   res->beam_kernel = be::last_beam_kernel();
   if (c.dec->profile && be::d2h(c.dec->prof, c.dec->w_prof.p, N_PROF * 8, &c.err)) return fail(CTCDEC_ERR_DEVICE, c.err);
@@ -1596,7 +1759,9 @@ static int finish_stream_push(DecodeCall& c) {
 // this call's prune stage left there (whatever max_surv the overflow redo ended with), one kernel folds each run and one
 // float64 per token comes back -- in the order of ctcdec_result_token_frames. A label that is missing from a frame's
 // survivors is a broken invariant ("Token confidences"): the call fails, there is no substitute value.
+static int stream_token_confidences(DecodeCall& c);
 static int token_confidences(DecodeCall& c) {
+  if (c.rs) return stream_token_confidences(c);
   ctcdec_decoder* dec = c.dec;
   ctcdec_result* res = c.res.get();
   std::string& err = c.err;
@@ -1663,6 +1828,74 @@ static int token_confidences(DecodeCall& c) {
   if (c.host_timing)
     fprintf(stderr, "[ctcdec host] token confidences: %zu tokens, pack + upload %.3f ms, kernel %.3f ms, download %.3f ms\n", nt,
             logp_ms[0], logp_ms[1], logp_ms[2]);
+  return CTCDEC_OK;
+}
+
+// ... of a device-resident stream: a token's frames may lie in any chunk pushed so far, so its run is rows of the stream's
+// survivor ledger (row = frame - the stream's first frame) and token_logp_ledger<fold> folds it; the rest is the same.
+static int stream_token_confidences(DecodeCall& c) {
+  ctcdec_decoder* dec = c.dec;
+  ctcdec_stream* rs = c.rs;
+  ctcdec_result* res = c.res.get();
+  std::string& err = c.err;
+  if (!c.led || c.led != c.fold || c.led_rows.size() != (size_t)c.n_utts) return fail(CTCDEC_ERR_INTERNAL, "token confidences: the stream keeps no ledger");
+  auto t0 = Clock::now();
+  size_t nt = 0;
+  for (const auto& beams : res->utts)
+    for (const BeamResult& b : beams) nt += b.tok.size() / 3;
+  if (dec->h_truns.ensure(std::max<size_t>(nt, 1) * sizeof(LedgerRun), &err)) return fail(CTCDEC_ERR_DEVICE, err);
+  LedgerRun* runs = (LedgerRun*)dec->h_truns.p;
+  size_t o = 0;
+  for (int32_t u = 0; u < c.n_utts; ++u)
+    for (const BeamResult& b : res->utts[(size_t)u]) {
+      const int32_t* t = b.tok.data();
+      for (size_t k = 0, n = b.tok.size() / 3; k < n; ++k, ++o, t += 3) {
+        const int64_t s = (int64_t)t[1] - rs->led_first[(size_t)u], e = (int64_t)t[2] - rs->led_first[(size_t)u];
+        if (t[0] < 0 || t[0] >= c.V || s < 0 || e <= s || e > c.led_rows[(size_t)u]) return fail(CTCDEC_ERR_INTERNAL, "token frames out of range");
+        runs[o] = LedgerRun{(uint32_t)u, (uint32_t)s, (uint32_t)(e - s), (uint32_t)t[0]};
+      }
+    }
+  res->tk_logp.resize(nt);
+  uint32_t missing = 0;
+  double kernel_ms = 0;
+#ifdef CTC_SIM  // (the simulator's device memory is host memory: the kernel's body, token by token)
+  for (size_t i = 0; i < nt; ++i) {
+    const size_t u = runs[i].stream;
+    const uint64_t* ro = (const uint64_t*)rs->led_off.p + u * (rs->led_row_cap + 1);
+    const uint16_t* id = (const uint16_t*)rs->led_id.p + u * rs->led_ent_cap;
+    const double* lp = (const double*)rs->led_lp.p + u * rs->led_ent_cap;
+    missing += c.fold == LOGP_MEAN  ? ledger_logp_of<LOGP_MEAN>(runs[i], ro, id, lp, &res->tk_logp[i])
+               : c.fold == LOGP_MIN ? ledger_logp_of<LOGP_MIN>(runs[i], ro, id, lp, &res->tk_logp[i])
+                                    : ledger_logp_of<LOGP_MAX>(runs[i], ro, id, lp, &res->tk_logp[i]);
+  }
+#else
+  if (nt) {
+    if (dec->w_truns.ensure(nt * sizeof(LedgerRun), &err) || be::h2d(dec->w_truns.p, runs, nt * sizeof(LedgerRun), &err) ||
+        dec->w_tlogp.ensure(nt * 8, &err) || dec->w_tmiss.ensure(16, &err) || be::zero(dec->w_tmiss.p, 16, &err))
+      return fail(CTCDEC_ERR_DEVICE, err);
+    be::LedgerLogpArgs ta;
+    ta.runs = (const LedgerRun*)dec->w_truns.p;
+    ta.n_tokens = (int64_t)nt;
+    ta.fold = c.fold;
+    ta.row_off = (const uint64_t*)rs->led_off.p;
+    ta.id = (const uint16_t*)rs->led_id.p;
+    ta.lp = (const double*)rs->led_lp.p;
+    ta.row_cap = rs->led_row_cap;
+    ta.ent_cap = rs->led_ent_cap;
+    ta.out = (double*)dec->w_tlogp.p;
+    ta.missing = (uint32_t*)dec->w_tmiss.p;
+    if (be::launch_ledger_logp(ta, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+    if (c.host_timing) kernel_ms = be::last_ledger_logp_ms();
+    if (be::d2h(res->tk_logp.data(), dec->w_tlogp.p, nt * 8, &err) || be::d2h(&missing, dec->w_tmiss.p, 4, &err))
+      return fail(CTCDEC_ERR_DEVICE, err);
+  }
+#endif
+  if (missing)
+    return fail(CTCDEC_ERR_INTERNAL, "token confidences: " + std::to_string(missing) + " token frames whose label is not in the frame's ledger row");
+  res->has_logp = true;
+  if (c.host_timing)
+    fprintf(stderr, "[ctcdec host] stream token confidences: %zu tokens, token_logp_ledger kernel %.3f ms, all of it %.3f ms\n", nt, kernel_ms,
+            ms(t0, Clock::now()));
   return CTCDEC_OK;
 }
 
@@ -1771,7 +2004,8 @@ int ctcdec_stream_open(ctcdec_decoder* dec, int32_t n_streams, const ctcdec_lm_s
   st->imp_off.assign((size_t)n_streams + 1, 0);
   if (st->carry.ensure((size_t)n_streams * ctcdec_stream::CAP * sizeof(ImportBeam), &err) ||
       (st->K > 1 && st->carry_x.ensure((size_t)n_streams * ctcdec_stream::CAP * (size_t)(st->K - 1) * sizeof(LmState), &err)) ||
-      st->sstate.ensure((size_t)n_streams * sizeof(StreamState), &err) ||
+      // (behind the counters: room for a survivor ledger's entry counts and its overrun word, read back with them)
+      st->sstate.ensure((size_t)n_streams * (sizeof(StreamState) + 8) + 8, &err) ||
       be::h2d(st->sstate.p, st->mirror.data(), (size_t)n_streams * sizeof(StreamState), &err))
     return fail(CTCDEC_ERR_DEVICE, err);
   *out = st.release();
@@ -1784,7 +2018,10 @@ int ctcdec_stream_push(ctcdec_stream* st, const void* const* chunk_logits, const
   if (!st || !params || !chunk_frames) return fail(CTCDEC_ERR_ARG, "bad arguments");
   if ((want_result || is_end) && !out) return fail(CTCDEC_ERR_ARG, "a result is wanted but there is nowhere to put it");
   std::vector<int32_t> ff((size_t)st->n);
-  for (int32_t u = 0; u < st->n; ++u) ff[(size_t)u] = first_frame ? first_frame[u] : (int32_t)st->frames[(size_t)u];
+  // (a stream with a survivor ledger numbers its frames from its first chunk's first_frame)
+  const bool led = st->led_fold != 0 && st->pushes > 0;
+  for (int32_t u = 0; u < st->n; ++u)
+    ff[(size_t)u] = first_frame ? first_frame[u] : (int32_t)st->frames[(size_t)u] + (led ? st->led_first[(size_t)u] : 0);
   const StreamIn sin{ff.data(), st->has_import ? st->imp_beams.data() : nullptr, st->imp_off.data(), st->imp_blob.data(),
                      (force_next_word || is_end) ? 1 : 0, is_end ? 1 : 0};
   ctcdec_result* res = nullptr;
@@ -1975,6 +2212,12 @@ static int decode_host_sliced(ctcdec_decoder* dec, const void* const* utt_logits
 int ctcdec_stream_frames(const ctcdec_stream* st, int64_t* frames_out) {
   if (!st || !frames_out) return fail(CTCDEC_ERR_ARG, "bad arguments");
   for (int32_t u = 0; u < st->n; ++u) frames_out[u] = st->frames[(size_t)u];
+  return CTCDEC_OK;
+}
+
+int ctcdec_stream_ledger_bytes(const ctcdec_stream* st, int64_t* bytes_out) {
+  if (!st || !bytes_out) return fail(CTCDEC_ERR_ARG, "bad arguments");
+  *bytes_out = (int64_t)st->led_bytes();
   return CTCDEC_OK;
 }
 

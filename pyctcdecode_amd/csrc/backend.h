@@ -9,6 +9,7 @@
 #include <string>
 
 #include "beam_core.h"
+#include "surv_ledger.h"
 #include "token_logp.h"
 
 namespace ctc {
@@ -176,6 +177,44 @@ struct TokenLogpArgs {
 };
 int launch_token_logp(const TokenLogpArgs& a, std::string* err);
 double last_token_logp_ms();  // the last launch_token_logp's kernel time (HIP events); waits for the kernel
+
+// A resident stream's survivor ledger (surv_ledger.h). Append: once per push, when the chunk's survivor lists are final, one
+// wavefront per stream copies the first min(surv_cnt, max_surv) entries of each of the chunk's rows (utt_row0[u] ..
+// utt_row0[u + 1] of the strided arrays) behind the stream's ledger rows led_row0[u] and extends row_off. Stream u's entry
+// count after the chunk goes to used_out[u]; a stream that would pass row_cap / ent_cap (the host reserves the chunk's worst
+// case: never) writes nothing there and sets *overrun.
+struct LedgerAppendArgs {
+  int32_t n_streams;
+  const int64_t* utt_row0;    // [n_streams + 1] (device)
+  const uint32_t* surv_cnt;
+  const uint16_t* surv_id;
+  const double* surv_lp;
+  int32_t max_surv;
+  const uint32_t* led_row0;   // [n_streams] (device): ledger rows of each stream before this chunk
+  uint64_t* row_off;          // [n_streams * (row_cap + 1)]
+  uint16_t* id;               // [n_streams * ent_cap]
+  double* lp;                 // [n_streams * ent_cap]
+  uint64_t row_cap, ent_cap;  // rows / entries per stream
+  uint64_t* used_out;         // [n_streams] (device)
+  uint64_t* overrun;          // [1] (device), zeroed when the ledger was made
+};
+int launch_ledger_append(const LedgerAppendArgs& a, std::string* err);
+// Token confidences of a resident stream: launch_token_logp over ledger rows.
+struct LedgerLogpArgs {
+  const LedgerRun* runs;  // [n_tokens] (device)
+  int64_t n_tokens;
+  int32_t fold;           // LOGP_MEAN / LOGP_MIN / LOGP_MAX
+  const uint64_t* row_off;
+  const uint16_t* id;
+  const double* lp;
+  uint64_t row_cap, ent_cap;
+  double* out;            // [n_tokens] (device)
+  uint32_t* missing;      // [1] (device), zeroed by the caller
+};
+int launch_ledger_logp(const LedgerLogpArgs& a, std::string* err);
+// the last launch_ledger_append's / launch_ledger_logp's kernel time (HIP events); waits for the kernel
+double last_ledger_append_ms();
+double last_ledger_logp_ms();
 
 // stage timing (ms) of the last launch_prune / launch_beam pair, measured on the decode stream
 void last_timing(double* prune_ms, double* beam_ms);

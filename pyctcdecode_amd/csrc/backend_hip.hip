@@ -2358,5 +2358,103 @@ double last_token_logp_ms() {
   return hipEventElapsedTime(&ms, g_logp_ev[0], g_logp_ev[1]) == hipSuccess ? (double)ms : 0.0;
 }
 
+// Survivor ledger, append (surv_ledger.h): one wavefront per stream. A step takes 64 of the chunk's rows, one per lane: the
+// clamped counts are scanned across the wave (DPP, no LDS, no barrier), the running offset of the stream is wave-uniform and
+// carried from step to step, every lane writes its row's end into row_off and copies its row's handful of (id, lp) pairs.
+// Rows of one stream are contiguous in the strided arrays, so a step reads 64 consecutive counts and 64 rows max_surv entries
+// apart, and writes one contiguous piece of the ledger. Plain vector stores throughout.
+__global__ __launch_bounds__(64) void surv_ledger_append(LedgerAppendArgs a) {
+  const uint32_t u = blockIdx.x, lane = threadIdx.x;
+  const int64_t src0 = a.utt_row0[u];
+  const uint32_t T = (uint32_t)(a.utt_row0[u + 1] - src0);
+  const uint32_t r0 = a.led_row0[u];
+  const uint32_t max_surv = (uint32_t)a.max_surv;
+  uint64_t* ro = a.row_off + (size_t)u * (a.row_cap + 1);
+  uint16_t* did = a.id + (size_t)u * a.ent_cap;
+  double* dlp = a.lp + (size_t)u * a.ent_cap;
+  if ((uint64_t)r0 + T > a.row_cap) {  // (the host reserved the rows: never)
+    if (lane == 0) *a.overrun = 1;
+    return;
+  }
+  uint64_t base = 0;  // wave-uniform: entries of the stream before the step's rows
+  if (r0 == 0) {
+    if (lane == 0) ro[0] = 0;
+  } else {
+    base = ro[r0];
+  }
+  bool bad = false;
+  for (uint32_t t0 = 0; t0 < T; t0 += 64) {
+    const uint32_t t = t0 + lane;
+    const size_t src = (size_t)(src0 + t);
+    const uint32_t cnt = t < T ? ledger_row_count(a.surv_cnt[src], max_surv) : 0u;
+    const uint32_t incl = wave_incl_scan_u32(cnt);
+    const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+    const uint64_t end = base + incl;
+    if (t < T) {
+      if (end <= a.ent_cap) {
+        ro[(size_t)r0 + t + 1] = end;
+        ledger_put_row(a.surv_id + src * max_surv, a.surv_lp + src * max_surv, cnt, did + (end - cnt), dlp + (end - cnt));
+      } else {
+        bad = true;
+      }
+    }
+    base += total;
+  }
+  if (bad) *a.overrun = 1;  // (the host reserved the chunk's worst case: never)
+  else if (lane == 0) a.used_out[u] = base;
+}
+
+template <int FOLD>
+__global__ __launch_bounds__(256) void token_logp_ledger(LedgerLogpArgs a) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.n_tokens) return;
+  const LedgerRun t = a.runs[i];
+  double v;
+  const uint32_t missing = ledger_logp_of<FOLD>(t, a.row_off + (size_t)t.stream * (a.row_cap + 1), a.id + (size_t)t.stream * a.ent_cap,
+                                                a.lp + (size_t)t.stream * a.ent_cap, &v);
+  a.out[i] = v;
+  if (missing) atomicAdd(a.missing, missing);
+}
+
+static hipEvent_t g_led_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // append start / end, fold start / end
+static int ledger_events() {
+  if (g_led_ev[0]) return 0;
+  for (int k = 0; k < 4; ++k)
+    if (hipEventCreate(&g_led_ev[k]) != hipSuccess) return -1;
+  return 0;
+}
+static double ledger_ms(int k) {
+  float ms = 0.f;
+  if (!g_led_ev[k + 1] || hipEventSynchronize(g_led_ev[k + 1]) != hipSuccess) return 0.0;
+  return hipEventElapsedTime(&ms, g_led_ev[k], g_led_ev[k + 1]) == hipSuccess ? (double)ms : 0.0;
+}
+int launch_ledger_append(const LedgerAppendArgs& a, std::string* err) {
+  if (a.n_streams <= 0) return 0;
+  HIP_TRY(ledger_events() ? hipErrorUnknown : hipSuccess);
+  HIP_TRY(hipEventRecord(g_led_ev[0], g_stream));
+  hipLaunchKernelGGL(surv_ledger_append, dim3((unsigned)a.n_streams), dim3(64), 0, g_stream, a);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(g_led_ev[1], g_stream));
+  return 0;
+}
+int launch_ledger_logp(const LedgerLogpArgs& a, std::string* err) {
+  if (a.n_tokens <= 0) return 0;
+  HIP_TRY(ledger_events() ? hipErrorUnknown : hipSuccess);
+  const dim3 grid((unsigned)((a.n_tokens + 255) / 256)), block(256);
+  HIP_TRY(hipEventRecord(g_led_ev[2], g_stream));
+  if (a.fold == LOGP_MEAN) hipLaunchKernelGGL(token_logp_ledger<LOGP_MEAN>, grid, block, 0, g_stream, a);
+  else if (a.fold == LOGP_MIN) hipLaunchKernelGGL(token_logp_ledger<LOGP_MIN>, grid, block, 0, g_stream, a);
+  else if (a.fold == LOGP_MAX) hipLaunchKernelGGL(token_logp_ledger<LOGP_MAX>, grid, block, 0, g_stream, a);
+  else {
+    if (err) *err = "unknown token_logp fold";
+    return -1;
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(g_led_ev[3], g_stream));
+  return 0;
+}
+double last_ledger_append_ms() { return ledger_ms(0); }
+double last_ledger_logp_ms() { return ledger_ms(2); }
+
 }  // namespace be
 }  // namespace ctc

@@ -58,6 +58,22 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
 #undef CTC_MAX_STEP
   return (uint32_t)__builtin_amdgcn_readlane(x, 63);
 }
+// Wave-wide INCLUSIVE prefix sum of 32-bit unsigned values, the same six steps with an add: row_shr 1 / 2 / 4 / 8 scan each row
+// of 16 lanes (lanes without a source read 0), row_bcast:15 adds a row's total to the row behind it (rows 1 and 3), row_bcast:31
+// the total of rows 0 + 1 to rows 2 and 3. Every lane ends with the sum of the lanes up to and including itself; lane 63 holds
+// the wave's total. All 64 lanes have to be active.
+__device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v) {
+  int x = (int)v;
+#define CTC_SCAN_STEP(CTRL, ROWS, BOUND) x += __builtin_amdgcn_update_dpp(0, x, CTRL, ROWS, 0xf, BOUND);
+  CTC_SCAN_STEP(0x111, 0xf, true)
+  CTC_SCAN_STEP(0x112, 0xf, true)
+  CTC_SCAN_STEP(0x114, 0xf, true)
+  CTC_SCAN_STEP(0x118, 0xf, true)
+  CTC_SCAN_STEP(0x142, 0xa, false)
+  CTC_SCAN_STEP(0x143, 0xc, false)
+#undef CTC_SCAN_STEP
+  return (uint32_t)x;
+}
 // Wave-wide maximum of 64-bit unsigned values as two 32-bit ones: the high words, then the low words of the lanes that hold the
 // highest high word (~17 VALU instructions; the 64-bit DPP reduction is six rounds of two moves, a 64-bit compare and two
 // selects plus the moves that fill the lanes without a source: ~45).

@@ -84,6 +84,28 @@ class LMBeam(Beam):
 
 
 @dataclasses.dataclass(frozen=True)
+class TokenLMBeam(LMBeam):
+    """An LMBeam with the frames of its tokens (partial_decode_beams(..., token_frames=True)), as TokenOutputBeam lists
+    them, from the START of the stream: the tokens of the words of ``text_frames`` (words closed by ``force_next_word``
+    included), then those of the still open ``partial_word`` -- the last of which ends at ``partial_frames[1]``. Frames are
+    absolute, in the numbering of ``text_frames`` / ``partial_frames``."""
+
+    token_frames: List[Tuple[str, Frames]]
+
+
+@dataclasses.dataclass(frozen=True)
+class ConfidenceLMBeam(TokenLMBeam):
+    """A TokenLMBeam with confidences (partial_decode_beams(..., confidence="mean" | "min" | "max")), as
+    ConfidenceOutputBeam defines them. ``token_logp`` is parallel to ``token_frames`` -- a token that runs across a chunk
+    boundary, or lies wholly in an earlier chunk, is folded over all of its frames, and its value is the float64
+    decode_beams(confidence=...) gives for the same frames. ``word_logp`` is parallel to ``text_frames``: closed words only,
+    the smallest ``token_logp`` among the word's tokens."""
+
+    token_logp: List[float]
+    word_logp: List[float]
+
+
+@dataclasses.dataclass(frozen=True)
 class OutputBeam:
     """decoder.py:102-118."""
 
@@ -196,6 +218,7 @@ class TokenFrames:
         return TokenFrames, (self.label, self.start, self.end, self.offsets, self.labels, self.logp)
 
 
+_LM_BEAM_FIELDS = dataclasses.fields(LMBeam)
 NULL_FRAMES: Frames = (-1, -1)
 EMPTY_START_BEAM = Beam("", "", "", None, [], NULL_FRAMES, 0.0)
 
@@ -410,6 +433,10 @@ class _DeviceStreams:
         self.memos: List[Dict[Any, Any]] = []
         self.parents: Optional[List[List[Beam]]] = None  # the caller's beams of the last import
         self.lists: List[Any] = []  # weak references to the lazy lists of the current generation
+        # tokens / confidences (ctcdec_params.token_frames of the stream's chunks; a fold is fixed by the first chunk) and, for
+        # the fold's frame numbering, where the next chunk of each stream has to begin
+        self.token_mode = 0
+        self.next_frame: Optional[List[int]] = None
         h = C.c_void_p()
         self.lib.check(self.lib.dll.ctcdec_stream_open(decoder._handle, n, None, C.byref(h)))
         self.handle = h
@@ -540,6 +567,28 @@ class _DeviceStreams:
                 lst._peeked = True
 
     def unpack(self, res) -> List[List[LMBeam]]:
+        """The beams of a stream result; with token_frames / confidence as TokenLMBeams / ConfidenceLMBeams."""
+        out = self._unpack_plain(res)
+        mode = int(self.params.token_frames) if self.params is not None else 0
+        if not mode:
+            return out
+        with_logp = mode > 1
+        tf = self.decoder._token_frames(res, sum(len(bs) for bs in out), with_logp)
+        k = 0
+        for bs in out:
+            for i, b in enumerate(bs):
+                base = tuple(getattr(b, f.name) for f in _LM_BEAM_FIELDS)
+                toks = tf.of(k)
+                if with_logp:
+                    lps = tf.logp_of(k)
+                    words = _word_logps([(None, f) for f in b.text_frames], toks, lps)
+                    bs[i] = ConfidenceLMBeam(*base, toks, lps, words)
+                else:
+                    bs[i] = TokenLMBeam(*base, toks)
+                k += 1
+        return out
+
+    def _unpack_plain(self, res) -> List[List[LMBeam]]:
         dec = self.decoder
         lib = self.lib
         n = self.n
@@ -1498,9 +1547,18 @@ class BeamSearchDecoderCTC:
         hotword_scorer: Optional[HotwordScorer] = None,
         force_next_word: bool = False,
         is_end: bool = False,
+        token_frames: bool = False,
+        confidence: Optional[str] = None,
     ) -> List[List[LMBeam]]:
         """Many independent streams advanced by one chunk each in ONE device launch (extension of
         partial_decode_beams, decoder.py:681-728).
+
+        token_frames=True: the beams are TokenLMBeams, with the tokens of the stream so far; confidence="mean" | "min" | "max":
+        ConfidenceLMBeams, with per-token and per-word confidences as decode_beams(confidence=...) gives them. Both need the
+        stream to be device-resident from its start -- beams handed back unchanged, the default; lists the caller built or
+        edited, a seeded memo, a changed hot-word set or CTCDEC_RESIDENT_STREAMS=0 raise NotImplementedError --, and a
+        confidence has to be asked for from the stream's first chunk on, with the same fold and with processed_frames that
+        continue the stream (ValueError otherwise).
 
         The streams are device-resident (ctcdec_stream_*): the beams, their LM states and the words decoded so far stay
         on the GPU between chunks. What comes back is, per stream, a list of LMBeam that fills itself the first time it
@@ -1512,12 +1570,15 @@ class BeamSearchDecoderCTC:
         with self._call_lock:
             return self._partial_decode_beams_batch_locked(
                 logits_list, cached_lm_scores_list, cached_p_lm_scores_list, beams_list, processed_frames_list,
-                beam_width, beam_prune_logp, token_min_logp, prune_history, hotword_scorer, force_next_word, is_end)
+                beam_width, beam_prune_logp, token_min_logp, prune_history, hotword_scorer, force_next_word, is_end,
+                token_frames, confidence)
 
     def _partial_decode_beams_batch_locked(
         self, logits_list, cached_lm_scores_list, cached_p_lm_scores_list, beams_list, processed_frames_list,
         beam_width, beam_prune_logp, token_min_logp, prune_history, hotword_scorer, force_next_word, is_end,
+        token_frames=False, confidence=None,
     ) -> List[List[LMBeam]]:
+        token_mode = _confidence_fold(confidence) or int(bool(token_frames))
         n = len(logits_list)
         if n == 0:
             return []
@@ -1542,10 +1603,6 @@ class BeamSearchDecoderCTC:
         # (the carried beams' view of their open word depends on the words: another list means importing them again)
         key = tuple(unigrams) if hot_sets is None else ("per-stream",) + tuple(
             hot_sets[0][k][0] if k >= 0 else () for k in hot_sets[1])
-        if hot_sets is None and key != self._hot_key:
-            blob, off = B.pack_strings(unigrams)
-            self._lib.check(self._lib.dll.ctcdec_set_hotwords(self._handle, blob, B.off_ptr(off), len(unigrams)))
-            self._hot_key = key
         for beams in beams_list:
             if not isinstance(beams, _ResidentBeams) and len(beams) == 0:
                 raise ValueError("a stream needs at least one beam (use get_starting_state())")
@@ -1560,13 +1617,25 @@ class BeamSearchDecoderCTC:
         # which device streams do these beams belong to?
         streams: Optional[_DeviceStreams] = None
         first = beams_list[0]
-        if (isinstance(first, _ResidentBeams) and first._streams.alive(self) and first._streams.n == n and
-                first._streams.hot_key == key and
-                all(isinstance(b, _ResidentBeams) and b._streams is first._streams and b._index == u and b._current()
-                    for u, b in enumerate(beams_list))):
+        handed_back = (isinstance(first, _ResidentBeams) and first._streams.alive(self) and first._streams.n == n and
+                       all(isinstance(b, _ResidentBeams) and b._streams is first._streams and b._index == u and b._current()
+                           for u, b in enumerate(beams_list)))
+        resident = handed_back and first._streams.hot_key == key
+        at_start = not resident and all(len(b) == 1 and b[0] == EMPTY_START_BEAM for b in beams_list)
+        fresh = at_start and all(self._memo_starts_at_default(m) for m in cached_lm_scores_list)
+        frames_in = [int(p) for p in processed_frames_list]
+        if token_mode or (resident and first._streams.token_mode > 1):
+            # tokens and confidences come from the chains and the survivor ledger of a stream that has been on the device from
+            # its start: every other route is refused here, before any stream is opened, imported into or retired
+            self._check_stream_tokens(token_mode, lazy_ok, handed_back, resident, at_start, fresh,
+                                      first._streams if resident else None, frames_in)
+        if hot_sets is None and key != self._hot_key:
+            blob, off = B.pack_strings(unigrams)
+            self._lib.check(self._lib.dll.ctcdec_set_hotwords(self._handle, blob, B.off_ptr(off), len(unigrams)))
+            self._hot_key = key
+        if resident:
             streams = first._streams  # handed back unchanged: nothing to import
-        elif (all(len(b) == 1 and b[0] == EMPTY_START_BEAM for b in beams_list) and
-              all(self._memo_starts_at_default(m) for m in cached_lm_scores_list)):
+        elif fresh:
             streams = _DeviceStreams(self, n)  # the reference's starting state: the model's own start state, nothing scored
         else:
             # built or edited by the caller (or fed to another call in between): the host resolves their strings
@@ -1579,9 +1648,10 @@ class BeamSearchDecoderCTC:
             raise ValueError("the logits live on cuda:%d but this decoder was built for cuda:%d (one process per GPU: "
                              "LOCAL_RANK / CTCDEC_DEVICE pick the device)" % (batch.device_index, self._device))
         ptrs, frames = _c_arrays(batch)
-        first_frames = (C.c_int32 * n)(*[int(p) for p in processed_frames_list])
+        first_frames = (C.c_int32 * n)(*frames_in)
         want = bool(is_end) or not lazy_ok
         res = C.c_void_p()
+        params.token_frames = token_mode
         streams.retire_lists()
         if hot_sets is not None:
             self._arm_hot_sets(hot_sets)
@@ -1590,6 +1660,12 @@ class BeamSearchDecoderCTC:
             int(bool(force_next_word)), int(bool(is_end)), int(want), C.byref(res)))
         streams.params = params
         streams.memos = list(cached_lm_scores_list)
+        if is_end:
+            streams.token_mode, streams.next_frame = 0, None
+        else:
+            if streams.next_frame is None:
+                streams.token_mode = token_mode
+            streams.next_frame = [f + int(t) for f, t in zip(frames_in, batch.frames)]
         try:
             if want:
                 return streams.unpack(res)
@@ -1597,6 +1673,36 @@ class BeamSearchDecoderCTC:
             if res:
                 self._lib.dll.ctcdec_result_free(res)
         return streams.lazy_lists()
+
+    @staticmethod
+    def _check_stream_tokens(token_mode: int, lazy_ok: bool, handed_back: bool, resident: bool, at_start: bool, fresh: bool,
+                             streams: Optional[_DeviceStreams], frames_in: List[int]) -> None:
+        """partial_decode_beams(token_frames=... / confidence=...): the routes that cannot serve them, and a stream's fold and
+        frame numbering (what the library refuses itself, api.cpp: check_stream_tokens, raised here while the previous
+        chunk's lists are still readable)."""
+        what = "token_frames / confidence of a streaming decode"
+        if not lazy_ok:
+            raise NotImplementedError(what + " need device-resident streams, which CTCDEC_RESIDENT_STREAMS=0 turns off")
+        if streams is None:
+            if handed_back:
+                raise NotImplementedError(what + ": the hot words changed, so the beams are imported again and their chains "
+                                                 "no longer reach back to the start of the stream")
+            if at_start and not fresh:
+                raise NotImplementedError(what + ": cached_lm_scores was seeded with another start state, so the stream "
+                                                 "starts from imported beams, whose chains carry no tokens")
+            if not at_start:
+                raise NotImplementedError(what + " need the beams handed back as partial_decode_beams returned them: lists the "
+                                                 "caller built or edited are imported, and their chains carry no tokens")
+            return  # a fresh stream: anything goes
+        if streams.parents is not None:
+            raise NotImplementedError(what + ": this stream was started from imported beams, whose chains carry no tokens")
+        fold = streams.token_mode if streams.token_mode > 1 else 0
+        if token_mode > 1 and token_mode != fold:
+            raise ValueError("confidence has to be asked for from a stream's first chunk on, with the same fold every time"
+                             if not fold else "a stream keeps the confidence fold its first chunk asked for")
+        if fold and streams.next_frame is not None and frames_in != streams.next_frame:
+            raise ValueError("processed_frames %r does not continue the stream (confidence: expected %r)"
+                             % (frames_in, streams.next_frame))
 
     def _memo_starts_at_default(self, memo: Dict[Any, Any]) -> bool:
         """Is the memo's entry for the empty text what get_starting_state() puts there -- (0, 0, the model's start state)?
@@ -1629,11 +1735,14 @@ class BeamSearchDecoderCTC:
         hotword_scorer: Optional[HotwordScorer] = None,
         force_next_word: bool = False,
         is_end: bool = False,
+        token_frames: bool = False,
+        confidence: Optional[str] = None,
     ) -> List[LMBeam]:
-        """decoder.py:681-728: advance one stream by one chunk; feed the returned beams back in."""
+        """decoder.py:681-728: advance one stream by one chunk; feed the returned beams back in.
+        token_frames / confidence: TokenLMBeams / ConfidenceLMBeams (partial_decode_beams_batch)."""
         return self.partial_decode_beams_batch(
             [logits], [cached_lm_scores], [cached_p_lm_scores], [beams], [processed_frames], beam_width,
-            beam_prune_logp, token_min_logp, prune_history, hotword_scorer, force_next_word, is_end,
+            beam_prune_logp, token_min_logp, prune_history, hotword_scorer, force_next_word, is_end, token_frames, confidence,
         )[0]
 
 
