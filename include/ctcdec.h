@@ -335,6 +335,38 @@ int ctcdec_result_token_frames(ctcdec_result* r, const int64_t** tok_off, const 
  * refuses the fold. decode_beams(..., confidence="mean") / decode_batch / partial_decode_beams(..., confidence=...) */
 int ctcdec_result_token_logp(ctcdec_result* r, const double** logp, int64_t* n_tokens);
 
+/* ---- forced alignment: where a transcript the caller already has lies in the audio ---------------------------------
+ * No reference analogue (pyctcdecode decodes; torchaudio.functional.forced_align is the usual tool). Utterance u's target
+ * is the label ids targets[target_off[u] .. target_off[u + 1]) (alphabet indices, never the blank; at most 2047 of them);
+ * logits, frame counts, dtype and is_device are those of ctcdec_decode_batch, and the probabilities-or-logits rule is the
+ * decode's own (the same device-side test). The library finds the path through blank / label / blank / ... that maximises the
+ * sum of the frames' log-probabilities -- clip(log_softmax(x), ln 1e-15, 0), or log(clip(p, 1e-15, 1)) of probability-like
+ * input, all in float64 (every input dtype widens exactly; the float32 prune path's bits are not reproduced). Equal scores
+ * prefer staying in a state, then the next state, then the skip over a blank; the last label is preferred over a trailing blank.
+ * fold: 0, or CTCDEC_TOKEN_LOGP_MEAN / _MIN / _MAX for each target label's confidence over its own frames of the path.
+ * bp_budget: bytes of back-pointer tables (frames * ceil((2 L + 1) / 4) per utterance) one kernel launch may hold, 0 for the
+ * default of 1 GiB; a batch that needs more is aligned in several launches with the same results.
+ * Everything is validated before anything is launched: a label outside the alphabet or equal to the blank, or an utterance
+ * with fewer frames than labels plus adjacent equal labels (no path exists; the message lists the utterances) is
+ * CTCDEC_ERR_ARG; more than 2047 labels, or one utterance whose table alone exceeds the budget, is CTCDEC_ERR_LIMIT.
+ * Text-to-label mapping and word grouping are the caller's (decoder.py: align / align_batch). */
+typedef struct ctcdec_alignment ctcdec_alignment; /* opaque */
+int ctcdec_align_batch(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts,
+                       int32_t dtype, int32_t is_device, const int32_t* targets, const int64_t* target_off, int32_t fold,
+                       int64_t bp_budget, ctcdec_alignment** out);
+/* Utterance u's path is path[path_off[u] .. path_off[u + 1]): the label taken at each frame, the blank's index for blanks;
+ * score[u] is the sum of the log-probabilities along it. Pointers stay valid until ctcdec_alignment_free. */
+int ctcdec_alignment_paths(const ctcdec_alignment* a, const int64_t** path_off, const int32_t** path, const double** score,
+                           int64_t* n_utts);
+/* Every target label with its frames, in the layout of ctcdec_result_token_frames / ctcdec_result_token_logp: utterance u's
+ * are [tok_off[u], tok_off[u + 1]) of label / start / end (end exclusive) and, when a fold was asked for, logp (else NULL). */
+int ctcdec_alignment_tokens(const ctcdec_alignment* a, const int64_t** tok_off, const int32_t** label, const int32_t** start,
+                            const int32_t** end, const double** logp, int64_t* n_tokens);
+/* milliseconds: [0] the classification (frame-prune kernels), [1] row_lse, [2] ctc_viterbi (HIP events on the decode
+ * stream, summed over the launches), [3] the whole native call; launches: ctc_viterbi launches the budget made (may be NULL) */
+int ctcdec_alignment_timing(const ctcdec_alignment* a, double* ms4, int32_t* launches);
+void ctcdec_alignment_free(ctcdec_alignment* a);
+
 /* timing of the last call's device stages in milliseconds (HIP events on the decode stream):
  * [0] frame-prune kernel, [1] beam kernel, [2] total device time incl. result copy */
 int ctcdec_result_timing(const ctcdec_result* r, double* ms3);

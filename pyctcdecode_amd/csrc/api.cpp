@@ -206,6 +206,9 @@ struct ctcdec_decoder {
   DevBuf w_logits, w_ptrs, w_row0, w_rowsum, w_isprob, w_scnt, w_sid, w_slp, w_flags, w_text, w_emit, w_toff,
       w_eoff, w_start, w_out, w_nout, w_status, w_tok, w_head, w_prof, w_imp, w_impoff, w_ff, w_cold, w_pay, w_tscr, w_tsoff, w_tpool,
       d_toktext, d_tokbytes, w_slow, w_order, w_side, w_truns, w_tlogp, w_tmiss, w_ledrow;
+  // forced alignment (ctcdec_align_batch): row log-sum-exps, targets, paths, token spans, confidences, scores, the launch's
+  // back-pointer tables and utterance records
+  DevBuf w_alse, w_alab, w_apath, w_atok, w_atlp, w_ascore, w_abp, w_autts;
   bool slicing = false;  // a time-sliced host ingest is under way (decode_host_sliced): the prune stage notes each slice's side of 1
   uint32_t max_label_bytes = 1;
   bool arenas_worst_case = false;  // a call has outgrown the usual reservation of the node arenas: reserve the worst case from now on
@@ -2268,6 +2271,263 @@ int ctcdec_frame_survivors(ctcdec_decoder* dec, const void* logits, int32_t n_fr
   }
   return CTCDEC_OK;
 }
+
+// ---- forced alignment ("Forced alignment") --------------------------------------------------------------------
+}  // extern "C"
+
+struct ctcdec_alignment {
+  std::vector<int64_t> path_off, tok_off;
+  std::vector<int32_t> path, label, start, end;
+  std::vector<double> score, logp;
+  bool has_logp = false;
+  int32_t launches = 0;
+  double ms[4] = {0, 0, 0, 0};
+};
+
+// The back-pointer tables of one ctc_viterbi launch (T * align_chunks(L) bytes per utterance) when the caller names no budget
+static const int64_t ALIGN_BP_BUDGET = (int64_t)1 << 30;
+
+#ifdef CTC_SIM
+namespace {
+struct AlignSeqCtx {
+  int tid = 0, nt = 1;
+  void sync() {}
+};
+}  // namespace
+#endif
+
+// Everything the kernels index with comes from the caller: checked here, before anything moves.
+static int check_alignment(const ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts,
+                           const int32_t* targets, const int64_t* target_off, int64_t budget, int V, int blank) {
+  (void)dec;
+  if (target_off[0] != 0) return fail(CTCDEC_ERR_ARG, "target_off must start at 0");
+  std::string infeasible;
+  for (int32_t u = 0; u < n_utts; ++u) {
+    const int64_t T = utt_frames[u], L = target_off[u + 1] - target_off[u];
+    if (T < 0) return fail(CTCDEC_ERR_ARG, "negative frame count");
+    if (L < 0) return fail(CTCDEC_ERR_ARG, "target_off must not decrease");
+    if (L > ALIGN_MAX_LABELS)
+      return fail(CTCDEC_ERR_LIMIT, "utterance " + std::to_string(u) + ": " + std::to_string(L) + " target labels, above the limit of " +
+                                        std::to_string(ALIGN_MAX_LABELS) + " (two fp64 score columns of 2L + 1 states in LDS)");
+    if (L > 0 && !targets) return fail(CTCDEC_ERR_ARG, "no targets");
+    if (T > 0 && !utt_logits[u]) return fail(CTCDEC_ERR_ARG, "utterance " + std::to_string(u) + ": no logits");
+    int64_t need = L;
+    for (int64_t k = 0; k < L; ++k) {
+      const int32_t id = targets[target_off[u] + k];
+      if (id < 0 || id >= V)
+        return fail(CTCDEC_ERR_ARG, "utterance " + std::to_string(u) + ": target label " + std::to_string(id) + " is outside the alphabet");
+      if (id == blank) return fail(CTCDEC_ERR_ARG, "utterance " + std::to_string(u) + ": the blank is not a target label");
+      if (k > 0 && id == targets[target_off[u] + k - 1]) ++need;
+    }
+    if (T < need) infeasible += (infeasible.empty() ? "" : ", ") + std::to_string(u);
+    if (T * (int64_t)align_chunks((int32_t)L) > budget)
+      return fail(CTCDEC_ERR_LIMIT, "utterance " + std::to_string(u) + ": a back-pointer table of " +
+                                        std::to_string(T * (int64_t)align_chunks((int32_t)L)) + " bytes, above the budget of " +
+                                        std::to_string(budget) + " bytes for one launch");
+  }
+  if (!infeasible.empty())
+    return fail(CTCDEC_ERR_ARG, "no alignment path (fewer frames than target labels plus adjacent repeats) for utterances: " + infeasible);
+  return CTCDEC_OK;
+}
+
+extern "C" {
+
+int ctcdec_align_batch(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts, int32_t dtype,
+                       int32_t is_device, const int32_t* targets, const int64_t* target_off, int32_t fold, int64_t bp_budget,
+                       ctcdec_alignment** out) {
+  if (!dec || !out || n_utts < 0 || !target_off || bp_budget < 0 || (n_utts > 0 && (!utt_logits || !utt_frames)))
+    return fail(CTCDEC_ERR_ARG, "bad arguments");
+  if (dtype < CTCDEC_F32 || dtype > CTCDEC_BF16) return fail(CTCDEC_ERR_ARG, "dtype must be f32, f64, f16 or bf16");
+  if (fold != 0 && fold != LOGP_MEAN && fold != LOGP_MIN && fold != LOGP_MAX) return fail(CTCDEC_ERR_ARG, "unknown confidence fold");
+  const int V = (int)dec->alpha.labels.size();
+  int blank = -1;
+  for (int v = 0; v < V && blank < 0; ++v)
+    if (dec->alpha.labels[(size_t)v].empty()) blank = v;
+  if (blank < 0) return fail(CTCDEC_ERR_ARG, "the alphabet has no blank label");
+  const int64_t budget = bp_budget ? bp_budget : ALIGN_BP_BUDGET;
+  if (int rc = check_alignment(dec, utt_logits, utt_frames, n_utts, targets, target_off, budget, V, blank)) return rc;
+  const auto t_begin = Clock::now();
+  std::unique_ptr<ctcdec_alignment> res(new ctcdec_alignment());
+  const size_t n = (size_t)n_utts;
+  const int64_t NL = target_off[n];
+  std::vector<int64_t> row0(n + 1, 0);
+  for (size_t u = 0; u < n; ++u) row0[u + 1] = row0[u] + utt_frames[u];
+  const int64_t R = row0[n];
+  res->path_off = row0;
+  res->tok_off.assign(target_off, target_off + n + 1);
+  res->label.assign(targets, targets + NL);
+  res->path.resize((size_t)R);
+  res->start.assign((size_t)NL, 0);
+  res->end.assign((size_t)NL, 0);
+  res->score.assign(n, 0.0);
+  res->has_logp = fold != 0;
+  if (fold) res->logp.assign((size_t)NL, 0.0);
+  if (R > 0) {
+    std::string err;
+    std::lock_guard<std::mutex> device_lock(g_device_mu);
+    if (be::bind_thread(&err)) return fail(CTCDEC_ERR_DEVICE, err);
+    // logits: device pointers are used in place, host matrices are staged (consecutive ones in one copy)
+    const size_t row_bytes = (size_t)V * dtype_size(dtype);
+    std::vector<const void*> ptrs(n);
+    if (is_device) {
+      for (size_t u = 0; u < n; ++u) ptrs[u] = utt_logits[u];
+    } else {
+      if (dec->w_logits.ensure((size_t)R * row_bytes, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+      for (size_t u = 0; u < n;) {
+        char* dst = (char*)dec->w_logits.p + (size_t)row0[u] * row_bytes;
+        const char* src = (const char*)utt_logits[u];
+        size_t bytes = (size_t)utt_frames[u] * row_bytes;
+        ptrs[u] = dst;
+        size_t v = u + 1;
+        while (v < n && (const char*)utt_logits[v] == src + bytes) {
+          ptrs[v] = dst + bytes;
+          bytes += (size_t)utt_frames[v] * row_bytes;
+          ++v;
+        }
+        if (bytes && be::h2d(dst, src, bytes, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+        u = v;
+      }
+    }
+    if (upload(dec->w_ptrs, ptrs, &err) || upload(dec->w_row0, row0, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+    // probabilities or logits? The decode's own prune stage decides (pass 0 and its sniff, the exact test for the ambiguous),
+    // at a threshold nothing but a certain label passes: its survivor lists are three entries wide and are not looked at.
+    PruneStage s{dec, &ptrs, n_utts, dtype, R, V, 0.0};
+    if (int rc = prune_stage(s, nullptr)) return rc;
+    std::vector<uint32_t> is_prob(n);
+    if (be::d2h(is_prob.data(), dec->w_isprob.p, n * 4, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+    double beam_ms = 0;
+    be::last_timing(&res->ms[0], &beam_ms);
+    if (dec->w_alse.ensure((size_t)R * 8, &err) || dec->w_apath.ensure((size_t)R * 4, &err) ||
+        dec->w_alab.ensure((size_t)std::max<int64_t>(NL, 1) * 4, &err) || dec->w_atok.ensure((size_t)std::max<int64_t>(NL, 1) * 8, &err) ||
+        dec->w_atlp.ensure((size_t)std::max<int64_t>(NL, 1) * 8, &err) || dec->w_ascore.ensure(n * 8, &err))
+      return fail(CTCDEC_ERR_DEVICE, err);
+    if ((NL && be::h2d(dec->w_alab.p, targets, (size_t)NL * 4, &err)) || be::zero(dec->w_atok.p, (size_t)std::max<int64_t>(NL, 1) * 8, &err) ||
+        be::zero(dec->w_atlp.p, (size_t)std::max<int64_t>(NL, 1) * 8, &err) || be::zero(dec->w_ascore.p, n * 8, &err))
+      return fail(CTCDEC_ERR_DEVICE, err);
+    double* lse = (double*)dec->w_alse.p;
+#ifdef CTC_SIM  // (the simulator's device memory is host memory: the kernels' bodies, row by row and utterance by utterance)
+    for (size_t u = 0; u < n; ++u)
+      for (int64_t t = 0; !is_prob[u] && t < utt_frames[u]; ++t)
+        lse[row0[u] + t] = row_lse_seq(ptrs[u], dtype, (size_t)t * (size_t)V, V);
+#else
+    be::align_timing_reset();
+    be::RowLseArgs la;
+    la.utt_logits = (const void* const*)dec->w_ptrs.p;
+    la.utt_row0 = (const int64_t*)dec->w_row0.p;
+    la.utt_is_prob = (const uint32_t*)dec->w_isprob.p;
+    la.n_utts = n_utts;
+    la.n_rows = R;
+    la.n_labels = V;
+    la.dtype = dtype;
+    la.lse = lse;
+    if (be::launch_row_lse(la, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+#endif
+    // launches: utterances in input order until their back-pointer tables fill the budget; longest first inside a launch
+    std::vector<std::vector<int32_t>> groups;
+    int64_t used = 0, most = 0;
+    for (int32_t u = 0; u < n_utts; ++u) {
+      if (utt_frames[u] == 0) continue;
+      const int64_t bytes = (int64_t)utt_frames[u] * align_chunks((int32_t)(target_off[u + 1] - target_off[u]));
+      if (groups.empty() || used + bytes > budget) {
+        groups.emplace_back();
+        used = 0;
+      }
+      groups.back().push_back(u);
+      used += bytes;
+      most = std::max(most, used);
+    }
+    if (dec->w_abp.ensure((size_t)std::max<int64_t>(most, 1), &err)) return fail(CTCDEC_ERR_DEVICE, err);
+    const double clip_lo = log(1e-15);  // ln(MIN_TOKEN_CLIP_P) (constants.py:17)
+    std::vector<AlignUtt> utts;
+    for (auto& g : groups) {
+      std::stable_sort(g.begin(), g.end(), [&](int32_t a, int32_t b) { return utt_frames[a] > utt_frames[b]; });
+      utts.clear();
+      int64_t bp_off = 0;
+      int32_t max_chunks = 1;
+      for (int32_t u : g) {
+        const int32_t L = (int32_t)(target_off[u + 1] - target_off[u]);
+        AlignUtt a;
+        a.x = ptrs[(size_t)u];
+        a.lse = lse + row0[(size_t)u];
+        a.lab = (const int32_t*)dec->w_alab.p + target_off[u];
+        a.bp = (uint8_t*)dec->w_abp.p + bp_off;
+        a.path = (int32_t*)dec->w_apath.p + row0[(size_t)u];
+        a.tok_start = (int32_t*)dec->w_atok.p + target_off[u];
+        a.tok_end = (int32_t*)dec->w_atok.p + NL + target_off[u];
+        a.tok_logp = (double*)dec->w_atlp.p + target_off[u];
+        a.score = (double*)dec->w_ascore.p + u;
+        a.T = utt_frames[u];
+        a.L = L;
+        a.is_prob = is_prob[(size_t)u] ? 1 : 0;
+        a.pad = 0;
+        utts.push_back(a);
+        bp_off += (int64_t)utt_frames[u] * align_chunks(L);
+        max_chunks = std::max(max_chunks, align_chunks(L));
+      }
+#ifdef CTC_SIM
+      std::vector<double> col((size_t)8 * (size_t)max_chunks);
+      AlignSeqCtx cx;
+      for (const AlignUtt& a : utts) ctc_viterbi_utt(cx, a, V, dtype, blank, fold, clip_lo, col.data());
+#else
+      if (upload(dec->w_autts, utts, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+      be::ViterbiArgs va;
+      va.utts = (const AlignUtt*)dec->w_autts.p;
+      va.n_utts = (int32_t)utts.size();
+      va.n_labels = V;
+      va.dtype = dtype;
+      va.blank = blank;
+      va.fold = fold;
+      va.max_chunks = max_chunks;
+      va.clip_lo = clip_lo;
+      if (be::launch_ctc_viterbi(va, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+#endif
+      ++res->launches;
+    }
+    if (be::d2h(res->path.data(), dec->w_apath.p, (size_t)R * 4, &err) || be::d2h(res->score.data(), dec->w_ascore.p, n * 8, &err))
+      return fail(CTCDEC_ERR_DEVICE, err);
+    if (NL && (be::d2h(res->start.data(), dec->w_atok.p, (size_t)NL * 4, &err) ||
+               be::d2h(res->end.data(), (const int32_t*)dec->w_atok.p + NL, (size_t)NL * 4, &err) ||
+               (fold && be::d2h(res->logp.data(), dec->w_atlp.p, (size_t)NL * 8, &err))))
+      return fail(CTCDEC_ERR_DEVICE, err);
+#ifndef CTC_SIM
+    be::align_timing(&res->ms[1], &res->ms[2]);
+#endif
+  }
+  res->ms[3] = ms(t_begin, Clock::now());
+  *out = res.release();
+  return CTCDEC_OK;
+}
+
+int ctcdec_alignment_paths(const ctcdec_alignment* a, const int64_t** path_off_out, const int32_t** path_out, const double** score_out,
+                           int64_t* n_utts_out) {
+  if (!a || !path_off_out || !path_out || !score_out || !n_utts_out) return fail(CTCDEC_ERR_ARG, "no alignment");
+  *path_off_out = a->path_off.data();
+  *path_out = a->path.data();
+  *score_out = a->score.data();
+  *n_utts_out = (int64_t)a->score.size();
+  return CTCDEC_OK;
+}
+
+int ctcdec_alignment_tokens(const ctcdec_alignment* a, const int64_t** tok_off_out, const int32_t** label_out, const int32_t** start_out,
+                            const int32_t** end_out, const double** logp_out, int64_t* n_tokens_out) {
+  if (!a || !tok_off_out || !label_out || !start_out || !end_out || !logp_out || !n_tokens_out) return fail(CTCDEC_ERR_ARG, "no alignment");
+  *tok_off_out = a->tok_off.data();
+  *label_out = a->label.data();
+  *start_out = a->start.data();
+  *end_out = a->end.data();
+  *logp_out = a->has_logp ? a->logp.data() : nullptr;
+  *n_tokens_out = (int64_t)a->label.size();
+  return CTCDEC_OK;
+}
+
+int ctcdec_alignment_timing(const ctcdec_alignment* a, double* ms4, int32_t* launches_out) {
+  if (!a || !ms4) return fail(CTCDEC_ERR_ARG, "no alignment");
+  for (int k = 0; k < 4; ++k) ms4[k] = a->ms[k];
+  if (launches_out) *launches_out = a->launches;
+  return CTCDEC_OK;
+}
+
+void ctcdec_alignment_free(ctcdec_alignment* a) { delete a; }
 
 // a texts-only result (params.texts_only) as ordinary beams, for the accessors that want them
 static void materialise(const ctcdec_result* cr) {

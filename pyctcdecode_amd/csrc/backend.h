@@ -9,6 +9,7 @@
 #include <string>
 
 #include "beam_core.h"
+#include "ctc_align.h"
 #include "surv_ledger.h"
 #include "token_logp.h"
 
@@ -215,6 +216,35 @@ int launch_ledger_logp(const LedgerLogpArgs& a, std::string* err);
 // the last launch_ledger_append's / launch_ledger_logp's kernel time (HIP events); waits for the kernel
 double last_ledger_append_ms();
 double last_ledger_logp_ms();
+
+// Forced alignment (ctc_align.h; kernels: ctc_align_hip.hip). row_lse: the fp64 log-sum-exp of every row of the utterances
+// the prune stage's sniff did not classify as probabilities (utt_is_prob[u] == 0); lse is indexed like the prune stage's rows.
+struct RowLseArgs {
+  const void* const* utt_logits;  // [n_utts] (device)
+  const int64_t* utt_row0;        // [n_utts + 1] (device)
+  const uint32_t* utt_is_prob;    // [n_utts] (device)
+  int32_t n_utts;
+  int64_t n_rows;
+  int32_t n_labels;
+  int32_t dtype;  // ctcdec_dtype
+  double* lse;    // [n_rows] out
+};
+int launch_row_lse(const RowLseArgs& a, std::string* err);
+// ctc_viterbi: one workgroup per entry of `utts`, all of them validated by the host (AlignUtt)
+struct ViterbiArgs {
+  const AlignUtt* utts;  // [n_utts] (device)
+  int32_t n_utts;
+  int32_t n_labels;
+  int32_t dtype;
+  int32_t blank;
+  int32_t fold;        // 0, LOGP_MEAN / LOGP_MIN / LOGP_MAX
+  int32_t max_chunks;  // the largest align_chunks(L) of the launch: sizes the two score columns in LDS
+  double clip_lo;      // ln(MIN_TOKEN_CLIP_P)
+};
+int launch_ctc_viterbi(const ViterbiArgs& a, std::string* err);
+// kernel times (HIP events) of the launch_row_lse / launch_ctc_viterbi calls since the last reset; waits for the kernels
+void align_timing_reset();
+void align_timing(double* row_lse_ms, double* viterbi_ms);
 
 // stage timing (ms) of the last launch_prune / launch_beam pair, measured on the decode stream
 void last_timing(double* prune_ms, double* beam_ms);

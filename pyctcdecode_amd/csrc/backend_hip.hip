@@ -2358,6 +2358,12 @@ double last_token_logp_ms() {
   return hipEventElapsedTime(&ms, g_logp_ev[0], g_logp_ev[1]) == hipSuccess ? (double)ms : 0.0;
 }
 
+// Forced alignment: the kernels live in ctc_align_hip.hip and run on the decode stream like everything else
+int launch_row_lse_on(const RowLseArgs& a, hipStream_t stream, std::string* err);
+int launch_ctc_viterbi_on(const ViterbiArgs& a, hipStream_t stream, std::string* err);
+int launch_row_lse(const RowLseArgs& a, std::string* err) { return launch_row_lse_on(a, g_stream, err); }
+int launch_ctc_viterbi(const ViterbiArgs& a, std::string* err) { return launch_ctc_viterbi_on(a, g_stream, err); }
+
 // Survivor ledger, append (surv_ledger.h): one wavefront per stream. A step takes 64 of the chunk's rows, one per lane: the
 // clamped counts are scanned across the wave (DPP, no LDS, no barrier), the running offset of the stream is wave-uniform and
 // carried from step to step, every lane writes its row's end into row_off and copies its row's handful of (id, lp) pairs.

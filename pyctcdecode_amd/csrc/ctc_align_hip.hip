@@ -1,0 +1,191 @@
+// ctc_align_hip.hip -- forced alignment on gfx950 (ctc_align.h): row_lse, the fp64 log-sum-exp of every frame row, and
+// ctc_viterbi, one workgroup per utterance over the blank / label / blank / ... states. A translation unit of its own.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <string>
+#include <vector>
+
+#include "backend.h"
+#include "ctc_align.h"
+
+namespace ctc {
+namespace be {
+
+#define HIP_TRY_A(expr)                                                                  \
+  do {                                                                                   \
+    hipError_t e_ = (expr);                                                              \
+    if (e_ != hipSuccess) {                                                              \
+      if (err) *err = std::string(#expr) + ": " + hipGetErrorString(e_);                 \
+      return -1;                                                                         \
+    }                                                                                    \
+  } while (0)
+
+// ---------------------------------------------------------------------------------------------
+// row_lse: G lanes per row (a whole wave for wide rows, 16 or 4 lanes for small vocabularies, so that a wave takes 4 or 16
+// rows). Every logit is read once: a row that starts on a 16-byte boundary in 16-byte vectors (single elements for the
+// V mod (16 / element size) left over), any other row element by element in the same grouping. A lane folds 16 values at a
+// time into its running (max, sum of exp) pair -- one exp for the rescale, one per value -- and the lanes' pairs are merged
+// by a butterfly of shuffles. 8 bytes out per row.
+// ---------------------------------------------------------------------------------------------
+template <int DT>
+__device__ __forceinline__ void unpack16(const uint4 q, double* out) {
+  if (DT == 0) {
+    out[0] = (double)__uint_as_float(q.x);
+    out[1] = (double)__uint_as_float(q.y);
+    out[2] = (double)__uint_as_float(q.z);
+    out[3] = (double)__uint_as_float(q.w);
+  } else if (DT == 1) {
+    out[0] = __hiloint2double((int)q.y, (int)q.x);
+    out[1] = __hiloint2double((int)q.w, (int)q.z);
+  } else {
+    const uint32_t w[4] = {q.x, q.y, q.z, q.w};
+    CTC_UNROLL
+    for (int k = 0; k < 4; ++k) {
+      const uint16_t lo = (uint16_t)(w[k] & 0xFFFFu), hi = (uint16_t)(w[k] >> 16);
+      out[2 * k] = (double)(DT == 2 ? f16_bits_to_f32(lo) : bf16_bits_to_f32(lo));
+      out[2 * k + 1] = (double)(DT == 2 ? f16_bits_to_f32(hi) : bf16_bits_to_f32(hi));
+    }
+  }
+}
+
+template <int G, int DT>
+__global__ __launch_bounds__(256) void row_lse(RowLseArgs a) {
+  constexpr int RPB = 256 / G;                            // rows per workgroup
+  constexpr int ESZ = DT == 0 ? 4 : DT == 1 ? 8 : 2;      // bytes per element
+  constexpr int EPV = 16 / ESZ;                           // elements per 16-byte vector
+  constexpr int VPB = ALIGN_LSE_BLOCK / EPV;              // vectors per block of values
+  const int64_t row = (int64_t)blockIdx.x * RPB + (int)(threadIdx.x / G);
+  const int l = (int)(threadIdx.x % G);
+  if (row >= a.n_rows) return;
+  int lo = 0, hi = a.n_utts;  // utt_row0[lo] <= row < utt_row0[hi]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (a.utt_row0[mid] <= row) lo = mid;
+    else hi = mid;
+  }
+  if (a.utt_is_prob[lo]) return;  // (the whole group of lanes: `row` is theirs alone)
+  const int V = a.n_labels;
+  const char* p = (const char*)a.utt_logits[lo] + (size_t)(row - a.utt_row0[lo]) * (size_t)V * ESZ;
+  // Which values a lane folds, and in which order, depends on the element index alone -- never on where the row lies in memory:
+  // the same row gives the same bits whether it comes alone, inside a batch or out of a staging buffer.
+  const bool vec = ((uintptr_t)p & 15u) == 0;
+  const int nvec = V / EPV, tail = nvec * EPV;
+  LseAcc acc = lse_empty();
+  for (int i = tail + l; i < V; i += G) lse_push(acc, align_load(p, DT, (size_t)i));
+  const uint4* pv = (const uint4*)p;
+  for (int base = 0; base < nvec; base += G * VPB) {
+    double v[ALIGN_LSE_BLOCK];
+    CTC_UNROLL
+    for (int j = 0; j < VPB; ++j) {
+      const int i = base + j * G + l;  // (neighbouring lanes, neighbouring 16-byte groups)
+      if (i >= nvec) {
+        CTC_UNROLL
+        for (int k = 0; k < EPV; ++k) v[j * EPV + k] = align_neg_inf();
+      } else if (vec) {
+        unpack16<DT>(pv[i], v + j * EPV);
+      } else {
+        CTC_UNROLL
+        for (int k = 0; k < EPV; ++k) v[j * EPV + k] = align_load(p, DT, (size_t)i * EPV + (size_t)k);
+      }
+    }
+    lse_push_block(acc, v);
+  }
+  CTC_UNROLL
+  for (int off = G / 2; off >= 1; off >>= 1) {
+    LseAcc o;
+    o.m = __shfl_xor(acc.m, off, G);
+    o.s = __shfl_xor(acc.s, off, G);
+    acc = lse_merge(acc, o);
+  }
+  if (l == 0) a.lse[row] = lse_value(acc);
+}
+
+// ---------------------------------------------------------------------------------------------
+// ctc_viterbi: 256 threads per utterance, both score columns in LDS, one barrier per frame (ctc_align.h)
+// ---------------------------------------------------------------------------------------------
+struct AlignGpuCtx {
+  int tid, nt;
+  __device__ __forceinline__ void sync() { __syncthreads(); }
+};
+
+__global__ __launch_bounds__(ALIGN_THREADS) void ctc_viterbi(ViterbiArgs a) {
+  extern __shared__ double align_cols[];
+  AlignGpuCtx cx{(int)threadIdx.x, ALIGN_THREADS};
+  ctc_viterbi_utt(cx, a.utts[blockIdx.x], a.n_labels, a.dtype, a.blank, a.fold, a.clip_lo, align_cols);
+}
+
+// kernel times: one pair of events per launch since the last reset
+struct EventLog {
+  std::vector<hipEvent_t> ev;
+  size_t used = 0;
+  int next(hipEvent_t* out, std::string* err) {
+    if (used == ev.size()) {
+      hipEvent_t e;
+      HIP_TRY_A(hipEventCreate(&e));
+      ev.push_back(e);
+    }
+    *out = ev[used++];
+    return 0;
+  }
+  double total() {
+    double sum = 0.0;
+    for (size_t k = 0; k + 1 < used; k += 2) {
+      float ms = 0.f;
+      if (hipEventSynchronize(ev[k + 1]) == hipSuccess && hipEventElapsedTime(&ms, ev[k], ev[k + 1]) == hipSuccess) sum += (double)ms;
+    }
+    return sum;
+  }
+};
+static EventLog g_lse_log, g_vit_log;
+
+void align_timing_reset() { g_lse_log.used = g_vit_log.used = 0; }
+void align_timing(double* row_lse_ms, double* viterbi_ms) {
+  *row_lse_ms = g_lse_log.total();
+  *viterbi_ms = g_vit_log.total();
+}
+
+template <int G>
+static void launch_row_lse_g(const RowLseArgs& a, hipStream_t stream) {
+  const dim3 grid((unsigned)((a.n_rows + (256 / G) - 1) / (256 / G))), block(256);
+  if (a.dtype == 0) hipLaunchKernelGGL((row_lse<G, 0>), grid, block, 0, stream, a);
+  else if (a.dtype == 1) hipLaunchKernelGGL((row_lse<G, 1>), grid, block, 0, stream, a);
+  else if (a.dtype == 2) hipLaunchKernelGGL((row_lse<G, 2>), grid, block, 0, stream, a);
+  else hipLaunchKernelGGL((row_lse<G, 3>), grid, block, 0, stream, a);
+}
+
+int launch_row_lse_on(const RowLseArgs& a, hipStream_t stream, std::string* err) {
+  if (a.n_rows <= 0 || a.n_utts <= 0) return 0;
+  if (a.dtype < 0 || a.dtype > 3 || a.n_labels < 1 || a.n_rows > (int64_t)0x7FFFFFFF * 4) {
+    if (err) *err = "row_lse: bad arguments";
+    return -1;
+  }
+  hipEvent_t e0, e1;
+  if (g_lse_log.next(&e0, err) || g_lse_log.next(&e1, err)) return -1;
+  HIP_TRY_A(hipEventRecord(e0, stream));
+  if (a.n_labels >= 256) launch_row_lse_g<64>(a, stream);
+  else if (a.n_labels >= 32) launch_row_lse_g<16>(a, stream);
+  else launch_row_lse_g<4>(a, stream);
+  HIP_TRY_A(hipGetLastError());
+  HIP_TRY_A(hipEventRecord(e1, stream));
+  return 0;
+}
+
+int launch_ctc_viterbi_on(const ViterbiArgs& a, hipStream_t stream, std::string* err) {
+  if (a.n_utts <= 0) return 0;
+  if (a.max_chunks < 1 || a.max_chunks > align_chunks(ALIGN_MAX_LABELS)) {
+    if (err) *err = "ctc_viterbi: more states than two score columns in LDS hold";
+    return -1;
+  }
+  const size_t lds = (size_t)2 * 4 * (size_t)a.max_chunks * sizeof(double);  // <= 64 KB
+  hipEvent_t e0, e1;
+  if (g_vit_log.next(&e0, err) || g_vit_log.next(&e1, err)) return -1;
+  HIP_TRY_A(hipEventRecord(e0, stream));
+  hipLaunchKernelGGL(ctc_viterbi, dim3((unsigned)a.n_utts), dim3(ALIGN_THREADS), lds, stream, a);
+  HIP_TRY_A(hipGetLastError());
+  HIP_TRY_A(hipEventRecord(e1, stream));
+  return 0;
+}
+
+}  // namespace be
+}  // namespace ctc

@@ -142,6 +142,27 @@ class ConfidenceOutputBeam(TokenOutputBeam):
     token_logp: List[float]
     word_logp: List[float]
 
+ALIGN_MAX_LABELS = 2047  # ALIGN_MAX_LABELS of csrc/ctc_align.h: 2 L + 1 states, two fp64 score columns in a workgroup's LDS
+ALIGN_BP_BUDGET = 1 << 30  # bytes of back-pointer tables one ctc_viterbi launch holds by default ("Forced alignment")
+
+
+@dataclasses.dataclass(frozen=True)
+class AlignedText:
+    """Where a known transcript lies in the audio (BeamSearchDecoderCTC.align / align_batch): the best CTC path through
+    blank / label / blank / ... for the target. ``path`` is the label id taken at each frame (int32 ``[T]``, the blank's id
+    for blanks), ``score`` the sum of the clipped log-probabilities along it. ``token_frames`` and ``text_frames`` are those
+    of TokenOutputBeam / OutputBeam (end exclusive; the space label of a character alphabet is no token); with
+    ``confidence=...`` ``token_logp`` and ``word_logp`` are those of ConfidenceOutputBeam, folded over the token's own frames
+    of ``path``, else None."""
+
+    text: str
+    path: np.ndarray
+    score: float
+    token_frames: List[Tuple[str, Frames]]
+    text_frames: List[WordFrames]
+    token_logp: Optional[List[float]] = None
+    word_logp: Optional[List[float]] = None
+
 
 CONFIDENCE_FOLDS = {"mean": 2, "min": 3, "max": 4}  # ctcdec_params.token_frames: CTCDEC_TOKEN_LOGP_MEAN / _MIN / _MAX
 
@@ -1443,6 +1464,165 @@ class BeamSearchDecoderCTC:
             return self._with_tokens(res, beams, bool(fold)) if token_frames else beams
         finally:
             self._lib.dll.ctcdec_result_free(res)
+
+    # -- forced alignment (no reference analogue; DESIGN.md, "Forced alignment") ------------------------
+    def _target_of_text(self, text: str) -> List[int]:
+        """The label ids of a whitespace-normalised text under a character alphabet: its characters, the space label
+        between words."""
+        out = []
+        for ch in " ".join(text.split()):
+            idx = self._vocab2idx.get(ch)
+            if idx is None or ch == "":
+                raise ValueError("character %r of the text %r is not a label of the alphabet" % (ch, text))
+            out.append(idx)
+        return out
+
+    def _words_of_target(self, ids: Sequence[int]):
+        """-> (text, kept, words): the positions of the target that are tokens (all but the space label of a character
+        alphabet) and, per word, (its string, first kept index, one past its last kept index)."""
+        labels = self._labels_list
+        kept, words, cur, lo = [], [], [], 0
+        from .alphabet import BPE_TOKEN
+
+        def close():
+            nonlocal cur, lo
+            if cur:
+                words.append(("".join(cur), lo, len(kept)))
+            cur, lo = [], len(kept)
+
+        force = False
+        for pos, c in enumerate(ids):
+            lab = labels[c]
+            if not self._is_bpe:
+                if lab == " ":
+                    close()
+                    continue
+                cur.append(lab)
+            else:
+                if force or lab.startswith(BPE_TOKEN):
+                    close()
+                force = len(lab) > 1 and lab.endswith(BPE_TOKEN)
+                cur.append(lab.strip(BPE_TOKEN))
+            kept.append(pos)
+        close()
+        return " ".join(w for w, _, _ in words), kept, words
+
+    def align(self, logits: Any, text: Optional[str] = None, tokens: Optional[Sequence[int]] = None,
+              confidence: Optional[str] = None) -> "AlignedText":
+        """Forced alignment of one utterance: align_batch of a batch of one (a ValueError when no path exists)."""
+        self._check_logits_dimension(logits)
+        return self.align_batch([logits], None if text is None else [text], tokens=None if tokens is None else [tokens],
+                                confidence=confidence)[0]
+
+    def align_batch(self, logits_list: Any, texts: Optional[Sequence[str]] = None, tokens: Optional[Sequence[Sequence[int]]] = None,
+                    confidence: Optional[str] = None, strict: bool = True, _bp_budget: int = 0) -> List[Optional["AlignedText"]]:
+        """Where each known transcript lies in its utterance, in one native call: per utterance the best CTC path for its
+        target (row_lse + ctc_viterbi, csrc/ctc_align_hip.hip), as AlignedText. ``logits_list`` is what decode_batch takes,
+        and probabilities are told from logits by the same rule. ``texts`` (character alphabets): the target is the
+        characters of the whitespace-normalised text; ``tokens``: label ids per utterance, the only form for BPE alphabets.
+        An utterance with fewer frames than target labels plus adjacent equal labels has no path: ``strict=True`` raises a
+        ValueError that lists them, ``strict=False`` returns None in their place."""
+        fold = _confidence_fold(confidence)
+        if (texts is None) == (tokens is None):
+            raise ValueError("align: give exactly one of texts and tokens")
+        if texts is not None and self._is_bpe:
+            raise ValueError("a text has many segmentations under a BPE alphabet: give the target as tokens=")
+        if getattr(logits_list, "ndim", 0) != 3:
+            logits_list = list(logits_list)
+        n = len(logits_list)
+        given = texts if texts is not None else tokens
+        if isinstance(given, str) or len(given) != n:
+            raise ValueError("align: %d targets for %d utterances" % (1 if isinstance(given, str) else len(given), n))
+        blank, n_labels = self._vocab2idx[""], len(self._labels_list)
+        targets: List[List[int]] = []
+        for u, g in enumerate(given):
+            if texts is not None:
+                if not isinstance(g, str):
+                    raise ValueError("align: texts[%d] is not a str" % u)
+                ids = self._target_of_text(g)
+            else:
+                ids = []
+                for c in g:
+                    if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 0 <= int(c) < n_labels or int(c) == blank:
+                        raise ValueError("align: tokens[%d] holds %r: not a label id in [0, %d) other than the blank (%d)"
+                                         % (u, c, n_labels, blank))
+                    ids.append(int(c))
+            if len(ids) > ALIGN_MAX_LABELS:
+                raise ValueError("align: utterance %d has %d target labels, above the limit of %d labels per utterance"
+                                 % (u, len(ids), ALIGN_MAX_LABELS))
+            targets.append(ids)
+        if n == 0:
+            return []
+        with self._call_lock:
+            batch = _Batch(logits_list, n_labels)
+            if batch.is_device and batch.device_index is not None and batch.device_index != self._device:
+                raise ValueError("the logits live on cuda:%d but this decoder was built for cuda:%d (one process per GPU: "
+                                 "LOCAL_RANK / CTCDEC_DEVICE pick the device)" % (batch.device_index, self._device))
+            frames = np.asarray(batch.frames, dtype=np.int32)
+            ptrs = np.asarray(batch.ptrs, dtype=np.uint64)
+            budget = int(_bp_budget) or ALIGN_BP_BUDGET
+            keep, bad = [], []
+            for u, ids in enumerate(targets):
+                need = len(ids) + sum(1 for a, b in zip(ids, ids[1:]) if a == b)
+                (keep if int(frames[u]) >= need else bad).append(u)
+                table = int(frames[u]) * ((2 * len(ids) + 1 + 3) // 4)
+                if table > budget:
+                    raise ValueError("align: utterance %d needs a back-pointer table of %d bytes, above the memory budget of %d "
+                                     "bytes of one launch" % (u, table, budget))
+            if bad and strict:
+                raise ValueError("align: no path for utterances %s: fewer frames than target labels plus adjacent equal labels"
+                                 % bad)
+            out: List[Optional[AlignedText]] = [None] * n
+            if not keep:
+                return out
+            k_ptrs = np.ascontiguousarray(ptrs[keep])
+            k_frames = np.ascontiguousarray(frames[keep])
+            flat = np.array([c for u in keep for c in targets[u]] or [0], dtype=np.int32)
+            off = np.zeros(len(keep) + 1, dtype=np.int64)
+            off[1:] = np.cumsum([len(targets[u]) for u in keep])
+            res = C.c_void_p()
+            lib = self._lib
+            lib.check(lib.dll.ctcdec_align_batch(
+                self._handle, k_ptrs.ctypes.data_as(C.POINTER(C.c_void_p)), k_frames.ctypes.data_as(C.POINTER(C.c_int32)),
+                len(keep), batch.dtype, int(batch.is_device), flat.ctypes.data_as(C.POINTER(C.c_int32)), B.off_ptr(off), fold,
+                int(_bp_budget), C.byref(res)))
+            try:
+                po, pp, ps, nu = C.POINTER(C.c_int64)(), C.POINTER(C.c_int32)(), C.POINTER(C.c_double)(), C.c_int64()
+                lib.check(lib.dll.ctcdec_alignment_paths(res, C.byref(po), C.byref(pp), C.byref(ps), C.byref(nu)))
+                to, tl, ts, te, tp, nt = (C.POINTER(C.c_int64)(), C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)(),
+                                          C.POINTER(C.c_int32)(), C.POINTER(C.c_double)(), C.c_int64())
+                lib.check(lib.dll.ctcdec_alignment_tokens(res, C.byref(to), C.byref(tl), C.byref(ts), C.byref(te), C.byref(tp),
+                                                          C.byref(nt)))
+                if int(nu.value) != len(keep) or int(nt.value) != int(off[-1]):
+                    raise B.NativeError("the alignment holds another number of utterances or tokens than was asked for")
+                path_off = np.ctypeslib.as_array(po, shape=(len(keep) + 1,))
+                total = int(path_off[-1])
+                path = np.ctypeslib.as_array(pp, shape=(total,)).copy() if total else np.zeros(0, dtype=np.int32)
+                score = np.ctypeslib.as_array(ps, shape=(len(keep),)).tolist()
+                ntok = int(nt.value)
+                start = np.ctypeslib.as_array(ts, shape=(ntok,)).tolist() if ntok else []
+                end = np.ctypeslib.as_array(te, shape=(ntok,)).tolist() if ntok else []
+                logp = np.ctypeslib.as_array(tp, shape=(ntok,)).tolist() if ntok and fold else []
+                ms, launches = (C.c_double * 4)(), C.c_int32()
+                lib.dll.ctcdec_alignment_timing(res, ms, C.byref(launches))
+                # [classification (frame-prune kernels), row_lse, ctc_viterbi (HIP events), whole native call]; launches made
+                self.last_align_timing_ms = tuple(float(v) for v in ms)
+                self.last_align_launches = int(launches.value)
+                path_off = path_off.tolist()
+            finally:
+                lib.dll.ctcdec_alignment_free(res)
+            labels = self._labels_list
+            for j, u in enumerate(keep):
+                ids, o = targets[u], int(off[j])
+                text, kept, words = self._words_of_target(ids)
+                tok = [(labels[ids[k]], (start[o + k], end[o + k])) for k in kept]
+                wf = [(w, (tok[lo][1][0], tok[hi - 1][1][1])) for w, lo, hi in words]
+                tlp = wlp = None
+                if fold:
+                    tlp = [logp[o + k] for k in kept]
+                    wlp = [min(tlp[lo:hi]) for _w, lo, hi in words]
+                out[u] = AlignedText(text, path[path_off[j]:path_off[j + 1]].copy(), float(score[j]), tok, wf, tlp, wlp)
+            return out
 
     # -- serialisation (decoder.py:947-1043): alphabet.json + language_model/ --------------------------
     _ALPHABET_SERIALIZED_FILENAME = "alphabet.json"

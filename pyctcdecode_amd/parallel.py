@@ -191,6 +191,11 @@ def decode_beams_batch_sharded(decoder, logits_list, group=None, **kwargs) -> Li
 # ---------------------------------------------------------------------------------------------------------------------
 # DevicePool: what `pool` is to the reference's decode_batch(pool, ...) -- ONE caller process, several devices
 # ---------------------------------------------------------------------------------------------------------------------
+def align_batch_sharded(decoder, logits_list, texts=None, group=None, **kwargs):
+    """Forced alignment is not sharded over ranks: each rank calls decoder.align_batch on its own slice."""
+    raise NotImplementedError("align_batch is not gathered over ranks: align each rank's slice with decoder.align_batch itself")
+
+
 def _device_worker(conn, device: int, decoder_dir: str, library: Optional[str]) -> None:
     """One worker process = one GPU (the native library binds one device per process): loads the saved decoder on its device and
     serves (method, logits, kwargs) requests until it is told to stop."""
@@ -307,6 +312,12 @@ class DevicePool:
         if err is not None:
             raise err
         return parts
+
+    def align_batch(self, logits_list, texts=None, **kwargs):
+        """Forced alignment runs on the calling process's own device: a pool does not shard it."""
+        raise NotImplementedError("DevicePool does not shard align_batch: call decoder.align_batch on the process's own device")
+
+    align = align_batch
 
     def decode_batch(self, logits_list, **kwargs) -> List[str]:
         if kwargs.get("token_frames") or kwargs.get("confidence") is not None:  # (texts, TokenFrames) per slice -> one of each, offsets rebased

@@ -1,4 +1,4 @@
-"""Register / LDS / spill table of every kernel in libctcdec.so: recompiles the three device translation units with the flags
+"""Register / LDS / spill table of every kernel in libctcdec.so: recompiles the device translation units with the flags
 pyctcdecode_amd/build.py uses plus -Rpass-analysis=kernel-resource-usage and prints one line per kernel.
   python tools/kernel_resources.py [name-filter] > profiles/rNN_kernel_resources.txt"""
 import os
@@ -19,7 +19,7 @@ def demangle(names):
 def main():
     flt = sys.argv[1] if len(sys.argv) > 1 else ""
     rows = []
-    srcs = ("backend_hip.hip", "beam_wave_hip.hip", "beam_group_hip.hip")
+    srcs = tuple(s for s in build.SOURCES if s.endswith(".hip"))
     from concurrent.futures import ThreadPoolExecutor
 
     def remarks(src):
@@ -29,7 +29,7 @@ def main():
                                                                         "-o", "/dev/null"]
         return subprocess.run(cmd, capture_output=True, text=True).stderr
 
-    with ThreadPoolExecutor(3) as ex:
+    with ThreadPoolExecutor(len(srcs)) as ex:
         errs = list(ex.map(remarks, srcs))
     for src, err in zip(srcs, errs):
         cur = None
