@@ -367,6 +367,31 @@ int ctcdec_alignment_tokens(const ctcdec_alignment* a, const int64_t** tok_off, 
 int ctcdec_alignment_timing(const ctcdec_alignment* a, double* ms4, int32_t* launches);
 void ctcdec_alignment_free(ctcdec_alignment* a);
 
+/* ---- transcript likelihood: how probable a label sequence the caller already has is, given the audio -----------------
+ * No reference analogue (torch.nn.functional.ctc_loss computes the negative of it). Utterance u owns the hypotheses
+ * [hyp_off[u], hyp_off[u + 1]); hypothesis h is the label ids targets[target_off[h] .. target_off[h + 1]) (alphabet
+ * indices, never the blank; at most 2047 of them). Logits, frame counts, dtype, is_device, the probabilities-or-logits
+ * rule and the per-frame log-probabilities (clipped, float64) are those of ctcdec_align_batch. logp_out[h] is the CTC forward
+ * score: the natural log of the sum, over ALL paths through blank / label / blank / ... that collapse to the hypothesis,
+ * of the product of the frames' probabilities -- where ctcdec_align_batch's score is the largest single term of that sum.
+ * Each step adds its two or three predecessors as m + log(sum of exp(v - m)) in float64. A hypothesis with fewer frames
+ * than labels plus adjacent equal labels has no path: -inf (decided by the host; not an error). The empty hypothesis scores
+ * the all-blank path, and 0.0 for an utterance without frames. The row log-sum-exps are computed once per utterance,
+ * however many hypotheses it has; an utterance none of whose hypotheses is launched (none given, or none with a path) is
+ * neither staged nor classified nor summed.
+ * kernel: 0 lets the library choose between its two kernels (one wavefront per hypothesis up to 127 labels, one workgroup
+ * above), 1 prefers the wavefront kernel (longer hypotheses still take the workgroup kernel), 2 forces the workgroup kernel;
+ * both return the same bits. score / score_batch pass it from the environment variable CTCDEC_FORWARD_KERNEL=wave|group.
+ * ms4 (may be NULL): milliseconds of [0] the classification, [1] row_lse, [2] the forward kernels (HIP events on the decode
+ * stream), [3] the whole native call. launched2 (may be NULL): hypotheses that went to [0] the wavefront kernel, [1] the
+ * workgroup kernel. Everything is validated before anything is launched: a null pointer, offsets that do not start at 0 or
+ * decrease, a negative frame count, a label outside the alphabet or equal to the blank is CTCDEC_ERR_ARG; more than 2047
+ * labels is CTCDEC_ERR_LIMIT. Text-to-label mapping and the language-model term are the caller's (decoder.py: score /
+ * score_batch). */
+int ctcdec_score_batch(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts,
+                       int32_t dtype, int32_t is_device, const int32_t* targets, const int64_t* target_off,
+                       const int64_t* hyp_off, int32_t kernel, double* logp_out, double* ms4, int64_t* launched2);
+
 /* timing of the last call's device stages in milliseconds (HIP events on the decode stream):
  * [0] frame-prune kernel, [1] beam kernel, [2] total device time incl. result copy */
 int ctcdec_result_timing(const ctcdec_result* r, double* ms3);

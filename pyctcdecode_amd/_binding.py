@@ -153,6 +153,9 @@ _PROTOS = {
                                           C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.c_int64)]),
     "ctcdec_alignment_timing": (C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
     "ctcdec_alignment_free": (None, [_VP]),
+    "ctcdec_score_batch": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32,
+                                     C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32,
+                                     C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "ctcdec_result_timing": (C.c_int, [_VP, C.POINTER(C.c_double)]),
     "ctcdec_result_beam_kernel": (C.c_int, [_VP]),
     "ctcdec_device": (C.c_int, []),

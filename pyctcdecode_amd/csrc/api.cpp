@@ -209,6 +209,8 @@ struct ctcdec_decoder {
   // forced alignment (ctcdec_align_batch): row log-sum-exps, targets, paths, token spans, confidences, scores, the launch's
   // back-pointer tables and utterance records
   DevBuf w_alse, w_alab, w_apath, w_atok, w_atlp, w_ascore, w_abp, w_autts;
+  // transcript likelihood (ctcdec_score_batch): the hypothesis records of a launch (labels: w_alab, scores: w_ascore)
+  DevBuf w_fhyps;
   bool slicing = false;  // a time-sliced host ingest is under way (decode_host_sliced): the prune stage notes each slice's side of 1
   uint32_t max_label_bytes = 1;
   bool arenas_worst_case = false;  // a call has outgrown the usual reservation of the node arenas: reserve the worst case from now on
@@ -2290,6 +2292,7 @@ static const int64_t ALIGN_BP_BUDGET = (int64_t)1 << 30;
 #ifdef CTC_SIM
 namespace {
 struct AlignSeqCtx {
+  enum { GROUPS = FORWARD_MAX_GROUPS };  // (ctc_forward_hyp: the one thread owns every group)
   int tid = 0, nt = 1;
   void sync() {}
 };
@@ -2330,6 +2333,73 @@ static int check_alignment(const ctcdec_decoder* dec, const void* const* utt_log
   return CTCDEC_OK;
 }
 
+// What ctcdec_align_batch and ctcdec_score_batch do before their own recursion, under the device lock: host matrices staged
+// (consecutive ones in one copy; device pointers are used in place), pointers and row offsets uploaded, the utterances
+// classified as probabilities or logits, and row_lse over the rows of the logit utterances -- once per utterance.
+struct AlignFront {
+  std::vector<const void*> ptrs;   // [n] device pointers of the utterances' matrices
+  std::vector<uint32_t> is_prob;   // [n] the classification read back
+  double* lse = nullptr;           // [R] (device) row log-sum-exps, indexed like row0
+  double sniff_ms = 0;             // the classification's kernel time
+};
+static int align_front(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts, int32_t dtype,
+                       int32_t is_device, int V, const std::vector<int64_t>& row0, AlignFront& f) {
+  std::string err;
+  const size_t n = (size_t)n_utts;
+  const int64_t R = row0[n];
+  const size_t row_bytes = (size_t)V * dtype_size(dtype);
+  std::vector<const void*>& ptrs = f.ptrs;
+  ptrs.assign(n, nullptr);
+  if (is_device) {
+    for (size_t u = 0; u < n; ++u) ptrs[u] = utt_logits[u];
+  } else {
+    if (dec->w_logits.ensure((size_t)R * row_bytes, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+    for (size_t u = 0; u < n;) {
+      char* dst = (char*)dec->w_logits.p + (size_t)row0[u] * row_bytes;
+      const char* src = (const char*)utt_logits[u];
+      size_t bytes = (size_t)utt_frames[u] * row_bytes;
+      ptrs[u] = dst;
+      size_t v = u + 1;
+      while (v < n && (const char*)utt_logits[v] == src + bytes) {
+        ptrs[v] = dst + bytes;
+        bytes += (size_t)utt_frames[v] * row_bytes;
+        ++v;
+      }
+      if (bytes && be::h2d(dst, src, bytes, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+      u = v;
+    }
+  }
+  if (upload(dec->w_ptrs, ptrs, &err) || upload(dec->w_row0, row0, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+  // probabilities or logits? The decode's own prune stage decides (pass 0 and its sniff, the exact test for the ambiguous),
+  // at a threshold nothing but a certain label passes: its survivor lists are three entries wide and are not looked at.
+  PruneStage s{dec, &ptrs, n_utts, dtype, R, V, 0.0};
+  if (int rc = prune_stage(s, nullptr)) return rc;
+  f.is_prob.assign(n, 0);
+  if (be::d2h(f.is_prob.data(), dec->w_isprob.p, n * 4, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+  double beam_ms = 0;
+  be::last_timing(&f.sniff_ms, &beam_ms);
+  if (dec->w_alse.ensure((size_t)R * 8, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+  double* lse = f.lse = (double*)dec->w_alse.p;
+#ifdef CTC_SIM  // (the simulator's device memory is host memory: the kernels' bodies, row by row and utterance by utterance)
+  for (size_t u = 0; u < n; ++u)
+    for (int64_t t = 0; !f.is_prob[u] && t < utt_frames[u]; ++t)
+      lse[row0[u] + t] = row_lse_seq(ptrs[u], dtype, (size_t)t * (size_t)V, V);
+#else
+  be::align_timing_reset();
+  be::RowLseArgs la;
+  la.utt_logits = (const void* const*)dec->w_ptrs.p;
+  la.utt_row0 = (const int64_t*)dec->w_row0.p;
+  la.utt_is_prob = (const uint32_t*)dec->w_isprob.p;
+  la.n_utts = n_utts;
+  la.n_rows = R;
+  la.n_labels = V;
+  la.dtype = dtype;
+  la.lse = lse;
+  if (be::launch_row_lse(la, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+#endif
+  return CTCDEC_OK;
+}
+
 extern "C" {
 
 int ctcdec_align_batch(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts, int32_t dtype,
@@ -2366,62 +2436,19 @@ int ctcdec_align_batch(ctcdec_decoder* dec, const void* const* utt_logits, const
     std::string err;
     std::lock_guard<std::mutex> device_lock(g_device_mu);
     if (be::bind_thread(&err)) return fail(CTCDEC_ERR_DEVICE, err);
-    // logits: device pointers are used in place, host matrices are staged (consecutive ones in one copy)
-    const size_t row_bytes = (size_t)V * dtype_size(dtype);
-    std::vector<const void*> ptrs(n);
-    if (is_device) {
-      for (size_t u = 0; u < n; ++u) ptrs[u] = utt_logits[u];
-    } else {
-      if (dec->w_logits.ensure((size_t)R * row_bytes, &err)) return fail(CTCDEC_ERR_DEVICE, err);
-      for (size_t u = 0; u < n;) {
-        char* dst = (char*)dec->w_logits.p + (size_t)row0[u] * row_bytes;
-        const char* src = (const char*)utt_logits[u];
-        size_t bytes = (size_t)utt_frames[u] * row_bytes;
-        ptrs[u] = dst;
-        size_t v = u + 1;
-        while (v < n && (const char*)utt_logits[v] == src + bytes) {
-          ptrs[v] = dst + bytes;
-          bytes += (size_t)utt_frames[v] * row_bytes;
-          ++v;
-        }
-        if (bytes && be::h2d(dst, src, bytes, &err)) return fail(CTCDEC_ERR_DEVICE, err);
-        u = v;
-      }
-    }
-    if (upload(dec->w_ptrs, ptrs, &err) || upload(dec->w_row0, row0, &err)) return fail(CTCDEC_ERR_DEVICE, err);
-    // probabilities or logits? The decode's own prune stage decides (pass 0 and its sniff, the exact test for the ambiguous),
-    // at a threshold nothing but a certain label passes: its survivor lists are three entries wide and are not looked at.
-    PruneStage s{dec, &ptrs, n_utts, dtype, R, V, 0.0};
-    if (int rc = prune_stage(s, nullptr)) return rc;
-    std::vector<uint32_t> is_prob(n);
-    if (be::d2h(is_prob.data(), dec->w_isprob.p, n * 4, &err)) return fail(CTCDEC_ERR_DEVICE, err);
-    double beam_ms = 0;
-    be::last_timing(&res->ms[0], &beam_ms);
-    if (dec->w_alse.ensure((size_t)R * 8, &err) || dec->w_apath.ensure((size_t)R * 4, &err) ||
+    AlignFront fr;
+    if (int rc = align_front(dec, utt_logits, utt_frames, n_utts, dtype, is_device, V, row0, fr)) return rc;
+    const std::vector<const void*>& ptrs = fr.ptrs;
+    const std::vector<uint32_t>& is_prob = fr.is_prob;
+    double* lse = fr.lse;
+    res->ms[0] = fr.sniff_ms;
+    if (dec->w_apath.ensure((size_t)R * 4, &err) ||
         dec->w_alab.ensure((size_t)std::max<int64_t>(NL, 1) * 4, &err) || dec->w_atok.ensure((size_t)std::max<int64_t>(NL, 1) * 8, &err) ||
         dec->w_atlp.ensure((size_t)std::max<int64_t>(NL, 1) * 8, &err) || dec->w_ascore.ensure(n * 8, &err))
       return fail(CTCDEC_ERR_DEVICE, err);
     if ((NL && be::h2d(dec->w_alab.p, targets, (size_t)NL * 4, &err)) || be::zero(dec->w_atok.p, (size_t)std::max<int64_t>(NL, 1) * 8, &err) ||
         be::zero(dec->w_atlp.p, (size_t)std::max<int64_t>(NL, 1) * 8, &err) || be::zero(dec->w_ascore.p, n * 8, &err))
       return fail(CTCDEC_ERR_DEVICE, err);
-    double* lse = (double*)dec->w_alse.p;
-#ifdef CTC_SIM  // (the simulator's device memory is host memory: the kernels' bodies, row by row and utterance by utterance)
-    for (size_t u = 0; u < n; ++u)
-      for (int64_t t = 0; !is_prob[u] && t < utt_frames[u]; ++t)
-        lse[row0[u] + t] = row_lse_seq(ptrs[u], dtype, (size_t)t * (size_t)V, V);
-#else
-    be::align_timing_reset();
-    be::RowLseArgs la;
-    la.utt_logits = (const void* const*)dec->w_ptrs.p;
-    la.utt_row0 = (const int64_t*)dec->w_row0.p;
-    la.utt_is_prob = (const uint32_t*)dec->w_isprob.p;
-    la.n_utts = n_utts;
-    la.n_rows = R;
-    la.n_labels = V;
-    la.dtype = dtype;
-    la.lse = lse;
-    if (be::launch_row_lse(la, &err)) return fail(CTCDEC_ERR_DEVICE, err);
-#endif
     // launches: utterances in input order until their back-pointer tables fill the budget; longest first inside a launch
     std::vector<std::vector<int32_t>> groups;
     int64_t used = 0, most = 0;
@@ -2528,6 +2555,161 @@ int ctcdec_alignment_timing(const ctcdec_alignment* a, double* ms4, int32_t* lau
 }
 
 void ctcdec_alignment_free(ctcdec_alignment* a) { delete a; }
+
+// ---- transcript likelihood ("Transcript likelihood") -----------------------------------------------------------
+}  // extern "C"
+
+// Everything ctcdec_score_batch indexes with comes from the caller: checked here, in the order in which one array bounds the
+// next, before anything moves. need[h]: labels plus adjacent equal labels of hypothesis h.
+static int check_scores(const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts, const int32_t* targets,
+                        const int64_t* target_off, const int64_t* hyp_off, int V, int blank, std::vector<int32_t>& need) {
+  if (hyp_off[0] != 0) return fail(CTCDEC_ERR_ARG, "hyp_off must start at 0");
+  for (int32_t u = 0; u < n_utts; ++u) {
+    if (hyp_off[u + 1] < hyp_off[u]) return fail(CTCDEC_ERR_ARG, "hyp_off must not decrease");
+    if (utt_frames[u] < 0) return fail(CTCDEC_ERR_ARG, "utterance " + std::to_string(u) + ": negative frame count");
+    if (utt_frames[u] > 0 && !utt_logits[u]) return fail(CTCDEC_ERR_ARG, "utterance " + std::to_string(u) + ": no logits");
+  }
+  const int64_t NH = hyp_off[n_utts];
+  if (NH > (int64_t)0x7FFFFFFF) return fail(CTCDEC_ERR_LIMIT, "more than 2^31 - 1 hypotheses in one call");
+  if (target_off[0] != 0) return fail(CTCDEC_ERR_ARG, "target_off must start at 0");
+  need.assign((size_t)NH, 0);
+  for (int32_t u = 0; u < n_utts; ++u)
+    for (int64_t h = hyp_off[u]; h < hyp_off[u + 1]; ++h) {
+      const std::string who = "utterance " + std::to_string(u) + ", hypothesis " + std::to_string(h - hyp_off[u]);
+      const int64_t L = target_off[h + 1] - target_off[h];
+      if (L < 0) return fail(CTCDEC_ERR_ARG, "target_off must not decrease");
+      if (L > ALIGN_MAX_LABELS)
+        return fail(CTCDEC_ERR_LIMIT, who + ": " + std::to_string(L) + " labels, above the limit of " + std::to_string(ALIGN_MAX_LABELS));
+      if (L > 0 && !targets) return fail(CTCDEC_ERR_ARG, "no targets");
+      int64_t nd = L;
+      for (int64_t k = 0; k < L; ++k) {
+        const int32_t id = targets[target_off[h] + k];
+        if (id < 0 || id >= V) return fail(CTCDEC_ERR_ARG, who + ": label " + std::to_string(id) + " is outside the alphabet");
+        if (id == blank) return fail(CTCDEC_ERR_ARG, who + ": the blank is not a label to score");
+        if (k > 0 && id == targets[target_off[h] + k - 1]) ++nd;
+      }
+      need[(size_t)h] = (int32_t)nd;
+    }
+  return CTCDEC_OK;
+}
+
+extern "C" {
+
+int ctcdec_score_batch(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts, int32_t dtype,
+                       int32_t is_device, const int32_t* targets, const int64_t* target_off, const int64_t* hyp_off, int32_t kernel,
+                       double* logp_out, double* ms4, int64_t* launched2) {
+  if (!dec || n_utts < 0 || !target_off || !hyp_off || (n_utts > 0 && (!utt_logits || !utt_frames)))
+    return fail(CTCDEC_ERR_ARG, "bad arguments");
+  if (dtype < CTCDEC_F32 || dtype > CTCDEC_BF16) return fail(CTCDEC_ERR_ARG, "dtype must be f32, f64, f16 or bf16");
+  if (kernel < 0 || kernel > 2) return fail(CTCDEC_ERR_ARG, "kernel must be 0 (the library chooses), 1 (wave) or 2 (group)");
+  const int V = (int)dec->alpha.labels.size();
+  int blank = -1;
+  for (int v = 0; v < V && blank < 0; ++v)
+    if (dec->alpha.labels[(size_t)v].empty()) blank = v;
+  if (blank < 0) return fail(CTCDEC_ERR_ARG, "the alphabet has no blank label");
+  std::vector<int32_t> need;
+  if (int rc = check_scores(utt_logits, utt_frames, n_utts, targets, target_off, hyp_off, V, blank, need)) return rc;
+  const size_t n = (size_t)n_utts;
+  const int64_t NH = hyp_off[n];
+  if (NH > 0 && !logp_out) return fail(CTCDEC_ERR_ARG, "no room for the scores");
+  const auto t_begin = Clock::now();
+  double tms[4] = {0, 0, 0, 0};
+  int64_t launched[2] = {0, 0};
+  // A hypothesis with fewer frames than labels plus adjacent equal labels has no alignment: probability 0, decided here.
+  // The empty one without frames has the one empty alignment. Everything else goes to a kernel: the wave kernel up to its
+  // limit (unless the group kernel is forced), the group kernel above it.
+  const int32_t wave_max = kernel == 2 ? -1 : FORWARD_WAVE_MAX_LABELS;
+  std::vector<int32_t> run[2];  // [0] wave, [1] group: hypothesis indices
+  std::vector<int32_t> utt_of((size_t)NH);
+  for (int32_t u = 0; u < n_utts; ++u)
+    for (int64_t h = hyp_off[u]; h < hyp_off[u + 1]; ++h) {
+      const int64_t L = target_off[h + 1] - target_off[h];
+      utt_of[(size_t)h] = u;
+      if (utt_frames[u] < need[(size_t)h]) logp_out[h] = align_neg_inf();
+      else if (utt_frames[u] == 0) logp_out[h] = 0.0;
+      else run[L <= wave_max ? 0 : 1].push_back((int32_t)h);
+    }
+  if (!run[0].empty() || !run[1].empty()) {
+    // (an utterance none of whose hypotheses is launched takes no part: nothing of it is staged, classified or summed)
+    std::vector<int32_t> use_frames(n, 0);
+    for (int w = 0; w < 2; ++w)
+      for (int32_t h : run[w]) use_frames[(size_t)utt_of[(size_t)h]] = utt_frames[utt_of[(size_t)h]];
+    std::vector<int64_t> row0(n + 1, 0);
+    for (size_t u = 0; u < n; ++u) row0[u + 1] = row0[u] + use_frames[u];
+    const int64_t NL = target_off[NH];
+    std::string err;
+    std::lock_guard<std::mutex> device_lock(g_device_mu);
+    if (be::bind_thread(&err)) return fail(CTCDEC_ERR_DEVICE, err);
+    AlignFront fr;
+    if (int rc = align_front(dec, utt_logits, use_frames.data(), n_utts, dtype, is_device, V, row0, fr)) return rc;
+    tms[0] = fr.sniff_ms;
+    if (dec->w_alab.ensure((size_t)std::max<int64_t>(NL, 1) * 4, &err) || dec->w_ascore.ensure((size_t)NH * 8, &err))
+      return fail(CTCDEC_ERR_DEVICE, err);
+    if ((NL && be::h2d(dec->w_alab.p, targets, (size_t)NL * 4, &err)) || be::zero(dec->w_ascore.p, (size_t)NH * 8, &err))
+      return fail(CTCDEC_ERR_DEVICE, err);
+    const double clip_lo = log(1e-15);  // ln(MIN_TOKEN_CLIP_P) (constants.py:17)
+    // one launch per kernel, longest utterance first inside it; the records of both go over in one copy
+    std::vector<ForwardHyp> hyps;
+    int32_t max_chunks[2] = {1, 1};
+    for (int w = 0; w < 2; ++w) {
+      std::vector<int32_t>& g = run[w];
+      std::stable_sort(g.begin(), g.end(), [&](int32_t a, int32_t b) { return utt_frames[utt_of[(size_t)a]] > utt_frames[utt_of[(size_t)b]]; });
+      for (int32_t h : g) {
+        const int32_t u = utt_of[(size_t)h];
+        ForwardHyp a;
+        a.x = fr.ptrs[(size_t)u];
+        a.lse = fr.lse + row0[(size_t)u];
+        a.lab = (const int32_t*)dec->w_alab.p + target_off[h];
+        a.logp = (double*)dec->w_ascore.p + h;
+        a.T = utt_frames[u];
+        a.L = (int32_t)(target_off[h + 1] - target_off[h]);
+        a.is_prob = fr.is_prob[(size_t)u] ? 1 : 0;
+        a.pad = 0;
+        hyps.push_back(a);
+        max_chunks[w] = std::max(max_chunks[w], align_chunks(a.L));
+      }
+      launched[w] = (int64_t)g.size();
+    }
+#ifdef CTC_SIM  // (both kernels are the one body here: a single thread owns every group)
+    std::vector<double> col((size_t)2 * (size_t)std::max(max_chunks[0], max_chunks[1]));
+    AlignSeqCtx cx;
+    for (const ForwardHyp& a : hyps) {
+      if (dtype == 0) ctc_forward_hyp<0>(cx, a, V, blank, clip_lo, col.data());
+      else if (dtype == 1) ctc_forward_hyp<1>(cx, a, V, blank, clip_lo, col.data());
+      else if (dtype == 2) ctc_forward_hyp<2>(cx, a, V, blank, clip_lo, col.data());
+      else ctc_forward_hyp<3>(cx, a, V, blank, clip_lo, col.data());
+    }
+#else
+    if (upload(dec->w_fhyps, hyps, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+    for (int w = 0; w < 2; ++w) {
+      be::ForwardArgs fa;
+      fa.hyps = (const ForwardHyp*)dec->w_fhyps.p + (w ? run[0].size() : 0);
+      fa.n_hyps = (int32_t)run[w].size();
+      fa.n_labels = V;
+      fa.dtype = dtype;
+      fa.blank = blank;
+      fa.max_chunks = max_chunks[w];
+      fa.pad = 0;
+      fa.clip_lo = clip_lo;
+      if (be::launch_ctc_forward(fa, w == 0, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+    }
+#endif
+    std::vector<double> got((size_t)NH);
+    if (be::d2h(got.data(), dec->w_ascore.p, (size_t)NH * 8, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+    for (int w = 0; w < 2; ++w)
+      for (int32_t h : run[w]) logp_out[h] = got[(size_t)h];
+#ifndef CTC_SIM
+    double vit_ms = 0;
+    be::align_timing(&tms[1], &vit_ms);
+    tms[2] = be::forward_timing();
+#endif
+  }
+  tms[3] = ms(t_begin, Clock::now());
+  if (ms4)
+    for (int k = 0; k < 4; ++k) ms4[k] = tms[k];
+  if (launched2) launched2[0] = launched[0], launched2[1] = launched[1];
+  return CTCDEC_OK;
+}
 
 // a texts-only result (params.texts_only) as ordinary beams, for the accessors that want them
 static void materialise(const ctcdec_result* cr) {

@@ -242,9 +242,24 @@ struct ViterbiArgs {
   double clip_lo;      // ln(MIN_TOKEN_CLIP_P)
 };
 int launch_ctc_viterbi(const ViterbiArgs& a, std::string* err);
-// kernel times (HIP events) of the launch_row_lse / launch_ctc_viterbi calls since the last reset; waits for the kernels
+// ctc_forward (wave == 0: one workgroup per entry of `hyps`) / ctc_forward_wave (wave != 0: one wavefront per entry, every
+// L <= FORWARD_WAVE_MAX_LABELS), all entries validated by the host (ForwardHyp)
+struct ForwardArgs {
+  const ForwardHyp* hyps;  // [n_hyps] (device)
+  int32_t n_hyps;
+  int32_t n_labels;
+  int32_t dtype;
+  int32_t blank;
+  int32_t max_chunks;  // the largest align_chunks(L) of the launch: sizes ctc_forward's two columns in LDS
+  int32_t pad;
+  double clip_lo;      // ln(MIN_TOKEN_CLIP_P)
+};
+int launch_ctc_forward(const ForwardArgs& a, int wave, std::string* err);
+// kernel times (HIP events) of the launch_row_lse / launch_ctc_viterbi / launch_ctc_forward calls since the last reset; waits
+// for the kernels
 void align_timing_reset();
 void align_timing(double* row_lse_ms, double* viterbi_ms);
+double forward_timing();
 
 // stage timing (ms) of the last launch_prune / launch_beam pair, measured on the decode stream
 void last_timing(double* prune_ms, double* beam_ms);

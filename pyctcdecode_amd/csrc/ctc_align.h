@@ -1,7 +1,9 @@
 // ctc_align.h -- forced alignment of a known label sequence to an utterance's frames ("Forced alignment"): the
 // fp64 log-sum-exp of a frame row and the Viterbi recursion over the blank / label / blank / ... states, with its back-trace
-// and the confidence fold over the path. One body each for the HIP kernels (ctc_align_hip.hip: row_lse, ctc_viterbi) and for
-// the CPU simulator build, whose "device" memory is host memory (api.cpp under CTC_SIM runs them with a one-thread context).
+// and the confidence fold over the path; and the likelihood of a label sequence ("Transcript likelihood"): the
+// forward recursion over the same states, the sum over all alignments where the Viterbi takes the best one. One body each
+// for the HIP kernels (ctc_align_hip.hip: row_lse, ctc_viterbi, ctc_forward, ctc_forward_wave) and for the CPU simulator
+// build, whose "device" memory is host memory (api.cpp under CTC_SIM runs them with a one-thread context).
 #pragma once
 #include <math.h>
 #include <stddef.h>
@@ -46,11 +48,14 @@ CTC_HD double align_load(const void* x, int dtype, size_t i) {
 
 // The log-probability the alignment sees for one entry: log(clip(p, 1e-15, 1)) of a probability-like utterance, else
 // clip(x - lse, ln 1e-15, 0). A NaN takes the floor, so that every score stays ordered.
-CTC_HD double align_emit(const void* x, int dtype, size_t i, double lse, bool is_prob, double clip_lo) {
-  const double v = align_load(x, dtype, i);
+// (of_value: of an entry loaded earlier -- the forward kernels ask for a frame's entries one frame ahead of their use)
+CTC_HD double align_emit_of_value(double v, double lse, bool is_prob, double clip_lo) {
   if (is_prob) return log(!(v >= 1e-15) ? 1e-15 : (v > 1.0 ? 1.0 : v));
   const double y = v - lse;
   return !(y >= clip_lo) ? clip_lo : (y > 0.0 ? 0.0 : y);
+}
+CTC_HD double align_emit(const void* x, int dtype, size_t i, double lse, bool is_prob, double clip_lo) {
+  return align_emit_of_value(align_load(x, dtype, i), lse, is_prob, clip_lo);
 }
 
 // ---- row_lse: running maximum m and sum of exp(x - m) --------------------------------------------------------------------
@@ -212,6 +217,249 @@ CTC_HD void ctc_viterbi_utt(Ctx& cx, const AlignUtt& u, int V, int dtype, int bl
       else acc = (t == t0 || lp > acc) ? lp : acc;
     }
     u.tok_logp[k] = fold == LOGP_MEAN ? acc / (double)(t1 - t0) : acc;
+  }
+}
+
+// ---- ctc_forward / ctc_forward_wave ----------------------------------------------------------------------------------------
+// The likelihood of a label sequence: over the states and the reachable-state window of ctc_viterbi,
+//   a_t[s] = lse3(a_{t-1}[s], a_{t-1}[s-1], skip ? a_{t-1}[s-2] : -inf) + emit(t, s),   result = lse2(a_{T-1}[S-1], a_{T-1}[S-2]).
+// One hypothesis of a launch. The host validates every field before a launch as for AlignUtt (T >= L + repeats >= 1).
+struct ForwardHyp {
+  const void* x;       // [T, V] logits or probabilities of the hypothesis' utterance, of the launch's dtype
+  const double* lse;   // [T] log-sum-exp of each row (not read when is_prob)
+  const int32_t* lab;  // [L] the labels scored
+  double* logp;        // [1] out
+  int32_t T, L, is_prob, pad;
+};
+
+constexpr int32_t FORWARD_MAX_GROUPS = (2 * ALIGN_MAX_LABELS + 1 + 3) / 4;  // align_chunks(ALIGN_MAX_LABELS)
+constexpr int32_t FORWARD_WAVE_MAX_LABELS = 127;  // ctc_forward_wave: 2L + 1 <= 256 states, four to each of a wave's 64 lanes
+
+// log(exp(stay) + exp(step) + exp(skip)): the maximum first, then the sum in that fixed order; -inf when all three are.
+// No multiplication: contraction has nothing to fuse, and every caller gets the same bits from the same operands. An
+// operand of -inf adds exactly 0, with or without its exp (a blank's skip is the constant -inf: its exp compiles away).
+CTC_HD double align_lse3(double stay, double step, double skip) {
+  const double NEG = align_neg_inf();
+  double m = stay > step ? stay : step;
+  m = skip > m ? skip : m;
+  if (!(m > NEG)) return NEG;
+  double s = stay > NEG ? exp(stay - m) : 0.0;
+  s += step > NEG ? exp(step - m) : 0.0;
+  s += skip > NEG ? exp(skip - m) : 0.0;
+  return m + log(s);
+}
+CTC_HD double align_lse2(double a, double b) { return align_lse3(a, b, align_neg_inf()); }
+
+// What a group of four states (blank, label 2c, blank, label 2c + 1) keeps for the whole recursion: its labels (-1: the
+// target ends before them) and whether each may be entered over the blank before it.
+struct ForwardGroup {
+  int32_t l0, l1;
+  bool skip0, skip1, blank2;  // label 2c differs from label 2c - 1; label 2c + 1 from label 2c; the state 4c + 2 exists
+};
+CTC_HD ForwardGroup forward_group(const int32_t* lab, int L, int c) {
+  const int k0 = 2 * c, k1 = 2 * c + 1;
+  ForwardGroup g;
+  g.l0 = k0 < L ? lab[k0] : -1;
+  g.l1 = k1 < L ? lab[k1] : -1;
+  const int lm1 = k0 > 0 && k0 <= L ? lab[k0 - 1] : -1;
+  g.skip0 = g.l0 >= 0 && lm1 >= 0 && lm1 != g.l0;
+  g.skip1 = g.l1 >= 0 && g.l1 != g.l0;
+  g.blank2 = 4 * c + 2 < 2 * L + 1;
+  return g;
+}
+// One frame of one group, in place: p[0..3] the group's states at the frame before, pm1 the last state of the group below
+// (it serves the blank's step and the first label's skip), e_* the frame's emissions.
+CTC_HD void forward_step(const ForwardGroup& g, double pm1, double e_blank, double e0, double e1, double* p) {
+  const double NEG = align_neg_inf();
+  const double p0 = p[0], p1 = p[1], p2 = p[2], p3 = p[3];
+  p[0] = align_lse2(p0, pm1) + e_blank;
+  p[1] = g.l0 >= 0 ? align_lse3(p1, p0, g.skip0 ? pm1 : NEG) + e0 : NEG;
+  p[2] = g.blank2 ? align_lse2(p2, p1) + e_blank : NEG;
+  p[3] = g.l1 >= 0 ? align_lse3(p3, p2, g.skip1 ? p1 : NEG) + e1 : NEG;
+}
+// The groups that hold a state reachable from the start and from the end at frame t: [lo, hi] (ctc_viterbi's window)
+CTC_HD void forward_window(int t, int T, int S, int* clo, int* chi) {
+  const int lo = S - 2 - 2 * (T - 1 - t), hi = 2 * t + 1;
+  *clo = lo > 0 ? lo >> 2 : 0;
+  *chi = (hi < S - 1 ? hi : S - 1) >> 2;
+}
+
+// An entry of a matrix of dtype code DT as it lies in memory, and its (exact) widening to double. The forward kernels ask for
+// a frame's entries one frame ahead and keep them as loaded: a conversion at the load would make the load's latency wait there.
+template <int DT> struct AlignRaw { typedef uint16_t type; };
+template <> struct AlignRaw<0> { typedef float type; };
+template <> struct AlignRaw<1> { typedef double type; };
+template <int DT>
+CTC_HD typename AlignRaw<DT>::type align_load_raw(const void* x, size_t i) { return ((const typename AlignRaw<DT>::type*)x)[i]; }
+template <int DT>
+CTC_HD double align_widen(typename AlignRaw<DT>::type r) {
+  if (DT == 0 || DT == 1) return (double)r;
+  return (double)(DT == 2 ? f16_bits_to_f32((uint16_t)r) : bf16_bits_to_f32((uint16_t)r));
+}
+
+// ctc_forward: the threads of cx (tid, nt, sync(); Ctx::GROUPS * nt >= align_chunks(L)) share one hypothesis of a matrix of
+// dtype DT. Thread tid owns the groups tid, tid + nt, ... for the whole recursion: their labels and skip flags are read once,
+// their states stay in registers, and only a group's last state goes through `col` (2 * align_chunks(L) doubles, the columns
+// of two successive frames) to the thread that owns the group above: one barrier per frame. Nothing the recursion computes
+// decides the entries of frame t + 1: they are requested -- without a branch, at indices that are always valid, and kept as
+// loaded -- after the neighbour's state is in hand and before frame t's arithmetic and barrier.
+template <int DT, class Ctx>
+CTC_HD void ctc_forward_hyp(Ctx& cx, const ForwardHyp& hyp, int V, int blank, double clip_lo, double* col) {
+  typedef typename AlignRaw<DT>::type Raw;
+  constexpr int G = Ctx::GROUPS;
+  const void* const x = hyp.x;  // (the record, once: the loop below reads none of it again)
+  const double* const lse = hyp.lse;
+  const int32_t* const lab = hyp.lab;
+  double* const out = hyp.logp;
+  const int T = hyp.T, L = hyp.L;
+  const bool is_prob = hyp.is_prob != 0;
+  if (T <= 0) return;
+  const int S = 2 * L + 1, nch = align_chunks(L);
+  const double NEG = align_neg_inf();
+  ForwardGroup g[G];
+  int i0[G], i1[G];  // the columns a group's two labels read (the blank's where the target ends before them)
+  double p[G][4];    // states
+  Raw v0[G], v1[G];  // the entries of the frame in hand at those columns, as loaded
+  CTC_UNROLL
+  for (int k = 0; k < G; ++k) {
+    const int c = cx.tid + k * cx.nt;
+    p[k][0] = p[k][1] = p[k][2] = p[k][3] = NEG;
+    if (c < nch) g[k] = forward_group(lab, L, c);
+    else g[k] = ForwardGroup{-1, -1, false, false, false};
+    i0[k] = g[k].l0 >= 0 ? g[k].l0 : blank;
+    i1[k] = g[k].l1 >= 0 ? g[k].l1 : blank;
+  }
+  // (always 0, but per thread as far as the compiler knows: a row's log-sum-exp then comes by a vector load like the entries.
+  // Loaded at a workgroup-uniform address it would be a scalar load, which shares its counter with the LDS reads: the wait for
+  // the neighbour's state would wait for the next frame's value as well.)
+  const int per_thread_zero = g[0].l0 == -2 ? 1 : 0;
+  const double* const lse_v = lse + per_thread_zero;
+  for (int i = cx.tid; i < 2 * nch; i += cx.nt) col[i] = NEG;
+  if (cx.tid == 0) {
+    const double lse0 = is_prob ? 0.0 : lse[0];
+    p[0][0] = align_emit(x, DT, (size_t)blank, lse0, is_prob, clip_lo);
+    if (L > 0) p[0][1] = align_emit(x, DT, (size_t)lab[0], lse0, is_prob, clip_lo);
+  }
+  cx.sync();
+  // frame 1's entries (a single frame: frame 0's again, never used)
+  int clo = 0, chi = -1, clo_prev = 0;
+  if (T > 1) forward_window(1, T, S, &clo, &chi);
+  const size_t row1 = T > 1 ? (size_t)V : 0;
+  Raw vb = align_load_raw<DT>(x, row1 + (size_t)blank);
+  double lse_t = lse_v[T > 1 ? 1 : 0];
+  CTC_UNROLL
+  for (int k = 0; k < G; ++k) {
+    v0[k] = align_load_raw<DT>(x, row1 + (size_t)i0[k]);
+    v1[k] = align_load_raw<DT>(x, row1 + (size_t)i1[k]);
+  }
+  for (int t = 1; t < T; ++t) {
+    const double* prev = col + ((t - 1) & 1) * nch;
+    double* cur = col + (t & 1) * nch;
+    // the neighbours' states first: what lies below the window of the frame before is unreachable from the end and reads
+    // as -inf, as in ctc_viterbi
+    double pm1[G];
+    CTC_UNROLL
+    for (int k = 0; k < G; ++k) {
+      const int c = cx.tid + k * cx.nt;
+      pm1[k] = c >= clo && c <= chi && c > 0 && c - 1 >= clo_prev ? prev[c - 1] : NEG;
+    }
+    // then ask for frame t + 1 (after the last frame: the last frame again)
+    const int tn = t + 1 < T ? t + 1 : t;
+    int nlo = 0, nhi = -1;
+    if (t + 1 < T) forward_window(tn, T, S, &nlo, &nhi);
+    const size_t row = (size_t)tn * (size_t)V;
+    const Raw nvb = align_load_raw<DT>(x, row + (size_t)blank);
+    const double nlse = lse_v[tn];
+    Raw n0[G], n1[G];
+    CTC_UNROLL
+    for (int k = 0; k < G; ++k) {
+      n0[k] = align_load_raw<DT>(x, row + (size_t)i0[k]);
+      n1[k] = align_load_raw<DT>(x, row + (size_t)i1[k]);
+    }
+    const double lse_use = is_prob ? 0.0 : lse_t;
+    const double e_blank = align_emit_of_value(align_widen<DT>(vb), lse_use, is_prob, clip_lo);
+    CTC_UNROLL
+    for (int k = 0; k < G; ++k) {
+      const int c = cx.tid + k * cx.nt;
+      if (c < clo || c > chi) continue;
+      const double e0 = align_emit_of_value(align_widen<DT>(v0[k]), lse_use, is_prob, clip_lo);
+      const double e1 = align_emit_of_value(align_widen<DT>(v1[k]), lse_use, is_prob, clip_lo);
+      forward_step(g[k], pm1[k], e_blank, e0, e1, p[k]);
+      cur[c] = p[k][3];
+    }
+    clo_prev = clo;
+    clo = nlo, chi = nhi, vb = nvb, lse_t = nlse;
+    CTC_UNROLL
+    for (int k = 0; k < G; ++k) v0[k] = n0[k], v1[k] = n1[k];
+    cx.sync();  // the one barrier of a frame: the columns swap roles
+  }
+  // the last blank and the last label: state S - 1 = 2L is entry 0 or 2 of its group, S - 2 the entry before it
+  const int cf = (S - 1) >> 2, jf = (S - 1) & 3;
+  const double* fin = col + ((T - 1) & 1) * nch;
+  CTC_UNROLL
+  for (int k = 0; k < G; ++k) {
+    if (cx.tid + k * cx.nt != cf) continue;
+    const double last = jf == 2 ? p[k][2] : p[k][0];
+    const double before = jf == 2 ? p[k][1] : (cf > 0 ? fin[cf - 1] : NEG);
+    *out = align_lse2(last, before);
+  }
+}
+
+// ctc_forward_wave: one wavefront per hypothesis of at most FORWARD_WAVE_MAX_LABELS labels. Lane c owns group c; the last
+// state of the group below comes from lane c - 1 by cx.up() (one fp64 shuffle per frame): no LDS, no barrier. The same
+// groups, steps and prefetch as ctc_forward_hyp, so the same bits. cx: lane, up(v) = v of the lane below (any value in lane 0).
+template <int DT, class Ctx>
+CTC_HD void ctc_forward_wave_hyp(Ctx& cx, const ForwardHyp& hyp, int V, int blank, double clip_lo) {
+  typedef typename AlignRaw<DT>::type Raw;
+  const void* const x = hyp.x;
+  const double* const lse = hyp.lse;
+  const int32_t* const lab = hyp.lab;
+  double* const out = hyp.logp;
+  const int T = hyp.T, L = hyp.L, c = cx.lane;
+  const bool is_prob = hyp.is_prob != 0;
+  if (T <= 0) return;
+  const int S = 2 * L + 1, nch = align_chunks(L);
+  const double NEG = align_neg_inf();
+  const ForwardGroup g = c < nch ? forward_group(lab, L, c) : ForwardGroup{-1, -1, false, false, false};
+  const int i0 = g.l0 >= 0 ? g.l0 : blank, i1 = g.l1 >= 0 ? g.l1 : blank;
+  double p[4] = {NEG, NEG, NEG, NEG};
+  if (c == 0) {
+    const double lse0 = is_prob ? 0.0 : lse[0];
+    p[0] = align_emit(x, DT, (size_t)blank, lse0, is_prob, clip_lo);
+    if (L > 0) p[1] = align_emit(x, DT, (size_t)lab[0], lse0, is_prob, clip_lo);
+  }
+  int clo = 0, chi = -1, clo_prev = 0;
+  if (T > 1) forward_window(1, T, S, &clo, &chi);
+  const size_t row1 = T > 1 ? (size_t)V : 0;
+  Raw vb = align_load_raw<DT>(x, row1 + (size_t)blank);
+  Raw v0 = align_load_raw<DT>(x, row1 + (size_t)i0), v1 = align_load_raw<DT>(x, row1 + (size_t)i1);
+  double lse_t = lse[T > 1 ? 1 : 0];
+  for (int t = 1; t < T; ++t) {
+    const double below = cx.up(p[3]);  // (every lane takes part, whatever its window says)
+    const int tn = t + 1 < T ? t + 1 : t;
+    int nlo = 0, nhi = -1;
+    if (t + 1 < T) forward_window(tn, T, S, &nlo, &nhi);
+    const size_t row = (size_t)tn * (size_t)V;
+    const Raw nvb = align_load_raw<DT>(x, row + (size_t)blank);
+    const Raw n0 = align_load_raw<DT>(x, row + (size_t)i0), n1 = align_load_raw<DT>(x, row + (size_t)i1);
+    const double nlse = lse[tn];
+    if (c >= clo && c <= chi) {
+      const double pm1 = c > 0 && c - 1 >= clo_prev ? below : NEG;
+      const double lse_use = is_prob ? 0.0 : lse_t;
+      const double e_blank = align_emit_of_value(align_widen<DT>(vb), lse_use, is_prob, clip_lo);
+      const double e0 = align_emit_of_value(align_widen<DT>(v0), lse_use, is_prob, clip_lo);
+      const double e1 = align_emit_of_value(align_widen<DT>(v1), lse_use, is_prob, clip_lo);
+      forward_step(g, pm1, e_blank, e0, e1, p);
+    }
+    clo_prev = clo;
+    clo = nlo, chi = nhi, vb = nvb, lse_t = nlse, v0 = n0, v1 = n1;
+  }
+  const int cf = (S - 1) >> 2, jf = (S - 1) & 3;
+  const double below = cx.up(p[3]);
+  if (c == cf) {
+    const double last = jf == 2 ? p[2] : p[0];
+    const double before = jf == 2 ? p[1] : (cf > 0 ? below : NEG);
+    *out = align_lse2(last, before);
   }
 }
 

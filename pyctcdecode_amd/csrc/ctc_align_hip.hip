@@ -1,5 +1,6 @@
-// ctc_align_hip.hip -- forced alignment on gfx950 (ctc_align.h): row_lse, the fp64 log-sum-exp of every frame row, and
-// ctc_viterbi, one workgroup per utterance over the blank / label / blank / ... states. A translation unit of its own.
+// ctc_align_hip.hip -- forced alignment and transcript likelihood on gfx950 (ctc_align.h): row_lse, the fp64 log-sum-exp of
+// every frame row; ctc_viterbi, one workgroup per utterance over the blank / label / blank / ... states; ctc_forward and
+// ctc_forward_wave, the sum over all alignments of a hypothesis, one workgroup / one wavefront each. A translation unit of its own.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -115,6 +116,42 @@ __global__ __launch_bounds__(ALIGN_THREADS) void ctc_viterbi(ViterbiArgs a) {
   ctc_viterbi_utt(cx, a.utts[blockIdx.x], a.n_labels, a.dtype, a.blank, a.fold, a.clip_lo, align_cols);
 }
 
+// ---------------------------------------------------------------------------------------------
+// ctc_forward: one workgroup per hypothesis, one group of four states per thread in registers (256 threads up to 511 labels,
+// 1024 above), the groups' last states in two LDS columns, one barrier per frame. ctc_forward_wave: a wavefront per
+// hypothesis of at most 127 labels, four to a workgroup that never synchronises; the neighbour's state by one fp64 shuffle
+// per frame (ctc_align.h)
+// ---------------------------------------------------------------------------------------------
+struct ForwardGpuCtx {
+  enum { GROUPS = 1 };
+  int tid, nt;
+  __device__ __forceinline__ void sync() { __syncthreads(); }
+};
+constexpr int FORWARD_THREADS_MAX = 1024;
+static_assert(FORWARD_THREADS_MAX * ForwardGpuCtx::GROUPS >= FORWARD_MAX_GROUPS, "a thread per group of the longest target");
+
+template <int NT, int DT>
+__global__ __launch_bounds__(NT) void ctc_forward(ForwardArgs a) {
+  extern __shared__ double forward_cols[];
+  ForwardGpuCtx cx{(int)threadIdx.x, NT};
+  ctc_forward_hyp<DT>(cx, a.hyps[blockIdx.x], a.n_labels, a.blank, a.clip_lo, forward_cols);
+}
+
+struct ForwardWaveCtx {
+  int lane;
+  __device__ __forceinline__ double up(double v) { return __shfl_up(v, 1, 64); }
+};
+
+constexpr int FORWARD_WAVES = ALIGN_THREADS / 64;  // hypotheses per workgroup of ctc_forward_wave
+
+template <int DT>
+__global__ __launch_bounds__(ALIGN_THREADS) void ctc_forward_wave(ForwardArgs a) {
+  const int i = (int)blockIdx.x * FORWARD_WAVES + (int)(threadIdx.x >> 6);
+  if (i >= a.n_hyps) return;  // (a whole wave: nothing in this kernel waits for another wave)
+  ForwardWaveCtx cx{(int)(threadIdx.x & 63u)};
+  ctc_forward_wave_hyp<DT>(cx, a.hyps[i], a.n_labels, a.blank, a.clip_lo);
+}
+
 // kernel times: one pair of events per launch since the last reset
 struct EventLog {
   std::vector<hipEvent_t> ev;
@@ -137,9 +174,10 @@ struct EventLog {
     return sum;
   }
 };
-static EventLog g_lse_log, g_vit_log;
+static EventLog g_lse_log, g_vit_log, g_fwd_log;
 
-void align_timing_reset() { g_lse_log.used = g_vit_log.used = 0; }
+void align_timing_reset() { g_lse_log.used = g_vit_log.used = g_fwd_log.used = 0; }
+double forward_timing() { return g_fwd_log.total(); }
 void align_timing(double* row_lse_ms, double* viterbi_ms) {
   *row_lse_ms = g_lse_log.total();
   *viterbi_ms = g_vit_log.total();
@@ -182,6 +220,35 @@ int launch_ctc_viterbi_on(const ViterbiArgs& a, hipStream_t stream, std::string*
   if (g_vit_log.next(&e0, err) || g_vit_log.next(&e1, err)) return -1;
   HIP_TRY_A(hipEventRecord(e0, stream));
   hipLaunchKernelGGL(ctc_viterbi, dim3((unsigned)a.n_utts), dim3(ALIGN_THREADS), lds, stream, a);
+  HIP_TRY_A(hipGetLastError());
+  HIP_TRY_A(hipEventRecord(e1, stream));
+  return 0;
+}
+
+template <int DT>
+static void launch_forward_dt(const ForwardArgs& a, int wave, hipStream_t stream) {
+  if (wave) {
+    hipLaunchKernelGGL(ctc_forward_wave<DT>, dim3((unsigned)((a.n_hyps + FORWARD_WAVES - 1) / FORWARD_WAVES)), dim3(ALIGN_THREADS), 0, stream, a);
+    return;
+  }
+  const size_t lds = (size_t)2 * (size_t)a.max_chunks * sizeof(double);  // <= 16 KB
+  if (a.max_chunks <= ALIGN_THREADS) hipLaunchKernelGGL((ctc_forward<ALIGN_THREADS, DT>), dim3((unsigned)a.n_hyps), dim3(ALIGN_THREADS), lds, stream, a);
+  else hipLaunchKernelGGL((ctc_forward<FORWARD_THREADS_MAX, DT>), dim3((unsigned)a.n_hyps), dim3(FORWARD_THREADS_MAX), lds, stream, a);
+}
+
+int launch_ctc_forward_on(const ForwardArgs& a, int wave, hipStream_t stream, std::string* err) {
+  if (a.n_hyps <= 0) return 0;
+  if (a.dtype < 0 || a.dtype > 3 || a.max_chunks < 1 || a.max_chunks > (wave ? align_chunks(FORWARD_WAVE_MAX_LABELS) : align_chunks(ALIGN_MAX_LABELS))) {
+    if (err) *err = "ctc_forward: more states than the kernel holds";
+    return -1;
+  }
+  hipEvent_t e0, e1;
+  if (g_fwd_log.next(&e0, err) || g_fwd_log.next(&e1, err)) return -1;
+  HIP_TRY_A(hipEventRecord(e0, stream));
+  if (a.dtype == 0) launch_forward_dt<0>(a, wave, stream);
+  else if (a.dtype == 1) launch_forward_dt<1>(a, wave, stream);
+  else if (a.dtype == 2) launch_forward_dt<2>(a, wave, stream);
+  else launch_forward_dt<3>(a, wave, stream);
   HIP_TRY_A(hipGetLastError());
   HIP_TRY_A(hipEventRecord(e1, stream));
   return 0;

@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import ctypes as C
 import dataclasses
+import itertools
 import logging
 import math
 import os
@@ -164,6 +165,22 @@ class AlignedText:
     word_logp: Optional[List[float]] = None
 
 
+@dataclasses.dataclass(frozen=True)
+class ScoredText:
+    """How probable a transcript is, given the audio (BeamSearchDecoderCTC.score / score_batch): ``logp`` is the CTC forward
+    score of the label ids ``tokens`` -- the natural log of the sum, over all their alignments, of the product of the frames'
+    clipped probabilities -- and ``-inf`` where no alignment exists. ``text`` is the normalised text, formed the way
+    AlignedText.text is. ``lm_logp`` (``with_lm=True``, else None) is what the beam search adds for a finished beam with this
+    text and no hot words; ``total`` is ``logp + (lm_logp or 0.0)``."""
+
+    text: str
+    tokens: List[int]
+    logp: float
+    lm_logp: Optional[float] = None
+    total: float = 0.0
+
+
+FORWARD_KERNELS = {"wave": 1, "group": 2}  # ctcdec_score_batch's `kernel` from CTCDEC_FORWARD_KERNEL (unset: the library chooses)
 CONFIDENCE_FOLDS = {"mean": 2, "min": 3, "max": 4}  # ctcdec_params.token_frames: CTCDEC_TOKEN_LOGP_MEAN / _MIN / _MAX
 
 
@@ -1044,6 +1061,10 @@ class BeamSearchDecoderCTC:
         # one native call at a time per decoder: hot words / per-model weights are decoder state that a call sets
         # up first (host threads may share a decoder; ctypes releases the GIL while the device works)
         self._call_lock = threading.RLock()
+        # diagnostics of the last score / score_batch call (ms: classification, row_lse, forward kernels, native call;
+        # hypotheses taken by the wave kernel and by the group kernel)
+        self.last_score_timing_ms = (0.0, 0.0, 0.0, 0.0)
+        self.last_score_launched = (0, 0)
 
     def __del__(self):
         h = getattr(self, "_handle", None)
@@ -1623,6 +1644,118 @@ class BeamSearchDecoderCTC:
                     wlp = [min(tlp[lo:hi]) for _w, lo, hi in words]
                 out[u] = AlignedText(text, path[path_off[j]:path_off[j + 1]].copy(), float(score[j]), tok, wf, tlp, wlp)
             return out
+
+    # -- transcript likelihood (no reference analogue; DESIGN.md, "Transcript likelihood") ----------------
+    def score(self, logits: Any, texts: Optional[Sequence[str]] = None, tokens: Optional[Sequence[Sequence[int]]] = None,
+              with_lm: bool = False) -> List["ScoredText"]:
+        """The likelihood of each hypothesis for one utterance: score_batch of a batch of one."""
+        self._check_logits_dimension(logits)
+        return self.score_batch([logits], None if texts is None else [texts], tokens=None if tokens is None else [tokens],
+                                with_lm=with_lm)[0]
+
+    def score_batch(self, logits_list: Any, texts: Optional[Sequence[Sequence[str]]] = None,
+                    tokens: Optional[Sequence[Sequence[Sequence[int]]]] = None, with_lm: bool = False) -> List[List["ScoredText"]]:
+        """How probable each given transcript is, in one native call: per utterance a sequence of hypotheses, per hypothesis
+        the CTC forward score (row_lse once per utterance + ctc_forward / ctc_forward_wave, csrc/ctc_align_hip.hip) as
+        ScoredText. ``logits_list`` is what align_batch takes; ``texts[u]`` (character alphabets) is a list of str,
+        ``tokens[u]`` a list of lists of label ids, the only form for BPE alphabets. A hypothesis without an alignment --
+        fewer frames than labels plus adjacent equal labels -- has ``logp == -inf``; the empty hypothesis scores the all-blank
+        path. ``with_lm=True`` adds the language model's score of the text as a finished beam's (no hot words)."""
+        if (texts is None) == (tokens is None):
+            raise ValueError("score: give exactly one of texts and tokens")
+        if texts is not None and self._is_bpe:
+            raise ValueError("a text has many segmentations under a BPE alphabet: give the hypotheses as tokens=")
+        lm = self._language_model
+        if with_lm and lm is None:
+            raise ValueError("score: with_lm=True needs a decoder with a language model")
+        if getattr(logits_list, "ndim", 0) != 3:
+            logits_list = list(logits_list)
+        n = len(logits_list)
+        given = texts if texts is not None else tokens
+        if not isinstance(given, str):
+            given = list(given)  # (a generator has no len())
+        if isinstance(given, str) or len(given) != n:
+            raise ValueError("score: hypotheses for %d utterances, but %d utterances" % (1 if isinstance(given, str) else len(given), n))
+        blank, n_labels = self._vocab2idx[""], len(self._labels_list)
+        hyps: List[List[List[int]]] = []
+        for u, per_utt in enumerate(given):
+            if isinstance(per_utt, str):
+                raise ValueError("score: utterance %d got a bare str where a sequence of hypotheses is expected (wrap it in a "
+                                 "list: a str would be read character by character)" % u)
+            cur = []
+            for j, g in enumerate(per_utt):
+                who = "utterance %d, hypothesis %d" % (u, j)
+                if texts is not None:
+                    if not isinstance(g, str):
+                        raise ValueError("score: %s is not a str" % who)
+                    ids = self._target_of_text(g)
+                else:
+                    if isinstance(g, str):
+                        raise ValueError("score: %s is a str, not a sequence of label ids" % who)
+                    ids = list(g)
+                    if set(map(type, ids)) <= {int} and (not ids or (0 <= min(ids) and max(ids) < n_labels and blank not in ids)):
+                        pass  # (plain ints, all in range: the check below, without a Python-level loop)
+                    else:
+                        for k, c in enumerate(ids):
+                            if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 0 <= int(c) < n_labels or int(c) == blank:
+                                raise ValueError("score: %s holds %r: not a label id in [0, %d) other than the blank (%d)"
+                                                 % (who, c, n_labels, blank))
+                            ids[k] = int(c)
+                if len(ids) > ALIGN_MAX_LABELS:
+                    raise ValueError("score: %s has %d labels, above the limit of %d labels per hypothesis"
+                                     % (who, len(ids), ALIGN_MAX_LABELS))
+                cur.append(ids)
+            hyps.append(cur)
+        if n == 0:
+            self.last_score_timing_ms, self.last_score_launched = (0.0, 0.0, 0.0, 0.0), (0, 0)
+            return []
+        kernel_env = os.environ.get("CTCDEC_FORWARD_KERNEL", "")
+        if kernel_env and kernel_env not in FORWARD_KERNELS:
+            raise ValueError("CTCDEC_FORWARD_KERNEL must be wave or group, not %r" % kernel_env)
+        with self._call_lock:
+            batch = _Batch(logits_list, n_labels)
+            if batch.is_device and batch.device_index is not None and batch.device_index != self._device:
+                raise ValueError("the logits live on cuda:%d but this decoder was built for cuda:%d (one process per GPU: "
+                                 "LOCAL_RANK / CTCDEC_DEVICE pick the device)" % (batch.device_index, self._device))
+            frames = np.ascontiguousarray(np.asarray(batch.frames, dtype=np.int32))
+            ptrs = np.ascontiguousarray(np.asarray(batch.ptrs, dtype=np.uint64))
+            flat_hyps = [ids for cur in hyps for ids in cur]
+            flat = np.fromiter(itertools.chain.from_iterable(flat_hyps), dtype=np.int32)
+            if not len(flat):
+                flat = np.zeros(1, dtype=np.int32)
+            target_off = np.zeros(len(flat_hyps) + 1, dtype=np.int64)
+            target_off[1:] = np.cumsum([len(ids) for ids in flat_hyps])
+            hyp_off = np.zeros(n + 1, dtype=np.int64)
+            hyp_off[1:] = np.cumsum([len(cur) for cur in hyps])
+            logp = np.zeros(max(len(flat_hyps), 1), dtype=np.float64)
+            ms, launched = (C.c_double * 4)(), (C.c_int64 * 2)()
+            lib = self._lib
+            lib.check(lib.dll.ctcdec_score_batch(
+                self._handle, ptrs.ctypes.data_as(C.POINTER(C.c_void_p)), frames.ctypes.data_as(C.POINTER(C.c_int32)), n,
+                batch.dtype, int(batch.is_device), flat.ctypes.data_as(C.POINTER(C.c_int32)), B.off_ptr(target_off),
+                B.off_ptr(hyp_off), FORWARD_KERNELS.get(kernel_env, 0), logp.ctypes.data_as(C.POINTER(C.c_double)), ms, launched))
+            # [classification (frame-prune kernels), row_lse, forward kernels (HIP events), whole native call]; hypotheses that
+            # went to (ctc_forward_wave, ctc_forward)
+            self.last_score_timing_ms = tuple(float(v) for v in ms)
+            self.last_score_launched = (int(launched[0]), int(launched[1]))
+        out: List[List[ScoredText]] = []
+        h = 0
+        for cur in hyps:
+            res = []
+            for ids in cur:
+                text = self._words_of_target(ids)[0]
+                lm_logp = None
+                if with_lm:
+                    # what the beam search adds for a finished beam (decoder.py:446-497 of the reference, without hot words)
+                    state, lm_logp, words = lm.get_start_state(), 0.0, text.split()
+                    for k, word in enumerate(words):
+                        word_score, state = lm.score(state, word, is_last_word=k == len(words) - 1)
+                        lm_logp += word_score
+                lp = float(logp[h])
+                res.append(ScoredText(text, list(ids), lp, lm_logp, lp + (lm_logp or 0.0)))
+                h += 1
+            out.append(res)
+        return out
 
     # -- serialisation (decoder.py:947-1043): alphabet.json + language_model/ --------------------------
     _ALPHABET_SERIALIZED_FILENAME = "alphabet.json"

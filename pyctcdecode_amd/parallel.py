@@ -196,6 +196,11 @@ def align_batch_sharded(decoder, logits_list, texts=None, group=None, **kwargs):
     raise NotImplementedError("align_batch is not gathered over ranks: align each rank's slice with decoder.align_batch itself")
 
 
+def score_batch_sharded(decoder, logits_list, texts=None, group=None, **kwargs):
+    """Transcript scoring is not sharded over ranks: each rank calls decoder.score_batch on its own slice."""
+    raise NotImplementedError("score_batch is not gathered over ranks: score each rank's slice with decoder.score_batch itself")
+
+
 def _device_worker(conn, device: int, decoder_dir: str, library: Optional[str]) -> None:
     """One worker process = one GPU (the native library binds one device per process): loads the saved decoder on its device and
     serves (method, logits, kwargs) requests until it is told to stop."""
@@ -318,6 +323,12 @@ class DevicePool:
         raise NotImplementedError("DevicePool does not shard align_batch: call decoder.align_batch on the process's own device")
 
     align = align_batch
+
+    def score_batch(self, logits_list, texts=None, **kwargs):
+        """Transcript scoring runs on the calling process's own device: a pool does not shard it."""
+        raise NotImplementedError("DevicePool does not shard score_batch: call decoder.score_batch on the process's own device")
+
+    score = score_batch
 
     def decode_batch(self, logits_list, **kwargs) -> List[str]:
         if kwargs.get("token_frames") or kwargs.get("confidence") is not None:  # (texts, TokenFrames) per slice -> one of each, offsets rebased

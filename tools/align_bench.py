@@ -1,8 +1,11 @@
-"""Times forced alignment (align_batch: row_lse + ctc_viterbi, csrc/ctc_align_hip.hip) at the bench shape -- 4096 utterances
-of 1000 frames x 1024 labels, float32, each aligned to its own decoded tokens -- and at 64 utterances, with the plain
-decode_batch step of the same process for scale. Kernel times are HIP events on the decode stream (ctcdec_alignment_timing).
+"""Times forced alignment (align_batch: row_lse + ctc_viterbi, csrc/ctc_align_hip.hip) and transcript likelihood (score_batch:
+row_lse + ctc_forward / ctc_forward_wave) at the bench shape -- 4096 utterances of 1000 frames x 1024 labels, float32, each
+aligned to / scored with its own decoded tokens, and scored with 8 hypotheses (its tokens plus seven copies with one label
+substituted), each forward kernel forced in turn -- and at 64 utterances, with the plain decode_batch step of the same process
+for scale; then a sweep of target lengths on 256 utterances of random logits, which is what the wave / group threshold of
+ctcdec_score_batch rests on. Kernel times are HIP events on the decode stream (ctcdec_alignment_timing, ctcdec_score_batch).
   python tools/align_bench.py [--out profiles/align_bench.txt] [--steps 3]
-The 4096 utterances are 256 distinct ones repeated: neither kernel's time depends on the rows being distinct."""
+The 4096 utterances are 256 distinct ones repeated: no kernel's time depends on the rows being distinct."""
 import argparse
 import os
 import sys
@@ -22,6 +25,115 @@ _G = {}
 def _gen(u):
     g = _G
     return synth.d_words(4, u, T, g["labels"], True, g["words"], g["sentences"], len(g["labels"]), boost=6.0)
+
+
+def med(v):
+    return float(np.median(v[1:]))  # (the first step is the warm-up)
+
+
+def time_score(dec, dev, hyps, kernel, steps):
+    """Medians over `steps` calls after one warm-up of score_batch under CTCDEC_FORWARD_KERNEL=kernel ("" : the library
+    chooses): (forward kernels ms, row_lse ms, whole native call ms, Python wall ms, hypotheses per kernel)."""
+    if kernel:
+        os.environ["CTCDEC_FORWARD_KERNEL"] = kernel
+    else:
+        os.environ.pop("CTCDEC_FORWARD_KERNEL", None)
+    fwd, lse, native, wall = [], [], [], []
+    for _ in range(steps + 1):
+        t0 = time.perf_counter()
+        out = dec.score_batch(dev, tokens=hyps)
+        wall.append((time.perf_counter() - t0) * 1e3)
+        ms = dec.last_score_timing_ms
+        lse.append(ms[1]), fwd.append(ms[2]), native.append(ms[3])
+    os.environ.pop("CTCDEC_FORWARD_KERNEL", None)
+    assert all(np.isfinite(g.logp) for per_utt in out for g in per_utt)
+    return med(fwd), med(lse), med(native), med(wall), dec.last_score_launched
+
+
+def score_lines(dec, dev, targets, steps, vit_ms):
+    rng = np.random.default_rng(3)
+    blank = dec._alphabet.labels.index("")
+    pool = [c for c in range(V) if c != blank]
+    lines = []
+    eight = []
+    for t in targets:
+        hyps = [list(t)]
+        for _ in range(7):
+            sub = list(t)
+            if sub:
+                sub[int(rng.integers(0, len(sub)))] = pool[int(rng.integers(0, len(pool)))]
+            hyps.append(sub)
+        eight.append(hyps)
+    for what, hyps in (("1 hypothesis ", [[t] for t in targets]), ("8 hypotheses", eight)):
+        for kernel in ("wave", "group", ""):
+            fwd, lse, native, wall, launched = time_score(dec, dev, hyps, kernel, steps)
+            lines.append("  score_batch %s %-5s  forward %9.3f ms  row_lse %9.3f ms  native call %9.3f ms  Python call %9.3f ms  "
+                         "(wave kernel %d, group kernel %d hypotheses)" % (what, kernel or "auto", fwd, lse, native, wall, launched[0], launched[1]))
+            if what.startswith("1") and kernel == "group":
+                lines.append("    ctc_forward / ctc_viterbi at this batch: %.2f" % (fwd / vit_ms))
+    return lines
+
+
+def time_forward(dec, dev, hyps, kernels, steps):
+    """The forward kernels' time (HIP events) under each forced kernel: one warm-up call each, then `steps` rounds that
+    alternate between them (clocks as they come: neither kernel gets the warmer half of the run). -> {kernel: median ms}"""
+    got = {k: [] for k in kernels}
+    for step in range(steps + 1):
+        for k in kernels:
+            os.environ["CTCDEC_FORWARD_KERNEL"] = k
+            dec.score_batch(dev, tokens=hyps)
+            if step:
+                got[k].append(dec.last_score_timing_ms[2])
+    os.environ.pop("CTCDEC_FORWARD_KERNEL", None)
+    return {k: float(np.median(v)) for k, v in got.items()}
+
+
+def sweep_lines(dec, steps):
+    """256 utterances of standard-normal logits x 3, random targets without repeats of each length, one hypothesis and eight
+    (the target plus seven copies with one label substituted) per utterance: both forward kernels where both take the length,
+    and ctc_viterbi on the same batch."""
+    import torch
+
+    lines = ["sweep of target lengths, 256 utterances x %d labels float32 (random logits), 1 and 8 hypotheses per utterance; "
+             "%d alternating steps after one warm-up each, medians:" % (V, steps),
+             "  %6s %6s | %12s %12s %10s | %12s %12s %10s | %12s %8s" % (
+                 "labels", "frames", "wave x1", "group x1", "wave/group", "wave x8", "group x8", "wave/group", "ctc_viterbi", "fwd/vit")]
+    rng = np.random.default_rng(5)
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(5)
+    blank = dec._alphabet.labels.index("")
+    pool = np.array([c for c in range(V) if c != blank])
+    # (15 labels twice, first and last: what the first row of a sweep measures may be the first use, not the length)
+    for L in (15, 31, 63, 127, 255, 511, 2047, 15):
+        frames = T if L < T - 100 else 2100
+        dev = torch.randn((DISTINCT, frames, V), generator=gen, device="cuda", dtype=torch.float32) * 3
+        torch.cuda.synchronize()
+        targets, eight = [], []
+        for _ in range(DISTINCT):
+            t = pool[rng.integers(0, len(pool), size=L)]
+            same = np.flatnonzero(t[1:] == t[:-1]) + 1
+            t[same] = pool[(np.searchsorted(pool, t[same]) + 1) % len(pool)]
+            targets.append(t.tolist())
+            hyps = [t.tolist()]
+            for _k in range(7):
+                sub = t.copy()
+                sub[int(rng.integers(0, L))] = pool[int(rng.integers(0, len(pool)))]
+                hyps.append(sub.tolist())
+            eight.append(hyps)
+        kernels = ("wave", "group") if L <= 127 else ("group",)
+        one = time_forward(dec, dev, [[t] for t in targets], kernels, steps)
+        many = time_forward(dec, dev, eight, kernels, steps)
+        vit = []
+        for _ in range(steps + 1):
+            dec.align_batch(dev, tokens=targets)
+            vit.append(dec.last_align_timing_ms[2])
+        cell = lambda d, k: "%9.3f ms" % d[k] if k in d else "%12s" % "-"  # noqa: E731
+        ratio = lambda d: "%10.2f" % (d["wave"] / d["group"]) if "wave" in d else "%10s" % "-"  # noqa: E731
+        lines.append("  %6d %6d | %s %s %s | %s %s %s | %9.3f ms %8.2f" % (
+            L, frames, cell(one, "wave"), cell(one, "group"), ratio(one), cell(many, "wave"), cell(many, "group"), ratio(many),
+            med(vit), one["group"] / med(vit)))
+        del dev
+    return lines
 
 
 def main():
@@ -45,7 +157,7 @@ def main():
 
     dec = build_ctcdecoder(labels, lm.path)
     base_dev = torch.from_numpy(base).cuda()
-    lines = ["forced alignment, %d frames x %d labels float32 per utterance, targets = the utterance's own decoded tokens; "
+    lines = ["forced alignment and transcript likelihood, %d frames x %d labels float32 per utterance, targets = the utterance's own decoded tokens; "
              "%d steps after one warm-up, medians" % (T, V, args.steps)]
     for n in (4096, 64):
         dev = base_dev.repeat(n // DISTINCT, 1, 1) if n > DISTINCT else base_dev[:n].contiguous()
@@ -65,7 +177,6 @@ def main():
             ms = dec.last_align_timing_ms
             sniff.append(ms[0]), lse.append(ms[1]), vit.append(ms[2]), native.append(ms[3])
         assert all(a is not None and len(a.path) == T for a in out)
-        med = lambda v: float(np.median(v[1:]))  # noqa: E731
         read = n * T * V * 4
         dev_ms = med(sniff) + med(lse) + med(vit)
         lines += [
@@ -78,7 +189,9 @@ def main():
             "  align_batch      %9.3f ms  (Python share %.3f ms: targets in, AlignedText objects out)" % (med(wall), med(wall) - med(native)),
             "  decode_batch     %9.3f ms  (the plain beam-search step on the same tensor, for scale)" % med(decode_ms),
         ]
+        lines += score_lines(dec, dev, targets, args.steps, med(vit))
         del dev
+    lines += sweep_lines(dec, max(args.steps, 5))
     text = "\n".join(lines) + "\n"
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
