@@ -392,6 +392,46 @@ int ctcdec_score_batch(ctcdec_decoder* dec, const void* const* utt_logits, const
                        int32_t dtype, int32_t is_device, const int32_t* targets, const int64_t* target_off,
                        const int64_t* hyp_off, int32_t kernel, double* logp_out, double* ms4, int64_t* launched2);
 
+/* ---- frame posteriors: where, under ALL alignments of a label sequence the caller already has, each frame lies ---------
+ * No reference analogue: the CTC forward-backward. Utterance u's target is labels[label_off[u] .. label_off[u + 1]) (alphabet
+ * indices, never the blank; at most 2047 of them); logits, frame counts, dtype, is_device, the probabilities-or-logits rule
+ * and the per-frame log-probabilities e(t, s) (clipped, float64) are those of ctcdec_align_batch. Over the S = 2 L + 1 states
+ * blank / label 0 / blank / ... / label L - 1 / blank:
+ *   a_t[s]: the forward recursion of ctcdec_score_batch, which includes frame t's emission; logp = lse2(a_{T-1}[S-1],
+ *           a_{T-1}[S-2]) is that call's score for the same input, bit for bit;
+ *   b_t[s]: the log of the sum over all completions from state s after frame t (frame t's emission excluded):
+ *           b_{T-1}[S-1] = b_{T-1}[S-2] = 0,
+ *           b_t[s] = lse3(b_{t+1}[s] + e(t+1, s), b_{t+1}[s+1] + e(t+1, s+1), skip(s+2) ? b_{t+1}[s+2] + e(t+1, s+2) : -inf),
+ *           summed in that order as m + log(sum of exp(v - m));
+ *   logp_backward = lse2(b_0[0] + e(0, blank), b_0[1] + e(0, label 0)): logp again, read off the other end;
+ *   gamma[t, s] = exp(a_t[s] + b_t[s] - logp), as computed (not clamped: a value may exceed 1 by rounding), and exactly 0.0
+ *           for a state outside the window S - 2 - 2 (T - 1 - t) <= s <= 2 t + 1 no alignment passes through;
+ *   occupancy[k] = sum over t of gamma[t, 2 k + 1], centre[k] = sum over t of t * gamma[t, 2 k + 1], over occupancy[k]; both
+ *           are summed on the device in the order t = T - 1 .. 0 and have the same bits with and without `dense`.
+ * dense != 0 also returns gamma (copied to the host launch by launch; 32 * T * ceil(S / 4) bytes per utterance: large batches
+ * want dense == 0). table_budget: bytes of such tables one kernel launch may hold, 0 for the default of 4 GiB; a batch that
+ * needs more runs in several launches with the same results. Everything is validated before anything is launched, with
+ * ctcdec_align_batch's codes: a label outside the alphabet or equal to the blank, or an utterance with fewer frames than
+ * labels plus adjacent equal labels (the message lists them) is CTCDEC_ERR_ARG; more than 2047 labels, or one utterance whose
+ * table alone exceeds the budget, is CTCDEC_ERR_LIMIT. An utterance without frames and with the empty target has logp 0.0. */
+typedef struct ctcdec_posteriors ctcdec_posteriors; /* opaque */
+int ctcdec_posteriors_batch(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts,
+                            int32_t dtype, int32_t is_device, const int64_t* label_off, const int32_t* labels, int32_t dense,
+                            int64_t table_budget, ctcdec_posteriors** out);
+/* logp[u] and logp_backward[u] of every utterance. Pointers stay valid until ctcdec_posteriors_free. */
+int ctcdec_posteriors_scores(const ctcdec_posteriors* p, const double** logp, const double** logp_backward, int64_t* n_utts);
+/* Utterance u's token summaries are [tok_off[u], tok_off[u + 1]) of occupancy / centre (tok_off is label_off). */
+int ctcdec_posteriors_tokens(const ctcdec_posteriors* p, const int64_t** tok_off, const double** occupancy, const double** centre,
+                             int64_t* n_tokens);
+/* The dense tables: utterance u's gamma[t, s] is gamma[gamma_off[u] + t * row_stride[u] + s], s < 2 L + 1 (the row stride, in
+ * doubles, is S rounded up to a multiple of four; the padding holds 0.0). gamma is NULL when dense was 0. */
+int ctcdec_posteriors_gamma(const ctcdec_posteriors* p, const int64_t** gamma_off, const int32_t** row_stride, const double** gamma);
+/* milliseconds: [0] the classification (frame-prune kernels), [1] row_lse, [2] ctc_posteriors (HIP events on the decode
+ * stream, summed over the launches), [3] the whole native call; launches: kernel launches made (may be NULL); launched2 (may
+ * be NULL): utterances that went to [0] the 256-thread kernel (up to 511 labels), [1] the 1024-thread kernel */
+int ctcdec_posteriors_timing(const ctcdec_posteriors* p, double* ms4, int32_t* launches, int64_t* launched2);
+void ctcdec_posteriors_free(ctcdec_posteriors* p);
+
 /* timing of the last call's device stages in milliseconds (HIP events on the decode stream):
  * [0] frame-prune kernel, [1] beam kernel, [2] total device time incl. result copy */
 int ctcdec_result_timing(const ctcdec_result* r, double* ms3);

@@ -156,6 +156,16 @@ _PROTOS = {
     "ctcdec_score_batch": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32,
                                      C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32,
                                      C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
+    "ctcdec_posteriors_batch": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32,
+                                          C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int32, C.c_int64, C.POINTER(_VP)]),
+    "ctcdec_posteriors_scores": (C.c_int, [_VP, C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.POINTER(C.c_double)),
+                                           C.POINTER(C.c_int64)]),
+    "ctcdec_posteriors_tokens": (C.c_int, [_VP, C.POINTER(C.POINTER(C.c_int64)), C.POINTER(C.POINTER(C.c_double)),
+                                           C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.c_int64)]),
+    "ctcdec_posteriors_gamma": (C.c_int, [_VP, C.POINTER(C.POINTER(C.c_int64)), C.POINTER(C.POINTER(C.c_int32)),
+                                          C.POINTER(C.POINTER(C.c_double))]),
+    "ctcdec_posteriors_timing": (C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "ctcdec_posteriors_free": (None, [_VP]),
     "ctcdec_result_timing": (C.c_int, [_VP, C.POINTER(C.c_double)]),
     "ctcdec_result_beam_kernel": (C.c_int, [_VP]),
     "ctcdec_device": (C.c_int, []),

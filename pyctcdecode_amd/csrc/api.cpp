@@ -211,6 +211,9 @@ struct ctcdec_decoder {
   DevBuf w_alse, w_alab, w_apath, w_atok, w_atlp, w_ascore, w_abp, w_autts;
   // transcript likelihood (ctcdec_score_batch): the hypothesis records of a launch (labels: w_alab, scores: w_ascore)
   DevBuf w_fhyps;
+  // frame posteriors (ctcdec_posteriors_batch): a launch's tables and utterance records, the token sums (labels: w_alab,
+  // score pairs: w_ascore)
+  DevBuf w_ptab, w_putts, w_pocc;
   bool slicing = false;  // a time-sliced host ingest is under way (decode_host_sliced): the prune stage notes each slice's side of 1
   uint32_t max_label_bytes = 1;
   bool arenas_worst_case = false;  // a call has outgrown the usual reservation of the node arenas: reserve the worst case from now on
@@ -2710,6 +2713,221 @@ int ctcdec_score_batch(ctcdec_decoder* dec, const void* const* utt_logits, const
   if (launched2) launched2[0] = launched[0], launched2[1] = launched[1];
   return CTCDEC_OK;
 }
+
+// ---- frame posteriors ("Frame posteriors") --------------------------------------------------------------------
+}  // extern "C"
+
+struct ctcdec_posteriors {
+  std::vector<int64_t> tok_off, gamma_off;
+  std::vector<int32_t> gamma_stride;
+  std::vector<double> logp, logp_backward, occupancy, centre, gamma;
+  bool dense = false;
+  int32_t launches = 0;
+  int64_t launched[2] = {0, 0};
+  double ms[4] = {0, 0, 0, 0};
+};
+
+// The tables of one ctc_posteriors launch (32 * frames * align_chunks(L) bytes per utterance) when the caller names no budget:
+// about 640 utterances of 1000 frames and 100 labels, more than two workgroups for each of the device's 256 compute units,
+// and under 1.5 % of its memory
+static const int64_t POSTERIORS_TABLE_BUDGET = (int64_t)4 << 30;
+
+static int64_t posteriors_table_bytes(int64_t T, int64_t L) { return 32 * T * (int64_t)align_chunks((int32_t)L); }
+
+extern "C" {
+
+int ctcdec_posteriors_batch(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts, int32_t dtype,
+                            int32_t is_device, const int64_t* label_off, const int32_t* labels, int32_t dense, int64_t table_budget,
+                            ctcdec_posteriors** out) {
+  if (!dec || !out || n_utts < 0 || !label_off || table_budget < 0 || (n_utts > 0 && (!utt_logits || !utt_frames)))
+    return fail(CTCDEC_ERR_ARG, "bad arguments");
+  if (dtype < CTCDEC_F32 || dtype > CTCDEC_BF16) return fail(CTCDEC_ERR_ARG, "dtype must be f32, f64, f16 or bf16");
+  const int V = (int)dec->alpha.labels.size();
+  int blank = -1;
+  for (int v = 0; v < V && blank < 0; ++v)
+    if (dec->alpha.labels[(size_t)v].empty()) blank = v;
+  if (blank < 0) return fail(CTCDEC_ERR_ARG, "the alphabet has no blank label");
+  const int64_t budget = table_budget ? table_budget : POSTERIORS_TABLE_BUDGET;
+  // labels, frame counts and feasibility are ctcdec_align_batch's; the budget is this call's own
+  if (int rc = check_alignment(dec, utt_logits, utt_frames, n_utts, labels, label_off, INT64_MAX, V, blank)) return rc;
+  for (int32_t u = 0; u < n_utts; ++u) {
+    const int64_t bytes = posteriors_table_bytes(utt_frames[u], label_off[u + 1] - label_off[u]);
+    if (bytes > budget)
+      return fail(CTCDEC_ERR_LIMIT, "utterance " + std::to_string(u) + ": a table of " + std::to_string(bytes) + " bytes, above the budget of " +
+                                        std::to_string(budget) + " bytes for one launch");
+  }
+  const auto t_begin = Clock::now();
+  std::unique_ptr<ctcdec_posteriors> res(new ctcdec_posteriors());
+  const size_t n = (size_t)n_utts;
+  const int64_t NL = label_off[n];
+  std::vector<int64_t> row0(n + 1, 0);
+  for (size_t u = 0; u < n; ++u) row0[u + 1] = row0[u] + utt_frames[u];
+  const int64_t R = row0[n];
+  res->dense = dense != 0;
+  res->tok_off.assign(label_off, label_off + n + 1);
+  res->logp.assign(n, 0.0);  // (no frames and the empty target: the one empty alignment)
+  res->logp_backward.assign(n, 0.0);
+  res->occupancy.assign((size_t)NL, 0.0);
+  res->centre.assign((size_t)NL, 0.0);
+  res->gamma_off.assign(n + 1, 0);
+  res->gamma_stride.assign(n, 0);
+  for (size_t u = 0; u < n; ++u) {
+    res->gamma_stride[u] = 4 * align_chunks((int32_t)(label_off[u + 1] - label_off[u]));
+    res->gamma_off[u + 1] = res->gamma_off[u] + (dense ? (int64_t)utt_frames[u] * res->gamma_stride[u] : 0);
+  }
+  if (dense) res->gamma.resize((size_t)res->gamma_off[n]);
+  if (R > 0) {
+    std::string err;
+    std::lock_guard<std::mutex> device_lock(g_device_mu);
+    if (be::bind_thread(&err)) return fail(CTCDEC_ERR_DEVICE, err);
+    AlignFront fr;
+    if (int rc = align_front(dec, utt_logits, utt_frames, n_utts, dtype, is_device, V, row0, fr)) return rc;
+    res->ms[0] = fr.sniff_ms;
+    const size_t nl1 = (size_t)std::max<int64_t>(NL, 1);
+    if (dec->w_alab.ensure(nl1 * 4, &err) || dec->w_pocc.ensure(nl1 * 16, &err) || dec->w_ascore.ensure(n * 16, &err))
+      return fail(CTCDEC_ERR_DEVICE, err);
+    if ((NL && be::h2d(dec->w_alab.p, labels, (size_t)NL * 4, &err)) || be::zero(dec->w_pocc.p, nl1 * 16, &err) ||
+        be::zero(dec->w_ascore.p, n * 16, &err))
+      return fail(CTCDEC_ERR_DEVICE, err);
+    // launches: utterances in input order until their tables fill the budget (ctcdec_align_batch's rule); inside a launch the
+    // short targets (256 threads) before the long ones (1024), longest utterance first in each
+    std::vector<std::vector<int32_t>> groups;
+    int64_t used = 0, most = 0;
+    for (int32_t u = 0; u < n_utts; ++u) {
+      if (utt_frames[u] == 0) continue;
+      const int64_t bytes = posteriors_table_bytes(utt_frames[u], label_off[u + 1] - label_off[u]);
+      if (groups.empty() || used + bytes > budget) {
+        groups.emplace_back();
+        used = 0;
+      }
+      groups.back().push_back(u);
+      used += bytes;
+      most = std::max(most, used);
+    }
+    if (dec->w_ptab.ensure((size_t)std::max<int64_t>(most, 32), &err)) return fail(CTCDEC_ERR_DEVICE, err);
+    const double clip_lo = log(1e-15);  // ln(MIN_TOKEN_CLIP_P) (constants.py:17)
+    std::vector<PostUtt> utts;
+    for (auto& g : groups) {
+      std::stable_sort(g.begin(), g.end(), [&](int32_t a, int32_t b) {
+        const bool la = align_chunks((int32_t)(label_off[a + 1] - label_off[a])) > ALIGN_THREADS;
+        const bool lb = align_chunks((int32_t)(label_off[b + 1] - label_off[b])) > ALIGN_THREADS;
+        return la != lb ? lb : utt_frames[a] > utt_frames[b];
+      });
+      utts.clear();
+      std::vector<int64_t> tab_off;
+      int64_t off = 0;
+      int32_t max_chunks[2] = {1, 1}, count[2] = {0, 0};
+      for (int32_t u : g) {
+        const int32_t L = (int32_t)(label_off[u + 1] - label_off[u]);
+        PostUtt a;
+        a.x = fr.ptrs[(size_t)u];
+        a.lse = fr.lse + row0[(size_t)u];
+        a.lab = (const int32_t*)dec->w_alab.p + label_off[u];
+        a.table = (double*)dec->w_ptab.p + off;
+        a.logp = (double*)dec->w_ascore.p + 2 * (size_t)u;
+        a.occ = (double*)dec->w_pocc.p + label_off[u];
+        a.centre = (double*)dec->w_pocc.p + NL + label_off[u];
+        a.T = utt_frames[u];
+        a.L = L;
+        a.is_prob = fr.is_prob[(size_t)u] ? 1 : 0;
+        a.pad = 0;
+        utts.push_back(a);
+        tab_off.push_back(off);
+        off += posteriors_table_bytes(utt_frames[u], L) / 8;
+        const int w = align_chunks(L) > ALIGN_THREADS ? 1 : 0;
+        max_chunks[w] = std::max(max_chunks[w], align_chunks(L));
+        ++count[w];
+      }
+#ifdef CTC_SIM  // (the kernel's body: a single thread owns every group)
+      std::vector<double> col((size_t)4 * (size_t)std::max(max_chunks[0], max_chunks[1]) + 2);
+      AlignSeqCtx cx;
+      for (const PostUtt& a : utts) {
+        if (dtype == 0) ctc_posteriors_utt<0>(cx, a, V, blank, clip_lo, dense, col.data());
+        else if (dtype == 1) ctc_posteriors_utt<1>(cx, a, V, blank, clip_lo, dense, col.data());
+        else if (dtype == 2) ctc_posteriors_utt<2>(cx, a, V, blank, clip_lo, dense, col.data());
+        else ctc_posteriors_utt<3>(cx, a, V, blank, clip_lo, dense, col.data());
+      }
+      for (int w = 0; w < 2; ++w) res->launches += count[w] ? 1 : 0;
+#else
+      if (upload(dec->w_putts, utts, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+      for (int w = 0; w < 2; ++w) {
+        if (!count[w]) continue;
+        be::PosteriorsArgs pa;
+        pa.utts = (const PostUtt*)dec->w_putts.p + (w ? count[0] : 0);
+        pa.n_utts = count[w];
+        pa.n_labels = V;
+        pa.dtype = dtype;
+        pa.blank = blank;
+        pa.max_chunks = max_chunks[w];
+        pa.dense = dense ? 1 : 0;
+        pa.clip_lo = clip_lo;
+        if (be::launch_ctc_posteriors(pa, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+        ++res->launches;
+      }
+#endif
+      res->launched[0] += count[0];
+      res->launched[1] += count[1];
+      // a dense result leaves with its launch: the next one takes the tables over
+      for (size_t j = 0; dense && j < g.size(); ++j) {
+        const size_t u = (size_t)g[j];
+        const size_t cnt = (size_t)(res->gamma_off[u + 1] - res->gamma_off[u]);
+        if (cnt && be::d2h(res->gamma.data() + res->gamma_off[u], (const double*)dec->w_ptab.p + tab_off[j], cnt * 8, &err))
+          return fail(CTCDEC_ERR_DEVICE, err);
+      }
+    }
+    std::vector<double> pair(2 * n);
+    if (be::d2h(pair.data(), dec->w_ascore.p, n * 16, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+    for (size_t u = 0; u < n; ++u)
+      if (utt_frames[u] > 0) res->logp[u] = pair[2 * u], res->logp_backward[u] = pair[2 * u + 1];
+    if (NL && (be::d2h(res->occupancy.data(), dec->w_pocc.p, (size_t)NL * 8, &err) ||
+               be::d2h(res->centre.data(), (const double*)dec->w_pocc.p + NL, (size_t)NL * 8, &err)))
+      return fail(CTCDEC_ERR_DEVICE, err);
+#ifndef CTC_SIM
+    double vit_ms = 0;
+    be::align_timing(&res->ms[1], &vit_ms);
+    res->ms[2] = be::posteriors_timing();
+#endif
+  }
+  res->ms[3] = ms(t_begin, Clock::now());
+  *out = res.release();
+  return CTCDEC_OK;
+}
+
+int ctcdec_posteriors_scores(const ctcdec_posteriors* p, const double** logp_out, const double** logp_backward_out, int64_t* n_utts_out) {
+  if (!p || !logp_out || !logp_backward_out || !n_utts_out) return fail(CTCDEC_ERR_ARG, "no posteriors");
+  *logp_out = p->logp.data();
+  *logp_backward_out = p->logp_backward.data();
+  *n_utts_out = (int64_t)p->logp.size();
+  return CTCDEC_OK;
+}
+
+int ctcdec_posteriors_tokens(const ctcdec_posteriors* p, const int64_t** tok_off_out, const double** occupancy_out, const double** centre_out,
+                             int64_t* n_tokens_out) {
+  if (!p || !tok_off_out || !occupancy_out || !centre_out || !n_tokens_out) return fail(CTCDEC_ERR_ARG, "no posteriors");
+  *tok_off_out = p->tok_off.data();
+  *occupancy_out = p->occupancy.data();
+  *centre_out = p->centre.data();
+  *n_tokens_out = (int64_t)p->occupancy.size();
+  return CTCDEC_OK;
+}
+
+int ctcdec_posteriors_gamma(const ctcdec_posteriors* p, const int64_t** gamma_off_out, const int32_t** row_stride_out, const double** gamma_out) {
+  if (!p || !gamma_off_out || !row_stride_out || !gamma_out) return fail(CTCDEC_ERR_ARG, "no posteriors");
+  *gamma_off_out = p->gamma_off.data();
+  *row_stride_out = p->gamma_stride.data();
+  *gamma_out = p->dense ? p->gamma.data() : nullptr;
+  return CTCDEC_OK;
+}
+
+int ctcdec_posteriors_timing(const ctcdec_posteriors* p, double* ms4, int32_t* launches_out, int64_t* launched2) {
+  if (!p || !ms4) return fail(CTCDEC_ERR_ARG, "no posteriors");
+  for (int k = 0; k < 4; ++k) ms4[k] = p->ms[k];
+  if (launches_out) *launches_out = p->launches;
+  if (launched2) launched2[0] = p->launched[0], launched2[1] = p->launched[1];
+  return CTCDEC_OK;
+}
+
+void ctcdec_posteriors_free(ctcdec_posteriors* p) { delete p; }
 
 // a texts-only result (params.texts_only) as ordinary beams, for the accessors that want them
 static void materialise(const ctcdec_result* cr) {

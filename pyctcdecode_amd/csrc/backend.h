@@ -255,11 +255,25 @@ struct ForwardArgs {
   double clip_lo;      // ln(MIN_TOKEN_CLIP_P)
 };
 int launch_ctc_forward(const ForwardArgs& a, int wave, std::string* err);
-// kernel times (HIP events) of the launch_row_lse / launch_ctc_viterbi / launch_ctc_forward calls since the last reset; waits
-// for the kernels
+// ctc_posteriors: one workgroup per entry of `utts`, all of them validated by the host (PostUtt); 256 threads when every
+// utterance of the launch has at most 256 groups of states, else 1024
+struct PosteriorsArgs {
+  const PostUtt* utts;  // [n_utts] (device)
+  int32_t n_utts;
+  int32_t n_labels;
+  int32_t dtype;
+  int32_t blank;
+  int32_t max_chunks;  // the largest align_chunks(L) of the launch: sizes the columns in LDS
+  int32_t dense;       // 1: the tables are left holding gamma (0.0 outside the window); 0: only the scores and the token sums
+  double clip_lo;      // ln(MIN_TOKEN_CLIP_P)
+};
+int launch_ctc_posteriors(const PosteriorsArgs& a, std::string* err);
+// kernel times (HIP events) of the launch_row_lse / launch_ctc_viterbi / launch_ctc_forward / launch_ctc_posteriors calls since
+// the last reset; waits for the kernels
 void align_timing_reset();
 void align_timing(double* row_lse_ms, double* viterbi_ms);
 double forward_timing();
+double posteriors_timing();
 
 // stage timing (ms) of the last launch_prune / launch_beam pair, measured on the decode stream
 void last_timing(double* prune_ms, double* beam_ms);

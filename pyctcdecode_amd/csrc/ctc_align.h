@@ -1,8 +1,9 @@
 // ctc_align.h -- forced alignment of a known label sequence to an utterance's frames ("Forced alignment"): the
 // fp64 log-sum-exp of a frame row and the Viterbi recursion over the blank / label / blank / ... states, with its back-trace
 // and the confidence fold over the path; and the likelihood of a label sequence ("Transcript likelihood"): the
-// forward recursion over the same states, the sum over all alignments where the Viterbi takes the best one. One body each
-// for the HIP kernels (ctc_align_hip.hip: row_lse, ctc_viterbi, ctc_forward, ctc_forward_wave) and for the CPU simulator
+// forward recursion over the same states, the sum over all alignments where the Viterbi takes the best one; and the frame
+// posteriors of a label sequence ("Frame posteriors"): the forward-backward over the same states. One body each
+// for the HIP kernels (ctc_align_hip.hip: row_lse, ctc_viterbi, ctc_forward, ctc_forward_wave, ctc_posteriors) and for the CPU simulator
 // build, whose "device" memory is host memory (api.cpp under CTC_SIM runs them with a one-thread context).
 #pragma once
 #include <math.h>
@@ -460,6 +461,270 @@ CTC_HD void ctc_forward_wave_hyp(Ctx& cx, const ForwardHyp& hyp, int V, int blan
     const double last = jf == 2 ? p[2] : p[0];
     const double before = jf == 2 ? p[1] : (cf > 0 ? below : NEG);
     *out = align_lse2(last, before);
+  }
+}
+
+// ---- ctc_posteriors ----------------------------------------------------------------------------------------------------------
+// The frame posteriors of a label sequence ("Frame posteriors"): the CTC forward-backward over the states and the
+// window of ctc_forward,
+//   gamma[t, s] = exp(a_t[s] + b_t[s] - logp),
+//   a: ctc_forward's recursion (it includes frame t's emission), logp: ctc_forward's result, bit for bit;
+//   b_{T-1}[S-1] = b_{T-1}[S-2] = 0,
+//   b_t[s] = lse3(b_{t+1}[s] + e(t+1, s), b_{t+1}[s+1] + e(t+1, s+1), skip(s+2) ? b_{t+1}[s+2] + e(t+1, s+2) : -inf)
+// (b excludes frame t's emission), and exactly 0.0 for a state outside the window S - 2 - 2 (T - 1 - t) <= s <= 2 t + 1.
+// One utterance of a launch. The host validates every field before a launch as for AlignUtt (T >= L + repeats >= 1).
+struct PostUtt {
+  const void* x;       // [T, V] logits or probabilities, of the launch's dtype
+  const double* lse;   // [T] log-sum-exp of each row (not read when is_prob)
+  const int32_t* lab;  // [L] target labels
+  double* table;       // [T][4 * align_chunks(L)], 16-byte aligned: a of the forward pass, overwritten by gamma when dense
+  double* logp;        // [2] out: the forward score, and the same quantity read off frame 0 of the backward pass
+  double* occ;         // [L] out: sum over t of gamma[t, 2k + 1]
+  double* centre;      // [L] out: sum over t of t * gamma[t, 2k + 1], over occ[k]
+  int32_t T, L, is_prob, pad;
+};
+
+// a group's four states as they lie in the table: one 32-byte slot, moved as two 16-byte halves that stay in registers
+typedef double PostPair __attribute__((vector_size(16)));
+CTC_HD void post_store(double* slot, double v0, double v1, double v2, double v3) {
+  ((PostPair*)slot)[0] = PostPair{v0, v1};
+  ((PostPair*)slot)[1] = PostPair{v2, v3};
+}
+CTC_HD size_t post_slot(int t, int nch, int c) { return ((size_t)t * (size_t)nch + (size_t)c) * 4; }
+
+// One frame of one group of the backward pass, in place. In: q[0..3] = b + e of the group's states at the frame after, up0 /
+// up1 the same of the first blank and the first label of the group above (-inf where there is none), skip_up: that label
+// differs from this group's second. Out: q[0..3] = b of this frame. A state the target does not have stays -inf.
+CTC_HD void backward_step(const ForwardGroup& g, bool skip_up, double up0, double up1, double* q) {
+  const double NEG = align_neg_inf();
+  const double q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
+  q[0] = align_lse3(q0, q1, NEG);
+  q[1] = g.l0 >= 0 ? align_lse3(q1, q2, g.skip1 ? q3 : NEG) : NEG;
+  q[2] = g.blank2 ? align_lse3(q2, q3, NEG) : NEG;
+  q[3] = g.l1 >= 0 ? align_lse3(q3, up0, skip_up ? up1 : NEG) : NEG;
+}
+
+// ctc_posteriors: the threads of cx (tid, nt, sync(); Ctx::GROUPS * nt >= align_chunks(L)) share one utterance of a matrix of
+// dtype DT; thread tid owns the groups tid, tid + nt, ... for the whole call. `col`: 4 * align_chunks(L) + 2 doubles.
+// Forward: ctc_forward_hyp's loop, operand for operand, which also stores the four a of every in-window group of every frame
+// into the table. Backward, t = T - 1 .. 0: a group's b + e stay in registers; the first two go through two columns of `col`
+// that swap roles every frame to the thread that owns the group below (one barrier per frame). The a row and the entries of
+// frame t - 1 depend on nothing the recursion computes: they are requested one frame ahead, at slots that are always inside
+// the window, and kept as loaded. gamma overwrites a in its own slot, by the thread that wrote it; with `dense` every
+// out-of-window state of every frame (the padding of the last group included) is written as 0.0 -- the table comes from a
+// workspace that holds stale data, so the forward pass writes and the backward pass reads in-window slots only. A thread sums
+// gamma and t * gamma of its two labels in registers, in the order of the frames, and writes them once after frame 0.
+template <int DT, class Ctx>
+CTC_HD void ctc_posteriors_utt(Ctx& cx, const PostUtt& utt, int V, int blank, double clip_lo, int dense, double* col) {
+  typedef typename AlignRaw<DT>::type Raw;
+  constexpr int G = Ctx::GROUPS;
+  const void* const x = utt.x;  // (the record, once: the loops below read none of it again)
+  const double* const lse = utt.lse;
+  const int32_t* const lab = utt.lab;
+  double* const table = utt.table;
+  double* const out = utt.logp;
+  const int T = utt.T, L = utt.L;
+  const bool is_prob = utt.is_prob != 0;
+  if (T <= 0) return;
+  const int S = 2 * L + 1, nch = align_chunks(L);
+  const double NEG = align_neg_inf();
+  ForwardGroup g[G];
+  bool skip_up[G];   // the first label of the group above differs from this group's second
+  int i0[G], i1[G];  // the columns a group's two labels read (the blank's where the target ends before them)
+  double p[G][4];    // the forward pass' states
+  Raw v0[G], v1[G];  // the entries of the frame in hand at those columns, as loaded
+  CTC_UNROLL
+  for (int k = 0; k < G; ++k) {
+    const int c = cx.tid + k * cx.nt;
+    p[k][0] = p[k][1] = p[k][2] = p[k][3] = NEG;
+    if (c < nch) g[k] = forward_group(lab, L, c);
+    else g[k] = ForwardGroup{-1, -1, false, false, false};
+    skip_up[k] = g[k].l1 >= 0 && 2 * c + 2 < L && lab[2 * c + 2] != g[k].l1;
+    i0[k] = g[k].l0 >= 0 ? g[k].l0 : blank;
+    i1[k] = g[k].l1 >= 0 ? g[k].l1 : blank;
+  }
+  const int per_thread_zero = g[0].l0 == -2 ? 1 : 0;  // (ctc_forward_hyp: a row's log-sum-exp by a vector load)
+  const double* const lse_v = lse + per_thread_zero;
+  for (int i = cx.tid; i < 2 * nch; i += cx.nt) col[i] = NEG;
+  if (cx.tid == 0) {
+    const double lse0 = is_prob ? 0.0 : lse[0];
+    p[0][0] = align_emit(x, DT, (size_t)blank, lse0, is_prob, clip_lo);
+    if (L > 0) p[0][1] = align_emit(x, DT, (size_t)lab[0], lse0, is_prob, clip_lo);
+    post_store(table + post_slot(0, nch, 0), p[0][0], p[0][1], p[0][2], p[0][3]);  // (frame 0's window: group 0)
+  }
+  cx.sync();
+  int clo = 0, chi = -1, clo_prev = 0;
+  if (T > 1) forward_window(1, T, S, &clo, &chi);
+  const size_t row1 = T > 1 ? (size_t)V : 0;
+  Raw vb = align_load_raw<DT>(x, row1 + (size_t)blank);
+  double lse_t = lse_v[T > 1 ? 1 : 0];
+  CTC_UNROLL
+  for (int k = 0; k < G; ++k) {
+    v0[k] = align_load_raw<DT>(x, row1 + (size_t)i0[k]);
+    v1[k] = align_load_raw<DT>(x, row1 + (size_t)i1[k]);
+  }
+  for (int t = 1; t < T; ++t) {
+    const double* prev = col + ((t - 1) & 1) * nch;
+    double* cur = col + (t & 1) * nch;
+    double pm1[G];
+    CTC_UNROLL
+    for (int k = 0; k < G; ++k) {
+      const int c = cx.tid + k * cx.nt;
+      pm1[k] = c >= clo && c <= chi && c > 0 && c - 1 >= clo_prev ? prev[c - 1] : NEG;
+    }
+    const int tn = t + 1 < T ? t + 1 : t;
+    int nlo = 0, nhi = -1;
+    if (t + 1 < T) forward_window(tn, T, S, &nlo, &nhi);
+    const size_t row = (size_t)tn * (size_t)V;
+    const Raw nvb = align_load_raw<DT>(x, row + (size_t)blank);
+    const double nlse = lse_v[tn];
+    Raw n0[G], n1[G];
+    CTC_UNROLL
+    for (int k = 0; k < G; ++k) {
+      n0[k] = align_load_raw<DT>(x, row + (size_t)i0[k]);
+      n1[k] = align_load_raw<DT>(x, row + (size_t)i1[k]);
+    }
+    const double lse_use = is_prob ? 0.0 : lse_t;
+    const double e_blank = align_emit_of_value(align_widen<DT>(vb), lse_use, is_prob, clip_lo);
+    CTC_UNROLL
+    for (int k = 0; k < G; ++k) {
+      const int c = cx.tid + k * cx.nt;
+      if (c < clo || c > chi) continue;
+      const double e0 = align_emit_of_value(align_widen<DT>(v0[k]), lse_use, is_prob, clip_lo);
+      const double e1 = align_emit_of_value(align_widen<DT>(v1[k]), lse_use, is_prob, clip_lo);
+      forward_step(g[k], pm1[k], e_blank, e0, e1, p[k]);
+      cur[c] = p[k][3];
+      post_store(table + post_slot(t, nch, c), p[k][0], p[k][1], p[k][2], p[k][3]);
+    }
+    clo_prev = clo;
+    clo = nlo, chi = nhi, vb = nvb, lse_t = nlse;
+    CTC_UNROLL
+    for (int k = 0; k < G; ++k) v0[k] = n0[k], v1[k] = n1[k];
+    cx.sync();  // the one barrier of a frame: the columns swap roles
+  }
+  // logp, formed as ctc_forward_hyp forms it, and handed to every thread
+  const int cf = (S - 1) >> 2, jf = (S - 1) & 3;
+  const double* fin = col + ((T - 1) & 1) * nch;
+  double* const share = col + 4 * nch;
+  CTC_UNROLL
+  for (int k = 0; k < G; ++k) {
+    if (cx.tid + k * cx.nt != cf) continue;
+    const double last = jf == 2 ? p[k][2] : p[k][0];
+    const double before = jf == 2 ? p[k][1] : (cf > 0 ? fin[cf - 1] : NEG);
+    const double sum = align_lse2(last, before);
+    out[0] = sum;
+    share[0] = sum;
+  }
+  cx.sync();
+  const double logp = share[0];
+
+  // ---- backward ----
+  double bq[G][4];  // the backward pass' states, with their frame's emissions: b + e
+  double occ0[G], occ1[G], cen0[G], cen1[G];
+  PostPair a01[G], a23[G];  // a of the frame in hand, as loaded
+  CTC_UNROLL
+  for (int k = 0; k < G; ++k) {
+    bq[k][0] = bq[k][1] = bq[k][2] = bq[k][3] = NEG;
+    occ0[k] = occ1[k] = cen0[k] = cen1[k] = 0.0;
+  }
+  // frame T - 1's entries and a (what a thread reads here it wrote itself)
+  forward_window(T - 1, T, S, &clo, &chi);
+  {
+    const size_t row = (size_t)(T - 1) * (size_t)V;
+    vb = align_load_raw<DT>(x, row + (size_t)blank);
+    lse_t = lse_v[T - 1];
+    CTC_UNROLL
+    for (int k = 0; k < G; ++k) {
+      const int c = cx.tid + k * cx.nt;
+      const int cc = c < clo ? clo : (c > chi ? chi : c);
+      v0[k] = align_load_raw<DT>(x, row + (size_t)i0[k]);
+      v1[k] = align_load_raw<DT>(x, row + (size_t)i1[k]);
+      a01[k] = ((const PostPair*)(table + post_slot(T - 1, nch, cc)))[0];
+      a23[k] = ((const PostPair*)(table + post_slot(T - 1, nch, cc)))[1];
+    }
+  }
+  int chi_next = -1;  // the last group of the window of the frame after
+  for (int t = T - 1; t >= 0; --t) {
+    const double* prev = col + ((t + 1) & 1) * 2 * nch;
+    double* cur = col + (t & 1) * 2 * nch;
+    // the group above first: beyond the window of the frame after there is nothing a state of this frame's window needs
+    double up0[G], up1[G];
+    CTC_UNROLL
+    for (int k = 0; k < G; ++k) {
+      const int c = cx.tid + k * cx.nt;
+      const bool have = c >= clo && c <= chi && c + 1 <= chi_next;
+      up0[k] = have ? prev[2 * (c + 1)] : NEG;
+      up1[k] = have ? prev[2 * (c + 1) + 1] : NEG;
+    }
+    // then ask for frame t - 1 (before frame 0: frame 0 again)
+    const int tn = t > 0 ? t - 1 : 0;
+    int nlo, nhi;
+    forward_window(tn, T, S, &nlo, &nhi);
+    const size_t row = (size_t)tn * (size_t)V;
+    const Raw nvb = align_load_raw<DT>(x, row + (size_t)blank);
+    const double nlse = lse_v[tn];
+    Raw n0[G], n1[G];
+    PostPair na01[G], na23[G];
+    CTC_UNROLL
+    for (int k = 0; k < G; ++k) {
+      const int c = cx.tid + k * cx.nt;
+      const int cc = c < nlo ? nlo : (c > nhi ? nhi : c);
+      n0[k] = align_load_raw<DT>(x, row + (size_t)i0[k]);
+      n1[k] = align_load_raw<DT>(x, row + (size_t)i1[k]);
+      na01[k] = ((const PostPair*)(table + post_slot(tn, nch, cc)))[0];
+      na23[k] = ((const PostPair*)(table + post_slot(tn, nch, cc)))[1];
+    }
+    const double lse_use = is_prob ? 0.0 : lse_t;
+    const double e_blank = align_emit_of_value(align_widen<DT>(vb), lse_use, is_prob, clip_lo);
+    const int lo = S - 2 - 2 * (T - 1 - t), hi = 2 * t + 1 < S - 1 ? 2 * t + 1 : S - 1;
+    const double ft = (double)t;
+    CTC_UNROLL
+    for (int k = 0; k < G; ++k) {
+      const int c = cx.tid + k * cx.nt;
+      if (c < clo || c > chi) {
+        if (dense && c < nch) post_store(table + post_slot(t, nch, c), 0.0, 0.0, 0.0, 0.0);
+        continue;
+      }
+      double* q = bq[k];
+      const int s0 = 4 * c;
+      if (t == T - 1) {
+        q[0] = (s0 == S - 1 || s0 == S - 2) ? 0.0 : NEG;
+        q[1] = (s0 + 1 == S - 1 || s0 + 1 == S - 2) ? 0.0 : NEG;
+        q[2] = (s0 + 2 == S - 1 || s0 + 2 == S - 2) ? 0.0 : NEG;
+        q[3] = (s0 + 3 == S - 1 || s0 + 3 == S - 2) ? 0.0 : NEG;
+      } else {
+        backward_step(g[k], skip_up[k], up0[k], up1[k], q);
+      }
+      const double gm0 = (s0 < lo || s0 > hi) ? 0.0 : exp(a01[k][0] + q[0] - logp);
+      const double gm1 = (s0 + 1 < lo || s0 + 1 > hi) ? 0.0 : exp(a01[k][1] + q[1] - logp);
+      const double gm2 = (s0 + 2 < lo || s0 + 2 > hi) ? 0.0 : exp(a23[k][0] + q[2] - logp);
+      const double gm3 = (s0 + 3 < lo || s0 + 3 > hi) ? 0.0 : exp(a23[k][1] + q[3] - logp);
+      if (dense) post_store(table + post_slot(t, nch, c), gm0, gm1, gm2, gm3);
+      occ0[k] += gm1;
+      cen0[k] += ft * gm1;
+      occ1[k] += gm3;
+      cen1[k] += ft * gm3;
+      const double e0 = align_emit_of_value(align_widen<DT>(v0[k]), lse_use, is_prob, clip_lo);
+      const double e1 = align_emit_of_value(align_widen<DT>(v1[k]), lse_use, is_prob, clip_lo);
+      q[0] += e_blank;
+      q[1] += e0;
+      q[2] += e_blank;
+      q[3] += e1;
+      cur[2 * c] = q[0];
+      cur[2 * c + 1] = q[1];
+    }
+    chi_next = chi;
+    clo = nlo, chi = nhi, vb = nvb, lse_t = nlse;
+    CTC_UNROLL
+    for (int k = 0; k < G; ++k) v0[k] = n0[k], v1[k] = n1[k], a01[k] = na01[k], a23[k] = na23[k];
+    cx.sync();  // the one barrier of a frame: the columns swap roles
+  }
+  CTC_UNROLL
+  for (int k = 0; k < G; ++k) {
+    const int c = cx.tid + k * cx.nt;
+    if (c == 0) out[1] = align_lse2(bq[k][0], bq[k][1]);  // b_0 + e(0, .) of the two states a path may start in
+    if (g[k].l0 >= 0) utt.occ[2 * c] = occ0[k], utt.centre[2 * c] = cen0[k] / occ0[k];
+    if (g[k].l1 >= 0) utt.occ[2 * c + 1] = occ1[k], utt.centre[2 * c + 1] = cen1[k] / occ1[k];
   }
 }
 

@@ -1,6 +1,7 @@
 // ctc_align_hip.hip -- forced alignment and transcript likelihood on gfx950 (ctc_align.h): row_lse, the fp64 log-sum-exp of
 // every frame row; ctc_viterbi, one workgroup per utterance over the blank / label / blank / ... states; ctc_forward and
-// ctc_forward_wave, the sum over all alignments of a hypothesis, one workgroup / one wavefront each. A translation unit of its own.
+// ctc_forward_wave, the sum over all alignments of a hypothesis, one workgroup / one wavefront each; ctc_posteriors, the
+// forward-backward of an utterance's transcript, one workgroup each. A translation unit of its own.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -152,6 +153,19 @@ __global__ __launch_bounds__(ALIGN_THREADS) void ctc_forward_wave(ForwardArgs a)
   ctc_forward_wave_hyp<DT>(cx, a.hyps[i], a.n_labels, a.blank, a.clip_lo);
 }
 
+// ---------------------------------------------------------------------------------------------
+// ctc_posteriors: one workgroup per utterance, one group of four states per thread for both passes (256 threads up to 511
+// labels, 1024 above); the forward pass leaves its states in the utterance's table, the backward pass turns them into
+// posteriors in place (ctc_align.h)
+// ---------------------------------------------------------------------------------------------
+// (four waves per SIMD: what 1024 threads need to be resident at all, and the 256-thread kernel is held to the same 128 VGPRs)
+template <int NT, int DT>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4))) void ctc_posteriors(PosteriorsArgs a) {
+  extern __shared__ double posteriors_cols[];
+  ForwardGpuCtx cx{(int)threadIdx.x, NT};
+  ctc_posteriors_utt<DT>(cx, a.utts[blockIdx.x], a.n_labels, a.blank, a.clip_lo, a.dense, posteriors_cols);
+}
+
 // kernel times: one pair of events per launch since the last reset
 struct EventLog {
   std::vector<hipEvent_t> ev;
@@ -174,10 +188,11 @@ struct EventLog {
     return sum;
   }
 };
-static EventLog g_lse_log, g_vit_log, g_fwd_log;
+static EventLog g_lse_log, g_vit_log, g_fwd_log, g_post_log;
 
-void align_timing_reset() { g_lse_log.used = g_vit_log.used = g_fwd_log.used = 0; }
+void align_timing_reset() { g_lse_log.used = g_vit_log.used = g_fwd_log.used = g_post_log.used = 0; }
 double forward_timing() { return g_fwd_log.total(); }
+double posteriors_timing() { return g_post_log.total(); }
 void align_timing(double* row_lse_ms, double* viterbi_ms) {
   *row_lse_ms = g_lse_log.total();
   *viterbi_ms = g_vit_log.total();
@@ -249,6 +264,31 @@ int launch_ctc_forward_on(const ForwardArgs& a, int wave, hipStream_t stream, st
   else if (a.dtype == 1) launch_forward_dt<1>(a, wave, stream);
   else if (a.dtype == 2) launch_forward_dt<2>(a, wave, stream);
   else launch_forward_dt<3>(a, wave, stream);
+  HIP_TRY_A(hipGetLastError());
+  HIP_TRY_A(hipEventRecord(e1, stream));
+  return 0;
+}
+
+template <int DT>
+static void launch_posteriors_dt(const PosteriorsArgs& a, hipStream_t stream) {
+  const size_t lds = ((size_t)4 * (size_t)a.max_chunks + 2) * sizeof(double);  // <= 32 KB + 16
+  if (a.max_chunks <= ALIGN_THREADS) hipLaunchKernelGGL((ctc_posteriors<ALIGN_THREADS, DT>), dim3((unsigned)a.n_utts), dim3(ALIGN_THREADS), lds, stream, a);
+  else hipLaunchKernelGGL((ctc_posteriors<FORWARD_THREADS_MAX, DT>), dim3((unsigned)a.n_utts), dim3(FORWARD_THREADS_MAX), lds, stream, a);
+}
+
+int launch_ctc_posteriors_on(const PosteriorsArgs& a, hipStream_t stream, std::string* err) {
+  if (a.n_utts <= 0) return 0;
+  if (a.dtype < 0 || a.dtype > 3 || a.max_chunks < 1 || a.max_chunks > align_chunks(ALIGN_MAX_LABELS)) {
+    if (err) *err = "ctc_posteriors: more states than the kernel holds";
+    return -1;
+  }
+  hipEvent_t e0, e1;
+  if (g_post_log.next(&e0, err) || g_post_log.next(&e1, err)) return -1;
+  HIP_TRY_A(hipEventRecord(e0, stream));
+  if (a.dtype == 0) launch_posteriors_dt<0>(a, stream);
+  else if (a.dtype == 1) launch_posteriors_dt<1>(a, stream);
+  else if (a.dtype == 2) launch_posteriors_dt<2>(a, stream);
+  else launch_posteriors_dt<3>(a, stream);
   HIP_TRY_A(hipGetLastError());
   HIP_TRY_A(hipEventRecord(e1, stream));
   return 0;

@@ -180,6 +180,37 @@ class ScoredText:
     total: float = 0.0
 
 
+@dataclasses.dataclass(frozen=True, eq=False)
+class TranscriptPosteriors:
+    """Where, under ALL alignments of a known transcript, each frame lies (BeamSearchDecoderCTC.posteriors /
+    posteriors_batch): the CTC forward-backward. ``text`` and ``tokens`` are ScoredText's. ``logp`` is the CTC forward score,
+    the float score / score_batch returns for the same input; ``logp_backward`` is the same quantity read off frame 0 of the
+    backward pass, a self-check. ``gamma`` (float64 ``[T, 2 L + 1]``, None with ``dense=False``) is the probability that
+    frame t is in state s of blank / label 0 / blank / ... / label L - 1 / blank: as computed, so a value may exceed 1 by
+    rounding, and exactly 0.0 for a state no alignment can be in at that frame. ``occupancy[k]`` is the expected number of
+    frames of token k (the sum over t of ``gamma[t, 2 k + 1]``) and ``centre[k]`` its expected frame; both are summed on the
+    device and have the same bits with and without ``dense``."""
+
+    text: str
+    tokens: List[int]
+    logp: float
+    logp_backward: float
+    gamma: Optional[np.ndarray]
+    occupancy: np.ndarray
+    centre: np.ndarray
+
+    @property
+    def token_post(self) -> Optional[np.ndarray]:
+        """``[T, L]``: the posterior of each token at each frame."""
+        return None if self.gamma is None else self.gamma[:, 1::2]
+
+    @property
+    def blank_post(self) -> Optional[np.ndarray]:
+        """``[T]``: the posterior of a blank, whichever one, at each frame."""
+        return None if self.gamma is None else self.gamma[:, 0::2].sum(axis=1)
+
+
+POSTERIORS_TABLE_BUDGET = 4 << 30  # bytes of tables one ctc_posteriors launch holds by default (DESIGN.md, "Frame posteriors")
 FORWARD_KERNELS = {"wave": 1, "group": 2}  # ctcdec_score_batch's `kernel` from CTCDEC_FORWARD_KERNEL (unset: the library chooses)
 CONFIDENCE_FOLDS = {"mean": 2, "min": 3, "max": 4}  # ctcdec_params.token_frames: CTCDEC_TOKEN_LOGP_MEAN / _MIN / _MAX
 
@@ -1065,6 +1096,11 @@ class BeamSearchDecoderCTC:
         # hypotheses taken by the wave kernel and by the group kernel)
         self.last_score_timing_ms = (0.0, 0.0, 0.0, 0.0)
         self.last_score_launched = (0, 0)
+        # ... and of the last posteriors / posteriors_batch call (ms likewise; kernel launches made; utterances taken by the
+        # 256-thread and by the 1024-thread kernel)
+        self.last_posteriors_timing_ms = (0.0, 0.0, 0.0, 0.0)
+        self.last_posteriors_launches = 0
+        self.last_posteriors_launched = (0, 0)
 
     def __del__(self):
         h = getattr(self, "_handle", None)
@@ -1528,6 +1564,39 @@ class BeamSearchDecoderCTC:
         close()
         return " ".join(w for w, _, _ in words), kept, words
 
+    def _one_target_each(self, what: str, logits_list: Any, texts, tokens):
+        """-> (logits_list, targets): the checks align_batch and posteriors_batch make of their arguments before anything is
+        staged -- one target per utterance, as a text (character alphabets) or as label ids."""
+        if (texts is None) == (tokens is None):
+            raise ValueError("%s: give exactly one of texts and tokens" % what)
+        if texts is not None and self._is_bpe:
+            raise ValueError("a text has many segmentations under a BPE alphabet: give the target as tokens=")
+        if getattr(logits_list, "ndim", 0) != 3:
+            logits_list = list(logits_list)
+        n = len(logits_list)
+        given = texts if texts is not None else tokens
+        if isinstance(given, str) or len(given) != n:
+            raise ValueError("%s: %d targets for %d utterances" % (what, 1 if isinstance(given, str) else len(given), n))
+        blank, n_labels = self._vocab2idx[""], len(self._labels_list)
+        targets: List[List[int]] = []
+        for u, g in enumerate(given):
+            if texts is not None:
+                if not isinstance(g, str):
+                    raise ValueError("%s: texts[%d] is not a str" % (what, u))
+                ids = self._target_of_text(g)
+            else:
+                ids = []
+                for c in g:
+                    if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 0 <= int(c) < n_labels or int(c) == blank:
+                        raise ValueError("%s: tokens[%d] holds %r: not a label id in [0, %d) other than the blank (%d)"
+                                         % (what, u, c, n_labels, blank))
+                    ids.append(int(c))
+            if len(ids) > ALIGN_MAX_LABELS:
+                raise ValueError("%s: utterance %d has %d target labels, above the limit of %d labels per utterance"
+                                 % (what, u, len(ids), ALIGN_MAX_LABELS))
+            targets.append(ids)
+        return logits_list, targets
+
     def align(self, logits: Any, text: Optional[str] = None, tokens: Optional[Sequence[int]] = None,
               confidence: Optional[str] = None) -> "AlignedText":
         """Forced alignment of one utterance: align_batch of a batch of one (a ValueError when no path exists)."""
@@ -1544,34 +1613,8 @@ class BeamSearchDecoderCTC:
         An utterance with fewer frames than target labels plus adjacent equal labels has no path: ``strict=True`` raises a
         ValueError that lists them, ``strict=False`` returns None in their place."""
         fold = _confidence_fold(confidence)
-        if (texts is None) == (tokens is None):
-            raise ValueError("align: give exactly one of texts and tokens")
-        if texts is not None and self._is_bpe:
-            raise ValueError("a text has many segmentations under a BPE alphabet: give the target as tokens=")
-        if getattr(logits_list, "ndim", 0) != 3:
-            logits_list = list(logits_list)
-        n = len(logits_list)
-        given = texts if texts is not None else tokens
-        if isinstance(given, str) or len(given) != n:
-            raise ValueError("align: %d targets for %d utterances" % (1 if isinstance(given, str) else len(given), n))
-        blank, n_labels = self._vocab2idx[""], len(self._labels_list)
-        targets: List[List[int]] = []
-        for u, g in enumerate(given):
-            if texts is not None:
-                if not isinstance(g, str):
-                    raise ValueError("align: texts[%d] is not a str" % u)
-                ids = self._target_of_text(g)
-            else:
-                ids = []
-                for c in g:
-                    if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 0 <= int(c) < n_labels or int(c) == blank:
-                        raise ValueError("align: tokens[%d] holds %r: not a label id in [0, %d) other than the blank (%d)"
-                                         % (u, c, n_labels, blank))
-                    ids.append(int(c))
-            if len(ids) > ALIGN_MAX_LABELS:
-                raise ValueError("align: utterance %d has %d target labels, above the limit of %d labels per utterance"
-                                 % (u, len(ids), ALIGN_MAX_LABELS))
-            targets.append(ids)
+        logits_list, targets = self._one_target_each("align", logits_list, texts, tokens)
+        n, n_labels = len(targets), len(self._labels_list)
         if n == 0:
             return []
         with self._call_lock:
@@ -1756,6 +1799,100 @@ class BeamSearchDecoderCTC:
                 h += 1
             out.append(res)
         return out
+
+    # -- frame posteriors (no reference analogue; DESIGN.md, "Frame posteriors") ---------------------------
+    def posteriors(self, logits: Any, text: Optional[str] = None, tokens: Optional[Sequence[int]] = None,
+                   dense: bool = True) -> "TranscriptPosteriors":
+        """The frame posteriors of one utterance's transcript: posteriors_batch of a batch of one (a ValueError when no
+        alignment exists)."""
+        self._check_logits_dimension(logits)
+        return self.posteriors_batch([logits], None if text is None else [text], tokens=None if tokens is None else [tokens],
+                                     dense=dense)[0]
+
+    def posteriors_batch(self, logits_list: Any, texts: Optional[Sequence[str]] = None,
+                         tokens: Optional[Sequence[Sequence[int]]] = None, dense: bool = True, strict: bool = True,
+                         _table_budget: int = 0) -> List[Optional["TranscriptPosteriors"]]:
+        """Under all alignments of each known transcript, where its frames lie, in one native call: per utterance the CTC
+        forward-backward for its target (row_lse + ctc_posteriors, csrc/ctc_align_hip.hip), as TranscriptPosteriors. The
+        arguments are align_batch's: ``logits_list``, ``texts`` or ``tokens`` (the only form for BPE alphabets), and
+        ``strict`` for utterances with fewer frames than target labels plus adjacent equal labels, which have no alignment.
+        ``dense=True`` returns every utterance's ``gamma`` as a host array of ``8 * T * (2 L + 1)`` bytes, copied launch by
+        launch -- 26 GB for 4096 utterances of 1000 frames and 100 labels: a large batch wants ``dense=False``, which returns
+        the scores and the per-token ``occupancy`` / ``centre`` alone, with the same bits."""
+        logits_list, targets = self._one_target_each("posteriors", logits_list, texts, tokens)
+        n, n_labels = len(targets), len(self._labels_list)
+        self.last_posteriors_timing_ms, self.last_posteriors_launches, self.last_posteriors_launched = (0.0,) * 4, 0, (0, 0)
+        if n == 0:
+            return []
+        with self._call_lock:
+            batch = _Batch(logits_list, n_labels)
+            if batch.is_device and batch.device_index is not None and batch.device_index != self._device:
+                raise ValueError("the logits live on cuda:%d but this decoder was built for cuda:%d (one process per GPU: "
+                                 "LOCAL_RANK / CTCDEC_DEVICE pick the device)" % (batch.device_index, self._device))
+            frames = np.asarray(batch.frames, dtype=np.int32)
+            ptrs = np.asarray(batch.ptrs, dtype=np.uint64)
+            budget = int(_table_budget) or POSTERIORS_TABLE_BUDGET
+            keep, bad = [], []
+            for u, ids in enumerate(targets):
+                need = len(ids) + sum(1 for a, b in zip(ids, ids[1:]) if a == b)
+                (keep if int(frames[u]) >= need else bad).append(u)
+                table = 32 * int(frames[u]) * ((2 * len(ids) + 1 + 3) // 4)
+                if table > budget:
+                    raise ValueError("posteriors: utterance %d needs a table of %d bytes, above the memory budget of %d bytes of "
+                                     "one launch" % (u, table, budget))
+            if bad and strict:
+                raise ValueError("posteriors: no alignment for utterances %s: fewer frames than target labels plus adjacent "
+                                 "equal labels" % bad)
+            out: List[Optional[TranscriptPosteriors]] = [None] * n
+            if not keep:
+                return out
+            k_ptrs = np.ascontiguousarray(ptrs[keep])
+            k_frames = np.ascontiguousarray(frames[keep])
+            flat = np.array([c for u in keep for c in targets[u]] or [0], dtype=np.int32)
+            off = np.zeros(len(keep) + 1, dtype=np.int64)
+            off[1:] = np.cumsum([len(targets[u]) for u in keep])
+            res = C.c_void_p()
+            lib = self._lib
+            lib.check(lib.dll.ctcdec_posteriors_batch(
+                self._handle, k_ptrs.ctypes.data_as(C.POINTER(C.c_void_p)), k_frames.ctypes.data_as(C.POINTER(C.c_int32)),
+                len(keep), batch.dtype, int(batch.is_device), B.off_ptr(off), flat.ctypes.data_as(C.POINTER(C.c_int32)),
+                int(bool(dense)), int(_table_budget), C.byref(res)))
+            try:
+                pl, pb, nu = C.POINTER(C.c_double)(), C.POINTER(C.c_double)(), C.c_int64()
+                lib.check(lib.dll.ctcdec_posteriors_scores(res, C.byref(pl), C.byref(pb), C.byref(nu)))
+                to, po, pc, nt = C.POINTER(C.c_int64)(), C.POINTER(C.c_double)(), C.POINTER(C.c_double)(), C.c_int64()
+                lib.check(lib.dll.ctcdec_posteriors_tokens(res, C.byref(to), C.byref(po), C.byref(pc), C.byref(nt)))
+                go, gs, gp = C.POINTER(C.c_int64)(), C.POINTER(C.c_int32)(), C.POINTER(C.c_double)()
+                lib.check(lib.dll.ctcdec_posteriors_gamma(res, C.byref(go), C.byref(gs), C.byref(gp)))
+                if int(nu.value) != len(keep) or int(nt.value) != int(off[-1]):
+                    raise B.NativeError("the posteriors hold another number of utterances or tokens than was asked for")
+                logp = np.ctypeslib.as_array(pl, shape=(len(keep),)).tolist()
+                logp_b = np.ctypeslib.as_array(pb, shape=(len(keep),)).tolist()
+                ntok = int(nt.value)
+                occ = np.ctypeslib.as_array(po, shape=(ntok,)).copy() if ntok else np.zeros(0)
+                cen = np.ctypeslib.as_array(pc, shape=(ntok,)).copy() if ntok else np.zeros(0)
+                gammas: List[Optional[np.ndarray]] = [None] * len(keep)
+                if dense:
+                    g_off = np.ctypeslib.as_array(go, shape=(len(keep) + 1,)).tolist()
+                    stride = np.ctypeslib.as_array(gs, shape=(len(keep),)).tolist()
+                    flat_g = np.ctypeslib.as_array(gp, shape=(g_off[-1],)) if g_off[-1] else np.zeros(0)
+                    for j, u in enumerate(keep):
+                        T, S = int(frames[u]), 2 * len(targets[u]) + 1
+                        gammas[j] = flat_g[g_off[j]:g_off[j + 1]].reshape(T, stride[j])[:, :S].copy()
+                ms, launches, launched = (C.c_double * 4)(), C.c_int32(), (C.c_int64 * 2)()
+                lib.dll.ctcdec_posteriors_timing(res, ms, C.byref(launches), launched)
+                # [classification (frame-prune kernels), row_lse, ctc_posteriors (HIP events), whole native call]; kernel
+                # launches made; utterances that went to (the 256-thread kernel, the 1024-thread kernel)
+                self.last_posteriors_timing_ms = tuple(float(v) for v in ms)
+                self.last_posteriors_launches = int(launches.value)
+                self.last_posteriors_launched = (int(launched[0]), int(launched[1]))
+            finally:
+                lib.dll.ctcdec_posteriors_free(res)
+            for j, u in enumerate(keep):
+                ids, o = targets[u], int(off[j])
+                out[u] = TranscriptPosteriors(self._words_of_target(ids)[0], list(ids), float(logp[j]), float(logp_b[j]), gammas[j],
+                                              occ[o:o + len(ids)].copy(), cen[o:o + len(ids)].copy())
+            return out
 
     # -- serialisation (decoder.py:947-1043): alphabet.json + language_model/ --------------------------
     _ALPHABET_SERIALIZED_FILENAME = "alphabet.json"

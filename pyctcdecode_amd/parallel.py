@@ -201,6 +201,11 @@ def score_batch_sharded(decoder, logits_list, texts=None, group=None, **kwargs):
     raise NotImplementedError("score_batch is not gathered over ranks: score each rank's slice with decoder.score_batch itself")
 
 
+def posteriors_batch_sharded(decoder, logits_list, texts=None, group=None, **kwargs):
+    """Frame posteriors are not sharded over ranks: each rank calls decoder.posteriors_batch on its own slice."""
+    raise NotImplementedError("posteriors_batch is not gathered over ranks: call decoder.posteriors_batch on each rank's slice itself")
+
+
 def _device_worker(conn, device: int, decoder_dir: str, library: Optional[str]) -> None:
     """One worker process = one GPU (the native library binds one device per process): loads the saved decoder on its device and
     serves (method, logits, kwargs) requests until it is told to stop."""
@@ -329,6 +334,12 @@ class DevicePool:
         raise NotImplementedError("DevicePool does not shard score_batch: call decoder.score_batch on the process's own device")
 
     score = score_batch
+
+    def posteriors_batch(self, logits_list, texts=None, **kwargs):
+        """Frame posteriors run on the calling process's own device: a pool does not shard them."""
+        raise NotImplementedError("DevicePool does not shard posteriors_batch: call decoder.posteriors_batch on the process's own device")
+
+    posteriors = posteriors_batch
 
     def decode_batch(self, logits_list, **kwargs) -> List[str]:
         if kwargs.get("token_frames") or kwargs.get("confidence") is not None:  # (texts, TokenFrames) per slice -> one of each, offsets rebased

@@ -1,10 +1,12 @@
-"""Times forced alignment (align_batch: row_lse + ctc_viterbi, csrc/ctc_align_hip.hip) and transcript likelihood (score_batch:
-row_lse + ctc_forward / ctc_forward_wave) at the bench shape -- 4096 utterances of 1000 frames x 1024 labels, float32, each
+"""Times forced alignment (align_batch: row_lse + ctc_viterbi, csrc/ctc_align_hip.hip), transcript likelihood (score_batch:
+row_lse + ctc_forward / ctc_forward_wave) and frame posteriors (posteriors_batch with dense=False: row_lse + ctc_posteriors,
+next to ctc_forward on the same batch) at the bench shape -- 4096 utterances of 1000 frames x 1024 labels, float32, each
 aligned to / scored with its own decoded tokens, and scored with 8 hypotheses (its tokens plus seven copies with one label
 substituted), each forward kernel forced in turn -- and at 64 utterances, with the plain decode_batch step of the same process
 for scale; then a sweep of target lengths on 256 utterances of random logits, which is what the wave / group threshold of
-ctcdec_score_batch rests on. Kernel times are HIP events on the decode stream (ctcdec_alignment_timing, ctcdec_score_batch).
-  python tools/align_bench.py [--out profiles/align_bench.txt] [--steps 3]
+ctcdec_score_batch rests on. Kernel times are HIP events on the decode stream (ctcdec_alignment_timing, ctcdec_score_batch,
+ctcdec_posteriors_timing).
+  python tools/align_bench.py [--out profiles/align_bench.txt] [--steps 3] [--legs align,score,posteriors,sweep]
 The 4096 utterances are 256 distinct ones repeated: no kernel's time depends on the rows being distinct."""
 import argparse
 import os
@@ -74,6 +76,32 @@ def score_lines(dec, dev, targets, steps, vit_ms):
     return lines
 
 
+def time_posteriors(dec, dev, targets, steps):
+    """ctc_posteriors (dense=False) and the group ctc_forward on the same batch, alternating after one warm-up each:
+    medians of (posteriors kernel ms, forward kernel ms, posteriors native call ms, posteriors Python call ms), launches."""
+    os.environ["CTCDEC_FORWARD_KERNEL"] = "group"
+    hyps = [[t] for t in targets]
+    post, fwd, native, wall = [], [], [], []
+    for _ in range(steps + 1):
+        dec.score_batch(dev, tokens=hyps)
+        fwd.append(dec.last_score_timing_ms[2])
+        t0 = time.perf_counter()
+        out = dec.posteriors_batch(dev, tokens=targets, dense=False)
+        wall.append((time.perf_counter() - t0) * 1e3)
+        post.append(dec.last_posteriors_timing_ms[2]), native.append(dec.last_posteriors_timing_ms[3])
+    os.environ.pop("CTCDEC_FORWARD_KERNEL", None)
+    assert all(abs(g.logp - g.logp_backward) <= 1e-9 for g in out)
+    return med(post), med(fwd), med(native), med(wall), dec.last_posteriors_launches
+
+
+def posteriors_lines(dec, dev, targets, steps):
+    post, fwd, native, wall, launches = time_posteriors(dec, dev, targets, steps)
+    table = sum(32 * T * ((2 * len(t) + 1 + 3) // 4) for t in targets)
+    return ["  posteriors_batch dense=False  ctc_posteriors %9.3f ms in %d launch(es)  (%.2f GB of tables written and read back)  "
+            "native call %9.3f ms  Python call %9.3f ms" % (post, launches, table / 1e9, native, wall),
+            "    ctc_posteriors / ctc_forward (%.3f ms, one group-kernel hypothesis each) at this batch: %.2f" % (fwd, post / fwd)]
+
+
 def time_forward(dec, dev, hyps, kernels, steps):
     """The forward kernels' time (HIP events) under each forced kernel: one warm-up call each, then `steps` rounds that
     alternate between them (clocks as they come: neither kernel gets the warmer half of the run). -> {kernel: median ms}"""
@@ -97,7 +125,8 @@ def sweep_lines(dec, steps):
     lines = ["sweep of target lengths, 256 utterances x %d labels float32 (random logits), 1 and 8 hypotheses per utterance; "
              "%d alternating steps after one warm-up each, medians:" % (V, steps),
              "  %6s %6s | %12s %12s %10s | %12s %12s %10s | %12s %8s" % (
-                 "labels", "frames", "wave x1", "group x1", "wave/group", "wave x8", "group x8", "wave/group", "ctc_viterbi", "fwd/vit")]
+                 "labels", "frames", "wave x1", "group x1", "wave/group", "wave x8", "group x8", "wave/group", "ctc_viterbi", "fwd/vit")
+             + " | %14s %8s" % ("ctc_posteriors", "post/fwd")]
     rng = np.random.default_rng(5)
     gen = torch.Generator(device="cuda")
     gen.manual_seed(5)
@@ -129,11 +158,41 @@ def sweep_lines(dec, steps):
             vit.append(dec.last_align_timing_ms[2])
         cell = lambda d, k: "%9.3f ms" % d[k] if k in d else "%12s" % "-"  # noqa: E731
         ratio = lambda d: "%10.2f" % (d["wave"] / d["group"]) if "wave" in d else "%10s" % "-"  # noqa: E731
-        lines.append("  %6d %6d | %s %s %s | %s %s %s | %9.3f ms %8.2f" % (
+        post, fwd = time_posteriors(dec, dev, targets, steps)[:2]
+        lines.append("  %6d %6d | %s %s %s | %s %s %s | %9.3f ms %8.2f | %11.3f ms %8.2f" % (
             L, frames, cell(one, "wave"), cell(one, "group"), ratio(one), cell(many, "wave"), cell(many, "group"), ratio(many),
-            med(vit), one["group"] / med(vit)))
+            med(vit), one["group"] / med(vit), post, post / fwd))
         del dev
     return lines
+
+
+def align_lines(dec, dev, targets, n, steps):
+    """-> (ctc_viterbi ms, lines): align_batch with confidences, and the plain decode_batch step for scale."""
+    decode_ms = []
+    for k in range(steps + 1):
+        t0 = time.perf_counter()
+        dec.decode_batch(None, dev)
+        decode_ms.append((time.perf_counter() - t0) * 1e3)
+    wall, native, sniff, lse, vit = [], [], [], [], []
+    for k in range(steps + 1):
+        t0 = time.perf_counter()
+        out = dec.align_batch(dev, tokens=targets, confidence="mean")
+        wall.append((time.perf_counter() - t0) * 1e3)
+        ms = dec.last_align_timing_ms
+        sniff.append(ms[0]), lse.append(ms[1]), vit.append(ms[2]), native.append(ms[3])
+    assert all(a is not None and len(a.path) == T for a in out)
+    read = n * T * V * 4
+    dev_ms = med(sniff) + med(lse) + med(vit)
+    lines = [
+        "  %d ctc_viterbi launch(es)" % dec.last_align_launches,
+        "  row_lse          %9.3f ms  (%.2f GB read: %.1f %% of the 8 TB/s peak)" % (med(lse), read / 1e9, 100.0 * read / (med(lse) * 1e-3) / HBM_PEAK),
+        "  ctc_viterbi      %9.3f ms" % med(vit),
+        "  classification   %9.3f ms  (the decode's own frame-prune stage and sniff, at a threshold of 0)" % med(sniff),
+        "  native call      %9.3f ms  (host share %.3f ms: validation, staging, result copies)" % (med(native), med(native) - dev_ms),
+        "  align_batch      %9.3f ms  (Python share %.3f ms: targets in, AlignedText objects out)" % (med(wall), med(wall) - med(native)),
+        "  decode_batch     %9.3f ms  (the plain beam-search step on the same tensor, for scale)" % med(decode_ms),
+    ]
+    return med(vit), lines
 
 
 def main():
@@ -141,7 +200,9 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "align_bench.txt"))
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--procs", type=int, default=16)
+    ap.add_argument("--legs", default="align,score,posteriors,sweep", help="which parts to run (a partial run wants its own --out)")
     args = ap.parse_args()
+    legs = set(args.legs.split(","))
     lm = synth.SynthLM(os.path.join(ROOT, "bench_cache"), 2000, 6000, order=3, seed=7, max_ngrams={2: 60_000, 3: 120_000})
     labels = synth.make_bpe_vocab(lm.words, size=V - 1)
     _G.update(labels=labels, words=lm.words, sentences=lm.sentences)
@@ -164,34 +225,18 @@ def main():
         torch.cuda.synchronize()
         _texts, tf = dec.decode_batch(None, dev, token_frames=True)
         targets = [tf.label[int(tf.offsets[u]):int(tf.offsets[u + 1])].tolist() for u in range(n)]
-        decode_ms = []
-        for k in range(args.steps + 1):
-            t0 = time.perf_counter()
-            dec.decode_batch(None, dev)
-            decode_ms.append((time.perf_counter() - t0) * 1e3)
-        wall, native, sniff, lse, vit = [], [], [], [], []
-        for k in range(args.steps + 1):
-            t0 = time.perf_counter()
-            out = dec.align_batch(dev, tokens=targets, confidence="mean")
-            wall.append((time.perf_counter() - t0) * 1e3)
-            ms = dec.last_align_timing_ms
-            sniff.append(ms[0]), lse.append(ms[1]), vit.append(ms[2]), native.append(ms[3])
-        assert all(a is not None and len(a.path) == T for a in out)
-        read = n * T * V * 4
-        dev_ms = med(sniff) + med(lse) + med(vit)
-        lines += [
-            "%d utterances (%.0f target tokens on average, %d ctc_viterbi launch(es)):" % (n, np.mean([len(t) for t in targets]),
-                                                                                          dec.last_align_launches),
-            "  row_lse          %9.3f ms  (%.2f GB read: %.1f %% of the 8 TB/s peak)" % (med(lse), read / 1e9, 100.0 * read / (med(lse) * 1e-3) / HBM_PEAK),
-            "  ctc_viterbi      %9.3f ms" % med(vit),
-            "  classification   %9.3f ms  (the decode's own frame-prune stage and sniff, at a threshold of 0)" % med(sniff),
-            "  native call      %9.3f ms  (host share %.3f ms: validation, staging, result copies)" % (med(native), med(native) - dev_ms),
-            "  align_batch      %9.3f ms  (Python share %.3f ms: targets in, AlignedText objects out)" % (med(wall), med(wall) - med(native)),
-            "  decode_batch     %9.3f ms  (the plain beam-search step on the same tensor, for scale)" % med(decode_ms),
-        ]
-        lines += score_lines(dec, dev, targets, args.steps, med(vit))
+        lines.append("%d utterances (%.0f target tokens on average):" % (n, np.mean([len(t) for t in targets])))
+        vit_ms = None
+        if "align" in legs:
+            vit_ms, align = align_lines(dec, dev, targets, n, args.steps)
+            lines += align
+        if "score" in legs and vit_ms is not None:
+            lines += score_lines(dec, dev, targets, args.steps, vit_ms)
+        if "posteriors" in legs:
+            lines += posteriors_lines(dec, dev, targets, args.steps)
         del dev
-    lines += sweep_lines(dec, max(args.steps, 5))
+    if "sweep" in legs:
+        lines += sweep_lines(dec, max(args.steps, 5))
     text = "\n".join(lines) + "\n"
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
