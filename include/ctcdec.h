@@ -432,6 +432,25 @@ int ctcdec_posteriors_gamma(const ctcdec_posteriors* p, const int64_t** gamma_of
 int ctcdec_posteriors_timing(const ctcdec_posteriors* p, double* ms4, int32_t* launches, int64_t* launched2);
 void ctcdec_posteriors_free(ctcdec_posteriors* p);
 
+/* ---- transcript gradient: d logp / d (the utterance's own matrix) of a label sequence the caller already has --------------
+ * Arguments, checks, codes and messages are those of ctcdec_posteriors_batch; logp_out[u] is its logp[u], bit for bit. With
+ * gamma of "frame posteriors", G[t, k] the sum of gamma[t, s] over the states s whose label is k (the blank: the even states),
+ * lse[t] the row's log-sum-exp and y = x[t, k] - lse[t]:
+ *   logits:        u = y >= ln 1e-15 ? 1 : 0 (a NaN or -inf entry: 0),  G' = u G,  M[t] = sum over k of G'[t, k],
+ *                  grad[t, v] = G'[t, v] - exp(x[t, v] - lse[t]) M[t]    (nothing clipped: G - softmax)
+ *   probabilities: grad[t, v] = 1e-15 <= p <= 1 ? G[t, v] / p : 0
+ * grad_out[u] points to T_u * V elements of grad_dtype -- CTCDEC_F64 for CTCDEC_F64 logits, CTCDEC_F32 for every other dtype;
+ * computed in float64 and rounded once -- in host memory when is_device is 0 (the rows are copied back launch by launch), else
+ * in device memory, where the kernel writes them in place. An utterance without frames has logp 0.0 and its grad_out[u] is
+ * not touched. No floating-point atomics: the same utterance gives the same bits alone and in a batch, in one launch and in
+ * several, from host and from device memory. ms5 (may be NULL): [0] the classification, [1] row_lse, [2] ctc_posteriors,
+ * [3] ctc_grad_rows (HIP events, summed over the launches), [4] the whole native call; launches (may be NULL): kernel launches
+ * of ctc_posteriors and ctc_grad_rows made; launched2 (may be NULL): as ctcdec_posteriors_timing. */
+int ctcdec_gradient_batch(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts,
+                          int32_t dtype, int32_t is_device, const int64_t* label_off, const int32_t* labels, void* const* grad_out,
+                          int32_t grad_dtype, int64_t table_budget, double* logp_out, double* ms5, int32_t* launches,
+                          int64_t* launched2);
+
 /* timing of the last call's device stages in milliseconds (HIP events on the decode stream):
  * [0] frame-prune kernel, [1] beam kernel, [2] total device time incl. result copy */
 int ctcdec_result_timing(const ctcdec_result* r, double* ms3);

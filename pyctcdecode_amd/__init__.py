@@ -2,7 +2,7 @@
 (reference exports: pyctcdecode/__init__.py:2-4)."""
 from .alphabet import Alphabet  # noqa: F401
 from .decoder import (AlignedText, BeamSearchDecoderCTC, ConfidenceLMBeam, ConfidenceOutputBeam, ScoredText, TokenFrames,  # noqa: F401
-                      TokenLMBeam, TokenOutputBeam, TranscriptPosteriors, build_ctcdecoder)
+                      TokenLMBeam, TokenOutputBeam, TranscriptGradient, TranscriptPosteriors, build_ctcdecoder)
 from .language_model import LanguageModel  # noqa: F401
 
 __version__ = "0.1.0"

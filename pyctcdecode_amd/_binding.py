@@ -166,6 +166,10 @@ _PROTOS = {
                                           C.POINTER(C.POINTER(C.c_double))]),
     "ctcdec_posteriors_timing": (C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "ctcdec_posteriors_free": (None, [_VP]),
+    "ctcdec_gradient_batch": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32,
+                                        C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(_VP), C.c_int32, C.c_int64,
+                                        C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32),
+                                        C.POINTER(C.c_int64)]),
     "ctcdec_result_timing": (C.c_int, [_VP, C.POINTER(C.c_double)]),
     "ctcdec_result_beam_kernel": (C.c_int, [_VP]),
     "ctcdec_device": (C.c_int, []),

@@ -214,6 +214,9 @@ struct ctcdec_decoder {
   // frame posteriors (ctcdec_posteriors_batch): a launch's tables and utterance records, the token sums (labels: w_alab,
   // score pairs: w_ascore)
   DevBuf w_ptab, w_putts, w_pocc;
+  // transcript gradient (ctcdec_gradient_batch): the labels' occurrence lists, a launch's row records and, for host callers,
+  // its gradient rows (tables, labels and scores: the posteriors')
+  DevBuf w_gocc, w_gutts, w_grad;
   bool slicing = false;  // a time-sliced host ingest is under way (decode_host_sliced): the prune stage notes each slice's side of 1
   uint32_t max_label_bytes = 1;
   bool arenas_worst_case = false;  // a call has outgrown the usual reservation of the node arenas: reserve the worst case from now on
@@ -2734,6 +2737,116 @@ static const int64_t POSTERIORS_TABLE_BUDGET = (int64_t)4 << 30;
 
 static int64_t posteriors_table_bytes(int64_t T, int64_t L) { return 32 * T * (int64_t)align_chunks((int32_t)L); }
 
+// What ctcdec_posteriors_batch and ctcdec_gradient_batch check before anything moves: labels, frame counts and feasibility
+// are ctcdec_align_batch's; the budget is these calls' own
+static int check_posteriors(const ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts,
+                            const int64_t* label_off, const int32_t* labels, int64_t budget, int V, int blank) {
+  if (int rc = check_alignment(dec, utt_logits, utt_frames, n_utts, labels, label_off, INT64_MAX, V, blank)) return rc;
+  for (int32_t u = 0; u < n_utts; ++u) {
+    const int64_t bytes = posteriors_table_bytes(utt_frames[u], label_off[u + 1] - label_off[u]);
+    if (bytes > budget)
+      return fail(CTCDEC_ERR_LIMIT, "utterance " + std::to_string(u) + ": a table of " + std::to_string(bytes) + " bytes, above the budget of " +
+                                        std::to_string(budget) + " bytes for one launch");
+  }
+  return CTCDEC_OK;
+}
+
+// The launches of a call: utterances in input order until their tables fill the budget (ctcdec_align_batch's rule). Returns
+// the bytes of the largest launch's tables.
+static int64_t posteriors_groups(const int32_t* utt_frames, int32_t n_utts, const int64_t* label_off, int64_t budget,
+                                 std::vector<std::vector<int32_t>>& groups) {
+  int64_t used = 0, most = 0;
+  for (int32_t u = 0; u < n_utts; ++u) {
+    if (utt_frames[u] == 0) continue;
+    const int64_t bytes = posteriors_table_bytes(utt_frames[u], label_off[u + 1] - label_off[u]);
+    if (groups.empty() || used + bytes > budget) {
+      groups.emplace_back();
+      used = 0;
+    }
+    groups.back().push_back(u);
+    used += bytes;
+    most = std::max(most, used);
+  }
+  return most;
+}
+
+// One launch of ctc_posteriors over the utterances `g` of a call (at most two kernel launches: inside a launch the short
+// targets, 256 threads, come before the long ones, 1024, longest utterance first in each; `g` leaves in that order). The
+// call has uploaded its labels to w_alab and zeroed w_pocc and w_ascore. tab_off[j]: where utterance g[j]'s table starts in
+// w_ptab, in doubles; count: the utterances each instantiation took; launches: kernel launches made.
+struct PosteriorsLaunch {
+  std::vector<int64_t> tab_off;
+  int32_t count[2] = {0, 0};
+  int32_t launches = 0;
+};
+static int posteriors_launch(ctcdec_decoder* dec, std::vector<int32_t>& g, const AlignFront& fr, const std::vector<int64_t>& row0,
+                             const int32_t* utt_frames, const int64_t* label_off, int64_t NL, int V, int blank, int32_t dtype,
+                             int32_t dense, double clip_lo, PosteriorsLaunch& out) {
+  std::string err;
+  std::stable_sort(g.begin(), g.end(), [&](int32_t a, int32_t b) {
+    const bool la = align_chunks((int32_t)(label_off[a + 1] - label_off[a])) > ALIGN_THREADS;
+    const bool lb = align_chunks((int32_t)(label_off[b + 1] - label_off[b])) > ALIGN_THREADS;
+    return la != lb ? lb : utt_frames[a] > utt_frames[b];
+  });
+  std::vector<PostUtt> utts;
+  std::vector<int64_t>& tab_off = out.tab_off;
+  tab_off.clear();
+  int64_t off = 0;
+  int32_t max_chunks[2] = {1, 1};
+  int32_t* count = out.count;
+  count[0] = count[1] = 0;
+  out.launches = 0;
+  for (int32_t u : g) {
+    const int32_t L = (int32_t)(label_off[u + 1] - label_off[u]);
+    PostUtt a;
+    a.x = fr.ptrs[(size_t)u];
+    a.lse = fr.lse + row0[(size_t)u];
+    a.lab = (const int32_t*)dec->w_alab.p + label_off[u];
+    a.table = (double*)dec->w_ptab.p + off;
+    a.logp = (double*)dec->w_ascore.p + 2 * (size_t)u;
+    a.occ = (double*)dec->w_pocc.p + label_off[u];
+    a.centre = (double*)dec->w_pocc.p + NL + label_off[u];
+    a.T = utt_frames[u];
+    a.L = L;
+    a.is_prob = fr.is_prob[(size_t)u] ? 1 : 0;
+    a.pad = 0;
+    utts.push_back(a);
+    tab_off.push_back(off);
+    off += posteriors_table_bytes(utt_frames[u], L) / 8;
+    const int w = align_chunks(L) > ALIGN_THREADS ? 1 : 0;
+    max_chunks[w] = std::max(max_chunks[w], align_chunks(L));
+    ++count[w];
+  }
+#ifdef CTC_SIM  // (the kernel's body: a single thread owns every group)
+  std::vector<double> col((size_t)4 * (size_t)std::max(max_chunks[0], max_chunks[1]) + 2);
+  AlignSeqCtx cx;
+  for (const PostUtt& a : utts) {
+    if (dtype == 0) ctc_posteriors_utt<0>(cx, a, V, blank, clip_lo, dense, col.data());
+    else if (dtype == 1) ctc_posteriors_utt<1>(cx, a, V, blank, clip_lo, dense, col.data());
+    else if (dtype == 2) ctc_posteriors_utt<2>(cx, a, V, blank, clip_lo, dense, col.data());
+    else ctc_posteriors_utt<3>(cx, a, V, blank, clip_lo, dense, col.data());
+  }
+  for (int w = 0; w < 2; ++w) out.launches += count[w] ? 1 : 0;
+#else
+  if (upload(dec->w_putts, utts, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+  for (int w = 0; w < 2; ++w) {
+    if (!count[w]) continue;
+    be::PosteriorsArgs pa;
+    pa.utts = (const PostUtt*)dec->w_putts.p + (w ? count[0] : 0);
+    pa.n_utts = count[w];
+    pa.n_labels = V;
+    pa.dtype = dtype;
+    pa.blank = blank;
+    pa.max_chunks = max_chunks[w];
+    pa.dense = dense ? 1 : 0;
+    pa.clip_lo = clip_lo;
+    if (be::launch_ctc_posteriors(pa, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+    ++out.launches;
+  }
+#endif
+  return CTCDEC_OK;
+}
+
 extern "C" {
 
 int ctcdec_posteriors_batch(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts, int32_t dtype,
@@ -2748,14 +2861,7 @@ int ctcdec_posteriors_batch(ctcdec_decoder* dec, const void* const* utt_logits, 
     if (dec->alpha.labels[(size_t)v].empty()) blank = v;
   if (blank < 0) return fail(CTCDEC_ERR_ARG, "the alphabet has no blank label");
   const int64_t budget = table_budget ? table_budget : POSTERIORS_TABLE_BUDGET;
-  // labels, frame counts and feasibility are ctcdec_align_batch's; the budget is this call's own
-  if (int rc = check_alignment(dec, utt_logits, utt_frames, n_utts, labels, label_off, INT64_MAX, V, blank)) return rc;
-  for (int32_t u = 0; u < n_utts; ++u) {
-    const int64_t bytes = posteriors_table_bytes(utt_frames[u], label_off[u + 1] - label_off[u]);
-    if (bytes > budget)
-      return fail(CTCDEC_ERR_LIMIT, "utterance " + std::to_string(u) + ": a table of " + std::to_string(bytes) + " bytes, above the budget of " +
-                                        std::to_string(budget) + " bytes for one launch");
-  }
+  if (int rc = check_posteriors(dec, utt_logits, utt_frames, n_utts, label_off, labels, budget, V, blank)) return rc;
   const auto t_begin = Clock::now();
   std::unique_ptr<ctcdec_posteriors> res(new ctcdec_posteriors());
   const size_t n = (size_t)n_utts;
@@ -2789,84 +2895,17 @@ int ctcdec_posteriors_batch(ctcdec_decoder* dec, const void* const* utt_logits, 
     if ((NL && be::h2d(dec->w_alab.p, labels, (size_t)NL * 4, &err)) || be::zero(dec->w_pocc.p, nl1 * 16, &err) ||
         be::zero(dec->w_ascore.p, n * 16, &err))
       return fail(CTCDEC_ERR_DEVICE, err);
-    // launches: utterances in input order until their tables fill the budget (ctcdec_align_batch's rule); inside a launch the
-    // short targets (256 threads) before the long ones (1024), longest utterance first in each
     std::vector<std::vector<int32_t>> groups;
-    int64_t used = 0, most = 0;
-    for (int32_t u = 0; u < n_utts; ++u) {
-      if (utt_frames[u] == 0) continue;
-      const int64_t bytes = posteriors_table_bytes(utt_frames[u], label_off[u + 1] - label_off[u]);
-      if (groups.empty() || used + bytes > budget) {
-        groups.emplace_back();
-        used = 0;
-      }
-      groups.back().push_back(u);
-      used += bytes;
-      most = std::max(most, used);
-    }
+    const int64_t most = posteriors_groups(utt_frames, n_utts, label_off, budget, groups);
     if (dec->w_ptab.ensure((size_t)std::max<int64_t>(most, 32), &err)) return fail(CTCDEC_ERR_DEVICE, err);
     const double clip_lo = log(1e-15);  // ln(MIN_TOKEN_CLIP_P) (constants.py:17)
-    std::vector<PostUtt> utts;
+    PosteriorsLaunch pl;
     for (auto& g : groups) {
-      std::stable_sort(g.begin(), g.end(), [&](int32_t a, int32_t b) {
-        const bool la = align_chunks((int32_t)(label_off[a + 1] - label_off[a])) > ALIGN_THREADS;
-        const bool lb = align_chunks((int32_t)(label_off[b + 1] - label_off[b])) > ALIGN_THREADS;
-        return la != lb ? lb : utt_frames[a] > utt_frames[b];
-      });
-      utts.clear();
-      std::vector<int64_t> tab_off;
-      int64_t off = 0;
-      int32_t max_chunks[2] = {1, 1}, count[2] = {0, 0};
-      for (int32_t u : g) {
-        const int32_t L = (int32_t)(label_off[u + 1] - label_off[u]);
-        PostUtt a;
-        a.x = fr.ptrs[(size_t)u];
-        a.lse = fr.lse + row0[(size_t)u];
-        a.lab = (const int32_t*)dec->w_alab.p + label_off[u];
-        a.table = (double*)dec->w_ptab.p + off;
-        a.logp = (double*)dec->w_ascore.p + 2 * (size_t)u;
-        a.occ = (double*)dec->w_pocc.p + label_off[u];
-        a.centre = (double*)dec->w_pocc.p + NL + label_off[u];
-        a.T = utt_frames[u];
-        a.L = L;
-        a.is_prob = fr.is_prob[(size_t)u] ? 1 : 0;
-        a.pad = 0;
-        utts.push_back(a);
-        tab_off.push_back(off);
-        off += posteriors_table_bytes(utt_frames[u], L) / 8;
-        const int w = align_chunks(L) > ALIGN_THREADS ? 1 : 0;
-        max_chunks[w] = std::max(max_chunks[w], align_chunks(L));
-        ++count[w];
-      }
-#ifdef CTC_SIM  // (the kernel's body: a single thread owns every group)
-      std::vector<double> col((size_t)4 * (size_t)std::max(max_chunks[0], max_chunks[1]) + 2);
-      AlignSeqCtx cx;
-      for (const PostUtt& a : utts) {
-        if (dtype == 0) ctc_posteriors_utt<0>(cx, a, V, blank, clip_lo, dense, col.data());
-        else if (dtype == 1) ctc_posteriors_utt<1>(cx, a, V, blank, clip_lo, dense, col.data());
-        else if (dtype == 2) ctc_posteriors_utt<2>(cx, a, V, blank, clip_lo, dense, col.data());
-        else ctc_posteriors_utt<3>(cx, a, V, blank, clip_lo, dense, col.data());
-      }
-      for (int w = 0; w < 2; ++w) res->launches += count[w] ? 1 : 0;
-#else
-      if (upload(dec->w_putts, utts, &err)) return fail(CTCDEC_ERR_DEVICE, err);
-      for (int w = 0; w < 2; ++w) {
-        if (!count[w]) continue;
-        be::PosteriorsArgs pa;
-        pa.utts = (const PostUtt*)dec->w_putts.p + (w ? count[0] : 0);
-        pa.n_utts = count[w];
-        pa.n_labels = V;
-        pa.dtype = dtype;
-        pa.blank = blank;
-        pa.max_chunks = max_chunks[w];
-        pa.dense = dense ? 1 : 0;
-        pa.clip_lo = clip_lo;
-        if (be::launch_ctc_posteriors(pa, &err)) return fail(CTCDEC_ERR_DEVICE, err);
-        ++res->launches;
-      }
-#endif
-      res->launched[0] += count[0];
-      res->launched[1] += count[1];
+      if (int rc = posteriors_launch(dec, g, fr, row0, utt_frames, label_off, NL, V, blank, dtype, dense, clip_lo, pl)) return rc;
+      const std::vector<int64_t>& tab_off = pl.tab_off;
+      res->launches += pl.launches;
+      res->launched[0] += pl.count[0];
+      res->launched[1] += pl.count[1];
       // a dense result leaves with its launch: the next one takes the tables over
       for (size_t j = 0; dense && j < g.size(); ++j) {
         const size_t u = (size_t)g[j];
@@ -2928,6 +2967,169 @@ int ctcdec_posteriors_timing(const ctcdec_posteriors* p, double* ms4, int32_t* l
 }
 
 void ctcdec_posteriors_free(ctcdec_posteriors* p) { delete p; }
+
+// ---- transcript gradient ("Transcript gradient") ------------------------------------------------------------------
+}  // extern "C"
+
+#ifdef CTC_SIM
+namespace {
+struct GradSeqCtx {
+  enum { KEEP = 1 };  // (ctc_grad_row: the one thread owns every entry, and forms each share in both passes)
+  int tid = 0, nt = 1;
+  double sum(double v, int) { return v; }
+};
+template <int DT, class GT>
+void grad_rows_seq(const std::vector<GradUtt>& utts, int V, int blank, double clip_lo) {
+  GradSeqCtx cx;
+  for (const GradUtt& u : utts)
+    for (int t = 0; t < u.T; ++t) ctc_grad_row<DT, GT>(cx, u, t, V, blank, clip_lo);
+}
+}  // namespace
+#endif
+
+extern "C" {
+
+int ctcdec_gradient_batch(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts, int32_t dtype,
+                          int32_t is_device, const int64_t* label_off, const int32_t* labels, void* const* grad_out, int32_t grad_dtype,
+                          int64_t table_budget, double* logp_out, double* ms5, int32_t* launches_out, int64_t* launched2) {
+  if (!dec || n_utts < 0 || !label_off || table_budget < 0 || (n_utts > 0 && (!utt_logits || !utt_frames || !grad_out || !logp_out)))
+    return fail(CTCDEC_ERR_ARG, "bad arguments");
+  if (dtype < CTCDEC_F32 || dtype > CTCDEC_BF16) return fail(CTCDEC_ERR_ARG, "dtype must be f32, f64, f16 or bf16");
+  if (grad_dtype != (dtype == CTCDEC_F64 ? CTCDEC_F64 : CTCDEC_F32))
+    return fail(CTCDEC_ERR_ARG, "grad_dtype must be f64 for f64 logits and f32 for every other dtype");
+  const int V = (int)dec->alpha.labels.size();
+  int blank = -1;
+  for (int v = 0; v < V && blank < 0; ++v)
+    if (dec->alpha.labels[(size_t)v].empty()) blank = v;
+  if (blank < 0) return fail(CTCDEC_ERR_ARG, "the alphabet has no blank label");
+  const int64_t budget = table_budget ? table_budget : POSTERIORS_TABLE_BUDGET;
+  if (int rc = check_posteriors(dec, utt_logits, utt_frames, n_utts, label_off, labels, budget, V, blank)) return rc;
+  for (int32_t u = 0; u < n_utts; ++u)
+    if (utt_frames[u] > 0 && !grad_out[u]) return fail(CTCDEC_ERR_ARG, "utterance " + std::to_string(u) + ": no gradient buffer");
+  const auto t_begin = Clock::now();
+  const size_t n = (size_t)n_utts;
+  const int64_t NL = label_off[n];
+  std::vector<int64_t> row0(n + 1, 0);
+  for (size_t u = 0; u < n; ++u) row0[u + 1] = row0[u] + utt_frames[u];
+  const int64_t R = row0[n];
+  const size_t gsz = grad_dtype == CTCDEC_F64 ? 8 : 4;
+  double tms[5] = {0, 0, 0, 0, 0};
+  int32_t launches = 0;
+  int64_t launched[2] = {0, 0};
+  for (size_t u = 0; u < n; ++u) logp_out[u] = 0.0;  // (no frames and the empty target: the one empty alignment)
+  if (R > 0) {
+    std::string err;
+    std::lock_guard<std::mutex> device_lock(g_device_mu);
+    if (be::bind_thread(&err)) return fail(CTCDEC_ERR_DEVICE, err);
+    AlignFront fr;
+    if (int rc = align_front(dec, utt_logits, utt_frames, n_utts, dtype, is_device, V, row0, fr)) return rc;
+    tms[0] = fr.sniff_ms;
+    const size_t nl1 = (size_t)std::max<int64_t>(NL, 1);
+    if (dec->w_alab.ensure(nl1 * 4, &err) || dec->w_pocc.ensure(nl1 * 16, &err) || dec->w_ascore.ensure(n * 16, &err))
+      return fail(CTCDEC_ERR_DEVICE, err);
+    if ((NL && be::h2d(dec->w_alab.p, labels, (size_t)NL * 4, &err)) || be::zero(dec->w_pocc.p, nl1 * 16, &err) ||
+        be::zero(dec->w_ascore.p, n * 16, &err))
+      return fail(CTCDEC_ERR_DEVICE, err);
+    // every utterance's occurrence lists: [n][V + 1] offsets into its own part of the [NL] states, which are 2 k + 1 in the
+    // order of k under each label
+    std::vector<int32_t> occ(n * (size_t)(V + 1) + nl1, 0);
+    int32_t* const occ_state = occ.data() + n * (size_t)(V + 1);
+    std::vector<int32_t> next((size_t)V);
+    for (size_t u = 0; u < n; ++u) {
+      int32_t* off = occ.data() + u * (size_t)(V + 1);
+      const int32_t* lab = labels + label_off[u];
+      const int32_t L = (int32_t)(label_off[u + 1] - label_off[u]);
+      for (int32_t k = 0; k < L; ++k) ++off[lab[k] + 1];
+      for (int v = 0; v < V; ++v) off[v + 1] += off[v], next[(size_t)v] = off[v];
+      for (int32_t k = 0; k < L; ++k) occ_state[label_off[u] + next[(size_t)lab[k]]++] = 2 * k + 1;
+    }
+    if (upload(dec->w_gocc, occ, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+    const int32_t* const d_occ_off = (const int32_t*)dec->w_gocc.p;
+    const int32_t* const d_occ_state = d_occ_off + n * (size_t)(V + 1);
+    std::vector<std::vector<int32_t>> groups;
+    const int64_t most = posteriors_groups(utt_frames, n_utts, label_off, budget, groups);
+    if (dec->w_ptab.ensure((size_t)std::max<int64_t>(most, 32), &err)) return fail(CTCDEC_ERR_DEVICE, err);
+    if (!is_device) {  // a launch's rows leave through a buffer of the device's own
+      int64_t rows = 0;
+      for (const auto& g : groups) {
+        int64_t r = 0;
+        for (int32_t u : g) r += utt_frames[u];
+        rows = std::max(rows, r);
+      }
+      if (dec->w_grad.ensure((size_t)rows * (size_t)V * gsz, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+    }
+    const double clip_lo = log(1e-15);  // ln(MIN_TOKEN_CLIP_P) (constants.py:17)
+    PosteriorsLaunch pl;
+    std::vector<GradUtt> gutts;
+    for (auto& g : groups) {
+      if (int rc = posteriors_launch(dec, g, fr, row0, utt_frames, label_off, NL, V, blank, dtype, 1, clip_lo, pl)) return rc;
+      launches += pl.launches;
+      launched[0] += pl.count[0];
+      launched[1] += pl.count[1];
+      // the launch's rows, on the same stream, before the next launch takes the tables over
+      gutts.clear();
+      int64_t rows = 0;
+      for (size_t j = 0; j < g.size(); ++j) {
+        const size_t u = (size_t)g[j];
+        GradUtt a;
+        a.x = fr.ptrs[u];
+        a.lse = fr.lse + row0[u];
+        a.table = (const double*)dec->w_ptab.p + pl.tab_off[j];
+        a.occ_off = d_occ_off + u * (size_t)(V + 1);
+        a.occ_state = d_occ_state + label_off[u];
+        a.grad = is_device ? grad_out[u] : (void*)((char*)dec->w_grad.p + (size_t)rows * (size_t)V * gsz);
+        a.row_begin = rows;
+        a.T = utt_frames[u];
+        a.L = (int32_t)(label_off[u + 1] - label_off[u]);
+        a.is_prob = fr.is_prob[u] ? 1 : 0;
+        a.pad = 0;
+        gutts.push_back(a);
+        rows += utt_frames[u];
+      }
+#ifdef CTC_SIM  // (the kernel's body, row by row)
+      if (dtype == 0) grad_rows_seq<0, float>(gutts, V, blank, clip_lo);
+      else if (dtype == 1) grad_rows_seq<1, double>(gutts, V, blank, clip_lo);
+      else if (dtype == 2) grad_rows_seq<2, float>(gutts, V, blank, clip_lo);
+      else grad_rows_seq<3, float>(gutts, V, blank, clip_lo);
+#else
+      if (upload(dec->w_gutts, gutts, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+      be::GradRowsArgs ga;
+      ga.utts = (const GradUtt*)dec->w_gutts.p;
+      ga.n_utts = (int32_t)gutts.size();
+      ga.n_labels = V;
+      ga.n_rows = rows;
+      ga.dtype = dtype;
+      ga.grad_dtype = grad_dtype;
+      ga.blank = blank;
+      ga.pad = 0;
+      ga.clip_lo = clip_lo;
+      if (be::launch_ctc_grad_rows(ga, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+#endif
+      ++launches;
+      for (size_t j = 0; !is_device && j < g.size(); ++j) {
+        const size_t u = (size_t)g[j];
+        const size_t bytes = (size_t)utt_frames[u] * (size_t)V * gsz;
+        if (be::d2h(grad_out[u], gutts[j].grad, bytes, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+      }
+    }
+    std::vector<double> pair(2 * n);
+    if (be::d2h(pair.data(), dec->w_ascore.p, n * 16, &err)) return fail(CTCDEC_ERR_DEVICE, err);  // (waits for the last launch)
+    for (size_t u = 0; u < n; ++u)
+      if (utt_frames[u] > 0) logp_out[u] = pair[2 * u];
+#ifndef CTC_SIM
+    double vit_ms = 0;
+    be::align_timing(&tms[1], &vit_ms);
+    tms[2] = be::posteriors_timing();
+    tms[3] = be::grad_rows_timing();
+#endif
+  }
+  tms[4] = ms(t_begin, Clock::now());
+  if (ms5)
+    for (int k = 0; k < 5; ++k) ms5[k] = tms[k];
+  if (launches_out) *launches_out = launches;
+  if (launched2) launched2[0] = launched[0], launched2[1] = launched[1];
+  return CTCDEC_OK;
+}
 
 // a texts-only result (params.texts_only) as ordinary beams, for the accessors that want them
 static void materialise(const ctcdec_result* cr) {

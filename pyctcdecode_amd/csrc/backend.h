@@ -268,12 +268,28 @@ struct PosteriorsArgs {
   double clip_lo;      // ln(MIN_TOKEN_CLIP_P)
 };
 int launch_ctc_posteriors(const PosteriorsArgs& a, std::string* err);
-// kernel times (HIP events) of the launch_row_lse / launch_ctc_viterbi / launch_ctc_forward / launch_ctc_posteriors calls since
-// the last reset; waits for the kernels
+// ctc_grad_rows: the threads of a workgroup share one row, or 4 or 16 rows of a small vocabulary, of the n_rows rows of the
+// entries of `utts` (GradUtt::row_begin ascending from 0), all of them validated by the host; their tables hold the gamma of
+// a dense launch_ctc_posteriors queued before this launch
+struct GradRowsArgs {
+  const GradUtt* utts;  // [n_utts] (device)
+  int32_t n_utts;
+  int32_t n_labels;
+  int64_t n_rows;
+  int32_t dtype;
+  int32_t grad_dtype;  // ctcdec_dtype of GradUtt::grad: f64 for f64 rows, f32 for every other dtype
+  int32_t blank;
+  int32_t pad;
+  double clip_lo;      // ln(MIN_TOKEN_CLIP_P)
+};
+int launch_ctc_grad_rows(const GradRowsArgs& a, std::string* err);
+// kernel times (HIP events) of the launch_row_lse / launch_ctc_viterbi / launch_ctc_forward / launch_ctc_posteriors /
+// launch_ctc_grad_rows calls since the last reset; waits for the kernels
 void align_timing_reset();
 void align_timing(double* row_lse_ms, double* viterbi_ms);
 double forward_timing();
 double posteriors_timing();
+double grad_rows_timing();
 
 // stage timing (ms) of the last launch_prune / launch_beam pair, measured on the decode stream
 void last_timing(double* prune_ms, double* beam_ms);

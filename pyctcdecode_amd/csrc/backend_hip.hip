@@ -2365,6 +2365,8 @@ int launch_ctc_forward_on(const ForwardArgs& a, int wave, hipStream_t stream, st
 int launch_ctc_forward(const ForwardArgs& a, int wave, std::string* err) { return launch_ctc_forward_on(a, wave, g_stream, err); }
 int launch_ctc_posteriors_on(const PosteriorsArgs& a, hipStream_t stream, std::string* err);
 int launch_ctc_posteriors(const PosteriorsArgs& a, std::string* err) { return launch_ctc_posteriors_on(a, g_stream, err); }
+int launch_ctc_grad_rows_on(const GradRowsArgs& a, hipStream_t stream, std::string* err);
+int launch_ctc_grad_rows(const GradRowsArgs& a, std::string* err) { return launch_ctc_grad_rows_on(a, g_stream, err); }
 int launch_row_lse(const RowLseArgs& a, std::string* err) { return launch_row_lse_on(a, g_stream, err); }
 int launch_ctc_viterbi(const ViterbiArgs& a, std::string* err) { return launch_ctc_viterbi_on(a, g_stream, err); }
 

@@ -2,9 +2,11 @@
 // fp64 log-sum-exp of a frame row and the Viterbi recursion over the blank / label / blank / ... states, with its back-trace
 // and the confidence fold over the path; and the likelihood of a label sequence ("Transcript likelihood"): the
 // forward recursion over the same states, the sum over all alignments where the Viterbi takes the best one; and the frame
-// posteriors of a label sequence ("Frame posteriors"): the forward-backward over the same states. One body each
-// for the HIP kernels (ctc_align_hip.hip: row_lse, ctc_viterbi, ctc_forward, ctc_forward_wave, ctc_posteriors) and for the CPU simulator
-// build, whose "device" memory is host memory (api.cpp under CTC_SIM runs them with a one-thread context).
+// posteriors of a label sequence ("Frame posteriors"): the forward-backward over the same states; and the gradient
+// of the likelihood with respect to the frames' entries ("Transcript gradient"): the posteriors folded by label,
+// row by row. One body each for the HIP kernels (ctc_align_hip.hip: row_lse, ctc_viterbi, ctc_forward, ctc_forward_wave,
+// ctc_posteriors, ctc_grad_rows) and for the CPU simulator build, whose "device" memory is host memory (api.cpp under CTC_SIM
+// runs them with a one-thread context).
 #pragma once
 #include <math.h>
 #include <stddef.h>
@@ -725,6 +727,95 @@ CTC_HD void ctc_posteriors_utt(Ctx& cx, const PostUtt& utt, int V, int blank, do
     if (c == 0) out[1] = align_lse2(bq[k][0], bq[k][1]);  // b_0 + e(0, .) of the two states a path may start in
     if (g[k].l0 >= 0) utt.occ[2 * c] = occ0[k], utt.centre[2 * c] = cen0[k] / occ0[k];
     if (g[k].l1 >= 0) utt.occ[2 * c + 1] = occ1[k], utt.centre[2 * c + 1] = cen1[k] / occ1[k];
+  }
+}
+
+// ---- ctc_grad_rows -----------------------------------------------------------------------------------------------------------
+// The gradient of ctc_forward's logp with respect to the utterance's own matrix ("Transcript gradient"), one row
+// (t, utterance) at a time, from the gamma a dense ctc_posteriors launch left in the utterance's table. With G[t, k] the sum
+// of gamma[t, s] over the states s whose label is k, and e the emission of align_emit_of_value:
+//   logits:        u = (x - lse >= clip_lo), G' = u G, M = sum_k G'[t, k],  grad[t, v] = G'[t, v] - exp(x[t, v] - lse[t]) M
+//   probabilities: grad[t, v] = 1e-15 <= p <= 1 ? G[t, v] / p : 0
+// (the clip has derivative 0 where it holds: a NaN or -inf entry has u = 0). Nothing is scattered: the host lists, per
+// utterance, the states of every label (occ_off[v] .. occ_off[v + 1] of occ_state, ascending), and the thread that owns entry
+// v sums its list in that order. One utterance of a launch, validated by the host like PostUtt.
+struct GradUtt {
+  const void* x;             // [T, V] logits or probabilities, of the launch's dtype
+  const double* lse;         // [T] log-sum-exp of each row (not read when is_prob)
+  const double* table;       // [T][4 * align_chunks(L)] gamma, 0.0 outside the window (a dense ctc_posteriors launch wrote it)
+  const int32_t* occ_off;    // [V + 1] label v is the target's labels occ_off[v] .. occ_off[v + 1] in occ_state (the blank: none)
+  const int32_t* occ_state;  // [L] state indices 2 k + 1, ascending within a label
+  void* grad;                // [T, V] out, of the launch's gradient type
+  int64_t row_begin;         // the utterance's first row among the rows of the launch
+  int32_t T, L, is_prob, pad;
+};
+
+// 1.0 where the emission is not held by its clip, else 0.0
+CTC_HD double grad_unclipped(double v, double lse, bool is_prob, double clip_lo) {
+  if (is_prob) return (v >= 1e-15 && v <= 1.0) ? 1.0 : 0.0;
+  return (v - lse >= clip_lo) ? 1.0 : 0.0;
+}
+// G[t, v] of a label: its states inside the window [lo, hi], in ascending order (outside it gamma is 0.0: skipping adds the same)
+CTC_HD double grad_label_sum(const double* gamma, const int32_t* occ_off, const int32_t* occ_state, int v, int lo, int hi) {
+  double acc = 0.0;
+  const int j1 = occ_off[v + 1];
+  for (int j = occ_off[v]; j < j1; ++j) {
+    const int s = occ_state[j];
+    if (s >= lo && s <= hi) acc += gamma[s];
+  }
+  return acc;
+}
+// u G (logits) or G / p (probabilities) of entry v, whose value is xv. Only the blank and the target's labels have a G.
+CTC_HD double grad_share(const GradUtt& u, const double* gamma, int v, int blank, double g_blank, double xv, double lse, double clip_lo,
+                         int lo, int hi) {
+  const bool is_prob = u.is_prob != 0;
+  const double g = v == blank ? g_blank : grad_label_sum(gamma, u.occ_off, u.occ_state, v, lo, hi);
+  if (grad_unclipped(xv, lse, is_prob, clip_lo) == 0.0) return 0.0;
+  return is_prob ? g / xv : g;
+}
+
+// One row. cx: tid, nt (the threads that share the row), KEEP (entries a thread keeps in registers between the two passes),
+// sum(v, slot): the sum of v over the nt threads in a fixed tree, the same bits in every thread. Thread tid owns the entries
+// tid, tid + nt, ...: pass one loads each once, forms its share and adds it to the thread's part of M; pass two writes. What
+// lies beyond KEEP * nt entries is formed again in pass two, with the same operands. The blank's G is the sum of the even
+// states of the window: thread tid takes the states 2 (tid + i nt) in ascending i, and sum() folds the parts.
+template <int DT, class GT, class Ctx>
+CTC_HD void ctc_grad_row(Ctx& cx, const GradUtt& u, int t, int V, int blank, double clip_lo) {
+  constexpr int K = Ctx::KEEP;
+  const int T = u.T, S = 2 * u.L + 1, nch = align_chunks(u.L);
+  const bool is_prob = u.is_prob != 0;
+  const double* const gamma = u.table + post_slot(t, nch, 0);
+  const int lo_raw = S - 2 - 2 * (T - 1 - t), lo = lo_raw > 0 ? lo_raw : 0, hi = 2 * t + 1 < S - 1 ? 2 * t + 1 : S - 1;
+  double part = 0.0;
+  for (int s = ((lo + 1) & ~1) + 2 * cx.tid; s <= hi; s += 2 * cx.nt) part += gamma[s];
+  const double g_blank = cx.sum(part, 0);
+  const double lse = is_prob ? 0.0 : u.lse[t];
+  const size_t row = (size_t)t * (size_t)V;
+  GT* const out = (GT*)u.grad + row;
+  double xv[K], share[K];
+  double m = 0.0;
+  CTC_UNROLL
+  for (int k = 0; k < K; ++k) {
+    const int v = cx.tid + k * cx.nt;
+    xv[k] = share[k] = 0.0;
+    if (v >= V) continue;
+    xv[k] = align_load(u.x, DT, row + (size_t)v);
+    share[k] = grad_share(u, gamma, v, blank, g_blank, xv[k], lse, clip_lo, lo, hi);
+    m += share[k];
+  }
+  for (int v = cx.tid + K * cx.nt; v < V; v += cx.nt)
+    m += grad_share(u, gamma, v, blank, g_blank, align_load(u.x, DT, row + (size_t)v), lse, clip_lo, lo, hi);
+  const double M = cx.sum(m, 1);
+  CTC_UNROLL
+  for (int k = 0; k < K; ++k) {
+    const int v = cx.tid + k * cx.nt;
+    if (v >= V) continue;
+    out[v] = (GT)(is_prob ? share[k] : share[k] - exp(xv[k] - lse) * M);
+  }
+  for (int v = cx.tid + K * cx.nt; v < V; v += cx.nt) {
+    const double x = align_load(u.x, DT, row + (size_t)v);
+    const double sh = grad_share(u, gamma, v, blank, g_blank, x, lse, clip_lo, lo, hi);
+    out[v] = (GT)(is_prob ? sh : sh - exp(x - lse) * M);
   }
 }
 

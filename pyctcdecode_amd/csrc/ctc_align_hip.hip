@@ -1,7 +1,8 @@
 // ctc_align_hip.hip -- forced alignment and transcript likelihood on gfx950 (ctc_align.h): row_lse, the fp64 log-sum-exp of
 // every frame row; ctc_viterbi, one workgroup per utterance over the blank / label / blank / ... states; ctc_forward and
 // ctc_forward_wave, the sum over all alignments of a hypothesis, one workgroup / one wavefront each; ctc_posteriors, the
-// forward-backward of an utterance's transcript, one workgroup each. A translation unit of its own.
+// forward-backward of an utterance's transcript, one workgroup each; ctc_grad_rows, the gradient of the likelihood from the
+// posteriors a dense ctc_posteriors launch left, row by row. A translation unit of its own.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -166,6 +167,48 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4))) void ct
   ctc_posteriors_utt<DT>(cx, a.utts[blockIdx.x], a.n_labels, a.blank, a.clip_lo, a.dense, posteriors_cols);
 }
 
+// ---------------------------------------------------------------------------------------------
+// ctc_grad_rows: G threads per row (a workgroup for wide rows, a wave or 16 lanes for small vocabularies, so that a workgroup
+// takes 4 or 16 rows); a thread keeps K of its entries and their shares of gamma in registers between the pass that sums M and
+// the pass that writes (ctc_align.h). Every logit and every gamma is read once, every gradient entry is written once, in
+// neighbouring lanes' neighbouring entries. The sums over a row's threads are butterflies of shuffles inside a wave and, for a
+// workgroup, the four waves' parts through LDS in a fixed order: no atomics, the same bits wherever the row runs.
+// ---------------------------------------------------------------------------------------------
+template <int G, int K>
+struct GradGpuCtx {
+  enum { KEEP = K };
+  int tid, nt;
+  double* parts;  // [8] (G == 256): the waves' parts of the two sums of a row
+  __device__ __forceinline__ double sum(double v, int slot) {
+    constexpr int W = G < 64 ? G : 64;
+    CTC_UNROLL
+    for (int off = W / 2; off >= 1; off >>= 1) v += __shfl_xor(v, off, W);
+    if (G <= 64) return v;
+    double* p = parts + 4 * slot;
+    if ((tid & 63) == 0) p[tid >> 6] = v;
+    __syncthreads();
+    return (p[0] + p[1]) + (p[2] + p[3]);
+  }
+};
+
+template <int G, int K, int DT, class GT>
+__global__ __launch_bounds__(ALIGN_THREADS) void ctc_grad_rows(GradRowsArgs a) {
+  static_assert(G == 16 || G == 64 || G == ALIGN_THREADS, "a row's threads: part of a wave, a wave or the workgroup");
+  constexpr int RPB = ALIGN_THREADS / G;  // rows per workgroup
+  __shared__ double parts[8];
+  const int64_t row = (int64_t)blockIdx.x * RPB + (int)(threadIdx.x / G);
+  if (row >= a.n_rows) return;  // (the whole group of threads: `row` is theirs alone, and a workgroup's when it synchronises)
+  int lo = 0, hi = a.n_utts;  // utts[lo].row_begin <= row < utts[hi].row_begin
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (a.utts[mid].row_begin <= row) lo = mid;
+    else hi = mid;
+  }
+  const GradUtt u = a.utts[lo];
+  GradGpuCtx<G, K> cx{(int)(threadIdx.x % G), G, parts};
+  ctc_grad_row<DT, GT>(cx, u, (int)(row - u.row_begin), a.n_labels, a.blank, a.clip_lo);
+}
+
 // kernel times: one pair of events per launch since the last reset
 struct EventLog {
   std::vector<hipEvent_t> ev;
@@ -188,11 +231,12 @@ struct EventLog {
     return sum;
   }
 };
-static EventLog g_lse_log, g_vit_log, g_fwd_log, g_post_log;
+static EventLog g_lse_log, g_vit_log, g_fwd_log, g_post_log, g_grad_log;
 
-void align_timing_reset() { g_lse_log.used = g_vit_log.used = g_fwd_log.used = g_post_log.used = 0; }
+void align_timing_reset() { g_lse_log.used = g_vit_log.used = g_fwd_log.used = g_post_log.used = g_grad_log.used = 0; }
 double forward_timing() { return g_fwd_log.total(); }
 double posteriors_timing() { return g_post_log.total(); }
+double grad_rows_timing() { return g_grad_log.total(); }
 void align_timing(double* row_lse_ms, double* viterbi_ms) {
   *row_lse_ms = g_lse_log.total();
   *viterbi_ms = g_vit_log.total();
@@ -289,6 +333,37 @@ int launch_ctc_posteriors_on(const PosteriorsArgs& a, hipStream_t stream, std::s
   else if (a.dtype == 1) launch_posteriors_dt<1>(a, stream);
   else if (a.dtype == 2) launch_posteriors_dt<2>(a, stream);
   else launch_posteriors_dt<3>(a, stream);
+  HIP_TRY_A(hipGetLastError());
+  HIP_TRY_A(hipEventRecord(e1, stream));
+  return 0;
+}
+
+// the row's threads and what they keep by the vocabulary alone: 16 lanes up to 64 labels, a wave up to 256 (four entries
+// each), the workgroup above (four entries each up to 1024 labels, else sixteen; beyond 4096 labels the rest is formed twice)
+template <int DT, class GT>
+static void launch_grad_rows_dt(const GradRowsArgs& a, hipStream_t stream) {
+  const int V = a.n_labels;
+  const int rpb = V <= 64 ? 16 : V <= 256 ? 4 : 1;
+  const dim3 grid((unsigned)((a.n_rows + rpb - 1) / rpb)), block(ALIGN_THREADS);
+  if (V <= 64) hipLaunchKernelGGL((ctc_grad_rows<16, 4, DT, GT>), grid, block, 0, stream, a);
+  else if (V <= 256) hipLaunchKernelGGL((ctc_grad_rows<64, 4, DT, GT>), grid, block, 0, stream, a);
+  else if (V <= 1024) hipLaunchKernelGGL((ctc_grad_rows<ALIGN_THREADS, 4, DT, GT>), grid, block, 0, stream, a);
+  else hipLaunchKernelGGL((ctc_grad_rows<ALIGN_THREADS, 16, DT, GT>), grid, block, 0, stream, a);
+}
+
+int launch_ctc_grad_rows_on(const GradRowsArgs& a, hipStream_t stream, std::string* err) {
+  if (a.n_utts <= 0 || a.n_rows <= 0) return 0;
+  if (a.dtype < 0 || a.dtype > 3 || a.grad_dtype != (a.dtype == 1 ? 1 : 0) || a.n_labels < 1 || a.n_rows > (int64_t)0x7FFFFFFF) {
+    if (err) *err = "ctc_grad_rows: bad arguments";
+    return -1;
+  }
+  hipEvent_t e0, e1;
+  if (g_grad_log.next(&e0, err) || g_grad_log.next(&e1, err)) return -1;
+  HIP_TRY_A(hipEventRecord(e0, stream));
+  if (a.dtype == 0) launch_grad_rows_dt<0, float>(a, stream);
+  else if (a.dtype == 1) launch_grad_rows_dt<1, double>(a, stream);
+  else if (a.dtype == 2) launch_grad_rows_dt<2, float>(a, stream);
+  else launch_grad_rows_dt<3, float>(a, stream);
   HIP_TRY_A(hipGetLastError());
   HIP_TRY_A(hipEventRecord(e1, stream));
   return 0;

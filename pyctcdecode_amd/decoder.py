@@ -210,6 +210,22 @@ class TranscriptPosteriors:
         return None if self.gamma is None else self.gamma[:, 0::2].sum(axis=1)
 
 
+@dataclasses.dataclass(frozen=True, eq=False)
+class TranscriptGradient:
+    """What the likelihood of a known transcript asks of each entry of the utterance's matrix (BeamSearchDecoderCTC.gradient /
+    gradient_batch): ``text`` and ``tokens`` are ScoredText's, ``logp`` is the CTC forward score, the float score /
+    score_batch returns for the same input, and ``grad`` (``[T, V]``) is its derivative with respect to the input as it was
+    given -- logits: ``G' - softmax * M`` (DESIGN.md, "Transcript gradient"; ``G - softmax`` where nothing is clipped);
+    probabilities: ``G / p`` -- with derivative 0 wherever the library's clip holds the entry. The sign is logp's: a loss
+    negates it. ``grad`` is float64 for float64 input and float32 for float32 / float16 / bfloat16 input (computed in float64,
+    rounded once): a numpy array for host input, a torch tensor on the input's device for device tensors."""
+
+    text: str
+    tokens: List[int]
+    logp: float
+    grad: Any
+
+
 POSTERIORS_TABLE_BUDGET = 4 << 30  # bytes of tables one ctc_posteriors launch holds by default (DESIGN.md, "Frame posteriors")
 FORWARD_KERNELS = {"wave": 1, "group": 2}  # ctcdec_score_batch's `kernel` from CTCDEC_FORWARD_KERNEL (unset: the library chooses)
 CONFIDENCE_FOLDS = {"mean": 2, "min": 3, "max": 4}  # ctcdec_params.token_frames: CTCDEC_TOKEN_LOGP_MEAN / _MIN / _MAX
@@ -303,6 +319,41 @@ def _same_lm_state(a: Any, b: Any) -> bool:
 
 def _is_device_tensor(x: Any) -> bool:
     return hasattr(x, "data_ptr") and hasattr(x, "is_cuda")
+
+
+_CTC_LOSS_FUNCTION = None
+
+
+def _ctc_loss_function():
+    """The torch.autograd.Function behind BeamSearchDecoderCTC.ctc_loss (made on first use: the shell runs without torch)."""
+    global _CTC_LOSS_FUNCTION
+    if _CTC_LOSS_FUNCTION is not None:
+        return _CTC_LOSS_FUNCTION
+    import torch
+
+    class CtcLoss(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, decoder, texts, tokens, reduction, cube, *xs):
+            res, buf, _keep = decoder._gradient_batch(xs[0] if cube else list(xs), texts, tokens, True, 0)
+            ctx.cube, ctx.reduction = cube, reduction
+            ctx.dtypes = [x.dtype for x in xs]
+            # one native call serves both passes: the gradient rows stay on the device until backward
+            ctx.grads = [buf.view(xs[0].shape)] if cube and buf is not None else [r.grad for r in res]
+            loss = -torch.tensor([r.logp for r in res], dtype=torch.float64, device=xs[0].device)
+            return loss.sum() if reduction == "sum" else loss
+
+        @staticmethod
+        def backward(ctx, upstream):
+            up = upstream.to(torch.float64)
+            if ctx.cube:
+                scale = up if ctx.reduction == "sum" else up.view(-1, 1, 1)
+                grads = [(ctx.grads[0] * -scale).to(ctx.dtypes[0])]
+            else:
+                grads = [(g * -(up if ctx.reduction == "sum" else up[u])).to(d) for u, (g, d) in enumerate(zip(ctx.grads, ctx.dtypes))]
+            return (None, None, None, None, None) + tuple(grads)
+
+    _CTC_LOSS_FUNCTION = CtcLoss
+    return CtcLoss
 
 
 def _is_per_utt_hotwords(hotwords: Any) -> bool:
@@ -1101,6 +1152,11 @@ class BeamSearchDecoderCTC:
         self.last_posteriors_timing_ms = (0.0, 0.0, 0.0, 0.0)
         self.last_posteriors_launches = 0
         self.last_posteriors_launched = (0, 0)
+        # ... and of the last gradient / gradient_batch / ctc_loss call (ms: classification, row_lse, ctc_posteriors,
+        # ctc_grad_rows, whole native call; launches of both kernels; utterances by ctc_posteriors instantiation)
+        self.last_gradient_timing_ms = (0.0, 0.0, 0.0, 0.0, 0.0)
+        self.last_gradient_launches = 0
+        self.last_gradient_launched = (0, 0)
 
     def __del__(self):
         h = getattr(self, "_handle", None)
@@ -1893,6 +1949,109 @@ class BeamSearchDecoderCTC:
                 out[u] = TranscriptPosteriors(self._words_of_target(ids)[0], list(ids), float(logp[j]), float(logp_b[j]), gammas[j],
                                               occ[o:o + len(ids)].copy(), cen[o:o + len(ids)].copy())
             return out
+
+    # -- transcript gradient (no reference analogue; DESIGN.md, "Transcript gradient") ---------------------
+    def gradient(self, logits: Any, text: Optional[str] = None, tokens: Optional[Sequence[int]] = None) -> "TranscriptGradient":
+        """The gradient of one utterance's transcript likelihood: gradient_batch of a batch of one (a ValueError when no
+        alignment exists)."""
+        self._check_logits_dimension(logits)
+        return self.gradient_batch([logits], None if text is None else [text], tokens=None if tokens is None else [tokens])[0]
+
+    def gradient_batch(self, logits_list: Any, texts: Optional[Sequence[str]] = None,
+                       tokens: Optional[Sequence[Sequence[int]]] = None, strict: bool = True,
+                       _table_budget: int = 0) -> List[Optional["TranscriptGradient"]]:
+        """The derivative of each known transcript's CTC likelihood with respect to its utterance's matrix, in one native
+        call: row_lse, a dense ctc_posteriors launch and ctc_grad_rows over its tables (csrc/ctc_align_hip.hip), as
+        TranscriptGradient. Arguments, checks and limits are posteriors_batch's. Host arrays give numpy arrays; device
+        tensors give torch tensors on the same device -- views of one allocation the kernel writes in place, never copied to
+        the host."""
+        return self._gradient_batch(logits_list, texts, tokens, strict, _table_budget)[0]
+
+    def _gradient_batch(self, logits_list, texts, tokens, strict, _table_budget):
+        """-> (gradient_batch's list, the one buffer every ``grad`` is a view of -- None without rows --, the utterances that
+        have an alignment)."""
+        logits_list, targets = self._one_target_each("gradient", logits_list, texts, tokens)
+        n, n_labels = len(targets), len(self._labels_list)
+        self.last_gradient_timing_ms, self.last_gradient_launches, self.last_gradient_launched = (0.0,) * 5, 0, (0, 0)
+        if n == 0:
+            return [], None, []
+        with self._call_lock:
+            batch = _Batch(logits_list, n_labels)
+            if batch.is_device and batch.device_index is not None and batch.device_index != self._device:
+                raise ValueError("the logits live on cuda:%d but this decoder was built for cuda:%d (one process per GPU: "
+                                 "LOCAL_RANK / CTCDEC_DEVICE pick the device)" % (batch.device_index, self._device))
+            frames = np.asarray(batch.frames, dtype=np.int32)
+            ptrs = np.asarray(batch.ptrs, dtype=np.uint64)
+            budget = int(_table_budget) or POSTERIORS_TABLE_BUDGET
+            keep, bad = [], []
+            for u, ids in enumerate(targets):
+                need = len(ids) + sum(1 for a, b in zip(ids, ids[1:]) if a == b)
+                (keep if int(frames[u]) >= need else bad).append(u)
+                table = 32 * int(frames[u]) * ((2 * len(ids) + 1 + 3) // 4)
+                if table > budget:
+                    raise ValueError("gradient: utterance %d needs a table of %d bytes, above the memory budget of %d bytes of "
+                                     "one launch" % (u, table, budget))
+            if bad and strict:
+                raise ValueError("gradient: no alignment for utterances %s: fewer frames than target labels plus adjacent "
+                                 "equal labels" % bad)
+            out: List[Optional[TranscriptGradient]] = [None] * n
+            if not keep:
+                return out, None, keep
+            k_ptrs = np.ascontiguousarray(ptrs[keep])
+            k_frames = np.ascontiguousarray(frames[keep])
+            flat = np.array([c for u in keep for c in targets[u]] or [0], dtype=np.int32)
+            off = np.zeros(len(keep) + 1, dtype=np.int64)
+            off[1:] = np.cumsum([len(targets[u]) for u in keep])
+            # one buffer for every utterance's rows, of float64 for float64 input and float32 otherwise: the shell makes it,
+            # the native call fills it -- on the device for device tensors
+            row0 = np.zeros(len(keep) + 1, dtype=np.int64)
+            row0[1:] = np.cumsum(k_frames, dtype=np.int64)
+            wide = batch.dtype == 1
+            if batch.is_device:
+                import torch
+
+                buf = torch.empty(int(row0[-1]) * n_labels, dtype=torch.float64 if wide else torch.float32, device=batch.keep[0].device)
+                base, size = buf.data_ptr(), buf.element_size()
+            else:
+                buf = np.empty(int(row0[-1]) * n_labels, dtype=np.float64 if wide else np.float32)
+                base, size = buf.ctypes.data, buf.itemsize
+            g_ptrs = (np.uint64(base) + row0[:-1].astype(np.uint64) * np.uint64(n_labels * size)).astype(np.uint64)
+            logp = np.zeros(len(keep), dtype=np.float64)
+            ms, launches, launched = (C.c_double * 5)(), C.c_int32(), (C.c_int64 * 2)()
+            lib = self._lib
+            lib.check(lib.dll.ctcdec_gradient_batch(
+                self._handle, k_ptrs.ctypes.data_as(C.POINTER(C.c_void_p)), k_frames.ctypes.data_as(C.POINTER(C.c_int32)),
+                len(keep), batch.dtype, int(batch.is_device), B.off_ptr(off), flat.ctypes.data_as(C.POINTER(C.c_int32)),
+                g_ptrs.ctypes.data_as(C.POINTER(C.c_void_p)), 1 if wide else 0, int(_table_budget),
+                logp.ctypes.data_as(C.POINTER(C.c_double)), ms, C.byref(launches), launched))
+            # [classification (frame-prune kernels), row_lse, ctc_posteriors, ctc_grad_rows (HIP events), whole native call];
+            # kernel launches made (both kernels); utterances that went to (the 256-thread, the 1024-thread) ctc_posteriors
+            self.last_gradient_timing_ms = tuple(float(v) for v in ms)
+            self.last_gradient_launches = int(launches.value)
+            self.last_gradient_launched = (int(launched[0]), int(launched[1]))
+            for j, u in enumerate(keep):
+                ids = targets[u]
+                grad = buf[int(row0[j]) * n_labels:int(row0[j + 1]) * n_labels].reshape(int(k_frames[j]), n_labels)
+                out[u] = TranscriptGradient(self._words_of_target(ids)[0], list(ids), float(logp[j]), grad)
+            return out, buf, keep
+
+    def ctc_loss(self, logits: Any, texts: Optional[Sequence[str]] = None, tokens: Optional[Sequence[Sequence[int]]] = None,
+                 reduction: str = "sum"):
+        """``-logp`` of each utterance's transcript as a differentiable torch value: ``logits`` is a list of ``[T, V]`` device
+        tensors or one ``[B, T, V]`` device tensor, ``texts`` / ``tokens`` gradient_batch's. Returns a float64 tensor of B
+        values (``reduction="none"``) or their sum (``"sum"``), the floats of ``-score``. The forward pass makes one native
+        call and keeps its gradient; ``backward`` hands ``-grad * grad_output`` to each input, in its dtype and shape. There is
+        no ``"mean"``: torch's divides by the target lengths, other libraries by the batch size -- divide the result by what
+        the training recipe means. An utterance without an alignment raises a ValueError."""
+        import torch
+
+        if reduction not in ("sum", "none"):
+            raise ValueError("ctc_loss: reduction is 'sum' or 'none' (divide by what the recipe calls the mean), not %r" % (reduction,))
+        cube = getattr(logits, "ndim", 0) == 3
+        xs = [logits] if cube else list(logits)
+        if not all(isinstance(x, torch.Tensor) and x.is_cuda for x in xs):
+            raise ValueError("ctc_loss: the logits are device tensors (gradient_batch takes host arrays)")
+        return _ctc_loss_function().apply(self, texts, tokens, reduction, cube, *xs)
 
     # -- serialisation (decoder.py:947-1043): alphabet.json + language_model/ --------------------------
     _ALPHABET_SERIALIZED_FILENAME = "alphabet.json"

@@ -206,6 +206,11 @@ def posteriors_batch_sharded(decoder, logits_list, texts=None, group=None, **kwa
     raise NotImplementedError("posteriors_batch is not gathered over ranks: call decoder.posteriors_batch on each rank's slice itself")
 
 
+def gradient_batch_sharded(decoder, logits_list, texts=None, group=None, **kwargs):
+    """Transcript gradients are not sharded over ranks: each rank calls decoder.gradient_batch on its own slice."""
+    raise NotImplementedError("gradient_batch is not gathered over ranks: call decoder.gradient_batch on each rank's slice itself")
+
+
 def _device_worker(conn, device: int, decoder_dir: str, library: Optional[str]) -> None:
     """One worker process = one GPU (the native library binds one device per process): loads the saved decoder on its device and
     serves (method, logits, kwargs) requests until it is told to stop."""
@@ -340,6 +345,12 @@ class DevicePool:
         raise NotImplementedError("DevicePool does not shard posteriors_batch: call decoder.posteriors_batch on the process's own device")
 
     posteriors = posteriors_batch
+
+    def gradient_batch(self, logits_list, texts=None, **kwargs):
+        """Transcript gradients run on the calling process's own device: a pool does not shard them."""
+        raise NotImplementedError("DevicePool does not shard gradient_batch: call decoder.gradient_batch on the process's own device")
+
+    gradient = gradient_batch
 
     def decode_batch(self, logits_list, **kwargs) -> List[str]:
         if kwargs.get("token_frames") or kwargs.get("confidence") is not None:  # (texts, TokenFrames) per slice -> one of each, offsets rebased

@@ -6,7 +6,8 @@ substituted), each forward kernel forced in turn -- and at 64 utterances, with t
 for scale; then a sweep of target lengths on 256 utterances of random logits, which is what the wave / group threshold of
 ctcdec_score_batch rests on. Kernel times are HIP events on the decode stream (ctcdec_alignment_timing, ctcdec_score_batch,
 ctcdec_posteriors_timing).
-  python tools/align_bench.py [--out profiles/align_bench.txt] [--steps 3] [--legs align,score,posteriors,sweep]
+  python tools/align_bench.py [--out profiles/align_bench.txt] [--steps 3] [--legs align,score,posteriors,sweep,gradient]
+The gradient leg (not in the default set) times gradient_batch -- ctc_grad_rows alone, next to posteriors_batch(dense=False).
 The 4096 utterances are 256 distinct ones repeated: no kernel's time depends on the rows being distinct."""
 import argparse
 import os
@@ -21,6 +22,7 @@ import synth  # noqa: E402
 
 T, V, DISTINCT = 1000, 1024, 256
 HBM_PEAK = 8.0e12  # bytes / s
+PRUNE_RATE = 3.5e12  # bytes / s: what frame_prune reaches on the same logits (README)
 _G = {}
 
 
@@ -100,6 +102,31 @@ def posteriors_lines(dec, dev, targets, steps):
     return ["  posteriors_batch dense=False  ctc_posteriors %9.3f ms in %d launch(es)  (%.2f GB of tables written and read back)  "
             "native call %9.3f ms  Python call %9.3f ms" % (post, launches, table / 1e9, native, wall),
             "    ctc_posteriors / ctc_forward (%.3f ms, one group-kernel hypothesis each) at this batch: %.2f" % (fwd, post / fwd)]
+
+
+def gradient_lines(dec, dev, targets, steps):
+    """gradient_batch on the device tensor (its rows written in place into one device buffer) and posteriors_batch(dense=False)
+    on the same batch, alternating after one warm-up each: ctc_grad_rows alone, the dense ctc_posteriors launches in front of
+    it, and the bytes the row kernel must move -- T * (V * (in + out) + 32 * align_chunks(L)) per utterance -- over its time,
+    against the rate frame_prune reaches on the same logits."""
+    grad, dense, lean, native, wall = [], [], [], [], []
+    for _ in range(steps + 1):
+        dec.posteriors_batch(dev, tokens=targets, dense=False)
+        lean.append(dec.last_posteriors_timing_ms[2])
+        t0 = time.perf_counter()
+        out = dec.gradient_batch(dev, tokens=targets)
+        wall.append((time.perf_counter() - t0) * 1e3)
+        ms = dec.last_gradient_timing_ms
+        dense.append(ms[2]), grad.append(ms[3]), native.append(ms[4])
+    assert all(g.grad.is_cuda and g.grad.shape == (T, V) for g in out)
+    launches = dec.last_gradient_launches
+    del out
+    moved = sum(T * (V * (4 + 4) + 32 * ((2 * len(t) + 1 + 3) // 4)) for t in targets)
+    rate = moved / (med(grad) * 1e-3)
+    return ["  gradient_batch  ctc_grad_rows %9.3f ms  (%.2f GB to move: %.2f TB/s, %.2f of frame_prune's %.1f TB/s)  dense ctc_posteriors "
+            "%9.3f ms  (%d launches of both)  native call %9.3f ms  Python call %9.3f ms"
+            % (med(grad), moved / 1e9, rate / 1e12, rate / PRUNE_RATE, PRUNE_RATE / 1e12, med(dense), launches, med(native), med(wall)),
+            "    ctc_grad_rows / ctc_posteriors dense=False (%.3f ms) at this batch: %.2f" % (med(lean), med(grad) / med(lean))]
 
 
 def time_forward(dec, dev, hyps, kernels, steps):
@@ -234,6 +261,8 @@ def main():
             lines += score_lines(dec, dev, targets, args.steps, vit_ms)
         if "posteriors" in legs:
             lines += posteriors_lines(dec, dev, targets, args.steps)
+        if "gradient" in legs:
+            lines += gradient_lines(dec, dev, targets, args.steps)
         del dev
     if "sweep" in legs:
         lines += sweep_lines(dec, max(args.steps, 5))
