@@ -451,6 +451,49 @@ int ctcdec_gradient_batch(ctcdec_decoder* dec, const void* const* utt_logits, co
                           int32_t grad_dtype, int64_t table_budget, double* logp_out, double* ms5, int32_t* launches,
                           int64_t* launched2);
 
+/* ---- phrase search: does a label sequence occur somewhere in the utterance, where, and how well -------------------------------
+ * No reference analogue. Utterance u owns the phrases [hyp_off[u], hyp_off[u + 1]); phrase h is the label ids
+ * labels[label_off[h] .. label_off[h + 1]) (alphabet indices, never the blank; 1 to 2047 of them). Logits, frame counts,
+ * dtype, is_device, the probabilities-or-logits rule and the per-frame log-probabilities e(t, c) (clipped, float64) are those
+ * of ctcdec_align_batch. The states are that call's, S = 2 L + 1, but only the interior states 1 .. S - 2 exist: an
+ * occurrence begins on a frame of the first label and ends on a frame of the last. Every state exists in every frame and
+ * holds a score d[s] and the frame st[s] its path began on. In frame t state s takes the best of
+ *   stay d[s];  step d[s - 1], s >= 2;  skip d[s - 2], s >= 3, a label that differs from the label before it;
+ *   a fresh start 0.0 begun at t, for s = 1 alone
+ * -- equal scores prefer the earlier in that order --, and adds e(t, label of s); a state with no finite candidate is -inf.
+ * After frame t: end_logp[t] = d[S - 2], end_start[t] = st[S - 2] (-inf / -1): the best occurrence whose last label sits on
+ * frame t. The hits: until max_hits (1 .. 64) are taken or no end frame qualifies, among the end frames t with a finite
+ * end_logp[t] >= min_logp (-inf: no threshold; a NaN is refused) whose window [end_start[t], t] shares no frame with a window
+ * taken before, the one with the largest end_logp, the smallest t on a tie. A hit is (start, end = t + 1, logp), in the order
+ * taken, best first. An end frame whose best window overlaps a hit already taken is dropped, even if a worse window ending
+ * there would not overlap. A phrase with fewer frames than labels plus adjacent equal labels occurs nowhere: no hits, nothing
+ * launched (the host decides; not an error), and an utterance none of whose phrases is launched is neither staged nor
+ * classified nor summed. want_trace != 0 also returns every phrase's end_logp / end_start rows.
+ * kernel: 0 lets the library choose between its two kernels (one wavefront per phrase up to 127 labels, one workgroup above),
+ * 1 prefers the wavefront kernel (longer phrases still take the workgroup kernel), 2 forces the workgroup kernel; both return
+ * the same bits. find / find_batch pass it from the environment variable CTCDEC_FIND_KERNEL=wave|group.
+ * trace_budget: bytes of traces (12 per frame of a launched phrase) one launch may hold, 0 for the default of 1 GiB; a batch
+ * that needs more runs in several launches with the same results. Everything is validated before anything is launched: a
+ * null pointer, offsets that do not start at 0 or decrease, a negative frame count, a label outside the alphabet or equal to
+ * the blank, an empty phrase, max_hits outside 1 .. 64 or a NaN min_logp is CTCDEC_ERR_ARG; more than 2047 labels, or one
+ * phrase whose trace alone exceeds the budget, is CTCDEC_ERR_LIMIT. */
+typedef struct ctcdec_search ctcdec_search; /* opaque */
+int ctcdec_find_batch(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts, int32_t dtype,
+                      int32_t is_device, const int64_t* hyp_off, const int64_t* label_off, const int32_t* labels, int32_t max_hits,
+                      double min_logp, int32_t want_trace, int32_t kernel, int64_t trace_budget, ctcdec_search** out);
+/* Phrase h's hits are [hit_off[h], hit_off[h + 1]) of start / end / logp (its hit count: the difference), best first.
+ * Pointers stay valid until ctcdec_search_free. */
+int ctcdec_search_hits(const ctcdec_search* s, const int64_t** hit_off, const int32_t** start, const int32_t** end,
+                       const double** logp, int64_t* n_phrases);
+/* Phrase h's trace is [trace_off[h], trace_off[h + 1]) of end_logp / end_start, one entry per frame of its utterance (-inf /
+ * -1 throughout for a phrase that was not launched). Both are NULL, and trace_off all 0, when want_trace was 0. */
+int ctcdec_search_trace(const ctcdec_search* s, const int64_t** trace_off, const double** end_logp, const int32_t** end_start);
+/* milliseconds: [0] the classification (frame-prune kernels), [1] row_lse, [2] the find kernels (HIP events on the decode
+ * stream, summed over the launches), [3] the whole native call; launches: kernel launches made (may be NULL); launched2 (may
+ * be NULL): phrases that went to [0] the wavefront kernel, [1] the workgroup kernel */
+int ctcdec_search_timing(const ctcdec_search* s, double* ms4, int32_t* launches, int64_t* launched2);
+void ctcdec_search_free(ctcdec_search* s);
+
 /* timing of the last call's device stages in milliseconds (HIP events on the decode stream):
  * [0] frame-prune kernel, [1] beam kernel, [2] total device time incl. result copy */
 int ctcdec_result_timing(const ctcdec_result* r, double* ms3);

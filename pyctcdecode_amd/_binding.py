@@ -170,6 +170,15 @@ _PROTOS = {
                                         C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(_VP), C.c_int32, C.c_int64,
                                         C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32),
                                         C.POINTER(C.c_int64)]),
+    "ctcdec_find_batch": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32,
+                                    C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int32, C.c_double,
+                                    C.c_int32, C.c_int32, C.c_int64, C.POINTER(_VP)]),
+    "ctcdec_search_hits": (C.c_int, [_VP, C.POINTER(C.POINTER(C.c_int64)), C.POINTER(C.POINTER(C.c_int32)),
+                                     C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.c_int64)]),
+    "ctcdec_search_trace": (C.c_int, [_VP, C.POINTER(C.POINTER(C.c_int64)), C.POINTER(C.POINTER(C.c_double)),
+                                      C.POINTER(C.POINTER(C.c_int32))]),
+    "ctcdec_search_timing": (C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "ctcdec_search_free": (None, [_VP]),
     "ctcdec_result_timing": (C.c_int, [_VP, C.POINTER(C.c_double)]),
     "ctcdec_result_beam_kernel": (C.c_int, [_VP]),
     "ctcdec_device": (C.c_int, []),

@@ -217,6 +217,8 @@ struct ctcdec_decoder {
   // transcript gradient (ctcdec_gradient_batch): the labels' occurrence lists, a launch's row records and, for host callers,
   // its gradient rows (tables, labels and scores: the posteriors')
   DevBuf w_gocc, w_gutts, w_grad;
+  // phrase search (ctcdec_find_batch): a launch's traces and phrase records, the call's hits (labels: w_alab)
+  DevBuf w_ftrace, w_fphr, w_fhits;
   bool slicing = false;  // a time-sliced host ingest is under way (decode_host_sliced): the prune stage notes each slice's side of 1
   uint32_t max_label_bytes = 1;
   bool arenas_worst_case = false;  // a call has outgrown the usual reservation of the node arenas: reserve the worst case from now on
@@ -2566,9 +2568,11 @@ void ctcdec_alignment_free(ctcdec_alignment* a) { delete a; }
 }  // extern "C"
 
 // Everything ctcdec_score_batch indexes with comes from the caller: checked here, in the order in which one array bounds the
-// next, before anything moves. need[h]: labels plus adjacent equal labels of hypothesis h.
+// next, before anything moves. need[h]: labels plus adjacent equal labels of hypothesis h. (ctcdec_find_batch checks its
+// phrases with it too: `item` is what a message calls an entry.)
 static int check_scores(const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts, const int32_t* targets,
-                        const int64_t* target_off, const int64_t* hyp_off, int V, int blank, std::vector<int32_t>& need) {
+                        const int64_t* target_off, const int64_t* hyp_off, int V, int blank, std::vector<int32_t>& need,
+                        const char* item = "hypothesis") {
   if (hyp_off[0] != 0) return fail(CTCDEC_ERR_ARG, "hyp_off must start at 0");
   for (int32_t u = 0; u < n_utts; ++u) {
     if (hyp_off[u + 1] < hyp_off[u]) return fail(CTCDEC_ERR_ARG, "hyp_off must not decrease");
@@ -2576,12 +2580,12 @@ static int check_scores(const void* const* utt_logits, const int32_t* utt_frames
     if (utt_frames[u] > 0 && !utt_logits[u]) return fail(CTCDEC_ERR_ARG, "utterance " + std::to_string(u) + ": no logits");
   }
   const int64_t NH = hyp_off[n_utts];
-  if (NH > (int64_t)0x7FFFFFFF) return fail(CTCDEC_ERR_LIMIT, "more than 2^31 - 1 hypotheses in one call");
+  if (NH > (int64_t)0x7FFFFFFF) return fail(CTCDEC_ERR_LIMIT, "more than 2^31 - 1 entries of hyp_off in one call");
   if (target_off[0] != 0) return fail(CTCDEC_ERR_ARG, "target_off must start at 0");
   need.assign((size_t)NH, 0);
   for (int32_t u = 0; u < n_utts; ++u)
     for (int64_t h = hyp_off[u]; h < hyp_off[u + 1]; ++h) {
-      const std::string who = "utterance " + std::to_string(u) + ", hypothesis " + std::to_string(h - hyp_off[u]);
+      const std::string who = "utterance " + std::to_string(u) + ", " + item + " " + std::to_string(h - hyp_off[u]);
       const int64_t L = target_off[h + 1] - target_off[h];
       if (L < 0) return fail(CTCDEC_ERR_ARG, "target_off must not decrease");
       if (L > ALIGN_MAX_LABELS)
@@ -3130,6 +3134,271 @@ int ctcdec_gradient_batch(ctcdec_decoder* dec, const void* const* utt_logits, co
   if (launched2) launched2[0] = launched[0], launched2[1] = launched[1];
   return CTCDEC_OK;
 }
+
+// ---- phrase search ("Phrase search") ---------------------------------------------------------------------------------
+}  // extern "C"
+
+struct ctcdec_search {
+  std::vector<int64_t> hit_off, trace_off;
+  std::vector<int32_t> start, end, end_start;
+  std::vector<double> logp, end_logp;
+  bool has_trace = false;
+  int32_t launches = 0;
+  int64_t launched[2] = {0, 0};
+  double ms[4] = {0, 0, 0, 0};
+};
+
+// A launched phrase's trace: a float64 end_logp and an int32 end_start per frame. The traces of one launch come under the
+// budget of the alignment's back-pointer tables (ALIGN_BP_BUDGET) when the caller names none.
+static const int64_t FIND_TRACE_BYTES = 12;
+
+#ifdef CTC_SIM
+namespace {
+// (ctc_find_phrase: the one thread owns every group and is the whole "wavefront" of the selection)
+struct FindSeqCtx {
+  enum { GROUPS = FORWARD_MAX_GROUPS };
+  int tid = 0, nt = 1;
+  int32_t hs[FIND_MAX_HITS], he[FIND_MAX_HITS];
+  void sync() {}
+  bool same_wave(int) const { return true; }
+  void publish() const {}
+  int lane() const { return 0; }
+  int lanes() const { return 1; }
+  bool any(bool b) const { return b; }
+  void best(double&, int&, int&) const {}
+  void put(int j, int32_t s, int32_t e) { hs[j] = s, he[j] = e; }
+  void get(int j, int32_t* s, int32_t* e) const { *s = hs[j], *e = he[j]; }
+};
+static_assert(FORWARD_MAX_GROUPS >= find_chunks(ALIGN_MAX_LABELS), "a group per four states of the longest phrase");
+}  // namespace
+#endif
+
+extern "C" {
+
+int ctcdec_find_batch(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts, int32_t dtype,
+                      int32_t is_device, const int64_t* hyp_off, const int64_t* label_off, const int32_t* labels, int32_t max_hits,
+                      double min_logp, int32_t want_trace, int32_t kernel, int64_t trace_budget, ctcdec_search** out) {
+  if (!dec || !out || n_utts < 0 || !label_off || !hyp_off || trace_budget < 0 || (n_utts > 0 && (!utt_logits || !utt_frames)))
+    return fail(CTCDEC_ERR_ARG, "bad arguments");
+  if (dtype < CTCDEC_F32 || dtype > CTCDEC_BF16) return fail(CTCDEC_ERR_ARG, "dtype must be f32, f64, f16 or bf16");
+  if (kernel < 0 || kernel > 2) return fail(CTCDEC_ERR_ARG, "kernel must be 0 (the library chooses), 1 (wave) or 2 (group)");
+  if (max_hits < 1 || max_hits > FIND_MAX_HITS) return fail(CTCDEC_ERR_ARG, "max_hits must be in 1 .. " + std::to_string(FIND_MAX_HITS));
+  if (min_logp != min_logp) return fail(CTCDEC_ERR_ARG, "min_logp is not a number");
+  const int V = (int)dec->alpha.labels.size();
+  int blank = -1;
+  for (int v = 0; v < V && blank < 0; ++v)
+    if (dec->alpha.labels[(size_t)v].empty()) blank = v;
+  if (blank < 0) return fail(CTCDEC_ERR_ARG, "the alphabet has no blank label");
+  std::vector<int32_t> need;
+  if (int rc = check_scores(utt_logits, utt_frames, n_utts, labels, label_off, hyp_off, V, blank, need, "phrase")) return rc;
+  const size_t n = (size_t)n_utts;
+  const int64_t NH = hyp_off[n];
+  const int64_t budget = trace_budget ? trace_budget : ALIGN_BP_BUDGET;
+  for (int32_t u = 0; u < n_utts; ++u)
+    for (int64_t h = hyp_off[u]; h < hyp_off[u + 1]; ++h) {
+      const std::string who = "utterance " + std::to_string(u) + ", phrase " + std::to_string(h - hyp_off[u]);
+      if (label_off[h + 1] == label_off[h]) return fail(CTCDEC_ERR_ARG, who + ": an empty phrase occurs everywhere and nowhere");
+      if (utt_frames[u] >= need[(size_t)h] && FIND_TRACE_BYTES * utt_frames[u] > budget)
+        return fail(CTCDEC_ERR_LIMIT, who + ": a trace of " + std::to_string(FIND_TRACE_BYTES * utt_frames[u]) +
+                                          " bytes, above the budget of " + std::to_string(budget) + " bytes for one launch");
+    }
+  const auto t_begin = Clock::now();
+  std::unique_ptr<ctcdec_search> res(new ctcdec_search());
+  res->has_trace = want_trace != 0;
+  // A phrase with fewer frames than labels plus adjacent equal labels occurs nowhere: no hits, decided here. Everything else
+  // goes to a kernel: the wave kernel up to its limit (unless the group kernel is forced), the group kernel above it.
+  const int32_t wave_max = kernel == 2 ? -1 : FIND_WAVE_MAX_LABELS;
+  std::vector<int32_t> utt_of((size_t)NH);
+  std::vector<int32_t> run;  // the phrases that are launched, in input order
+  res->trace_off.assign((size_t)NH + 1, 0);
+  for (int32_t u = 0; u < n_utts; ++u)
+    for (int64_t h = hyp_off[u]; h < hyp_off[u + 1]; ++h) {
+      utt_of[(size_t)h] = u;
+      if (utt_frames[u] >= need[(size_t)h]) run.push_back((int32_t)h);
+      res->trace_off[(size_t)h + 1] = res->trace_off[(size_t)h] + (want_trace ? utt_frames[u] : 0);
+    }
+  if (want_trace) {  // (a phrase that is not launched ends nowhere)
+    res->end_logp.assign((size_t)res->trace_off[(size_t)NH], align_neg_inf());
+    res->end_start.assign((size_t)res->trace_off[(size_t)NH], -1);
+  }
+  std::vector<int32_t> n_hits((size_t)NH, 0), h_start, h_end;
+  std::vector<double> h_logp;
+  const size_t K = (size_t)max_hits;
+  if (!run.empty()) {
+    // (an utterance none of whose phrases is launched takes no part: nothing of it is staged, classified or summed)
+    std::vector<int32_t> use_frames(n, 0);
+    for (int32_t h : run) use_frames[(size_t)utt_of[(size_t)h]] = utt_frames[utt_of[(size_t)h]];
+    std::vector<int64_t> row0(n + 1, 0);
+    for (size_t u = 0; u < n; ++u) row0[u + 1] = row0[u] + use_frames[u];
+    const int64_t NL = label_off[NH];
+    std::string err;
+    std::lock_guard<std::mutex> device_lock(g_device_mu);
+    if (be::bind_thread(&err)) return fail(CTCDEC_ERR_DEVICE, err);
+    AlignFront fr;
+    if (int rc = align_front(dec, utt_logits, use_frames.data(), n_utts, dtype, is_device, V, row0, fr)) return rc;
+    res->ms[0] = fr.sniff_ms;
+    // the call's hits: per phrase max_hits scores, then as many starts and ends, then the counts
+    const size_t hits_bytes = (size_t)NH * K * 16 + (size_t)NH * 4;
+    if (dec->w_alab.ensure((size_t)NL * 4, &err) || dec->w_fhits.ensure(hits_bytes, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+    if (be::h2d(dec->w_alab.p, labels, (size_t)NL * 4, &err) || be::zero(dec->w_fhits.p, hits_bytes, &err))
+      return fail(CTCDEC_ERR_DEVICE, err);
+    double* const d_logp = (double*)dec->w_fhits.p;
+    int32_t* const d_start = (int32_t*)(d_logp + (size_t)NH * K);
+    int32_t* const d_end = d_start + (size_t)NH * K;
+    int32_t* const d_count = d_end + (size_t)NH * K;
+    // launches: phrases in input order until their traces fill the budget (ctcdec_align_batch's rule)
+    std::vector<std::vector<int32_t>> groups;
+    int64_t used = 0, most = 0;
+    for (int32_t h : run) {
+      const int64_t bytes = FIND_TRACE_BYTES * utt_frames[utt_of[(size_t)h]];
+      if (groups.empty() || used + bytes > budget) {
+        groups.emplace_back();
+        used = 0;
+      }
+      groups.back().push_back(h);
+      used += bytes;
+      most = std::max(most, used);
+    }
+    if (dec->w_ftrace.ensure((size_t)most, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+    const double clip_lo = log(1e-15);  // ln(MIN_TOKEN_CLIP_P) (constants.py:17)
+    std::vector<FindPhrase> phrases;
+    std::vector<double> t_logp;
+    std::vector<int32_t> t_start;
+    for (auto& g : groups) {
+      // inside a launch the wave kernel's phrases come before the group kernel's, longest utterance first in each; the scores
+      // of the launch's traces lie before its start frames, each in that order
+      std::stable_sort(g.begin(), g.end(), [&](int32_t a, int32_t b) {
+        const bool wa = label_off[a + 1] - label_off[a] <= wave_max, wb = label_off[b + 1] - label_off[b] <= wave_max;
+        return wa != wb ? wa : utt_frames[utt_of[(size_t)a]] > utt_frames[utt_of[(size_t)b]];
+      });
+      int64_t frames = 0;
+      for (int32_t h : g) frames += utt_frames[utt_of[(size_t)h]];
+      double* const tr_logp = (double*)dec->w_ftrace.p;
+      int32_t* const tr_start = (int32_t*)(tr_logp + frames);
+      phrases.clear();
+      int32_t count[2] = {0, 0}, max_chunks[2] = {1, 1};
+      int64_t off = 0;
+      for (int32_t h : g) {
+        const int32_t u = utt_of[(size_t)h];
+        FindPhrase a;
+        a.x = fr.ptrs[(size_t)u];
+        a.lse = fr.lse + row0[(size_t)u];
+        a.lab = (const int32_t*)dec->w_alab.p + label_off[h];
+        a.end_logp = tr_logp + off;
+        a.end_start = tr_start + off;
+        a.hit_logp = d_logp + (size_t)h * K;
+        a.hit_start = d_start + (size_t)h * K;
+        a.hit_end = d_end + (size_t)h * K;
+        a.n_hits = d_count + h;
+        a.T = utt_frames[u];
+        a.L = (int32_t)(label_off[h + 1] - label_off[h]);
+        a.is_prob = fr.is_prob[(size_t)u] ? 1 : 0;
+        a.pad = 0;
+        phrases.push_back(a);
+        off += a.T;
+        const int w = a.L <= wave_max ? 0 : 1;
+        max_chunks[w] = std::max(max_chunks[w], find_chunks(a.L));
+        ++count[w];
+      }
+#ifdef CTC_SIM  // (both kernels are the one body here: a single thread owns every group)
+      std::vector<double> col((size_t)3 * (size_t)std::max(max_chunks[0], max_chunks[1]));
+      FindSeqCtx cx;
+      for (const FindPhrase& a : phrases) {
+        if (dtype == 0) ctc_find_phrase<0>(cx, a, V, blank, clip_lo, max_hits, min_logp, col.data());
+        else if (dtype == 1) ctc_find_phrase<1>(cx, a, V, blank, clip_lo, max_hits, min_logp, col.data());
+        else if (dtype == 2) ctc_find_phrase<2>(cx, a, V, blank, clip_lo, max_hits, min_logp, col.data());
+        else ctc_find_phrase<3>(cx, a, V, blank, clip_lo, max_hits, min_logp, col.data());
+      }
+      for (int w = 0; w < 2; ++w) res->launches += count[w] ? 1 : 0;
+#else
+      if (upload(dec->w_fphr, phrases, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+      for (int w = 0; w < 2; ++w) {
+        if (!count[w]) continue;
+        be::FindArgs fa;
+        fa.phrases = (const FindPhrase*)dec->w_fphr.p + (w ? count[0] : 0);
+        fa.n_phrases = count[w];
+        fa.n_labels = V;
+        fa.dtype = dtype;
+        fa.blank = blank;
+        fa.max_chunks = max_chunks[w];
+        fa.max_hits = max_hits;
+        fa.clip_lo = clip_lo;
+        fa.min_logp = min_logp;
+        if (be::launch_ctc_find(fa, w == 0, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+        ++res->launches;
+      }
+#endif
+      res->launched[0] += count[0];
+      res->launched[1] += count[1];
+      if (want_trace) {  // a launch's traces leave with it: the next one takes the workspace over
+        t_logp.resize((size_t)frames);
+        t_start.resize((size_t)frames);
+        if (be::d2h(t_logp.data(), tr_logp, (size_t)frames * 8, &err) || be::d2h(t_start.data(), tr_start, (size_t)frames * 4, &err))
+          return fail(CTCDEC_ERR_DEVICE, err);
+        off = 0;
+        for (int32_t h : g) {
+          const size_t T = (size_t)utt_frames[utt_of[(size_t)h]];
+          std::copy(t_logp.begin() + off, t_logp.begin() + off + (int64_t)T, res->end_logp.begin() + res->trace_off[(size_t)h]);
+          std::copy(t_start.begin() + off, t_start.begin() + off + (int64_t)T, res->end_start.begin() + res->trace_off[(size_t)h]);
+          off += (int64_t)T;
+        }
+      }
+    }
+    h_logp.resize((size_t)NH * K);
+    h_start.resize((size_t)NH * K);
+    h_end.resize((size_t)NH * K);
+    if (be::d2h(h_logp.data(), d_logp, (size_t)NH * K * 8, &err) || be::d2h(h_start.data(), d_start, (size_t)NH * K * 4, &err) ||
+        be::d2h(h_end.data(), d_end, (size_t)NH * K * 4, &err) || be::d2h(n_hits.data(), d_count, (size_t)NH * 4, &err))
+      return fail(CTCDEC_ERR_DEVICE, err);
+#ifndef CTC_SIM
+    double vit_ms = 0;
+    be::align_timing(&res->ms[1], &vit_ms);
+    res->ms[2] = be::find_timing();
+#endif
+  }
+  res->hit_off.assign((size_t)NH + 1, 0);
+  for (size_t h = 0; h < (size_t)NH; ++h) {
+    if (n_hits[h] < 0 || n_hits[h] > max_hits) return fail(CTCDEC_ERR_DEVICE, "ctc_find returned a hit count outside 0 .. max_hits");
+    res->hit_off[h + 1] = res->hit_off[h] + n_hits[h];
+    for (size_t j = 0; j < (size_t)n_hits[h]; ++j) {
+      res->start.push_back(h_start[h * K + j]);
+      res->end.push_back(h_end[h * K + j]);
+      res->logp.push_back(h_logp[h * K + j]);
+    }
+  }
+  res->ms[3] = ms(t_begin, Clock::now());
+  *out = res.release();
+  return CTCDEC_OK;
+}
+
+int ctcdec_search_hits(const ctcdec_search* s, const int64_t** hit_off_out, const int32_t** start_out, const int32_t** end_out,
+                       const double** logp_out, int64_t* n_phrases_out) {
+  if (!s || !hit_off_out || !start_out || !end_out || !logp_out || !n_phrases_out) return fail(CTCDEC_ERR_ARG, "no search");
+  *hit_off_out = s->hit_off.data();
+  *start_out = s->start.data();
+  *end_out = s->end.data();
+  *logp_out = s->logp.data();
+  *n_phrases_out = (int64_t)s->hit_off.size() - 1;
+  return CTCDEC_OK;
+}
+
+int ctcdec_search_trace(const ctcdec_search* s, const int64_t** trace_off_out, const double** end_logp_out, const int32_t** end_start_out) {
+  if (!s || !trace_off_out || !end_logp_out || !end_start_out) return fail(CTCDEC_ERR_ARG, "no search");
+  *trace_off_out = s->trace_off.data();
+  *end_logp_out = s->has_trace ? s->end_logp.data() : nullptr;
+  *end_start_out = s->has_trace ? s->end_start.data() : nullptr;
+  return CTCDEC_OK;
+}
+
+int ctcdec_search_timing(const ctcdec_search* s, double* ms4, int32_t* launches_out, int64_t* launched2) {
+  if (!s || !ms4) return fail(CTCDEC_ERR_ARG, "no search");
+  for (int k = 0; k < 4; ++k) ms4[k] = s->ms[k];
+  if (launches_out) *launches_out = s->launches;
+  if (launched2) launched2[0] = s->launched[0], launched2[1] = s->launched[1];
+  return CTCDEC_OK;
+}
+
+void ctcdec_search_free(ctcdec_search* s) { delete s; }
 
 // a texts-only result (params.texts_only) as ordinary beams, for the accessors that want them
 static void materialise(const ctcdec_result* cr) {

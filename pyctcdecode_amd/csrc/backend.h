@@ -283,13 +283,28 @@ struct GradRowsArgs {
   double clip_lo;      // ln(MIN_TOKEN_CLIP_P)
 };
 int launch_ctc_grad_rows(const GradRowsArgs& a, std::string* err);
+// ctc_find (wave == 0: one workgroup per entry of `phrases`) / ctc_find_wave (wave != 0: one wavefront per entry, every
+// L <= FIND_WAVE_MAX_LABELS), all entries validated by the host (FindPhrase)
+struct FindArgs {
+  const FindPhrase* phrases;  // [n_phrases] (device)
+  int32_t n_phrases;
+  int32_t n_labels;
+  int32_t dtype;
+  int32_t blank;
+  int32_t max_chunks;  // the largest find_chunks(L) of the launch: sizes ctc_find's two columns in LDS
+  int32_t max_hits;    // 1 .. FIND_MAX_HITS
+  double clip_lo;      // ln(MIN_TOKEN_CLIP_P)
+  double min_logp;     // a hit's least score (-inf: none)
+};
+int launch_ctc_find(const FindArgs& a, int wave, std::string* err);
 // kernel times (HIP events) of the launch_row_lse / launch_ctc_viterbi / launch_ctc_forward / launch_ctc_posteriors /
-// launch_ctc_grad_rows calls since the last reset; waits for the kernels
+// launch_ctc_grad_rows / launch_ctc_find calls since the last reset; waits for the kernels
 void align_timing_reset();
 void align_timing(double* row_lse_ms, double* viterbi_ms);
 double forward_timing();
 double posteriors_timing();
 double grad_rows_timing();
+double find_timing();
 
 // stage timing (ms) of the last launch_prune / launch_beam pair, measured on the decode stream
 void last_timing(double* prune_ms, double* beam_ms);

@@ -2367,6 +2367,8 @@ int launch_ctc_posteriors_on(const PosteriorsArgs& a, hipStream_t stream, std::s
 int launch_ctc_posteriors(const PosteriorsArgs& a, std::string* err) { return launch_ctc_posteriors_on(a, g_stream, err); }
 int launch_ctc_grad_rows_on(const GradRowsArgs& a, hipStream_t stream, std::string* err);
 int launch_ctc_grad_rows(const GradRowsArgs& a, std::string* err) { return launch_ctc_grad_rows_on(a, g_stream, err); }
+int launch_ctc_find_on(const FindArgs& a, int wave, hipStream_t stream, std::string* err);
+int launch_ctc_find(const FindArgs& a, int wave, std::string* err) { return launch_ctc_find_on(a, wave, g_stream, err); }
 int launch_row_lse(const RowLseArgs& a, std::string* err) { return launch_row_lse_on(a, g_stream, err); }
 int launch_ctc_viterbi(const ViterbiArgs& a, std::string* err) { return launch_ctc_viterbi_on(a, g_stream, err); }
 

@@ -4,9 +4,10 @@
 // forward recursion over the same states, the sum over all alignments where the Viterbi takes the best one; and the frame
 // posteriors of a label sequence ("Frame posteriors"): the forward-backward over the same states; and the gradient
 // of the likelihood with respect to the frames' entries ("Transcript gradient"): the posteriors folded by label,
-// row by row. One body each for the HIP kernels (ctc_align_hip.hip: row_lse, ctc_viterbi, ctc_forward, ctc_forward_wave,
-// ctc_posteriors, ctc_grad_rows) and for the CPU simulator build, whose "device" memory is host memory (api.cpp under CTC_SIM
-// runs them with a one-thread context).
+// row by row; and the search for a phrase inside an utterance ("Phrase search"): the Viterbi recursion with a free
+// start and a free end, and the selection of its hits. One body each for the HIP kernels (ctc_align_hip.hip: row_lse,
+// ctc_viterbi, ctc_forward, ctc_forward_wave, ctc_posteriors, ctc_grad_rows, ctc_find, ctc_find_wave) and for the CPU simulator
+// build, whose "device" memory is host memory (api.cpp under CTC_SIM runs them with a one-thread context).
 #pragma once
 #include <math.h>
 #include <stddef.h>
@@ -817,6 +818,255 @@ CTC_HD void ctc_grad_row(Ctx& cx, const GradUtt& u, int t, int V, int blank, dou
     const double sh = grad_share(u, gamma, v, blank, g_blank, x, lse, clip_lo, lo, hi);
     out[v] = (GT)(is_prob ? sh : sh - exp(x - lse) * M);
   }
+}
+
+// ---- ctc_find / ctc_find_wave -----------------------------------------------------------------------------------------------
+// Where a phrase occurs in an utterance, and how well ("Phrase search"): the Viterbi recursion over the states of
+// ctc_viterbi with a free start and a free end. Only the interior states 1 .. S - 2 exist -- an occurrence begins on a frame
+// of the first label and ends on a frame of the last --, every one of them in every frame, and each carries the frame its
+// path began on along with its score: d[s], st[s]. In frame t state s takes the best of stay (d[s]), step (d[s-1], s >= 2),
+// skip (d[s-2], s >= 3, a label that differs from the label before it) and, for s = 1 alone, a fresh start (0.0, begun at
+// t), equal scores preferring the earlier in that order, and adds emit(t, s); a state without a finite candidate is -inf.
+// After frame t the trace holds end_logp[t] = d[S-2] and end_start[t] = st[S-2] (-inf / -1): the best occurrence whose last
+// label sits on frame t. One phrase of a launch; the host validates every field before a launch (T >= L + repeats, L >= 1).
+struct FindPhrase {
+  const void* x;        // [T, V] logits or probabilities of the phrase's utterance, of the launch's dtype
+  const double* lse;    // [T] log-sum-exp of each row (not read when is_prob)
+  const int32_t* lab;   // [L] the labels searched for
+  double* end_logp;     // [T] out: the trace's scores
+  int32_t* end_start;   // [T] out: the trace's start frames
+  double* hit_logp;     // [max_hits] out
+  int32_t* hit_start;   // [max_hits] out
+  int32_t* hit_end;     // [max_hits] out: one past the hit's last frame
+  int32_t* n_hits;      // [1] out
+  int32_t T, L, is_prob, pad;
+};
+
+constexpr int32_t FIND_MAX_HITS = 64;          // a wavefront keeps the windows taken so far one to a lane
+constexpr int32_t FIND_WAVE_MAX_LABELS = 127;  // ctc_find_wave: 2L - 1 <= 253 interior states, four to each of a wave's 64 lanes
+CTC_HD constexpr int32_t find_chunks(int32_t L) { return (L + 1) >> 1; }  // groups of four states that hold an interior state
+
+// One frame of one group (blank, label 2c, blank, label 2c + 1: ForwardGroup), in place: d / st the group's scores and start
+// frames at the frame before, dm1 / sm1 those of the last state of the group below. `first`: the group holds state 1, the only
+// one a path may begin in; its state 0 does not exist. Nothing but compares and additions: the same operands give the same
+// bits wherever this is inlined.
+CTC_HD void find_step(const ForwardGroup& g, bool first, int t, double dm1, int32_t sm1, double e_blank, double e0, double e1,
+                      double* d, int32_t* st) {
+  const double NEG = align_neg_inf();
+  const double d0 = d[0], d1 = d[1], d2 = d[2], d3 = d[3];
+  const int32_t s0 = st[0], s1 = st[1], s2 = st[2], s3 = st[3];
+  double b;
+  int32_t bs;
+  // blank 4c: stay / step
+  b = d0, bs = s0;
+  if (dm1 > b) b = dm1, bs = sm1;
+  d[0] = !first && g.l0 >= 0 ? b + e_blank : NEG;
+  st[0] = bs;
+  // label 2c: stay / step / skip / a fresh start
+  b = d1, bs = s1;
+  if (d0 > b) b = d0, bs = s0;
+  if (g.skip0 && dm1 > b) b = dm1, bs = sm1;
+  if (first && 0.0 > b) b = 0.0, bs = t;
+  d[1] = g.l0 >= 0 ? b + e0 : NEG;
+  st[1] = bs;
+  // blank 4c + 2 (interior when label 2c + 1 exists): stay / step
+  b = d2, bs = s2;
+  if (d1 > b) b = d1, bs = s1;
+  d[2] = g.l1 >= 0 ? b + e_blank : NEG;
+  st[2] = bs;
+  // label 2c + 1: stay / step / skip
+  b = d3, bs = s3;
+  if (d2 > b) b = d2, bs = s2;
+  if (g.skip1 && d1 > b) b = d1, bs = s1;
+  d[3] = g.l1 >= 0 ? b + e1 : NEG;
+  st[3] = bs;
+}
+
+// The selection, by one wavefront over the trace it wrote itself: until max_hits are taken or no end frame qualifies, the
+// end frame t with the largest finite end_logp[t] >= min_logp whose window [end_start[t], t] shares no frame with a window
+// taken before, the smallest such t on a tie. A hit is (start, end = t + 1, logp), best first. An end frame whose best
+// window overlaps a taken one is dropped, even if a worse window ending there would not.
+// cx: lane(), lanes(); any(b): b in some lane; best(v, t, s): the largest v over the lanes, the smallest t among equals, with
+// its s, in every lane; put(j, s, e) / get(j, &s, &e): the j-th window taken (j < FIND_MAX_HITS). Every lane runs every
+// call of cx together: the loops' bounds are the same in all of them.
+template <class Ctx>
+CTC_HD void find_select(Ctx& cx, const FindPhrase& ph, int max_hits, double min_logp) {
+  const double NEG = align_neg_inf();
+  const int T = ph.T, lane = cx.lane(), nl = cx.lanes();
+  const double* const end_logp = ph.end_logp;
+  const int32_t* const end_start = ph.end_start;
+  int n = 0;
+  for (; n < max_hits; ++n) {
+    double bv = NEG;
+    int bt = 0x7FFFFFFF, bs = -1;
+    for (int t0 = 0; t0 < T; t0 += nl) {
+      const int t = t0 + lane;
+      const double v = t < T ? end_logp[t] : NEG;
+      const int s = t < T ? end_start[t] : -1;
+      // (a lane meets its frames in ascending order: an equal score keeps the smaller t)
+      bool cand = v > NEG && v >= min_logp && v > bv;
+      if (!cx.any(cand)) continue;
+      for (int j = 0; j < n; ++j) {
+        int hs, he;
+        cx.get(j, &hs, &he);
+        if (s < he && hs <= t) cand = false;
+      }
+      if (cand) bv = v, bt = t, bs = s;
+    }
+    cx.best(bv, bt, bs);
+    if (bt == 0x7FFFFFFF) break;
+    cx.put(n, bs, bt + 1);
+    if (lane == 0) ph.hit_logp[n] = bv, ph.hit_start[n] = bs, ph.hit_end[n] = bt + 1;
+  }
+  if (lane == 0) *ph.n_hits = n;
+}
+
+// ctc_find: the threads of cx (tid, nt, sync(); Ctx::GROUPS * nt >= find_chunks(L)) share one phrase of a matrix of dtype DT,
+// arranged as ctc_forward_hyp is: thread tid owns the groups tid, tid + nt, ... for the whole recursion, their scores and
+// start frames stay in registers, and only a group's last state goes through `col` -- 2 * find_chunks(L) doubles, then as many
+// int32: the columns of two successive frames -- to the thread that owns the group above: one barrier per frame. Frame
+// t + 1's entries are requested before frame t's arithmetic and kept as loaded. The thread that owns state S - 2 writes the
+// trace; after the last frame its wavefront alone (cx.same_wave, after cx.publish) selects the hits from what it wrote.
+template <int DT, class Ctx>
+CTC_HD void ctc_find_phrase(Ctx& cx, const FindPhrase& ph, int V, int blank, double clip_lo, int max_hits, double min_logp, double* col) {
+  typedef typename AlignRaw<DT>::type Raw;
+  constexpr int G = Ctx::GROUPS;
+  const void* const x = ph.x;  // (the record, once: the frame loop reads none of it again)
+  const double* const lse = ph.lse;
+  const int32_t* const lab = ph.lab;
+  double* const end_logp = ph.end_logp;
+  int32_t* const end_start = ph.end_start;
+  const int T = ph.T, L = ph.L;
+  const bool is_prob = ph.is_prob != 0;
+  if (T <= 0 || L <= 0) return;
+  const int nch = find_chunks(L);
+  const int cf = (2 * L - 1) >> 2, jf = (2 * L - 1) & 3;  // state S - 2, the last label: entry 1 or 3 of its group
+  const double NEG = align_neg_inf();
+  double* const col_d = col;
+  int32_t* const col_s = (int32_t*)(col + 2 * nch);
+  ForwardGroup g[G];
+  int i0[G], i1[G];  // the columns a group's two labels read (the blank's where the phrase ends before them)
+  double d[G][4];    // scores
+  int32_t st[G][4];  // start frames
+  Raw v0[G], v1[G];  // the entries of the frame in hand at those columns, as loaded
+  CTC_UNROLL
+  for (int k = 0; k < G; ++k) {
+    const int c = cx.tid + k * cx.nt;
+    d[k][0] = d[k][1] = d[k][2] = d[k][3] = NEG;
+    st[k][0] = st[k][1] = st[k][2] = st[k][3] = -1;
+    if (c < nch) g[k] = forward_group(lab, L, c);
+    else g[k] = ForwardGroup{-1, -1, false, false, false};
+    i0[k] = g[k].l0 >= 0 ? g[k].l0 : blank;
+    i1[k] = g[k].l1 >= 0 ? g[k].l1 : blank;
+  }
+  // (always 0, but per thread as far as the compiler knows: a row's log-sum-exp then comes by a vector load, as in ctc_forward_hyp)
+  const int per_thread_zero = g[0].l0 == -2 ? 1 : 0;
+  const double* const lse_v = lse + per_thread_zero;
+  for (int i = cx.tid; i < 2 * nch; i += cx.nt) col_d[i] = NEG, col_s[i] = -1;
+  cx.sync();
+  Raw vb = align_load_raw<DT>(x, (size_t)blank);
+  double lse_t = lse_v[0];
+  CTC_UNROLL
+  for (int k = 0; k < G; ++k) {
+    v0[k] = align_load_raw<DT>(x, (size_t)i0[k]);
+    v1[k] = align_load_raw<DT>(x, (size_t)i1[k]);
+  }
+  for (int t = 0; t < T; ++t) {
+    const int po = ((t + 1) & 1) * nch, co = (t & 1) * nch;
+    double dm1[G];
+    int32_t sm1[G];
+    CTC_UNROLL
+    for (int k = 0; k < G; ++k) {
+      const int c = cx.tid + k * cx.nt;
+      dm1[k] = c > 0 && c < nch ? col_d[po + c - 1] : NEG;
+      sm1[k] = c > 0 && c < nch ? col_s[po + c - 1] : -1;
+    }
+    // then ask for frame t + 1 (after the last frame: the last frame again)
+    const int tn = t + 1 < T ? t + 1 : t;
+    const size_t row = (size_t)tn * (size_t)V;
+    const Raw nvb = align_load_raw<DT>(x, row + (size_t)blank);
+    const double nlse = lse_v[tn];
+    Raw n0[G], n1[G];
+    CTC_UNROLL
+    for (int k = 0; k < G; ++k) {
+      n0[k] = align_load_raw<DT>(x, row + (size_t)i0[k]);
+      n1[k] = align_load_raw<DT>(x, row + (size_t)i1[k]);
+    }
+    const double lse_use = is_prob ? 0.0 : lse_t;
+    const double e_blank = align_emit_of_value(align_widen<DT>(vb), lse_use, is_prob, clip_lo);
+    CTC_UNROLL
+    for (int k = 0; k < G; ++k) {
+      const int c = cx.tid + k * cx.nt;
+      if (c >= nch) continue;
+      const double e0 = align_emit_of_value(align_widen<DT>(v0[k]), lse_use, is_prob, clip_lo);
+      const double e1 = align_emit_of_value(align_widen<DT>(v1[k]), lse_use, is_prob, clip_lo);
+      find_step(g[k], c == 0, t, dm1[k], sm1[k], e_blank, e0, e1, d[k], st[k]);
+      col_d[co + c] = d[k][3];
+      col_s[co + c] = st[k][3];
+      if (c == cf) {
+        const double v = jf == 1 ? d[k][1] : d[k][3];
+        end_logp[t] = v;
+        end_start[t] = v > NEG ? (jf == 1 ? st[k][1] : st[k][3]) : -1;
+      }
+    }
+    vb = nvb, lse_t = nlse;
+    CTC_UNROLL
+    for (int k = 0; k < G; ++k) v0[k] = n0[k], v1[k] = n1[k];
+    cx.sync();  // the one barrier of a frame: the columns swap roles
+  }
+  if (!cx.same_wave(cf % cx.nt)) return;
+  cx.publish();
+  find_select(cx, ph, max_hits, min_logp);
+}
+
+// ctc_find_wave: one wavefront per phrase of at most FIND_WAVE_MAX_LABELS labels. Lane c owns group c; the last state of the
+// group below -- a score and a start frame -- comes from lane c - 1 by cx.up() / cx.up_i(): no LDS, no barrier. The same
+// groups, steps and prefetch as ctc_find_phrase, so the same bits. Lane cf writes the trace, the wave selects.
+template <int DT, class Ctx>
+CTC_HD void ctc_find_wave_phrase(Ctx& cx, const FindPhrase& ph, int V, int blank, double clip_lo, int max_hits, double min_logp) {
+  typedef typename AlignRaw<DT>::type Raw;
+  const void* const x = ph.x;
+  const double* const lse = ph.lse;
+  const int32_t* const lab = ph.lab;
+  double* const end_logp = ph.end_logp;
+  int32_t* const end_start = ph.end_start;
+  const int T = ph.T, L = ph.L, c = cx.lane();
+  const bool is_prob = ph.is_prob != 0;
+  if (T <= 0 || L <= 0) return;
+  const int nch = find_chunks(L);
+  const int cf = (2 * L - 1) >> 2, jf = (2 * L - 1) & 3;
+  const double NEG = align_neg_inf();
+  const ForwardGroup g = c < nch ? forward_group(lab, L, c) : ForwardGroup{-1, -1, false, false, false};
+  const int i0 = g.l0 >= 0 ? g.l0 : blank, i1 = g.l1 >= 0 ? g.l1 : blank;
+  double d[4] = {NEG, NEG, NEG, NEG};
+  int32_t st[4] = {-1, -1, -1, -1};
+  Raw vb = align_load_raw<DT>(x, (size_t)blank);
+  Raw v0 = align_load_raw<DT>(x, (size_t)i0), v1 = align_load_raw<DT>(x, (size_t)i1);
+  double lse_t = lse[0];
+  for (int t = 0; t < T; ++t) {
+    const double below_d = cx.up(d[3]);  // (every lane takes part)
+    const int32_t below_s = cx.up_i(st[3]);
+    const int tn = t + 1 < T ? t + 1 : t;
+    const size_t row = (size_t)tn * (size_t)V;
+    const Raw nvb = align_load_raw<DT>(x, row + (size_t)blank);
+    const Raw n0 = align_load_raw<DT>(x, row + (size_t)i0), n1 = align_load_raw<DT>(x, row + (size_t)i1);
+    const double nlse = lse[tn];
+    if (c < nch) {
+      const double lse_use = is_prob ? 0.0 : lse_t;
+      const double e_blank = align_emit_of_value(align_widen<DT>(vb), lse_use, is_prob, clip_lo);
+      const double e0 = align_emit_of_value(align_widen<DT>(v0), lse_use, is_prob, clip_lo);
+      const double e1 = align_emit_of_value(align_widen<DT>(v1), lse_use, is_prob, clip_lo);
+      find_step(g, c == 0, t, c > 0 ? below_d : NEG, c > 0 ? below_s : -1, e_blank, e0, e1, d, st);
+      if (c == cf) {
+        const double v = jf == 1 ? d[1] : d[3];
+        end_logp[t] = v;
+        end_start[t] = v > NEG ? (jf == 1 ? st[1] : st[3]) : -1;
+      }
+    }
+    vb = nvb, lse_t = nlse, v0 = n0, v1 = n1;
+  }
+  cx.publish();
+  find_select(cx, ph, max_hits, min_logp);
 }
 
 }  // namespace ctc

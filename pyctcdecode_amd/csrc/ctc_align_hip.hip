@@ -2,7 +2,8 @@
 // every frame row; ctc_viterbi, one workgroup per utterance over the blank / label / blank / ... states; ctc_forward and
 // ctc_forward_wave, the sum over all alignments of a hypothesis, one workgroup / one wavefront each; ctc_posteriors, the
 // forward-backward of an utterance's transcript, one workgroup each; ctc_grad_rows, the gradient of the likelihood from the
-// posteriors a dense ctc_posteriors launch left, row by row. A translation unit of its own.
+// posteriors a dense ctc_posteriors launch left, row by row; ctc_find and ctc_find_wave, the occurrences of a phrase inside
+// an utterance, one workgroup / one wavefront each. A translation unit of its own.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -209,6 +210,71 @@ __global__ __launch_bounds__(ALIGN_THREADS) void ctc_grad_rows(GradRowsArgs a) {
   ctc_grad_row<DT, GT>(cx, u, (int)(row - u.row_begin), a.n_labels, a.blank, a.clip_lo);
 }
 
+// ---------------------------------------------------------------------------------------------
+// ctc_find: one workgroup per phrase, one group of four states per thread in registers, scores and start frames (256 threads
+// up to 511 labels, 1024 above), the groups' last states in two LDS columns of 12 bytes an entry, one barrier per frame.
+// ctc_find_wave: a wavefront per phrase of at most 127 labels, four to a workgroup that never synchronises; the neighbour's
+// state by one fp64 and one int32 shuffle per frame. In both, the thread that owns the last label writes the trace and its
+// wavefront alone selects the hits from it (ctc_align.h)
+// ---------------------------------------------------------------------------------------------
+// What find_select asks of a wavefront: the windows taken so far live one to a lane.
+struct FindSelectGpu {
+  int lane_;
+  int32_t hs = 0, he = 0;
+  __device__ __forceinline__ int lane() const { return lane_; }
+  __device__ __forceinline__ int lanes() const { return 64; }
+  __device__ __forceinline__ bool any(bool b) const { return __any(b ? 1 : 0) != 0; }
+  // (the trace: stored by one lane of this wave, loaded by all of them)
+  __device__ __forceinline__ void publish() const { __threadfence_block(); }
+  __device__ __forceinline__ void best(double& v, int& t, int& s) const {
+    CTC_UNROLL
+    for (int off = 32; off >= 1; off >>= 1) {
+      const double ov = __shfl_xor(v, off, 64);
+      const int ot = __shfl_xor(t, off, 64), os = __shfl_xor(s, off, 64);
+      if (ov > v || (ov == v && ot < t)) v = ov, t = ot, s = os;
+    }
+  }
+  __device__ __forceinline__ void put(int j, int32_t s, int32_t e) {
+    if (lane_ == j) hs = s, he = e;
+  }
+  __device__ __forceinline__ void get(int j, int32_t* s, int32_t* e) const {
+    *s = __shfl(hs, j, 64);
+    *e = __shfl(he, j, 64);
+  }
+};
+static_assert(FIND_MAX_HITS <= 64, "a lane per window taken");
+
+struct FindGpuCtx : FindSelectGpu {
+  enum { GROUPS = 1 };
+  int tid, nt;
+  __device__ __forceinline__ FindGpuCtx(int tid_, int nt_) : FindSelectGpu{tid_ & 63}, tid(tid_), nt(nt_) {}
+  __device__ __forceinline__ void sync() { __syncthreads(); }
+  __device__ __forceinline__ bool same_wave(int other_tid) const { return (tid >> 6) == (other_tid >> 6); }
+};
+static_assert(FORWARD_THREADS_MAX * FindGpuCtx::GROUPS >= find_chunks(ALIGN_MAX_LABELS), "a thread per group of the longest phrase");
+
+template <int NT, int DT>
+__global__ __launch_bounds__(NT) void ctc_find(FindArgs a) {
+  extern __shared__ double find_cols[];
+  FindGpuCtx cx((int)threadIdx.x, NT);
+  ctc_find_phrase<DT>(cx, a.phrases[blockIdx.x], a.n_labels, a.blank, a.clip_lo, a.max_hits, a.min_logp, find_cols);
+}
+
+struct FindWaveCtx : FindSelectGpu {
+  __device__ __forceinline__ explicit FindWaveCtx(int lane) : FindSelectGpu{lane} {}
+  __device__ __forceinline__ double up(double v) const { return __shfl_up(v, 1, 64); }
+  __device__ __forceinline__ int32_t up_i(int32_t v) const { return __shfl_up(v, 1, 64); }
+};
+static_assert(find_chunks(FIND_WAVE_MAX_LABELS) <= 64, "a lane per group");
+
+template <int DT>
+__global__ __launch_bounds__(ALIGN_THREADS) void ctc_find_wave(FindArgs a) {
+  const int i = (int)blockIdx.x * FORWARD_WAVES + (int)(threadIdx.x >> 6);
+  if (i >= a.n_phrases) return;  // (a whole wave: nothing in this kernel waits for another wave)
+  FindWaveCtx cx((int)(threadIdx.x & 63u));
+  ctc_find_wave_phrase<DT>(cx, a.phrases[i], a.n_labels, a.blank, a.clip_lo, a.max_hits, a.min_logp);
+}
+
 // kernel times: one pair of events per launch since the last reset
 struct EventLog {
   std::vector<hipEvent_t> ev;
@@ -231,12 +297,13 @@ struct EventLog {
     return sum;
   }
 };
-static EventLog g_lse_log, g_vit_log, g_fwd_log, g_post_log, g_grad_log;
+static EventLog g_lse_log, g_vit_log, g_fwd_log, g_post_log, g_grad_log, g_find_log;
 
-void align_timing_reset() { g_lse_log.used = g_vit_log.used = g_fwd_log.used = g_post_log.used = g_grad_log.used = 0; }
+void align_timing_reset() { g_lse_log.used = g_vit_log.used = g_fwd_log.used = g_post_log.used = g_grad_log.used = g_find_log.used = 0; }
 double forward_timing() { return g_fwd_log.total(); }
 double posteriors_timing() { return g_post_log.total(); }
 double grad_rows_timing() { return g_grad_log.total(); }
+double find_timing() { return g_find_log.total(); }
 void align_timing(double* row_lse_ms, double* viterbi_ms) {
   *row_lse_ms = g_lse_log.total();
   *viterbi_ms = g_vit_log.total();
@@ -364,6 +431,36 @@ int launch_ctc_grad_rows_on(const GradRowsArgs& a, hipStream_t stream, std::stri
   else if (a.dtype == 1) launch_grad_rows_dt<1, double>(a, stream);
   else if (a.dtype == 2) launch_grad_rows_dt<2, float>(a, stream);
   else launch_grad_rows_dt<3, float>(a, stream);
+  HIP_TRY_A(hipGetLastError());
+  HIP_TRY_A(hipEventRecord(e1, stream));
+  return 0;
+}
+
+template <int DT>
+static void launch_find_dt(const FindArgs& a, int wave, hipStream_t stream) {
+  if (wave) {
+    hipLaunchKernelGGL(ctc_find_wave<DT>, dim3((unsigned)((a.n_phrases + FORWARD_WAVES - 1) / FORWARD_WAVES)), dim3(ALIGN_THREADS), 0, stream, a);
+    return;
+  }
+  const size_t lds = (size_t)2 * (size_t)a.max_chunks * (sizeof(double) + sizeof(int32_t));  // <= 24 KB
+  if (a.max_chunks <= ALIGN_THREADS) hipLaunchKernelGGL((ctc_find<ALIGN_THREADS, DT>), dim3((unsigned)a.n_phrases), dim3(ALIGN_THREADS), lds, stream, a);
+  else hipLaunchKernelGGL((ctc_find<FORWARD_THREADS_MAX, DT>), dim3((unsigned)a.n_phrases), dim3(FORWARD_THREADS_MAX), lds, stream, a);
+}
+
+int launch_ctc_find_on(const FindArgs& a, int wave, hipStream_t stream, std::string* err) {
+  if (a.n_phrases <= 0) return 0;
+  if (a.dtype < 0 || a.dtype > 3 || a.max_hits < 1 || a.max_hits > FIND_MAX_HITS || a.max_chunks < 1 ||
+      a.max_chunks > (wave ? find_chunks(FIND_WAVE_MAX_LABELS) : find_chunks(ALIGN_MAX_LABELS))) {
+    if (err) *err = "ctc_find: more states or hits than the kernel holds";
+    return -1;
+  }
+  hipEvent_t e0, e1;
+  if (g_find_log.next(&e0, err) || g_find_log.next(&e1, err)) return -1;
+  HIP_TRY_A(hipEventRecord(e0, stream));
+  if (a.dtype == 0) launch_find_dt<0>(a, wave, stream);
+  else if (a.dtype == 1) launch_find_dt<1>(a, wave, stream);
+  else if (a.dtype == 2) launch_find_dt<2>(a, wave, stream);
+  else launch_find_dt<3>(a, wave, stream);
   HIP_TRY_A(hipGetLastError());
   HIP_TRY_A(hipEventRecord(e1, stream));
   return 0;

@@ -226,8 +226,44 @@ class TranscriptGradient:
     grad: Any
 
 
+@dataclasses.dataclass(frozen=True)
+class PhraseHit:
+    """One occurrence of a phrase (BeamSearchDecoderCTC.find / find_batch): the frames ``[start, end)`` -- the first is a frame
+    of the phrase's first label, the last a frame of its last label -- and ``logp``, the sum of the clipped log-probabilities
+    along the best CTC path of the phrase through exactly those frames."""
+
+    start: int
+    end: int
+    logp: float
+
+    @property
+    def frames(self) -> int:
+        return self.end - self.start
+
+    @property
+    def mean_logp(self) -> float:
+        return self.logp / (self.end - self.start)
+
+
+@dataclasses.dataclass(frozen=True, eq=False)
+class PhraseSearch:
+    """Where a phrase occurs in an utterance (BeamSearchDecoderCTC.find / find_batch): ``text`` and ``tokens`` are
+    ScoredText's; ``hits`` are the occurrences taken, best first, pairwise disjoint -- none when the utterance has fewer
+    frames than the phrase has labels plus adjacent equal labels. With ``trace=True``, ``end_logp[t]`` (float64) is the score
+    of the best occurrence whose last label sits on frame ``t`` and ``end_start[t]`` (int32) its first frame, ``-inf`` / ``-1``
+    where none ends; else both are None."""
+
+    text: str
+    tokens: List[int]
+    hits: List[PhraseHit]
+    end_logp: Optional[np.ndarray] = None
+    end_start: Optional[np.ndarray] = None
+
+
 POSTERIORS_TABLE_BUDGET = 4 << 30  # bytes of tables one ctc_posteriors launch holds by default (DESIGN.md, "Frame posteriors")
 FORWARD_KERNELS = {"wave": 1, "group": 2}  # ctcdec_score_batch's `kernel` from CTCDEC_FORWARD_KERNEL (unset: the library chooses)
+FIND_KERNELS = {"wave": 1, "group": 2}  # ctcdec_find_batch's `kernel` from CTCDEC_FIND_KERNEL (unset: the library chooses)
+FIND_MAX_HITS = 64  # FIND_MAX_HITS of csrc/ctc_align.h: a wavefront keeps the windows taken so far one to a lane
 CONFIDENCE_FOLDS = {"mean": 2, "min": 3, "max": 4}  # ctcdec_params.token_frames: CTCDEC_TOKEN_LOGP_MEAN / _MIN / _MAX
 
 
@@ -1157,6 +1193,11 @@ class BeamSearchDecoderCTC:
         self.last_gradient_timing_ms = (0.0, 0.0, 0.0, 0.0, 0.0)
         self.last_gradient_launches = 0
         self.last_gradient_launched = (0, 0)
+        # ... and of the last find / find_batch call (ms: classification, row_lse, find kernels, native call; kernel launches
+        # made; phrases taken by the wave kernel and by the group kernel)
+        self.last_find_timing_ms = (0.0, 0.0, 0.0, 0.0)
+        self.last_find_launches = 0
+        self.last_find_launched = (0, 0)
 
     def __del__(self):
         h = getattr(self, "_handle", None)
@@ -1744,6 +1785,52 @@ class BeamSearchDecoderCTC:
                 out[u] = AlignedText(text, path[path_off[j]:path_off[j + 1]].copy(), float(score[j]), tok, wf, tlp, wlp)
             return out
 
+    def _many_targets_each(self, what: str, item: str, items: str, logits_list: Any, texts, tokens):
+        """The label ids of any number of given texts or token lists per utterance, checked: (logits_list, ids[u][j])."""
+        if (texts is None) == (tokens is None):
+            raise ValueError("%s: give exactly one of texts and tokens" % what)
+        if texts is not None and self._is_bpe:
+            raise ValueError("a text has many segmentations under a BPE alphabet: give the %s as tokens=" % items)
+        if getattr(logits_list, "ndim", 0) != 3:
+            logits_list = list(logits_list)
+        n = len(logits_list)
+        given = texts if texts is not None else tokens
+        if not isinstance(given, str):
+            given = list(given)  # (a generator has no len())
+        if isinstance(given, str) or len(given) != n:
+            raise ValueError("%s: %s for %d utterances, but %d utterances" % (what, items, 1 if isinstance(given, str) else len(given), n))
+        blank, n_labels = self._vocab2idx[""], len(self._labels_list)
+        out: List[List[List[int]]] = []
+        for u, per_utt in enumerate(given):
+            if isinstance(per_utt, str):
+                raise ValueError("%s: utterance %d got a bare str where a sequence of %s is expected (wrap it in a "
+                                 "list: a str would be read character by character)" % (what, u, items))
+            cur = []
+            for j, g in enumerate(per_utt):
+                who = "utterance %d, %s %d" % (u, item, j)
+                if texts is not None:
+                    if not isinstance(g, str):
+                        raise ValueError("%s: %s is not a str" % (what, who))
+                    ids = self._target_of_text(g)
+                else:
+                    if isinstance(g, str):
+                        raise ValueError("%s: %s is a str, not a sequence of label ids" % (what, who))
+                    ids = list(g)
+                    if set(map(type, ids)) <= {int} and (not ids or (0 <= min(ids) and max(ids) < n_labels and blank not in ids)):
+                        pass  # (plain ints, all in range: the check below, without a Python-level loop)
+                    else:
+                        for k, c in enumerate(ids):
+                            if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 0 <= int(c) < n_labels or int(c) == blank:
+                                raise ValueError("%s: %s holds %r: not a label id in [0, %d) other than the blank (%d)"
+                                                 % (what, who, c, n_labels, blank))
+                            ids[k] = int(c)
+                if len(ids) > ALIGN_MAX_LABELS:
+                    raise ValueError("%s: %s has %d labels, above the limit of %d labels per %s"
+                                     % (what, who, len(ids), ALIGN_MAX_LABELS, item))
+                cur.append(ids)
+            out.append(cur)
+        return logits_list, out
+
     # -- transcript likelihood (no reference analogue; DESIGN.md, "Transcript likelihood") ----------------
     def score(self, logits: Any, texts: Optional[Sequence[str]] = None, tokens: Optional[Sequence[Sequence[int]]] = None,
               with_lm: bool = False) -> List["ScoredText"]:
@@ -1760,51 +1847,11 @@ class BeamSearchDecoderCTC:
         ``tokens[u]`` a list of lists of label ids, the only form for BPE alphabets. A hypothesis without an alignment --
         fewer frames than labels plus adjacent equal labels -- has ``logp == -inf``; the empty hypothesis scores the all-blank
         path. ``with_lm=True`` adds the language model's score of the text as a finished beam's (no hot words)."""
-        if (texts is None) == (tokens is None):
-            raise ValueError("score: give exactly one of texts and tokens")
-        if texts is not None and self._is_bpe:
-            raise ValueError("a text has many segmentations under a BPE alphabet: give the hypotheses as tokens=")
         lm = self._language_model
         if with_lm and lm is None:
             raise ValueError("score: with_lm=True needs a decoder with a language model")
-        if getattr(logits_list, "ndim", 0) != 3:
-            logits_list = list(logits_list)
-        n = len(logits_list)
-        given = texts if texts is not None else tokens
-        if not isinstance(given, str):
-            given = list(given)  # (a generator has no len())
-        if isinstance(given, str) or len(given) != n:
-            raise ValueError("score: hypotheses for %d utterances, but %d utterances" % (1 if isinstance(given, str) else len(given), n))
-        blank, n_labels = self._vocab2idx[""], len(self._labels_list)
-        hyps: List[List[List[int]]] = []
-        for u, per_utt in enumerate(given):
-            if isinstance(per_utt, str):
-                raise ValueError("score: utterance %d got a bare str where a sequence of hypotheses is expected (wrap it in a "
-                                 "list: a str would be read character by character)" % u)
-            cur = []
-            for j, g in enumerate(per_utt):
-                who = "utterance %d, hypothesis %d" % (u, j)
-                if texts is not None:
-                    if not isinstance(g, str):
-                        raise ValueError("score: %s is not a str" % who)
-                    ids = self._target_of_text(g)
-                else:
-                    if isinstance(g, str):
-                        raise ValueError("score: %s is a str, not a sequence of label ids" % who)
-                    ids = list(g)
-                    if set(map(type, ids)) <= {int} and (not ids or (0 <= min(ids) and max(ids) < n_labels and blank not in ids)):
-                        pass  # (plain ints, all in range: the check below, without a Python-level loop)
-                    else:
-                        for k, c in enumerate(ids):
-                            if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 0 <= int(c) < n_labels or int(c) == blank:
-                                raise ValueError("score: %s holds %r: not a label id in [0, %d) other than the blank (%d)"
-                                                 % (who, c, n_labels, blank))
-                            ids[k] = int(c)
-                if len(ids) > ALIGN_MAX_LABELS:
-                    raise ValueError("score: %s has %d labels, above the limit of %d labels per hypothesis"
-                                     % (who, len(ids), ALIGN_MAX_LABELS))
-                cur.append(ids)
-            hyps.append(cur)
+        logits_list, hyps = self._many_targets_each("score", "hypothesis", "hypotheses", logits_list, texts, tokens)
+        n, n_labels = len(hyps), len(self._labels_list)
         if n == 0:
             self.last_score_timing_ms, self.last_score_launched = (0.0, 0.0, 0.0, 0.0), (0, 0)
             return []
@@ -1854,6 +1901,117 @@ class BeamSearchDecoderCTC:
                 res.append(ScoredText(text, list(ids), lp, lm_logp, lp + (lm_logp or 0.0)))
                 h += 1
             out.append(res)
+        return out
+
+    # -- phrase search (no reference analogue; DESIGN.md, "Phrase search") ----------------------------------
+    def find(self, logits: Any, texts: Optional[Sequence[str]] = None, tokens: Optional[Sequence[Sequence[int]]] = None,
+             max_hits: int = 1, min_logp: Optional[float] = None, trace: bool = False) -> List["PhraseSearch"]:
+        """Where each phrase occurs in one utterance: find_batch of a batch of one."""
+        if isinstance(logits, (_ResidentBeams, _DeviceStreams)):
+            raise NotImplementedError("find searches an utterance's matrix; the frames a stream has consumed are not kept")
+        self._check_logits_dimension(logits)
+        return self.find_batch([logits], None if texts is None else [texts], tokens=None if tokens is None else [tokens],
+                               max_hits=max_hits, min_logp=min_logp, trace=trace)[0]
+
+    def find_batch(self, logits_list: Any, texts: Optional[Sequence[Sequence[str]]] = None,
+                   tokens: Optional[Sequence[Sequence[Sequence[int]]]] = None, max_hits: int = 1,
+                   min_logp: Optional[float] = None, trace: bool = False, _trace_budget: int = 0) -> List[List["PhraseSearch"]]:
+        """Does each phrase occur somewhere in its utterance, where, and how well, in one native call: per utterance a
+        sequence of phrases, per phrase a PhraseSearch (row_lse once per utterance + ctc_find / ctc_find_wave,
+        csrc/ctc_align_hip.hip). ``logits_list`` is what align_batch takes; ``texts[u]`` (character alphabets) is a list of
+        str, ``tokens[u]`` a list of lists of label ids, the only form for BPE alphabets. An occurrence is a window of frames
+        that begins on the phrase's first label and ends on its last, scored by its best CTC path; per end frame the best
+        window is kept. Up to ``max_hits`` (1 .. 64) pairwise disjoint windows are taken, best first, none below ``min_logp``
+        (None: no threshold); an end frame whose best window overlaps a hit already taken is dropped, even if a worse window
+        ending there would not overlap. ``trace=True`` also returns the per-frame ``end_logp`` / ``end_start``."""
+        if isinstance(logits_list, (_ResidentBeams, _DeviceStreams)) or (
+                isinstance(logits_list, (list, tuple)) and any(isinstance(x, (_ResidentBeams, _DeviceStreams)) for x in logits_list)):
+            raise NotImplementedError("find_batch searches utterances' matrices; the frames a stream has consumed are not kept")
+        logits_list, phrases = self._many_targets_each("find", "phrase", "phrases", logits_list, texts, tokens)
+        for u, cur in enumerate(phrases):
+            for j, ids in enumerate(cur):
+                if not ids:
+                    raise ValueError("find: utterance %d, phrase %d is empty: it would occur everywhere and nowhere" % (u, j))
+        if isinstance(max_hits, bool) or not isinstance(max_hits, (int, np.integer)) or not 1 <= int(max_hits) <= FIND_MAX_HITS:
+            raise ValueError("find: max_hits must be an int in 1 .. %d, not %r" % (FIND_MAX_HITS, max_hits))
+        floor = -math.inf if min_logp is None else float(min_logp)
+        if math.isnan(floor):
+            raise ValueError("find: min_logp is not a number")
+        n, n_labels = len(phrases), len(self._labels_list)
+        self.last_find_timing_ms, self.last_find_launches, self.last_find_launched = (0.0, 0.0, 0.0, 0.0), 0, (0, 0)
+        if n == 0:
+            return []
+        kernel_env = os.environ.get("CTCDEC_FIND_KERNEL", "")
+        if kernel_env and kernel_env not in FIND_KERNELS:
+            raise ValueError("CTCDEC_FIND_KERNEL must be wave or group, not %r" % kernel_env)
+        with self._call_lock:
+            batch = _Batch(logits_list, n_labels)
+            if batch.is_device and batch.device_index is not None and batch.device_index != self._device:
+                raise ValueError("the logits live on cuda:%d but this decoder was built for cuda:%d (one process per GPU: "
+                                 "LOCAL_RANK / CTCDEC_DEVICE pick the device)" % (batch.device_index, self._device))
+            frames = np.ascontiguousarray(np.asarray(batch.frames, dtype=np.int32))
+            ptrs = np.ascontiguousarray(np.asarray(batch.ptrs, dtype=np.uint64))
+            budget = int(_trace_budget) or ALIGN_BP_BUDGET
+            for u, cur in enumerate(phrases):
+                for j, ids in enumerate(cur):
+                    need = len(ids) + sum(1 for a, b in zip(ids, ids[1:]) if a == b)
+                    if int(frames[u]) >= need and 12 * int(frames[u]) > budget:
+                        raise ValueError("find: utterance %d, phrase %d needs a trace of %d bytes, above the memory budget of %d "
+                                         "bytes of one launch" % (u, j, 12 * int(frames[u]), budget))
+            flat_phrases = [ids for cur in phrases for ids in cur]
+            flat = np.fromiter(itertools.chain.from_iterable(flat_phrases), dtype=np.int32)
+            if not len(flat):
+                flat = np.zeros(1, dtype=np.int32)
+            label_off = np.zeros(len(flat_phrases) + 1, dtype=np.int64)
+            label_off[1:] = np.cumsum([len(ids) for ids in flat_phrases])
+            hyp_off = np.zeros(n + 1, dtype=np.int64)
+            hyp_off[1:] = np.cumsum([len(cur) for cur in phrases])
+            res = C.c_void_p()
+            lib = self._lib
+            lib.check(lib.dll.ctcdec_find_batch(
+                self._handle, ptrs.ctypes.data_as(C.POINTER(C.c_void_p)), frames.ctypes.data_as(C.POINTER(C.c_int32)), n,
+                batch.dtype, int(batch.is_device), B.off_ptr(hyp_off), B.off_ptr(label_off), flat.ctypes.data_as(C.POINTER(C.c_int32)),
+                int(max_hits), floor, int(bool(trace)), FIND_KERNELS.get(kernel_env, 0), int(_trace_budget), C.byref(res)))
+            try:
+                ho, ps, pe, pl, nph = (C.POINTER(C.c_int64)(), C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)(),
+                                       C.POINTER(C.c_double)(), C.c_int64())
+                lib.check(lib.dll.ctcdec_search_hits(res, C.byref(ho), C.byref(ps), C.byref(pe), C.byref(pl), C.byref(nph)))
+                if int(nph.value) != len(flat_phrases):
+                    raise B.NativeError("the search holds another number of phrases than was asked for")
+                hit_off = np.ctypeslib.as_array(ho, shape=(len(flat_phrases) + 1,)).tolist()
+                nh = hit_off[-1]
+                starts = np.ctypeslib.as_array(ps, shape=(nh,)).tolist() if nh else []
+                ends = np.ctypeslib.as_array(pe, shape=(nh,)).tolist() if nh else []
+                logps = np.ctypeslib.as_array(pl, shape=(nh,)).tolist() if nh else []
+                t_off, t_logp, t_start = None, None, None
+                if trace:
+                    to, tl, ts = C.POINTER(C.c_int64)(), C.POINTER(C.c_double)(), C.POINTER(C.c_int32)()
+                    lib.check(lib.dll.ctcdec_search_trace(res, C.byref(to), C.byref(tl), C.byref(ts)))
+                    t_off = np.ctypeslib.as_array(to, shape=(len(flat_phrases) + 1,)).tolist()
+                    nt = t_off[-1]
+                    t_logp = np.ctypeslib.as_array(tl, shape=(nt,)).copy() if nt else np.zeros(0)
+                    t_start = np.ctypeslib.as_array(ts, shape=(nt,)).copy() if nt else np.zeros(0, dtype=np.int32)
+                ms, launches, launched = (C.c_double * 4)(), C.c_int32(), (C.c_int64 * 2)()
+                lib.dll.ctcdec_search_timing(res, ms, C.byref(launches), launched)
+                # [classification (frame-prune kernels), row_lse, find kernels (HIP events), whole native call]; kernel launches
+                # made; phrases that went to (ctc_find_wave, ctc_find)
+                self.last_find_timing_ms = tuple(float(v) for v in ms)
+                self.last_find_launches = int(launches.value)
+                self.last_find_launched = (int(launched[0]), int(launched[1]))
+            finally:
+                lib.dll.ctcdec_search_free(res)
+        out: List[List[PhraseSearch]] = []
+        h = 0
+        for cur in phrases:
+            found = []
+            for ids in cur:
+                hits = [PhraseHit(starts[k], ends[k], logps[k]) for k in range(hit_off[h], hit_off[h + 1])]
+                el = es = None
+                if trace:
+                    el, es = t_logp[t_off[h]:t_off[h + 1]].copy(), t_start[t_off[h]:t_off[h + 1]].copy()
+                found.append(PhraseSearch(self._words_of_target(ids)[0], list(ids), hits, el, es))
+                h += 1
+            out.append(found)
         return out
 
     # -- frame posteriors (no reference analogue; DESIGN.md, "Frame posteriors") ---------------------------

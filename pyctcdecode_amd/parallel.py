@@ -211,6 +211,11 @@ def gradient_batch_sharded(decoder, logits_list, texts=None, group=None, **kwarg
     raise NotImplementedError("gradient_batch is not gathered over ranks: call decoder.gradient_batch on each rank's slice itself")
 
 
+def find_batch_sharded(decoder, logits_list, texts=None, group=None, **kwargs):
+    """Phrase search is not sharded over ranks: each rank calls decoder.find_batch on its own slice."""
+    raise NotImplementedError("find_batch is not gathered over ranks: search each rank's slice with decoder.find_batch itself")
+
+
 def _device_worker(conn, device: int, decoder_dir: str, library: Optional[str]) -> None:
     """One worker process = one GPU (the native library binds one device per process): loads the saved decoder on its device and
     serves (method, logits, kwargs) requests until it is told to stop."""
@@ -351,6 +356,12 @@ class DevicePool:
         raise NotImplementedError("DevicePool does not shard gradient_batch: call decoder.gradient_batch on the process's own device")
 
     gradient = gradient_batch
+
+    def find_batch(self, logits_list, texts=None, **kwargs):
+        """Phrase search runs on the calling process's own device: a pool does not shard it."""
+        raise NotImplementedError("DevicePool does not shard find_batch: call decoder.find_batch on the process's own device")
+
+    find = find_batch
 
     def decode_batch(self, logits_list, **kwargs) -> List[str]:
         if kwargs.get("token_frames") or kwargs.get("confidence") is not None:  # (texts, TokenFrames) per slice -> one of each, offsets rebased

@@ -6,8 +6,11 @@ substituted), each forward kernel forced in turn -- and at 64 utterances, with t
 for scale; then a sweep of target lengths on 256 utterances of random logits, which is what the wave / group threshold of
 ctcdec_score_batch rests on. Kernel times are HIP events on the decode stream (ctcdec_alignment_timing, ctcdec_score_batch,
 ctcdec_posteriors_timing).
-  python tools/align_bench.py [--out profiles/align_bench.txt] [--steps 3] [--legs align,score,posteriors,sweep,gradient]
+  python tools/align_bench.py [--out profiles/align_bench.txt] [--steps 3] [--legs align,score,posteriors,sweep,gradient,find]
 The gradient leg (not in the default set) times gradient_batch -- ctc_grad_rows alone, next to posteriors_batch(dense=False).
+The find leg (not in the default set either) times find_batch -- ctc_find / ctc_find_wave forced in turn, alternating: at the
+bench shape each utterance searched for 1 and for 8 phrases of 8 labels cut from its own decoded tokens, then 256 and 2048
+phrases of 15 / 127 / 511 labels on 256 utterances of random logits, next to ctc_viterbi and ctc_forward on the same batch.
 The 4096 utterances are 256 distinct ones repeated: no kernel's time depends on the rows being distinct."""
 import argparse
 import os
@@ -127,6 +130,92 @@ def gradient_lines(dec, dev, targets, steps):
             "%9.3f ms  (%d launches of both)  native call %9.3f ms  Python call %9.3f ms"
             % (med(grad), moved / 1e9, rate / 1e12, rate / PRUNE_RATE, PRUNE_RATE / 1e12, med(dense), launches, med(native), med(wall)),
             "    ctc_grad_rows / ctc_posteriors dense=False (%.3f ms) at this batch: %.2f" % (med(lean), med(grad) / med(lean))]
+
+
+def time_find(dec, dev, phrases, kernels, steps):
+    """The find kernels' time (HIP events) under each forced kernel, as time_forward measures the forward kernels: one warm-up
+    call each, then `steps` alternating rounds. -> {kernel: (median kernel ms, native call ms, Python call ms)}, phrases per kernel"""
+    got = {k: [] for k in kernels}
+    launched = {}
+    for step in range(steps + 1):
+        for k in kernels:
+            os.environ["CTCDEC_FIND_KERNEL"] = k
+            t0 = time.perf_counter()
+            out = dec.find_batch(dev, tokens=phrases)
+            wall = (time.perf_counter() - t0) * 1e3
+            if step:
+                got[k].append((dec.last_find_timing_ms[2], dec.last_find_timing_ms[3], wall))
+            launched[k] = dec.last_find_launched
+    os.environ.pop("CTCDEC_FIND_KERNEL", None)
+    assert all(len(g.hits) == 1 for per_utt in out for g in per_utt)
+    return {k: tuple(float(np.median([r[i] for r in v])) for i in range(3)) for k, v in got.items()}, launched
+
+
+def find_lines(dec, dev, targets, steps, phrase_labels=8):
+    """Each utterance searched for 1 and for 8 phrases of `phrase_labels` labels cut from its own decoded tokens, the two
+    kernels alternating."""
+    rng = np.random.default_rng(9)
+    cuts = []
+    for t in targets:
+        cur = []
+        for _ in range(8):
+            k = int(rng.integers(0, max(1, len(t) - phrase_labels + 1)))
+            cur.append(list(t[k:k + phrase_labels]))
+        cuts.append(cur)
+    lines = []
+    for what, phrases in (("1 phrase ", [c[:1] for c in cuts]), ("8 phrases", cuts)):
+        got, launched = time_find(dec, dev, phrases, ("wave", "group"), steps)
+        for k in ("wave", "group"):
+            lines.append("  find_batch %s of %d labels  %-5s  find kernel %9.3f ms  native call %9.3f ms  Python call %9.3f ms  "
+                         "(wave kernel %d, group kernel %d phrases)" % ((what, phrase_labels, k) + got[k] + tuple(launched[k])))
+    return lines
+
+
+def find_sweep_lines(dec, steps):
+    """256 utterances of standard-normal logits x 3, random phrases without repeats of 15 / 127 / 511 labels, one and eight per
+    utterance (256 and 2048 phrases): both find kernels where both take the length, alternating, next to ctc_viterbi and the
+    group ctc_forward on the same batch with the same label sequences in the same run."""
+    import torch
+
+    lines = ["find: sweep of phrase lengths, 256 utterances x %d frames x %d labels float32 (random logits), 1 and 8 phrases per "
+             "utterance; %d alternating steps after one warm-up each, medians (kernels alone, HIP events):" % (T, V, steps),
+             "  %6s | %12s %12s %10s | %12s %12s %10s | %12s %12s | %8s %8s" % (
+                 "labels", "wave x1", "group x1", "wave/group", "wave x8", "group x8", "wave/group", "ctc_viterbi", "ctc_forward",
+                 "find/vit", "find/fwd")]
+    rng = np.random.default_rng(5)
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(5)
+    blank = dec._alphabet.labels.index("")
+    pool = np.array([c for c in range(V) if c != blank])
+    dev = torch.randn((DISTINCT, T, V), generator=gen, device="cuda", dtype=torch.float32) * 3
+    torch.cuda.synchronize()
+    for L in (15, 127, 511, 15):  # (15 labels twice: what the first row measures may be the first use, not the length)
+        ones, eights = [], []
+        for _ in range(DISTINCT):
+            cur = []
+            for _k in range(8):
+                t = pool[rng.integers(0, len(pool), size=L)]
+                same = np.flatnonzero(t[1:] == t[:-1]) + 1
+                t[same] = pool[(np.searchsorted(pool, t[same]) + 1) % len(pool)]
+                cur.append(t.tolist())
+            ones.append(cur[:1])
+            eights.append(cur)
+        kernels = ("wave", "group") if L <= 127 else ("group",)
+        one = {k: v[0] for k, v in time_find(dec, dev, ones, kernels, steps)[0].items()}
+        many = {k: v[0] for k, v in time_find(dec, dev, eights, kernels, steps)[0].items()}
+        targets = [c[0] for c in ones]
+        fwd = time_forward(dec, dev, ones, ("group",), steps)["group"]
+        vit = []
+        for _ in range(steps + 1):
+            dec.align_batch(dev, tokens=targets)
+            vit.append(dec.last_align_timing_ms[2])
+        cell = lambda d, k: "%9.3f ms" % d[k] if k in d else "%12s" % "-"  # noqa: E731
+        ratio = lambda d: "%10.2f" % (d["wave"] / d["group"]) if "wave" in d else "%10s" % "-"  # noqa: E731
+        lines.append("  %6d | %s %s %s | %s %s %s | %9.3f ms %9.3f ms | %8.2f %8.2f" % (
+            L, cell(one, "wave"), cell(one, "group"), ratio(one), cell(many, "wave"), cell(many, "group"), ratio(many),
+            med(vit), fwd, one["group"] / med(vit), one["group"] / fwd))
+    del dev
+    return lines
 
 
 def time_forward(dec, dev, hyps, kernels, steps):
@@ -263,9 +352,13 @@ def main():
             lines += posteriors_lines(dec, dev, targets, args.steps)
         if "gradient" in legs:
             lines += gradient_lines(dec, dev, targets, args.steps)
+        if "find" in legs:
+            lines += find_lines(dec, dev, targets, args.steps)
         del dev
     if "sweep" in legs:
         lines += sweep_lines(dec, max(args.steps, 5))
+    if "find" in legs:
+        lines += find_sweep_lines(dec, args.steps)
     text = "\n".join(lines) + "\n"
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
