@@ -367,6 +367,42 @@ int ctcdec_alignment_tokens(const ctcdec_alignment* a, const int64_t** tok_off, 
 int ctcdec_alignment_timing(const ctcdec_alignment* a, double* ms4, int32_t* launches);
 void ctcdec_alignment_free(ctcdec_alignment* a);
 
+/* ---- alignment with gaps: a transcript that does not cover all of the audio ------------------------------------------
+ * torchaudio's forced_align tutorials do this with a "star" token. ctcdec_align_batch with one more kind of target item:
+ * CTCDEC_ALIGN_GAP stands for "something nobody transcribed". A target is a sequence of items, each a label id (alphabet
+ * index, never the blank) or a gap; with L labels y[0 .. L) there are L + 1 slots -- before y[0], between neighbours, after
+ * y[L - 1] --, each plain or a gap. The states are ctcdec_align_batch's, S = 2 L + 1: even state 2 j is slot j, odd state
+ * 2 k + 1 is label k. With e(t, c) that call's clipped float64 log-probabilities:
+ *   a label state emits e(t, y[k]); a plain slot emits e(t, blank);
+ *   a gap slot emits g(t), the largest e(t, c) over all columns c, the blank included -- the clipped value of the row's
+ *   largest entry that is not a NaN (a row without one takes the floor, as every NaN entry does).
+ * So a gap is a blank that may also absorb any labels, at the price the best unconstrained path would pay for those frames.
+ * It may be empty wherever the plain blank may be skipped; between two equal labels it takes at least one frame, as the
+ * blank does. Transitions are unchanged: stay, step, and the skip for a label that differs from the label before it.
+ * Ties: in label states and plain slots equal scores prefer stay, then step, then skip; in a gap slot they prefer step over
+ * stay. (Wherever a target label is its row's maximum, g(t) equals e(t, label) bit for bit, and "the label keeps this frame"
+ * ties with "the gap already has it": under this rule such frames go to the label at both of its ends.) At the end the last
+ * label is preferred over the trailing slot. A path exists when T >= L + (adjacent equal labels); a target needs a label.
+ * Two consequences are exact, because floating-point addition is monotone and the sums run in frame order: a target without
+ * gaps gives ctcdec_align_batch's path, token frames, confidences and score, bit for bit; the score with gaps is >= that
+ * call's score for the same labels and <= the sum of g(t) over all frames.
+ * The arguments are ctcdec_align_batch's, except that targets may hold CTCDEC_ALIGN_GAP. Validation, before any launch:
+ * that call's checks with its codes (on the labels alone: gaps do not count towards the 2047); two adjacent gaps or a target
+ * without a label is CTCDEC_ERR_ARG. The budget is that call's (the tables are as large).
+ * The result is read by ctcdec_alignment_paths (path holds -1 on the frames spent in a gap slot), ctcdec_alignment_tokens
+ * (labels only), ctcdec_alignment_timing ([1] row_lse_max, [2] ctc_viterbi_gaps) and ctcdec_alignment_gaps, and freed by
+ * ctcdec_alignment_free. decoder.py: align_gaps / align_gaps_batch. */
+#define CTCDEC_ALIGN_GAP (-1)
+int ctcdec_align_gaps_batch(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts,
+                            int32_t dtype, int32_t is_device, const int32_t* targets, const int64_t* target_off, int32_t fold,
+                            int64_t bp_budget, ctcdec_alignment** out);
+/* Utterance u's gaps, in target order, are [gap_off[u], gap_off[u + 1]) of start / end / logp. A gap's frames [start, end)
+ * are everything between the end of the label before it (0 for a leading gap) and the start of the label after it (T for a
+ * trailing one): an empty gap has start == end. logp is the sum of g(t) over them, in frame order. CTCDEC_ERR_ARG on an
+ * alignment made by ctcdec_align_batch. */
+int ctcdec_alignment_gaps(const ctcdec_alignment* a, const int64_t** gap_off, const int32_t** start, const int32_t** end,
+                          const double** logp, int64_t* n_gaps);
+
 /* ---- transcript likelihood: how probable a label sequence the caller already has is, given the audio -----------------
  * No reference analogue (torch.nn.functional.ctc_loss computes the negative of it). Utterance u owns the hypotheses
  * [hyp_off[u], hyp_off[u + 1]); hypothesis h is the label ids targets[target_off[h] .. target_off[h + 1]) (alphabet

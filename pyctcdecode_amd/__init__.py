@@ -1,8 +1,8 @@
 """MI355X-native CTC beam-search decoder with the pyctcdecode API surface
 (reference exports: pyctcdecode/__init__.py:2-4)."""
 from .alphabet import Alphabet  # noqa: F401
-from .decoder import (AlignedText, BeamSearchDecoderCTC, ConfidenceLMBeam, ConfidenceOutputBeam, PhraseHit, PhraseSearch,  # noqa: F401
-                      ScoredText, TokenFrames, TokenLMBeam, TokenOutputBeam, TranscriptGradient, TranscriptPosteriors,
+from .decoder import (AlignedText, BeamSearchDecoderCTC, ConfidenceLMBeam, ConfidenceOutputBeam, GappedAlignment, PhraseHit,  # noqa: F401
+                      PhraseSearch, ScoredText, TokenFrames, TokenLMBeam, TokenOutputBeam, TranscriptGradient, TranscriptPosteriors,
                       build_ctcdecoder)
 from .language_model import LanguageModel  # noqa: F401
 

@@ -219,6 +219,9 @@ struct ctcdec_decoder {
   DevBuf w_gocc, w_gutts, w_grad;
   // phrase search (ctcdec_find_batch): a launch's traces and phrase records, the call's hits (labels: w_alab)
   DevBuf w_ftrace, w_fphr, w_fhits;
+  // alignment with gaps (ctcdec_align_gaps_batch): row maxima, the slots' gap flags, the gaps' sums, a launch's utterance
+  // records (everything else: the alignment's)
+  DevBuf w_amax, w_agap, w_aglp, w_agutts;
   bool slicing = false;  // a time-sliced host ingest is under way (decode_host_sliced): the prune stage notes each slice's side of 1
   uint32_t max_label_bytes = 1;
   bool arenas_worst_case = false;  // a call has outgrown the usual reservation of the node arenas: reserve the worst case from now on
@@ -2292,6 +2295,11 @@ struct ctcdec_alignment {
   bool has_logp = false;
   int32_t launches = 0;
   double ms[4] = {0, 0, 0, 0};
+  // ctcdec_align_gaps_batch: utterance u's gaps, in target order, are [gap_off[u], gap_off[u + 1])
+  bool has_gaps = false;
+  std::vector<int64_t> gap_off;
+  std::vector<int32_t> gap_start, gap_end;
+  std::vector<double> gap_logp;
 };
 
 // The back-pointer tables of one ctc_viterbi launch (T * align_chunks(L) bytes per utterance) when the caller names no budget
@@ -2349,6 +2357,8 @@ struct AlignFront {
   std::vector<uint32_t> is_prob;   // [n] the classification read back
   double* lse = nullptr;           // [R] (device) row log-sum-exps, indexed like row0
   double sniff_ms = 0;             // the classification's kernel time
+  bool want_max = false;           // in: row_lse_max instead of row_lse (ctcdec_align_gaps_batch)
+  double* rmax = nullptr;          // [R] (device, want_max) every row's largest entry that is not a NaN
 };
 static int align_front(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts, int32_t dtype,
                        int32_t is_device, int V, const std::vector<int64_t>& row0, AlignFront& f) {
@@ -2388,9 +2398,16 @@ static int align_front(ctcdec_decoder* dec, const void* const* utt_logits, const
   be::last_timing(&f.sniff_ms, &beam_ms);
   if (dec->w_alse.ensure((size_t)R * 8, &err)) return fail(CTCDEC_ERR_DEVICE, err);
   double* lse = f.lse = (double*)dec->w_alse.p;
+  if (f.want_max) {
+    if (dec->w_amax.ensure((size_t)R * 8, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+    f.rmax = (double*)dec->w_amax.p;
+  }
 #ifdef CTC_SIM  // (the simulator's device memory is host memory: the kernels' bodies, row by row and utterance by utterance)
   for (size_t u = 0; u < n; ++u)
-    for (int64_t t = 0; !f.is_prob[u] && t < utt_frames[u]; ++t)
+    for (int64_t t = 0; f.want_max && t < utt_frames[u]; ++t)
+      row_lse_max_seq(ptrs[u], dtype, (size_t)t * (size_t)V, V, f.is_prob[u] != 0, &lse[row0[u] + t], &f.rmax[row0[u] + t]);
+  for (size_t u = 0; u < n; ++u)
+    for (int64_t t = 0; !f.want_max && !f.is_prob[u] && t < utt_frames[u]; ++t)
       lse[row0[u] + t] = row_lse_seq(ptrs[u], dtype, (size_t)t * (size_t)V, V);
 #else
   be::align_timing_reset();
@@ -2403,7 +2420,7 @@ static int align_front(ctcdec_decoder* dec, const void* const* utt_logits, const
   la.n_labels = V;
   la.dtype = dtype;
   la.lse = lse;
-  if (be::launch_row_lse(la, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+  if (f.want_max ? be::launch_row_lse_max(la, f.rmax, &err) : be::launch_row_lse(la, &err)) return fail(CTCDEC_ERR_DEVICE, err);
 #endif
   return CTCDEC_OK;
 }
@@ -2563,6 +2580,193 @@ int ctcdec_alignment_timing(const ctcdec_alignment* a, double* ms4, int32_t* lau
 }
 
 void ctcdec_alignment_free(ctcdec_alignment* a) { delete a; }
+
+// ---- alignment with gaps ("Alignment with gaps") -------------------------------------------------------------
+int ctcdec_align_gaps_batch(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts, int32_t dtype,
+                            int32_t is_device, const int32_t* targets, const int64_t* target_off, int32_t fold, int64_t bp_budget,
+                            ctcdec_alignment** out) {
+  if (!dec || !out || n_utts < 0 || !target_off || bp_budget < 0 || (n_utts > 0 && (!utt_logits || !utt_frames)))
+    return fail(CTCDEC_ERR_ARG, "bad arguments");
+  if (dtype < CTCDEC_F32 || dtype > CTCDEC_BF16) return fail(CTCDEC_ERR_ARG, "dtype must be f32, f64, f16 or bf16");
+  if (fold != 0 && fold != LOGP_MEAN && fold != LOGP_MIN && fold != LOGP_MAX) return fail(CTCDEC_ERR_ARG, "unknown confidence fold");
+  const int V = (int)dec->alpha.labels.size();
+  int blank = -1;
+  for (int v = 0; v < V && blank < 0; ++v)
+    if (dec->alpha.labels[(size_t)v].empty()) blank = v;
+  if (blank < 0) return fail(CTCDEC_ERR_ARG, "the alphabet has no blank label");
+  const int64_t budget = bp_budget ? bp_budget : ALIGN_BP_BUDGET;
+  const size_t n = (size_t)n_utts;
+  // the items apart: the labels, with offsets of their own, and one flag per slot (before label 0, between neighbours, after
+  // the last label). Everything align checks is then checked by align's own code, on the labels.
+  if (target_off[0] != 0) return fail(CTCDEC_ERR_ARG, "target_off must start at 0");
+  std::vector<int32_t> labels;
+  std::vector<int64_t> lab_off(n + 1, 0), slot_off(n + 1, 0);
+  std::vector<uint8_t> slot_gap;
+  for (size_t u = 0; u < n; ++u) {
+    const int64_t N = target_off[u + 1] - target_off[u];
+    if (N < 0) return fail(CTCDEC_ERR_ARG, "target_off must not decrease");
+    if (N > 0 && !targets) return fail(CTCDEC_ERR_ARG, "no targets");
+    slot_gap.push_back(0);
+    for (int64_t k = 0; k < N; ++k) {
+      const int32_t id = targets[target_off[u] + k];
+      if (id != CTCDEC_ALIGN_GAP) {
+        labels.push_back(id);
+        slot_gap.push_back(0);
+        continue;
+      }
+      if (k > 0 && targets[target_off[u] + k - 1] == CTCDEC_ALIGN_GAP)
+        return fail(CTCDEC_ERR_ARG, "utterance " + std::to_string(u) + ": two adjacent gaps are one gap");
+      slot_gap.back() = 1;
+    }
+    lab_off[u + 1] = (int64_t)labels.size();
+    slot_off[u + 1] = (int64_t)slot_gap.size();
+  }
+  if (labels.empty()) labels.push_back(0);  // (never read: .data() of an empty vector may be null)
+  if (int rc = check_alignment(dec, utt_logits, utt_frames, n_utts, labels.data(), lab_off.data(), budget, V, blank)) return rc;
+  for (size_t u = 0; u < n; ++u)
+    if (lab_off[u + 1] == lab_off[u])
+      return fail(CTCDEC_ERR_ARG, "utterance " + std::to_string(u) + ": a target needs at least one label");
+  const auto t_begin = Clock::now();
+  std::unique_ptr<ctcdec_alignment> res(new ctcdec_alignment());
+  const int64_t NL = lab_off[n], NS = slot_off[n];
+  std::vector<int64_t> row0(n + 1, 0);
+  for (size_t u = 0; u < n; ++u) row0[u + 1] = row0[u] + utt_frames[u];
+  const int64_t R = row0[n];
+  res->has_gaps = true;
+  res->path_off = row0;
+  res->tok_off = lab_off;
+  res->label.assign(labels.begin(), labels.begin() + NL);
+  res->path.resize((size_t)R);
+  res->start.assign((size_t)NL, 0);
+  res->end.assign((size_t)NL, 0);
+  res->score.assign(n, 0.0);
+  res->has_logp = fold != 0;
+  if (fold) res->logp.assign((size_t)NL, 0.0);
+  std::vector<double> slot_logp((size_t)NS, 0.0);
+  if (n > 0) {  // (every utterance has a label, so a frame: R >= n)
+    std::string err;
+    std::lock_guard<std::mutex> device_lock(g_device_mu);
+    if (be::bind_thread(&err)) return fail(CTCDEC_ERR_DEVICE, err);
+    AlignFront fr;
+    fr.want_max = true;
+    if (int rc = align_front(dec, utt_logits, utt_frames, n_utts, dtype, is_device, V, row0, fr)) return rc;
+    res->ms[0] = fr.sniff_ms;
+    if (dec->w_apath.ensure((size_t)R * 4, &err) || dec->w_alab.ensure((size_t)NL * 4, &err) || dec->w_atok.ensure((size_t)NL * 8, &err) ||
+        dec->w_atlp.ensure((size_t)NL * 8, &err) || dec->w_ascore.ensure(n * 8, &err) || dec->w_agap.ensure((size_t)NS, &err) ||
+        dec->w_aglp.ensure((size_t)NS * 8, &err))
+      return fail(CTCDEC_ERR_DEVICE, err);
+    if (be::h2d(dec->w_alab.p, labels.data(), (size_t)NL * 4, &err) || be::h2d(dec->w_agap.p, slot_gap.data(), (size_t)NS, &err) ||
+        be::zero(dec->w_atok.p, (size_t)NL * 8, &err) || be::zero(dec->w_atlp.p, (size_t)NL * 8, &err) ||
+        be::zero(dec->w_ascore.p, n * 8, &err) || be::zero(dec->w_aglp.p, (size_t)NS * 8, &err))
+      return fail(CTCDEC_ERR_DEVICE, err);
+    // launches: utterances in input order until their back-pointer tables fill the budget; longest first inside a launch
+    // (ctcdec_align_batch's rule)
+    std::vector<std::vector<int32_t>> groups;
+    int64_t used = 0, most = 0;
+    for (int32_t u = 0; u < n_utts; ++u) {
+      const int64_t bytes = (int64_t)utt_frames[u] * align_chunks((int32_t)(lab_off[(size_t)u + 1] - lab_off[(size_t)u]));
+      if (groups.empty() || used + bytes > budget) {
+        groups.emplace_back();
+        used = 0;
+      }
+      groups.back().push_back(u);
+      used += bytes;
+      most = std::max(most, used);
+    }
+    if (dec->w_abp.ensure((size_t)std::max<int64_t>(most, 1), &err)) return fail(CTCDEC_ERR_DEVICE, err);
+    const double clip_lo = log(1e-15);  // ln(MIN_TOKEN_CLIP_P) (constants.py:17)
+    std::vector<GapsUtt> utts;
+    for (auto& g : groups) {
+      std::stable_sort(g.begin(), g.end(), [&](int32_t a, int32_t b) { return utt_frames[a] > utt_frames[b]; });
+      utts.clear();
+      int64_t bp_off = 0;
+      int32_t max_chunks = 1;
+      for (int32_t u : g) {
+        const int64_t lo = lab_off[(size_t)u], so = slot_off[(size_t)u];
+        const int32_t L = (int32_t)(lab_off[(size_t)u + 1] - lo);
+        GapsUtt a;
+        a.x = fr.ptrs[(size_t)u];
+        a.lse = fr.lse + row0[(size_t)u];
+        a.rmax = fr.rmax + row0[(size_t)u];
+        a.lab = (const int32_t*)dec->w_alab.p + lo;
+        a.gap = (const uint8_t*)dec->w_agap.p + so;
+        a.bp = (uint8_t*)dec->w_abp.p + bp_off;
+        a.path = (int32_t*)dec->w_apath.p + row0[(size_t)u];
+        a.tok_start = (int32_t*)dec->w_atok.p + lo;
+        a.tok_end = (int32_t*)dec->w_atok.p + NL + lo;
+        a.tok_logp = (double*)dec->w_atlp.p + lo;
+        a.gap_logp = (double*)dec->w_aglp.p + so;
+        a.score = (double*)dec->w_ascore.p + u;
+        a.T = utt_frames[u];
+        a.L = L;
+        a.is_prob = fr.is_prob[(size_t)u] ? 1 : 0;
+        a.pad = 0;
+        utts.push_back(a);
+        bp_off += (int64_t)utt_frames[u] * align_chunks(L);
+        max_chunks = std::max(max_chunks, align_chunks(L));
+      }
+#ifdef CTC_SIM
+      std::vector<double> col((size_t)2 * (size_t)max_chunks);
+      AlignSeqCtx cx;
+      for (const GapsUtt& a : utts) {
+        if (dtype == 0) ctc_viterbi_gaps_utt<0>(cx, a, V, blank, fold, clip_lo, col.data());
+        else if (dtype == 1) ctc_viterbi_gaps_utt<1>(cx, a, V, blank, fold, clip_lo, col.data());
+        else if (dtype == 2) ctc_viterbi_gaps_utt<2>(cx, a, V, blank, fold, clip_lo, col.data());
+        else ctc_viterbi_gaps_utt<3>(cx, a, V, blank, fold, clip_lo, col.data());
+      }
+#else
+      if (upload(dec->w_agutts, utts, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+      be::ViterbiGapsArgs va;
+      va.utts = (const GapsUtt*)dec->w_agutts.p;
+      va.n_utts = (int32_t)utts.size();
+      va.n_labels = V;
+      va.dtype = dtype;
+      va.blank = blank;
+      va.fold = fold;
+      va.max_chunks = max_chunks;
+      va.clip_lo = clip_lo;
+      if (be::launch_ctc_viterbi_gaps(va, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+#endif
+      ++res->launches;
+    }
+    if (be::d2h(res->path.data(), dec->w_apath.p, (size_t)R * 4, &err) || be::d2h(res->score.data(), dec->w_ascore.p, n * 8, &err) ||
+        be::d2h(res->start.data(), dec->w_atok.p, (size_t)NL * 4, &err) ||
+        be::d2h(res->end.data(), (const int32_t*)dec->w_atok.p + NL, (size_t)NL * 4, &err) ||
+        (fold && be::d2h(res->logp.data(), dec->w_atlp.p, (size_t)NL * 8, &err)) ||
+        be::d2h(slot_logp.data(), dec->w_aglp.p, (size_t)NS * 8, &err))
+      return fail(CTCDEC_ERR_DEVICE, err);
+#ifndef CTC_SIM
+    be::align_gaps_timing(&res->ms[1], &res->ms[2]);
+#endif
+  }
+  // the gaps, in target order: everything between the end of the label before and the start of the label after
+  res->gap_off.assign(n + 1, 0);
+  for (size_t u = 0; u < n; ++u) {
+    const int64_t lo = lab_off[u], L = lab_off[u + 1] - lo;
+    for (int64_t j = 0; j <= L; ++j) {
+      if (!slot_gap[(size_t)(slot_off[u] + j)]) continue;
+      res->gap_start.push_back(j > 0 ? res->end[(size_t)(lo + j - 1)] : 0);
+      res->gap_end.push_back(j < L ? res->start[(size_t)(lo + j)] : utt_frames[u]);
+      res->gap_logp.push_back(slot_logp[(size_t)(slot_off[u] + j)]);
+    }
+    res->gap_off[u + 1] = (int64_t)res->gap_start.size();
+  }
+  res->ms[3] = ms(t_begin, Clock::now());
+  *out = res.release();
+  return CTCDEC_OK;
+}
+
+int ctcdec_alignment_gaps(const ctcdec_alignment* a, const int64_t** gap_off_out, const int32_t** start_out, const int32_t** end_out,
+                          const double** logp_out, int64_t* n_gaps_out) {
+  if (!a || !gap_off_out || !start_out || !end_out || !logp_out || !n_gaps_out) return fail(CTCDEC_ERR_ARG, "no alignment");
+  if (!a->has_gaps) return fail(CTCDEC_ERR_ARG, "the alignment was made without gaps (ctcdec_align_batch)");
+  *gap_off_out = a->gap_off.data();
+  *start_out = a->gap_start.data();
+  *end_out = a->gap_end.data();
+  *logp_out = a->gap_logp.data();
+  *n_gaps_out = (int64_t)a->gap_start.size();
+  return CTCDEC_OK;
+}
 
 // ---- transcript likelihood ("Transcript likelihood") -----------------------------------------------------------
 }  // extern "C"

@@ -297,10 +297,28 @@ struct FindArgs {
   double min_logp;     // a hit's least score (-inf: none)
 };
 int launch_ctc_find(const FindArgs& a, int wave, std::string* err);
+// Alignment with gaps. row_lse_max: row_lse (the same bits in a.lse) that also stores each row's largest entry that is not a
+// NaN in rmax -- for the rows of probability-like utterances too, which get no log-sum-exp. ctc_viterbi_gaps: one workgroup
+// per entry of `utts`, all of them validated by the host (GapsUtt); 256 threads when every utterance of the launch has at
+// most 256 groups of states, else 1024
+int launch_row_lse_max(const RowLseArgs& a, double* rmax, std::string* err);
+struct ViterbiGapsArgs {
+  const GapsUtt* utts;  // [n_utts] (device)
+  int32_t n_utts;
+  int32_t n_labels;
+  int32_t dtype;
+  int32_t blank;
+  int32_t fold;        // 0, LOGP_MEAN / LOGP_MIN / LOGP_MAX
+  int32_t max_chunks;  // the largest align_chunks(L) of the launch: sizes the two columns in LDS
+  double clip_lo;      // ln(MIN_TOKEN_CLIP_P)
+};
+int launch_ctc_viterbi_gaps(const ViterbiGapsArgs& a, std::string* err);
 // kernel times (HIP events) of the launch_row_lse / launch_ctc_viterbi / launch_ctc_forward / launch_ctc_posteriors /
-// launch_ctc_grad_rows / launch_ctc_find calls since the last reset; waits for the kernels
+// launch_ctc_grad_rows / launch_ctc_find / launch_row_lse_max / launch_ctc_viterbi_gaps calls since the last reset; waits
+// for the kernels
 void align_timing_reset();
 void align_timing(double* row_lse_ms, double* viterbi_ms);
+void align_gaps_timing(double* row_lse_max_ms, double* viterbi_gaps_ms);
 double forward_timing();
 double posteriors_timing();
 double grad_rows_timing();

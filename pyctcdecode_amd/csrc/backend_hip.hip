@@ -2371,6 +2371,10 @@ int launch_ctc_find_on(const FindArgs& a, int wave, hipStream_t stream, std::str
 int launch_ctc_find(const FindArgs& a, int wave, std::string* err) { return launch_ctc_find_on(a, wave, g_stream, err); }
 int launch_row_lse(const RowLseArgs& a, std::string* err) { return launch_row_lse_on(a, g_stream, err); }
 int launch_ctc_viterbi(const ViterbiArgs& a, std::string* err) { return launch_ctc_viterbi_on(a, g_stream, err); }
+int launch_row_lse_max_on(const RowLseArgs& a, double* rmax, hipStream_t stream, std::string* err);
+int launch_row_lse_max(const RowLseArgs& a, double* rmax, std::string* err) { return launch_row_lse_max_on(a, rmax, g_stream, err); }
+int launch_ctc_viterbi_gaps_on(const ViterbiGapsArgs& a, hipStream_t stream, std::string* err);
+int launch_ctc_viterbi_gaps(const ViterbiGapsArgs& a, std::string* err) { return launch_ctc_viterbi_gaps_on(a, g_stream, err); }
 
 // Survivor ledger, append (surv_ledger.h): one wavefront per stream. A step takes 64 of the chunk's rows, one per lane: the
 // clamped counts are scanned across the wave (DPP, no LDS, no barrier), the running offset of the stream is wave-uniform and

@@ -5,9 +5,11 @@
 // posteriors of a label sequence ("Frame posteriors"): the forward-backward over the same states; and the gradient
 // of the likelihood with respect to the frames' entries ("Transcript gradient"): the posteriors folded by label,
 // row by row; and the search for a phrase inside an utterance ("Phrase search"): the Viterbi recursion with a free
-// start and a free end, and the selection of its hits. One body each for the HIP kernels (ctc_align_hip.hip: row_lse,
-// ctc_viterbi, ctc_forward, ctc_forward_wave, ctc_posteriors, ctc_grad_rows, ctc_find, ctc_find_wave) and for the CPU simulator
-// build, whose "device" memory is host memory (api.cpp under CTC_SIM runs them with a one-thread context).
+// start and a free end, and the selection of its hits; and the alignment of a target with gaps ("Alignment with
+// gaps"): the row maximum next to the row's log-sum-exp, and the Viterbi recursion with its states in registers and slots that
+// take a frame's best entry. One body each for the HIP kernels (ctc_align_hip.hip: row_lse, ctc_viterbi, ctc_forward,
+// ctc_forward_wave, ctc_posteriors, ctc_grad_rows, ctc_find, ctc_find_wave, row_lse_max, ctc_viterbi_gaps) and for the CPU
+// simulator build, whose "device" memory is host memory (api.cpp under CTC_SIM runs them with a one-thread context).
 #pragma once
 #include <math.h>
 #include <stddef.h>
@@ -1067,6 +1069,256 @@ CTC_HD void ctc_find_wave_phrase(Ctx& cx, const FindPhrase& ph, int V, int blank
   }
   cx.publish();
   find_select(cx, ph, max_hits, min_logp);
+}
+
+// ---- row_lse_max / ctc_viterbi_gaps ------------------------------------------------------------------------------------------
+// Forced alignment of a target with gaps ("Alignment with gaps"). The states are ctc_viterbi's, S = 2L + 1: even
+// state 2j is slot j (before label j; slot L follows the last label), odd state 2k + 1 is label k. A plain slot emits the
+// blank; a gap slot emits g(t) = align_emit_of_value(largest entry of row t that is not a NaN, lse[t], ...): the best any
+// label or the blank has in that frame, so the gap takes the frames nobody transcribed at the price the best unconstrained
+// path would pay for them. Transitions are ctc_viterbi's. Equal scores prefer stay, then step, then skip in label states and
+// plain slots; in a gap slot they prefer step over stay -- where a target label is its row's maximum, g(t) and the label's
+// emission are the same bits, and this is the rule under which such a frame goes to the label at both of its ends.
+
+// One row, one thread: row_lse_seq's blocks in row_lse_seq's order, and the running maximum that the sum was scaled by -- the
+// largest entry that is not a NaN (-inf for a row without one). A probability-like row takes the maximum alone.
+CTC_HD void row_lse_max_seq(const void* x, int dtype, size_t row0, int V, bool is_prob, double* lse_out, double* max_out) {
+  if (is_prob) {
+    double m = align_neg_inf();
+    for (int i = 0; i < V; ++i) {
+      const double v = align_load(x, dtype, row0 + (size_t)i);
+      m = v > m ? v : m;
+    }
+    *max_out = m;
+    return;
+  }
+  LseAcc a = lse_empty();
+  double v[ALIGN_LSE_BLOCK];
+  for (int b = 0; b < V; b += ALIGN_LSE_BLOCK) {
+    for (int i = 0; i < ALIGN_LSE_BLOCK; ++i) v[i] = b + i < V ? align_load(x, dtype, row0 + (size_t)(b + i)) : align_neg_inf();
+    lse_push_block(a, v);
+  }
+  *lse_out = lse_value(a);
+  *max_out = a.m;
+}
+
+// One utterance of a ctc_viterbi_gaps launch. The host validates every field before a launch: the labels are in [0, V) and
+// not the blank, L >= 1, T >= L + (adjacent equal labels), and every array is as long as its comment says.
+struct GapsUtt {
+  const void* x;        // [T, V] logits or probabilities, of the launch's dtype
+  const double* lse;    // [T] log-sum-exp of each row (not read when is_prob)
+  const double* rmax;   // [T] largest entry of each row that is not a NaN
+  const int32_t* lab;   // [L] target labels
+  const uint8_t* gap;   // [L + 1] 1: the slot is a gap
+  uint8_t* bp;          // [T * align_chunks(L)] back-pointers, four 2-bit entries per byte
+  int32_t* path;        // [T] out: the label taken at each frame, the blank id in a plain slot, -1 in a gap slot
+  int32_t* tok_start;   // [L] out: first frame of each target label
+  int32_t* tok_end;     // [L] out: one past its last frame
+  double* tok_logp;     // [L] out (fold != 0): the fold of the label's log-probability over [tok_start, tok_end)
+  double* gap_logp;     // [L + 1] out, gap slots only: the sum of g(t) over the slot's frames, in frame order
+  double* score;        // [1] out: the sum of the log-probabilities along `path`
+  int32_t T, L, is_prob, pad;
+};
+
+// One frame of one group (slot 2c, label 2c, slot 2c + 1, label 2c + 1: ForwardGroup), in place: p the group's scores at the
+// frame before, pm1 that of the last state of the group below. gap0 / gap2: the group's two slots are gaps; e_gap = g(t).
+// Returns the group's byte of back-pointers (0 stay, 1 step, 2 skip; state j in bits 2j, 2j + 1). Nothing but compares and
+// additions -- ctc_viterbi's, operand for operand, where no slot is a gap: the same operands give the same bits wherever this
+// is inlined.
+CTC_HD unsigned gap_step(const ForwardGroup& g, bool gap0, bool gap2, double pm1, double e_blank, double e_gap, double e0, double e1,
+                         double* p) {
+  const double NEG = align_neg_inf();
+  const double p0 = p[0], p1 = p[1], p2 = p[2], p3 = p[3];
+  unsigned bp = 0;
+  double b = p0;
+  if (gap0 ? (pm1 >= b && pm1 > NEG) : pm1 > b) b = pm1, bp = 1u;
+  p[0] = b + (gap0 ? e_gap : e_blank);
+  if (g.l0 >= 0) {
+    unsigned q = 0;
+    b = p1;
+    if (p0 > b) b = p0, q = 1u;
+    if (g.skip0 && pm1 > b) b = pm1, q = 2u;
+    bp |= q << 2;
+    p[1] = b + e0;
+  } else {
+    p[1] = NEG;
+  }
+  if (g.blank2) {
+    unsigned q = 0;
+    b = p2;
+    if (gap2 ? (p1 >= b && p1 > NEG) : p1 > b) b = p1, q = 1u;
+    bp |= q << 4;
+    p[2] = b + (gap2 ? e_gap : e_blank);
+  } else {
+    p[2] = NEG;
+  }
+  if (g.l1 >= 0) {
+    unsigned q = 0;
+    b = p3;
+    if (p2 > b) b = p2, q = 1u;
+    if (g.skip1 && p1 > b) b = p1, q = 2u;
+    bp |= q << 6;
+    p[3] = b + e1;
+  } else {
+    p[3] = NEG;
+  }
+  return bp;
+}
+
+// ctc_viterbi_gaps: the threads of cx (tid, nt, sync(); Ctx::GROUPS * nt >= align_chunks(L)) share one utterance of a matrix of
+// dtype DT, arranged as ctc_forward_hyp / ctc_find_phrase are: thread tid owns the groups tid, tid + nt, ... for the whole
+// recursion, their scores stay in registers, and only a group's last state goes through `col` -- 2 * align_chunks(L) doubles,
+// the columns of two successive frames -- to the thread that owns the group above: one barrier per frame. Frame t + 1's
+// entries (the blank, the group's labels, the row's log-sum-exp and maximum) are requested before frame t's arithmetic and
+// kept as loaded. Per frame and group one byte of back-pointers, neighbouring threads writing neighbouring bytes. No window
+// of reachable states: every state exists in every frame, and all but states 0 and 1 begin at -inf (every emission is finite,
+// so -inf stays -inf until a path arrives; a state no path can leave towards the end is never traced). After the last frame
+// the thread that owns the last state walks the back-pointers, as ctc_viterbi's does; then one thread per label folds its
+// confidence and one thread per gap sums g(t) over the gap's frames.
+template <int DT, class Ctx>
+CTC_HD void ctc_viterbi_gaps_utt(Ctx& cx, const GapsUtt& utt, int V, int blank, int fold, double clip_lo, double* col) {
+  typedef typename AlignRaw<DT>::type Raw;
+  constexpr int G = Ctx::GROUPS;
+  const void* const x = utt.x;  // (the record, once: the frame loop reads none of it again)
+  const double* const lse = utt.lse;
+  const double* const rmax = utt.rmax;
+  const int32_t* const lab = utt.lab;
+  const uint8_t* const gap = utt.gap;
+  uint8_t* const bps = utt.bp;
+  const int T = utt.T, L = utt.L;
+  const bool is_prob = utt.is_prob != 0;
+  if (T <= 0 || L <= 0) return;
+  const int S = 2 * L + 1, nch = align_chunks(L);
+  const double NEG = align_neg_inf();
+  ForwardGroup g[G];
+  bool gap0[G], gap2[G];
+  int i0[G], i1[G];  // the columns a group's two labels read (the blank's where the target ends before them)
+  double p[G][4];    // scores
+  Raw v0[G], v1[G];  // the entries of the frame in hand at those columns, as loaded
+  CTC_UNROLL
+  for (int k = 0; k < G; ++k) {
+    const int c = cx.tid + k * cx.nt;
+    p[k][0] = p[k][1] = p[k][2] = p[k][3] = NEG;
+    if (c < nch) g[k] = forward_group(lab, L, c);
+    else g[k] = ForwardGroup{-1, -1, false, false, false};
+    gap0[k] = c < nch && 2 * c <= L && gap[2 * c] != 0;
+    gap2[k] = c < nch && 2 * c + 1 <= L && gap[2 * c + 1] != 0;
+    i0[k] = g[k].l0 >= 0 ? g[k].l0 : blank;
+    i1[k] = g[k].l1 >= 0 ? g[k].l1 : blank;
+  }
+  // (always 0, but per thread as far as the compiler knows: a row's log-sum-exp and maximum then come by vector loads, as in
+  // ctc_forward_hyp)
+  const int per_thread_zero = g[0].l0 == -2 ? 1 : 0;
+  const double* const lse_v = (is_prob ? rmax : lse) + per_thread_zero;  // (probabilities: any valid address, never used)
+  const double* const max_v = rmax + per_thread_zero;
+  for (int i = cx.tid; i < 2 * nch; i += cx.nt) col[i] = NEG;
+  if (cx.tid == 0) {  // frame 0: states 0 and 1
+    const double lse0 = is_prob ? 0.0 : lse[0];
+    p[0][0] = gap0[0] ? align_emit_of_value(rmax[0], lse0, is_prob, clip_lo) : align_emit(x, DT, (size_t)blank, lse0, is_prob, clip_lo);
+    p[0][1] = align_emit(x, DT, (size_t)lab[0], lse0, is_prob, clip_lo);
+  }
+  cx.sync();
+  // frame 1's entries (a single frame: frame 0's again, never used)
+  const size_t row1 = T > 1 ? (size_t)V : 0;
+  Raw vb = align_load_raw<DT>(x, row1 + (size_t)blank);
+  double lse_t = lse_v[T > 1 ? 1 : 0], max_t = max_v[T > 1 ? 1 : 0];
+  CTC_UNROLL
+  for (int k = 0; k < G; ++k) {
+    v0[k] = align_load_raw<DT>(x, row1 + (size_t)i0[k]);
+    v1[k] = align_load_raw<DT>(x, row1 + (size_t)i1[k]);
+  }
+  for (int t = 1; t < T; ++t) {
+    const double* prev = col + ((t - 1) & 1) * nch;
+    double* cur = col + (t & 1) * nch;
+    double pm1[G];
+    CTC_UNROLL
+    for (int k = 0; k < G; ++k) {
+      const int c = cx.tid + k * cx.nt;
+      pm1[k] = c > 0 && c < nch ? prev[c - 1] : NEG;
+    }
+    // then ask for frame t + 1 (after the last frame: the last frame again)
+    const int tn = t + 1 < T ? t + 1 : t;
+    const size_t row = (size_t)tn * (size_t)V;
+    const Raw nvb = align_load_raw<DT>(x, row + (size_t)blank);
+    const double nlse = lse_v[tn], nmax = max_v[tn];
+    Raw n0[G], n1[G];
+    CTC_UNROLL
+    for (int k = 0; k < G; ++k) {
+      n0[k] = align_load_raw<DT>(x, row + (size_t)i0[k]);
+      n1[k] = align_load_raw<DT>(x, row + (size_t)i1[k]);
+    }
+    const double lse_use = is_prob ? 0.0 : lse_t;
+    const double e_blank = align_emit_of_value(align_widen<DT>(vb), lse_use, is_prob, clip_lo);
+    const double e_gap = align_emit_of_value(max_t, lse_use, is_prob, clip_lo);
+    uint8_t* const bp_row = bps + (size_t)t * (size_t)nch;
+    CTC_UNROLL
+    for (int k = 0; k < G; ++k) {
+      const int c = cx.tid + k * cx.nt;
+      if (c >= nch) continue;
+      const double e0 = align_emit_of_value(align_widen<DT>(v0[k]), lse_use, is_prob, clip_lo);
+      const double e1 = align_emit_of_value(align_widen<DT>(v1[k]), lse_use, is_prob, clip_lo);
+      const unsigned b = gap_step(g[k], gap0[k], gap2[k], pm1[k], e_blank, e_gap, e0, e1, p[k]);
+      cur[c] = p[k][3];
+      bp_row[c] = (uint8_t)b;
+    }
+    vb = nvb, lse_t = nlse, max_t = nmax;
+    CTC_UNROLL
+    for (int k = 0; k < G; ++k) v0[k] = n0[k], v1[k] = n1[k];
+    cx.sync();  // the one barrier of a frame: the columns swap roles
+  }
+  // back-trace, by the thread that holds the last slot (state S - 1 = 2L: entry 0 or 2 of its group; the last label is the
+  // entry before it). The last label is preferred over the trailing slot.
+  const int cf = (S - 1) >> 2, jf = (S - 1) & 3;
+  const double* fin = col + ((T - 1) & 1) * nch;
+  CTC_UNROLL
+  for (int k = 0; k < G; ++k) {
+    if (cx.tid + k * cx.nt != cf) continue;
+    const double last = jf == 2 ? p[k][2] : p[k][0];
+    const double before = jf == 2 ? p[k][1] : fin[cf - 1];  // (L >= 1: jf == 0 only in a group above the first)
+    int s = before >= last ? S - 2 : S - 1;
+    *utt.score = before >= last ? before : last;
+    int open = -1;
+    for (int t = T - 1; t >= 0; --t) {
+      if (s & 1) {
+        const int kk = s >> 1;
+        if (kk != open) utt.tok_end[kk] = t + 1, open = kk;
+        utt.tok_start[kk] = t;
+        utt.path[t] = lab[kk];
+      } else {
+        utt.path[t] = gap[s >> 1] ? -1 : blank;
+      }
+      if (t > 0) {
+        const unsigned b = (bps[(size_t)t * (size_t)nch + (size_t)(s >> 2)] >> (2 * (s & 3))) & 3u;
+        s -= (int)b;
+        if (s < 0) s = 0;
+      }
+    }
+  }
+  cx.sync();  // (the spans that thread wrote are read by every thread)
+  for (int j = cx.tid; j <= L; j += cx.nt) {
+    if (!gap[j]) continue;
+    int t0 = j > 0 ? utt.tok_end[j - 1] : 0, t1 = j < L ? utt.tok_start[j] : T;
+    t0 = t0 < 0 ? 0 : t0;
+    t1 = t1 > T ? T : t1;
+    double acc = 0.0;
+    for (int t = t0; t < t1; ++t) acc += align_emit_of_value(rmax[t], is_prob ? 0.0 : lse[t], is_prob, clip_lo);
+    utt.gap_logp[j] = acc;
+  }
+  if (!fold) return;
+  for (int k = cx.tid; k < L; k += cx.nt) {
+    int t0 = utt.tok_start[k], t1 = utt.tok_end[k];
+    t0 = t0 < 0 ? 0 : t0;
+    t1 = t1 > T ? T : t1;
+    const size_t lb = (size_t)lab[k];
+    double acc = 0.0;
+    for (int t = t0; t < t1; ++t) {
+      const double lp = align_emit(x, DT, (size_t)t * (size_t)V + lb, is_prob ? 0.0 : lse[t], is_prob, clip_lo);
+      if (fold == LOGP_MEAN) acc += lp;
+      else if (fold == LOGP_MIN) acc = (t == t0 || lp < acc) ? lp : acc;
+      else acc = (t == t0 || lp > acc) ? lp : acc;
+    }
+    utt.tok_logp[k] = fold == LOGP_MEAN ? acc / (double)(t1 - t0) : acc;
+  }
 }
 
 }  // namespace ctc

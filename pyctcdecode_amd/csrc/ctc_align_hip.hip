@@ -3,7 +3,8 @@
 // ctc_forward_wave, the sum over all alignments of a hypothesis, one workgroup / one wavefront each; ctc_posteriors, the
 // forward-backward of an utterance's transcript, one workgroup each; ctc_grad_rows, the gradient of the likelihood from the
 // posteriors a dense ctc_posteriors launch left, row by row; ctc_find and ctc_find_wave, the occurrences of a phrase inside
-// an utterance, one workgroup / one wavefront each. A translation unit of its own.
+// an utterance, one workgroup / one wavefront each; row_lse_max and ctc_viterbi_gaps, the alignment of a target with gaps, one
+// workgroup per utterance with its states in registers. A translation unit of its own.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -275,6 +276,99 @@ __global__ __launch_bounds__(ALIGN_THREADS) void ctc_find_wave(FindArgs a) {
   ctc_find_wave_phrase<DT>(cx, a.phrases[i], a.n_labels, a.blank, a.clip_lo, a.max_hits, a.min_logp);
 }
 
+// ---------------------------------------------------------------------------------------------
+// row_lse_max: row_lse that also stores the row's largest entry that is not a NaN -- the m its (max, sum of exp) pair ends
+// with: a second 8 bytes per row, no new arithmetic. The same lanes fold the same values in the same order and the same
+// butterfly merges them, so the log-sum-exp has row_lse's bits, wherever the row lies in memory. The rows of a probability-
+// like utterance, which row_lse skips, take the same loads and a plain maximum, without an exponential. Every logit is
+// still read once.
+// ---------------------------------------------------------------------------------------------
+template <int G, int DT, bool MAX_ONLY>
+__device__ __forceinline__ LseAcc row_fold(const char* p, int V, int l) {
+  constexpr int ESZ = DT == 0 ? 4 : DT == 1 ? 8 : 2;      // bytes per element
+  constexpr int EPV = 16 / ESZ;                           // elements per 16-byte vector
+  constexpr int VPB = ALIGN_LSE_BLOCK / EPV;              // vectors per block of values
+  const bool vec = ((uintptr_t)p & 15u) == 0;
+  const int nvec = V / EPV, tail = nvec * EPV;
+  LseAcc acc = lse_empty();
+  for (int i = tail + l; i < V; i += G) {
+    const double v = align_load(p, DT, (size_t)i);
+    if (MAX_ONLY) acc.m = v > acc.m ? v : acc.m;
+    else lse_push(acc, v);
+  }
+  const uint4* pv = (const uint4*)p;
+  for (int base = 0; base < nvec; base += G * VPB) {
+    double v[ALIGN_LSE_BLOCK];
+    CTC_UNROLL
+    for (int j = 0; j < VPB; ++j) {
+      const int i = base + j * G + l;  // (neighbouring lanes, neighbouring 16-byte groups)
+      if (i >= nvec) {
+        CTC_UNROLL
+        for (int k = 0; k < EPV; ++k) v[j * EPV + k] = align_neg_inf();
+      } else if (vec) {
+        unpack16<DT>(pv[i], v + j * EPV);
+      } else {
+        CTC_UNROLL
+        for (int k = 0; k < EPV; ++k) v[j * EPV + k] = align_load(p, DT, (size_t)i * EPV + (size_t)k);
+      }
+    }
+    if (MAX_ONLY) {
+      CTC_UNROLL
+      for (int i = 0; i < ALIGN_LSE_BLOCK; ++i) acc.m = v[i] > acc.m ? v[i] : acc.m;
+    } else {
+      lse_push_block(acc, v);
+    }
+  }
+  CTC_UNROLL
+  for (int off = G / 2; off >= 1; off >>= 1) {
+    LseAcc o;
+    o.m = __shfl_xor(acc.m, off, G);
+    o.s = __shfl_xor(acc.s, off, G);
+    if (MAX_ONLY) acc.m = o.m > acc.m ? o.m : acc.m;
+    else acc = lse_merge(acc, o);
+  }
+  return acc;
+}
+
+template <int G, int DT>
+__global__ __launch_bounds__(256) void row_lse_max(RowLseArgs a, double* rmax) {
+  constexpr int RPB = 256 / G;                            // rows per workgroup
+  constexpr int ESZ = DT == 0 ? 4 : DT == 1 ? 8 : 2;
+  const int64_t row = (int64_t)blockIdx.x * RPB + (int)(threadIdx.x / G);
+  const int l = (int)(threadIdx.x % G);
+  if (row >= a.n_rows) return;
+  int lo = 0, hi = a.n_utts;  // utt_row0[lo] <= row < utt_row0[hi]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (a.utt_row0[mid] <= row) lo = mid;
+    else hi = mid;
+  }
+  const int V = a.n_labels;
+  const char* p = (const char*)a.utt_logits[lo] + (size_t)(row - a.utt_row0[lo]) * (size_t)V * ESZ;
+  if (a.utt_is_prob[lo]) {  // (the whole group of lanes: `row` is theirs alone)
+    const LseAcc acc = row_fold<G, DT, true>(p, V, l);
+    if (l == 0) rmax[row] = acc.m;
+    return;
+  }
+  const LseAcc acc = row_fold<G, DT, false>(p, V, l);
+  if (l == 0) {
+    a.lse[row] = lse_value(acc);
+    rmax[row] = acc.m;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// ctc_viterbi_gaps: one workgroup per utterance, one group of four states per thread in registers (256 threads up to 511
+// labels, 1024 above), the groups' last states in two LDS columns (at most 16 KB), one barrier and one byte of back-pointers
+// per group and frame (ctc_align.h)
+// ---------------------------------------------------------------------------------------------
+template <int NT, int DT>
+__global__ __launch_bounds__(NT) void ctc_viterbi_gaps(ViterbiGapsArgs a) {
+  extern __shared__ double gaps_cols[];
+  ForwardGpuCtx cx{(int)threadIdx.x, NT};
+  ctc_viterbi_gaps_utt<DT>(cx, a.utts[blockIdx.x], a.n_labels, a.blank, a.fold, a.clip_lo, gaps_cols);
+}
+
 // kernel times: one pair of events per launch since the last reset
 struct EventLog {
   std::vector<hipEvent_t> ev;
@@ -297,9 +391,16 @@ struct EventLog {
     return sum;
   }
 };
-static EventLog g_lse_log, g_vit_log, g_fwd_log, g_post_log, g_grad_log, g_find_log;
+static EventLog g_lse_log, g_vit_log, g_fwd_log, g_post_log, g_grad_log, g_find_log, g_lsemax_log, g_vitgaps_log;
 
-void align_timing_reset() { g_lse_log.used = g_vit_log.used = g_fwd_log.used = g_post_log.used = g_grad_log.used = g_find_log.used = 0; }
+void align_timing_reset() {
+  g_lse_log.used = g_vit_log.used = g_fwd_log.used = g_post_log.used = g_grad_log.used = g_find_log.used = 0;
+  g_lsemax_log.used = g_vitgaps_log.used = 0;
+}
+void align_gaps_timing(double* row_lse_max_ms, double* viterbi_gaps_ms) {
+  *row_lse_max_ms = g_lsemax_log.total();
+  *viterbi_gaps_ms = g_vitgaps_log.total();
+}
 double forward_timing() { return g_fwd_log.total(); }
 double posteriors_timing() { return g_post_log.total(); }
 double grad_rows_timing() { return g_grad_log.total(); }
@@ -346,6 +447,58 @@ int launch_ctc_viterbi_on(const ViterbiArgs& a, hipStream_t stream, std::string*
   if (g_vit_log.next(&e0, err) || g_vit_log.next(&e1, err)) return -1;
   HIP_TRY_A(hipEventRecord(e0, stream));
   hipLaunchKernelGGL(ctc_viterbi, dim3((unsigned)a.n_utts), dim3(ALIGN_THREADS), lds, stream, a);
+  HIP_TRY_A(hipGetLastError());
+  HIP_TRY_A(hipEventRecord(e1, stream));
+  return 0;
+}
+
+template <int G>
+static void launch_row_lse_max_g(const RowLseArgs& a, double* rmax, hipStream_t stream) {
+  const dim3 grid((unsigned)((a.n_rows + (256 / G) - 1) / (256 / G))), block(256);
+  if (a.dtype == 0) hipLaunchKernelGGL((row_lse_max<G, 0>), grid, block, 0, stream, a, rmax);
+  else if (a.dtype == 1) hipLaunchKernelGGL((row_lse_max<G, 1>), grid, block, 0, stream, a, rmax);
+  else if (a.dtype == 2) hipLaunchKernelGGL((row_lse_max<G, 2>), grid, block, 0, stream, a, rmax);
+  else hipLaunchKernelGGL((row_lse_max<G, 3>), grid, block, 0, stream, a, rmax);
+}
+
+// (the lanes per row by the vocabulary alone, as launch_row_lse_on picks them: the same grouping, the same bits)
+int launch_row_lse_max_on(const RowLseArgs& a, double* rmax, hipStream_t stream, std::string* err) {
+  if (a.n_rows <= 0 || a.n_utts <= 0) return 0;
+  if (a.dtype < 0 || a.dtype > 3 || a.n_labels < 1 || a.n_rows > (int64_t)0x7FFFFFFF * 4 || !rmax) {
+    if (err) *err = "row_lse_max: bad arguments";
+    return -1;
+  }
+  hipEvent_t e0, e1;
+  if (g_lsemax_log.next(&e0, err) || g_lsemax_log.next(&e1, err)) return -1;
+  HIP_TRY_A(hipEventRecord(e0, stream));
+  if (a.n_labels >= 256) launch_row_lse_max_g<64>(a, rmax, stream);
+  else if (a.n_labels >= 32) launch_row_lse_max_g<16>(a, rmax, stream);
+  else launch_row_lse_max_g<4>(a, rmax, stream);
+  HIP_TRY_A(hipGetLastError());
+  HIP_TRY_A(hipEventRecord(e1, stream));
+  return 0;
+}
+
+template <int DT>
+static void launch_viterbi_gaps_dt(const ViterbiGapsArgs& a, hipStream_t stream) {
+  const size_t lds = (size_t)2 * (size_t)a.max_chunks * sizeof(double);  // <= 16 KB
+  if (a.max_chunks <= ALIGN_THREADS) hipLaunchKernelGGL((ctc_viterbi_gaps<ALIGN_THREADS, DT>), dim3((unsigned)a.n_utts), dim3(ALIGN_THREADS), lds, stream, a);
+  else hipLaunchKernelGGL((ctc_viterbi_gaps<FORWARD_THREADS_MAX, DT>), dim3((unsigned)a.n_utts), dim3(FORWARD_THREADS_MAX), lds, stream, a);
+}
+
+int launch_ctc_viterbi_gaps_on(const ViterbiGapsArgs& a, hipStream_t stream, std::string* err) {
+  if (a.n_utts <= 0) return 0;
+  if (a.dtype < 0 || a.dtype > 3 || a.max_chunks < 1 || a.max_chunks > align_chunks(ALIGN_MAX_LABELS)) {
+    if (err) *err = "ctc_viterbi_gaps: more states than the kernel holds";
+    return -1;
+  }
+  hipEvent_t e0, e1;
+  if (g_vitgaps_log.next(&e0, err) || g_vitgaps_log.next(&e1, err)) return -1;
+  HIP_TRY_A(hipEventRecord(e0, stream));
+  if (a.dtype == 0) launch_viterbi_gaps_dt<0>(a, stream);
+  else if (a.dtype == 1) launch_viterbi_gaps_dt<1>(a, stream);
+  else if (a.dtype == 2) launch_viterbi_gaps_dt<2>(a, stream);
+  else launch_viterbi_gaps_dt<3>(a, stream);
   HIP_TRY_A(hipGetLastError());
   HIP_TRY_A(hipEventRecord(e1, stream));
   return 0;

@@ -166,6 +166,30 @@ class AlignedText:
 
 
 @dataclasses.dataclass(frozen=True)
+class GappedAlignment:
+    """Where a transcript that does not cover all of the audio lies in it (BeamSearchDecoderCTC.align_gaps /
+    align_gaps_batch; DESIGN.md, "Alignment with gaps"): the best CTC path for a target in which a gap stands wherever
+    something was not transcribed. ``text`` is the normalised text with the marker where a gap stands, ``tokens`` the label
+    ids with -1 for each gap (adjacent gaps merged). ``path`` is the label id taken at each frame (int32 ``[T]``, the blank's
+    id for blanks, -1 on the frames a gap took), ``score`` the sum of the clipped log-probabilities along it, a gap frame
+    counting the best any label or the blank has in that frame. ``token_frames``, ``text_frames``, ``token_logp`` and
+    ``word_logp`` are AlignedText's: gaps are neither tokens nor words. ``gaps`` holds, per gap in target order, its frames
+    ``(start, end)`` (end exclusive; everything between the label before and the label after, so ``start == end`` for an empty
+    gap) and ``gap_logp`` the sum of the best log-probability of each of those frames."""
+
+    text: str
+    tokens: List[int]
+    path: np.ndarray
+    score: float
+    token_frames: List[Tuple[str, Frames]]
+    text_frames: List[WordFrames]
+    gaps: List[Frames]
+    gap_logp: List[float]
+    token_logp: Optional[List[float]] = None
+    word_logp: Optional[List[float]] = None
+
+
+@dataclasses.dataclass(frozen=True)
 class ScoredText:
     """How probable a transcript is, given the audio (BeamSearchDecoderCTC.score / score_batch): ``logp`` is the CTC forward
     score of the label ids ``tokens`` -- the natural log of the sum, over all their alignments, of the product of the frames'
@@ -1198,6 +1222,10 @@ class BeamSearchDecoderCTC:
         self.last_find_timing_ms = (0.0, 0.0, 0.0, 0.0)
         self.last_find_launches = 0
         self.last_find_launched = (0, 0)
+        # ... and of the last align_gaps / align_gaps_batch call (ms: classification, row_lse_max, ctc_viterbi_gaps, native
+        # call; kernel launches made)
+        self.last_align_gaps_timing_ms = (0.0, 0.0, 0.0, 0.0)
+        self.last_align_gaps_launches = 0
 
     def __del__(self):
         h = getattr(self, "_handle", None)
@@ -1783,6 +1811,177 @@ class BeamSearchDecoderCTC:
                     tlp = [logp[o + k] for k in kept]
                     wlp = [min(tlp[lo:hi]) for _w, lo, hi in words]
                 out[u] = AlignedText(text, path[path_off[j]:path_off[j + 1]].copy(), float(score[j]), tok, wf, tlp, wlp)
+            return out
+
+    # -- alignment with gaps (no reference analogue; DESIGN.md, "Alignment with gaps") --------------------
+    def _gapped_targets(self, what: str, logits_list: Any, texts, tokens, gap: str):
+        """-> (logits_list, items): the checks align_gaps_batch makes of its arguments before anything is staged -- one
+        target per utterance, as a text (character alphabets) or as label ids, -1 standing for a gap; adjacent gaps merged."""
+        if not isinstance(gap, str) or gap == "" or gap.split() != [gap]:
+            raise ValueError("%s: the gap marker %r must be a non-empty string without whitespace" % (what, gap))
+        if gap in self._vocab2idx:
+            raise ValueError("%s: the gap marker %r is a label of the alphabet: choose another with gap=" % (what, gap))
+        if (texts is None) == (tokens is None):
+            raise ValueError("%s: give exactly one of texts and tokens" % what)
+        if texts is not None and self._is_bpe:
+            raise ValueError("a text has many segmentations under a BPE alphabet: give the target as tokens=")
+        if getattr(logits_list, "ndim", 0) != 3:
+            logits_list = list(logits_list)
+        n = len(logits_list)
+        given = texts if texts is not None else tokens
+        if isinstance(given, str) or len(given) != n:
+            raise ValueError("%s: %d targets for %d utterances" % (what, 1 if isinstance(given, str) else len(given), n))
+        blank, n_labels, space = self._vocab2idx[""], len(self._labels_list), self._vocab2idx.get(" ")
+        targets: List[List[int]] = []
+        for u, g in enumerate(given):
+            ids: List[int] = []
+            if texts is not None:
+                if not isinstance(g, str):
+                    raise ValueError("%s: texts[%d] is not a str" % (what, u))
+                for word in g.split():
+                    if word == gap:
+                        if not ids or ids[-1] != -1:  # (repeated markers are one gap)
+                            ids.append(-1)
+                        continue
+                    if ids and ids[-1] != -1:  # (the space label between two words; a gap absorbs the ones next to it)
+                        if space is None:
+                            raise ValueError("character ' ' of the text %r is not a label of the alphabet" % g)
+                        ids.append(space)
+                    ids.extend(self._target_of_text(word))
+            else:
+                for c in g:
+                    if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not -1 <= int(c) < n_labels or int(c) == blank:
+                        raise ValueError("%s: tokens[%d] holds %r: not a label id in [0, %d) other than the blank (%d), nor -1 for "
+                                         "a gap" % (what, u, c, n_labels, blank))
+                    if int(c) == -1 and ids and ids[-1] == -1:
+                        continue
+                    ids.append(int(c))
+            n_lab = sum(1 for c in ids if c != -1)
+            if n_lab == 0:
+                raise ValueError("%s: the target of utterance %d has no label: a gap alone aligns to everything" % (what, u))
+            if n_lab > ALIGN_MAX_LABELS:
+                raise ValueError("%s: utterance %d has %d target labels, above the limit of %d labels per utterance"
+                                 % (what, u, n_lab, ALIGN_MAX_LABELS))
+            targets.append(ids)
+        return logits_list, targets
+
+    def align_gaps(self, logits: Any, text: Optional[str] = None, tokens: Optional[Sequence[int]] = None, gap: str = "*",
+                   confidence: Optional[str] = None) -> "GappedAlignment":
+        """Alignment of one utterance to a transcript with gaps: align_gaps_batch of a batch of one."""
+        self._check_logits_dimension(logits)
+        return self.align_gaps_batch([logits], None if text is None else [text], tokens=None if tokens is None else [tokens],
+                                     gap=gap, confidence=confidence)[0]
+
+    def align_gaps_batch(self, logits_list: Any, texts: Optional[Sequence[str]] = None,
+                         tokens: Optional[Sequence[Sequence[int]]] = None, gap: str = "*", confidence: Optional[str] = None,
+                         strict: bool = True, _bp_budget: int = 0) -> List[Optional["GappedAlignment"]]:
+        """align_batch for transcripts that do not cover all of the audio, in one native call (row_lse_max +
+        ctc_viterbi_gaps, csrc/ctc_align_hip.hip), as GappedAlignment. In ``texts`` (character alphabets) a
+        whitespace-delimited word equal to ``gap`` is a gap: ``"* bugs * bunny"`` is something untranscribed, "bugs",
+        something untranscribed, "bunny" and then the end of the audio. The space labels that would stand next to a gap are
+        dropped -- the gap absorbs them --, and repeated markers are one gap. In ``tokens`` -1 is a gap. A gap takes, frame
+        by frame, the best log-probability any label or the blank has, so it costs what the best unconstrained path would
+        pay for its frames; it may be empty wherever a blank may be skipped. A target without gaps gives align_batch's
+        result. ``strict`` and the feasibility bound (frames >= labels plus adjacent equal labels) are align_batch's."""
+        fold = _confidence_fold(confidence)
+        logits_list, targets = self._gapped_targets("align_gaps", logits_list, texts, tokens, gap)
+        n, n_labels = len(targets), len(self._labels_list)
+        if n == 0:
+            return []
+        with self._call_lock:
+            batch = _Batch(logits_list, n_labels)
+            if batch.is_device and batch.device_index is not None and batch.device_index != self._device:
+                raise ValueError("the logits live on cuda:%d but this decoder was built for cuda:%d (one process per GPU: "
+                                 "LOCAL_RANK / CTCDEC_DEVICE pick the device)" % (batch.device_index, self._device))
+            frames = np.asarray(batch.frames, dtype=np.int32)
+            ptrs = np.asarray(batch.ptrs, dtype=np.uint64)
+            budget = int(_bp_budget) or ALIGN_BP_BUDGET
+            keep, bad = [], []
+            for u, items in enumerate(targets):
+                ids = [c for c in items if c != -1]
+                need = len(ids) + sum(1 for a, b in zip(ids, ids[1:]) if a == b)
+                (keep if int(frames[u]) >= need else bad).append(u)
+                table = int(frames[u]) * ((2 * len(ids) + 1 + 3) // 4)
+                if table > budget:
+                    raise ValueError("align_gaps: utterance %d needs a back-pointer table of %d bytes, above the memory budget of "
+                                     "%d bytes of one launch" % (u, table, budget))
+            if bad and strict:
+                raise ValueError("align_gaps: no path for utterances %s: fewer frames than target labels plus adjacent equal "
+                                 "labels" % bad)
+            out: List[Optional[GappedAlignment]] = [None] * n
+            if not keep:
+                return out
+            k_ptrs = np.ascontiguousarray(ptrs[keep])
+            k_frames = np.ascontiguousarray(frames[keep])
+            flat = np.array([c for u in keep for c in targets[u]], dtype=np.int32)
+            off = np.zeros(len(keep) + 1, dtype=np.int64)
+            off[1:] = np.cumsum([len(targets[u]) for u in keep])
+            res = C.c_void_p()
+            lib = self._lib
+            lib.check(lib.dll.ctcdec_align_gaps_batch(
+                self._handle, k_ptrs.ctypes.data_as(C.POINTER(C.c_void_p)), k_frames.ctypes.data_as(C.POINTER(C.c_int32)),
+                len(keep), batch.dtype, int(batch.is_device), flat.ctypes.data_as(C.POINTER(C.c_int32)), B.off_ptr(off), fold,
+                int(_bp_budget), C.byref(res)))
+            try:
+                po, pp, ps, nu = C.POINTER(C.c_int64)(), C.POINTER(C.c_int32)(), C.POINTER(C.c_double)(), C.c_int64()
+                lib.check(lib.dll.ctcdec_alignment_paths(res, C.byref(po), C.byref(pp), C.byref(ps), C.byref(nu)))
+                to, tl, ts, te, tp, nt = (C.POINTER(C.c_int64)(), C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)(),
+                                          C.POINTER(C.c_int32)(), C.POINTER(C.c_double)(), C.c_int64())
+                lib.check(lib.dll.ctcdec_alignment_tokens(res, C.byref(to), C.byref(tl), C.byref(ts), C.byref(te), C.byref(tp),
+                                                          C.byref(nt)))
+                go, gs, ge, gl, ng = (C.POINTER(C.c_int64)(), C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)(),
+                                      C.POINTER(C.c_double)(), C.c_int64())
+                lib.check(lib.dll.ctcdec_alignment_gaps(res, C.byref(go), C.byref(gs), C.byref(ge), C.byref(gl), C.byref(ng)))
+                n_lab = sum(1 for u in keep for c in targets[u] if c != -1)
+                n_gap = int(off[-1]) - n_lab
+                if int(nu.value) != len(keep) or int(nt.value) != n_lab or int(ng.value) != n_gap:
+                    raise B.NativeError("the alignment holds another number of utterances, tokens or gaps than was asked for")
+                path_off = np.ctypeslib.as_array(po, shape=(len(keep) + 1,)).tolist()
+                total = int(path_off[-1])
+                path = np.ctypeslib.as_array(pp, shape=(total,)).copy()
+                score = np.ctypeslib.as_array(ps, shape=(len(keep),)).tolist()
+                tok_off = np.ctypeslib.as_array(to, shape=(len(keep) + 1,)).tolist()
+                start = np.ctypeslib.as_array(ts, shape=(n_lab,)).tolist()
+                end = np.ctypeslib.as_array(te, shape=(n_lab,)).tolist()
+                logp = np.ctypeslib.as_array(tp, shape=(n_lab,)).tolist() if fold else []
+                gap_off = np.ctypeslib.as_array(go, shape=(len(keep) + 1,)).tolist()
+                g_start = np.ctypeslib.as_array(gs, shape=(n_gap,)).tolist() if n_gap else []
+                g_end = np.ctypeslib.as_array(ge, shape=(n_gap,)).tolist() if n_gap else []
+                g_logp = np.ctypeslib.as_array(gl, shape=(n_gap,)).tolist() if n_gap else []
+                ms, launches = (C.c_double * 4)(), C.c_int32()
+                lib.dll.ctcdec_alignment_timing(res, ms, C.byref(launches))
+                # [classification (frame-prune kernels), row_lse_max, ctc_viterbi_gaps (HIP events), whole native call]
+                self.last_align_gaps_timing_ms = tuple(float(v) for v in ms)
+                self.last_align_gaps_launches = int(launches.value)
+            finally:
+                lib.dll.ctcdec_alignment_free(res)
+            labels = self._labels_list
+            for j, u in enumerate(keep):
+                items, o = targets[u], tok_off[j]
+                # the runs of labels between the gaps: each has its own words (a gap ends a word)
+                parts, tok, wf, tlp, wlp, run = [], [], [], [], [], []
+                for c in items + [-1]:
+                    if c != -1:
+                        run.append(c)
+                        continue
+                    if run:
+                        text, kept, words = self._words_of_target(run)
+                        base = len(tok)
+                        tok.extend((labels[run[k]], (start[o + k], end[o + k])) for k in kept)
+                        wf.extend((w, (tok[base + lo][1][0], tok[base + hi - 1][1][1])) for w, lo, hi in words)
+                        if fold:
+                            tlp.extend(logp[o + k] for k in kept)
+                            wlp.extend(min(tlp[base + lo:base + hi]) for _w, lo, hi in words)
+                        if text:
+                            parts.append(text)
+                        o += len(run)
+                        run = []
+                    parts.append(gap)
+                parts.pop()  # (the sentinel's)
+                g0, g1 = gap_off[j], gap_off[j + 1]
+                out[u] = GappedAlignment(" ".join(parts), list(items), path[path_off[j]:path_off[j + 1]].copy(), float(score[j]), tok,
+                                         wf, list(zip(g_start[g0:g1], g_end[g0:g1])), g_logp[g0:g1], tlp if fold else None,
+                                         wlp if fold else None)
             return out
 
     def _many_targets_each(self, what: str, item: str, items: str, logits_list: Any, texts, tokens):

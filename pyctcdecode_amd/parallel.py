@@ -216,6 +216,11 @@ def find_batch_sharded(decoder, logits_list, texts=None, group=None, **kwargs):
     raise NotImplementedError("find_batch is not gathered over ranks: search each rank's slice with decoder.find_batch itself")
 
 
+def align_gaps_batch_sharded(decoder, logits_list, texts=None, group=None, **kwargs):
+    """Alignment with gaps is not sharded over ranks: each rank calls decoder.align_gaps_batch on its own slice."""
+    raise NotImplementedError("align_gaps_batch is not gathered over ranks: align each rank's slice with decoder.align_gaps_batch itself")
+
+
 def _device_worker(conn, device: int, decoder_dir: str, library: Optional[str]) -> None:
     """One worker process = one GPU (the native library binds one device per process): loads the saved decoder on its device and
     serves (method, logits, kwargs) requests until it is told to stop."""
@@ -362,6 +367,12 @@ class DevicePool:
         raise NotImplementedError("DevicePool does not shard find_batch: call decoder.find_batch on the process's own device")
 
     find = find_batch
+
+    def align_gaps_batch(self, logits_list, texts=None, **kwargs):
+        """Alignment with gaps runs on the calling process's own device: a pool does not shard it."""
+        raise NotImplementedError("DevicePool does not shard align_gaps_batch: call decoder.align_gaps_batch on the process's own device")
+
+    align_gaps = align_gaps_batch
 
     def decode_batch(self, logits_list, **kwargs) -> List[str]:
         if kwargs.get("token_frames") or kwargs.get("confidence") is not None:  # (texts, TokenFrames) per slice -> one of each, offsets rebased

@@ -6,11 +6,14 @@ substituted), each forward kernel forced in turn -- and at 64 utterances, with t
 for scale; then a sweep of target lengths on 256 utterances of random logits, which is what the wave / group threshold of
 ctcdec_score_batch rests on. Kernel times are HIP events on the decode stream (ctcdec_alignment_timing, ctcdec_score_batch,
 ctcdec_posteriors_timing).
-  python tools/align_bench.py [--out profiles/align_bench.txt] [--steps 3] [--legs align,score,posteriors,sweep,gradient,find]
+  python tools/align_bench.py [--out profiles/align_bench.txt] [--steps 3] [--legs align,score,posteriors,sweep,gradient,find,gaps]
 The gradient leg (not in the default set) times gradient_batch -- ctc_grad_rows alone, next to posteriors_batch(dense=False).
 The find leg (not in the default set either) times find_batch -- ctc_find / ctc_find_wave forced in turn, alternating: at the
 bench shape each utterance searched for 1 and for 8 phrases of 8 labels cut from its own decoded tokens, then 256 and 2048
 phrases of 15 / 127 / 511 labels on 256 utterances of random logits, next to ctc_viterbi and ctc_forward on the same batch.
+The gaps leg (not in the default set either) times align_gaps_batch next to align_batch on the same batch, alternating:
+row_lse_max against row_lse, ctc_viterbi_gaps on the gap-free targets against ctc_viterbi on the same targets, and
+ctc_viterbi_gaps again with a leading gap, a trailing gap and one gap at every word boundary.
 The 4096 utterances are 256 distinct ones repeated: no kernel's time depends on the rows being distinct."""
 import argparse
 import os
@@ -218,6 +221,58 @@ def find_sweep_lines(dec, steps):
     return lines
 
 
+def gaps_lines(dec, dev, targets, steps):
+    """align_batch and align_gaps_batch on the same batch, one warm-up round and then `steps` rounds that alternate between
+    align, the gap-free targets, a leading gap, a trailing gap and one gap at every word boundary (kernels alone, HIP events on
+    the decode stream; medians)."""
+    some = next(c for c, lab in enumerate(dec._alphabet.labels) if lab != "")
+    targets = [list(t) if len(t) else [some] for t in targets]  # (a target needs a label)
+
+    def between_words(t):
+        starts = {lo for _w, lo, _hi in dec._words_of_target(t)[2][1:]}  # (a BPE alphabet: every label is a token)
+        out = []
+        for k, c in enumerate(t):
+            if k in starts:
+                out.append(-1)
+            out.append(c)
+        return out
+
+    forms = [("no gap", targets),
+             ("leading gap", [[-1] + list(t) for t in targets]),
+             ("trailing gap", [list(t) + [-1] for t in targets]),
+             ("gap per word boundary", [between_words(t) for t in targets])]
+    n_gaps = float(np.mean([sum(1 for c in t if c == -1) for t in forms[3][1]]))
+    lse, vit = [], []
+    got = {name: ([], [], [], []) for name, _ in forms}
+    for step in range(steps + 1):
+        dec.align_batch(dev, tokens=targets)
+        ms = dec.last_align_timing_ms
+        if step:
+            lse.append(ms[1]), vit.append(ms[2])
+        for name, items in forms:
+            t0 = time.perf_counter()
+            out = dec.align_gaps_batch(dev, tokens=items)
+            wall = (time.perf_counter() - t0) * 1e3
+            ms = dec.last_align_gaps_timing_ms
+            if step:
+                for k, v in enumerate((ms[1], ms[2], ms[3], wall)):
+                    got[name][k].append(v)
+            assert all(a is not None and len(a.path) == T for a in out)
+    m = lambda v: float(np.median(v))  # noqa: E731
+    read = len(targets) * T * V * 4
+    lse_max = m([v for name, _ in forms for v in got[name][0]])
+    lines = ["  row_lse          %9.3f ms   row_lse_max %9.3f ms  (%.2f of row_lse; %.2f GB read: %.1f %% of the 8 TB/s peak)"
+             % (m(lse), lse_max, lse_max / m(lse), read / 1e9, 100.0 * read / (lse_max * 1e-3) / HBM_PEAK),
+             "  ctc_viterbi      %9.3f ms   (the same targets, the same run; %.2f us per frame of the launch)"
+             % (m(vit), m(vit) * 1e3 / T)]
+    for name, _ in forms:
+        g = got[name]
+        extra = "  (%.1f gaps on average)" % n_gaps if name.startswith("gap per") else ""
+        lines.append("  ctc_viterbi_gaps %9.3f ms   %-22s %.2f of ctc_viterbi  native call %9.3f ms  Python call %9.3f ms%s"
+                     % (m(g[1]), name, m(g[1]) / m(vit), m(g[2]), m(g[3]), extra))
+    return lines
+
+
 def time_forward(dec, dev, hyps, kernels, steps):
     """The forward kernels' time (HIP events) under each forced kernel: one warm-up call each, then `steps` rounds that
     alternate between them (clocks as they come: neither kernel gets the warmer half of the run). -> {kernel: median ms}"""
@@ -354,6 +409,8 @@ def main():
             lines += gradient_lines(dec, dev, targets, args.steps)
         if "find" in legs:
             lines += find_lines(dec, dev, targets, args.steps)
+        if "gaps" in legs:
+            lines += gaps_lines(dec, dev, targets, args.steps)
         del dev
     if "sweep" in legs:
         lines += sweep_lines(dec, max(args.steps, 5))
