@@ -14,6 +14,7 @@
 #include <memory>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -2315,10 +2316,76 @@ struct AlignSeqCtx {
 }  // namespace
 #endif
 
+// ---- what the transcript calls share ---------------------------------------------------------------------------------------
+// A call's constants: the alphabet's size, its blank and ln(MIN_TOKEN_CLIP_P) (constants.py:17)
+struct TranscriptCall {
+  int V = 0, blank = -1;
+  double clip_lo = 0;
+};
+
+// What every entry point checks first, in this order: the pointers and counts it reads (args_ok, the decoder among them),
+// the dtype, its own option (bad_option: the message, empty for a good one), the alphabet's blank.
+static int transcript_open(const ctcdec_decoder* dec, bool args_ok, int32_t dtype, const std::string& bad_option, TranscriptCall& tc) {
+  if (!args_ok) return fail(CTCDEC_ERR_ARG, "bad arguments");
+  if (dtype < CTCDEC_F32 || dtype > CTCDEC_BF16) return fail(CTCDEC_ERR_ARG, "dtype must be f32, f64, f16 or bf16");
+  if (!bad_option.empty()) return fail(CTCDEC_ERR_ARG, bad_option);
+  tc.V = (int)dec->alpha.labels.size();
+  for (int v = 0; v < tc.V && tc.blank < 0; ++v)
+    if (dec->alpha.labels[(size_t)v].empty()) tc.blank = v;
+  if (tc.blank < 0) return fail(CTCDEC_ERR_ARG, "the alphabet has no blank label");
+  tc.clip_lo = log(1e-15);
+  return CTCDEC_OK;
+}
+static std::string bad_fold(int32_t fold) {
+  return fold != 0 && fold != LOGP_MEAN && fold != LOGP_MIN && fold != LOGP_MAX ? "unknown confidence fold" : "";
+}
+static std::string bad_kernel(int32_t kernel) {
+  return kernel < 0 || kernel > 2 ? "kernel must be 0 (the library chooses), 1 (wave) or 2 (group)" : "";
+}
+
+// Where each utterance's rows start among the rows of the call: [n + 1]
+static std::vector<int64_t> row_starts(const int32_t* frames, size_t n) {
+  std::vector<int64_t> row0(n + 1, 0);
+  for (size_t u = 0; u < n; ++u) row0[u + 1] = row0[u] + frames[u];
+  return row0;
+}
+
+// The launches of a call: items in input order until their tables fill the budget. An item without a table (bytes_of(i) == 0:
+// no frames, or nothing to launch) is in none of them. Returns the bytes of the largest launch's tables.
+template <class BytesOf>
+static int64_t budget_groups(int32_t n, BytesOf bytes_of, int64_t budget, std::vector<std::vector<int32_t>>& groups) {
+  int64_t used = 0, most = 0;
+  for (int32_t i = 0; i < n; ++i) {
+    const int64_t bytes = bytes_of(i);
+    if (bytes == 0) continue;
+    if (groups.empty() || used + bytes > budget) {
+      groups.emplace_back();
+      used = 0;
+    }
+    groups.back().push_back(i);
+    used += bytes;
+    most = std::max(most, used);
+  }
+  return most;
+}
+
+// The labels of one target, who() in a message (formed only for one): inside the alphabet and not the blank, which the message
+// calls `noun` and `not_a`. Returns through `need` the labels plus the adjacent equal labels: the fewest frames a path takes.
+template <class Who>
+static int check_labels(const int32_t* lab, int64_t L, int V, int blank, Who who, const char* noun, const char* not_a, int64_t& need) {
+  need = L;
+  for (int64_t k = 0; k < L; ++k) {
+    const int32_t id = lab[k];
+    if (id < 0 || id >= V) return fail(CTCDEC_ERR_ARG, who() + ": " + noun + " " + std::to_string(id) + " is outside the alphabet");
+    if (id == blank) return fail(CTCDEC_ERR_ARG, who() + ": the blank is not a " + not_a);
+    if (k > 0 && id == lab[k - 1]) ++need;
+  }
+  return CTCDEC_OK;
+}
+
 // Everything the kernels index with comes from the caller: checked here, before anything moves.
-static int check_alignment(const ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts,
-                           const int32_t* targets, const int64_t* target_off, int64_t budget, int V, int blank) {
-  (void)dec;
+static int check_alignment(const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts, const int32_t* targets,
+                           const int64_t* target_off, int64_t budget, const TranscriptCall& tc) {
   if (target_off[0] != 0) return fail(CTCDEC_ERR_ARG, "target_off must start at 0");
   std::string infeasible;
   for (int32_t u = 0; u < n_utts; ++u) {
@@ -2330,14 +2397,10 @@ static int check_alignment(const ctcdec_decoder* dec, const void* const* utt_log
                                         std::to_string(ALIGN_MAX_LABELS) + " (two fp64 score columns of 2L + 1 states in LDS)");
     if (L > 0 && !targets) return fail(CTCDEC_ERR_ARG, "no targets");
     if (T > 0 && !utt_logits[u]) return fail(CTCDEC_ERR_ARG, "utterance " + std::to_string(u) + ": no logits");
-    int64_t need = L;
-    for (int64_t k = 0; k < L; ++k) {
-      const int32_t id = targets[target_off[u] + k];
-      if (id < 0 || id >= V)
-        return fail(CTCDEC_ERR_ARG, "utterance " + std::to_string(u) + ": target label " + std::to_string(id) + " is outside the alphabet");
-      if (id == blank) return fail(CTCDEC_ERR_ARG, "utterance " + std::to_string(u) + ": the blank is not a target label");
-      if (k > 0 && id == targets[target_off[u] + k - 1]) ++need;
-    }
+    int64_t need = 0;
+    if (int rc = check_labels(targets + target_off[u], L, tc.V, tc.blank, [&] { return "utterance " + std::to_string(u); }, "target label",
+                              "target label", need))
+      return rc;
     if (T < need) infeasible += (infeasible.empty() ? "" : ", ") + std::to_string(u);
     if (T * (int64_t)align_chunks((int32_t)L) > budget)
       return fail(CTCDEC_ERR_LIMIT, "utterance " + std::to_string(u) + ": a back-pointer table of " +
@@ -2349,10 +2412,12 @@ static int check_alignment(const ctcdec_decoder* dec, const void* const* utt_log
   return CTCDEC_OK;
 }
 
-// What ctcdec_align_batch and ctcdec_score_batch do before their own recursion, under the device lock: host matrices staged
-// (consecutive ones in one copy; device pointers are used in place), pointers and row offsets uploaded, the utterances
-// classified as probabilities or logits, and row_lse over the rows of the logit utterances -- once per utterance.
+// What every transcript call does before its own recursion: the device lock taken (held while the AlignFront lives) and the
+// device bound to the thread, host matrices staged (consecutive ones in one copy; device pointers are used in place),
+// pointers and row offsets uploaded, the utterances classified as probabilities or logits, and row_lse over the rows of the
+// logit utterances -- once per utterance.
 struct AlignFront {
+  std::unique_lock<std::mutex> device_lock;
   std::vector<const void*> ptrs;   // [n] device pointers of the utterances' matrices
   std::vector<uint32_t> is_prob;   // [n] the classification read back
   double* lse = nullptr;           // [R] (device) row log-sum-exps, indexed like row0
@@ -2363,6 +2428,8 @@ struct AlignFront {
 static int align_front(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts, int32_t dtype,
                        int32_t is_device, int V, const std::vector<int64_t>& row0, AlignFront& f) {
   std::string err;
+  f.device_lock = std::unique_lock<std::mutex>(g_device_mu);
+  if (be::bind_thread(&err)) return fail(CTCDEC_ERR_DEVICE, err);
   const size_t n = (size_t)n_utts;
   const int64_t R = row0[n];
   const size_t row_bytes = (size_t)V * dtype_size(dtype);
@@ -2425,126 +2492,145 @@ static int align_front(ctcdec_decoder* dec, const void* const* utt_logits, const
   return CTCDEC_OK;
 }
 
-extern "C" {
+// What ctcdec_align_gaps_batch adds to a Viterbi call: one flag per slot of every utterance (L + 1 of them from off[u]) and,
+// out, the sum of g(t) over each gap slot's frames
+struct GapSlots {
+  std::vector<uint8_t> gap;
+  std::vector<int64_t> off;
+  std::vector<double> logp;
+};
 
-int ctcdec_align_batch(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts, int32_t dtype,
-                       int32_t is_device, const int32_t* targets, const int64_t* target_off, int32_t fold, int64_t bp_budget,
-                       ctcdec_alignment** out) {
-  if (!dec || !out || n_utts < 0 || !target_off || bp_budget < 0 || (n_utts > 0 && (!utt_logits || !utt_frames)))
-    return fail(CTCDEC_ERR_ARG, "bad arguments");
-  if (dtype < CTCDEC_F32 || dtype > CTCDEC_BF16) return fail(CTCDEC_ERR_ARG, "dtype must be f32, f64, f16 or bf16");
-  if (fold != 0 && fold != LOGP_MEAN && fold != LOGP_MIN && fold != LOGP_MAX) return fail(CTCDEC_ERR_ARG, "unknown confidence fold");
-  const int V = (int)dec->alpha.labels.size();
-  int blank = -1;
-  for (int v = 0; v < V && blank < 0; ++v)
-    if (dec->alpha.labels[(size_t)v].empty()) blank = v;
-  if (blank < 0) return fail(CTCDEC_ERR_ARG, "the alphabet has no blank label");
-  const int64_t budget = bp_budget ? bp_budget : ALIGN_BP_BUDGET;
-  if (int rc = check_alignment(dec, utt_logits, utt_frames, n_utts, targets, target_off, budget, V, blank)) return rc;
-  const auto t_begin = Clock::now();
-  std::unique_ptr<ctcdec_alignment> res(new ctcdec_alignment());
+// The call behind ctcdec_align_batch (Utt = AlignUtt, no slots) and ctcdec_align_gaps_batch (Utt = GapsUtt): the checked
+// labels of every utterance to a result with its paths, spans, scores and, with a fold, confidences.
+template <class Utt>
+static int viterbi_call(ctcdec_decoder* dec, const TranscriptCall& tc, const void* const* utt_logits, const int32_t* utt_frames,
+                        int32_t n_utts, int32_t dtype, int32_t is_device, const int32_t* labels, const int64_t* lab_off, int32_t fold,
+                        int64_t budget, GapSlots* slots, std::unique_ptr<ctcdec_alignment>& res) {
+  constexpr bool GAPS = std::is_same<Utt, GapsUtt>::value;
+  res.reset(new ctcdec_alignment());
   const size_t n = (size_t)n_utts;
-  const int64_t NL = target_off[n];
-  std::vector<int64_t> row0(n + 1, 0);
-  for (size_t u = 0; u < n; ++u) row0[u + 1] = row0[u] + utt_frames[u];
+  const int64_t NL = lab_off[n], NS = GAPS ? slots->off[n] : 0;
+  const std::vector<int64_t> row0 = row_starts(utt_frames, n);
   const int64_t R = row0[n];
+  res->has_gaps = GAPS;
   res->path_off = row0;
-  res->tok_off.assign(target_off, target_off + n + 1);
-  res->label.assign(targets, targets + NL);
+  res->tok_off.assign(lab_off, lab_off + n + 1);
+  res->label.assign(labels, labels + NL);
   res->path.resize((size_t)R);
   res->start.assign((size_t)NL, 0);
   res->end.assign((size_t)NL, 0);
   res->score.assign(n, 0.0);
   res->has_logp = fold != 0;
   if (fold) res->logp.assign((size_t)NL, 0.0);
-  if (R > 0) {
-    std::string err;
-    std::lock_guard<std::mutex> device_lock(g_device_mu);
-    if (be::bind_thread(&err)) return fail(CTCDEC_ERR_DEVICE, err);
-    AlignFront fr;
-    if (int rc = align_front(dec, utt_logits, utt_frames, n_utts, dtype, is_device, V, row0, fr)) return rc;
-    const std::vector<const void*>& ptrs = fr.ptrs;
-    const std::vector<uint32_t>& is_prob = fr.is_prob;
-    double* lse = fr.lse;
-    res->ms[0] = fr.sniff_ms;
-    if (dec->w_apath.ensure((size_t)R * 4, &err) ||
-        dec->w_alab.ensure((size_t)std::max<int64_t>(NL, 1) * 4, &err) || dec->w_atok.ensure((size_t)std::max<int64_t>(NL, 1) * 8, &err) ||
-        dec->w_atlp.ensure((size_t)std::max<int64_t>(NL, 1) * 8, &err) || dec->w_ascore.ensure(n * 8, &err))
-      return fail(CTCDEC_ERR_DEVICE, err);
-    if ((NL && be::h2d(dec->w_alab.p, targets, (size_t)NL * 4, &err)) || be::zero(dec->w_atok.p, (size_t)std::max<int64_t>(NL, 1) * 8, &err) ||
-        be::zero(dec->w_atlp.p, (size_t)std::max<int64_t>(NL, 1) * 8, &err) || be::zero(dec->w_ascore.p, n * 8, &err))
-      return fail(CTCDEC_ERR_DEVICE, err);
-    // launches: utterances in input order until their back-pointer tables fill the budget; longest first inside a launch
-    std::vector<std::vector<int32_t>> groups;
-    int64_t used = 0, most = 0;
-    for (int32_t u = 0; u < n_utts; ++u) {
-      if (utt_frames[u] == 0) continue;
-      const int64_t bytes = (int64_t)utt_frames[u] * align_chunks((int32_t)(target_off[u + 1] - target_off[u]));
-      if (groups.empty() || used + bytes > budget) {
-        groups.emplace_back();
-        used = 0;
+  if (GAPS) slots->logp.assign((size_t)NS, 0.0);
+  if (R == 0) return CTCDEC_OK;
+  std::string err;
+  AlignFront fr;
+  fr.want_max = GAPS;
+  if (int rc = align_front(dec, utt_logits, utt_frames, n_utts, dtype, is_device, tc.V, row0, fr)) return rc;
+  res->ms[0] = fr.sniff_ms;
+  const size_t nl1 = (size_t)std::max<int64_t>(NL, 1);
+  if (dec->w_apath.ensure((size_t)R * 4, &err) || dec->w_alab.ensure(nl1 * 4, &err) || dec->w_atok.ensure(nl1 * 8, &err) ||
+      dec->w_atlp.ensure(nl1 * 8, &err) || dec->w_ascore.ensure(n * 8, &err) ||
+      (GAPS && (dec->w_agap.ensure((size_t)NS, &err) || dec->w_aglp.ensure((size_t)NS * 8, &err))))
+    return fail(CTCDEC_ERR_DEVICE, err);
+  if ((NL && be::h2d(dec->w_alab.p, labels, (size_t)NL * 4, &err)) || be::zero(dec->w_atok.p, nl1 * 8, &err) ||
+      be::zero(dec->w_atlp.p, nl1 * 8, &err) || be::zero(dec->w_ascore.p, n * 8, &err) ||
+      (GAPS && (be::h2d(dec->w_agap.p, slots->gap.data(), (size_t)NS, &err) || be::zero(dec->w_aglp.p, (size_t)NS * 8, &err))))
+    return fail(CTCDEC_ERR_DEVICE, err);
+  // launches: utterances in input order until their back-pointer tables fill the budget; longest first inside a launch
+  const auto chunks_of = [&](int32_t u) { return align_chunks((int32_t)(lab_off[u + 1] - lab_off[u])); };
+  std::vector<std::vector<int32_t>> groups;
+  const int64_t most = budget_groups(n_utts, [&](int32_t u) { return (int64_t)utt_frames[u] * chunks_of(u); }, budget, groups);
+  if (dec->w_abp.ensure((size_t)std::max<int64_t>(most, 1), &err)) return fail(CTCDEC_ERR_DEVICE, err);
+  std::vector<Utt> utts;
+  for (auto& g : groups) {
+    std::stable_sort(g.begin(), g.end(), [&](int32_t a, int32_t b) { return utt_frames[a] > utt_frames[b]; });
+    utts.clear();
+    int64_t bp_off = 0;
+    int32_t max_chunks = 1;
+    for (int32_t u : g) {
+      const int64_t lo = lab_off[u];
+      Utt a;
+      a.x = fr.ptrs[(size_t)u];
+      a.lse = fr.lse + row0[(size_t)u];
+      a.lab = (const int32_t*)dec->w_alab.p + lo;
+      a.bp = (uint8_t*)dec->w_abp.p + bp_off;
+      a.path = (int32_t*)dec->w_apath.p + row0[(size_t)u];
+      a.tok_start = (int32_t*)dec->w_atok.p + lo;
+      a.tok_end = (int32_t*)dec->w_atok.p + NL + lo;
+      a.tok_logp = (double*)dec->w_atlp.p + lo;
+      a.score = (double*)dec->w_ascore.p + u;
+      a.T = utt_frames[u];
+      a.L = (int32_t)(lab_off[u + 1] - lo);
+      a.is_prob = fr.is_prob[(size_t)u] ? 1 : 0;
+      a.pad = 0;
+      if constexpr (GAPS) {
+        a.rmax = fr.rmax + row0[(size_t)u];
+        a.gap = (const uint8_t*)dec->w_agap.p + slots->off[(size_t)u];
+        a.gap_logp = (double*)dec->w_aglp.p + slots->off[(size_t)u];
       }
-      groups.back().push_back(u);
-      used += bytes;
-      most = std::max(most, used);
+      utts.push_back(a);
+      bp_off += (int64_t)utt_frames[u] * chunks_of(u);
+      max_chunks = std::max(max_chunks, chunks_of(u));
     }
-    if (dec->w_abp.ensure((size_t)std::max<int64_t>(most, 1), &err)) return fail(CTCDEC_ERR_DEVICE, err);
-    const double clip_lo = log(1e-15);  // ln(MIN_TOKEN_CLIP_P) (constants.py:17)
-    std::vector<AlignUtt> utts;
-    for (auto& g : groups) {
-      std::stable_sort(g.begin(), g.end(), [&](int32_t a, int32_t b) { return utt_frames[a] > utt_frames[b]; });
-      utts.clear();
-      int64_t bp_off = 0;
-      int32_t max_chunks = 1;
-      for (int32_t u : g) {
-        const int32_t L = (int32_t)(target_off[u + 1] - target_off[u]);
-        AlignUtt a;
-        a.x = ptrs[(size_t)u];
-        a.lse = lse + row0[(size_t)u];
-        a.lab = (const int32_t*)dec->w_alab.p + target_off[u];
-        a.bp = (uint8_t*)dec->w_abp.p + bp_off;
-        a.path = (int32_t*)dec->w_apath.p + row0[(size_t)u];
-        a.tok_start = (int32_t*)dec->w_atok.p + target_off[u];
-        a.tok_end = (int32_t*)dec->w_atok.p + NL + target_off[u];
-        a.tok_logp = (double*)dec->w_atlp.p + target_off[u];
-        a.score = (double*)dec->w_ascore.p + u;
-        a.T = utt_frames[u];
-        a.L = L;
-        a.is_prob = is_prob[(size_t)u] ? 1 : 0;
-        a.pad = 0;
-        utts.push_back(a);
-        bp_off += (int64_t)utt_frames[u] * align_chunks(L);
-        max_chunks = std::max(max_chunks, align_chunks(L));
-      }
 #ifdef CTC_SIM
-      std::vector<double> col((size_t)8 * (size_t)max_chunks);
-      AlignSeqCtx cx;
-      for (const AlignUtt& a : utts) ctc_viterbi_utt(cx, a, V, dtype, blank, fold, clip_lo, col.data());
-#else
-      if (upload(dec->w_autts, utts, &err)) return fail(CTCDEC_ERR_DEVICE, err);
-      be::ViterbiArgs va;
-      va.utts = (const AlignUtt*)dec->w_autts.p;
-      va.n_utts = (int32_t)utts.size();
-      va.n_labels = V;
-      va.dtype = dtype;
-      va.blank = blank;
-      va.fold = fold;
-      va.max_chunks = max_chunks;
-      va.clip_lo = clip_lo;
-      if (be::launch_ctc_viterbi(va, &err)) return fail(CTCDEC_ERR_DEVICE, err);
-#endif
-      ++res->launches;
+    std::vector<double> col((size_t)(GAPS ? 2 : 8) * (size_t)max_chunks);
+    AlignSeqCtx cx;
+    for (const Utt& a : utts) {
+      if constexpr (GAPS)
+        for_dtype(dtype, [&](auto dt) { ctc_viterbi_gaps_utt<decltype(dt)::value>(cx, a, tc.V, tc.blank, fold, tc.clip_lo, col.data()); });
+      else
+        ctc_viterbi_utt(cx, a, tc.V, dtype, tc.blank, fold, tc.clip_lo, col.data());
     }
-    if (be::d2h(res->path.data(), dec->w_apath.p, (size_t)R * 4, &err) || be::d2h(res->score.data(), dec->w_ascore.p, n * 8, &err))
-      return fail(CTCDEC_ERR_DEVICE, err);
-    if (NL && (be::d2h(res->start.data(), dec->w_atok.p, (size_t)NL * 4, &err) ||
-               be::d2h(res->end.data(), (const int32_t*)dec->w_atok.p + NL, (size_t)NL * 4, &err) ||
-               (fold && be::d2h(res->logp.data(), dec->w_atlp.p, (size_t)NL * 8, &err))))
-      return fail(CTCDEC_ERR_DEVICE, err);
-#ifndef CTC_SIM
-    be::align_timing(&res->ms[1], &res->ms[2]);
+#else
+    DevBuf& records = GAPS ? dec->w_agutts : dec->w_autts;
+    if (upload(records, utts, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+    typename std::conditional<GAPS, be::ViterbiGapsArgs, be::ViterbiArgs>::type va;
+    va.utts = (const Utt*)records.p;
+    va.n_utts = (int32_t)utts.size();
+    va.n_labels = tc.V;
+    va.dtype = dtype;
+    va.blank = tc.blank;
+    va.fold = fold;
+    va.max_chunks = max_chunks;
+    va.clip_lo = tc.clip_lo;
+    int rc;
+    if constexpr (GAPS) rc = be::launch_ctc_viterbi_gaps(va, &err);
+    else rc = be::launch_ctc_viterbi(va, &err);
+    if (rc) return fail(CTCDEC_ERR_DEVICE, err);
 #endif
+    ++res->launches;
   }
+  if (be::d2h(res->path.data(), dec->w_apath.p, (size_t)R * 4, &err) || be::d2h(res->score.data(), dec->w_ascore.p, n * 8, &err))
+    return fail(CTCDEC_ERR_DEVICE, err);
+  if (NL && (be::d2h(res->start.data(), dec->w_atok.p, (size_t)NL * 4, &err) ||
+             be::d2h(res->end.data(), (const int32_t*)dec->w_atok.p + NL, (size_t)NL * 4, &err) ||
+             (fold && be::d2h(res->logp.data(), dec->w_atlp.p, (size_t)NL * 8, &err))))
+    return fail(CTCDEC_ERR_DEVICE, err);
+  if (GAPS && be::d2h(slots->logp.data(), dec->w_aglp.p, (size_t)NS * 8, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+#ifndef CTC_SIM
+  res->ms[1] = be::align_kernel_ms(GAPS ? be::K_ROW_LSE_MAX : be::K_ROW_LSE);
+  res->ms[2] = be::align_kernel_ms(GAPS ? be::K_VITERBI_GAPS : be::K_VITERBI);
+#endif
+  return CTCDEC_OK;
+}
+
+extern "C" {
+
+int ctcdec_align_batch(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts, int32_t dtype,
+                       int32_t is_device, const int32_t* targets, const int64_t* target_off, int32_t fold, int64_t bp_budget,
+                       ctcdec_alignment** out) {
+  TranscriptCall tc;
+  const bool args_ok = dec && out && n_utts >= 0 && target_off && bp_budget >= 0 && (n_utts == 0 || (utt_logits && utt_frames));
+  if (int rc = transcript_open(dec, args_ok, dtype, bad_fold(fold), tc)) return rc;
+  const int64_t budget = bp_budget ? bp_budget : ALIGN_BP_BUDGET;
+  if (int rc = check_alignment(utt_logits, utt_frames, n_utts, targets, target_off, budget, tc)) return rc;
+  const auto t_begin = Clock::now();
+  std::unique_ptr<ctcdec_alignment> res;
+  if (int rc = viterbi_call<AlignUtt>(dec, tc, utt_logits, utt_frames, n_utts, dtype, is_device, targets, target_off, fold, budget,
+                                      nullptr, res))
+    return rc;
   res->ms[3] = ms(t_begin, Clock::now());
   *out = res.release();
   return CTCDEC_OK;
@@ -2585,169 +2671,56 @@ void ctcdec_alignment_free(ctcdec_alignment* a) { delete a; }
 int ctcdec_align_gaps_batch(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts, int32_t dtype,
                             int32_t is_device, const int32_t* targets, const int64_t* target_off, int32_t fold, int64_t bp_budget,
                             ctcdec_alignment** out) {
-  if (!dec || !out || n_utts < 0 || !target_off || bp_budget < 0 || (n_utts > 0 && (!utt_logits || !utt_frames)))
-    return fail(CTCDEC_ERR_ARG, "bad arguments");
-  if (dtype < CTCDEC_F32 || dtype > CTCDEC_BF16) return fail(CTCDEC_ERR_ARG, "dtype must be f32, f64, f16 or bf16");
-  if (fold != 0 && fold != LOGP_MEAN && fold != LOGP_MIN && fold != LOGP_MAX) return fail(CTCDEC_ERR_ARG, "unknown confidence fold");
-  const int V = (int)dec->alpha.labels.size();
-  int blank = -1;
-  for (int v = 0; v < V && blank < 0; ++v)
-    if (dec->alpha.labels[(size_t)v].empty()) blank = v;
-  if (blank < 0) return fail(CTCDEC_ERR_ARG, "the alphabet has no blank label");
+  TranscriptCall tc;
+  const bool args_ok = dec && out && n_utts >= 0 && target_off && bp_budget >= 0 && (n_utts == 0 || (utt_logits && utt_frames));
+  if (int rc = transcript_open(dec, args_ok, dtype, bad_fold(fold), tc)) return rc;
   const int64_t budget = bp_budget ? bp_budget : ALIGN_BP_BUDGET;
   const size_t n = (size_t)n_utts;
   // the items apart: the labels, with offsets of their own, and one flag per slot (before label 0, between neighbours, after
   // the last label). Everything align checks is then checked by align's own code, on the labels.
   if (target_off[0] != 0) return fail(CTCDEC_ERR_ARG, "target_off must start at 0");
   std::vector<int32_t> labels;
-  std::vector<int64_t> lab_off(n + 1, 0), slot_off(n + 1, 0);
-  std::vector<uint8_t> slot_gap;
+  std::vector<int64_t> lab_off(n + 1, 0);
+  GapSlots slots;
+  slots.off.assign(n + 1, 0);
   for (size_t u = 0; u < n; ++u) {
     const int64_t N = target_off[u + 1] - target_off[u];
     if (N < 0) return fail(CTCDEC_ERR_ARG, "target_off must not decrease");
     if (N > 0 && !targets) return fail(CTCDEC_ERR_ARG, "no targets");
-    slot_gap.push_back(0);
+    slots.gap.push_back(0);
     for (int64_t k = 0; k < N; ++k) {
       const int32_t id = targets[target_off[u] + k];
       if (id != CTCDEC_ALIGN_GAP) {
         labels.push_back(id);
-        slot_gap.push_back(0);
+        slots.gap.push_back(0);
         continue;
       }
       if (k > 0 && targets[target_off[u] + k - 1] == CTCDEC_ALIGN_GAP)
         return fail(CTCDEC_ERR_ARG, "utterance " + std::to_string(u) + ": two adjacent gaps are one gap");
-      slot_gap.back() = 1;
+      slots.gap.back() = 1;
     }
     lab_off[u + 1] = (int64_t)labels.size();
-    slot_off[u + 1] = (int64_t)slot_gap.size();
+    slots.off[u + 1] = (int64_t)slots.gap.size();
   }
   if (labels.empty()) labels.push_back(0);  // (never read: .data() of an empty vector may be null)
-  if (int rc = check_alignment(dec, utt_logits, utt_frames, n_utts, labels.data(), lab_off.data(), budget, V, blank)) return rc;
+  if (int rc = check_alignment(utt_logits, utt_frames, n_utts, labels.data(), lab_off.data(), budget, tc)) return rc;
   for (size_t u = 0; u < n; ++u)
     if (lab_off[u + 1] == lab_off[u])
       return fail(CTCDEC_ERR_ARG, "utterance " + std::to_string(u) + ": a target needs at least one label");
   const auto t_begin = Clock::now();
-  std::unique_ptr<ctcdec_alignment> res(new ctcdec_alignment());
-  const int64_t NL = lab_off[n], NS = slot_off[n];
-  std::vector<int64_t> row0(n + 1, 0);
-  for (size_t u = 0; u < n; ++u) row0[u + 1] = row0[u] + utt_frames[u];
-  const int64_t R = row0[n];
-  res->has_gaps = true;
-  res->path_off = row0;
-  res->tok_off = lab_off;
-  res->label.assign(labels.begin(), labels.begin() + NL);
-  res->path.resize((size_t)R);
-  res->start.assign((size_t)NL, 0);
-  res->end.assign((size_t)NL, 0);
-  res->score.assign(n, 0.0);
-  res->has_logp = fold != 0;
-  if (fold) res->logp.assign((size_t)NL, 0.0);
-  std::vector<double> slot_logp((size_t)NS, 0.0);
-  if (n > 0) {  // (every utterance has a label, so a frame: R >= n)
-    std::string err;
-    std::lock_guard<std::mutex> device_lock(g_device_mu);
-    if (be::bind_thread(&err)) return fail(CTCDEC_ERR_DEVICE, err);
-    AlignFront fr;
-    fr.want_max = true;
-    if (int rc = align_front(dec, utt_logits, utt_frames, n_utts, dtype, is_device, V, row0, fr)) return rc;
-    res->ms[0] = fr.sniff_ms;
-    if (dec->w_apath.ensure((size_t)R * 4, &err) || dec->w_alab.ensure((size_t)NL * 4, &err) || dec->w_atok.ensure((size_t)NL * 8, &err) ||
-        dec->w_atlp.ensure((size_t)NL * 8, &err) || dec->w_ascore.ensure(n * 8, &err) || dec->w_agap.ensure((size_t)NS, &err) ||
-        dec->w_aglp.ensure((size_t)NS * 8, &err))
-      return fail(CTCDEC_ERR_DEVICE, err);
-    if (be::h2d(dec->w_alab.p, labels.data(), (size_t)NL * 4, &err) || be::h2d(dec->w_agap.p, slot_gap.data(), (size_t)NS, &err) ||
-        be::zero(dec->w_atok.p, (size_t)NL * 8, &err) || be::zero(dec->w_atlp.p, (size_t)NL * 8, &err) ||
-        be::zero(dec->w_ascore.p, n * 8, &err) || be::zero(dec->w_aglp.p, (size_t)NS * 8, &err))
-      return fail(CTCDEC_ERR_DEVICE, err);
-    // launches: utterances in input order until their back-pointer tables fill the budget; longest first inside a launch
-    // (ctcdec_align_batch's rule)
-    std::vector<std::vector<int32_t>> groups;
-    int64_t used = 0, most = 0;
-    for (int32_t u = 0; u < n_utts; ++u) {
-      const int64_t bytes = (int64_t)utt_frames[u] * align_chunks((int32_t)(lab_off[(size_t)u + 1] - lab_off[(size_t)u]));
-      if (groups.empty() || used + bytes > budget) {
-        groups.emplace_back();
-        used = 0;
-      }
-      groups.back().push_back(u);
-      used += bytes;
-      most = std::max(most, used);
-    }
-    if (dec->w_abp.ensure((size_t)std::max<int64_t>(most, 1), &err)) return fail(CTCDEC_ERR_DEVICE, err);
-    const double clip_lo = log(1e-15);  // ln(MIN_TOKEN_CLIP_P) (constants.py:17)
-    std::vector<GapsUtt> utts;
-    for (auto& g : groups) {
-      std::stable_sort(g.begin(), g.end(), [&](int32_t a, int32_t b) { return utt_frames[a] > utt_frames[b]; });
-      utts.clear();
-      int64_t bp_off = 0;
-      int32_t max_chunks = 1;
-      for (int32_t u : g) {
-        const int64_t lo = lab_off[(size_t)u], so = slot_off[(size_t)u];
-        const int32_t L = (int32_t)(lab_off[(size_t)u + 1] - lo);
-        GapsUtt a;
-        a.x = fr.ptrs[(size_t)u];
-        a.lse = fr.lse + row0[(size_t)u];
-        a.rmax = fr.rmax + row0[(size_t)u];
-        a.lab = (const int32_t*)dec->w_alab.p + lo;
-        a.gap = (const uint8_t*)dec->w_agap.p + so;
-        a.bp = (uint8_t*)dec->w_abp.p + bp_off;
-        a.path = (int32_t*)dec->w_apath.p + row0[(size_t)u];
-        a.tok_start = (int32_t*)dec->w_atok.p + lo;
-        a.tok_end = (int32_t*)dec->w_atok.p + NL + lo;
-        a.tok_logp = (double*)dec->w_atlp.p + lo;
-        a.gap_logp = (double*)dec->w_aglp.p + so;
-        a.score = (double*)dec->w_ascore.p + u;
-        a.T = utt_frames[u];
-        a.L = L;
-        a.is_prob = fr.is_prob[(size_t)u] ? 1 : 0;
-        a.pad = 0;
-        utts.push_back(a);
-        bp_off += (int64_t)utt_frames[u] * align_chunks(L);
-        max_chunks = std::max(max_chunks, align_chunks(L));
-      }
-#ifdef CTC_SIM
-      std::vector<double> col((size_t)2 * (size_t)max_chunks);
-      AlignSeqCtx cx;
-      for (const GapsUtt& a : utts) {
-        if (dtype == 0) ctc_viterbi_gaps_utt<0>(cx, a, V, blank, fold, clip_lo, col.data());
-        else if (dtype == 1) ctc_viterbi_gaps_utt<1>(cx, a, V, blank, fold, clip_lo, col.data());
-        else if (dtype == 2) ctc_viterbi_gaps_utt<2>(cx, a, V, blank, fold, clip_lo, col.data());
-        else ctc_viterbi_gaps_utt<3>(cx, a, V, blank, fold, clip_lo, col.data());
-      }
-#else
-      if (upload(dec->w_agutts, utts, &err)) return fail(CTCDEC_ERR_DEVICE, err);
-      be::ViterbiGapsArgs va;
-      va.utts = (const GapsUtt*)dec->w_agutts.p;
-      va.n_utts = (int32_t)utts.size();
-      va.n_labels = V;
-      va.dtype = dtype;
-      va.blank = blank;
-      va.fold = fold;
-      va.max_chunks = max_chunks;
-      va.clip_lo = clip_lo;
-      if (be::launch_ctc_viterbi_gaps(va, &err)) return fail(CTCDEC_ERR_DEVICE, err);
-#endif
-      ++res->launches;
-    }
-    if (be::d2h(res->path.data(), dec->w_apath.p, (size_t)R * 4, &err) || be::d2h(res->score.data(), dec->w_ascore.p, n * 8, &err) ||
-        be::d2h(res->start.data(), dec->w_atok.p, (size_t)NL * 4, &err) ||
-        be::d2h(res->end.data(), (const int32_t*)dec->w_atok.p + NL, (size_t)NL * 4, &err) ||
-        (fold && be::d2h(res->logp.data(), dec->w_atlp.p, (size_t)NL * 8, &err)) ||
-        be::d2h(slot_logp.data(), dec->w_aglp.p, (size_t)NS * 8, &err))
-      return fail(CTCDEC_ERR_DEVICE, err);
-#ifndef CTC_SIM
-    be::align_gaps_timing(&res->ms[1], &res->ms[2]);
-#endif
-  }
+  std::unique_ptr<ctcdec_alignment> res;
+  if (int rc = viterbi_call<GapsUtt>(dec, tc, utt_logits, utt_frames, n_utts, dtype, is_device, labels.data(), lab_off.data(), fold,
+                                     budget, &slots, res))
+    return rc;
   // the gaps, in target order: everything between the end of the label before and the start of the label after
   res->gap_off.assign(n + 1, 0);
   for (size_t u = 0; u < n; ++u) {
     const int64_t lo = lab_off[u], L = lab_off[u + 1] - lo;
     for (int64_t j = 0; j <= L; ++j) {
-      if (!slot_gap[(size_t)(slot_off[u] + j)]) continue;
+      if (!slots.gap[(size_t)(slots.off[u] + j)]) continue;
       res->gap_start.push_back(j > 0 ? res->end[(size_t)(lo + j - 1)] : 0);
       res->gap_end.push_back(j < L ? res->start[(size_t)(lo + j)] : utt_frames[u]);
-      res->gap_logp.push_back(slot_logp[(size_t)(slot_off[u] + j)]);
+      res->gap_logp.push_back(slots.logp[(size_t)(slots.off[u] + j)]);
     }
     res->gap_off[u + 1] = (int64_t)res->gap_start.size();
   }
@@ -2775,7 +2748,7 @@ int ctcdec_alignment_gaps(const ctcdec_alignment* a, const int64_t** gap_off_out
 // next, before anything moves. need[h]: labels plus adjacent equal labels of hypothesis h. (ctcdec_find_batch checks its
 // phrases with it too: `item` is what a message calls an entry.)
 static int check_scores(const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts, const int32_t* targets,
-                        const int64_t* target_off, const int64_t* hyp_off, int V, int blank, std::vector<int32_t>& need,
+                        const int64_t* target_off, const int64_t* hyp_off, const TranscriptCall& tc, std::vector<int32_t>& need,
                         const char* item = "hypothesis") {
   if (hyp_off[0] != 0) return fail(CTCDEC_ERR_ARG, "hyp_off must start at 0");
   for (int32_t u = 0; u < n_utts; ++u) {
@@ -2795,13 +2768,8 @@ static int check_scores(const void* const* utt_logits, const int32_t* utt_frames
       if (L > ALIGN_MAX_LABELS)
         return fail(CTCDEC_ERR_LIMIT, who + ": " + std::to_string(L) + " labels, above the limit of " + std::to_string(ALIGN_MAX_LABELS));
       if (L > 0 && !targets) return fail(CTCDEC_ERR_ARG, "no targets");
-      int64_t nd = L;
-      for (int64_t k = 0; k < L; ++k) {
-        const int32_t id = targets[target_off[h] + k];
-        if (id < 0 || id >= V) return fail(CTCDEC_ERR_ARG, who + ": label " + std::to_string(id) + " is outside the alphabet");
-        if (id == blank) return fail(CTCDEC_ERR_ARG, who + ": the blank is not a label to score");
-        if (k > 0 && id == targets[target_off[h] + k - 1]) ++nd;
-      }
+      int64_t nd = 0;
+      if (int rc = check_labels(targets + target_off[h], L, tc.V, tc.blank, [&] { return who; }, "label", "label to score", nd)) return rc;
       need[(size_t)h] = (int32_t)nd;
     }
   return CTCDEC_OK;
@@ -2812,17 +2780,11 @@ extern "C" {
 int ctcdec_score_batch(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts, int32_t dtype,
                        int32_t is_device, const int32_t* targets, const int64_t* target_off, const int64_t* hyp_off, int32_t kernel,
                        double* logp_out, double* ms4, int64_t* launched2) {
-  if (!dec || n_utts < 0 || !target_off || !hyp_off || (n_utts > 0 && (!utt_logits || !utt_frames)))
-    return fail(CTCDEC_ERR_ARG, "bad arguments");
-  if (dtype < CTCDEC_F32 || dtype > CTCDEC_BF16) return fail(CTCDEC_ERR_ARG, "dtype must be f32, f64, f16 or bf16");
-  if (kernel < 0 || kernel > 2) return fail(CTCDEC_ERR_ARG, "kernel must be 0 (the library chooses), 1 (wave) or 2 (group)");
-  const int V = (int)dec->alpha.labels.size();
-  int blank = -1;
-  for (int v = 0; v < V && blank < 0; ++v)
-    if (dec->alpha.labels[(size_t)v].empty()) blank = v;
-  if (blank < 0) return fail(CTCDEC_ERR_ARG, "the alphabet has no blank label");
+  TranscriptCall tc;
+  const bool args_ok = dec && n_utts >= 0 && target_off && hyp_off && (n_utts == 0 || (utt_logits && utt_frames));
+  if (int rc = transcript_open(dec, args_ok, dtype, bad_kernel(kernel), tc)) return rc;
   std::vector<int32_t> need;
-  if (int rc = check_scores(utt_logits, utt_frames, n_utts, targets, target_off, hyp_off, V, blank, need)) return rc;
+  if (int rc = check_scores(utt_logits, utt_frames, n_utts, targets, target_off, hyp_off, tc, need)) return rc;
   const size_t n = (size_t)n_utts;
   const int64_t NH = hyp_off[n];
   if (NH > 0 && !logp_out) return fail(CTCDEC_ERR_ARG, "no room for the scores");
@@ -2848,20 +2810,16 @@ int ctcdec_score_batch(ctcdec_decoder* dec, const void* const* utt_logits, const
     std::vector<int32_t> use_frames(n, 0);
     for (int w = 0; w < 2; ++w)
       for (int32_t h : run[w]) use_frames[(size_t)utt_of[(size_t)h]] = utt_frames[utt_of[(size_t)h]];
-    std::vector<int64_t> row0(n + 1, 0);
-    for (size_t u = 0; u < n; ++u) row0[u + 1] = row0[u] + use_frames[u];
+    const std::vector<int64_t> row0 = row_starts(use_frames.data(), n);
     const int64_t NL = target_off[NH];
     std::string err;
-    std::lock_guard<std::mutex> device_lock(g_device_mu);
-    if (be::bind_thread(&err)) return fail(CTCDEC_ERR_DEVICE, err);
     AlignFront fr;
-    if (int rc = align_front(dec, utt_logits, use_frames.data(), n_utts, dtype, is_device, V, row0, fr)) return rc;
+    if (int rc = align_front(dec, utt_logits, use_frames.data(), n_utts, dtype, is_device, tc.V, row0, fr)) return rc;
     tms[0] = fr.sniff_ms;
     if (dec->w_alab.ensure((size_t)std::max<int64_t>(NL, 1) * 4, &err) || dec->w_ascore.ensure((size_t)NH * 8, &err))
       return fail(CTCDEC_ERR_DEVICE, err);
     if ((NL && be::h2d(dec->w_alab.p, targets, (size_t)NL * 4, &err)) || be::zero(dec->w_ascore.p, (size_t)NH * 8, &err))
       return fail(CTCDEC_ERR_DEVICE, err);
-    const double clip_lo = log(1e-15);  // ln(MIN_TOKEN_CLIP_P) (constants.py:17)
     // one launch per kernel, longest utterance first inside it; the records of both go over in one copy
     std::vector<ForwardHyp> hyps;
     int32_t max_chunks[2] = {1, 1};
@@ -2887,24 +2845,20 @@ int ctcdec_score_batch(ctcdec_decoder* dec, const void* const* utt_logits, const
 #ifdef CTC_SIM  // (both kernels are the one body here: a single thread owns every group)
     std::vector<double> col((size_t)2 * (size_t)std::max(max_chunks[0], max_chunks[1]));
     AlignSeqCtx cx;
-    for (const ForwardHyp& a : hyps) {
-      if (dtype == 0) ctc_forward_hyp<0>(cx, a, V, blank, clip_lo, col.data());
-      else if (dtype == 1) ctc_forward_hyp<1>(cx, a, V, blank, clip_lo, col.data());
-      else if (dtype == 2) ctc_forward_hyp<2>(cx, a, V, blank, clip_lo, col.data());
-      else ctc_forward_hyp<3>(cx, a, V, blank, clip_lo, col.data());
-    }
+    for (const ForwardHyp& a : hyps)
+      for_dtype(dtype, [&](auto dt) { ctc_forward_hyp<decltype(dt)::value>(cx, a, tc.V, tc.blank, tc.clip_lo, col.data()); });
 #else
     if (upload(dec->w_fhyps, hyps, &err)) return fail(CTCDEC_ERR_DEVICE, err);
     for (int w = 0; w < 2; ++w) {
       be::ForwardArgs fa;
       fa.hyps = (const ForwardHyp*)dec->w_fhyps.p + (w ? run[0].size() : 0);
       fa.n_hyps = (int32_t)run[w].size();
-      fa.n_labels = V;
+      fa.n_labels = tc.V;
       fa.dtype = dtype;
-      fa.blank = blank;
+      fa.blank = tc.blank;
       fa.max_chunks = max_chunks[w];
       fa.pad = 0;
-      fa.clip_lo = clip_lo;
+      fa.clip_lo = tc.clip_lo;
       if (be::launch_ctc_forward(fa, w == 0, &err)) return fail(CTCDEC_ERR_DEVICE, err);
     }
 #endif
@@ -2913,9 +2867,8 @@ int ctcdec_score_batch(ctcdec_decoder* dec, const void* const* utt_logits, const
     for (int w = 0; w < 2; ++w)
       for (int32_t h : run[w]) logp_out[h] = got[(size_t)h];
 #ifndef CTC_SIM
-    double vit_ms = 0;
-    be::align_timing(&tms[1], &vit_ms);
-    tms[2] = be::forward_timing();
+    tms[1] = be::align_kernel_ms(be::K_ROW_LSE);
+    tms[2] = be::align_kernel_ms(be::K_FORWARD);
 #endif
   }
   tms[3] = ms(t_begin, Clock::now());
@@ -2947,9 +2900,9 @@ static int64_t posteriors_table_bytes(int64_t T, int64_t L) { return 32 * T * (i
 
 // What ctcdec_posteriors_batch and ctcdec_gradient_batch check before anything moves: labels, frame counts and feasibility
 // are ctcdec_align_batch's; the budget is these calls' own
-static int check_posteriors(const ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts,
-                            const int64_t* label_off, const int32_t* labels, int64_t budget, int V, int blank) {
-  if (int rc = check_alignment(dec, utt_logits, utt_frames, n_utts, labels, label_off, INT64_MAX, V, blank)) return rc;
+static int check_posteriors(const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts, const int64_t* label_off,
+                            const int32_t* labels, int64_t budget, const TranscriptCall& tc) {
+  if (int rc = check_alignment(utt_logits, utt_frames, n_utts, labels, label_off, INT64_MAX, tc)) return rc;
   for (int32_t u = 0; u < n_utts; ++u) {
     const int64_t bytes = posteriors_table_bytes(utt_frames[u], label_off[u + 1] - label_off[u]);
     if (bytes > budget)
@@ -2957,25 +2910,6 @@ static int check_posteriors(const ctcdec_decoder* dec, const void* const* utt_lo
                                         std::to_string(budget) + " bytes for one launch");
   }
   return CTCDEC_OK;
-}
-
-// The launches of a call: utterances in input order until their tables fill the budget (ctcdec_align_batch's rule). Returns
-// the bytes of the largest launch's tables.
-static int64_t posteriors_groups(const int32_t* utt_frames, int32_t n_utts, const int64_t* label_off, int64_t budget,
-                                 std::vector<std::vector<int32_t>>& groups) {
-  int64_t used = 0, most = 0;
-  for (int32_t u = 0; u < n_utts; ++u) {
-    if (utt_frames[u] == 0) continue;
-    const int64_t bytes = posteriors_table_bytes(utt_frames[u], label_off[u + 1] - label_off[u]);
-    if (groups.empty() || used + bytes > budget) {
-      groups.emplace_back();
-      used = 0;
-    }
-    groups.back().push_back(u);
-    used += bytes;
-    most = std::max(most, used);
-  }
-  return most;
 }
 
 // One launch of ctc_posteriors over the utterances `g` of a call (at most two kernel launches: inside a launch the short
@@ -2988,8 +2922,8 @@ struct PosteriorsLaunch {
   int32_t launches = 0;
 };
 static int posteriors_launch(ctcdec_decoder* dec, std::vector<int32_t>& g, const AlignFront& fr, const std::vector<int64_t>& row0,
-                             const int32_t* utt_frames, const int64_t* label_off, int64_t NL, int V, int blank, int32_t dtype,
-                             int32_t dense, double clip_lo, PosteriorsLaunch& out) {
+                             const int32_t* utt_frames, const int64_t* label_off, int64_t NL, const TranscriptCall& tc, int32_t dtype,
+                             int32_t dense, PosteriorsLaunch& out) {
   std::string err;
   std::stable_sort(g.begin(), g.end(), [&](int32_t a, int32_t b) {
     const bool la = align_chunks((int32_t)(label_off[a + 1] - label_off[a])) > ALIGN_THREADS;
@@ -3028,12 +2962,8 @@ static int posteriors_launch(ctcdec_decoder* dec, std::vector<int32_t>& g, const
 #ifdef CTC_SIM  // (the kernel's body: a single thread owns every group)
   std::vector<double> col((size_t)4 * (size_t)std::max(max_chunks[0], max_chunks[1]) + 2);
   AlignSeqCtx cx;
-  for (const PostUtt& a : utts) {
-    if (dtype == 0) ctc_posteriors_utt<0>(cx, a, V, blank, clip_lo, dense, col.data());
-    else if (dtype == 1) ctc_posteriors_utt<1>(cx, a, V, blank, clip_lo, dense, col.data());
-    else if (dtype == 2) ctc_posteriors_utt<2>(cx, a, V, blank, clip_lo, dense, col.data());
-    else ctc_posteriors_utt<3>(cx, a, V, blank, clip_lo, dense, col.data());
-  }
+  for (const PostUtt& a : utts)
+    for_dtype(dtype, [&](auto dt) { ctc_posteriors_utt<decltype(dt)::value>(cx, a, tc.V, tc.blank, tc.clip_lo, dense, col.data()); });
   for (int w = 0; w < 2; ++w) out.launches += count[w] ? 1 : 0;
 #else
   if (upload(dec->w_putts, utts, &err)) return fail(CTCDEC_ERR_DEVICE, err);
@@ -3042,16 +2972,37 @@ static int posteriors_launch(ctcdec_decoder* dec, std::vector<int32_t>& g, const
     be::PosteriorsArgs pa;
     pa.utts = (const PostUtt*)dec->w_putts.p + (w ? count[0] : 0);
     pa.n_utts = count[w];
-    pa.n_labels = V;
+    pa.n_labels = tc.V;
     pa.dtype = dtype;
-    pa.blank = blank;
+    pa.blank = tc.blank;
     pa.max_chunks = max_chunks[w];
     pa.dense = dense ? 1 : 0;
-    pa.clip_lo = clip_lo;
+    pa.clip_lo = tc.clip_lo;
     if (be::launch_ctc_posteriors(pa, &err)) return fail(CTCDEC_ERR_DEVICE, err);
     ++out.launches;
   }
 #endif
+  return CTCDEC_OK;
+}
+
+// What ctcdec_posteriors_batch and ctcdec_gradient_batch do between their checks and their launches: the device front, the
+// labels uploaded, the token sums and the scores zeroed, the launches' utterances, and room for the largest launch's tables
+static int posteriors_front(ctcdec_decoder* dec, const TranscriptCall& tc, const void* const* utt_logits, const int32_t* utt_frames,
+                            int32_t n_utts, int32_t dtype, int32_t is_device, const int64_t* label_off, const int32_t* labels,
+                            int64_t budget, const std::vector<int64_t>& row0, AlignFront& fr, std::vector<std::vector<int32_t>>& groups) {
+  std::string err;
+  if (int rc = align_front(dec, utt_logits, utt_frames, n_utts, dtype, is_device, tc.V, row0, fr)) return rc;
+  const size_t n = (size_t)n_utts;
+  const int64_t NL = label_off[n];
+  const size_t nl1 = (size_t)std::max<int64_t>(NL, 1);
+  if (dec->w_alab.ensure(nl1 * 4, &err) || dec->w_pocc.ensure(nl1 * 16, &err) || dec->w_ascore.ensure(n * 16, &err))
+    return fail(CTCDEC_ERR_DEVICE, err);
+  if ((NL && be::h2d(dec->w_alab.p, labels, (size_t)NL * 4, &err)) || be::zero(dec->w_pocc.p, nl1 * 16, &err) ||
+      be::zero(dec->w_ascore.p, n * 16, &err))
+    return fail(CTCDEC_ERR_DEVICE, err);
+  const auto bytes_of = [&](int32_t u) { return posteriors_table_bytes(utt_frames[u], label_off[u + 1] - label_off[u]); };
+  const int64_t most = budget_groups(n_utts, bytes_of, budget, groups);
+  if (dec->w_ptab.ensure((size_t)std::max<int64_t>(most, 32), &err)) return fail(CTCDEC_ERR_DEVICE, err);
   return CTCDEC_OK;
 }
 
@@ -3060,22 +3011,16 @@ extern "C" {
 int ctcdec_posteriors_batch(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts, int32_t dtype,
                             int32_t is_device, const int64_t* label_off, const int32_t* labels, int32_t dense, int64_t table_budget,
                             ctcdec_posteriors** out) {
-  if (!dec || !out || n_utts < 0 || !label_off || table_budget < 0 || (n_utts > 0 && (!utt_logits || !utt_frames)))
-    return fail(CTCDEC_ERR_ARG, "bad arguments");
-  if (dtype < CTCDEC_F32 || dtype > CTCDEC_BF16) return fail(CTCDEC_ERR_ARG, "dtype must be f32, f64, f16 or bf16");
-  const int V = (int)dec->alpha.labels.size();
-  int blank = -1;
-  for (int v = 0; v < V && blank < 0; ++v)
-    if (dec->alpha.labels[(size_t)v].empty()) blank = v;
-  if (blank < 0) return fail(CTCDEC_ERR_ARG, "the alphabet has no blank label");
+  TranscriptCall tc;
+  const bool args_ok = dec && out && n_utts >= 0 && label_off && table_budget >= 0 && (n_utts == 0 || (utt_logits && utt_frames));
+  if (int rc = transcript_open(dec, args_ok, dtype, "", tc)) return rc;
   const int64_t budget = table_budget ? table_budget : POSTERIORS_TABLE_BUDGET;
-  if (int rc = check_posteriors(dec, utt_logits, utt_frames, n_utts, label_off, labels, budget, V, blank)) return rc;
+  if (int rc = check_posteriors(utt_logits, utt_frames, n_utts, label_off, labels, budget, tc)) return rc;
   const auto t_begin = Clock::now();
   std::unique_ptr<ctcdec_posteriors> res(new ctcdec_posteriors());
   const size_t n = (size_t)n_utts;
   const int64_t NL = label_off[n];
-  std::vector<int64_t> row0(n + 1, 0);
-  for (size_t u = 0; u < n; ++u) row0[u + 1] = row0[u] + utt_frames[u];
+  const std::vector<int64_t> row0 = row_starts(utt_frames, n);
   const int64_t R = row0[n];
   res->dense = dense != 0;
   res->tok_off.assign(label_off, label_off + n + 1);
@@ -3092,24 +3037,14 @@ int ctcdec_posteriors_batch(ctcdec_decoder* dec, const void* const* utt_logits, 
   if (dense) res->gamma.resize((size_t)res->gamma_off[n]);
   if (R > 0) {
     std::string err;
-    std::lock_guard<std::mutex> device_lock(g_device_mu);
-    if (be::bind_thread(&err)) return fail(CTCDEC_ERR_DEVICE, err);
     AlignFront fr;
-    if (int rc = align_front(dec, utt_logits, utt_frames, n_utts, dtype, is_device, V, row0, fr)) return rc;
-    res->ms[0] = fr.sniff_ms;
-    const size_t nl1 = (size_t)std::max<int64_t>(NL, 1);
-    if (dec->w_alab.ensure(nl1 * 4, &err) || dec->w_pocc.ensure(nl1 * 16, &err) || dec->w_ascore.ensure(n * 16, &err))
-      return fail(CTCDEC_ERR_DEVICE, err);
-    if ((NL && be::h2d(dec->w_alab.p, labels, (size_t)NL * 4, &err)) || be::zero(dec->w_pocc.p, nl1 * 16, &err) ||
-        be::zero(dec->w_ascore.p, n * 16, &err))
-      return fail(CTCDEC_ERR_DEVICE, err);
     std::vector<std::vector<int32_t>> groups;
-    const int64_t most = posteriors_groups(utt_frames, n_utts, label_off, budget, groups);
-    if (dec->w_ptab.ensure((size_t)std::max<int64_t>(most, 32), &err)) return fail(CTCDEC_ERR_DEVICE, err);
-    const double clip_lo = log(1e-15);  // ln(MIN_TOKEN_CLIP_P) (constants.py:17)
+    if (int rc = posteriors_front(dec, tc, utt_logits, utt_frames, n_utts, dtype, is_device, label_off, labels, budget, row0, fr, groups))
+      return rc;
+    res->ms[0] = fr.sniff_ms;
     PosteriorsLaunch pl;
     for (auto& g : groups) {
-      if (int rc = posteriors_launch(dec, g, fr, row0, utt_frames, label_off, NL, V, blank, dtype, dense, clip_lo, pl)) return rc;
+      if (int rc = posteriors_launch(dec, g, fr, row0, utt_frames, label_off, NL, tc, dtype, dense, pl)) return rc;
       const std::vector<int64_t>& tab_off = pl.tab_off;
       res->launches += pl.launches;
       res->launched[0] += pl.count[0];
@@ -3130,9 +3065,8 @@ int ctcdec_posteriors_batch(ctcdec_decoder* dec, const void* const* utt_logits, 
                be::d2h(res->centre.data(), (const double*)dec->w_pocc.p + NL, (size_t)NL * 8, &err)))
       return fail(CTCDEC_ERR_DEVICE, err);
 #ifndef CTC_SIM
-    double vit_ms = 0;
-    be::align_timing(&res->ms[1], &vit_ms);
-    res->ms[2] = be::posteriors_timing();
+    res->ms[1] = be::align_kernel_ms(be::K_ROW_LSE);
+    res->ms[2] = be::align_kernel_ms(be::K_POSTERIORS);
 #endif
   }
   res->ms[3] = ms(t_begin, Clock::now());
@@ -3186,8 +3120,9 @@ struct GradSeqCtx {
   int tid = 0, nt = 1;
   double sum(double v, int) { return v; }
 };
-template <int DT, class GT>
+template <int DT>
 void grad_rows_seq(const std::vector<GradUtt>& utts, int V, int blank, double clip_lo) {
+  typedef typename std::conditional<DT == 1, double, float>::type GT;  // (f64 for f64 rows, f32 for every other dtype)
   GradSeqCtx cx;
   for (const GradUtt& u : utts)
     for (int t = 0; t < u.T; ++t) ctc_grad_row<DT, GT>(cx, u, t, V, blank, clip_lo);
@@ -3200,25 +3135,21 @@ extern "C" {
 int ctcdec_gradient_batch(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts, int32_t dtype,
                           int32_t is_device, const int64_t* label_off, const int32_t* labels, void* const* grad_out, int32_t grad_dtype,
                           int64_t table_budget, double* logp_out, double* ms5, int32_t* launches_out, int64_t* launched2) {
-  if (!dec || n_utts < 0 || !label_off || table_budget < 0 || (n_utts > 0 && (!utt_logits || !utt_frames || !grad_out || !logp_out)))
-    return fail(CTCDEC_ERR_ARG, "bad arguments");
-  if (dtype < CTCDEC_F32 || dtype > CTCDEC_BF16) return fail(CTCDEC_ERR_ARG, "dtype must be f32, f64, f16 or bf16");
-  if (grad_dtype != (dtype == CTCDEC_F64 ? CTCDEC_F64 : CTCDEC_F32))
-    return fail(CTCDEC_ERR_ARG, "grad_dtype must be f64 for f64 logits and f32 for every other dtype");
-  const int V = (int)dec->alpha.labels.size();
-  int blank = -1;
-  for (int v = 0; v < V && blank < 0; ++v)
-    if (dec->alpha.labels[(size_t)v].empty()) blank = v;
-  if (blank < 0) return fail(CTCDEC_ERR_ARG, "the alphabet has no blank label");
+  TranscriptCall tc;
+  const bool args_ok = dec && n_utts >= 0 && label_off && table_budget >= 0 &&
+                       (n_utts == 0 || (utt_logits && utt_frames && grad_out && logp_out));
+  const bool grad_ok = grad_dtype == (dtype == CTCDEC_F64 ? CTCDEC_F64 : CTCDEC_F32);
+  if (int rc = transcript_open(dec, args_ok, dtype, grad_ok ? "" : "grad_dtype must be f64 for f64 logits and f32 for every other dtype", tc))
+    return rc;
+  const int V = tc.V;
   const int64_t budget = table_budget ? table_budget : POSTERIORS_TABLE_BUDGET;
-  if (int rc = check_posteriors(dec, utt_logits, utt_frames, n_utts, label_off, labels, budget, V, blank)) return rc;
+  if (int rc = check_posteriors(utt_logits, utt_frames, n_utts, label_off, labels, budget, tc)) return rc;
   for (int32_t u = 0; u < n_utts; ++u)
     if (utt_frames[u] > 0 && !grad_out[u]) return fail(CTCDEC_ERR_ARG, "utterance " + std::to_string(u) + ": no gradient buffer");
   const auto t_begin = Clock::now();
   const size_t n = (size_t)n_utts;
   const int64_t NL = label_off[n];
-  std::vector<int64_t> row0(n + 1, 0);
-  for (size_t u = 0; u < n; ++u) row0[u + 1] = row0[u] + utt_frames[u];
+  const std::vector<int64_t> row0 = row_starts(utt_frames, n);
   const int64_t R = row0[n];
   const size_t gsz = grad_dtype == CTCDEC_F64 ? 8 : 4;
   double tms[5] = {0, 0, 0, 0, 0};
@@ -3227,20 +3158,14 @@ int ctcdec_gradient_batch(ctcdec_decoder* dec, const void* const* utt_logits, co
   for (size_t u = 0; u < n; ++u) logp_out[u] = 0.0;  // (no frames and the empty target: the one empty alignment)
   if (R > 0) {
     std::string err;
-    std::lock_guard<std::mutex> device_lock(g_device_mu);
-    if (be::bind_thread(&err)) return fail(CTCDEC_ERR_DEVICE, err);
     AlignFront fr;
-    if (int rc = align_front(dec, utt_logits, utt_frames, n_utts, dtype, is_device, V, row0, fr)) return rc;
+    std::vector<std::vector<int32_t>> groups;
+    if (int rc = posteriors_front(dec, tc, utt_logits, utt_frames, n_utts, dtype, is_device, label_off, labels, budget, row0, fr, groups))
+      return rc;
     tms[0] = fr.sniff_ms;
-    const size_t nl1 = (size_t)std::max<int64_t>(NL, 1);
-    if (dec->w_alab.ensure(nl1 * 4, &err) || dec->w_pocc.ensure(nl1 * 16, &err) || dec->w_ascore.ensure(n * 16, &err))
-      return fail(CTCDEC_ERR_DEVICE, err);
-    if ((NL && be::h2d(dec->w_alab.p, labels, (size_t)NL * 4, &err)) || be::zero(dec->w_pocc.p, nl1 * 16, &err) ||
-        be::zero(dec->w_ascore.p, n * 16, &err))
-      return fail(CTCDEC_ERR_DEVICE, err);
     // every utterance's occurrence lists: [n][V + 1] offsets into its own part of the [NL] states, which are 2 k + 1 in the
     // order of k under each label
-    std::vector<int32_t> occ(n * (size_t)(V + 1) + nl1, 0);
+    std::vector<int32_t> occ(n * (size_t)(V + 1) + (size_t)std::max<int64_t>(NL, 1), 0);
     int32_t* const occ_state = occ.data() + n * (size_t)(V + 1);
     std::vector<int32_t> next((size_t)V);
     for (size_t u = 0; u < n; ++u) {
@@ -3254,9 +3179,6 @@ int ctcdec_gradient_batch(ctcdec_decoder* dec, const void* const* utt_logits, co
     if (upload(dec->w_gocc, occ, &err)) return fail(CTCDEC_ERR_DEVICE, err);
     const int32_t* const d_occ_off = (const int32_t*)dec->w_gocc.p;
     const int32_t* const d_occ_state = d_occ_off + n * (size_t)(V + 1);
-    std::vector<std::vector<int32_t>> groups;
-    const int64_t most = posteriors_groups(utt_frames, n_utts, label_off, budget, groups);
-    if (dec->w_ptab.ensure((size_t)std::max<int64_t>(most, 32), &err)) return fail(CTCDEC_ERR_DEVICE, err);
     if (!is_device) {  // a launch's rows leave through a buffer of the device's own
       int64_t rows = 0;
       for (const auto& g : groups) {
@@ -3266,11 +3188,10 @@ int ctcdec_gradient_batch(ctcdec_decoder* dec, const void* const* utt_logits, co
       }
       if (dec->w_grad.ensure((size_t)rows * (size_t)V * gsz, &err)) return fail(CTCDEC_ERR_DEVICE, err);
     }
-    const double clip_lo = log(1e-15);  // ln(MIN_TOKEN_CLIP_P) (constants.py:17)
     PosteriorsLaunch pl;
     std::vector<GradUtt> gutts;
     for (auto& g : groups) {
-      if (int rc = posteriors_launch(dec, g, fr, row0, utt_frames, label_off, NL, V, blank, dtype, 1, clip_lo, pl)) return rc;
+      if (int rc = posteriors_launch(dec, g, fr, row0, utt_frames, label_off, NL, tc, dtype, 1, pl)) return rc;
       launches += pl.launches;
       launched[0] += pl.count[0];
       launched[1] += pl.count[1];
@@ -3295,10 +3216,7 @@ int ctcdec_gradient_batch(ctcdec_decoder* dec, const void* const* utt_logits, co
         rows += utt_frames[u];
       }
 #ifdef CTC_SIM  // (the kernel's body, row by row)
-      if (dtype == 0) grad_rows_seq<0, float>(gutts, V, blank, clip_lo);
-      else if (dtype == 1) grad_rows_seq<1, double>(gutts, V, blank, clip_lo);
-      else if (dtype == 2) grad_rows_seq<2, float>(gutts, V, blank, clip_lo);
-      else grad_rows_seq<3, float>(gutts, V, blank, clip_lo);
+      for_dtype(dtype, [&](auto dt) { grad_rows_seq<decltype(dt)::value>(gutts, V, tc.blank, tc.clip_lo); });
 #else
       if (upload(dec->w_gutts, gutts, &err)) return fail(CTCDEC_ERR_DEVICE, err);
       be::GradRowsArgs ga;
@@ -3308,9 +3226,9 @@ int ctcdec_gradient_batch(ctcdec_decoder* dec, const void* const* utt_logits, co
       ga.n_rows = rows;
       ga.dtype = dtype;
       ga.grad_dtype = grad_dtype;
-      ga.blank = blank;
+      ga.blank = tc.blank;
       ga.pad = 0;
-      ga.clip_lo = clip_lo;
+      ga.clip_lo = tc.clip_lo;
       if (be::launch_ctc_grad_rows(ga, &err)) return fail(CTCDEC_ERR_DEVICE, err);
 #endif
       ++launches;
@@ -3325,10 +3243,9 @@ int ctcdec_gradient_batch(ctcdec_decoder* dec, const void* const* utt_logits, co
     for (size_t u = 0; u < n; ++u)
       if (utt_frames[u] > 0) logp_out[u] = pair[2 * u];
 #ifndef CTC_SIM
-    double vit_ms = 0;
-    be::align_timing(&tms[1], &vit_ms);
-    tms[2] = be::posteriors_timing();
-    tms[3] = be::grad_rows_timing();
+    tms[1] = be::align_kernel_ms(be::K_ROW_LSE);
+    tms[2] = be::align_kernel_ms(be::K_POSTERIORS);
+    tms[3] = be::align_kernel_ms(be::K_GRAD_ROWS);
 #endif
   }
   tms[4] = ms(t_begin, Clock::now());
@@ -3382,19 +3299,14 @@ extern "C" {
 int ctcdec_find_batch(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts, int32_t dtype,
                       int32_t is_device, const int64_t* hyp_off, const int64_t* label_off, const int32_t* labels, int32_t max_hits,
                       double min_logp, int32_t want_trace, int32_t kernel, int64_t trace_budget, ctcdec_search** out) {
-  if (!dec || !out || n_utts < 0 || !label_off || !hyp_off || trace_budget < 0 || (n_utts > 0 && (!utt_logits || !utt_frames)))
-    return fail(CTCDEC_ERR_ARG, "bad arguments");
-  if (dtype < CTCDEC_F32 || dtype > CTCDEC_BF16) return fail(CTCDEC_ERR_ARG, "dtype must be f32, f64, f16 or bf16");
-  if (kernel < 0 || kernel > 2) return fail(CTCDEC_ERR_ARG, "kernel must be 0 (the library chooses), 1 (wave) or 2 (group)");
-  if (max_hits < 1 || max_hits > FIND_MAX_HITS) return fail(CTCDEC_ERR_ARG, "max_hits must be in 1 .. " + std::to_string(FIND_MAX_HITS));
-  if (min_logp != min_logp) return fail(CTCDEC_ERR_ARG, "min_logp is not a number");
-  const int V = (int)dec->alpha.labels.size();
-  int blank = -1;
-  for (int v = 0; v < V && blank < 0; ++v)
-    if (dec->alpha.labels[(size_t)v].empty()) blank = v;
-  if (blank < 0) return fail(CTCDEC_ERR_ARG, "the alphabet has no blank label");
+  TranscriptCall tc;
+  const bool args_ok = dec && out && n_utts >= 0 && label_off && hyp_off && trace_budget >= 0 && (n_utts == 0 || (utt_logits && utt_frames));
+  std::string bad_option = bad_kernel(kernel);
+  if (bad_option.empty() && (max_hits < 1 || max_hits > FIND_MAX_HITS)) bad_option = "max_hits must be in 1 .. " + std::to_string(FIND_MAX_HITS);
+  if (bad_option.empty() && min_logp != min_logp) bad_option = "min_logp is not a number";
+  if (int rc = transcript_open(dec, args_ok, dtype, bad_option, tc)) return rc;
   std::vector<int32_t> need;
-  if (int rc = check_scores(utt_logits, utt_frames, n_utts, labels, label_off, hyp_off, V, blank, need, "phrase")) return rc;
+  if (int rc = check_scores(utt_logits, utt_frames, n_utts, labels, label_off, hyp_off, tc, need, "phrase")) return rc;
   const size_t n = (size_t)n_utts;
   const int64_t NH = hyp_off[n];
   const int64_t budget = trace_budget ? trace_budget : ALIGN_BP_BUDGET;
@@ -3432,14 +3344,11 @@ int ctcdec_find_batch(ctcdec_decoder* dec, const void* const* utt_logits, const 
     // (an utterance none of whose phrases is launched takes no part: nothing of it is staged, classified or summed)
     std::vector<int32_t> use_frames(n, 0);
     for (int32_t h : run) use_frames[(size_t)utt_of[(size_t)h]] = utt_frames[utt_of[(size_t)h]];
-    std::vector<int64_t> row0(n + 1, 0);
-    for (size_t u = 0; u < n; ++u) row0[u + 1] = row0[u] + use_frames[u];
+    const std::vector<int64_t> row0 = row_starts(use_frames.data(), n);
     const int64_t NL = label_off[NH];
     std::string err;
-    std::lock_guard<std::mutex> device_lock(g_device_mu);
-    if (be::bind_thread(&err)) return fail(CTCDEC_ERR_DEVICE, err);
     AlignFront fr;
-    if (int rc = align_front(dec, utt_logits, use_frames.data(), n_utts, dtype, is_device, V, row0, fr)) return rc;
+    if (int rc = align_front(dec, utt_logits, use_frames.data(), n_utts, dtype, is_device, tc.V, row0, fr)) return rc;
     res->ms[0] = fr.sniff_ms;
     // the call's hits: per phrase max_hits scores, then as many starts and ends, then the counts
     const size_t hits_bytes = (size_t)NH * K * 16 + (size_t)NH * 4;
@@ -3450,21 +3359,14 @@ int ctcdec_find_batch(ctcdec_decoder* dec, const void* const* utt_logits, const 
     int32_t* const d_start = (int32_t*)(d_logp + (size_t)NH * K);
     int32_t* const d_end = d_start + (size_t)NH * K;
     int32_t* const d_count = d_end + (size_t)NH * K;
-    // launches: phrases in input order until their traces fill the budget (ctcdec_align_batch's rule)
+    // launches: the launched phrases in input order until their traces fill the budget
     std::vector<std::vector<int32_t>> groups;
-    int64_t used = 0, most = 0;
-    for (int32_t h : run) {
-      const int64_t bytes = FIND_TRACE_BYTES * utt_frames[utt_of[(size_t)h]];
-      if (groups.empty() || used + bytes > budget) {
-        groups.emplace_back();
-        used = 0;
-      }
-      groups.back().push_back(h);
-      used += bytes;
-      most = std::max(most, used);
-    }
+    const auto bytes_of = [&](int32_t h) {
+      const int64_t T = utt_frames[utt_of[(size_t)h]];
+      return T >= need[(size_t)h] ? FIND_TRACE_BYTES * T : 0;
+    };
+    const int64_t most = budget_groups((int32_t)NH, bytes_of, budget, groups);
     if (dec->w_ftrace.ensure((size_t)most, &err)) return fail(CTCDEC_ERR_DEVICE, err);
-    const double clip_lo = log(1e-15);  // ln(MIN_TOKEN_CLIP_P) (constants.py:17)
     std::vector<FindPhrase> phrases;
     std::vector<double> t_logp;
     std::vector<int32_t> t_start;
@@ -3507,12 +3409,10 @@ int ctcdec_find_batch(ctcdec_decoder* dec, const void* const* utt_logits, const 
 #ifdef CTC_SIM  // (both kernels are the one body here: a single thread owns every group)
       std::vector<double> col((size_t)3 * (size_t)std::max(max_chunks[0], max_chunks[1]));
       FindSeqCtx cx;
-      for (const FindPhrase& a : phrases) {
-        if (dtype == 0) ctc_find_phrase<0>(cx, a, V, blank, clip_lo, max_hits, min_logp, col.data());
-        else if (dtype == 1) ctc_find_phrase<1>(cx, a, V, blank, clip_lo, max_hits, min_logp, col.data());
-        else if (dtype == 2) ctc_find_phrase<2>(cx, a, V, blank, clip_lo, max_hits, min_logp, col.data());
-        else ctc_find_phrase<3>(cx, a, V, blank, clip_lo, max_hits, min_logp, col.data());
-      }
+      for (const FindPhrase& a : phrases)
+        for_dtype(dtype, [&](auto dt) {
+          ctc_find_phrase<decltype(dt)::value>(cx, a, tc.V, tc.blank, tc.clip_lo, max_hits, min_logp, col.data());
+        });
       for (int w = 0; w < 2; ++w) res->launches += count[w] ? 1 : 0;
 #else
       if (upload(dec->w_fphr, phrases, &err)) return fail(CTCDEC_ERR_DEVICE, err);
@@ -3521,12 +3421,12 @@ int ctcdec_find_batch(ctcdec_decoder* dec, const void* const* utt_logits, const 
         be::FindArgs fa;
         fa.phrases = (const FindPhrase*)dec->w_fphr.p + (w ? count[0] : 0);
         fa.n_phrases = count[w];
-        fa.n_labels = V;
+        fa.n_labels = tc.V;
         fa.dtype = dtype;
-        fa.blank = blank;
+        fa.blank = tc.blank;
         fa.max_chunks = max_chunks[w];
         fa.max_hits = max_hits;
-        fa.clip_lo = clip_lo;
+        fa.clip_lo = tc.clip_lo;
         fa.min_logp = min_logp;
         if (be::launch_ctc_find(fa, w == 0, &err)) return fail(CTCDEC_ERR_DEVICE, err);
         ++res->launches;
@@ -3555,9 +3455,8 @@ int ctcdec_find_batch(ctcdec_decoder* dec, const void* const* utt_logits, const 
         be::d2h(h_end.data(), d_end, (size_t)NH * K * 4, &err) || be::d2h(n_hits.data(), d_count, (size_t)NH * 4, &err))
       return fail(CTCDEC_ERR_DEVICE, err);
 #ifndef CTC_SIM
-    double vit_ms = 0;
-    be::align_timing(&res->ms[1], &vit_ms);
-    res->ms[2] = be::find_timing();
+    res->ms[1] = be::align_kernel_ms(be::K_ROW_LSE);
+    res->ms[2] = be::align_kernel_ms(be::K_FIND);
 #endif
   }
   res->hit_off.assign((size_t)NH + 1, 0);

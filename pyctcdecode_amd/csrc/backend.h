@@ -313,16 +313,11 @@ struct ViterbiGapsArgs {
   double clip_lo;      // ln(MIN_TOKEN_CLIP_P)
 };
 int launch_ctc_viterbi_gaps(const ViterbiGapsArgs& a, std::string* err);
-// kernel times (HIP events) of the launch_row_lse / launch_ctc_viterbi / launch_ctc_forward / launch_ctc_posteriors /
-// launch_ctc_grad_rows / launch_ctc_find / launch_row_lse_max / launch_ctc_viterbi_gaps calls since the last reset; waits
-// for the kernels
+// kernel times (HIP events) of the launches of one of these kernels since the last reset; waits for the kernels.
+// ctc_forward and ctc_forward_wave share a log, as do ctc_find and ctc_find_wave.
+enum AlignKernel { K_ROW_LSE, K_VITERBI, K_FORWARD, K_POSTERIORS, K_GRAD_ROWS, K_FIND, K_ROW_LSE_MAX, K_VITERBI_GAPS, ALIGN_KERNELS };
 void align_timing_reset();
-void align_timing(double* row_lse_ms, double* viterbi_ms);
-void align_gaps_timing(double* row_lse_max_ms, double* viterbi_gaps_ms);
-double forward_timing();
-double posteriors_timing();
-double grad_rows_timing();
-double find_timing();
+double align_kernel_ms(AlignKernel kind);
 
 // stage timing (ms) of the last launch_prune / launch_beam pair, measured on the decode stream
 void last_timing(double* prune_ms, double* beam_ms);

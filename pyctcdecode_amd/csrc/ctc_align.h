@@ -1,19 +1,28 @@
-// ctc_align.h -- forced alignment of a known label sequence to an utterance's frames ("Forced alignment"): the
-// fp64 log-sum-exp of a frame row and the Viterbi recursion over the blank / label / blank / ... states, with its back-trace
-// and the confidence fold over the path; and the likelihood of a label sequence ("Transcript likelihood"): the
-// forward recursion over the same states, the sum over all alignments where the Viterbi takes the best one; and the frame
-// posteriors of a label sequence ("Frame posteriors"): the forward-backward over the same states; and the gradient
-// of the likelihood with respect to the frames' entries ("Transcript gradient"): the posteriors folded by label,
-// row by row; and the search for a phrase inside an utterance ("Phrase search"): the Viterbi recursion with a free
-// start and a free end, and the selection of its hits; and the alignment of a target with gaps ("Alignment with
-// gaps"): the row maximum next to the row's log-sum-exp, and the Viterbi recursion with its states in registers and slots that
-// take a frame's best entry. One body each for the HIP kernels (ctc_align_hip.hip: row_lse, ctc_viterbi, ctc_forward,
-// ctc_forward_wave, ctc_posteriors, ctc_grad_rows, ctc_find, ctc_find_wave, row_lse_max, ctc_viterbi_gaps) and for the CPU
-// simulator build, whose "device" memory is host memory (api.cpp under CTC_SIM runs them with a one-thread context).
+// ctc_align.h -- what is computed from an utterance's frames and a known label sequence ("Forced alignment" to
+// "Alignment with gaps"), over the states blank / label / blank / ... One body each for the HIP kernels (ctc_align_hip.hip)
+// and for the CPU simulator build, whose "device" memory is host memory (api.cpp under CTC_SIM runs them with a one-thread
+// context). The bodies:
+//   row_lse_seq, row_lse_max_seq   a row's fp64 log-sum-exp (and maximum): the simulator's; the kernels fold by lanes
+//   ctc_viterbi_utt                the best path, its columns in LDS            (kernel ctc_viterbi)
+//   ctc_forward_hyp / _wave_hyp    the sum over all paths                       (ctc_forward / ctc_forward_wave)
+//   ctc_posteriors_utt             the forward-backward                         (ctc_posteriors)
+//   ctc_grad_row                   the gradient of the likelihood, row by row   (ctc_grad_rows)
+//   ctc_find_phrase / _wave_phrase a phrase's occurrences, free start and end   (ctc_find / ctc_find_wave)
+//   ctc_viterbi_gaps_utt           the best path of a target with gaps          (ctc_viterbi_gaps)
+// The shared pieces, and who uses them:
+//   viterbi_backtrace, fold_token_logp                   ctc_viterbi, ctc_viterbi_gaps
+//   group_setup, EntrySource, FrameEntries               ctc_find, ctc_find_wave, ctc_viterbi_gaps
+//   thread_setup                                         ctc_find, ctc_viterbi_gaps
+// ctc_forward_hyp, ctc_forward_wave_hyp and ctc_posteriors_utt keep their loops in raw variables: over FrameEntries
+// ctc_forward took 8 to 13 % and ctc_posteriors 2 % longer on batches of 64 utterances (profiles/align_refactor_check.txt).
+//   find_trace, find_select                              ctc_find, ctc_find_wave
+//   for_dtype (host)                                     the launchers and the simulator's calls
 #pragma once
 #include <math.h>
 #include <stddef.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "common.h"
 #include "np_sum.h"
@@ -99,15 +108,16 @@ CTC_HD LseAcc lse_merge(const LseAcc& a, const LseAcc& b) {
 CTC_HD double lse_value(const LseAcc& a) { return a.m + log(a.s); }
 
 // One row, one thread (the simulator; the kernel spreads the same blocks over the lanes of a wave)
-CTC_HD double row_lse_seq(const void* x, int dtype, size_t row0, int V) {
+CTC_HD LseAcc row_fold_seq(const void* x, int dtype, size_t row0, int V) {
   LseAcc a = lse_empty();
   double v[ALIGN_LSE_BLOCK];
   for (int b = 0; b < V; b += ALIGN_LSE_BLOCK) {
     for (int i = 0; i < ALIGN_LSE_BLOCK; ++i) v[i] = b + i < V ? align_load(x, dtype, row0 + (size_t)(b + i)) : align_neg_inf();
     lse_push_block(a, v);
   }
-  return lse_value(a);
+  return a;
 }
+CTC_HD double row_lse_seq(const void* x, int dtype, size_t row0, int V) { return lse_value(row_fold_seq(x, dtype, row0, V)); }
 
 // ---- ctc_viterbi -------------------------------------------------------------------------------------------------------------
 // State s of the 2L+1: even = a blank, odd = target label s >> 1. A thread owns groups of four consecutive states (blank,
@@ -116,6 +126,51 @@ CTC_HD double row_lse_seq(const void* x, int dtype, size_t row0, int V) {
 // that hold a state reachable from the start (s <= 2t + 1) and from the end (s >= S - 2 - 2(T - 1 - t)); what lies below the
 // window of the previous frame reads as unreachable. `col`: 2 * 4 * align_chunks(L) doubles, shared by the threads of cx.
 // cx: tid, nt, sync().
+
+// The back-trace, by one thread: from state s of the last frame along the 2-bit back-pointers (four to a byte, nch bytes a
+// frame) to frame 0. Writes the path -- a label state its label, the even state 2j slot_value(j): the blank, or -1 for a gap
+// slot of ctc_viterbi_gaps -- and the span of every label.
+template <class SlotValue>
+CTC_HD void viterbi_backtrace(int s, int T, int nch, const uint8_t* bp, const int32_t* lab, int32_t* path, int32_t* tok_start,
+                              int32_t* tok_end, SlotValue slot_value) {
+  int open = -1;
+  for (int t = T - 1; t >= 0; --t) {
+    if (s & 1) {
+      const int k = s >> 1;
+      if (k != open) tok_end[k] = t + 1, open = k;
+      tok_start[k] = t;
+      path[t] = lab[k];
+    } else {
+      path[t] = slot_value(s >> 1);
+    }
+    if (t > 0) {
+      const unsigned b = (bp[(size_t)t * (size_t)nch + (size_t)(s >> 2)] >> (2 * (s & 3))) & 3u;
+      s -= (int)b;
+      if (s < 0) s = 0;
+    }
+  }
+}
+
+// The confidence fold, a thread per label: the mean, minimum or maximum of the label's log-probability over its span
+template <class Ctx>
+CTC_HD void fold_token_logp(Ctx& cx, const void* x, int dtype, const double* lse, const int32_t* lab, const int32_t* tok_start,
+                            const int32_t* tok_end, double* tok_logp, int T, int L, int V, bool is_prob, int fold, double clip_lo) {
+  for (int k = cx.tid; k < L; k += cx.nt) {
+    int t0 = tok_start[k], t1 = tok_end[k];
+    t0 = t0 < 0 ? 0 : t0;
+    t1 = t1 > T ? T : t1;
+    const size_t lb = (size_t)lab[k];
+    double acc = 0.0;
+    for (int t = t0; t < t1; ++t) {
+      const double lp = align_emit(x, dtype, (size_t)t * (size_t)V + lb, is_prob ? 0.0 : lse[t], is_prob, clip_lo);
+      if (fold == LOGP_MEAN) acc += lp;
+      else if (fold == LOGP_MIN) acc = (t == t0 || lp < acc) ? lp : acc;
+      else acc = (t == t0 || lp > acc) ? lp : acc;
+    }
+    tok_logp[k] = fold == LOGP_MEAN ? acc / (double)(t1 - t0) : acc;
+  }
+}
+
 template <class Ctx>
 CTC_HD void ctc_viterbi_utt(Ctx& cx, const AlignUtt& u, int V, int dtype, int blank, int fold, double clip_lo, double* col) {
   const int T = u.T, L = u.L;
@@ -191,39 +246,11 @@ CTC_HD void ctc_viterbi_utt(Ctx& cx, const AlignUtt& u, int V, int dtype, int bl
     const double* fin = ((T - 1) & 1) ? c1 : c0;
     int s = (L > 0 && fin[S - 2] >= fin[S - 1]) ? S - 2 : S - 1;
     *u.score = fin[s];
-    int open = -1;
-    for (int t = T - 1; t >= 0; --t) {
-      if (s & 1) {
-        const int k = s >> 1;
-        if (k != open) u.tok_end[k] = t + 1, open = k;
-        u.tok_start[k] = t;
-        u.path[t] = u.lab[k];
-      } else {
-        u.path[t] = blank;
-      }
-      if (t > 0) {
-        const unsigned b = (u.bp[(size_t)t * (size_t)nch + (size_t)(s >> 2)] >> (2 * (s & 3))) & 3u;
-        s -= (int)b;
-        if (s < 0) s = 0;
-      }
-    }
+    viterbi_backtrace(s, T, nch, u.bp, u.lab, u.path, u.tok_start, u.tok_end, [&](int) { return blank; });
   }
   if (!fold) return;
   cx.sync();  // (the spans thread 0 wrote are read by every thread)
-  for (int k = cx.tid; k < L; k += cx.nt) {
-    int t0 = u.tok_start[k], t1 = u.tok_end[k];
-    t0 = t0 < 0 ? 0 : t0;
-    t1 = t1 > T ? T : t1;
-    const size_t lab = (size_t)u.lab[k];
-    double acc = 0.0;
-    for (int t = t0; t < t1; ++t) {
-      const double lp = align_emit(u.x, dtype, (size_t)t * (size_t)V + lab, is_prob ? 0.0 : u.lse[t], is_prob, clip_lo);
-      if (fold == LOGP_MEAN) acc += lp;
-      else if (fold == LOGP_MIN) acc = (t == t0 || lp < acc) ? lp : acc;
-      else acc = (t == t0 || lp > acc) ? lp : acc;
-    }
-    u.tok_logp[k] = fold == LOGP_MEAN ? acc / (double)(t1 - t0) : acc;
-  }
+  fold_token_logp(cx, u.x, dtype, u.lse, u.lab, u.tok_start, u.tok_end, u.tok_logp, T, L, V, is_prob, fold, clip_lo);
 }
 
 // ---- ctc_forward / ctc_forward_wave ----------------------------------------------------------------------------------------
@@ -302,6 +329,84 @@ CTC_HD double align_widen(typename AlignRaw<DT>::type r) {
   if (DT == 0 || DT == 1) return (double)r;
   return (double)(DT == 2 ? f16_bits_to_f32((uint16_t)r) : bf16_bits_to_f32((uint16_t)r));
 }
+// (host) f(std::integral_constant<int, DT>()) for a dtype code: how a launcher, or the simulator, picks an instantiation
+template <class F>
+void for_dtype(int dtype, F f) {
+  if (dtype == 0) f(std::integral_constant<int, 0>());
+  else if (dtype == 1) f(std::integral_constant<int, 1>());
+  else if (dtype == 2) f(std::integral_constant<int, 2>());
+  else f(std::integral_constant<int, 3>());
+}
+
+// ---- what the bodies with a group per thread (or lane) share -----------------------------------------------------------------
+// Like ctc_forward and ctc_posteriors, ctc_find and ctc_viterbi_gaps give thread tid of cx (tid, nt, sync(); Ctx::GROUPS * nt >= the
+// target's groups) the groups tid, tid + nt, ... for the whole recursion: their labels and skip flags are read once, their
+// states stay in registers, and only a group's last state goes through LDS to the thread that owns the group above, one
+// barrier per frame. ctc_forward_wave and ctc_find_wave give lane c group c and pass that state by a shuffle.
+
+// Where a thread's entries come from, fixed for the recursion
+template <int G>
+struct EntrySource {
+  const void* x;        // [T, V] the utterance's matrix
+  const double* lse_v;  // [T] the rows' log-sum-exps (any valid address for probabilities: never used)
+  const double* max_v;  // [T] the rows' maxima (ctc_viterbi_gaps; else null)
+  int V, blank;
+  bool is_prob;
+  double clip_lo;
+  int i0[G], i1[G];     // the columns each group's two labels read
+};
+
+// Group c of a target with nch groups: the ForwardGroup, or the empty group past the last one, and the columns its two
+// labels read -- the blank's where the target ends before them, so that a load there is valid whatever the group
+CTC_HD ForwardGroup group_setup(const int32_t* lab, int L, int nch, int c, int blank, int* i0, int* i1) {
+  const ForwardGroup g = c < nch ? forward_group(lab, L, c) : ForwardGroup{-1, -1, false, false, false};
+  *i0 = g.l0 >= 0 ? g.l0 : blank;
+  *i1 = g.l1 >= 0 ? g.l1 : blank;
+  return g;
+}
+
+// A thread's opening: its groups, and the source of its entries
+template <class Ctx>
+CTC_HD void thread_setup(const Ctx& cx, const void* x, const double* lse, const double* rmax, const int32_t* lab, int L, int nch, int V,
+                         int blank, bool is_prob, double clip_lo, ForwardGroup* g, EntrySource<Ctx::GROUPS>& src) {
+  CTC_UNROLL
+  for (int k = 0; k < Ctx::GROUPS; ++k) g[k] = group_setup(lab, L, nch, cx.tid + k * cx.nt, blank, &src.i0[k], &src.i1[k]);
+  // (always 0, but per thread as far as the compiler knows: a row's log-sum-exp -- and maximum -- then comes by a vector load
+  // like the entries. Loaded at a workgroup-uniform address it would be a scalar load, which shares its counter with the LDS
+  // reads: the wait for the neighbour's state would wait for the next frame's value as well.)
+  const int per_thread_zero = g[0].l0 == -2 ? 1 : 0;
+  src.x = x;
+  src.lse_v = lse + per_thread_zero;
+  src.max_v = rmax ? rmax + per_thread_zero : nullptr;
+  src.V = V, src.blank = blank, src.is_prob = is_prob, src.clip_lo = clip_lo;
+}
+
+// A thread's entries of one frame, kept as loaded (AlignRaw). Nothing a recursion computes decides the entries of the frame
+// after: a body asks for them -- request(): loads alone, without a branch, at indices that are always valid -- into a second
+// instance after the neighbour's state is in hand and before the frame's arithmetic and barrier, and hands them over by
+// assignment at the end of the frame.
+template <int DT, int G, bool MAX = false>
+struct FrameEntries {
+  typedef typename AlignRaw<DT>::type Raw;
+  Raw vb, v0[G], v1[G];  // the blank's entry, and those of each group's two labels
+  double lse_t, max_t;   // the row's log-sum-exp and (MAX) maximum
+  CTC_HD void request(const EntrySource<G>& s, int tn) {
+    const size_t row = (size_t)tn * (size_t)s.V;
+    vb = align_load_raw<DT>(s.x, row + (size_t)s.blank);
+    lse_t = s.lse_v[tn];
+    max_t = MAX ? s.max_v[tn] : 0.0;
+    CTC_UNROLL
+    for (int k = 0; k < G; ++k) {
+      v0[k] = align_load_raw<DT>(s.x, row + (size_t)s.i0[k]);
+      v1[k] = align_load_raw<DT>(s.x, row + (size_t)s.i1[k]);
+    }
+  }
+  CTC_HD double emit(const EntrySource<G>& s, double v) const { return align_emit_of_value(v, s.is_prob ? 0.0 : lse_t, s.is_prob, s.clip_lo); }
+  CTC_HD double emit_blank(const EntrySource<G>& s) const { return emit(s, align_widen<DT>(vb)); }
+  CTC_HD double emit0(const EntrySource<G>& s, int k) const { return emit(s, align_widen<DT>(v0[k])); }
+  CTC_HD double emit1(const EntrySource<G>& s, int k) const { return emit(s, align_widen<DT>(v1[k])); }
+  CTC_HD double emit_max(const EntrySource<G>& s) const { return emit(s, max_t); }
+};
 
 // ctc_forward: the threads of cx (tid, nt, sync(); Ctx::GROUPS * nt >= align_chunks(L)) share one hypothesis of a matrix of
 // dtype DT. Thread tid owns the groups tid, tid + nt, ... for the whole recursion: their labels and skip flags are read once,
@@ -923,23 +1028,24 @@ CTC_HD void find_select(Ctx& cx, const FindPhrase& ph, int max_hits, double min_
   if (lane == 0) *ph.n_hits = n;
 }
 
+// The trace's entry of frame t, by whoever owns state S - 2, the last label (entry jf = 1 or 3 of its group)
+CTC_HD void find_trace(double* end_logp, int32_t* end_start, int t, int jf, const double* d, const int32_t* st) {
+  const double v = jf == 1 ? d[1] : d[3];
+  end_logp[t] = v;
+  end_start[t] = v > align_neg_inf() ? (jf == 1 ? st[1] : st[3]) : -1;
+}
+
 // ctc_find: the threads of cx (tid, nt, sync(); Ctx::GROUPS * nt >= find_chunks(L)) share one phrase of a matrix of dtype DT,
-// arranged as ctc_forward_hyp is: thread tid owns the groups tid, tid + nt, ... for the whole recursion, their scores and
-// start frames stay in registers, and only a group's last state goes through `col` -- 2 * find_chunks(L) doubles, then as many
-// int32: the columns of two successive frames -- to the thread that owns the group above: one barrier per frame. Frame
-// t + 1's entries are requested before frame t's arithmetic and kept as loaded. The thread that owns state S - 2 writes the
-// trace; after the last frame its wavefront alone (cx.same_wave, after cx.publish) selects the hits from what it wrote.
+// arranged as ctc_forward is: a group's scores and start frames stay in registers, and only its last state goes through `col`
+// -- 2 * find_chunks(L) doubles, then as many int32: the columns of two successive frames -- to the thread that owns the group
+// above: one barrier per frame. The thread that owns state S - 2 writes the trace; after the last frame its wavefront alone
+// (cx.same_wave, after cx.publish) selects the hits from what it wrote.
 template <int DT, class Ctx>
 CTC_HD void ctc_find_phrase(Ctx& cx, const FindPhrase& ph, int V, int blank, double clip_lo, int max_hits, double min_logp, double* col) {
-  typedef typename AlignRaw<DT>::type Raw;
   constexpr int G = Ctx::GROUPS;
-  const void* const x = ph.x;  // (the record, once: the frame loop reads none of it again)
-  const double* const lse = ph.lse;
-  const int32_t* const lab = ph.lab;
-  double* const end_logp = ph.end_logp;
+  double* const end_logp = ph.end_logp;  // (the record, once: the frame loop reads none of it again)
   int32_t* const end_start = ph.end_start;
   const int T = ph.T, L = ph.L;
-  const bool is_prob = ph.is_prob != 0;
   if (T <= 0 || L <= 0) return;
   const int nch = find_chunks(L);
   const int cf = (2 * L - 1) >> 2, jf = (2 * L - 1) & 3;  // state S - 2, the last label: entry 1 or 3 of its group
@@ -947,32 +1053,19 @@ CTC_HD void ctc_find_phrase(Ctx& cx, const FindPhrase& ph, int V, int blank, dou
   double* const col_d = col;
   int32_t* const col_s = (int32_t*)(col + 2 * nch);
   ForwardGroup g[G];
-  int i0[G], i1[G];  // the columns a group's two labels read (the blank's where the phrase ends before them)
+  EntrySource<G> src;
+  thread_setup(cx, ph.x, ph.lse, nullptr, ph.lab, L, nch, V, blank, ph.is_prob != 0, clip_lo, g, src);
   double d[G][4];    // scores
   int32_t st[G][4];  // start frames
-  Raw v0[G], v1[G];  // the entries of the frame in hand at those columns, as loaded
   CTC_UNROLL
   for (int k = 0; k < G; ++k) {
-    const int c = cx.tid + k * cx.nt;
     d[k][0] = d[k][1] = d[k][2] = d[k][3] = NEG;
     st[k][0] = st[k][1] = st[k][2] = st[k][3] = -1;
-    if (c < nch) g[k] = forward_group(lab, L, c);
-    else g[k] = ForwardGroup{-1, -1, false, false, false};
-    i0[k] = g[k].l0 >= 0 ? g[k].l0 : blank;
-    i1[k] = g[k].l1 >= 0 ? g[k].l1 : blank;
   }
-  // (always 0, but per thread as far as the compiler knows: a row's log-sum-exp then comes by a vector load, as in ctc_forward_hyp)
-  const int per_thread_zero = g[0].l0 == -2 ? 1 : 0;
-  const double* const lse_v = lse + per_thread_zero;
   for (int i = cx.tid; i < 2 * nch; i += cx.nt) col_d[i] = NEG, col_s[i] = -1;
   cx.sync();
-  Raw vb = align_load_raw<DT>(x, (size_t)blank);
-  double lse_t = lse_v[0];
-  CTC_UNROLL
-  for (int k = 0; k < G; ++k) {
-    v0[k] = align_load_raw<DT>(x, (size_t)i0[k]);
-    v1[k] = align_load_raw<DT>(x, (size_t)i1[k]);
-  }
+  FrameEntries<DT, G> now, next;
+  now.request(src, 0);
   for (int t = 0; t < T; ++t) {
     const int po = ((t + 1) & 1) * nch, co = (t & 1) * nch;
     double dm1[G];
@@ -983,37 +1076,18 @@ CTC_HD void ctc_find_phrase(Ctx& cx, const FindPhrase& ph, int V, int blank, dou
       dm1[k] = c > 0 && c < nch ? col_d[po + c - 1] : NEG;
       sm1[k] = c > 0 && c < nch ? col_s[po + c - 1] : -1;
     }
-    // then ask for frame t + 1 (after the last frame: the last frame again)
-    const int tn = t + 1 < T ? t + 1 : t;
-    const size_t row = (size_t)tn * (size_t)V;
-    const Raw nvb = align_load_raw<DT>(x, row + (size_t)blank);
-    const double nlse = lse_v[tn];
-    Raw n0[G], n1[G];
-    CTC_UNROLL
-    for (int k = 0; k < G; ++k) {
-      n0[k] = align_load_raw<DT>(x, row + (size_t)i0[k]);
-      n1[k] = align_load_raw<DT>(x, row + (size_t)i1[k]);
-    }
-    const double lse_use = is_prob ? 0.0 : lse_t;
-    const double e_blank = align_emit_of_value(align_widen<DT>(vb), lse_use, is_prob, clip_lo);
+    next.request(src, t + 1 < T ? t + 1 : t);  // (after the last frame: the last frame again)
+    const double e_blank = now.emit_blank(src);
     CTC_UNROLL
     for (int k = 0; k < G; ++k) {
       const int c = cx.tid + k * cx.nt;
       if (c >= nch) continue;
-      const double e0 = align_emit_of_value(align_widen<DT>(v0[k]), lse_use, is_prob, clip_lo);
-      const double e1 = align_emit_of_value(align_widen<DT>(v1[k]), lse_use, is_prob, clip_lo);
-      find_step(g[k], c == 0, t, dm1[k], sm1[k], e_blank, e0, e1, d[k], st[k]);
+      find_step(g[k], c == 0, t, dm1[k], sm1[k], e_blank, now.emit0(src, k), now.emit1(src, k), d[k], st[k]);
       col_d[co + c] = d[k][3];
       col_s[co + c] = st[k][3];
-      if (c == cf) {
-        const double v = jf == 1 ? d[k][1] : d[k][3];
-        end_logp[t] = v;
-        end_start[t] = v > NEG ? (jf == 1 ? st[k][1] : st[k][3]) : -1;
-      }
+      if (c == cf) find_trace(end_logp, end_start, t, jf, d[k], st[k]);
     }
-    vb = nvb, lse_t = nlse;
-    CTC_UNROLL
-    for (int k = 0; k < G; ++k) v0[k] = n0[k], v1[k] = n1[k];
+    now = next;
     cx.sync();  // the one barrier of a frame: the columns swap roles
   }
   if (!cx.same_wave(cf % cx.nt)) return;
@@ -1023,49 +1097,31 @@ CTC_HD void ctc_find_phrase(Ctx& cx, const FindPhrase& ph, int V, int blank, dou
 
 // ctc_find_wave: one wavefront per phrase of at most FIND_WAVE_MAX_LABELS labels. Lane c owns group c; the last state of the
 // group below -- a score and a start frame -- comes from lane c - 1 by cx.up() / cx.up_i(): no LDS, no barrier. The same
-// groups, steps and prefetch as ctc_find_phrase, so the same bits. Lane cf writes the trace, the wave selects.
+// groups, steps and entries as ctc_find_phrase, so the same bits. Lane cf writes the trace, the wave selects.
 template <int DT, class Ctx>
 CTC_HD void ctc_find_wave_phrase(Ctx& cx, const FindPhrase& ph, int V, int blank, double clip_lo, int max_hits, double min_logp) {
-  typedef typename AlignRaw<DT>::type Raw;
-  const void* const x = ph.x;
-  const double* const lse = ph.lse;
-  const int32_t* const lab = ph.lab;
   double* const end_logp = ph.end_logp;
   int32_t* const end_start = ph.end_start;
   const int T = ph.T, L = ph.L, c = cx.lane();
-  const bool is_prob = ph.is_prob != 0;
   if (T <= 0 || L <= 0) return;
   const int nch = find_chunks(L);
   const int cf = (2 * L - 1) >> 2, jf = (2 * L - 1) & 3;
   const double NEG = align_neg_inf();
-  const ForwardGroup g = c < nch ? forward_group(lab, L, c) : ForwardGroup{-1, -1, false, false, false};
-  const int i0 = g.l0 >= 0 ? g.l0 : blank, i1 = g.l1 >= 0 ? g.l1 : blank;
+  EntrySource<1> src = {ph.x, ph.lse, nullptr, V, blank, ph.is_prob != 0, clip_lo, {0}, {0}};
+  const ForwardGroup g = group_setup(ph.lab, L, nch, c, blank, &src.i0[0], &src.i1[0]);
   double d[4] = {NEG, NEG, NEG, NEG};
   int32_t st[4] = {-1, -1, -1, -1};
-  Raw vb = align_load_raw<DT>(x, (size_t)blank);
-  Raw v0 = align_load_raw<DT>(x, (size_t)i0), v1 = align_load_raw<DT>(x, (size_t)i1);
-  double lse_t = lse[0];
+  FrameEntries<DT, 1> now, next;
+  now.request(src, 0);
   for (int t = 0; t < T; ++t) {
     const double below_d = cx.up(d[3]);  // (every lane takes part)
     const int32_t below_s = cx.up_i(st[3]);
-    const int tn = t + 1 < T ? t + 1 : t;
-    const size_t row = (size_t)tn * (size_t)V;
-    const Raw nvb = align_load_raw<DT>(x, row + (size_t)blank);
-    const Raw n0 = align_load_raw<DT>(x, row + (size_t)i0), n1 = align_load_raw<DT>(x, row + (size_t)i1);
-    const double nlse = lse[tn];
+    next.request(src, t + 1 < T ? t + 1 : t);
     if (c < nch) {
-      const double lse_use = is_prob ? 0.0 : lse_t;
-      const double e_blank = align_emit_of_value(align_widen<DT>(vb), lse_use, is_prob, clip_lo);
-      const double e0 = align_emit_of_value(align_widen<DT>(v0), lse_use, is_prob, clip_lo);
-      const double e1 = align_emit_of_value(align_widen<DT>(v1), lse_use, is_prob, clip_lo);
-      find_step(g, c == 0, t, c > 0 ? below_d : NEG, c > 0 ? below_s : -1, e_blank, e0, e1, d, st);
-      if (c == cf) {
-        const double v = jf == 1 ? d[1] : d[3];
-        end_logp[t] = v;
-        end_start[t] = v > NEG ? (jf == 1 ? st[1] : st[3]) : -1;
-      }
+      find_step(g, c == 0, t, c > 0 ? below_d : NEG, c > 0 ? below_s : -1, now.emit_blank(src), now.emit0(src, 0), now.emit1(src, 0), d, st);
+      if (c == cf) find_trace(end_logp, end_start, t, jf, d, st);
     }
-    vb = nvb, lse_t = nlse, v0 = n0, v1 = n1;
+    now = next;
   }
   cx.publish();
   find_select(cx, ph, max_hits, min_logp);
@@ -1092,12 +1148,7 @@ CTC_HD void row_lse_max_seq(const void* x, int dtype, size_t row0, int V, bool i
     *max_out = m;
     return;
   }
-  LseAcc a = lse_empty();
-  double v[ALIGN_LSE_BLOCK];
-  for (int b = 0; b < V; b += ALIGN_LSE_BLOCK) {
-    for (int i = 0; i < ALIGN_LSE_BLOCK; ++i) v[i] = b + i < V ? align_load(x, dtype, row0 + (size_t)(b + i)) : align_neg_inf();
-    lse_push_block(a, v);
-  }
+  const LseAcc a = row_fold_seq(x, dtype, row0, V);
   *lse_out = lse_value(a);
   *max_out = a.m;
 }
@@ -1166,18 +1217,16 @@ CTC_HD unsigned gap_step(const ForwardGroup& g, bool gap0, bool gap2, double pm1
 }
 
 // ctc_viterbi_gaps: the threads of cx (tid, nt, sync(); Ctx::GROUPS * nt >= align_chunks(L)) share one utterance of a matrix of
-// dtype DT, arranged as ctc_forward_hyp / ctc_find_phrase are: thread tid owns the groups tid, tid + nt, ... for the whole
-// recursion, their scores stay in registers, and only a group's last state goes through `col` -- 2 * align_chunks(L) doubles,
-// the columns of two successive frames -- to the thread that owns the group above: one barrier per frame. Frame t + 1's
-// entries (the blank, the group's labels, the row's log-sum-exp and maximum) are requested before frame t's arithmetic and
-// kept as loaded. Per frame and group one byte of back-pointers, neighbouring threads writing neighbouring bytes. No window
-// of reachable states: every state exists in every frame, and all but states 0 and 1 begin at -inf (every emission is finite,
-// so -inf stays -inf until a path arrives; a state no path can leave towards the end is never traced). After the last frame
-// the thread that owns the last state walks the back-pointers, as ctc_viterbi's does; then one thread per label folds its
-// confidence and one thread per gap sums g(t) over the gap's frames.
+// dtype DT, arranged as ctc_forward / ctc_find are: a group's scores stay in registers, and only its last state goes through
+// `col` -- 2 * align_chunks(L) doubles, the columns of two successive frames -- to the thread that owns the group above: one
+// barrier per frame. A frame's entries are the blank, the group's labels, and the row's log-sum-exp and maximum. Per frame
+// and group one byte of back-pointers, neighbouring threads writing neighbouring bytes. No window of reachable states: every
+// state exists in every frame, and all but states 0 and 1 begin at -inf (every emission is finite, so -inf stays -inf until a
+// path arrives; a state no path can leave towards the end is never traced). After the last frame the thread that owns the
+// last state walks the back-pointers, as ctc_viterbi's does; then one thread per label folds its confidence and one thread per
+// gap sums g(t) over the gap's frames.
 template <int DT, class Ctx>
 CTC_HD void ctc_viterbi_gaps_utt(Ctx& cx, const GapsUtt& utt, int V, int blank, int fold, double clip_lo, double* col) {
-  typedef typename AlignRaw<DT>::type Raw;
   constexpr int G = Ctx::GROUPS;
   const void* const x = utt.x;  // (the record, once: the frame loop reads none of it again)
   const double* const lse = utt.lse;
@@ -1191,26 +1240,17 @@ CTC_HD void ctc_viterbi_gaps_utt(Ctx& cx, const GapsUtt& utt, int V, int blank, 
   const int S = 2 * L + 1, nch = align_chunks(L);
   const double NEG = align_neg_inf();
   ForwardGroup g[G];
+  EntrySource<G> src;
+  thread_setup(cx, x, is_prob ? rmax : lse, rmax, lab, L, nch, V, blank, is_prob, clip_lo, g, src);
   bool gap0[G], gap2[G];
-  int i0[G], i1[G];  // the columns a group's two labels read (the blank's where the target ends before them)
-  double p[G][4];    // scores
-  Raw v0[G], v1[G];  // the entries of the frame in hand at those columns, as loaded
+  double p[G][4];  // scores
   CTC_UNROLL
   for (int k = 0; k < G; ++k) {
     const int c = cx.tid + k * cx.nt;
     p[k][0] = p[k][1] = p[k][2] = p[k][3] = NEG;
-    if (c < nch) g[k] = forward_group(lab, L, c);
-    else g[k] = ForwardGroup{-1, -1, false, false, false};
     gap0[k] = c < nch && 2 * c <= L && gap[2 * c] != 0;
     gap2[k] = c < nch && 2 * c + 1 <= L && gap[2 * c + 1] != 0;
-    i0[k] = g[k].l0 >= 0 ? g[k].l0 : blank;
-    i1[k] = g[k].l1 >= 0 ? g[k].l1 : blank;
   }
-  // (always 0, but per thread as far as the compiler knows: a row's log-sum-exp and maximum then come by vector loads, as in
-  // ctc_forward_hyp)
-  const int per_thread_zero = g[0].l0 == -2 ? 1 : 0;
-  const double* const lse_v = (is_prob ? rmax : lse) + per_thread_zero;  // (probabilities: any valid address, never used)
-  const double* const max_v = rmax + per_thread_zero;
   for (int i = cx.tid; i < 2 * nch; i += cx.nt) col[i] = NEG;
   if (cx.tid == 0) {  // frame 0: states 0 and 1
     const double lse0 = is_prob ? 0.0 : lse[0];
@@ -1219,14 +1259,8 @@ CTC_HD void ctc_viterbi_gaps_utt(Ctx& cx, const GapsUtt& utt, int V, int blank, 
   }
   cx.sync();
   // frame 1's entries (a single frame: frame 0's again, never used)
-  const size_t row1 = T > 1 ? (size_t)V : 0;
-  Raw vb = align_load_raw<DT>(x, row1 + (size_t)blank);
-  double lse_t = lse_v[T > 1 ? 1 : 0], max_t = max_v[T > 1 ? 1 : 0];
-  CTC_UNROLL
-  for (int k = 0; k < G; ++k) {
-    v0[k] = align_load_raw<DT>(x, row1 + (size_t)i0[k]);
-    v1[k] = align_load_raw<DT>(x, row1 + (size_t)i1[k]);
-  }
+  FrameEntries<DT, G, true> now, next;
+  now.request(src, T > 1 ? 1 : 0);
   for (int t = 1; t < T; ++t) {
     const double* prev = col + ((t - 1) & 1) * nch;
     double* cur = col + (t & 1) * nch;
@@ -1236,34 +1270,18 @@ CTC_HD void ctc_viterbi_gaps_utt(Ctx& cx, const GapsUtt& utt, int V, int blank, 
       const int c = cx.tid + k * cx.nt;
       pm1[k] = c > 0 && c < nch ? prev[c - 1] : NEG;
     }
-    // then ask for frame t + 1 (after the last frame: the last frame again)
-    const int tn = t + 1 < T ? t + 1 : t;
-    const size_t row = (size_t)tn * (size_t)V;
-    const Raw nvb = align_load_raw<DT>(x, row + (size_t)blank);
-    const double nlse = lse_v[tn], nmax = max_v[tn];
-    Raw n0[G], n1[G];
-    CTC_UNROLL
-    for (int k = 0; k < G; ++k) {
-      n0[k] = align_load_raw<DT>(x, row + (size_t)i0[k]);
-      n1[k] = align_load_raw<DT>(x, row + (size_t)i1[k]);
-    }
-    const double lse_use = is_prob ? 0.0 : lse_t;
-    const double e_blank = align_emit_of_value(align_widen<DT>(vb), lse_use, is_prob, clip_lo);
-    const double e_gap = align_emit_of_value(max_t, lse_use, is_prob, clip_lo);
+    next.request(src, t + 1 < T ? t + 1 : t);  // (after the last frame: the last frame again)
+    const double e_blank = now.emit_blank(src), e_gap = now.emit_max(src);
     uint8_t* const bp_row = bps + (size_t)t * (size_t)nch;
     CTC_UNROLL
     for (int k = 0; k < G; ++k) {
       const int c = cx.tid + k * cx.nt;
       if (c >= nch) continue;
-      const double e0 = align_emit_of_value(align_widen<DT>(v0[k]), lse_use, is_prob, clip_lo);
-      const double e1 = align_emit_of_value(align_widen<DT>(v1[k]), lse_use, is_prob, clip_lo);
-      const unsigned b = gap_step(g[k], gap0[k], gap2[k], pm1[k], e_blank, e_gap, e0, e1, p[k]);
+      const unsigned b = gap_step(g[k], gap0[k], gap2[k], pm1[k], e_blank, e_gap, now.emit0(src, k), now.emit1(src, k), p[k]);
       cur[c] = p[k][3];
       bp_row[c] = (uint8_t)b;
     }
-    vb = nvb, lse_t = nlse, max_t = nmax;
-    CTC_UNROLL
-    for (int k = 0; k < G; ++k) v0[k] = n0[k], v1[k] = n1[k];
+    now = next;
     cx.sync();  // the one barrier of a frame: the columns swap roles
   }
   // back-trace, by the thread that holds the last slot (state S - 1 = 2L: entry 0 or 2 of its group; the last label is the
@@ -1275,24 +1293,9 @@ CTC_HD void ctc_viterbi_gaps_utt(Ctx& cx, const GapsUtt& utt, int V, int blank, 
     if (cx.tid + k * cx.nt != cf) continue;
     const double last = jf == 2 ? p[k][2] : p[k][0];
     const double before = jf == 2 ? p[k][1] : fin[cf - 1];  // (L >= 1: jf == 0 only in a group above the first)
-    int s = before >= last ? S - 2 : S - 1;
     *utt.score = before >= last ? before : last;
-    int open = -1;
-    for (int t = T - 1; t >= 0; --t) {
-      if (s & 1) {
-        const int kk = s >> 1;
-        if (kk != open) utt.tok_end[kk] = t + 1, open = kk;
-        utt.tok_start[kk] = t;
-        utt.path[t] = lab[kk];
-      } else {
-        utt.path[t] = gap[s >> 1] ? -1 : blank;
-      }
-      if (t > 0) {
-        const unsigned b = (bps[(size_t)t * (size_t)nch + (size_t)(s >> 2)] >> (2 * (s & 3))) & 3u;
-        s -= (int)b;
-        if (s < 0) s = 0;
-      }
-    }
+    viterbi_backtrace(before >= last ? S - 2 : S - 1, T, nch, bps, lab, utt.path, utt.tok_start, utt.tok_end,
+                      [&](int j) { return gap[j] ? -1 : blank; });
   }
   cx.sync();  // (the spans that thread wrote are read by every thread)
   for (int j = cx.tid; j <= L; j += cx.nt) {
@@ -1304,21 +1307,7 @@ CTC_HD void ctc_viterbi_gaps_utt(Ctx& cx, const GapsUtt& utt, int V, int blank, 
     for (int t = t0; t < t1; ++t) acc += align_emit_of_value(rmax[t], is_prob ? 0.0 : lse[t], is_prob, clip_lo);
     utt.gap_logp[j] = acc;
   }
-  if (!fold) return;
-  for (int k = cx.tid; k < L; k += cx.nt) {
-    int t0 = utt.tok_start[k], t1 = utt.tok_end[k];
-    t0 = t0 < 0 ? 0 : t0;
-    t1 = t1 > T ? T : t1;
-    const size_t lb = (size_t)lab[k];
-    double acc = 0.0;
-    for (int t = t0; t < t1; ++t) {
-      const double lp = align_emit(x, DT, (size_t)t * (size_t)V + lb, is_prob ? 0.0 : lse[t], is_prob, clip_lo);
-      if (fold == LOGP_MEAN) acc += lp;
-      else if (fold == LOGP_MIN) acc = (t == t0 || lp < acc) ? lp : acc;
-      else acc = (t == t0 || lp > acc) ? lp : acc;
-    }
-    utt.tok_logp[k] = fold == LOGP_MEAN ? acc / (double)(t1 - t0) : acc;
-  }
+  if (fold) fold_token_logp(cx, x, DT, lse, lab, utt.tok_start, utt.tok_end, utt.tok_logp, T, L, V, is_prob, fold, clip_lo);
 }
 
 }  // namespace ctc

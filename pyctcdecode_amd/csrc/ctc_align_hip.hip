@@ -1,10 +1,11 @@
-// ctc_align_hip.hip -- forced alignment and transcript likelihood on gfx950 (ctc_align.h): row_lse, the fp64 log-sum-exp of
-// every frame row; ctc_viterbi, one workgroup per utterance over the blank / label / blank / ... states; ctc_forward and
-// ctc_forward_wave, the sum over all alignments of a hypothesis, one workgroup / one wavefront each; ctc_posteriors, the
-// forward-backward of an utterance's transcript, one workgroup each; ctc_grad_rows, the gradient of the likelihood from the
-// posteriors a dense ctc_posteriors launch left, row by row; ctc_find and ctc_find_wave, the occurrences of a phrase inside
-// an utterance, one workgroup / one wavefront each; row_lse_max and ctc_viterbi_gaps, the alignment of a target with gaps, one
-// workgroup per utterance with its states in registers. A translation unit of its own.
+// ctc_align_hip.hip -- the transcript kernels on gfx950, bodies in ctc_align.h. A translation unit of its own.
+//   row_lse, row_lse_max            G lanes per row; both fold with row_fold
+//   ctc_viterbi                     a workgroup per utterance, score columns in LDS
+//   ctc_forward, ctc_posteriors,    a workgroup per record, a group of four states per thread in registers
+//   ctc_find, ctc_viterbi_gaps        (256 threads up to 511 labels, 1024 above)
+//   ctc_forward_wave, ctc_find_wave a wavefront per record of at most 127 labels
+//   ctc_grad_rows                   G threads per row of a dense ctc_posteriors launch's tables
+// The launchers share timed_launch (the event pair of the kernel's log and the launch's error), for_dtype and for_threads.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -54,30 +55,23 @@ __device__ __forceinline__ void unpack16(const uint4 q, double* out) {
   }
 }
 
-template <int G, int DT>
-__global__ __launch_bounds__(256) void row_lse(RowLseArgs a) {
-  constexpr int RPB = 256 / G;                            // rows per workgroup
+// One row's fold by its G lanes, lane l: the (max, sum of exp) pair of the row in every lane, or with MAX_ONLY the largest
+// entry that is not a NaN alone, without an exponential (row_lse_max, for the rows of a probability-like utterance).
+template <int G, int DT, bool MAX_ONLY>
+__device__ __forceinline__ LseAcc row_fold(const char* p, int V, int l) {
   constexpr int ESZ = DT == 0 ? 4 : DT == 1 ? 8 : 2;      // bytes per element
   constexpr int EPV = 16 / ESZ;                           // elements per 16-byte vector
   constexpr int VPB = ALIGN_LSE_BLOCK / EPV;              // vectors per block of values
-  const int64_t row = (int64_t)blockIdx.x * RPB + (int)(threadIdx.x / G);
-  const int l = (int)(threadIdx.x % G);
-  if (row >= a.n_rows) return;
-  int lo = 0, hi = a.n_utts;  // utt_row0[lo] <= row < utt_row0[hi]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (a.utt_row0[mid] <= row) lo = mid;
-    else hi = mid;
-  }
-  if (a.utt_is_prob[lo]) return;  // (the whole group of lanes: `row` is theirs alone)
-  const int V = a.n_labels;
-  const char* p = (const char*)a.utt_logits[lo] + (size_t)(row - a.utt_row0[lo]) * (size_t)V * ESZ;
   // Which values a lane folds, and in which order, depends on the element index alone -- never on where the row lies in memory:
   // the same row gives the same bits whether it comes alone, inside a batch or out of a staging buffer.
   const bool vec = ((uintptr_t)p & 15u) == 0;
   const int nvec = V / EPV, tail = nvec * EPV;
   LseAcc acc = lse_empty();
-  for (int i = tail + l; i < V; i += G) lse_push(acc, align_load(p, DT, (size_t)i));
+  for (int i = tail + l; i < V; i += G) {
+    const double v = align_load(p, DT, (size_t)i);
+    if (MAX_ONLY) acc.m = v > acc.m ? v : acc.m;
+    else lse_push(acc, v);
+  }
   const uint4* pv = (const uint4*)p;
   for (int base = 0; base < nvec; base += G * VPB) {
     double v[ALIGN_LSE_BLOCK];
@@ -94,15 +88,41 @@ __global__ __launch_bounds__(256) void row_lse(RowLseArgs a) {
         for (int k = 0; k < EPV; ++k) v[j * EPV + k] = align_load(p, DT, (size_t)i * EPV + (size_t)k);
       }
     }
-    lse_push_block(acc, v);
+    if (MAX_ONLY) {
+      CTC_UNROLL
+      for (int i = 0; i < ALIGN_LSE_BLOCK; ++i) acc.m = v[i] > acc.m ? v[i] : acc.m;
+    } else {
+      lse_push_block(acc, v);
+    }
   }
   CTC_UNROLL
   for (int off = G / 2; off >= 1; off >>= 1) {
     LseAcc o;
     o.m = __shfl_xor(acc.m, off, G);
     o.s = __shfl_xor(acc.s, off, G);
-    acc = lse_merge(acc, o);
+    if (MAX_ONLY) acc.m = o.m > acc.m ? o.m : acc.m;
+    else acc = lse_merge(acc, o);
   }
+  return acc;
+}
+
+template <int G, int DT>
+__global__ __launch_bounds__(256) void row_lse(RowLseArgs a) {
+  constexpr int RPB = 256 / G;                            // rows per workgroup
+  constexpr int ESZ = DT == 0 ? 4 : DT == 1 ? 8 : 2;
+  const int64_t row = (int64_t)blockIdx.x * RPB + (int)(threadIdx.x / G);
+  const int l = (int)(threadIdx.x % G);
+  if (row >= a.n_rows) return;
+  int lo = 0, hi = a.n_utts;  // utt_row0[lo] <= row < utt_row0[hi]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (a.utt_row0[mid] <= row) lo = mid;
+    else hi = mid;
+  }
+  if (a.utt_is_prob[lo]) return;  // (the whole group of lanes: `row` is theirs alone)
+  const int V = a.n_labels;
+  const char* p = (const char*)a.utt_logits[lo] + (size_t)(row - a.utt_row0[lo]) * (size_t)V * ESZ;
+  const LseAcc acc = row_fold<G, DT, false>(p, V, l);
   if (l == 0) a.lse[row] = lse_value(acc);
 }
 
@@ -278,58 +298,10 @@ __global__ __launch_bounds__(ALIGN_THREADS) void ctc_find_wave(FindArgs a) {
 
 // ---------------------------------------------------------------------------------------------
 // row_lse_max: row_lse that also stores the row's largest entry that is not a NaN -- the m its (max, sum of exp) pair ends
-// with: a second 8 bytes per row, no new arithmetic. The same lanes fold the same values in the same order and the same
-// butterfly merges them, so the log-sum-exp has row_lse's bits, wherever the row lies in memory. The rows of a probability-
-// like utterance, which row_lse skips, take the same loads and a plain maximum, without an exponential. Every logit is
-// still read once.
+// with: a second 8 bytes per row, no new arithmetic. Both kernels fold a row with row_fold, so the log-sum-exp has row_lse's
+// bits, wherever the row lies in memory. The rows of a probability-like utterance, which row_lse skips, take the same loads
+// and a plain maximum, without an exponential. Every logit is still read once.
 // ---------------------------------------------------------------------------------------------
-template <int G, int DT, bool MAX_ONLY>
-__device__ __forceinline__ LseAcc row_fold(const char* p, int V, int l) {
-  constexpr int ESZ = DT == 0 ? 4 : DT == 1 ? 8 : 2;      // bytes per element
-  constexpr int EPV = 16 / ESZ;                           // elements per 16-byte vector
-  constexpr int VPB = ALIGN_LSE_BLOCK / EPV;              // vectors per block of values
-  const bool vec = ((uintptr_t)p & 15u) == 0;
-  const int nvec = V / EPV, tail = nvec * EPV;
-  LseAcc acc = lse_empty();
-  for (int i = tail + l; i < V; i += G) {
-    const double v = align_load(p, DT, (size_t)i);
-    if (MAX_ONLY) acc.m = v > acc.m ? v : acc.m;
-    else lse_push(acc, v);
-  }
-  const uint4* pv = (const uint4*)p;
-  for (int base = 0; base < nvec; base += G * VPB) {
-    double v[ALIGN_LSE_BLOCK];
-    CTC_UNROLL
-    for (int j = 0; j < VPB; ++j) {
-      const int i = base + j * G + l;  // (neighbouring lanes, neighbouring 16-byte groups)
-      if (i >= nvec) {
-        CTC_UNROLL
-        for (int k = 0; k < EPV; ++k) v[j * EPV + k] = align_neg_inf();
-      } else if (vec) {
-        unpack16<DT>(pv[i], v + j * EPV);
-      } else {
-        CTC_UNROLL
-        for (int k = 0; k < EPV; ++k) v[j * EPV + k] = align_load(p, DT, (size_t)i * EPV + (size_t)k);
-      }
-    }
-    if (MAX_ONLY) {
-      CTC_UNROLL
-      for (int i = 0; i < ALIGN_LSE_BLOCK; ++i) acc.m = v[i] > acc.m ? v[i] : acc.m;
-    } else {
-      lse_push_block(acc, v);
-    }
-  }
-  CTC_UNROLL
-  for (int off = G / 2; off >= 1; off >>= 1) {
-    LseAcc o;
-    o.m = __shfl_xor(acc.m, off, G);
-    o.s = __shfl_xor(acc.s, off, G);
-    if (MAX_ONLY) acc.m = o.m > acc.m ? o.m : acc.m;
-    else acc = lse_merge(acc, o);
-  }
-  return acc;
-}
-
 template <int G, int DT>
 __global__ __launch_bounds__(256) void row_lse_max(RowLseArgs a, double* rmax) {
   constexpr int RPB = 256 / G;                            // rows per workgroup
@@ -369,7 +341,11 @@ __global__ __launch_bounds__(NT) void ctc_viterbi_gaps(ViterbiGapsArgs a) {
   ctc_viterbi_gaps_utt<DT>(cx, a.utts[blockIdx.x], a.n_labels, a.blank, a.fold, a.clip_lo, gaps_cols);
 }
 
-// kernel times: one pair of events per launch since the last reset
+// ---------------------------------------------------------------------------------------------
+// launches. Every launcher validates its arguments, then makes one timed_launch: the kernel's instantiation is picked by
+// for_dtype (ctc_align.h) and, where the kernel has two sizes, for_threads; the row kernels' lanes per row by for_row_lanes.
+// ---------------------------------------------------------------------------------------------
+// kernel times: one pair of events per launch since the last reset, one log per kernel
 struct EventLog {
   std::vector<hipEvent_t> ev;
   size_t used = 0;
@@ -391,232 +367,173 @@ struct EventLog {
     return sum;
   }
 };
-static EventLog g_lse_log, g_vit_log, g_fwd_log, g_post_log, g_grad_log, g_find_log, g_lsemax_log, g_vitgaps_log;
+static EventLog g_logs[ALIGN_KERNELS];
 
 void align_timing_reset() {
-  g_lse_log.used = g_vit_log.used = g_fwd_log.used = g_post_log.used = g_grad_log.used = g_find_log.used = 0;
-  g_lsemax_log.used = g_vitgaps_log.used = 0;
+  for (EventLog& log : g_logs) log.used = 0;
 }
-void align_gaps_timing(double* row_lse_max_ms, double* viterbi_gaps_ms) {
-  *row_lse_max_ms = g_lsemax_log.total();
-  *viterbi_gaps_ms = g_vitgaps_log.total();
-}
-double forward_timing() { return g_fwd_log.total(); }
-double posteriors_timing() { return g_post_log.total(); }
-double grad_rows_timing() { return g_grad_log.total(); }
-double find_timing() { return g_find_log.total(); }
-void align_timing(double* row_lse_ms, double* viterbi_ms) {
-  *row_lse_ms = g_lse_log.total();
-  *viterbi_ms = g_vit_log.total();
-}
+double align_kernel_ms(AlignKernel kind) { return g_logs[kind].total(); }
 
-template <int G>
-static void launch_row_lse_g(const RowLseArgs& a, hipStream_t stream) {
-  const dim3 grid((unsigned)((a.n_rows + (256 / G) - 1) / (256 / G))), block(256);
-  if (a.dtype == 0) hipLaunchKernelGGL((row_lse<G, 0>), grid, block, 0, stream, a);
-  else if (a.dtype == 1) hipLaunchKernelGGL((row_lse<G, 1>), grid, block, 0, stream, a);
-  else if (a.dtype == 2) hipLaunchKernelGGL((row_lse<G, 2>), grid, block, 0, stream, a);
-  else hipLaunchKernelGGL((row_lse<G, 3>), grid, block, 0, stream, a);
-}
-
-int launch_row_lse_on(const RowLseArgs& a, hipStream_t stream, std::string* err) {
-  if (a.n_rows <= 0 || a.n_utts <= 0) return 0;
-  if (a.dtype < 0 || a.dtype > 3 || a.n_labels < 1 || a.n_rows > (int64_t)0x7FFFFFFF * 4) {
-    if (err) *err = "row_lse: bad arguments";
-    return -1;
-  }
+// launch() between two events of the kernel's log, and the error the launch left
+template <class F>
+static int timed_launch(AlignKernel kind, hipStream_t stream, std::string* err, F launch) {
   hipEvent_t e0, e1;
-  if (g_lse_log.next(&e0, err) || g_lse_log.next(&e1, err)) return -1;
+  if (g_logs[kind].next(&e0, err) || g_logs[kind].next(&e1, err)) return -1;
   HIP_TRY_A(hipEventRecord(e0, stream));
-  if (a.n_labels >= 256) launch_row_lse_g<64>(a, stream);
-  else if (a.n_labels >= 32) launch_row_lse_g<16>(a, stream);
-  else launch_row_lse_g<4>(a, stream);
+  launch();
   HIP_TRY_A(hipGetLastError());
   HIP_TRY_A(hipEventRecord(e1, stream));
   return 0;
+}
+static int bad_launch(std::string* err, const char* what) {
+  if (err) *err = what;
+  return -1;
+}
+
+// f(std::integral_constant<int, NT>): 256 threads when every record of the launch has at most 256 groups of states, else 1024
+template <class F>
+static void for_threads(int max_chunks, F f) {
+  if (max_chunks <= ALIGN_THREADS) f(std::integral_constant<int, ALIGN_THREADS>());
+  else f(std::integral_constant<int, FORWARD_THREADS_MAX>());
+}
+// f(std::integral_constant<int, G>): the lanes per row of row_lse and row_lse_max, by the vocabulary alone -- the same
+// grouping in both, so the same bits
+template <class F>
+static void for_row_lanes(int V, F f) {
+  if (V >= 256) f(std::integral_constant<int, 64>());
+  else if (V >= 32) f(std::integral_constant<int, 16>());
+  else f(std::integral_constant<int, 4>());
+}
+template <int G>
+static dim3 row_grid(int64_t n_rows) { return dim3((unsigned)((n_rows + (256 / G) - 1) / (256 / G))); }
+
+int launch_row_lse_on(const RowLseArgs& a, hipStream_t stream, std::string* err) {
+  if (a.n_rows <= 0 || a.n_utts <= 0) return 0;
+  if (a.dtype < 0 || a.dtype > 3 || a.n_labels < 1 || a.n_rows > (int64_t)0x7FFFFFFF * 4) return bad_launch(err, "row_lse: bad arguments");
+  return timed_launch(K_ROW_LSE, stream, err, [&] {
+    for_row_lanes(a.n_labels, [&](auto g) {
+      for_dtype(a.dtype, [&](auto dt) {
+        constexpr int G = decltype(g)::value, DT = decltype(dt)::value;
+        hipLaunchKernelGGL((row_lse<G, DT>), row_grid<G>(a.n_rows), dim3(256), 0, stream, a);
+      });
+    });
+  });
+}
+
+int launch_row_lse_max_on(const RowLseArgs& a, double* rmax, hipStream_t stream, std::string* err) {
+  if (a.n_rows <= 0 || a.n_utts <= 0) return 0;
+  if (a.dtype < 0 || a.dtype > 3 || a.n_labels < 1 || a.n_rows > (int64_t)0x7FFFFFFF * 4 || !rmax)
+    return bad_launch(err, "row_lse_max: bad arguments");
+  return timed_launch(K_ROW_LSE_MAX, stream, err, [&] {
+    for_row_lanes(a.n_labels, [&](auto g) {
+      for_dtype(a.dtype, [&](auto dt) {
+        constexpr int G = decltype(g)::value, DT = decltype(dt)::value;
+        hipLaunchKernelGGL((row_lse_max<G, DT>), row_grid<G>(a.n_rows), dim3(256), 0, stream, a, rmax);
+      });
+    });
+  });
 }
 
 int launch_ctc_viterbi_on(const ViterbiArgs& a, hipStream_t stream, std::string* err) {
   if (a.n_utts <= 0) return 0;
-  if (a.max_chunks < 1 || a.max_chunks > align_chunks(ALIGN_MAX_LABELS)) {
-    if (err) *err = "ctc_viterbi: more states than two score columns in LDS hold";
-    return -1;
-  }
+  if (a.max_chunks < 1 || a.max_chunks > align_chunks(ALIGN_MAX_LABELS))
+    return bad_launch(err, "ctc_viterbi: more states than two score columns in LDS hold");
   const size_t lds = (size_t)2 * 4 * (size_t)a.max_chunks * sizeof(double);  // <= 64 KB
-  hipEvent_t e0, e1;
-  if (g_vit_log.next(&e0, err) || g_vit_log.next(&e1, err)) return -1;
-  HIP_TRY_A(hipEventRecord(e0, stream));
-  hipLaunchKernelGGL(ctc_viterbi, dim3((unsigned)a.n_utts), dim3(ALIGN_THREADS), lds, stream, a);
-  HIP_TRY_A(hipGetLastError());
-  HIP_TRY_A(hipEventRecord(e1, stream));
-  return 0;
-}
-
-template <int G>
-static void launch_row_lse_max_g(const RowLseArgs& a, double* rmax, hipStream_t stream) {
-  const dim3 grid((unsigned)((a.n_rows + (256 / G) - 1) / (256 / G))), block(256);
-  if (a.dtype == 0) hipLaunchKernelGGL((row_lse_max<G, 0>), grid, block, 0, stream, a, rmax);
-  else if (a.dtype == 1) hipLaunchKernelGGL((row_lse_max<G, 1>), grid, block, 0, stream, a, rmax);
-  else if (a.dtype == 2) hipLaunchKernelGGL((row_lse_max<G, 2>), grid, block, 0, stream, a, rmax);
-  else hipLaunchKernelGGL((row_lse_max<G, 3>), grid, block, 0, stream, a, rmax);
-}
-
-// (the lanes per row by the vocabulary alone, as launch_row_lse_on picks them: the same grouping, the same bits)
-int launch_row_lse_max_on(const RowLseArgs& a, double* rmax, hipStream_t stream, std::string* err) {
-  if (a.n_rows <= 0 || a.n_utts <= 0) return 0;
-  if (a.dtype < 0 || a.dtype > 3 || a.n_labels < 1 || a.n_rows > (int64_t)0x7FFFFFFF * 4 || !rmax) {
-    if (err) *err = "row_lse_max: bad arguments";
-    return -1;
-  }
-  hipEvent_t e0, e1;
-  if (g_lsemax_log.next(&e0, err) || g_lsemax_log.next(&e1, err)) return -1;
-  HIP_TRY_A(hipEventRecord(e0, stream));
-  if (a.n_labels >= 256) launch_row_lse_max_g<64>(a, rmax, stream);
-  else if (a.n_labels >= 32) launch_row_lse_max_g<16>(a, rmax, stream);
-  else launch_row_lse_max_g<4>(a, rmax, stream);
-  HIP_TRY_A(hipGetLastError());
-  HIP_TRY_A(hipEventRecord(e1, stream));
-  return 0;
-}
-
-template <int DT>
-static void launch_viterbi_gaps_dt(const ViterbiGapsArgs& a, hipStream_t stream) {
-  const size_t lds = (size_t)2 * (size_t)a.max_chunks * sizeof(double);  // <= 16 KB
-  if (a.max_chunks <= ALIGN_THREADS) hipLaunchKernelGGL((ctc_viterbi_gaps<ALIGN_THREADS, DT>), dim3((unsigned)a.n_utts), dim3(ALIGN_THREADS), lds, stream, a);
-  else hipLaunchKernelGGL((ctc_viterbi_gaps<FORWARD_THREADS_MAX, DT>), dim3((unsigned)a.n_utts), dim3(FORWARD_THREADS_MAX), lds, stream, a);
+  return timed_launch(K_VITERBI, stream, err, [&] {
+    hipLaunchKernelGGL(ctc_viterbi, dim3((unsigned)a.n_utts), dim3(ALIGN_THREADS), lds, stream, a);
+  });
 }
 
 int launch_ctc_viterbi_gaps_on(const ViterbiGapsArgs& a, hipStream_t stream, std::string* err) {
   if (a.n_utts <= 0) return 0;
-  if (a.dtype < 0 || a.dtype > 3 || a.max_chunks < 1 || a.max_chunks > align_chunks(ALIGN_MAX_LABELS)) {
-    if (err) *err = "ctc_viterbi_gaps: more states than the kernel holds";
-    return -1;
-  }
-  hipEvent_t e0, e1;
-  if (g_vitgaps_log.next(&e0, err) || g_vitgaps_log.next(&e1, err)) return -1;
-  HIP_TRY_A(hipEventRecord(e0, stream));
-  if (a.dtype == 0) launch_viterbi_gaps_dt<0>(a, stream);
-  else if (a.dtype == 1) launch_viterbi_gaps_dt<1>(a, stream);
-  else if (a.dtype == 2) launch_viterbi_gaps_dt<2>(a, stream);
-  else launch_viterbi_gaps_dt<3>(a, stream);
-  HIP_TRY_A(hipGetLastError());
-  HIP_TRY_A(hipEventRecord(e1, stream));
-  return 0;
-}
-
-template <int DT>
-static void launch_forward_dt(const ForwardArgs& a, int wave, hipStream_t stream) {
-  if (wave) {
-    hipLaunchKernelGGL(ctc_forward_wave<DT>, dim3((unsigned)((a.n_hyps + FORWARD_WAVES - 1) / FORWARD_WAVES)), dim3(ALIGN_THREADS), 0, stream, a);
-    return;
-  }
+  if (a.dtype < 0 || a.dtype > 3 || a.max_chunks < 1 || a.max_chunks > align_chunks(ALIGN_MAX_LABELS))
+    return bad_launch(err, "ctc_viterbi_gaps: more states than the kernel holds");
   const size_t lds = (size_t)2 * (size_t)a.max_chunks * sizeof(double);  // <= 16 KB
-  if (a.max_chunks <= ALIGN_THREADS) hipLaunchKernelGGL((ctc_forward<ALIGN_THREADS, DT>), dim3((unsigned)a.n_hyps), dim3(ALIGN_THREADS), lds, stream, a);
-  else hipLaunchKernelGGL((ctc_forward<FORWARD_THREADS_MAX, DT>), dim3((unsigned)a.n_hyps), dim3(FORWARD_THREADS_MAX), lds, stream, a);
+  return timed_launch(K_VITERBI_GAPS, stream, err, [&] {
+    for_dtype(a.dtype, [&](auto dt) {
+      for_threads(a.max_chunks, [&](auto nt) {
+        constexpr int NT = decltype(nt)::value, DT = decltype(dt)::value;
+        hipLaunchKernelGGL((ctc_viterbi_gaps<NT, DT>), dim3((unsigned)a.n_utts), dim3(NT), lds, stream, a);
+      });
+    });
+  });
 }
 
 int launch_ctc_forward_on(const ForwardArgs& a, int wave, hipStream_t stream, std::string* err) {
   if (a.n_hyps <= 0) return 0;
-  if (a.dtype < 0 || a.dtype > 3 || a.max_chunks < 1 || a.max_chunks > (wave ? align_chunks(FORWARD_WAVE_MAX_LABELS) : align_chunks(ALIGN_MAX_LABELS))) {
-    if (err) *err = "ctc_forward: more states than the kernel holds";
-    return -1;
-  }
-  hipEvent_t e0, e1;
-  if (g_fwd_log.next(&e0, err) || g_fwd_log.next(&e1, err)) return -1;
-  HIP_TRY_A(hipEventRecord(e0, stream));
-  if (a.dtype == 0) launch_forward_dt<0>(a, wave, stream);
-  else if (a.dtype == 1) launch_forward_dt<1>(a, wave, stream);
-  else if (a.dtype == 2) launch_forward_dt<2>(a, wave, stream);
-  else launch_forward_dt<3>(a, wave, stream);
-  HIP_TRY_A(hipGetLastError());
-  HIP_TRY_A(hipEventRecord(e1, stream));
-  return 0;
-}
-
-template <int DT>
-static void launch_posteriors_dt(const PosteriorsArgs& a, hipStream_t stream) {
-  const size_t lds = ((size_t)4 * (size_t)a.max_chunks + 2) * sizeof(double);  // <= 32 KB + 16
-  if (a.max_chunks <= ALIGN_THREADS) hipLaunchKernelGGL((ctc_posteriors<ALIGN_THREADS, DT>), dim3((unsigned)a.n_utts), dim3(ALIGN_THREADS), lds, stream, a);
-  else hipLaunchKernelGGL((ctc_posteriors<FORWARD_THREADS_MAX, DT>), dim3((unsigned)a.n_utts), dim3(FORWARD_THREADS_MAX), lds, stream, a);
+  if (a.dtype < 0 || a.dtype > 3 || a.max_chunks < 1 || a.max_chunks > (wave ? align_chunks(FORWARD_WAVE_MAX_LABELS) : align_chunks(ALIGN_MAX_LABELS)))
+    return bad_launch(err, "ctc_forward: more states than the kernel holds");
+  const size_t lds = (size_t)2 * (size_t)a.max_chunks * sizeof(double);  // (ctc_forward) <= 16 KB
+  return timed_launch(K_FORWARD, stream, err, [&] {
+    for_dtype(a.dtype, [&](auto dt) {
+      constexpr int DT = decltype(dt)::value;
+      if (wave) {
+        hipLaunchKernelGGL(ctc_forward_wave<DT>, dim3((unsigned)((a.n_hyps + FORWARD_WAVES - 1) / FORWARD_WAVES)), dim3(ALIGN_THREADS), 0, stream, a);
+        return;
+      }
+      for_threads(a.max_chunks, [&](auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        hipLaunchKernelGGL((ctc_forward<NT, DT>), dim3((unsigned)a.n_hyps), dim3(NT), lds, stream, a);
+      });
+    });
+  });
 }
 
 int launch_ctc_posteriors_on(const PosteriorsArgs& a, hipStream_t stream, std::string* err) {
   if (a.n_utts <= 0) return 0;
-  if (a.dtype < 0 || a.dtype > 3 || a.max_chunks < 1 || a.max_chunks > align_chunks(ALIGN_MAX_LABELS)) {
-    if (err) *err = "ctc_posteriors: more states than the kernel holds";
-    return -1;
-  }
-  hipEvent_t e0, e1;
-  if (g_post_log.next(&e0, err) || g_post_log.next(&e1, err)) return -1;
-  HIP_TRY_A(hipEventRecord(e0, stream));
-  if (a.dtype == 0) launch_posteriors_dt<0>(a, stream);
-  else if (a.dtype == 1) launch_posteriors_dt<1>(a, stream);
-  else if (a.dtype == 2) launch_posteriors_dt<2>(a, stream);
-  else launch_posteriors_dt<3>(a, stream);
-  HIP_TRY_A(hipGetLastError());
-  HIP_TRY_A(hipEventRecord(e1, stream));
-  return 0;
+  if (a.dtype < 0 || a.dtype > 3 || a.max_chunks < 1 || a.max_chunks > align_chunks(ALIGN_MAX_LABELS))
+    return bad_launch(err, "ctc_posteriors: more states than the kernel holds");
+  const size_t lds = ((size_t)4 * (size_t)a.max_chunks + 2) * sizeof(double);  // <= 32 KB + 16
+  return timed_launch(K_POSTERIORS, stream, err, [&] {
+    for_dtype(a.dtype, [&](auto dt) {
+      for_threads(a.max_chunks, [&](auto nt) {
+        constexpr int NT = decltype(nt)::value, DT = decltype(dt)::value;
+        hipLaunchKernelGGL((ctc_posteriors<NT, DT>), dim3((unsigned)a.n_utts), dim3(NT), lds, stream, a);
+      });
+    });
+  });
 }
 
 // the row's threads and what they keep by the vocabulary alone: 16 lanes up to 64 labels, a wave up to 256 (four entries
 // each), the workgroup above (four entries each up to 1024 labels, else sixteen; beyond 4096 labels the rest is formed twice)
-template <int DT, class GT>
-static void launch_grad_rows_dt(const GradRowsArgs& a, hipStream_t stream) {
+int launch_ctc_grad_rows_on(const GradRowsArgs& a, hipStream_t stream, std::string* err) {
+  if (a.n_utts <= 0 || a.n_rows <= 0) return 0;
+  if (a.dtype < 0 || a.dtype > 3 || a.grad_dtype != (a.dtype == 1 ? 1 : 0) || a.n_labels < 1 || a.n_rows > (int64_t)0x7FFFFFFF)
+    return bad_launch(err, "ctc_grad_rows: bad arguments");
   const int V = a.n_labels;
   const int rpb = V <= 64 ? 16 : V <= 256 ? 4 : 1;
   const dim3 grid((unsigned)((a.n_rows + rpb - 1) / rpb)), block(ALIGN_THREADS);
-  if (V <= 64) hipLaunchKernelGGL((ctc_grad_rows<16, 4, DT, GT>), grid, block, 0, stream, a);
-  else if (V <= 256) hipLaunchKernelGGL((ctc_grad_rows<64, 4, DT, GT>), grid, block, 0, stream, a);
-  else if (V <= 1024) hipLaunchKernelGGL((ctc_grad_rows<ALIGN_THREADS, 4, DT, GT>), grid, block, 0, stream, a);
-  else hipLaunchKernelGGL((ctc_grad_rows<ALIGN_THREADS, 16, DT, GT>), grid, block, 0, stream, a);
-}
-
-int launch_ctc_grad_rows_on(const GradRowsArgs& a, hipStream_t stream, std::string* err) {
-  if (a.n_utts <= 0 || a.n_rows <= 0) return 0;
-  if (a.dtype < 0 || a.dtype > 3 || a.grad_dtype != (a.dtype == 1 ? 1 : 0) || a.n_labels < 1 || a.n_rows > (int64_t)0x7FFFFFFF) {
-    if (err) *err = "ctc_grad_rows: bad arguments";
-    return -1;
-  }
-  hipEvent_t e0, e1;
-  if (g_grad_log.next(&e0, err) || g_grad_log.next(&e1, err)) return -1;
-  HIP_TRY_A(hipEventRecord(e0, stream));
-  if (a.dtype == 0) launch_grad_rows_dt<0, float>(a, stream);
-  else if (a.dtype == 1) launch_grad_rows_dt<1, double>(a, stream);
-  else if (a.dtype == 2) launch_grad_rows_dt<2, float>(a, stream);
-  else launch_grad_rows_dt<3, float>(a, stream);
-  HIP_TRY_A(hipGetLastError());
-  HIP_TRY_A(hipEventRecord(e1, stream));
-  return 0;
-}
-
-template <int DT>
-static void launch_find_dt(const FindArgs& a, int wave, hipStream_t stream) {
-  if (wave) {
-    hipLaunchKernelGGL(ctc_find_wave<DT>, dim3((unsigned)((a.n_phrases + FORWARD_WAVES - 1) / FORWARD_WAVES)), dim3(ALIGN_THREADS), 0, stream, a);
-    return;
-  }
-  const size_t lds = (size_t)2 * (size_t)a.max_chunks * (sizeof(double) + sizeof(int32_t));  // <= 24 KB
-  if (a.max_chunks <= ALIGN_THREADS) hipLaunchKernelGGL((ctc_find<ALIGN_THREADS, DT>), dim3((unsigned)a.n_phrases), dim3(ALIGN_THREADS), lds, stream, a);
-  else hipLaunchKernelGGL((ctc_find<FORWARD_THREADS_MAX, DT>), dim3((unsigned)a.n_phrases), dim3(FORWARD_THREADS_MAX), lds, stream, a);
+  return timed_launch(K_GRAD_ROWS, stream, err, [&] {
+    for_dtype(a.dtype, [&](auto dt) {
+      constexpr int DT = decltype(dt)::value;
+      typedef typename std::conditional<DT == 1, double, float>::type GT;
+      if (V <= 64) hipLaunchKernelGGL((ctc_grad_rows<16, 4, DT, GT>), grid, block, 0, stream, a);
+      else if (V <= 256) hipLaunchKernelGGL((ctc_grad_rows<64, 4, DT, GT>), grid, block, 0, stream, a);
+      else if (V <= 1024) hipLaunchKernelGGL((ctc_grad_rows<ALIGN_THREADS, 4, DT, GT>), grid, block, 0, stream, a);
+      else hipLaunchKernelGGL((ctc_grad_rows<ALIGN_THREADS, 16, DT, GT>), grid, block, 0, stream, a);
+    });
+  });
 }
 
 int launch_ctc_find_on(const FindArgs& a, int wave, hipStream_t stream, std::string* err) {
   if (a.n_phrases <= 0) return 0;
   if (a.dtype < 0 || a.dtype > 3 || a.max_hits < 1 || a.max_hits > FIND_MAX_HITS || a.max_chunks < 1 ||
-      a.max_chunks > (wave ? find_chunks(FIND_WAVE_MAX_LABELS) : find_chunks(ALIGN_MAX_LABELS))) {
-    if (err) *err = "ctc_find: more states or hits than the kernel holds";
-    return -1;
-  }
-  hipEvent_t e0, e1;
-  if (g_find_log.next(&e0, err) || g_find_log.next(&e1, err)) return -1;
-  HIP_TRY_A(hipEventRecord(e0, stream));
-  if (a.dtype == 0) launch_find_dt<0>(a, wave, stream);
-  else if (a.dtype == 1) launch_find_dt<1>(a, wave, stream);
-  else if (a.dtype == 2) launch_find_dt<2>(a, wave, stream);
-  else launch_find_dt<3>(a, wave, stream);
-  HIP_TRY_A(hipGetLastError());
-  HIP_TRY_A(hipEventRecord(e1, stream));
-  return 0;
+      a.max_chunks > (wave ? find_chunks(FIND_WAVE_MAX_LABELS) : find_chunks(ALIGN_MAX_LABELS)))
+    return bad_launch(err, "ctc_find: more states or hits than the kernel holds");
+  const size_t lds = (size_t)2 * (size_t)a.max_chunks * (sizeof(double) + sizeof(int32_t));  // (ctc_find) <= 24 KB
+  return timed_launch(K_FIND, stream, err, [&] {
+    for_dtype(a.dtype, [&](auto dt) {
+      constexpr int DT = decltype(dt)::value;
+      if (wave) {
+        hipLaunchKernelGGL(ctc_find_wave<DT>, dim3((unsigned)((a.n_phrases + FORWARD_WAVES - 1) / FORWARD_WAVES)), dim3(ALIGN_THREADS), 0, stream, a);
+        return;
+      }
+      for_threads(a.max_chunks, [&](auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        hipLaunchKernelGGL((ctc_find<NT, DT>), dim3((unsigned)a.n_phrases), dim3(NT), lds, stream, a);
+      });
+    });
+  });
 }
 
 }  // namespace be

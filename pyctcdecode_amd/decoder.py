@@ -1722,6 +1722,55 @@ class BeamSearchDecoderCTC:
             targets.append(ids)
         return logits_list, targets
 
+    def _stage_transcript_call(self, logits_list: Any):
+        """-> (batch, frames, ptrs): what every transcript call stages, under the call lock -- the utterances as a _Batch,
+        on this decoder's device if on one, and their frame counts and matrix pointers as arrays for the native call."""
+        batch = _Batch(logits_list, len(self._labels_list))
+        if batch.is_device and batch.device_index is not None and batch.device_index != self._device:
+            raise ValueError("the logits live on cuda:%d but this decoder was built for cuda:%d (one process per GPU: "
+                             "LOCAL_RANK / CTCDEC_DEVICE pick the device)" % (batch.device_index, self._device))
+        return batch, np.ascontiguousarray(batch.frames, dtype=np.int32), np.ascontiguousarray(batch.ptrs, dtype=np.uint64)
+
+    @staticmethod
+    def _frames_needed(ids: Sequence[int]) -> int:
+        """The fewest frames a path through the labels takes: one each, and a blank between adjacent equal ones."""
+        return len(ids) + sum(1 for a, b in zip(ids, ids[1:]) if a == b)
+
+    def _feasible(self, what: str, frames, labels: Sequence[Sequence[int]], table_bytes, budget: int, strict: bool,
+                  table_name: str = "table", path_name: str = "alignment") -> List[int]:
+        """-> the utterances that have a path for their labels. One whose table, of ``table_bytes(frames, labels)`` bytes, is
+        above the budget of a launch is a ValueError, and so are, when ``strict``, the utterances without a path. The
+        messages call the table and the path by the call's own words."""
+        keep, bad = [], []
+        for u, ids in enumerate(labels):
+            (keep if int(frames[u]) >= self._frames_needed(ids) else bad).append(u)
+            table = table_bytes(int(frames[u]), len(ids))
+            if table > budget:
+                raise ValueError("%s: utterance %d needs a %s of %d bytes, above the memory budget of %d bytes of one launch"
+                                 % (what, u, table_name, table, budget))
+        if bad and strict:
+            raise ValueError("%s: no %s for utterances %s: fewer frames than target labels plus adjacent equal labels"
+                             % (what, path_name, bad))
+        return keep
+
+    @staticmethod
+    def _bp_table_bytes(frames: int, n_labels: int) -> int:
+        """A byte of back-pointers per frame and group of four states (ctc_viterbi, ctc_viterbi_gaps)"""
+        return frames * ((2 * n_labels + 1 + 3) // 4)
+
+    @staticmethod
+    def _state_table_bytes(frames: int, n_labels: int) -> int:
+        """32 bytes of states per frame and group of four states (ctc_posteriors)"""
+        return 32 * frames * ((2 * n_labels + 1 + 3) // 4)
+
+    @staticmethod
+    def _pack_ids(seqs: Sequence[Sequence[int]]):
+        """-> (flat, off): the id lists end to end as int32 (one 0 where there is none: never read) and where each starts."""
+        flat = np.fromiter(itertools.chain.from_iterable(seqs), dtype=np.int32)
+        off = np.zeros(len(seqs) + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(ids) for ids in seqs])
+        return (flat if len(flat) else np.zeros(1, dtype=np.int32)), off
+
     def align(self, logits: Any, text: Optional[str] = None, tokens: Optional[Sequence[int]] = None,
               confidence: Optional[str] = None) -> "AlignedText":
         """Forced alignment of one utterance: align_batch of a batch of one (a ValueError when no path exists)."""
@@ -1739,36 +1788,19 @@ class BeamSearchDecoderCTC:
         ValueError that lists them, ``strict=False`` returns None in their place."""
         fold = _confidence_fold(confidence)
         logits_list, targets = self._one_target_each("align", logits_list, texts, tokens)
-        n, n_labels = len(targets), len(self._labels_list)
+        n = len(targets)
         if n == 0:
             return []
         with self._call_lock:
-            batch = _Batch(logits_list, n_labels)
-            if batch.is_device and batch.device_index is not None and batch.device_index != self._device:
-                raise ValueError("the logits live on cuda:%d but this decoder was built for cuda:%d (one process per GPU: "
-                                 "LOCAL_RANK / CTCDEC_DEVICE pick the device)" % (batch.device_index, self._device))
-            frames = np.asarray(batch.frames, dtype=np.int32)
-            ptrs = np.asarray(batch.ptrs, dtype=np.uint64)
-            budget = int(_bp_budget) or ALIGN_BP_BUDGET
-            keep, bad = [], []
-            for u, ids in enumerate(targets):
-                need = len(ids) + sum(1 for a, b in zip(ids, ids[1:]) if a == b)
-                (keep if int(frames[u]) >= need else bad).append(u)
-                table = int(frames[u]) * ((2 * len(ids) + 1 + 3) // 4)
-                if table > budget:
-                    raise ValueError("align: utterance %d needs a back-pointer table of %d bytes, above the memory budget of %d "
-                                     "bytes of one launch" % (u, table, budget))
-            if bad and strict:
-                raise ValueError("align: no path for utterances %s: fewer frames than target labels plus adjacent equal labels"
-                                 % bad)
+            batch, frames, ptrs = self._stage_transcript_call(logits_list)
+            keep = self._feasible("align", frames, targets, self._bp_table_bytes, int(_bp_budget) or ALIGN_BP_BUDGET, strict,
+                                  "back-pointer table", "path")
             out: List[Optional[AlignedText]] = [None] * n
             if not keep:
                 return out
             k_ptrs = np.ascontiguousarray(ptrs[keep])
             k_frames = np.ascontiguousarray(frames[keep])
-            flat = np.array([c for u in keep for c in targets[u]] or [0], dtype=np.int32)
-            off = np.zeros(len(keep) + 1, dtype=np.int64)
-            off[1:] = np.cumsum([len(targets[u]) for u in keep])
+            flat, off = self._pack_ids([targets[u] for u in keep])
             res = C.c_void_p()
             lib = self._lib
             lib.check(lib.dll.ctcdec_align_batch(
@@ -1885,37 +1917,20 @@ class BeamSearchDecoderCTC:
         result. ``strict`` and the feasibility bound (frames >= labels plus adjacent equal labels) are align_batch's."""
         fold = _confidence_fold(confidence)
         logits_list, targets = self._gapped_targets("align_gaps", logits_list, texts, tokens, gap)
-        n, n_labels = len(targets), len(self._labels_list)
+        n = len(targets)
         if n == 0:
             return []
         with self._call_lock:
-            batch = _Batch(logits_list, n_labels)
-            if batch.is_device and batch.device_index is not None and batch.device_index != self._device:
-                raise ValueError("the logits live on cuda:%d but this decoder was built for cuda:%d (one process per GPU: "
-                                 "LOCAL_RANK / CTCDEC_DEVICE pick the device)" % (batch.device_index, self._device))
-            frames = np.asarray(batch.frames, dtype=np.int32)
-            ptrs = np.asarray(batch.ptrs, dtype=np.uint64)
-            budget = int(_bp_budget) or ALIGN_BP_BUDGET
-            keep, bad = [], []
-            for u, items in enumerate(targets):
-                ids = [c for c in items if c != -1]
-                need = len(ids) + sum(1 for a, b in zip(ids, ids[1:]) if a == b)
-                (keep if int(frames[u]) >= need else bad).append(u)
-                table = int(frames[u]) * ((2 * len(ids) + 1 + 3) // 4)
-                if table > budget:
-                    raise ValueError("align_gaps: utterance %d needs a back-pointer table of %d bytes, above the memory budget of "
-                                     "%d bytes of one launch" % (u, table, budget))
-            if bad and strict:
-                raise ValueError("align_gaps: no path for utterances %s: fewer frames than target labels plus adjacent equal "
-                                 "labels" % bad)
+            batch, frames, ptrs = self._stage_transcript_call(logits_list)
+            labels_only = [[c for c in items if c != -1] for items in targets]
+            keep = self._feasible("align_gaps", frames, labels_only, self._bp_table_bytes, int(_bp_budget) or ALIGN_BP_BUDGET, strict,
+                                  "back-pointer table", "path")
             out: List[Optional[GappedAlignment]] = [None] * n
             if not keep:
                 return out
             k_ptrs = np.ascontiguousarray(ptrs[keep])
             k_frames = np.ascontiguousarray(frames[keep])
-            flat = np.array([c for u in keep for c in targets[u]], dtype=np.int32)
-            off = np.zeros(len(keep) + 1, dtype=np.int64)
-            off[1:] = np.cumsum([len(targets[u]) for u in keep])
+            flat, off = self._pack_ids([targets[u] for u in keep])
             res = C.c_void_p()
             lib = self._lib
             lib.check(lib.dll.ctcdec_align_gaps_batch(
@@ -2050,7 +2065,7 @@ class BeamSearchDecoderCTC:
         if with_lm and lm is None:
             raise ValueError("score: with_lm=True needs a decoder with a language model")
         logits_list, hyps = self._many_targets_each("score", "hypothesis", "hypotheses", logits_list, texts, tokens)
-        n, n_labels = len(hyps), len(self._labels_list)
+        n = len(hyps)
         if n == 0:
             self.last_score_timing_ms, self.last_score_launched = (0.0, 0.0, 0.0, 0.0), (0, 0)
             return []
@@ -2058,18 +2073,9 @@ class BeamSearchDecoderCTC:
         if kernel_env and kernel_env not in FORWARD_KERNELS:
             raise ValueError("CTCDEC_FORWARD_KERNEL must be wave or group, not %r" % kernel_env)
         with self._call_lock:
-            batch = _Batch(logits_list, n_labels)
-            if batch.is_device and batch.device_index is not None and batch.device_index != self._device:
-                raise ValueError("the logits live on cuda:%d but this decoder was built for cuda:%d (one process per GPU: "
-                                 "LOCAL_RANK / CTCDEC_DEVICE pick the device)" % (batch.device_index, self._device))
-            frames = np.ascontiguousarray(np.asarray(batch.frames, dtype=np.int32))
-            ptrs = np.ascontiguousarray(np.asarray(batch.ptrs, dtype=np.uint64))
+            batch, frames, ptrs = self._stage_transcript_call(logits_list)
             flat_hyps = [ids for cur in hyps for ids in cur]
-            flat = np.fromiter(itertools.chain.from_iterable(flat_hyps), dtype=np.int32)
-            if not len(flat):
-                flat = np.zeros(1, dtype=np.int32)
-            target_off = np.zeros(len(flat_hyps) + 1, dtype=np.int64)
-            target_off[1:] = np.cumsum([len(ids) for ids in flat_hyps])
+            flat, target_off = self._pack_ids(flat_hyps)
             hyp_off = np.zeros(n + 1, dtype=np.int64)
             hyp_off[1:] = np.cumsum([len(cur) for cur in hyps])
             logp = np.zeros(max(len(flat_hyps), 1), dtype=np.float64)
@@ -2136,7 +2142,7 @@ class BeamSearchDecoderCTC:
         floor = -math.inf if min_logp is None else float(min_logp)
         if math.isnan(floor):
             raise ValueError("find: min_logp is not a number")
-        n, n_labels = len(phrases), len(self._labels_list)
+        n = len(phrases)
         self.last_find_timing_ms, self.last_find_launches, self.last_find_launched = (0.0, 0.0, 0.0, 0.0), 0, (0, 0)
         if n == 0:
             return []
@@ -2144,25 +2150,15 @@ class BeamSearchDecoderCTC:
         if kernel_env and kernel_env not in FIND_KERNELS:
             raise ValueError("CTCDEC_FIND_KERNEL must be wave or group, not %r" % kernel_env)
         with self._call_lock:
-            batch = _Batch(logits_list, n_labels)
-            if batch.is_device and batch.device_index is not None and batch.device_index != self._device:
-                raise ValueError("the logits live on cuda:%d but this decoder was built for cuda:%d (one process per GPU: "
-                                 "LOCAL_RANK / CTCDEC_DEVICE pick the device)" % (batch.device_index, self._device))
-            frames = np.ascontiguousarray(np.asarray(batch.frames, dtype=np.int32))
-            ptrs = np.ascontiguousarray(np.asarray(batch.ptrs, dtype=np.uint64))
+            batch, frames, ptrs = self._stage_transcript_call(logits_list)
             budget = int(_trace_budget) or ALIGN_BP_BUDGET
             for u, cur in enumerate(phrases):
                 for j, ids in enumerate(cur):
-                    need = len(ids) + sum(1 for a, b in zip(ids, ids[1:]) if a == b)
-                    if int(frames[u]) >= need and 12 * int(frames[u]) > budget:
+                    if int(frames[u]) >= self._frames_needed(ids) and 12 * int(frames[u]) > budget:
                         raise ValueError("find: utterance %d, phrase %d needs a trace of %d bytes, above the memory budget of %d "
                                          "bytes of one launch" % (u, j, 12 * int(frames[u]), budget))
             flat_phrases = [ids for cur in phrases for ids in cur]
-            flat = np.fromiter(itertools.chain.from_iterable(flat_phrases), dtype=np.int32)
-            if not len(flat):
-                flat = np.zeros(1, dtype=np.int32)
-            label_off = np.zeros(len(flat_phrases) + 1, dtype=np.int64)
-            label_off[1:] = np.cumsum([len(ids) for ids in flat_phrases])
+            flat, label_off = self._pack_ids(flat_phrases)
             hyp_off = np.zeros(n + 1, dtype=np.int64)
             hyp_off[1:] = np.cumsum([len(cur) for cur in phrases])
             res = C.c_void_p()
@@ -2233,37 +2229,19 @@ class BeamSearchDecoderCTC:
         launch -- 26 GB for 4096 utterances of 1000 frames and 100 labels: a large batch wants ``dense=False``, which returns
         the scores and the per-token ``occupancy`` / ``centre`` alone, with the same bits."""
         logits_list, targets = self._one_target_each("posteriors", logits_list, texts, tokens)
-        n, n_labels = len(targets), len(self._labels_list)
+        n = len(targets)
         self.last_posteriors_timing_ms, self.last_posteriors_launches, self.last_posteriors_launched = (0.0,) * 4, 0, (0, 0)
         if n == 0:
             return []
         with self._call_lock:
-            batch = _Batch(logits_list, n_labels)
-            if batch.is_device and batch.device_index is not None and batch.device_index != self._device:
-                raise ValueError("the logits live on cuda:%d but this decoder was built for cuda:%d (one process per GPU: "
-                                 "LOCAL_RANK / CTCDEC_DEVICE pick the device)" % (batch.device_index, self._device))
-            frames = np.asarray(batch.frames, dtype=np.int32)
-            ptrs = np.asarray(batch.ptrs, dtype=np.uint64)
-            budget = int(_table_budget) or POSTERIORS_TABLE_BUDGET
-            keep, bad = [], []
-            for u, ids in enumerate(targets):
-                need = len(ids) + sum(1 for a, b in zip(ids, ids[1:]) if a == b)
-                (keep if int(frames[u]) >= need else bad).append(u)
-                table = 32 * int(frames[u]) * ((2 * len(ids) + 1 + 3) // 4)
-                if table > budget:
-                    raise ValueError("posteriors: utterance %d needs a table of %d bytes, above the memory budget of %d bytes of "
-                                     "one launch" % (u, table, budget))
-            if bad and strict:
-                raise ValueError("posteriors: no alignment for utterances %s: fewer frames than target labels plus adjacent "
-                                 "equal labels" % bad)
+            batch, frames, ptrs = self._stage_transcript_call(logits_list)
+            keep = self._feasible("posteriors", frames, targets, self._state_table_bytes, int(_table_budget) or POSTERIORS_TABLE_BUDGET, strict)
             out: List[Optional[TranscriptPosteriors]] = [None] * n
             if not keep:
                 return out
             k_ptrs = np.ascontiguousarray(ptrs[keep])
             k_frames = np.ascontiguousarray(frames[keep])
-            flat = np.array([c for u in keep for c in targets[u]] or [0], dtype=np.int32)
-            off = np.zeros(len(keep) + 1, dtype=np.int64)
-            off[1:] = np.cumsum([len(targets[u]) for u in keep])
+            flat, off = self._pack_ids([targets[u] for u in keep])
             res = C.c_void_p()
             lib = self._lib
             lib.check(lib.dll.ctcdec_posteriors_batch(
@@ -2333,32 +2311,14 @@ class BeamSearchDecoderCTC:
         if n == 0:
             return [], None, []
         with self._call_lock:
-            batch = _Batch(logits_list, n_labels)
-            if batch.is_device and batch.device_index is not None and batch.device_index != self._device:
-                raise ValueError("the logits live on cuda:%d but this decoder was built for cuda:%d (one process per GPU: "
-                                 "LOCAL_RANK / CTCDEC_DEVICE pick the device)" % (batch.device_index, self._device))
-            frames = np.asarray(batch.frames, dtype=np.int32)
-            ptrs = np.asarray(batch.ptrs, dtype=np.uint64)
-            budget = int(_table_budget) or POSTERIORS_TABLE_BUDGET
-            keep, bad = [], []
-            for u, ids in enumerate(targets):
-                need = len(ids) + sum(1 for a, b in zip(ids, ids[1:]) if a == b)
-                (keep if int(frames[u]) >= need else bad).append(u)
-                table = 32 * int(frames[u]) * ((2 * len(ids) + 1 + 3) // 4)
-                if table > budget:
-                    raise ValueError("gradient: utterance %d needs a table of %d bytes, above the memory budget of %d bytes of "
-                                     "one launch" % (u, table, budget))
-            if bad and strict:
-                raise ValueError("gradient: no alignment for utterances %s: fewer frames than target labels plus adjacent "
-                                 "equal labels" % bad)
+            batch, frames, ptrs = self._stage_transcript_call(logits_list)
+            keep = self._feasible("gradient", frames, targets, self._state_table_bytes, int(_table_budget) or POSTERIORS_TABLE_BUDGET, strict)
             out: List[Optional[TranscriptGradient]] = [None] * n
             if not keep:
                 return out, None, keep
             k_ptrs = np.ascontiguousarray(ptrs[keep])
             k_frames = np.ascontiguousarray(frames[keep])
-            flat = np.array([c for u in keep for c in targets[u]] or [0], dtype=np.int32)
-            off = np.zeros(len(keep) + 1, dtype=np.int64)
-            off[1:] = np.cumsum([len(targets[u]) for u in keep])
+            flat, off = self._pack_ids([targets[u] for u in keep])
             # one buffer for every utterance's rows, of float64 for float64 input and float32 otherwise: the shell makes it,
             # the native call fills it -- on the device for device tensors
             row0 = np.zeros(len(keep) + 1, dtype=np.int64)
