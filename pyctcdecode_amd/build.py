@@ -9,23 +9,26 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libctcdec.so")
-SOURCES = ["api.cpp", "host_tables.cpp", "kenlm_binary.cpp", "backend_hip.hip", "beam_wave_hip.hip", "beam_group_hip.hip",
-           "ctc_align_hip.hip"]
+SOURCES = ["api.cpp", "host_tables.cpp", "kenlm_binary.cpp", "backend_hip.hip", "frame_prune_hip.hip", "beam_wave_hip.hip",
+           "beam_group_hip.hip", "ctc_align_hip.hip"]
 # The wave kernel is one loop over the frames with ~18 000 instructions in its body and a budget of 128 registers. LLVM's
 # machine-level loop-invariant code motion hoists every constant and address computation it finds out of that loop and
 # keeps them in registers across it: 105 registers spilled to scratch memory (and every reload of one waits for the
 # stores in flight). Without the pass: none.
-# Round 5: the machine scheduler's "max-ilp" strategy for the frame-prune and wave kernels. Their occupancy is fixed by LDS and by
-# the waves-per-SIMD attribute, so the default strategy's goal (the fewest registers, loads issued right before their use) buys
-# nothing; scheduling for instruction-level parallelism took 6 % off frame_prune_fast (4.22 -> 3.98 ms, A/B in one process) and
-# 1.4 % off a lone wave's frame; at sixteen waves per CU the wave kernel is unchanged (profiles/r05_ab_experiments.log).
+# Round 5: the machine scheduler's "max-ilp" strategy for the frame-prune kernels (frame_prune_hip.hip) and the wave kernel. Their
+# occupancy is fixed by LDS and by the waves-per-SIMD attribute, so the default strategy's goal (the fewest registers, loads issued
+# right before their use) buys nothing; scheduling for instruction-level parallelism took 6 % off frame_prune_fast (4.22 -> 3.98 ms,
+# A/B in one process) and 1.4 % off a lone wave's frame; at sixteen waves per CU the wave kernel is unchanged
+# (profiles/r05_ab_experiments.log). backend_hip.hip held the prune kernels then and keeps the flag: its small kernels were built
+# with it ever since, and nobody has measured them without.
 _MAX_ILP = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
 HIP_FLAGS = {"backend_hip.hip": _MAX_ILP,
+             "frame_prune_hip.hip": _MAX_ILP,
              "beam_wave_hip.hip": ["-mllvm", "-disable-machine-licm"] + _MAX_ILP,
              # (the workgroup kernel: 238 -> 195 registers, 255 -> 138 scalar registers spilled to vector lanes)
              "beam_group_hip.hip": ["-mllvm", "-disable-machine-licm"]}
 HEADERS = ["common.h", "beam_core.h", "beam_wave.h", "set_order.h", "set_order_small.h", "backend.h", "host_tables.h", "np_sum.h",
-           "np_f32.h", "wave_ops_hip.h", "text_wave.h", "token_logp.h", "surv_ledger.h", "ctc_align.h"]
+           "np_f32.h", "wave_ops_hip.h", "text_wave.h", "token_logp.h", "surv_ledger.h", "ctc_align.h", "hip_try.h", "prune_route.h"]
 
 
 def hipcc() -> str:

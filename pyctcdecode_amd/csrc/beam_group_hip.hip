@@ -8,19 +8,11 @@
 
 #include "backend.h"
 #include "beam_core.h"
+#include "hip_try.h"
 #include "wave_ops_hip.h"
 
 namespace ctc {
 namespace be {
-
-#define HIP_TRY_G(expr)                                                                  \
-  do {                                                                                   \
-    hipError_t e_ = (expr);                                                              \
-    if (e_ != hipSuccess) {                                                              \
-      if (err) *err = std::string(#expr) + ": " + hipGetErrorString(e_);                 \
-      return -1;                                                                         \
-    }                                                                                    \
-  } while (0)
 
 // ---------------------------------------------------------------------------------------------
 // beam kernel
@@ -131,7 +123,7 @@ __global__ __launch_bounds__(NT, NT > 256 ? 1 : 2) void beam_decode(BeamArgs a, 
 
 template <int BW, int NT, bool MULTI>
 static int launch_beam_t(const BeamArgs& a, const LdsShape& shape, size_t lds, hipStream_t stream, std::string* err) {
-  HIP_TRY_G(hipFuncSetAttribute((const void*)beam_decode<BW, NT, MULTI>, hipFuncAttributeMaxDynamicSharedMemorySize,
+  HIP_TRY(hipFuncSetAttribute((const void*)beam_decode<BW, NT, MULTI>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)lds));
   hipLaunchKernelGGL((beam_decode<BW, NT, MULTI>), dim3((unsigned)a.n_utts), dim3(NT), lds, stream, a, shape.surv);
   return 0;

@@ -9,19 +9,11 @@
 #include "backend.h"
 #include "beam_core.h"
 #include "beam_wave.h"
+#include "hip_try.h"
 #include "wave_ops_hip.h"
 
 namespace ctc {
 namespace be {
-
-#define HIP_TRY_W(expr)                                                                  \
-  do {                                                                                   \
-    hipError_t e_ = (expr);                                                              \
-    if (e_ != hipSuccess) {                                                              \
-      if (err) *err = std::string(#expr) + ": " + hipGetErrorString(e_);                 \
-      return -1;                                                                         \
-    }                                                                                    \
-  } while (0)
 
 // ---------------------------------------------------------------------------------------------
 // wave kernel: one wavefront per utterance (beam_wave.h)
@@ -237,7 +229,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BW <= 100 ? 
 template <int BW, int ORD, bool PROF>
 static int launch_wave_p(const BeamArgs& a, hipStream_t stream, std::string* err) {
   const size_t lds = wave_lds_bytes<BW>();
-  HIP_TRY_W(hipFuncSetAttribute((const void*)beam_wave<BW, ORD, PROF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  HIP_TRY(hipFuncSetAttribute((const void*)beam_wave<BW, ORD, PROF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL((beam_wave<BW, ORD, PROF>), dim3((unsigned)a.n_utts), dim3(64), lds, stream, a);
   return 0;
 }

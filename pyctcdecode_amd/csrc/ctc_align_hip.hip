@@ -14,18 +14,10 @@
 
 #include "backend.h"
 #include "ctc_align.h"
+#include "hip_try.h"
 
 namespace ctc {
 namespace be {
-
-#define HIP_TRY_A(expr)                                                                  \
-  do {                                                                                   \
-    hipError_t e_ = (expr);                                                              \
-    if (e_ != hipSuccess) {                                                              \
-      if (err) *err = std::string(#expr) + ": " + hipGetErrorString(e_);                 \
-      return -1;                                                                         \
-    }                                                                                    \
-  } while (0)
 
 // ---------------------------------------------------------------------------------------------
 // row_lse: G lanes per row (a whole wave for wide rows, 16 or 4 lanes for small vocabularies, so that a wave takes 4 or 16
@@ -352,7 +344,7 @@ struct EventLog {
   int next(hipEvent_t* out, std::string* err) {
     if (used == ev.size()) {
       hipEvent_t e;
-      HIP_TRY_A(hipEventCreate(&e));
+      HIP_TRY(hipEventCreate(&e));
       ev.push_back(e);
     }
     *out = ev[used++];
@@ -379,10 +371,10 @@ template <class F>
 static int timed_launch(AlignKernel kind, hipStream_t stream, std::string* err, F launch) {
   hipEvent_t e0, e1;
   if (g_logs[kind].next(&e0, err) || g_logs[kind].next(&e1, err)) return -1;
-  HIP_TRY_A(hipEventRecord(e0, stream));
+  HIP_TRY(hipEventRecord(e0, stream));
   launch();
-  HIP_TRY_A(hipGetLastError());
-  HIP_TRY_A(hipEventRecord(e1, stream));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(e1, stream));
   return 0;
 }
 static int bad_launch(std::string* err, const char* what) {

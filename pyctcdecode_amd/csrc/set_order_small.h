@@ -2,7 +2,7 @@
 //
 // The same CPython 3.10 algorithm (Objects/setobject.c, restated in set_order.h: cpython_set_order), with every table
 // size it can reach for so few keys written out, so that one frame's tables fit 96 bytes and a wavefront can order 64
-// frames at once, one frame per lane (frame_prune_fast in backend_hip.hip):
+// frames at once, one frame per lane (frame_prune_fast in frame_prune_hip.hip):
 //   * set(ids): 8 slots; the 5th key grows it to 32 (used * 5 >= mask * 3 -> resize for used * 4); the next growth would
 //     come with the 19th key;
 //   * `| {argmax}` copies the left operand (set_merge): up to 4 keys the copy has the same 8 slots and is the table

@@ -1,4 +1,4 @@
-// np_div_check.hip -- is the short division of np_exp_nonpos_pk (csrc/backend_hip.hip, CTC_NP_SHORT_DIV) IEEE-exact on this
+// np_div_check.hip -- is the short division of np_exp_nonpos_pk (csrc/frame_prune_hip.hip, CTC_NP_SHORT_DIV) IEEE-exact on this
 // chip? For EVERY float32 r with |r| <= 0.36 (the reduced argument of numpy's float32 exp is within ln2/2 = 0.3466 of zero):
 // num = P5(r), den = Q2(r) as numpy evaluates them, then  num / den  by the compiler's IEEE division against
 // v_rcp_f32 + one Newton step + quotient + one fused correction. Prints how many of the ~2.1e9 arguments differ (expected: 0).
