@@ -18,9 +18,10 @@
 //     lane; with more than 64 live beams a label is two half passes matched together;
 //   * duplicates are found by a wave-wide hash match: one ds_max_u64 per candidate on
 //     (57-bit key tag | 127 - candidate) and one read back -- the smallest candidate of the largest tag
-//     owns a slot, losers move on to their next slot; the members of a group announce themselves to
-//     their representative through one ds_or on a 64-bit mask, which gives the representative the
-//     fold order (ascending beam rank, decoder.py:217-223) and the donor (last arrival) at once;
+//     owns a slot, the few losers of that one round are settled among themselves in registers (wave_match);
+//     the members of a group announce themselves to their representative through one ds_or on a 64-bit
+//     mask, which gives the representative the fold order (ascending beam rank, decoder.py:217-223) and the
+//     donor (last arrival) at once -- in a pass where somebody joined somebody: most passes skip all of it;
 //   * the pool of merged, scored candidates keeps 24 bytes per entry in LDS -- {score key, history key} for the
 //     ranking walk, {arrival, payload index, donor} -- and the rest (summed logit, new partial word, its table
 //     view) in a per-utterance payload line in global memory that only the table build reads; the pool holds
@@ -33,7 +34,7 @@
 //     posterior) are consumed in place, 64 at a time, each checked to leave the order intact (label_run).
 // Diagnostics, all off by default: CTC_WAVE_TRACE (device printf of pool / beam records), CTC_RUN_TRACE
 // (host: which frames label_run consumed), CTC_SIM_DEBUG (index checks in the simulator), CTC_STATS (simulator:
-// live beams / survivors / pool entries per frame), tick<>() phase timers (ctcdec_profile_phases).
+// live beams / survivors / pool entries / match rounds and merges per frame: tools/wave_merge_stats.py), tick<>() phase timers (ctcdec_profile_phases).
 // Everything a lane shares with another lane goes through LDS, global memory or a cross-lane instruction; `wsync()`
 // marks the points where LDS traffic of different lanes meets (on the device a compiler fence -- one
 // wave issues its LDS operations in order --, in the 64-fiber test simulator a rendezvous). Global memory written by
@@ -198,6 +199,104 @@ CTC_HD int wave_bucket(int beam_width) { return beam_width <= 64 ? 64 : beam_wid
 // payload lines per utterance: one per candidate that can be pushed in a frame
 CTC_HD size_t wave_pay_stride(const DecodeParams& p) { return (size_t)p.max_surv * (size_t)wave_bucket(p.beam_width); }
 
+// ---- wave-wide hash match ---------------------------------------------------------------------------------------
+// rep[j] = the smallest candidate index whose 64-bit key has the same 57-bit tag (key & ~127), for A candidates per lane
+// (v = j * 64 + lane; valid ones only, the others keep rep = v). `table`: TS = 128 slots, cleared by the caller.
+//   * One table round: every candidate does one ds_max_u64 of (tag | 127 - v) on the slot its key names and reads the slot
+//     back. The largest tag owns the slot, and of that tag the smallest candidate; the candidates of the owner's tag are
+//     settled. All candidates of one tag go to the same slot with the same tag, so they win or lose TOGETHER.
+//   * The losers of the round -- a handful: ~46 keys in 128 slots leave ~7 behind, nearly all of them distinct keys that
+//     met in a slot, not duplicates -- are settled among themselves in registers: the lowest open candidate s broadcasts
+//     its key, every open candidate of that tag takes rep = s and closes. Exact because a tag's candidates are all still
+//     open when one of them is (above): the lowest open one is the lowest of its tag. No LDS access, one step per open tag.
+//   * More than WAVE_MATCH_LOOP_MAX losers (many keys in few slots): one more table round first, at the next slot of each
+//     key (other key bits) in a table cleared again -- legal: the settled candidates have read their representative -- so that
+//     the winners of round one are not in the way; then the loop.
+// Written against the execution context only (device wave / 64-fiber simulator / stand-alone harness: tests/sim).
+// Returns table rounds | loop steps << 16 (statistics).
+#ifndef CTC_MATCH_LOOP_MAX
+#define CTC_MATCH_LOOP_MAX 4  // (profiles/match_rounds_check.txt: 4, 8 and 16 timed against each other)
+#endif
+constexpr uint32_t WAVE_MATCH_LOOP_MAX = CTC_MATCH_LOOP_MAX;
+template <int A, int TS, class Ctx>
+CTC_HD uint32_t wave_match(Ctx& ctx, CTC_LDS uint64_t* table, int lane, const bool* valid, const uint64_t* ck, uint32_t* rep) {
+  static_assert(TS == 128, "the table is cleared as 64 x 16 bytes, and a candidate index takes the tag's low seven bits");
+  constexpr uint32_t MASK = (uint32_t)(TS - 1);
+  constexpr uint64_t TAG = ~127ull;
+  bool open[A];
+  uint32_t slot[A];
+  uint64_t om[A];  // (wave-uniform) the candidates still open
+CTC_UNROLL
+  for (int j = 0; j < A; ++j) {
+    open[j] = valid[j];
+    rep[j] = (uint32_t)(j * 64 + lane);
+    slot[j] = (uint32_t)(ck[j] >> 7) & MASK;
+  }
+  uint32_t rounds = 0, steps = 0;
+  for (uint32_t round = 0;; ++round) {
+    ++rounds;
+CTC_UNROLL
+    for (int j = 0; j < A; ++j) {
+      const uint32_t v = (uint32_t)(j * 64 + lane);
+      if (open[j]) ctx.lds_max_u64(&table[slot[j]], (ck[j] & TAG) | (uint64_t)(127u - v));
+    }
+    ctx.wsync();
+    uint64_t got[A];
+CTC_UNROLL
+    for (int j = 0; j < A; ++j) got[j] = open[j] ? table[slot[j]] : 0ull;
+    uint32_t n_open = 0;
+CTC_UNROLL
+    for (int j = 0; j < A; ++j) {
+      if (open[j]) {
+        if ((got[j] & TAG) == (ck[j] & TAG)) {
+          rep[j] = 127u - (uint32_t)(got[j] & 127ull);
+          open[j] = false;
+        } else {
+          slot[j] = (uint32_t)(ck[j] >> (15 + 8 * round)) & MASK;
+        }
+      }
+    }
+    ctx.wsync();
+CTC_UNROLL
+    for (int j = 0; j < A; ++j) {
+      om[j] = ctx.ballot(open[j]);
+      n_open += (uint32_t)ctx.popc64(om[j]);
+    }
+    if (round == 1u || n_open <= WAVE_MATCH_LOOP_MAX) break;
+    ((CTC_LDS u32x4*)table)[lane] = mk4(0, 0, 0, 0);
+    ctx.wsync();
+  }
+  for (;;) {
+    uint64_t any = 0ull;
+CTC_UNROLL
+    for (int j = 0; j < A; ++j) any |= om[j];
+    if (any == 0ull) break;
+    ++steps;
+    uint32_t s = 0;
+    uint64_t key = 0;
+    bool found = false;
+CTC_UNROLL
+    for (int j = 0; j < A; ++j) {
+      if (!found && om[j] != 0ull) {
+        const int src = ctx.ctz64(om[j]);
+        key = ctx.bcast64(ck[j], src);
+        s = (uint32_t)(j * 64 + src);
+        found = true;
+      }
+    }
+CTC_UNROLL
+    for (int j = 0; j < A; ++j) {
+      const bool hit = open[j] && ((ck[j] ^ key) & TAG) == 0ull;
+      if (hit) {
+        rep[j] = s;
+        open[j] = false;
+      }
+      om[j] &= ~ctx.ballot(hit);
+    }
+  }
+  return rounds | (steps << 16);
+}
+
 constexpr int W_PROF_LOAD = 0, W_PROF_COMP = 1, W_PROF_GEN = 2, W_PROF_MATCH = 3, W_PROF_FOLD = 4, W_PROF_SCORE = 5,
               W_PROF_RANK = 6, W_PROF_BUILD = 7, W_PROF_FINAL = 8, W_PROF_COMPACT = 9, W_PROF_PUSH = 10, W_PROF_PFTOK = 11,
               W_PROF_GATHER = 12, W_PROF_BIG = 13, W_PROF_TABLES = 14, W_PROF_RUN = 15, W_PROF_ST_COMP = 16, W_PROF_ST_PUSH = 17,
@@ -234,6 +333,9 @@ struct WaveDecoder {
   bool pf_live = false;
   bool run_ok = false;   // the beam table is the output of a full frame of this launch (label_run's precondition)
   unsigned long long t_last = 0;  // (diagnostics: phase ticks are accumulated in global memory)
+#ifdef CTC_STATS
+  uint32_t st_rounds = 0, st_loop = 0, st_members = 0, st_pass1 = 0;  // of the frame: match-table rounds, loser-loop steps, candidates that joined another, pass1 calls
+#endif
 
   CTC_HD WaveDecoder(Ctx& c, WaveLds& l, const UttIO& i) : ctx(c), L(l), io(i), lane(c.lane) {}
 
@@ -789,49 +891,16 @@ CTC_UNROLL
     c.lg = bits_f64(q_lo(k1)) + bits_f64(pack64(sv[2], sv[3]));
   }
 
-  // wave-wide hash match on 64-bit keys (valid lanes only): rep = smallest candidate index with the same key.
-  // The smallest candidate of the largest tag owns a slot; the others of its key join it, the rest move to their
-  // next slot (other key bits, then linear). A candidates per lane (v = j * 64 + lane), all inserted in the same
-  // round (the members of a key must see the same slot history); 128 slots, cleared by the caller. (A settled owner
-  // may later be displaced by a larger tag: its members have read their representative by then.)
+  // wave-wide hash match on 64-bit keys (wave_match above): rep = smallest candidate index with the same key tag
   template <int A>
   CTC_HD void match(const bool* valid, const uint64_t* ck, uint32_t* rep) {
-    constexpr uint32_t MASK = (uint32_t)(S::TS - 1);
-    bool open[A];
-    uint32_t slot[A];
-CTC_UNROLL
-    for (int j = 0; j < A; ++j) {
-      open[j] = valid[j];
-      rep[j] = (uint32_t)(j * 64 + lane);
-      slot[j] = (uint32_t)(ck[j] >> 7) & MASK;
-    }
-    for (uint32_t round = 0;; ++round) {
-      bool any_open = false;
-CTC_UNROLL
-      for (int j = 0; j < A; ++j) any_open = any_open || open[j];
-      if (ctx.ballot(any_open) == 0ull) break;
-CTC_UNROLL
-      for (int j = 0; j < A; ++j) {
-        const uint32_t v = (uint32_t)(j * 64 + lane);
-        if (open[j]) ctx.lds_max_u64(&L.table[slot[j]], (ck[j] & ~127ull) | (uint64_t)(127u - v));
-      }
-      ctx.wsync();
-      uint64_t got[A];
-CTC_UNROLL
-      for (int j = 0; j < A; ++j) got[j] = open[j] ? L.table[slot[j]] : 0ull;
-CTC_UNROLL
-      for (int j = 0; j < A; ++j) {
-        if (open[j]) {
-          if ((got[j] & ~127ull) == (ck[j] & ~127ull)) {
-            rep[j] = 127u - (uint32_t)(got[j] & 127ull);
-            open[j] = false;
-          } else {
-            slot[j] = round < 5u ? ((uint32_t)(ck[j] >> (15 + 8 * round)) & MASK) : ((slot[j] + 1u) & MASK);
-          }
-        }
-      }
-      ctx.wsync();
-    }
+    const uint32_t m = wave_match<A, S::TS>(ctx, L.table.p, lane, valid, ck, rep);
+#ifdef CTC_STATS
+    st_rounds += m & 0xFFFFu;
+    st_loop += m >> 16;
+#else
+    (void)m;
+#endif
   }
   CTC_HD void clear_table() { ((CTC_LDS u32x4*)L.table.p)[lane] = mk4(0, 0, 0, 0); }  // 128 slots = 64 x 16 bytes
 
@@ -1052,18 +1121,27 @@ CTC_UNROLL
     tick<W_PROF_GEN>();
     uint32_t rep;
     match<1>(&c.valid, &c.ck, &rep);
-    // members announce themselves to their representative (the mask words take the place of the table's first half)
-    *(CTC_LDS uint64_t*)&L.gmask[lane * 2] = 0ull;
-    ctx.wsync();
-    if (c.valid && rep != v) ctx.lds_or_u32(&L.gmask[rep * 2 + (v >> 5)], 1u << (v & 31u));
     c.is_rep = c.valid && rep == v;
-    ctx.wsync();
-    tick<W_PROF_MATCH>();
-    // ---- fold the group's logits in ascending beam rank (decoder.py:217-223); donor = last arrival
-    // (before the table probes and the ColdRec chunk that gen requested are looked at: the fold needs neither, and whatever it
-    //  costs is taken off the wait for them)
+    const uint64_t members = ctx.ballot(c.valid && rep != v);
+#ifdef CTC_STATS
+    ++st_pass1;
+    st_members += (uint32_t)ctx.popc64(members);
+#endif
     uint32_t imax = c.bi, dbr = c.br;
-    {
+    if (members == 0ull) {
+      // nobody joined anybody (all but 1 - 2 % of the frames of a real decode): every candidate stands for itself and is its
+      // own donor -- no announcement, no masks, no fold
+      tick<W_PROF_MATCH>();
+    } else {
+      // members announce themselves to their representative (the mask words take the place of the table's first half)
+      *(CTC_LDS uint64_t*)&L.gmask[lane * 2] = 0ull;
+      ctx.wsync();
+      if (c.valid && rep != v) ctx.lds_or_u32(&L.gmask[rep * 2 + (v >> 5)], 1u << (v & 31u));
+      ctx.wsync();
+      tick<W_PROF_MATCH>();
+      // ---- fold the group's logits in ascending beam rank (decoder.py:217-223); donor = last arrival
+      // (before the table probes and the ColdRec chunk that gen requested are looked at: the fold needs neither, and whatever
+      //  it costs is taken off the wait for them)
       uint32_t g0 = 0, g1 = 0;
       bool more = false;
       double lp = 0.0;
@@ -1126,38 +1204,49 @@ CTC_UNROLL
     }
     ctx.wsync();
     match<2>(valid, ck, rep);
-    uint64_t mlo[2], mhi[2];
-    group_masks<2>(valid, rep, mlo, mhi);
-    // fold in ascending beam rank (decoder.py:217-223); a member's summed logit is its beam's logit + the label's
     uint32_t imax[2];
     bool is_rep[2];
-    bool more = false;
+    bool member = false;
 CTC_UNROLL
     for (int h = 0; h < 2; ++h) {
       const uint32_t v = (uint32_t)(h * 64 + lane);
       is_rep[h] = valid[h] && rep[h] == v;
       imax[h] = v;
-      if (is_rep[h]) {
-        if (mlo[h]) imax[h] = (uint32_t)(63 - ctx.clz64(mlo[h]));
-        if (mhi[h]) imax[h] = (uint32_t)(127 - ctx.clz64(mhi[h]));
-      }
-      more = more || (is_rep[h] && (mlo[h] | mhi[h]) != 0ull);
+      member = member || (valid[h] && rep[h] != v);
     }
-    while (ctx.ballot(more) != 0ull) {
-      more = false;
+#ifdef CTC_STATS
+    for (int h = 0; h < 2; ++h) st_members += (uint32_t)ctx.popc64(ctx.ballot(valid[h] && rep[h] != (uint32_t)(h * 64 + lane)));
+#endif
+    // (nobody joined anybody -- the usual case: every candidate stands for itself and is its own donor)
+    if (ctx.ballot(member) != 0ull) {
+      uint64_t mlo[2], mhi[2];
+      group_masks<2>(valid, rep, mlo, mhi);
+      // fold in ascending beam rank (decoder.py:217-223); a member's summed logit is its beam's logit + the label's
+      bool more = false;
 CTC_UNROLL
       for (int h = 0; h < 2; ++h) {
-        if (is_rep[h] && (mlo[h] | mhi[h]) != 0ull) {
-          uint32_t mbit;
-          if (mlo[h]) {
-            mbit = (uint32_t)ctx.ctz64(mlo[h]);
-            mlo[h] &= mlo[h] - 1ull;
-          } else {
-            mbit = (uint32_t)(64 + ctx.ctz64(mhi[h]));
-            mhi[h] &= mhi[h] - 1ull;
+        if (is_rep[h]) {
+          if (mlo[h]) imax[h] = (uint32_t)(63 - ctx.clz64(mlo[h]));
+          if (mhi[h]) imax[h] = (uint32_t)(127 - ctx.clz64(mhi[h]));
+        }
+        more = more || (is_rep[h] && (mlo[h] | mhi[h]) != 0ull);
+      }
+      while (ctx.ballot(more) != 0ull) {
+        more = false;
+CTC_UNROLL
+        for (int h = 0; h < 2; ++h) {
+          if (is_rep[h] && (mlo[h] | mhi[h]) != 0ull) {
+            uint32_t mbit;
+            if (mlo[h]) {
+              mbit = (uint32_t)ctx.ctz64(mlo[h]);
+              mlo[h] &= mlo[h] - 1ull;
+            } else {
+              mbit = (uint32_t)(64 + ctx.ctz64(mhi[h]));
+              mhi[h] &= mhi[h] - 1ull;
+            }
+            lg[h] = lse2(lg[h], bits_f64(L.b64[mbit * 2]) + lp);
+            more = more || (mlo[h] | mhi[h]) != 0ull;
           }
-          lg[h] = lse2(lg[h], bits_f64(L.b64[mbit * 2]) + lp);
-          more = more || (mlo[h] | mhi[h]) != 0ull;
         }
       }
     }
@@ -1386,7 +1475,8 @@ CTC_UNROLL
 #endif
     uint32_t n = rank_pool(thr, hist);
 #ifdef CTC_STATS
-    if (lane == 0) fprintf(stderr, "ST %d %u %u %u\n", N, ns, pool_n, n);
+    if (lane == 0) fprintf(stderr, "ST %d %u %u %u %u %u %u %u\n", N, ns, pool_n, n, st_rounds, st_members, st_pass1, st_loop);
+    st_rounds = st_loop = st_members = st_pass1 = 0;
 #endif
     if (n > H.beam_width) n = H.beam_width;
     tick<W_PROF_RANK>();
