@@ -403,6 +403,42 @@ int ctcdec_align_gaps_batch(ctcdec_decoder* dec, const void* const* utt_logits, 
 int ctcdec_alignment_gaps(const ctcdec_alignment* a, const int64_t** gap_off, const int32_t** start, const int32_t** end,
                           const double** logp, int64_t* n_gaps);
 
+/* ---- greedy decode: the best path over all texts ----------------------------------------------------------------------
+ * No reference analogue (pyctcdecode always searches). Logits, frame counts, dtype and is_device are those of
+ * ctcdec_decode_batch. Frame t's label arg[t] is the smallest index among the entries of row t that equal the row's largest
+ * entry that is not a NaN (-0.0 and +0.0 are equal; a row without an entry above -inf takes the blank): the same for logits
+ * and for probabilities, so nothing is classified. A token is a maximal run of frames with the same label other than the
+ * blank: (label, start, end), end exclusive; equal labels with a blank frame between them are two tokens; an utterance has at
+ * most as many tokens as frames, and none of ctcdec_align_batch's limits applies. The text of an utterance is formed from
+ * its tokens' labels on the host: under a character alphabet the space label ends a word (it is a token of the result all
+ * the same), under a BPE alphabet a leading U+2581 begins a word and a trailing one ends it; words are joined by one space.
+ * fold: 0 -- one kernel reads every entry once and compares, a second collapses the labels: no classification, no
+ * exponential --, or CTCDEC_TOKEN_LOGP_MEAN / _MIN / _MAX. With a fold the call classifies as ctcdec_align_batch does and
+ * forms e(t), ctcdec_align_gaps_batch's g(t): the clipped float64 log-probability of row t's largest entry. score[u] is the
+ * sum of e(t) over all of utterance u's frames, blanks included, added in frame order; a token's logp is the fold of e(t)
+ * over its frames, in frame order. Both sums run as ctcdec_align_batch's do, so for an utterance with a token score[u]
+ * equals, bit for bit, that call's score for the greedy labels as the target -- no path beats the frames' maxima -- and that
+ * of ctcdec_align_gaps_batch with every slot a gap.
+ * CTCDEC_ERR_ARG before anything is launched: a null pointer, a negative frame count, a bad dtype or fold. Without frames
+ * nothing is launched. decoder.py: decode_greedy / decode_greedy_batch. */
+typedef struct ctcdec_greedy ctcdec_greedy; /* opaque */
+int ctcdec_greedy_batch(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts,
+                        int32_t dtype, int32_t is_device, int32_t fold, ctcdec_greedy** out);
+/* Utterance u's text is the UTF-8 bytes blob[off[u] .. off[u + 1]). Pointers stay valid until ctcdec_greedy_free. */
+int ctcdec_greedy_texts(const ctcdec_greedy* g, const char** blob, const int64_t** off, int64_t* n_utts);
+/* Every token, in the layout of ctcdec_alignment_tokens: utterance u's are [tok_off[u], tok_off[u + 1]) of label / start /
+ * end (end exclusive) and, when a fold was asked for, logp (else NULL). */
+int ctcdec_greedy_tokens(const ctcdec_greedy* g, const int64_t** tok_off, const int32_t** label, const int32_t** start,
+                         const int32_t** end, const double** logp, int64_t* n_tokens);
+/* score[u]: the sum of e(t) over utterance u's frames (0.0 without frames); NULL when no fold was asked for */
+int ctcdec_greedy_scores(const ctcdec_greedy* g, const double** score, int64_t* n_utts);
+/* milliseconds: [0] the classification (frame-prune kernels; 0 without a fold), [1] the row kernel -- row_argmax, or
+ * row_lse_argmax with a fold --, [2] greedy_collapse's two passes (HIP events on the decode stream), [3] the whole native
+ * call; launches: kernels launched after the classification (may be NULL); lse_ms: the part of [1] that a kernel with a
+ * log-sum-exp took -- [1] with a fold, 0 without (may be NULL) */
+int ctcdec_greedy_timing(const ctcdec_greedy* g, double* ms4, int32_t* launches, double* lse_ms);
+void ctcdec_greedy_free(ctcdec_greedy* g);
+
 /* ---- transcript likelihood: how probable a label sequence the caller already has is, given the audio -----------------
  * No reference analogue (torch.nn.functional.ctc_loss computes the negative of it). Utterance u owns the hypotheses
  * [hyp_off[u], hyp_off[u + 1]); hypothesis h is the label ids targets[target_off[h] .. target_off[h + 1]) (alphabet

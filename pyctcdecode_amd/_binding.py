@@ -157,6 +157,15 @@ _PROTOS = {
                                           C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_int32, C.c_int64, C.POINTER(_VP)]),
     "ctcdec_alignment_gaps": (C.c_int, [_VP, C.POINTER(C.POINTER(C.c_int64)), C.POINTER(C.POINTER(C.c_int32)),
                                         C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.c_int64)]),
+    "ctcdec_greedy_batch": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                      C.POINTER(_VP)]),
+    "ctcdec_greedy_texts": (C.c_int, [_VP, C.POINTER(C.c_void_p), C.POINTER(C.POINTER(C.c_int64)), C.POINTER(C.c_int64)]),
+    "ctcdec_greedy_tokens": (C.c_int, [_VP, C.POINTER(C.POINTER(C.c_int64)), C.POINTER(C.POINTER(C.c_int32)),
+                                       C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_int32)),
+                                       C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.c_int64)]),
+    "ctcdec_greedy_scores": (C.c_int, [_VP, C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.c_int64)]),
+    "ctcdec_greedy_timing": (C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "ctcdec_greedy_free": (None, [_VP]),
     "ctcdec_score_batch": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32,
                                      C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32,
                                      C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

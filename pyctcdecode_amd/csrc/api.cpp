@@ -223,6 +223,9 @@ struct ctcdec_decoder {
   // alignment with gaps (ctcdec_align_gaps_batch): row maxima, the slots' gap flags, the gaps' sums, a launch's utterance
   // records (everything else: the alignment's)
   DevBuf w_amax, w_agap, w_aglp, w_agutts;
+  // greedy decode (ctcdec_greedy_batch): the rows' labels, the utterances' token counts and offsets, the tokens' labels, spans
+  // and confidences (row maxima: w_amax, scores: w_ascore)
+  DevBuf w_garg, w_gcnt, w_gtoff, w_glab, w_gspan, w_glogp;
   bool slicing = false;  // a time-sliced host ingest is under way (decode_host_sliced): the prune stage notes each slice's side of 1
   uint32_t max_label_bytes = 1;
   bool arenas_worst_case = false;  // a call has outgrown the usual reservation of the node arenas: reserve the worst case from now on
@@ -2414,8 +2417,8 @@ static int check_alignment(const void* const* utt_logits, const int32_t* utt_fra
 
 // What every transcript call does before its own recursion: the device lock taken (held while the AlignFront lives) and the
 // device bound to the thread, host matrices staged (consecutive ones in one copy; device pointers are used in place),
-// pointers and row offsets uploaded, the utterances classified as probabilities or logits, and row_lse over the rows of the
-// logit utterances -- once per utterance.
+// pointers and row offsets uploaded -- align_stage, all that a greedy decode without confidences needs --, the utterances
+// classified as probabilities or logits, and row_lse over the rows of the logit utterances -- once per utterance.
 struct AlignFront {
   std::unique_lock<std::mutex> device_lock;
   std::vector<const void*> ptrs;   // [n] device pointers of the utterances' matrices
@@ -2424,8 +2427,10 @@ struct AlignFront {
   double sniff_ms = 0;             // the classification's kernel time
   bool want_max = false;           // in: row_lse_max instead of row_lse (ctcdec_align_gaps_batch)
   double* rmax = nullptr;          // [R] (device, want_max) every row's largest entry that is not a NaN
+  int want_arg_blank = -1;         // in: >= 0 (with want_max): row_lse_argmax, this the blank's index (ctcdec_greedy_batch)
+  int32_t* arg = nullptr;          // [R] (device, want_arg_blank >= 0) every row's most probable label
 };
-static int align_front(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts, int32_t dtype,
+static int align_stage(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts, int32_t dtype,
                        int32_t is_device, int V, const std::vector<int64_t>& row0, AlignFront& f) {
   std::string err;
   f.device_lock = std::unique_lock<std::mutex>(g_device_mu);
@@ -2455,6 +2460,15 @@ static int align_front(ctcdec_decoder* dec, const void* const* utt_logits, const
     }
   }
   if (upload(dec->w_ptrs, ptrs, &err) || upload(dec->w_row0, row0, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+  return CTCDEC_OK;
+}
+static int align_front(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts, int32_t dtype,
+                       int32_t is_device, int V, const std::vector<int64_t>& row0, AlignFront& f) {
+  if (int rc = align_stage(dec, utt_logits, utt_frames, n_utts, dtype, is_device, V, row0, f)) return rc;
+  std::string err;
+  const size_t n = (size_t)n_utts;
+  const int64_t R = row0[n];
+  std::vector<const void*>& ptrs = f.ptrs;
   // probabilities or logits? The decode's own prune stage decides (pass 0 and its sniff, the exact test for the ambiguous),
   // at a threshold nothing but a certain label passes: its survivor lists are three entries wide and are not looked at.
   PruneStage s{dec, &ptrs, n_utts, dtype, R, V, 0.0};
@@ -2469,10 +2483,17 @@ static int align_front(ctcdec_decoder* dec, const void* const* utt_logits, const
     if (dec->w_amax.ensure((size_t)R * 8, &err)) return fail(CTCDEC_ERR_DEVICE, err);
     f.rmax = (double*)dec->w_amax.p;
   }
+  const bool want_arg = f.want_max && f.want_arg_blank >= 0;
+  if (want_arg) {
+    if (dec->w_garg.ensure((size_t)R * 4, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+    f.arg = (int32_t*)dec->w_garg.p;
+  }
 #ifdef CTC_SIM  // (the simulator's device memory is host memory: the kernels' bodies, row by row and utterance by utterance)
   for (size_t u = 0; u < n; ++u)
-    for (int64_t t = 0; f.want_max && t < utt_frames[u]; ++t)
+    for (int64_t t = 0; f.want_max && t < utt_frames[u]; ++t) {
       row_lse_max_seq(ptrs[u], dtype, (size_t)t * (size_t)V, V, f.is_prob[u] != 0, &lse[row0[u] + t], &f.rmax[row0[u] + t]);
+      if (want_arg) f.arg[row0[u] + t] = row_argmax_seq(ptrs[u], dtype, (size_t)t * (size_t)V, V, f.want_arg_blank);
+    }
   for (size_t u = 0; u < n; ++u)
     for (int64_t t = 0; !f.want_max && !f.is_prob[u] && t < utt_frames[u]; ++t)
       lse[row0[u] + t] = row_lse_seq(ptrs[u], dtype, (size_t)t * (size_t)V, V);
@@ -2487,7 +2508,9 @@ static int align_front(ctcdec_decoder* dec, const void* const* utt_logits, const
   la.n_labels = V;
   la.dtype = dtype;
   la.lse = lse;
-  if (f.want_max ? be::launch_row_lse_max(la, f.rmax, &err) : be::launch_row_lse(la, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+  if (want_arg ? be::launch_row_lse_argmax(la, f.rmax, f.arg, f.want_arg_blank, &err)
+               : f.want_max ? be::launch_row_lse_max(la, f.rmax, &err) : be::launch_row_lse(la, &err))
+    return fail(CTCDEC_ERR_DEVICE, err);
 #endif
   return CTCDEC_OK;
 }
@@ -2742,6 +2765,255 @@ int ctcdec_alignment_gaps(const ctcdec_alignment* a, const int64_t** gap_off_out
 }
 
 // ---- transcript likelihood ("Transcript likelihood") -----------------------------------------------------------
+}  // extern "C"
+
+// ---- greedy decode ("Greedy decode") ---------------------------------------------------------------------------------
+struct ctcdec_greedy {
+  std::vector<int64_t> tok_off, text_off;
+  std::vector<int32_t> label, start, end;
+  std::vector<double> logp, score;
+  std::string texts;
+  bool has_fold = false;
+  int32_t launches = 0;
+  double ms[4] = {0, 0, 0, 0};
+  double lse_ms = 0;
+};
+
+#ifdef CTC_SIM
+namespace {
+struct GreedySeqCtx {  // (greedy_collapse_utt: a "wave" of one lane, a frame a step)
+  int lane() const { return 0; }
+  int lanes() const { return 1; }
+  int32_t up(int32_t v) const { return v; }
+  int32_t down(int32_t v) const { return v; }
+  int32_t first(int32_t v) const { return v; }
+  int32_t last(int32_t v) const { return v; }
+  uint64_t ballot(bool b) const { return b ? 1u : 0u; }
+  void publish() const {}
+};
+}  // namespace
+#endif
+
+// The text of a sequence of token labels, as decoder.py's _words_of_target forms it: under a character alphabet the space label
+// ends a word and the other labels are its pieces; under a BPE alphabet a label that begins with the mark, or follows one
+// that ends with it (and is more than the mark alone), begins a word, and the pieces are the labels without the marks at
+// either end. Words are joined by one space; a word of empty pieces alone (the bare mark) is a word too and takes its
+// separator. What a label contributes is worked out once per call, not once per token.
+struct GreedyWords {
+  std::vector<std::string> piece;          // what the label appends to its word
+  std::vector<uint8_t> ends, begins, forces;  // the space label; a leading mark; a trailing mark on more than the mark alone
+  explicit GreedyWords(const HostAlphabet& alpha) {
+    static const std::string MARK = "\xE2\x96\x81";  // U+2581
+    const size_t V = alpha.labels.size(), m = MARK.size();
+    piece.resize(V);
+    ends.assign(V, 0), begins.assign(V, 0), forces.assign(V, 0);
+    for (size_t c = 0; c < V; ++c) {
+      const std::string& l = alpha.labels[c];
+      if (!alpha.is_bpe) {
+        ends[c] = l == " ";
+        piece[c] = l;
+        continue;
+      }
+      begins[c] = l.compare(0, m, MARK) == 0;
+      forces[c] = utf8_length(l.data(), l.size()) > 1 && l.size() >= m && l.compare(l.size() - m, m, MARK) == 0;
+      size_t a = 0, b = l.size();  // str.strip(mark): every mark at either end
+      while (b - a >= m && l.compare(a, m, MARK) == 0) a += m;
+      while (b - a >= m && l.compare(b - m, m, MARK) == 0) b -= m;
+      piece[c] = l.substr(a, b - a);
+    }
+  }
+  void append_text(const int32_t* lab, int64_t n, std::string& out) const {
+    bool open = false, any_word = false, force = false;  // a word has a piece; the text has a word; the next label begins a word
+    for (int64_t k = 0; k < n; ++k) {
+      const size_t c = (size_t)lab[k];
+      if (ends[c]) {
+        open = false;
+        continue;
+      }
+      if (force || begins[c]) open = false;
+      force = forces[c] != 0;
+      if (!open) {
+        if (any_word) out += ' ';
+        open = any_word = true;
+      }
+      out += piece[c];
+    }
+  }
+};
+
+static int greedy_call(ctcdec_decoder* dec, const TranscriptCall& tc, const void* const* utt_logits, const int32_t* utt_frames,
+                       int32_t n_utts, int32_t dtype, int32_t is_device, int32_t fold, std::unique_ptr<ctcdec_greedy>& res) {
+  res.reset(new ctcdec_greedy());
+  const size_t n = (size_t)n_utts;
+  const std::vector<int64_t> row0 = row_starts(utt_frames, n);
+  const int64_t R = row0[n];
+  res->has_fold = fold != 0;
+  res->tok_off.assign(n + 1, 0);
+  res->text_off.assign(n + 1, 0);
+  if (fold) res->score.assign(n, 0.0);
+  if (R == 0) return CTCDEC_OK;  // (no frames: no tokens, empty texts, nothing launched)
+  std::string err;
+  AlignFront fr;
+  if (fold) {
+    fr.want_max = true;
+    fr.want_arg_blank = tc.blank;
+    if (int rc = align_front(dec, utt_logits, utt_frames, n_utts, dtype, is_device, tc.V, row0, fr)) return rc;
+    res->ms[0] = fr.sniff_ms;
+  } else {
+    // every logit is read once, by row_argmax: no classification, no log-sum-exp
+    if (int rc = align_stage(dec, utt_logits, utt_frames, n_utts, dtype, is_device, tc.V, row0, fr)) return rc;
+    if (dec->w_garg.ensure((size_t)R * 4, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+    fr.arg = (int32_t*)dec->w_garg.p;
+#ifdef CTC_SIM
+    for (size_t u = 0; u < n; ++u)
+      for (int64_t t = 0; t < utt_frames[u]; ++t)
+        fr.arg[row0[u] + t] = row_argmax_seq(fr.ptrs[u], dtype, (size_t)t * (size_t)tc.V, tc.V, tc.blank);
+#else
+    be::align_timing_reset();
+    be::RowLseArgs la;
+    la.utt_logits = (const void* const*)dec->w_ptrs.p;
+    la.utt_row0 = (const int64_t*)dec->w_row0.p;
+    la.utt_is_prob = nullptr;
+    la.n_utts = n_utts;
+    la.n_rows = R;
+    la.n_labels = tc.V;
+    la.dtype = dtype;
+    la.lse = nullptr;
+    if (be::launch_row_argmax(la, fr.arg, tc.blank, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+#endif
+  }
+  ++res->launches;
+  // the count pass, the host's scan of n counts, the write pass
+  if (dec->w_gcnt.ensure(n * 4, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+  GreedyArgs ga;
+  memset(&ga, 0, sizeof(ga));
+  ga.arg = fr.arg;
+  ga.row0 = (const int64_t*)dec->w_row0.p;
+  ga.count = (int32_t*)dec->w_gcnt.p;
+  ga.n_utts = n_utts;
+  ga.blank = tc.blank;
+  ga.fold = fold;
+  ga.write = 0;
+  ga.clip_lo = tc.clip_lo;
+  const auto collapse = [&]() -> int {
+#ifdef CTC_SIM
+    GreedySeqCtx cx;
+    for (int32_t u = 0; u < n_utts; ++u) greedy_collapse_utt(cx, ga, u);
+#else
+    if (be::launch_greedy_collapse(ga, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+#endif
+    ++res->launches;
+    return CTCDEC_OK;
+  };
+  if (int rc = collapse()) return rc;
+  std::vector<int32_t> count(n, 0);
+  if (be::d2h(count.data(), dec->w_gcnt.p, n * 4, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+  for (size_t u = 0; u < n; ++u) {
+    if (count[u] < 0 || count[u] > utt_frames[u]) return fail(CTCDEC_ERR_INTERNAL, "greedy_collapse counted more tokens than frames");
+    res->tok_off[u + 1] = res->tok_off[u] + count[u];
+  }
+  const int64_t NT = res->tok_off[n];
+  const size_t nt1 = (size_t)std::max<int64_t>(NT, 1);
+  if (upload(dec->w_gtoff, res->tok_off, &err) || dec->w_glab.ensure(nt1 * 4, &err) || dec->w_gspan.ensure(nt1 * 8, &err) ||
+      (fold && (dec->w_glogp.ensure(nt1 * 8, &err) || dec->w_ascore.ensure(n * 8, &err))))
+    return fail(CTCDEC_ERR_DEVICE, err);
+  ga.write = 1;
+  ga.tok_off = (const int64_t*)dec->w_gtoff.p;
+  ga.label = (int32_t*)dec->w_glab.p;
+  ga.start = (int32_t*)dec->w_gspan.p;
+  ga.end = (int32_t*)dec->w_gspan.p + nt1;
+  if (fold) {
+    ga.lse = fr.lse;
+    ga.rmax = fr.rmax;
+    ga.is_prob = (const uint32_t*)dec->w_isprob.p;
+    ga.logp = (double*)dec->w_glogp.p;
+    ga.score = (double*)dec->w_ascore.p;
+  }
+  if (int rc = collapse()) return rc;
+  // one copy per array, of the tokens' size
+  res->label.resize((size_t)NT);
+  res->start.resize((size_t)NT);
+  res->end.resize((size_t)NT);
+  if (fold) res->logp.resize((size_t)NT);
+  if (NT && (be::d2h(res->label.data(), ga.label, (size_t)NT * 4, &err) || be::d2h(res->start.data(), ga.start, (size_t)NT * 4, &err) ||
+             be::d2h(res->end.data(), ga.end, (size_t)NT * 4, &err) || (fold && be::d2h(res->logp.data(), ga.logp, (size_t)NT * 8, &err))))
+    return fail(CTCDEC_ERR_DEVICE, err);
+  if (fold && be::d2h(res->score.data(), ga.score, n * 8, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+#ifndef CTC_SIM
+  res->ms[1] = be::align_kernel_ms(fold ? be::K_ROW_LSE_ARGMAX : be::K_ROW_ARGMAX);
+  res->ms[2] = be::align_kernel_ms(be::K_GREEDY_COLLAPSE);
+  res->lse_ms = fold ? res->ms[1] : 0.0;
+  // (AlignFront::sniff_ms comes from be::last_timing, which reports nothing for a prune stage that no beam launch follows)
+  if (fold) res->ms[0] = be::last_prune_ms();
+#endif
+  // the texts, on the host. No kernel formed an address from a label: they are checked here, before they index the alphabet.
+  for (int64_t k = 0; k < NT; ++k)
+    if (res->label[(size_t)k] < 0 || res->label[(size_t)k] >= tc.V || res->label[(size_t)k] == tc.blank)
+      return fail(CTCDEC_ERR_INTERNAL, "greedy decode: a token's label is outside the alphabet");
+  const GreedyWords words(dec->alpha);
+  for (size_t u = 0; u < n; ++u) {
+    words.append_text(res->label.data() + res->tok_off[u], res->tok_off[u + 1] - res->tok_off[u], res->texts);
+    res->text_off[u + 1] = (int64_t)res->texts.size();
+  }
+  return CTCDEC_OK;
+}
+
+extern "C" {
+
+int ctcdec_greedy_batch(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts, int32_t dtype,
+                        int32_t is_device, int32_t fold, ctcdec_greedy** out) {
+  TranscriptCall tc;
+  const bool args_ok = dec && out && n_utts >= 0 && (n_utts == 0 || (utt_logits && utt_frames));
+  if (int rc = transcript_open(dec, args_ok, dtype, bad_fold(fold), tc)) return rc;
+  for (int32_t u = 0; u < n_utts; ++u) {
+    if (utt_frames[u] < 0) return fail(CTCDEC_ERR_ARG, "utterance " + std::to_string(u) + ": negative frame count");
+    if (utt_frames[u] > 0 && !utt_logits[u]) return fail(CTCDEC_ERR_ARG, "utterance " + std::to_string(u) + ": no logits");
+  }
+  const auto t_begin = Clock::now();
+  std::unique_ptr<ctcdec_greedy> res;
+  if (int rc = greedy_call(dec, tc, utt_logits, utt_frames, n_utts, dtype, is_device, fold, res)) return rc;
+  res->ms[3] = ms(t_begin, Clock::now());
+  *out = res.release();
+  return CTCDEC_OK;
+}
+
+int ctcdec_greedy_texts(const ctcdec_greedy* g, const char** blob_out, const int64_t** off_out, int64_t* n_utts_out) {
+  if (!g || !blob_out || !off_out || !n_utts_out) return fail(CTCDEC_ERR_ARG, "no greedy result");
+  *blob_out = g->texts.data();
+  *off_out = g->text_off.data();
+  *n_utts_out = (int64_t)g->text_off.size() - 1;
+  return CTCDEC_OK;
+}
+
+int ctcdec_greedy_tokens(const ctcdec_greedy* g, const int64_t** tok_off_out, const int32_t** label_out, const int32_t** start_out,
+                         const int32_t** end_out, const double** logp_out, int64_t* n_tokens_out) {
+  if (!g || !tok_off_out || !label_out || !start_out || !end_out || !logp_out || !n_tokens_out) return fail(CTCDEC_ERR_ARG, "no greedy result");
+  *tok_off_out = g->tok_off.data();
+  *label_out = g->label.data();
+  *start_out = g->start.data();
+  *end_out = g->end.data();
+  *logp_out = g->has_fold ? g->logp.data() : nullptr;
+  *n_tokens_out = (int64_t)g->label.size();
+  return CTCDEC_OK;
+}
+
+int ctcdec_greedy_scores(const ctcdec_greedy* g, const double** score_out, int64_t* n_utts_out) {
+  if (!g || !score_out || !n_utts_out) return fail(CTCDEC_ERR_ARG, "no greedy result");
+  *score_out = g->has_fold ? g->score.data() : nullptr;
+  *n_utts_out = (int64_t)g->tok_off.size() - 1;
+  return CTCDEC_OK;
+}
+
+int ctcdec_greedy_timing(const ctcdec_greedy* g, double* ms4, int32_t* launches_out, double* lse_ms_out) {
+  if (!g || !ms4) return fail(CTCDEC_ERR_ARG, "no greedy result");
+  for (int k = 0; k < 4; ++k) ms4[k] = g->ms[k];
+  if (launches_out) *launches_out = g->launches;
+  if (lse_ms_out) *lse_ms_out = g->lse_ms;
+  return CTCDEC_OK;
+}
+
+void ctcdec_greedy_free(ctcdec_greedy* g) { delete g; }
+
 }  // extern "C"
 
 // Everything ctcdec_score_batch indexes with comes from the caller: checked here, in the order in which one array bounds the

@@ -313,14 +313,27 @@ struct ViterbiGapsArgs {
   double clip_lo;      // ln(MIN_TOKEN_CLIP_P)
 };
 int launch_ctc_viterbi_gaps(const ViterbiGapsArgs& a, std::string* err);
+// Greedy decode. row_argmax: every row's most probable label -- the smallest index of the row's largest entry that is not a
+// NaN, `blank` for a row without an entry above -inf -- in arg[n_rows]; utt_is_prob and lse are not used. row_lse_argmax:
+// row_lse_max (the same bits in a.lse and rmax) that also stores row_argmax's label. greedy_collapse: one wavefront per
+// utterance, a count pass or a write pass (GreedyArgs)
+int launch_row_argmax(const RowLseArgs& a, int32_t* arg, int blank, std::string* err);
+int launch_row_lse_argmax(const RowLseArgs& a, double* rmax, int32_t* arg, int blank, std::string* err);
+int launch_greedy_collapse(const GreedyArgs& a, std::string* err);
 // kernel times (HIP events) of the launches of one of these kernels since the last reset; waits for the kernels.
-// ctc_forward and ctc_forward_wave share a log, as do ctc_find and ctc_find_wave.
-enum AlignKernel { K_ROW_LSE, K_VITERBI, K_FORWARD, K_POSTERIORS, K_GRAD_ROWS, K_FIND, K_ROW_LSE_MAX, K_VITERBI_GAPS, ALIGN_KERNELS };
+// ctc_forward and ctc_forward_wave share a log, as do ctc_find and ctc_find_wave, and greedy_collapse's two passes.
+enum AlignKernel {
+  K_ROW_LSE, K_VITERBI, K_FORWARD, K_POSTERIORS, K_GRAD_ROWS, K_FIND, K_ROW_LSE_MAX, K_VITERBI_GAPS, K_ROW_ARGMAX, K_ROW_LSE_ARGMAX,
+  K_GREEDY_COLLAPSE, ALIGN_KERNELS
+};
 void align_timing_reset();
 double align_kernel_ms(AlignKernel kind);
 
 // stage timing (ms) of the last launch_prune / launch_beam pair, measured on the decode stream
 void last_timing(double* prune_ms, double* beam_ms);
+// the frame-prune kernels of the last launch_prune sequence alone, whether or not a beam launch followed it (last_timing
+// reports a pair, and 0 for both until a beam launch has completed it); waits for the kernels
+double last_prune_ms();
 // which beam kernel the last launch_beam used: 1 = one wave per utterance (beam_wave.h), 2 = one workgroup
 // per utterance (beam_core.h), 0 = none yet
 int last_beam_kernel();

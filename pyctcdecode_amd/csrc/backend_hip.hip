@@ -5,7 +5,7 @@
 // beam_group_hip.hip (the two beam kernels), ctc_align_hip.hip (the transcript kernels); what is left here, top to bottom:
 //
 //   init, bind_thread, alloc*, h2d*, d2h*, d2d, zero, sync     device, streams, memory, copies
-//   last_timing                                                prune and beam stage times from g_ev[0..2]
+//   last_timing, last_prune_ms                                 prune and beam stage times from g_ev[0..2]
 //   launch_prune, launch_sniff_exact                           fronts of frame_prune_hip.hip: they record g_ev[0] / g_ev[1]
 //   assemble_texts                                             decode_batch's texts on the device (text_wave.h), a wave per utterance
 //   utt_weigh, utt_place                                       the wave kernel's launch order and per-utterance weights
@@ -152,6 +152,12 @@ void last_timing(double* prune_ms, double* beam_ms) {
   if (hipEventSynchronize(g_ev[2]) != hipSuccess) return;
   if (hipEventElapsedTime(&a, g_ev[0], g_ev[1]) == hipSuccess) *prune_ms = a;
   if (hipEventElapsedTime(&b, g_ev[1], g_ev[2]) == hipSuccess) *beam_ms = b;
+}
+
+double last_prune_ms() {
+  float ms = 0.f;
+  if (!g_ev[1] || hipEventSynchronize(g_ev[1]) != hipSuccess) return 0.0;
+  return hipEventElapsedTime(&ms, g_ev[0], g_ev[1]) == hipSuccess ? (double)ms : 0.0;
 }
 
 // Frame prune: the kernels and the choice among them live in frame_prune_hip.hip; the decode stream and the stage's two timing
@@ -567,6 +573,14 @@ int launch_row_lse_max_on(const RowLseArgs& a, double* rmax, hipStream_t stream,
 int launch_row_lse_max(const RowLseArgs& a, double* rmax, std::string* err) { return launch_row_lse_max_on(a, rmax, g_stream, err); }
 int launch_ctc_viterbi_gaps_on(const ViterbiGapsArgs& a, hipStream_t stream, std::string* err);
 int launch_ctc_viterbi_gaps(const ViterbiGapsArgs& a, std::string* err) { return launch_ctc_viterbi_gaps_on(a, g_stream, err); }
+int launch_row_argmax_on(const RowLseArgs& a, int32_t* arg, int blank, hipStream_t stream, std::string* err);
+int launch_row_argmax(const RowLseArgs& a, int32_t* arg, int blank, std::string* err) { return launch_row_argmax_on(a, arg, blank, g_stream, err); }
+int launch_row_lse_argmax_on(const RowLseArgs& a, double* rmax, int32_t* arg, int blank, hipStream_t stream, std::string* err);
+int launch_row_lse_argmax(const RowLseArgs& a, double* rmax, int32_t* arg, int blank, std::string* err) {
+  return launch_row_lse_argmax_on(a, rmax, arg, blank, g_stream, err);
+}
+int launch_greedy_collapse_on(const GreedyArgs& a, hipStream_t stream, std::string* err);
+int launch_greedy_collapse(const GreedyArgs& a, std::string* err) { return launch_greedy_collapse_on(a, g_stream, err); }
 
 // Survivor ledger, append (surv_ledger.h): one wavefront per stream. A step takes 64 of the chunk's rows, one per lane: the
 // clamped counts are scanned across the wave (DPP, no LDS, no barrier), the running offset of the stream is wave-uniform and

@@ -9,6 +9,8 @@
 //   ctc_grad_row                   the gradient of the likelihood, row by row   (ctc_grad_rows)
 //   ctc_find_phrase / _wave_phrase a phrase's occurrences, free start and end   (ctc_find / ctc_find_wave)
 //   ctc_viterbi_gaps_utt           the best path of a target with gaps          (ctc_viterbi_gaps)
+//   row_argmax_seq                 a row's most probable label: the simulator's; the kernels fold by lanes
+//   greedy_collapse_utt            runs of frame labels to tokens               (greedy_collapse)
 // The shared pieces, and who uses them:
 //   viterbi_backtrace, fold_token_logp                   ctc_viterbi, ctc_viterbi_gaps
 //   group_setup, EntrySource, FrameEntries               ctc_find, ctc_find_wave, ctc_viterbi_gaps
@@ -1308,6 +1310,119 @@ CTC_HD void ctc_viterbi_gaps_utt(Ctx& cx, const GapsUtt& utt, int V, int blank, 
     utt.gap_logp[j] = acc;
   }
   if (fold) fold_token_logp(cx, x, DT, lse, lab, utt.tok_start, utt.tok_end, utt.tok_logp, T, L, V, is_prob, fold, clip_lo);
+}
+
+// ---- row_argmax / row_lse_argmax / greedy_collapse ---------------------------------------------------------------------------
+// Greedy best-path decoding ("Greedy decode"): every frame takes its most probable label, runs of one label are one
+// token, blanks separate tokens and are dropped.
+
+// What a lane knows of a row: its largest entry that is not a NaN and the smallest index that holds it (ARG_NONE: no entry
+// above -inf so far). Two of them merge by (value, index), so the result does not depend on which lane folded which entry.
+constexpr int32_t ARG_NONE = 0x7FFFFFFF;
+template <class VT>
+CTC_HD void arg_merge(VT& v, int32_t& i, VT ov, int32_t oi) {
+  if (ov > v || (ov == v && oi < i)) v = ov, i = oi;
+}
+
+// One row, one thread (the simulator): the smallest index among the entries equal to the row's largest entry that is not a
+// NaN; the blank for a row without an entry above -inf. Compares alone: -0.0 and +0.0 are equal, a NaN is never greater.
+CTC_HD int32_t row_argmax_seq(const void* x, int dtype, size_t row0, int V, int blank) {
+  double m = align_neg_inf();
+  int32_t arg = ARG_NONE;
+  for (int i = 0; i < V; ++i) {
+    const double v = align_load(x, dtype, row0 + (size_t)i);
+    if (v > m) m = v, arg = i;
+  }
+  return arg == ARG_NONE ? blank : arg;
+}
+
+// One greedy_collapse launch: utterance u's frame labels are arg[row0[u] .. row0[u + 1]). The count pass (write == 0) leaves
+// the utterance's number of tokens in count[u]; the host scans the counts into tok_off, and the write pass puts token k of
+// utterance u at tok_off[u] + k of label / start / end -- compact across the batch. With a fold the write pass also sums
+// e(t) = align_emit_of_value(rmax[t], lse[t], ...) over all frames into score[u] and folds it over each token's frames.
+struct GreedyArgs {
+  const int32_t* arg;        // [n_rows] every row's label
+  const int64_t* row0;       // [n_utts + 1]
+  const int64_t* tok_off;    // [n_utts + 1] (write pass)
+  int32_t* count;            // [n_utts] out (count pass)
+  int32_t* label;            // [n_tokens] out (write pass), like start and end
+  int32_t* start;
+  int32_t* end;              // one past the token's last frame
+  const double* lse;         // [n_rows] (fold) row log-sum-exps of the logit utterances
+  const double* rmax;        // [n_rows] (fold) every row's largest entry that is not a NaN
+  const uint32_t* is_prob;   // [n_utts] (fold)
+  double* logp;              // [n_tokens] out (fold)
+  double* score;             // [n_utts] out (fold)
+  int32_t n_utts, blank, fold, write;
+  double clip_lo;
+};
+
+// One utterance by the lanes of cx, which take lanes() frames a step, lane l the frame t0 + l: lane(), lanes(), up(v) / down(v)
+// (the neighbour lane's v; the lane's own at the edge), first(v) / last(v) (the first / last lane's v), ballot(b) (bit l: lane
+// l's b) and publish() (this wave's stores, visible to its loads). A frame past the end reads as a blank, like the frame
+// before the first. A run starts where the label is no blank and differs from the frame before, and ends where it differs
+// from the frame after: the ballots of both give each token's ordinal by a count of the bits below the lane's.
+CTC_HD int32_t greedy_popcount(uint64_t bits) { return (int32_t)__builtin_popcountll(bits); }
+template <class Ctx>
+CTC_HD void greedy_collapse_utt(Ctx& cx, const GreedyArgs& a, int u) {
+  const int64_t r0 = a.row0[u];
+  const int T = (int)(a.row0[u + 1] - r0);
+  const int32_t* arg = a.arg + r0;
+  const int W = cx.lanes(), lane = cx.lane(), blank = a.blank;
+  const bool write = a.write != 0;
+  const int64_t o = write ? a.tok_off[u] : 0;
+  const uint64_t below = ((uint64_t)1 << lane) - 1;
+  int32_t n_start = 0, n_end = 0;
+  int32_t before = blank;  // the label of the frame before the step's first
+  int32_t cur = lane < T ? arg[lane] : blank;
+  for (int t0 = 0; t0 < T; t0 += W) {
+    const int t = t0 + lane;
+    const int32_t next = (int64_t)t + W < T ? arg[t + W] : blank;  // (the step after this one)
+    int32_t left = cx.up(cur), right = cx.down(cur);
+    const int32_t after = cx.first(next);
+    if (lane == 0) left = before;
+    if (lane == W - 1) right = after;
+    const bool starts = cur != blank && cur != left, ends = cur != blank && cur != right;
+    const uint64_t bs = cx.ballot(starts), be = cx.ballot(ends);
+    if (write && starts) {
+      const int64_t k = o + n_start + greedy_popcount(bs & below);
+      a.label[k] = cur;
+      a.start[k] = t;
+    }
+    if (write && ends) a.end[o + n_end + greedy_popcount(be & below)] = t + 1;
+    n_start += greedy_popcount(bs);
+    n_end += greedy_popcount(be);
+    before = cx.last(cur);
+    cur = next;
+  }
+  if (!write) {
+    if (lane == 0) a.count[u] = n_start;
+    return;
+  }
+  if (!a.fold) return;
+  cx.publish();  // (the spans: stored by the lanes that met them, loaded by the lanes the tokens are dealt to)
+  const bool is_prob = a.is_prob[u] != 0;
+  const double* lse = a.lse + r0;
+  const double* rmax = a.rmax + r0;
+  const auto e = [&](int t) { return align_emit_of_value(rmax[t], is_prob ? 0.0 : lse[t], is_prob, a.clip_lo); };
+  if (lane == 0) {  // in frame order, as ctc_viterbi adds a path's frames
+    double acc = 0.0;
+    for (int t = 0; t < T; ++t) acc = t == 0 ? e(0) : acc + e(t);
+    a.score[u] = acc;
+  }
+  for (int k = lane; k < n_start; k += W) {  // fold_token_logp's fold, of e(t)
+    int t0 = a.start[o + k], t1 = a.end[o + k];
+    t0 = t0 < 0 ? 0 : t0;
+    t1 = t1 > T ? T : t1;
+    double acc = 0.0;
+    for (int t = t0; t < t1; ++t) {
+      const double lp = e(t);
+      if (a.fold == LOGP_MEAN) acc += lp;
+      else if (a.fold == LOGP_MIN) acc = (t == t0 || lp < acc) ? lp : acc;
+      else acc = (t == t0 || lp > acc) ? lp : acc;
+    }
+    a.logp[o + k] = a.fold == LOGP_MEAN ? acc / (double)(t1 - t0) : acc;
+  }
 }
 
 }  // namespace ctc

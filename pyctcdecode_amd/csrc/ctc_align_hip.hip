@@ -5,6 +5,8 @@
 //   ctc_find, ctc_viterbi_gaps        (256 threads up to 511 labels, 1024 above)
 //   ctc_forward_wave, ctc_find_wave a wavefront per record of at most 127 labels
 //   ctc_grad_rows                   G threads per row of a dense ctc_posteriors launch's tables
+//   row_argmax, row_lse_argmax      G lanes per row; both fold with row_fold_arg
+//   greedy_collapse                 a wavefront per utterance
 // The launchers share timed_launch (the event pair of the kernel's log and the launch's error), for_dtype and for_threads.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -334,6 +336,217 @@ __global__ __launch_bounds__(NT) void ctc_viterbi_gaps(ViterbiGapsArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// row_argmax, row_lse_argmax: every row's most probable label (ctc_align.h, "greedy_collapse"), in row_lse's row mapping and
+// with row_lse's loads. A lane keeps (largest entry that is not a NaN, smallest index of it) and the lanes' pairs are merged
+// by a butterfly of shuffles that compares (value, index): the label does not depend on which lane folded which entry.
+//   row_argmax       compares alone -- no exponential, no logarithm -- in the row's own format (float for f16 / bf16): the
+//                    largest logit of a row is its largest probability. ARGMAX_ROWS successive rows per group of lanes.
+//   row_lse_argmax   row_lse_max that also stores the label: next to the pair a lane runs row_fold's accumulator through
+//                    row_fold's operations in row_fold's order, so lse has row_lse's bits and rmax row_lse_max's.
+// ---------------------------------------------------------------------------------------------
+template <int DT, class VT>
+__device__ __forceinline__ void unpack16_as(const uint4 q, VT* out) {
+  if (DT == 0) {
+    out[0] = (VT)__uint_as_float(q.x);
+    out[1] = (VT)__uint_as_float(q.y);
+    out[2] = (VT)__uint_as_float(q.z);
+    out[3] = (VT)__uint_as_float(q.w);
+  } else if (DT == 1) {
+    out[0] = (VT)__hiloint2double((int)q.y, (int)q.x);
+    out[1] = (VT)__hiloint2double((int)q.w, (int)q.z);
+  } else {
+    const uint32_t w[4] = {q.x, q.y, q.z, q.w};
+    CTC_UNROLL
+    for (int k = 0; k < 4; ++k) {
+      const uint16_t lo = (uint16_t)(w[k] & 0xFFFFu), hi = (uint16_t)(w[k] >> 16);
+      out[2 * k] = (VT)(DT == 2 ? f16_bits_to_f32(lo) : bf16_bits_to_f32(lo));
+      out[2 * k + 1] = (VT)(DT == 2 ? f16_bits_to_f32(hi) : bf16_bits_to_f32(hi));
+    }
+  }
+}
+template <int DT, class VT>
+__device__ __forceinline__ VT load_as(const char* p, size_t i) {
+  if (DT == 0) return (VT)((const float*)p)[i];
+  if (DT == 1) return (VT)((const double*)p)[i];
+  const uint16_t h = ((const uint16_t*)p)[i];
+  return (VT)(DT == 2 ? f16_bits_to_f32(h) : bf16_bits_to_f32(h));
+}
+
+enum { ARG_ONLY = 0, ARG_MAX = 1, ARG_LSE = 2 };  // what row_fold_arg keeps next to the label: nothing, row_fold<MAX_ONLY>'s or row_fold's accumulator
+
+// One row's label by its G lanes, lane l: ARG_NONE for a row without an entry above -inf. With ARG_MAX / ARG_LSE `acc` ends
+// as row_fold<G, DT, true / false> leaves it -- the same values through the same operations.
+template <int G, int DT, int MODE>
+__device__ __forceinline__ int32_t row_fold_arg(const char* p, int V, int l, LseAcc& acc) {
+  typedef typename std::conditional<MODE == ARG_ONLY && DT != 1, float, double>::type VT;
+  constexpr int ESZ = DT == 0 ? 4 : DT == 1 ? 8 : 2;      // bytes per element
+  constexpr int EPV = 16 / ESZ;                           // elements per 16-byte vector
+  constexpr int VPB = MODE == ARG_ONLY ? 4 : ALIGN_LSE_BLOCK / EPV;  // vectors per block of values (row_fold's where acc is kept)
+  constexpr int BLOCK = VPB * EPV;
+  const VT NEG = (VT)align_neg_inf();
+  const bool vec = ((uintptr_t)p & 15u) == 0;
+  const int nvec = V / EPV, tail = nvec * EPV;
+  acc = lse_empty();
+  // the left-over elements: the row's highest indices, ascending in a lane
+  VT tv = NEG;
+  int32_t ti = ARG_NONE;
+  for (int i = tail + l; i < V; i += G) {
+    const VT v = load_as<DT, VT>(p, (size_t)i);
+    if (v > tv) tv = v, ti = i;
+    if constexpr (MODE == ARG_MAX) acc.m = v > acc.m ? v : acc.m;
+    else if constexpr (MODE == ARG_LSE) lse_push(acc, v);
+  }
+  // the vectors: ascending indices in a lane, all below the left-over ones
+  VT bv = NEG;
+  int32_t bi = ARG_NONE;
+  const uint4* pv = (const uint4*)p;
+  for (int base = 0; base < nvec; base += G * VPB) {
+    VT v[BLOCK];
+    CTC_UNROLL
+    for (int j = 0; j < VPB; ++j) {
+      const int i = base + j * G + l;  // (neighbouring lanes, neighbouring 16-byte groups)
+      if (i >= nvec) {
+        CTC_UNROLL
+        for (int k = 0; k < EPV; ++k) v[j * EPV + k] = NEG;
+      } else if (vec) {
+        unpack16_as<DT, VT>(pv[i], v + j * EPV);
+      } else {
+        CTC_UNROLL
+        for (int k = 0; k < EPV; ++k) v[j * EPV + k] = load_as<DT, VT>(p, (size_t)i * EPV + (size_t)k);
+      }
+    }
+    if constexpr (MODE == ARG_ONLY) {
+      CTC_UNROLL
+      for (int j = 0; j < VPB; ++j) {
+        const int i0 = (base + j * G + l) * EPV;
+        CTC_UNROLL
+        for (int k = 0; k < EPV; ++k)
+          if (v[j * EPV + k] > bv) bv = v[j * EPV + k], bi = i0 + k;  // (a slot past the row holds -inf: never greater)
+      }
+    } else {
+      // Next to the exponentials the index costs a branch per block: the block's maximum -- which lse_push_block forms
+      // anyway -- seldom beats the lane's, and only then is the block searched, from its end, for the first entry equal to it.
+      VT bm = NEG;
+      CTC_UNROLL
+      for (int i = 0; i < BLOCK; ++i) bm = v[i] > bm ? v[i] : bm;
+      if (bm > bv) {
+        bv = bm;
+        CTC_UNROLL
+        for (int j = VPB - 1; j >= 0; --j) {
+          const int i0 = (base + j * G + l) * EPV;
+          CTC_UNROLL
+          for (int k = EPV - 1; k >= 0; --k)
+            if (v[j * EPV + k] == bm) bi = i0 + k;
+        }
+      }
+    }
+    if constexpr (MODE == ARG_MAX) {
+      CTC_UNROLL
+      for (int i = 0; i < BLOCK; ++i) acc.m = v[i] > acc.m ? v[i] : acc.m;
+    } else if constexpr (MODE == ARG_LSE) {
+      lse_push_block(acc, v);
+    }
+  }
+  arg_merge(bv, bi, tv, ti);
+  CTC_UNROLL
+  for (int off = G / 2; off >= 1; off >>= 1) {
+    arg_merge(bv, bi, (VT)__shfl_xor(bv, off, G), (int32_t)__shfl_xor(bi, off, G));
+    if constexpr (MODE != ARG_ONLY) {
+      LseAcc o;
+      o.m = __shfl_xor(acc.m, off, G);
+      o.s = __shfl_xor(acc.s, off, G);
+      if constexpr (MODE == ARG_MAX) acc.m = o.m > acc.m ? o.m : acc.m;
+      else acc = lse_merge(acc, o);
+    }
+  }
+  return bi;
+}
+
+// The utterance that holds `row`: utt_row0[lo] <= row < utt_row0[lo + 1]
+__device__ __forceinline__ int row_utt(const int64_t* utt_row0, int n_utts, int64_t row) {
+  int lo = 0, hi = n_utts;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (utt_row0[mid] <= row) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
+constexpr int ARGMAX_ROWS = 4;  // successive rows a group of lanes takes in row_argmax
+
+template <int G, int DT>
+__global__ __launch_bounds__(256) void row_argmax(RowLseArgs a, int32_t* arg, int blank) {
+  constexpr int RPB = 256 / G;                            // groups of lanes per workgroup
+  constexpr int ESZ = DT == 0 ? 4 : DT == 1 ? 8 : 2;
+  const int64_t first = ((int64_t)blockIdx.x * RPB + (int)(threadIdx.x / G)) * ARGMAX_ROWS;
+  const int l = (int)(threadIdx.x % G);
+  if (first >= a.n_rows) return;  // (the whole group of lanes: its rows are theirs alone)
+  const int V = a.n_labels;
+  int u = row_utt(a.utt_row0, a.n_utts, first);
+  for (int r = 0; r < ARGMAX_ROWS; ++r) {
+    const int64_t row = first + r;
+    if (row >= a.n_rows) return;
+    while (row >= a.utt_row0[u + 1]) ++u;  // (row < n_rows = utt_row0[n_utts]: ends inside the array)
+    const char* p = (const char*)a.utt_logits[u] + (size_t)(row - a.utt_row0[u]) * (size_t)V * ESZ;
+    LseAcc unused;
+    const int32_t i = row_fold_arg<G, DT, ARG_ONLY>(p, V, l, unused);
+    if (l == 0) arg[row] = i == ARG_NONE ? blank : i;
+  }
+}
+
+template <int G, int DT>
+__global__ __launch_bounds__(256) void row_lse_argmax(RowLseArgs a, double* rmax, int32_t* arg, int blank) {
+  constexpr int RPB = 256 / G;                            // rows per workgroup
+  constexpr int ESZ = DT == 0 ? 4 : DT == 1 ? 8 : 2;
+  const int64_t row = (int64_t)blockIdx.x * RPB + (int)(threadIdx.x / G);
+  const int l = (int)(threadIdx.x % G);
+  if (row >= a.n_rows) return;
+  const int u = row_utt(a.utt_row0, a.n_utts, row);
+  const int V = a.n_labels;
+  const char* p = (const char*)a.utt_logits[u] + (size_t)(row - a.utt_row0[u]) * (size_t)V * ESZ;
+  LseAcc acc;
+  if (a.utt_is_prob[u]) {  // (the whole group of lanes: `row` is theirs alone)
+    const int32_t i = row_fold_arg<G, DT, ARG_MAX>(p, V, l, acc);
+    if (l == 0) {
+      rmax[row] = acc.m;
+      arg[row] = i == ARG_NONE ? blank : i;
+    }
+    return;
+  }
+  const int32_t i = row_fold_arg<G, DT, ARG_LSE>(p, V, l, acc);
+  if (l == 0) {
+    a.lse[row] = lse_value(acc);
+    rmax[row] = acc.m;
+    arg[row] = i == ARG_NONE ? blank : i;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// greedy_collapse: a wavefront per utterance, four to a workgroup that never synchronises; a step takes 64 frames, one to a
+// lane. The neighbours' labels come by shuffles, a token's ordinal by the ballots of "a run starts / ends here"; no LDS, no
+// atomics (ctc_align.h)
+// ---------------------------------------------------------------------------------------------
+struct GreedyWaveCtx {
+  int lane_;
+  __device__ __forceinline__ int lane() const { return lane_; }
+  __device__ __forceinline__ int lanes() const { return 64; }
+  __device__ __forceinline__ int32_t up(int32_t v) const { return __shfl_up(v, 1, 64); }
+  __device__ __forceinline__ int32_t down(int32_t v) const { return __shfl_down(v, 1, 64); }
+  __device__ __forceinline__ int32_t first(int32_t v) const { return __shfl(v, 0, 64); }
+  __device__ __forceinline__ int32_t last(int32_t v) const { return __shfl(v, 63, 64); }
+  __device__ __forceinline__ uint64_t ballot(bool b) const { return __ballot(b ? 1 : 0); }
+  __device__ __forceinline__ void publish() const { __threadfence_block(); }
+};
+
+__global__ __launch_bounds__(ALIGN_THREADS) void greedy_collapse(GreedyArgs a) {
+  const int u = (int)blockIdx.x * FORWARD_WAVES + (int)(threadIdx.x >> 6);
+  if (u >= a.n_utts) return;  // (a whole wave: nothing in this kernel waits for another wave)
+  GreedyWaveCtx cx{(int)(threadIdx.x & 63u)};
+  greedy_collapse_utt(cx, a, u);
+}
+
+// ---------------------------------------------------------------------------------------------
 // launches. Every launcher validates its arguments, then makes one timed_launch: the kernel's instantiation is picked by
 // for_dtype (ctc_align.h) and, where the kernel has two sizes, for_threads; the row kernels' lanes per row by for_row_lanes.
 // ---------------------------------------------------------------------------------------------
@@ -423,6 +636,45 @@ int launch_row_lse_max_on(const RowLseArgs& a, double* rmax, hipStream_t stream,
         hipLaunchKernelGGL((row_lse_max<G, DT>), row_grid<G>(a.n_rows), dim3(256), 0, stream, a, rmax);
       });
     });
+  });
+}
+
+// (ARGMAX_ROWS rows to a group of lanes)
+int launch_row_argmax_on(const RowLseArgs& a, int32_t* arg, int blank, hipStream_t stream, std::string* err) {
+  if (a.n_rows <= 0 || a.n_utts <= 0) return 0;
+  if (a.dtype < 0 || a.dtype > 3 || a.n_labels < 1 || a.n_rows > (int64_t)0x7FFFFFFF * 4 || !arg || blank < 0 || blank >= a.n_labels)
+    return bad_launch(err, "row_argmax: bad arguments");
+  return timed_launch(K_ROW_ARGMAX, stream, err, [&] {
+    for_row_lanes(a.n_labels, [&](auto g) {
+      for_dtype(a.dtype, [&](auto dt) {
+        constexpr int G = decltype(g)::value, DT = decltype(dt)::value;
+        hipLaunchKernelGGL((row_argmax<G, DT>), row_grid<G>((a.n_rows + ARGMAX_ROWS - 1) / ARGMAX_ROWS), dim3(256), 0, stream, a, arg, blank);
+      });
+    });
+  });
+}
+
+int launch_row_lse_argmax_on(const RowLseArgs& a, double* rmax, int32_t* arg, int blank, hipStream_t stream, std::string* err) {
+  if (a.n_rows <= 0 || a.n_utts <= 0) return 0;
+  if (a.dtype < 0 || a.dtype > 3 || a.n_labels < 1 || a.n_rows > (int64_t)0x7FFFFFFF * 4 || !rmax || !arg || blank < 0 || blank >= a.n_labels)
+    return bad_launch(err, "row_lse_argmax: bad arguments");
+  return timed_launch(K_ROW_LSE_ARGMAX, stream, err, [&] {
+    for_row_lanes(a.n_labels, [&](auto g) {
+      for_dtype(a.dtype, [&](auto dt) {
+        constexpr int G = decltype(g)::value, DT = decltype(dt)::value;
+        hipLaunchKernelGGL((row_lse_argmax<G, DT>), row_grid<G>(a.n_rows), dim3(256), 0, stream, a, rmax, arg, blank);
+      });
+    });
+  });
+}
+
+int launch_greedy_collapse_on(const GreedyArgs& a, hipStream_t stream, std::string* err) {
+  if (a.n_utts <= 0) return 0;
+  if (!a.arg || !a.row0 || (a.write ? !a.tok_off || !a.label || !a.start || !a.end : !a.count) ||
+      (a.write && a.fold && (!a.lse || !a.rmax || !a.is_prob || !a.logp || !a.score)))
+    return bad_launch(err, "greedy_collapse: bad arguments");
+  return timed_launch(K_GREEDY_COLLAPSE, stream, err, [&] {
+    hipLaunchKernelGGL(greedy_collapse, dim3((unsigned)((a.n_utts + FORWARD_WAVES - 1) / FORWARD_WAVES)), dim3(ALIGN_THREADS), 0, stream, a);
   });
 }
 

@@ -363,6 +363,51 @@ class TokenFrames:
         return TokenFrames, (self.label, self.start, self.end, self.offsets, self.labels, self.logp)
 
 
+class GreedyFrames(TokenFrames):
+    """The token frames of a decode_greedy_batch(..., token_frames=True) call: TokenFrames (the space label of a character
+    alphabet is no token) and ``score``, after decode_greedy_batch(..., confidence=...) a float64 ``[B]`` array -- per utterance
+    the sum, over all its frames, of the clipped log-probability of the frame's most probable label (GreedyText.score) --,
+    else None."""
+
+    __slots__ = ("score",)
+
+    def __init__(self, label: np.ndarray, start: np.ndarray, end: np.ndarray, offsets: np.ndarray, labels: Sequence[str],
+                 logp: Optional[np.ndarray] = None, score: Optional[np.ndarray] = None):
+        super().__init__(label, start, end, offsets, labels, logp)
+        self.score = score
+
+    @classmethod
+    def join(cls, parts: Sequence["GreedyFrames"], labels: Sequence[str]) -> "GreedyFrames":
+        """The parts of consecutive slices of a batch as one (offsets rebased)."""
+        tf = TokenFrames.join(parts, labels)
+        score = None
+        if parts and all(t.score is not None for t in parts):
+            score = np.concatenate([t.score for t in parts])
+        return cls(tf.label, tf.start, tf.end, tf.offsets, labels, tf.logp, score)
+
+    def __reduce__(self):
+        return GreedyFrames, (self.label, self.start, self.end, self.offsets, self.labels, self.logp, self.score)
+
+
+@dataclasses.dataclass(frozen=True)
+class GreedyText:
+    """The best path over all texts (BeamSearchDecoderCTC.decode_greedy; DESIGN.md, "Greedy decode"): every frame takes its
+    most probable label, runs of a label are one token, blanks separate tokens. ``tokens`` are the tokens' label ids -- the
+    space label of a character alphabet among them: align(logits, tokens=tokens) is the same path --; ``text``,
+    ``token_frames``, ``text_frames``, ``token_logp`` and ``word_logp`` are AlignedText's, for those ids. ``score`` (with
+    ``confidence=...``, like ``token_logp`` and ``word_logp``; else None) is the sum over ALL frames of the clipped
+    log-probability of the frame's label: what align and align_gaps give for this path, and the upper bound of every
+    alignment of the utterance."""
+
+    text: str
+    tokens: List[int]
+    token_frames: List[Tuple[str, Frames]]
+    text_frames: List[WordFrames]
+    token_logp: Optional[List[float]] = None
+    word_logp: Optional[List[float]] = None
+    score: Optional[float] = None
+
+
 _LM_BEAM_FIELDS = dataclasses.fields(LMBeam)
 NULL_FRAMES: Frames = (-1, -1)
 EMPTY_START_BEAM = Beam("", "", "", None, [], NULL_FRAMES, 0.0)
@@ -1226,6 +1271,12 @@ class BeamSearchDecoderCTC:
         # call; kernel launches made)
         self.last_align_gaps_timing_ms = (0.0, 0.0, 0.0, 0.0)
         self.last_align_gaps_launches = 0
+        # ... and of the last decode_greedy / decode_greedy_batch call (ms: classification, row_argmax or row_lse_argmax,
+        # greedy_collapse, native call; kernel launches made; the part of the row kernel's time that a kernel with a
+        # log-sum-exp took: 0 without confidence=...)
+        self.last_greedy_timing_ms = (0.0, 0.0, 0.0, 0.0)
+        self.last_greedy_launches = 0
+        self.last_greedy_lse_ms = 0.0
 
     def __del__(self):
         h = getattr(self, "_handle", None)
@@ -1998,6 +2049,110 @@ class BeamSearchDecoderCTC:
                                          wf, list(zip(g_start[g0:g1], g_end[g0:g1])), g_logp[g0:g1], tlp if fold else None,
                                          wlp if fold else None)
             return out
+
+    # -- greedy decode (no reference analogue; DESIGN.md, "Greedy decode") ---------------------------------
+    def _greedy_call(self, logits_list: Any, fold: int):
+        """-> (texts, offsets, label, start, end, logp, score): one ctcdec_greedy_batch call's results copied out -- every
+        token of every utterance (the space label of a character alphabet included) as arrays, utterance u's at
+        ``[offsets[u], offsets[u + 1])``; ``logp`` and ``score`` are None without a fold."""
+        with self._call_lock:
+            batch, frames, ptrs = self._stage_transcript_call(logits_list)
+            n = len(frames)
+            res = C.c_void_p()
+            lib = self._lib
+            lib.check(lib.dll.ctcdec_greedy_batch(
+                self._handle, ptrs.ctypes.data_as(C.POINTER(C.c_void_p)), frames.ctypes.data_as(C.POINTER(C.c_int32)), n,
+                batch.dtype, int(batch.is_device), fold, C.byref(res)))
+            try:
+                blob_p, off_p, nu = C.c_void_p(), C.POINTER(C.c_int64)(), C.c_int64()
+                lib.check(lib.dll.ctcdec_greedy_texts(res, C.byref(blob_p), C.byref(off_p), C.byref(nu)))
+                to, tl, ts, te, tp, nt = (C.POINTER(C.c_int64)(), C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)(),
+                                          C.POINTER(C.c_int32)(), C.POINTER(C.c_double)(), C.c_int64())
+                lib.check(lib.dll.ctcdec_greedy_tokens(res, C.byref(to), C.byref(tl), C.byref(ts), C.byref(te), C.byref(tp),
+                                                       C.byref(nt)))
+                sp, ns = C.POINTER(C.c_double)(), C.c_int64()
+                lib.check(lib.dll.ctcdec_greedy_scores(res, C.byref(sp), C.byref(ns)))
+                if int(nu.value) != n or int(ns.value) != n:
+                    raise B.NativeError("the greedy result holds another number of utterances than was asked for")
+                text_off = np.ctypeslib.as_array(off_p, shape=(n + 1,)).tolist()
+                blob = C.string_at(blob_p, text_off[n]) if text_off[n] else b""
+                if blob.isascii():  # byte offsets == character offsets: decode once, slice the str
+                    whole = blob.decode("ascii")
+                    texts = [whole[text_off[k]:text_off[k + 1]] for k in range(n)]
+                else:
+                    texts = [blob[text_off[k]:text_off[k + 1]].decode("utf-8") for k in range(n)]
+                offsets = np.ctypeslib.as_array(to, shape=(n + 1,)).copy()
+                ntok = int(nt.value)
+                if ntok != int(offsets[-1]):
+                    raise B.NativeError("the greedy result holds another number of tokens than its offsets say")
+                label, start, end = (np.ctypeslib.as_array(q, shape=(ntok,)).copy() if ntok else np.zeros(0, dtype=np.int32)
+                                     for q in (tl, ts, te))
+                logp = score = None
+                if fold:
+                    logp = np.ctypeslib.as_array(tp, shape=(ntok,)).copy() if ntok else np.zeros(0, dtype=np.float64)
+                    score = np.ctypeslib.as_array(sp, shape=(n,)).copy()
+                ms, launches, lse_ms = (C.c_double * 4)(), C.c_int32(), C.c_double()
+                lib.dll.ctcdec_greedy_timing(res, ms, C.byref(launches), C.byref(lse_ms))
+                # [classification (frame-prune kernels), row_argmax / row_lse_argmax, greedy_collapse (HIP events), native call]
+                self.last_greedy_timing_ms = tuple(float(v) for v in ms)
+                self.last_greedy_launches = int(launches.value)
+                self.last_greedy_lse_ms = float(lse_ms.value)
+            finally:
+                lib.dll.ctcdec_greedy_free(res)
+            return texts, offsets, label, start, end, logp, score
+
+    def decode_greedy_batch(self, logits_list: Any, token_frames: bool = False, confidence: Optional[str] = None) -> Any:
+        """Greedy best-path decoding of a batch in one native call, without the language model and without a search: every
+        frame takes its most probable label -- the smallest index of the row's largest entry that is not a NaN; the blank
+        for a row of NaN and -inf alone --, runs of a label are one token, blanks separate tokens and are dropped
+        (row_argmax + greedy_collapse, csrc/ctc_align_hip.hip: one read of the logits, compares only). ``logits_list`` is
+        what decode_batch takes. Returns the texts, formed as align_batch forms an AlignedText's; with ``token_frames=True``
+        ``(texts, GreedyFrames)``. ``confidence="mean" | "min" | "max"`` (implies token_frames) classifies the utterances as
+        align_batch does and adds the tokens' confidences and each utterance's ``score`` (row_lse_argmax instead of
+        row_argmax). There is no pool, sharded or streaming form: a DevicePool raises NotImplementedError."""
+        fold = _confidence_fold(confidence)
+        token_frames = bool(token_frames) or bool(fold)
+        if type(logits_list).__name__ == "DevicePool":
+            raise NotImplementedError("DevicePool does not shard decode_greedy_batch: call it on the process's own device")
+        if getattr(logits_list, "ndim", 0) != 3:
+            logits_list = list(logits_list)
+        if len(logits_list) == 0:
+            z = np.zeros(0, dtype=np.int32)
+            empty = GreedyFrames(z, z.copy(), z.copy(), np.zeros(1, dtype=np.int64), self._alphabet.labels,
+                                 np.zeros(0, dtype=np.float64) if fold else None, np.zeros(0, dtype=np.float64) if fold else None)
+            return ([], empty) if token_frames else []
+        texts, offsets, label, start, end, logp, score = self._greedy_call(logits_list, fold)
+        if not token_frames:
+            return texts
+        space = None if self._is_bpe else self._vocab2idx.get(" ")
+        if space is not None and len(label):  # (the space label ends a word: no token)
+            keep = label != space
+            offsets = np.concatenate([np.zeros(1, dtype=np.int64), np.cumsum(keep, dtype=np.int64)])[offsets]
+            label, start, end = label[keep], start[keep], end[keep]
+            logp = logp[keep] if logp is not None else None
+        return texts, GreedyFrames(label, start, end, offsets, self._alphabet.labels, logp, score)
+
+    def decode_greedy(self, logits: Any, token_frames: bool = False, confidence: Optional[str] = None) -> Any:
+        """Greedy best-path decoding of one utterance: its text, or with ``token_frames=True`` or ``confidence=...`` a
+        GreedyText (decode_greedy_batch of a batch of one; word frames and confidences built as align builds them)."""
+        self._check_logits_dimension(logits)
+        fold = _confidence_fold(confidence)
+        texts, offsets, label, start, end, logp, score = self._greedy_call([logits], fold)
+        if not (token_frames or fold):
+            return texts[0]
+        ids, start, end = label.tolist(), start.tolist(), end.tolist()
+        labels = self._labels_list
+        text, kept, words = self._words_of_target(ids)
+        if text != texts[0]:
+            raise B.NativeError("the native text %r differs from the text of the greedy labels %r" % (texts[0], text))
+        tok = [(labels[ids[k]], (start[k], end[k])) for k in kept]
+        wf = [(w, (tok[lo][1][0], tok[hi - 1][1][1])) for w, lo, hi in words]
+        tlp = wlp = None
+        if fold:
+            lp = logp.tolist()
+            tlp = [lp[k] for k in kept]
+            wlp = [min(tlp[lo:hi]) for _w, lo, hi in words]
+        return GreedyText(text, ids, tok, wf, tlp, wlp, float(score[0]) if fold else None)
 
     def _many_targets_each(self, what: str, item: str, items: str, logits_list: Any, texts, tokens):
         """The label ids of any number of given texts or token lists per utterance, checked: (logits_list, ids[u][j])."""

@@ -221,6 +221,11 @@ def align_gaps_batch_sharded(decoder, logits_list, texts=None, group=None, **kwa
     raise NotImplementedError("align_gaps_batch is not gathered over ranks: align each rank's slice with decoder.align_gaps_batch itself")
 
 
+def decode_greedy_batch_sharded(decoder, logits_list, group=None, **kwargs):
+    """Greedy decoding is not sharded over ranks: each rank calls decoder.decode_greedy_batch on its own slice."""
+    raise NotImplementedError("decode_greedy_batch is not gathered over ranks: decode each rank's slice with decoder.decode_greedy_batch itself")
+
+
 def _device_worker(conn, device: int, decoder_dir: str, library: Optional[str]) -> None:
     """One worker process = one GPU (the native library binds one device per process): loads the saved decoder on its device and
     serves (method, logits, kwargs) requests until it is told to stop."""
@@ -373,6 +378,12 @@ class DevicePool:
         raise NotImplementedError("DevicePool does not shard align_gaps_batch: call decoder.align_gaps_batch on the process's own device")
 
     align_gaps = align_gaps_batch
+
+    def decode_greedy_batch(self, logits_list, **kwargs):
+        """Greedy decoding runs on the calling process's own device: a pool does not shard it."""
+        raise NotImplementedError("DevicePool does not shard decode_greedy_batch: call decoder.decode_greedy_batch on the process's own device")
+
+    decode_greedy = decode_greedy_batch
 
     def decode_batch(self, logits_list, **kwargs) -> List[str]:
         if kwargs.get("token_frames") or kwargs.get("confidence") is not None:  # (texts, TokenFrames) per slice -> one of each, offsets rebased

@@ -6,7 +6,7 @@ substituted), each forward kernel forced in turn -- and at 64 utterances, with t
 for scale; then a sweep of target lengths on 256 utterances of random logits, which is what the wave / group threshold of
 ctcdec_score_batch rests on. Kernel times are HIP events on the decode stream (ctcdec_alignment_timing, ctcdec_score_batch,
 ctcdec_posteriors_timing).
-  python tools/align_bench.py [--out profiles/align_bench.txt] [--steps 3] [--legs align,score,posteriors,sweep,gradient,find,gaps]
+  python tools/align_bench.py [--out profiles/align_bench.txt] [--steps 3] [--legs align,score,posteriors,sweep,gradient,find,gaps,greedy]
 The gradient leg (not in the default set) times gradient_batch -- ctc_grad_rows alone, next to posteriors_batch(dense=False).
 The find leg (not in the default set either) times find_batch -- ctc_find / ctc_find_wave forced in turn, alternating: at the
 bench shape each utterance searched for 1 and for 8 phrases of 8 labels cut from its own decoded tokens, then 256 and 2048
@@ -14,6 +14,8 @@ phrases of 15 / 127 / 511 labels on 256 utterances of random logits, next to ctc
 The gaps leg (not in the default set either) times align_gaps_batch next to align_batch on the same batch, alternating:
 row_lse_max against row_lse, ctc_viterbi_gaps on the gap-free targets against ctc_viterbi on the same targets, and
 ctc_viterbi_gaps again with a leading gap, a trailing gap and one gap at every word boundary.
+The greedy leg (not in the default set either) times decode_greedy_batch: row_argmax, row_lse_argmax and greedy_collapse,
+next to row_lse_max and decode_batch's frame-prune stage on the same batch in the same rounds, alternating.
 The 4096 utterances are 256 distinct ones repeated: no kernel's time depends on the rows being distinct."""
 import argparse
 import os
@@ -273,6 +275,54 @@ def gaps_lines(dec, dev, targets, steps):
     return lines
 
 
+def greedy_lines(dec, dev, targets, n, steps):
+    """decode_greedy_batch without and with confidences, align_gaps_batch on the gap-free decoded targets (its row_lse_max is the
+    kernel row_lse_argmax adds an index to) and the plain decode_batch step (its frame-prune stage reads the same bytes), one
+    warm-up round and then `steps` alternating rounds: kernels alone (HIP events on the decode stream), the native calls and
+    the Python calls; medians, and the spread of the rounds for the two log-sum-exp kernels."""
+    some = next(c for c, lab in enumerate(dec._alphabet.labels) if lab != "")
+    targets = [list(t) if len(t) else [some] for t in targets]  # (align_gaps: a target needs a label)
+    got = {k: [] for k in ("argmax", "collapse", "native", "wall", "lse_argmax", "collapse_c", "native_c", "wall_c", "lse_max", "prune")}
+    tokens = 0
+    for step in range(steps + 1):
+        t0 = time.perf_counter()
+        texts = dec.decode_greedy_batch(dev)
+        wall = (time.perf_counter() - t0) * 1e3
+        ms = dec.last_greedy_timing_ms
+        assert ms[0] == 0.0 and dec.last_greedy_lse_ms == 0.0 and len(texts) == n
+        row = [("argmax", ms[1]), ("collapse", ms[2]), ("native", ms[3]), ("wall", wall)]
+        t0 = time.perf_counter()
+        _texts, frames = dec.decode_greedy_batch(dev, confidence="mean")
+        wall = (time.perf_counter() - t0) * 1e3
+        ms = dec.last_greedy_timing_ms
+        tokens = int(frames.offsets[-1])
+        assert _texts == texts and np.isfinite(frames.score).all()
+        row += [("lse_argmax", ms[1]), ("collapse_c", ms[2]), ("native_c", ms[3]), ("wall_c", wall)]
+        dec.align_gaps_batch(dev, tokens=targets)
+        row.append(("lse_max", dec.last_align_gaps_timing_ms[1]))
+        dec.decode_batch(None, dev)
+        row.append(("prune", dec.last_timing_ms[0]))
+        if step:
+            for k, v in row:
+                got[k].append(v)
+    m = lambda k: float(np.median(got[k]))  # noqa: E731
+    spread = lambda k: max(got[k]) - min(got[k])  # noqa: E731
+    read = n * T * V * 4
+    tbs = lambda ms: read / (ms * 1e-3) / 1e12  # noqa: E731
+    return [
+        "  greedy decode, %d tokens in all" % tokens,
+        "  row_argmax       %9.3f ms  (%.2f GB read: %.2f TB/s; frame_prune reaches %.1f TB/s on the same bytes, the chip streams about 6.3)"
+        % (m("argmax"), read / 1e9, tbs(m("argmax")), PRUNE_RATE / 1e12),
+        "  greedy_collapse  %9.3f ms  (count pass and write pass)   with confidences %9.3f ms" % (m("collapse"), m("collapse_c")),
+        "  decode_greedy_batch                    native call %9.3f ms  Python call %9.3f ms" % (m("native"), m("wall")),
+        "  row_lse_argmax   %9.3f ms  (%.2f TB/s)   row_lse_max %9.3f ms in the same rounds  (%.3f of it; spread of the rounds: "
+        "row_lse_argmax %.3f ms, row_lse_max %.3f ms)"
+        % (m("lse_argmax"), tbs(m("lse_argmax")), m("lse_max"), m("lse_argmax") / m("lse_max"), spread("lse_argmax"), spread("lse_max")),
+        "  decode_greedy_batch confidence='mean'  native call %9.3f ms  Python call %9.3f ms" % (m("native_c"), m("wall_c")),
+        "  decode_batch's frame-prune stage %9.3f ms in the same rounds  (%.2f TB/s)" % (m("prune"), tbs(m("prune"))),
+    ]
+
+
 def time_forward(dec, dev, hyps, kernels, steps):
     """The forward kernels' time (HIP events) under each forced kernel: one warm-up call each, then `steps` rounds that
     alternate between them (clocks as they come: neither kernel gets the warmer half of the run). -> {kernel: median ms}"""
@@ -411,6 +461,8 @@ def main():
             lines += find_lines(dec, dev, targets, args.steps)
         if "gaps" in legs:
             lines += gaps_lines(dec, dev, targets, args.steps)
+        if "greedy" in legs:
+            lines += greedy_lines(dec, dev, targets, n, args.steps)
         del dev
     if "sweep" in legs:
         lines += sweep_lines(dec, max(args.steps, 5))
