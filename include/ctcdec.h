@@ -464,6 +464,43 @@ int ctcdec_score_batch(ctcdec_decoder* dec, const void* const* utt_logits, const
                        int32_t dtype, int32_t is_device, const int32_t* targets, const int64_t* target_off,
                        const int64_t* hyp_off, int32_t kernel, double* logp_out, double* ms4, int64_t* launched2);
 
+/* ---- prefix scores: how probable it is that the transcript STARTS with a label sequence followed by label c, for every c ---
+ * No reference analogue: the CTC prefix score an external decoder asks for at every step (joint CTC / attention decoding,
+ * rescoring another model's next-token distribution, constrained decoding). Utterance u owns the prefixes
+ * [prefix_off[u], prefix_off[u + 1]); prefix h is the label ids labels[label_off[h] .. label_off[h + 1]) (alphabet indices,
+ * never the blank; at most 2047 of them; none: the empty prefix). Logits, frame counts, dtype, is_device, the
+ * probabilities-or-logits rule and the per-frame log-probabilities e(t, c) (clipped, float64) are those of
+ * ctcdec_align_batch; a_t[s] is ctcdec_score_batch's forward recursion over the S = 2 L + 1 states of the prefix. With
+ *   B[0] = -inf,  B[t >= 1] = a_{t-1}[S-1],
+ *   A[0] = 0 for the empty prefix, else -inf,  A[t >= 1] = lse2(a_{t-1}[S-1], a_{t-1}[S-2])  (L = 0: a_{t-1}[0]),
+ *   end[h]      = lse2(a_{T-1}[S-1], a_{T-1}[S-2]): ctcdec_score_batch's score of the prefix as a whole transcript, bit for bit;
+ *   next[h][c]  = log sum_t exp(W_c[t] + e(t, c)),  W_c = B when c is the prefix' last label, else A;  next[h][blank] = -inf:
+ * the mass of all frame sequences whose labels through some frame t are exactly the prefix and then c, c first completed
+ * at t -- for normalised rows the probability that the transcript starts with the prefix followed by c. A prefix with
+ * fewer frames than labels plus adjacent equal labels has end = -inf and next = -inf everywhere and launches nothing; with
+ * exactly as many, end is finite and next all -inf; without frames the empty prefix has end = 0.0.
+ * The call is stateless: each prefix' forward pass runs from scratch (ctc_forward / ctc_forward_wave with per-frame end
+ * states; `kernel` as in ctcdec_score_batch, the same bits either way), then ctc_prefix_extend forms all V scores of up to 8
+ * prefixes of an utterance from one read of its rows. The row log-sum-exps are computed once per utterance. No atomics:
+ * a prefix' bits do not depend on the rest of the batch or on host / device input.
+ * next_out: NULL -- the result holds next as one [n_prefixes][V] float64 block --, or (is_device only) device memory of
+ * that shape, which the kernels write in place; the call returns when they have.
+ * Everything is validated before anything is launched, as in ctcdec_score_batch (CTCDEC_ERR_ARG; more than 2047 labels:
+ * CTCDEC_ERR_LIMIT). decoder.py: prefix_scores / prefix_scores_batch. */
+typedef struct ctcdec_prefix ctcdec_prefix; /* opaque */
+int ctcdec_prefix_batch(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts,
+                        int32_t dtype, int32_t is_device, const int32_t* labels, const int64_t* label_off,
+                        const int64_t* prefix_off, int32_t kernel, double* next_out, ctcdec_prefix** out);
+/* end[n_prefixes]; next[n_prefixes * n_labels], NULL when the call was given next_out. Valid until ctcdec_prefix_free. */
+int ctcdec_prefix_scores(const ctcdec_prefix* p, const double** end, const double** next, int64_t* n_prefixes, int32_t* n_labels);
+/* milliseconds: [0] the classification, [1] row_lse, [2] the forward kernels with end states, [3] ctc_prefix_extend (with
+ * ctc_prefix_finish and the fill of rows without a launch; HIP events on the decode stream), [4] the whole native call;
+ * launches3 (may be NULL): kernel launches of [0] row_lse -- one, however many prefixes an utterance has --, [1] the forward
+ * kernels, [2] ctc_prefix_extend, ctc_prefix_finish and the fill, as the kernels' event logs counted them; launched2 (may
+ * be NULL): prefixes that went to [0] the wavefront kernel, [1] the workgroup kernel */
+int ctcdec_prefix_timing(const ctcdec_prefix* p, double* ms5, int32_t* launches3, int64_t* launched2);
+void ctcdec_prefix_free(ctcdec_prefix* p);
+
 /* ---- frame posteriors: where, under ALL alignments of a label sequence the caller already has, each frame lies ---------
  * No reference analogue: the CTC forward-backward. Utterance u's target is labels[label_off[u] .. label_off[u + 1]) (alphabet
  * indices, never the blank; at most 2047 of them); logits, frame counts, dtype, is_device, the probabilities-or-logits rule

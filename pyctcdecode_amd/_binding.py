@@ -166,6 +166,13 @@ _PROTOS = {
     "ctcdec_greedy_scores": (C.c_int, [_VP, C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.c_int64)]),
     "ctcdec_greedy_timing": (C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "ctcdec_greedy_free": (None, [_VP]),
+    "ctcdec_prefix_batch": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32,
+                                      C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, _VP,
+                                      C.POINTER(_VP)]),
+    "ctcdec_prefix_scores": (C.c_int, [_VP, C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.c_int64),
+                                       C.POINTER(C.c_int32)]),
+    "ctcdec_prefix_timing": (C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "ctcdec_prefix_free": (None, [_VP]),
     "ctcdec_score_batch": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32,
                                      C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32,
                                      C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

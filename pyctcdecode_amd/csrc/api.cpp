@@ -226,6 +226,10 @@ struct ctcdec_decoder {
   // greedy decode (ctcdec_greedy_batch): the rows' labels, the utterances' token counts and offsets, the tokens' labels, spans
   // and confidences (row maxima: w_amax, scores: w_ascore)
   DevBuf w_garg, w_gcnt, w_gtoff, w_glab, w_gspan, w_glogp;
+  // prefix scores (ctcdec_prefix_batch): the end states and scales the forward pass stores, their records in launch order
+  // and by prefix, the prefixes' last labels, the chunks, a split launch's sums, the rows without a launch and, for host
+  // callers, the result (labels: w_alab, scores: w_ascore, hypothesis records: w_fhyps)
+  DevBuf w_xends, w_xscale, w_xrecl, w_xrech, w_xlast, w_xchunks, w_xpart, w_xrows, w_xnext;
   bool slicing = false;  // a time-sliced host ingest is under way (decode_host_sliced): the prune stage notes each slice's side of 1
   uint32_t max_label_bytes = 1;
   bool arenas_worst_case = false;  // a call has outgrown the usual reservation of the node arenas: reserve the worst case from now on
@@ -3149,6 +3153,267 @@ int ctcdec_score_batch(ctcdec_decoder* dec, const void* const* utt_logits, const
   if (launched2) launched2[0] = launched[0], launched2[1] = launched[1];
   return CTCDEC_OK;
 }
+
+// ---- prefix scores ("Prefix scores") ----------------------------------------------------------------------------
+}  // extern "C"
+
+struct ctcdec_prefix {
+  std::vector<double> end, next;  // [n_prefixes], [n_prefixes * V] (empty when the caller's device buffer took them)
+  int32_t V = 0;
+  bool next_with_caller = false;
+  int32_t launches[3] = {0, 0, 0};  // row_lse, the forward kernels, ctc_prefix_extend / _finish / _fill
+  int64_t launched[2] = {0, 0};
+  double ms[5] = {0, 0, 0, 0, 0};
+};
+
+// The call behind ctcdec_prefix_batch: the checked prefixes (need[h]: labels plus adjacent equal labels) to a result.
+static int prefix_call(ctcdec_decoder* dec, const TranscriptCall& tc, const void* const* utt_logits, const int32_t* utt_frames,
+                       int32_t n_utts, int32_t dtype, int32_t is_device, const int32_t* labels, const int64_t* label_off,
+                       const int64_t* prefix_off, const std::vector<int32_t>& need, int32_t kernel, double* next_out, ctcdec_prefix* res) {
+  const size_t n = (size_t)n_utts;
+  const int64_t NH = prefix_off[n];
+  const int V = tc.V;
+  const double NEG = align_neg_inf();
+  res->V = V;
+  res->next_with_caller = next_out != nullptr;
+  res->end.assign((size_t)NH, NEG);
+  if (NH == 0) return CTCDEC_OK;
+  // A prefix with fewer frames than labels plus adjacent equal labels cannot be complete: end and next are -inf, decided
+  // here. Without frames the empty prefix has the one empty alignment and nothing follows it. Everything else goes to a
+  // forward kernel -- the wave kernel up to its limit (unless the group kernel is forced), the group kernel above it -- and
+  // then, in chunks of PREFIX_K per utterance, to ctc_prefix_extend.
+  const int32_t wave_max = kernel == 2 ? -1 : FORWARD_WAVE_MAX_LABELS;
+  std::vector<int32_t> run[2], dead;  // [0] wave, [1] group; dead: no launch
+  std::vector<int32_t> utt_of((size_t)NH);
+  for (int32_t u = 0; u < n_utts; ++u)
+    for (int64_t h = prefix_off[u]; h < prefix_off[u + 1]; ++h) {
+      const int64_t L = label_off[h + 1] - label_off[h];
+      utt_of[(size_t)h] = u;
+      if (utt_frames[u] < need[(size_t)h] || utt_frames[u] == 0) {
+        if (utt_frames[u] >= need[(size_t)h]) res->end[(size_t)h] = 0.0;  // (no frames, no labels)
+        dead.push_back((int32_t)h);
+      } else {
+        run[L <= wave_max ? 0 : 1].push_back((int32_t)h);
+      }
+    }
+  std::string err;
+  const size_t next_count = (size_t)NH * (size_t)V;
+  if (!next_out) res->next.assign(next_count, NEG);
+  if (run[0].empty() && run[1].empty() && !next_out) return CTCDEC_OK;  // (the host's rows are filled already)
+  // (an utterance none of whose prefixes is launched takes no part: nothing of it is staged, classified or summed)
+  std::vector<int32_t> use_frames(n, 0);
+  for (int w = 0; w < 2; ++w)
+    for (int32_t h : run[w]) use_frames[(size_t)utt_of[(size_t)h]] = utt_frames[utt_of[(size_t)h]];
+  const std::vector<int64_t> row0 = row_starts(use_frames.data(), n);
+  const int64_t NL = label_off[NH];
+  AlignFront fr;
+  if (!run[0].empty() || !run[1].empty()) {
+    if (int rc = align_front(dec, utt_logits, use_frames.data(), n_utts, dtype, is_device, V, row0, fr)) return rc;
+  } else {  // (only rows to fill: the device all the same)
+    fr.device_lock = std::unique_lock<std::mutex>(g_device_mu);
+    if (be::bind_thread(&err)) return fail(CTCDEC_ERR_DEVICE, err);
+#ifndef CTC_SIM
+    be::align_timing_reset();
+#endif
+  }
+  double* next = next_out;
+  if (!next) {
+    if (dec->w_xnext.ensure(next_count * 8, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+    next = (double*)dec->w_xnext.p;
+  }
+  // the rows nothing is launched for: -inf, on the device (a host caller's were filled above)
+  if (next_out && !dead.empty()) {
+    if (upload(dec->w_xrows, dead, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+#ifdef CTC_SIM
+    for (int32_t h : dead)
+      for (int c = 0; c < V; ++c) next[(size_t)h * (size_t)V + (size_t)c] = NEG;
+#else
+    for (size_t at = 0; at < dead.size(); at += 65535) {
+      const int32_t rows = (int32_t)std::min<size_t>(65535, dead.size() - at);
+      if (be::launch_ctc_prefix_fill(next, (const int32_t*)dec->w_xrows.p + at, rows, V, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+    }
+#endif
+  }
+  if (!run[0].empty() || !run[1].empty()) {
+    if (dec->w_alab.ensure((size_t)std::max<int64_t>(NL, 1) * 4, &err) || dec->w_ascore.ensure((size_t)NH * 8, &err) ||
+        dec->w_xscale.ensure((size_t)NH * 8, &err))
+      return fail(CTCDEC_ERR_DEVICE, err);
+    if ((NL && be::h2d(dec->w_alab.p, labels, (size_t)NL * 4, &err)) || be::zero(dec->w_ascore.p, (size_t)NH * 8, &err))
+      return fail(CTCDEC_ERR_DEVICE, err);
+    // where each launched prefix' 2 T end states go, and its last label
+    std::vector<int64_t> ends_at((size_t)NH, -1);
+    std::vector<int32_t> last((size_t)NH, -1);
+    int64_t n_ends = 0;
+    for (int64_t h = 0; h < NH; ++h) {
+      const int32_t T = utt_frames[utt_of[(size_t)h]];
+      if (label_off[h + 1] > label_off[h]) last[(size_t)h] = labels[label_off[h + 1] - 1];
+      if (T < need[(size_t)h] || T == 0) continue;
+      ends_at[(size_t)h] = n_ends;
+      n_ends += 2 * (int64_t)T;
+    }
+    if (dec->w_xends.ensure((size_t)n_ends * 8, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+    std::vector<PrefixEnds> rec_h((size_t)NH, PrefixEnds{nullptr, nullptr}), rec_l;
+    for (int64_t h = 0; h < NH; ++h)
+      if (ends_at[(size_t)h] >= 0) rec_h[(size_t)h] = PrefixEnds{(double*)dec->w_xends.p + ends_at[(size_t)h], (double*)dec->w_xscale.p + h};
+    // one forward launch per kernel, longest utterance first inside it, as ctcdec_score_batch makes them
+    std::vector<ForwardHyp> hyps;
+    int32_t max_chunks[2] = {1, 1};
+    for (int w = 0; w < 2; ++w) {
+      std::vector<int32_t>& g = run[w];
+      std::stable_sort(g.begin(), g.end(), [&](int32_t a, int32_t b) { return utt_frames[utt_of[(size_t)a]] > utt_frames[utt_of[(size_t)b]]; });
+      for (int32_t h : g) {
+        const int32_t u = utt_of[(size_t)h];
+        ForwardHyp a;
+        a.x = fr.ptrs[(size_t)u];
+        a.lse = fr.lse + row0[(size_t)u];
+        a.lab = (const int32_t*)dec->w_alab.p + label_off[h];
+        a.logp = (double*)dec->w_ascore.p + h;
+        a.T = utt_frames[u];
+        a.L = (int32_t)(label_off[h + 1] - label_off[h]);
+        a.is_prob = fr.is_prob[(size_t)u] ? 1 : 0;
+        a.pad = 0;
+        hyps.push_back(a);
+        rec_l.push_back(rec_h[(size_t)h]);
+        max_chunks[w] = std::max(max_chunks[w], align_chunks(a.L));
+      }
+      res->launched[w] = (int64_t)g.size();
+    }
+    // the chunks: an utterance's launched prefixes in input order, PREFIX_K at a time
+    std::vector<PrefixChunk> chunks;
+    int32_t max_segs = 1;
+    for (int32_t u = 0; u < n_utts; ++u) {
+      PrefixChunk ch{};
+      ch.x = fr.ptrs[(size_t)u];
+      ch.lse = fr.lse + row0[(size_t)u];
+      ch.T = utt_frames[u];
+      ch.is_prob = fr.is_prob[(size_t)u] ? 1 : 0;
+      for (int64_t h = prefix_off[u]; h < prefix_off[u + 1]; ++h) {
+        if (ends_at[(size_t)h] < 0) continue;
+        ch.h[ch.n++] = (int32_t)h;
+        if (ch.n == PREFIX_K) chunks.push_back(ch), ch.n = 0;
+      }
+      if (ch.n) chunks.push_back(ch);
+      if (use_frames[(size_t)u]) max_segs = std::max(max_segs, prefix_segments(ch.T));
+    }
+    PrefixExtendArgs xa;
+    xa.n_chunks = (int32_t)chunks.size();
+    xa.n_labels = V;
+    xa.dtype = dtype;
+    xa.blank = tc.blank;
+    xa.max_segs = max_segs;
+    xa.split = prefix_split((int64_t)chunks.size(), V) ? 1 : 0;
+    xa.clip_lo = tc.clip_lo;
+    const size_t part = xa.split ? chunks.size() * (size_t)max_segs * PREFIX_K * (size_t)V : 1;
+    if (dec->w_xpart.ensure(part * 8, &err) || upload(dec->w_xrech, rec_h, &err) || upload(dec->w_xlast, last, &err) ||
+        upload(dec->w_xchunks, chunks, &err))
+      return fail(CTCDEC_ERR_DEVICE, err);
+    xa.chunks = (const PrefixChunk*)dec->w_xchunks.p;
+    xa.ends = (const PrefixEnds*)dec->w_xrech.p;
+    xa.last = (const int32_t*)dec->w_xlast.p;
+    xa.next = next;
+    xa.partial = (double*)dec->w_xpart.p;
+#ifdef CTC_SIM  // (both forward kernels are the one body here; a single thread owns every group and, in turn, every column)
+    std::vector<double> col((size_t)2 * (size_t)std::max(max_chunks[0], max_chunks[1]));
+    AlignSeqCtx cx;
+    for (size_t i = 0; i < hyps.size(); ++i)
+      for_dtype(dtype, [&](auto dt) { ctc_forward_hyp<decltype(dt)::value, true>(cx, hyps[i], V, tc.blank, tc.clip_lo, col.data(), &rec_l[i]); });
+    std::vector<double> w((size_t)PREFIX_W_DOUBLES);
+    for (int32_t k = 0; k < xa.n_chunks; ++k) {
+      const int nseg = prefix_segments(chunks[(size_t)k].T);
+      for (int c = 0; c < V; ++c) {
+        for_dtype(dtype, [&](auto dt) {
+          if (!xa.split) return ctc_prefix_extend_tile<decltype(dt)::value>(cx, xa, k, c, 0, nseg, w.data());
+          for (int seg = 0; seg < nseg; ++seg) ctc_prefix_extend_tile<decltype(dt)::value>(cx, xa, k, c, seg, seg + 1, w.data());
+        });
+        if (xa.split) ctc_prefix_finish_col(xa, k, c);
+      }
+    }
+#else
+    if (upload(dec->w_fhyps, hyps, &err) || upload(dec->w_xrecl, rec_l, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+    for (int w = 0; w < 2; ++w) {
+      be::ForwardArgs fa;
+      fa.hyps = (const ForwardHyp*)dec->w_fhyps.p + (w ? run[0].size() : 0);
+      fa.n_hyps = (int32_t)run[w].size();
+      fa.n_labels = V;
+      fa.dtype = dtype;
+      fa.blank = tc.blank;
+      fa.max_chunks = max_chunks[w];
+      fa.pad = 0;
+      fa.clip_lo = tc.clip_lo;
+      if (be::launch_ctc_forward_ends(fa, (const PrefixEnds*)dec->w_xrecl.p + (w ? run[0].size() : 0), w == 0, &err))
+        return fail(CTCDEC_ERR_DEVICE, err);
+    }
+    if (be::launch_ctc_prefix_extend(xa, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+#endif
+    std::vector<double> got((size_t)NH);
+    if (be::d2h(got.data(), dec->w_ascore.p, (size_t)NH * 8, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+    for (int w = 0; w < 2; ++w)
+      for (int32_t h : run[w]) res->end[(size_t)h] = got[(size_t)h];
+    if (!next_out) {
+      // the launched rows come back; the others keep the host's -inf (nothing wrote them on the device)
+      std::vector<double> back(next_count);
+      if (be::d2h(back.data(), next, next_count * 8, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+      for (int w = 0; w < 2; ++w)
+        for (int32_t h : run[w]) std::copy(back.begin() + (size_t)h * (size_t)V, back.begin() + ((size_t)h + 1) * (size_t)V, res->next.begin() + (size_t)h * (size_t)V);
+    }
+  }
+  if (be::sync(&err)) return fail(CTCDEC_ERR_DEVICE, err);
+#ifndef CTC_SIM
+  if (!run[0].empty() || !run[1].empty()) {
+    res->ms[0] = be::last_prune_ms();
+    res->ms[1] = be::align_kernel_ms(be::K_ROW_LSE);
+    res->ms[2] = be::align_kernel_ms(be::K_FORWARD);
+    res->launches[0] = be::align_kernel_launches(be::K_ROW_LSE);
+    res->launches[1] = be::align_kernel_launches(be::K_FORWARD);
+  }
+  res->ms[3] = be::align_kernel_ms(be::K_PREFIX_EXTEND);
+  res->launches[2] = be::align_kernel_launches(be::K_PREFIX_EXTEND);
+#endif
+  return CTCDEC_OK;
+}
+
+extern "C" {
+
+int ctcdec_prefix_batch(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts, int32_t dtype,
+                        int32_t is_device, const int32_t* labels, const int64_t* label_off, const int64_t* prefix_off, int32_t kernel,
+                        double* next_out, ctcdec_prefix** out) {
+  TranscriptCall tc;
+  const bool args_ok = dec && out && n_utts >= 0 && label_off && prefix_off && (n_utts == 0 || (utt_logits && utt_frames));
+  if (int rc = transcript_open(dec, args_ok, dtype, bad_kernel(kernel), tc)) return rc;
+  std::vector<int32_t> need;
+  if (int rc = check_scores(utt_logits, utt_frames, n_utts, labels, label_off, prefix_off, tc, need, "prefix")) return rc;
+  if (next_out && !is_device) return fail(CTCDEC_ERR_ARG, "a buffer for next is device memory: it goes with device logits");
+  if (prefix_off[n_utts] * (int64_t)tc.V > (int64_t)1 << 40) return fail(CTCDEC_ERR_LIMIT, "more than 2^40 prefix scores in one call");
+  const auto t_begin = Clock::now();
+  std::unique_ptr<ctcdec_prefix> res(new ctcdec_prefix);
+  if (int rc = prefix_call(dec, tc, utt_logits, utt_frames, n_utts, dtype, is_device, labels, label_off, prefix_off, need, kernel, next_out,
+                           res.get()))
+    return rc;
+  res->ms[4] = ms(t_begin, Clock::now());
+  *out = res.release();
+  return CTCDEC_OK;
+}
+
+int ctcdec_prefix_scores(const ctcdec_prefix* p, const double** end_out, const double** next_out, int64_t* n_prefixes_out,
+                         int32_t* n_labels_out) {
+  if (!p || !end_out || !next_out || !n_prefixes_out || !n_labels_out) return fail(CTCDEC_ERR_ARG, "no prefix result");
+  *end_out = p->end.data();
+  *next_out = p->next_with_caller ? nullptr : p->next.data();
+  *n_prefixes_out = (int64_t)p->end.size();
+  *n_labels_out = p->V;
+  return CTCDEC_OK;
+}
+
+int ctcdec_prefix_timing(const ctcdec_prefix* p, double* ms5, int32_t* launches3, int64_t* launched2) {
+  if (!p || !ms5) return fail(CTCDEC_ERR_ARG, "no prefix result");
+  for (int k = 0; k < 5; ++k) ms5[k] = p->ms[k];
+  if (launches3)
+    for (int k = 0; k < 3; ++k) launches3[k] = p->launches[k];
+  if (launched2) launched2[0] = p->launched[0], launched2[1] = p->launched[1];
+  return CTCDEC_OK;
+}
+
+void ctcdec_prefix_free(ctcdec_prefix* p) { delete p; }
 
 // ---- frame posteriors ("Frame posteriors") --------------------------------------------------------------------
 }  // extern "C"

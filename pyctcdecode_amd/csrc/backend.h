@@ -320,14 +320,23 @@ int launch_ctc_viterbi_gaps(const ViterbiGapsArgs& a, std::string* err);
 int launch_row_argmax(const RowLseArgs& a, int32_t* arg, int blank, std::string* err);
 int launch_row_lse_argmax(const RowLseArgs& a, double* rmax, int32_t* arg, int blank, std::string* err);
 int launch_greedy_collapse(const GreedyArgs& a, std::string* err);
+// Prefix scores (ctc_align.h, "ctc_prefix_extend"). launch_ctc_forward_ends: launch_ctc_forward whose kernels also store, for
+// entry i of `hyps`, the per-frame end states and their scale where ends[i] says (device). launch_ctc_prefix_extend: every
+// label's prefix score of the chunks' prefixes from what those kernels stored; a split launch is followed by ctc_prefix_finish.
+// launch_ctc_prefix_fill: -inf into the n_rows (at most 65535 a launch) rows `rows` (device) of next[.][V].
+int launch_ctc_forward_ends(const ForwardArgs& a, const PrefixEnds* ends, int wave, std::string* err);
+int launch_ctc_prefix_extend(const PrefixExtendArgs& a, std::string* err);
+int launch_ctc_prefix_fill(double* next, const int32_t* rows, int32_t n_rows, int32_t V, std::string* err);
 // kernel times (HIP events) of the launches of one of these kernels since the last reset; waits for the kernels.
-// ctc_forward and ctc_forward_wave share a log, as do ctc_find and ctc_find_wave, and greedy_collapse's two passes.
+// ctc_forward and ctc_forward_wave share a log (with their _ends forms), as do ctc_find and ctc_find_wave, greedy_collapse's
+// two passes, and ctc_prefix_extend, ctc_prefix_finish and ctc_prefix_fill.
 enum AlignKernel {
   K_ROW_LSE, K_VITERBI, K_FORWARD, K_POSTERIORS, K_GRAD_ROWS, K_FIND, K_ROW_LSE_MAX, K_VITERBI_GAPS, K_ROW_ARGMAX, K_ROW_LSE_ARGMAX,
-  K_GREEDY_COLLAPSE, ALIGN_KERNELS
+  K_GREEDY_COLLAPSE, K_PREFIX_EXTEND, ALIGN_KERNELS
 };
 void align_timing_reset();
 double align_kernel_ms(AlignKernel kind);
+int align_kernel_launches(AlignKernel kind);  // launches logged for the kernel since the last reset
 
 // stage timing (ms) of the last launch_prune / launch_beam pair, measured on the decode stream
 void last_timing(double* prune_ms, double* beam_ms);

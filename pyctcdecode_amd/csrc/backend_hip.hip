@@ -579,6 +579,16 @@ int launch_row_lse_argmax_on(const RowLseArgs& a, double* rmax, int32_t* arg, in
 int launch_row_lse_argmax(const RowLseArgs& a, double* rmax, int32_t* arg, int blank, std::string* err) {
   return launch_row_lse_argmax_on(a, rmax, arg, blank, g_stream, err);
 }
+int launch_ctc_forward_ends_on(const ForwardArgs& a, const PrefixEnds* ends, int wave, hipStream_t stream, std::string* err);
+int launch_ctc_forward_ends(const ForwardArgs& a, const PrefixEnds* ends, int wave, std::string* err) {
+  return launch_ctc_forward_ends_on(a, ends, wave, g_stream, err);
+}
+int launch_ctc_prefix_extend_on(const PrefixExtendArgs& a, hipStream_t stream, std::string* err);
+int launch_ctc_prefix_extend(const PrefixExtendArgs& a, std::string* err) { return launch_ctc_prefix_extend_on(a, g_stream, err); }
+int launch_ctc_prefix_fill_on(double* next, const int32_t* rows, int32_t n_rows, int32_t V, hipStream_t stream, std::string* err);
+int launch_ctc_prefix_fill(double* next, const int32_t* rows, int32_t n_rows, int32_t V, std::string* err) {
+  return launch_ctc_prefix_fill_on(next, rows, n_rows, V, g_stream, err);
+}
 int launch_greedy_collapse_on(const GreedyArgs& a, hipStream_t stream, std::string* err);
 int launch_greedy_collapse(const GreedyArgs& a, std::string* err) { return launch_greedy_collapse_on(a, g_stream, err); }
 

@@ -11,6 +11,8 @@
 //   ctc_viterbi_gaps_utt           the best path of a target with gaps          (ctc_viterbi_gaps)
 //   row_argmax_seq                 a row's most probable label: the simulator's; the kernels fold by lanes
 //   greedy_collapse_utt            runs of frame labels to tokens               (greedy_collapse)
+//   ctc_forward_hyp / _wave_hyp <ENDS>  the forward pass that also stores a prefix' end states  (ctc_forward_ends / ctc_forward_wave_ends)
+//   ctc_prefix_extend_tile, ctc_prefix_finish_col   every label's prefix score from them  (ctc_prefix_extend, ctc_prefix_finish)
 // The shared pieces, and who uses them:
 //   viterbi_backtrace, fold_token_logp                   ctc_viterbi, ctc_viterbi_gaps
 //   group_setup, EntrySource, FrameEntries               ctc_find, ctc_find_wave, ctc_viterbi_gaps
@@ -267,6 +269,15 @@ struct ForwardHyp {
   int32_t T, L, is_prob, pad;
 };
 
+// What the forward bodies leave behind per frame when they run for ctc_prefix_extend (ENDS; "ctc_prefix_extend" below):
+//   bc[t]     = a_{t-1}[S-1]   the target is complete and the frame before was a blank   (t = 0: -inf)
+//   bc[T + t] = a_{t-1}[S-2]   the target is complete and the frame before was its last label (t = 0: 0 for the empty target)
+// and scale[0], the largest of these 2T values: -inf when the target cannot be complete before the last frame.
+struct PrefixEnds {
+  double* bc;     // [2 T] out
+  double* scale;  // [1] out
+};
+
 constexpr int32_t FORWARD_MAX_GROUPS = (2 * ALIGN_MAX_LABELS + 1 + 3) / 4;  // align_chunks(ALIGN_MAX_LABELS)
 constexpr int32_t FORWARD_WAVE_MAX_LABELS = 127;  // ctc_forward_wave: 2L + 1 <= 256 states, four to each of a wave's 64 lanes
 
@@ -416,8 +427,10 @@ struct FrameEntries {
 // of two successive frames) to the thread that owns the group above: one barrier per frame. Nothing the recursion computes
 // decides the entries of frame t + 1: they are requested -- without a branch, at indices that are always valid, and kept as
 // loaded -- after the neighbour's state is in hand and before frame t's arithmetic and barrier.
-template <int DT, class Ctx>
-CTC_HD void ctc_forward_hyp(Ctx& cx, const ForwardHyp& hyp, int V, int blank, double clip_lo, double* col) {
+// ENDS: the thread that owns the last group also stores, ahead of every frame's step, the two states a complete target ends
+// in (PrefixEnds) -- two stores and two compares a frame, no arithmetic of the recursion changes.
+template <int DT, bool ENDS = false, class Ctx>
+CTC_HD void ctc_forward_hyp(Ctx& cx, const ForwardHyp& hyp, int V, int blank, double clip_lo, double* col, const PrefixEnds* ends = nullptr) {
   typedef typename AlignRaw<DT>::type Raw;
   constexpr int G = Ctx::GROUPS;
   const void* const x = hyp.x;  // (the record, once: the loop below reads none of it again)
@@ -453,6 +466,10 @@ CTC_HD void ctc_forward_hyp(Ctx& cx, const ForwardHyp& hyp, int V, int blank, do
     p[0][0] = align_emit(x, DT, (size_t)blank, lse0, is_prob, clip_lo);
     if (L > 0) p[0][1] = align_emit(x, DT, (size_t)lab[0], lse0, is_prob, clip_lo);
   }
+  double ends_m = L == 0 ? 0.0 : NEG;  // (ENDS) the largest end state stored so far
+  if constexpr (ENDS) {
+    if (cx.tid == 0) ends->bc[0] = NEG, ends->bc[T] = ends_m;
+  }
   cx.sync();
   // frame 1's entries (a single frame: frame 0's again, never used)
   int clo = 0, chi = -1, clo_prev = 0;
@@ -475,6 +492,19 @@ CTC_HD void ctc_forward_hyp(Ctx& cx, const ForwardHyp& hyp, int V, int blank, do
     for (int k = 0; k < G; ++k) {
       const int c = cx.tid + k * cx.nt;
       pm1[k] = c >= clo && c <= chi && c > 0 && c - 1 >= clo_prev ? prev[c - 1] : NEG;
+    }
+    if constexpr (ENDS) {  // a_{t-1}[S-1] and a_{t-1}[S-2], read as the result below reads them (the window never cuts them off)
+      const int ce = (S - 1) >> 2, je = (S - 1) & 3;
+      CTC_UNROLL
+      for (int k = 0; k < G; ++k) {
+        if (cx.tid + k * cx.nt != ce) continue;
+        const double last = je == 2 ? p[k][2] : p[k][0];
+        const double before = je == 2 ? p[k][1] : (ce > 0 ? prev[ce - 1] : NEG);
+        ends->bc[t] = last;
+        ends->bc[T + t] = before;
+        ends_m = last > ends_m ? last : ends_m;
+        ends_m = before > ends_m ? before : ends_m;
+      }
     }
     // then ask for frame t + 1 (after the last frame: the last frame again)
     const int tn = t + 1 < T ? t + 1 : t;
@@ -515,14 +545,15 @@ CTC_HD void ctc_forward_hyp(Ctx& cx, const ForwardHyp& hyp, int V, int blank, do
     const double last = jf == 2 ? p[k][2] : p[k][0];
     const double before = jf == 2 ? p[k][1] : (cf > 0 ? fin[cf - 1] : NEG);
     *out = align_lse2(last, before);
+    if constexpr (ENDS) *ends->scale = ends_m;
   }
 }
 
 // ctc_forward_wave: one wavefront per hypothesis of at most FORWARD_WAVE_MAX_LABELS labels. Lane c owns group c; the last
 // state of the group below comes from lane c - 1 by cx.up() (one fp64 shuffle per frame): no LDS, no barrier. The same
 // groups, steps and prefetch as ctc_forward_hyp, so the same bits. cx: lane, up(v) = v of the lane below (any value in lane 0).
-template <int DT, class Ctx>
-CTC_HD void ctc_forward_wave_hyp(Ctx& cx, const ForwardHyp& hyp, int V, int blank, double clip_lo) {
+template <int DT, bool ENDS = false, class Ctx>
+CTC_HD void ctc_forward_wave_hyp(Ctx& cx, const ForwardHyp& hyp, int V, int blank, double clip_lo, const PrefixEnds* ends = nullptr) {
   typedef typename AlignRaw<DT>::type Raw;
   const void* const x = hyp.x;
   const double* const lse = hyp.lse;
@@ -541,6 +572,10 @@ CTC_HD void ctc_forward_wave_hyp(Ctx& cx, const ForwardHyp& hyp, int V, int blan
     p[0] = align_emit(x, DT, (size_t)blank, lse0, is_prob, clip_lo);
     if (L > 0) p[1] = align_emit(x, DT, (size_t)lab[0], lse0, is_prob, clip_lo);
   }
+  double ends_m = L == 0 ? 0.0 : NEG;  // (ENDS) the largest end state stored so far
+  if constexpr (ENDS) {
+    if (c == 0) ends->bc[0] = NEG, ends->bc[T] = ends_m;
+  }
   int clo = 0, chi = -1, clo_prev = 0;
   if (T > 1) forward_window(1, T, S, &clo, &chi);
   const size_t row1 = T > 1 ? (size_t)V : 0;
@@ -549,6 +584,17 @@ CTC_HD void ctc_forward_wave_hyp(Ctx& cx, const ForwardHyp& hyp, int V, int blan
   double lse_t = lse[T > 1 ? 1 : 0];
   for (int t = 1; t < T; ++t) {
     const double below = cx.up(p[3]);  // (every lane takes part, whatever its window says)
+    if constexpr (ENDS) {  // a_{t-1}[S-1] and a_{t-1}[S-2], read as the result below reads them
+      const int ce = (S - 1) >> 2, je = (S - 1) & 3;
+      if (c == ce) {
+        const double last = je == 2 ? p[2] : p[0];
+        const double before = je == 2 ? p[1] : (ce > 0 ? below : NEG);
+        ends->bc[t] = last;
+        ends->bc[T + t] = before;
+        ends_m = last > ends_m ? last : ends_m;
+        ends_m = before > ends_m ? before : ends_m;
+      }
+    }
     const int tn = t + 1 < T ? t + 1 : t;
     int nlo = 0, nhi = -1;
     if (t + 1 < T) forward_window(tn, T, S, &nlo, &nhi);
@@ -573,6 +619,7 @@ CTC_HD void ctc_forward_wave_hyp(Ctx& cx, const ForwardHyp& hyp, int V, int blan
     const double last = jf == 2 ? p[2] : p[0];
     const double before = jf == 2 ? p[1] : (cf > 0 ? below : NEG);
     *out = align_lse2(last, before);
+    if constexpr (ENDS) *ends->scale = ends_m;
   }
 }
 
@@ -1422,6 +1469,156 @@ CTC_HD void greedy_collapse_utt(Ctx& cx, const GreedyArgs& a, int u) {
       else acc = (t == t0 || lp > acc) ? lp : acc;
     }
     a.logp[o + k] = a.fold == LOGP_MEAN ? acc / (double)(t1 - t0) : acc;
+  }
+}
+
+// ---- ctc_prefix_extend -------------------------------------------------------------------------------------------------------
+// The CTC prefix score ("Prefix scores"): for a prefix g of L labels and every label c at once,
+//   next(g)[c] = log sum_t exp(W_c[t] + e(t, c)),   W_c = B if c is g's last label, else A,
+//   B[t] = a_{t-1}[S-1],  A[t] = lse2(a_{t-1}[S-1], a_{t-1}[S-2])   (PrefixEnds: the forward bodies store both addends),
+// as a scaled product instead of a log-sum-exp per element: with m = PrefixEnds::scale (max_t A[t] - ln 2 <= m <= max_t A[t]),
+//   wB[t] = exp(bc[t] - m),  wA[t] = wB[t] + exp(bc[T + t] - m)   (A is never formed: its weight is the sum of two),
+//   next(g)[c] = m + log( sum_t w_c[t] * exp(e(t, c)) ),   -inf for an empty sum and for the blank.
+// exp(e) lies in [1e-15, 1] and is formed once per entry for all the prefixes of a chunk; a weight more than about 700 below
+// m is 0, which changes a sum by less than e^-650 of itself. The frames are cut into segments of PREFIX_SEG; a segment's
+// sum runs in frame order from 0.0 by fma, the segments' sums are added in ascending order from 0.0 -- inside one workgroup
+// or, when the launch is split, by ctc_prefix_finish from `partial`: the same additions either way, so the same bits.
+constexpr int32_t PREFIX_K = 8;       // prefixes of one utterance that share a read of its rows: 2 K accumulator registers a thread
+constexpr int32_t PREFIX_SEG = 128;   // frames of a segment
+constexpr int32_t PREFIX_COLS = 256;  // columns of a tile: one to a thread
+constexpr int32_t PREFIX_W_DOUBLES = (2 * PREFIX_K + 1) * PREFIX_SEG;  // a segment's weights (A's and B's per prefix) and log-sum-exps
+constexpr int32_t PREFIX_FUSE_BLOCKS = 1024;  // a launch with fewer (chunk, tile) pairs is split by segments as well
+
+// Up to PREFIX_K prefixes of one utterance. The host validates every field before a launch.
+struct PrefixChunk {
+  const void* x;        // [T, V] the utterance's matrix, of the launch's dtype
+  const double* lse;    // [T] log-sum-exp of each row (not read when is_prob)
+  int32_t h[PREFIX_K];  // the prefixes, as indices of the call ([0, n) used)
+  int32_t n, T, is_prob, pad;
+};
+struct PrefixExtendArgs {
+  const PrefixChunk* chunks;  // [n_chunks] (device)
+  const PrefixEnds* ends;     // [prefixes of the call] (device): what the forward pass stored; read for the chunks' prefixes only
+  const int32_t* last;        // [prefixes of the call] (device): a prefix's last label, -1 for the empty one
+  double* next;               // [prefixes of the call][V] out
+  double* partial;            // (split) [n_chunks][max_segs][PREFIX_K][V] the segments' sums
+  int32_t n_chunks, n_labels, dtype, blank;
+  int32_t max_segs;           // the most segments an utterance of the launch has
+  int32_t split;              // 1: a workgroup takes one segment and stores its sums; 0: all of them, and stores the result
+  double clip_lo;             // ln(MIN_TOKEN_CLIP_P)
+};
+CTC_HD int32_t prefix_segments(int32_t T) { return (T + PREFIX_SEG - 1) / PREFIX_SEG; }
+CTC_HD int32_t prefix_tiles(int32_t V) { return (V + PREFIX_COLS - 1) / PREFIX_COLS; }
+// (host) the one rule for `split`: by the launch's size alone; the result's bits do not depend on it
+inline bool prefix_split(int64_t n_chunks, int32_t V) { return n_chunks * (int64_t)prefix_tiles(V) < PREFIX_FUSE_BLOCKS; }
+CTC_HD size_t prefix_partial_at(const PrefixExtendArgs& a, int chunk, int seg, int k, int c) {
+  return (((size_t)chunk * (size_t)a.max_segs + (size_t)seg) * PREFIX_K + (size_t)k) * (size_t)a.n_labels + (size_t)c;
+}
+
+// A segment's weights, by all threads of cx: w[(2 k) * SEG + j] = wA, w[(2 k + 1) * SEG + j] = wB of prefix k at frame
+// seg * SEG + j (0 past the chunk's prefixes and past T), w[2 K * SEG + j] the row's log-sum-exp (0 where none is read)
+template <class Ctx>
+CTC_HD void prefix_weights(Ctx& cx, const PrefixExtendArgs& a, const PrefixChunk& ch, int seg, double* w) {
+  const double NEG = align_neg_inf();
+  const int T = ch.T, t0 = seg * PREFIX_SEG;
+  for (int i = cx.tid; i < PREFIX_K * PREFIX_SEG; i += cx.nt) {
+    const int k = i / PREFIX_SEG, j = i % PREFIX_SEG, t = t0 + j;
+    double wa = 0.0, wb = 0.0;
+    if (k < ch.n && t < T) {
+      const PrefixEnds e = a.ends[ch.h[k]];
+      const double m = *e.scale, b = e.bc[t], c = e.bc[T + t];
+      wb = b > NEG ? exp(b - m) : 0.0;  // (an end state above -inf: m is finite and not below it)
+      wa = wb + (c > NEG ? exp(c - m) : 0.0);
+    }
+    w[(2 * k) * PREFIX_SEG + j] = wa;
+    w[(2 * k + 1) * PREFIX_SEG + j] = wb;
+  }
+  for (int j = cx.tid; j < PREFIX_SEG; j += cx.nt) w[2 * PREFIX_K * PREFIX_SEG + j] = !ch.is_prob && t0 + j < T ? ch.lse[t0 + j] : 0.0;
+}
+
+// exp(e(t, c)) of an entry as loaded: the clipped probability itself, or exp of the clipped x - lse. A NaN takes the floor.
+CTC_HD double prefix_exp_emit(double v, double lse, bool is_prob, double clip_lo) {
+  if (is_prob) return !(v >= 1e-15) ? 1e-15 : (v > 1.0 ? 1.0 : v);
+  const double y = v - lse;
+  return exp(!(y >= clip_lo) ? clip_lo : (y > 0.0 ? 0.0 : y));
+}
+
+// Column c's sums over the nf frames of one segment, from 0.0 in frame order: acc[k] for the chunk's n prefixes, whose
+// weights start at w[base[k]] (FULL: n == PREFIX_K, no test per prefix). Four rows are asked for ahead of their use.
+template <int DT, bool FULL>
+CTC_HD void prefix_fold_segment(const void* x, int V, int c, int t0, int nf, bool is_prob, double clip_lo, int n, const double* w,
+                                const int* base, double* acc) {
+  typedef typename AlignRaw<DT>::type Raw;
+  const double* lse_w = w + 2 * PREFIX_K * PREFIX_SEG;
+  for (int j = 0; j < nf; j += 4) {
+    Raw r[4];
+    CTC_UNROLL
+    for (int i = 0; i < 4; ++i) {
+      const int jj = j + i < nf ? j + i : nf - 1;
+      r[i] = align_load_raw<DT>(x, (size_t)(t0 + jj) * (size_t)V + (size_t)c);
+    }
+    CTC_UNROLL
+    for (int i = 0; i < 4; ++i) {
+      if (j + i >= nf) break;
+      const double ee = prefix_exp_emit(align_widen<DT>(r[i]), lse_w[j + i], is_prob, clip_lo);
+      CTC_UNROLL
+      for (int k = 0; k < PREFIX_K; ++k)
+        if (FULL || k < n) acc[k] = fma(w[base[k] + j + i], ee, acc[k]);
+    }
+  }
+}
+
+CTC_HD void prefix_store(const PrefixExtendArgs& a, int h, int c, double total) {
+  a.next[(size_t)h * (size_t)a.n_labels + (size_t)c] = (c == a.blank || !(total > 0.0)) ? align_neg_inf() : *a.ends[h].scale + log(total);
+}
+
+// The threads of cx (tid, nt, sync()) share the segments [s0, s1) of one chunk; this thread owns column c (any c >= V: it
+// only helps with the weights). `w`: PREFIX_W_DOUBLES doubles shared by the threads. Every thread of cx makes the call with
+// the same chunk, s0 and s1.
+template <int DT, class Ctx>
+CTC_HD void ctc_prefix_extend_tile(Ctx& cx, const PrefixExtendArgs& a, int chunk, int c, int s0, int s1, double* w) {
+  const PrefixChunk& ch = a.chunks[chunk];
+  const int T = ch.T, V = a.n_labels, n = ch.n;
+  const bool live = c < V, is_prob = ch.is_prob != 0;
+  int base[PREFIX_K];  // the column of the prefix' last label takes B's weights: a choice of row, made once
+  double total[PREFIX_K];
+  CTC_UNROLL
+  for (int k = 0; k < PREFIX_K; ++k) {
+    base[k] = (2 * k + (live && k < n && a.last[ch.h[k]] == c ? 1 : 0)) * PREFIX_SEG;
+    total[k] = 0.0;
+  }
+  for (int seg = s0; seg < s1; ++seg) {
+    cx.sync();  // (the weights of the segment before are done with)
+    prefix_weights(cx, a, ch, seg, w);
+    cx.sync();
+    if (!live) continue;
+    const int t0 = seg * PREFIX_SEG, nf = T - t0 < PREFIX_SEG ? T - t0 : PREFIX_SEG;
+    double acc[PREFIX_K];
+    CTC_UNROLL
+    for (int k = 0; k < PREFIX_K; ++k) acc[k] = 0.0;
+    if (n == PREFIX_K) prefix_fold_segment<DT, true>(ch.x, V, c, t0, nf, is_prob, a.clip_lo, n, w, base, acc);
+    else prefix_fold_segment<DT, false>(ch.x, V, c, t0, nf, is_prob, a.clip_lo, n, w, base, acc);
+    CTC_UNROLL
+    for (int k = 0; k < PREFIX_K; ++k) {
+      if (k >= n) continue;
+      if (a.split) a.partial[prefix_partial_at(a, chunk, seg, k, c)] = acc[k];
+      else total[k] += acc[k];
+    }
+  }
+  if (a.split || !live) return;
+  CTC_UNROLL
+  for (int k = 0; k < PREFIX_K; ++k)
+    if (k < n) prefix_store(a, ch.h[k], c, total[k]);
+}
+
+// (split) column c of one chunk: the segments' sums in ascending order, as ctc_prefix_extend_tile adds its own
+CTC_HD void ctc_prefix_finish_col(const PrefixExtendArgs& a, int chunk, int c) {
+  const PrefixChunk& ch = a.chunks[chunk];
+  const int nseg = prefix_segments(ch.T);
+  for (int k = 0; k < ch.n; ++k) {
+    double total = 0.0;
+    for (int seg = 0; seg < nseg; ++seg) total += a.partial[prefix_partial_at(a, chunk, seg, k, c)];
+    prefix_store(a, ch.h[k], c, total);
   }
 }
 

@@ -7,6 +7,9 @@
 //   ctc_grad_rows                   G threads per row of a dense ctc_posteriors launch's tables
 //   row_argmax, row_lse_argmax      G lanes per row; both fold with row_fold_arg
 //   greedy_collapse                 a wavefront per utterance
+//   ctc_forward_ends, _wave_ends    ctc_forward / ctc_forward_wave that also store a prefix' end states per frame
+//   ctc_prefix_extend, _finish      a workgroup per (chunk of prefixes, tile of 256 columns[, segment of frames]), a column per thread
+//   ctc_prefix_fill                 -inf into the rows of the prefixes nothing was launched for
 // The launchers share timed_launch (the event pair of the kernel's log and the launch's error), for_dtype and for_threads.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -547,6 +550,54 @@ __global__ __launch_bounds__(ALIGN_THREADS) void greedy_collapse(GreedyArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// Prefix scores. ctc_forward_ends / ctc_forward_wave_ends: the forward kernels' bodies with ENDS, kernels of their own, so
+// that ctc_forward and ctc_forward_wave keep their code. ctc_prefix_extend: blockIdx.x = chunk * tiles + tile (the tiles of
+// a chunk next to each other: they read the same rows), blockIdx.y = the segment of a split launch. A thread owns one column;
+// a row's 256 entries are one coalesced load, formed into exp(e) once for the chunk's prefixes, whose weights come from LDS
+// (ctc_align.h). No atomics: a split launch leaves the segments' sums to ctc_prefix_finish.
+// ---------------------------------------------------------------------------------------------
+template <int NT, int DT>
+__global__ __launch_bounds__(NT) void ctc_forward_ends(ForwardArgs a, const PrefixEnds* ends) {
+  extern __shared__ double forward_ends_cols[];
+  ForwardGpuCtx cx{(int)threadIdx.x, NT};
+  ctc_forward_hyp<DT, true>(cx, a.hyps[blockIdx.x], a.n_labels, a.blank, a.clip_lo, forward_ends_cols, ends + blockIdx.x);
+}
+
+template <int DT>
+__global__ __launch_bounds__(ALIGN_THREADS) void ctc_forward_wave_ends(ForwardArgs a, const PrefixEnds* ends) {
+  const int i = (int)blockIdx.x * FORWARD_WAVES + (int)(threadIdx.x >> 6);
+  if (i >= a.n_hyps) return;  // (a whole wave: nothing in this kernel waits for another wave)
+  ForwardWaveCtx cx{(int)(threadIdx.x & 63u)};
+  ctc_forward_wave_hyp<DT, true>(cx, a.hyps[i], a.n_labels, a.blank, a.clip_lo, ends + i);
+}
+
+static_assert(PREFIX_COLS == ALIGN_THREADS, "a column per thread");
+
+template <int DT>
+__global__ __launch_bounds__(PREFIX_COLS) void ctc_prefix_extend(PrefixExtendArgs a) {
+  __shared__ double prefix_w[PREFIX_W_DOUBLES];
+  const int tiles = prefix_tiles(a.n_labels);
+  const int chunk = (int)(blockIdx.x / (unsigned)tiles), tile = (int)(blockIdx.x % (unsigned)tiles);
+  const int nseg = prefix_segments(a.chunks[chunk].T);
+  const int s0 = a.split ? (int)blockIdx.y : 0, s1 = a.split ? s0 + 1 : nseg;
+  if (s0 >= nseg) return;  // (the whole workgroup)
+  AlignGpuCtx cx{(int)threadIdx.x, PREFIX_COLS};
+  ctc_prefix_extend_tile<DT>(cx, a, chunk, tile * PREFIX_COLS + (int)threadIdx.x, s0, s1, prefix_w);
+}
+
+__global__ __launch_bounds__(PREFIX_COLS) void ctc_prefix_finish(PrefixExtendArgs a) {
+  const int tiles = prefix_tiles(a.n_labels);
+  const int chunk = (int)(blockIdx.x / (unsigned)tiles), c = (int)(blockIdx.x % (unsigned)tiles) * PREFIX_COLS + (int)threadIdx.x;
+  if (c < a.n_labels) ctc_prefix_finish_col(a, chunk, c);
+}
+
+// rows[blockIdx.y] of next[.][V]: -inf
+__global__ __launch_bounds__(PREFIX_COLS) void ctc_prefix_fill(double* next, const int32_t* rows, int V) {
+  const int c = (int)blockIdx.x * PREFIX_COLS + (int)threadIdx.x;
+  if (c < V) next[(size_t)rows[blockIdx.y] * (size_t)V + (size_t)c] = align_neg_inf();
+}
+
+// ---------------------------------------------------------------------------------------------
 // launches. Every launcher validates its arguments, then makes one timed_launch: the kernel's instantiation is picked by
 // for_dtype (ctc_align.h) and, where the kernel has two sizes, for_threads; the row kernels' lanes per row by for_row_lanes.
 // ---------------------------------------------------------------------------------------------
@@ -578,6 +629,7 @@ void align_timing_reset() {
   for (EventLog& log : g_logs) log.used = 0;
 }
 double align_kernel_ms(AlignKernel kind) { return g_logs[kind].total(); }
+int align_kernel_launches(AlignKernel kind) { return (int)(g_logs[kind].used / 2); }
 
 // launch() between two events of the kernel's log, and the error the launch left
 template <class F>
@@ -720,6 +772,55 @@ int launch_ctc_forward_on(const ForwardArgs& a, int wave, hipStream_t stream, st
         hipLaunchKernelGGL((ctc_forward<NT, DT>), dim3((unsigned)a.n_hyps), dim3(NT), lds, stream, a);
       });
     });
+  });
+}
+
+int launch_ctc_forward_ends_on(const ForwardArgs& a, const PrefixEnds* ends, int wave, hipStream_t stream, std::string* err) {
+  if (a.n_hyps <= 0) return 0;
+  if (a.dtype < 0 || a.dtype > 3 || !ends || a.max_chunks < 1 ||
+      a.max_chunks > (wave ? align_chunks(FORWARD_WAVE_MAX_LABELS) : align_chunks(ALIGN_MAX_LABELS)))
+    return bad_launch(err, "ctc_forward_ends: more states than the kernel holds");
+  const size_t lds = (size_t)2 * (size_t)a.max_chunks * sizeof(double);  // (ctc_forward_ends) <= 16 KB
+  return timed_launch(K_FORWARD, stream, err, [&] {
+    for_dtype(a.dtype, [&](auto dt) {
+      constexpr int DT = decltype(dt)::value;
+      if (wave) {
+        hipLaunchKernelGGL(ctc_forward_wave_ends<DT>, dim3((unsigned)((a.n_hyps + FORWARD_WAVES - 1) / FORWARD_WAVES)), dim3(ALIGN_THREADS), 0, stream, a, ends);
+        return;
+      }
+      for_threads(a.max_chunks, [&](auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        hipLaunchKernelGGL((ctc_forward_ends<NT, DT>), dim3((unsigned)a.n_hyps), dim3(NT), lds, stream, a, ends);
+      });
+    });
+  });
+}
+
+// ctc_prefix_extend and, for a split launch, ctc_prefix_finish behind it
+int launch_ctc_prefix_extend_on(const PrefixExtendArgs& a, hipStream_t stream, std::string* err) {
+  if (a.n_chunks <= 0) return 0;
+  const int64_t blocks = (int64_t)a.n_chunks * prefix_tiles(a.n_labels);
+  if (a.dtype < 0 || a.dtype > 3 || a.n_labels < 1 || a.blank < 0 || a.blank >= a.n_labels || a.max_segs < 1 || a.max_segs > 65535 ||
+      blocks > (int64_t)0x7FFFFFFF || !a.chunks || !a.ends || !a.last || !a.next || (a.split && !a.partial))
+    return bad_launch(err, "ctc_prefix_extend: bad arguments");
+  const dim3 grid((unsigned)blocks, a.split ? (unsigned)a.max_segs : 1u);
+  if (timed_launch(K_PREFIX_EXTEND, stream, err, [&] {
+        for_dtype(a.dtype, [&](auto dt) {
+          hipLaunchKernelGGL(ctc_prefix_extend<decltype(dt)::value>, grid, dim3(PREFIX_COLS), 0, stream, a);
+        });
+      }))
+    return -1;
+  if (!a.split) return 0;
+  return timed_launch(K_PREFIX_EXTEND, stream, err, [&] {
+    hipLaunchKernelGGL(ctc_prefix_finish, dim3((unsigned)blocks), dim3(PREFIX_COLS), 0, stream, a);
+  });
+}
+
+int launch_ctc_prefix_fill_on(double* next, const int32_t* rows, int32_t n_rows, int32_t V, hipStream_t stream, std::string* err) {
+  if (n_rows <= 0) return 0;
+  if (!next || !rows || V < 1 || n_rows > 65535) return bad_launch(err, "ctc_prefix_fill: bad arguments");
+  return timed_launch(K_PREFIX_EXTEND, stream, err, [&] {
+    hipLaunchKernelGGL(ctc_prefix_fill, dim3((unsigned)prefix_tiles(V), (unsigned)n_rows), dim3(PREFIX_COLS), 0, stream, next, rows, V);
   });
 }
 

@@ -189,6 +189,23 @@ class GappedAlignment:
     word_logp: Optional[List[float]] = None
 
 
+@dataclasses.dataclass(frozen=True, eq=False)
+class PrefixScores:
+    """How probable it is that the transcript starts with a prefix, and with the prefix followed by each label
+    (BeamSearchDecoderCTC.prefix_scores / prefix_scores_batch; DESIGN.md, "Prefix scores"). ``tokens`` are the prefix' label
+    ids and ``text`` its normalised text -- with one trailing space where the prefix ends on the space label of a character
+    alphabet. ``logp_end`` is the CTC forward score of the prefix as the whole transcript: the float score / score_batch
+    returns for it. ``next_logp`` (float64 ``[V]``) holds for every label c the natural log of the mass of all alignments
+    whose labels start with ``tokens + [c]`` -- for normalised rows the probability that the transcript starts so --,
+    ``-inf`` for the blank and wherever no frame is left for c. For host input it is a numpy array, for device tensors a
+    torch tensor on the same device: a view of the call's one ``[prefixes, V]`` allocation."""
+
+    text: str
+    tokens: List[int]
+    logp_end: float
+    next_logp: Any
+
+
 @dataclasses.dataclass(frozen=True)
 class ScoredText:
     """How probable a transcript is, given the audio (BeamSearchDecoderCTC.score / score_batch): ``logp`` is the CTC forward
@@ -1277,6 +1294,13 @@ class BeamSearchDecoderCTC:
         self.last_greedy_timing_ms = (0.0, 0.0, 0.0, 0.0)
         self.last_greedy_launches = 0
         self.last_greedy_lse_ms = 0.0
+        # ... and of the last prefix_scores / prefix_scores_batch call (ms: classification, row_lse, forward kernels with end
+        # states, ctc_prefix_extend, native call; prefixes taken by the wave and by the group forward kernel; kernel launches
+        # of row_lse, of the forward kernels and of ctc_prefix_extend with its finish and fill) and, for device input, the [prefixes, V] tensor every next_logp of that call is a view of
+        self.last_prefix_timing_ms = (0.0, 0.0, 0.0, 0.0, 0.0)
+        self.last_prefix_launched = (0, 0)
+        self.last_prefix_launches = (0, 0, 0)
+        self.last_prefix_next = None
 
     def __del__(self):
         h = getattr(self, "_handle", None)
@@ -2154,8 +2178,10 @@ class BeamSearchDecoderCTC:
             wlp = [min(tlp[lo:hi]) for _w, lo, hi in words]
         return GreedyText(text, ids, tok, wf, tlp, wlp, float(score[0]) if fold else None)
 
-    def _many_targets_each(self, what: str, item: str, items: str, logits_list: Any, texts, tokens):
-        """The label ids of any number of given texts or token lists per utterance, checked: (logits_list, ids[u][j])."""
+    def _many_targets_each(self, what: str, item: str, items: str, logits_list: Any, texts, tokens, ids_of_text=None):
+        """The label ids of any number of given texts or token lists per utterance, checked: (logits_list, ids[u][j]).
+        ``ids_of_text``: how a text becomes label ids (_target_of_text unless given)."""
+        ids_of_text = ids_of_text or self._target_of_text
         if (texts is None) == (tokens is None):
             raise ValueError("%s: give exactly one of texts and tokens" % what)
         if texts is not None and self._is_bpe:
@@ -2180,7 +2206,7 @@ class BeamSearchDecoderCTC:
                 if texts is not None:
                     if not isinstance(g, str):
                         raise ValueError("%s: %s is not a str" % (what, who))
-                    ids = self._target_of_text(g)
+                    ids = ids_of_text(g)
                 else:
                     if isinstance(g, str):
                         raise ValueError("%s: %s is a str, not a sequence of label ids" % (what, who))
@@ -2261,6 +2287,99 @@ class BeamSearchDecoderCTC:
                 res.append(ScoredText(text, list(ids), lp, lm_logp, lp + (lm_logp or 0.0)))
                 h += 1
             out.append(res)
+        return out
+
+    # -- prefix scores (no reference analogue; DESIGN.md, "Prefix scores") -----------------------------------
+    def _prefix_of_text(self, text: str) -> List[int]:
+        """The label ids of a prefix given as text (character alphabets): _target_of_text's, and one space label more when
+        the text ends in whitespace after a character -- "bugs " ends on a word boundary, "bugs" does not."""
+        ids = self._target_of_text(text)
+        if ids and text[-1:].isspace():
+            space = self._vocab2idx.get(" ")
+            if space is None:
+                raise ValueError("the prefix %r ends on a word boundary, but the alphabet has no space label" % text)
+            ids.append(space)
+        return ids
+
+    def prefix_scores(self, logits: Any, texts: Optional[Sequence[str]] = None,
+                      tokens: Optional[Sequence[Sequence[int]]] = None) -> List["PrefixScores"]:
+        """The prefix scores of each prefix for one utterance: prefix_scores_batch of a batch of one."""
+        self._check_logits_dimension(logits)
+        return self.prefix_scores_batch([logits], None if texts is None else [texts], tokens=None if tokens is None else [tokens])[0]
+
+    def prefix_scores_batch(self, logits_list: Any, texts: Optional[Sequence[Sequence[str]]] = None,
+                            tokens: Optional[Sequence[Sequence[Sequence[int]]]] = None) -> List[List["PrefixScores"]]:
+        """What an external decoder asks at every step, in one native call: per utterance any number of prefixes, per prefix
+        the CTC prefix score of every label at once as PrefixScores (row_lse once per utterance, ctc_forward_ends /
+        ctc_forward_wave_ends per prefix, ctc_prefix_extend over the rows for eight prefixes of an utterance at a time;
+        csrc/ctc_align_hip.hip). ``logits_list`` is what align_batch takes; ``texts[u]`` (character alphabets) is a list of
+        str -- whitespace runs collapse and leading whitespace is dropped as everywhere, but trailing whitespace is kept as
+        one space label --, ``tokens[u]`` a list of lists of label ids, the only form for BPE alphabets; ``[]`` or ``""`` is
+        the empty prefix. The call is stateless: nothing is carried from one step's prefixes to the next's. Host arrays give
+        numpy arrays; device tensors give torch tensors on the same device, views of ``last_prefix_next``, which the
+        kernels write in place."""
+        logits_list, prefixes = self._many_targets_each("prefix_scores", "prefix", "prefixes", logits_list, texts, tokens,
+                                                        ids_of_text=self._prefix_of_text)
+        n, n_labels = len(prefixes), len(self._labels_list)
+        self.last_prefix_timing_ms, self.last_prefix_launched, self.last_prefix_launches = (0.0,) * 5, (0, 0), (0, 0, 0)
+        self.last_prefix_next = None
+        if n == 0:
+            return []
+        kernel_env = os.environ.get("CTCDEC_FORWARD_KERNEL", "")
+        if kernel_env and kernel_env not in FORWARD_KERNELS:
+            raise ValueError("CTCDEC_FORWARD_KERNEL must be wave or group, not %r" % kernel_env)
+        with self._call_lock:
+            batch, frames, ptrs = self._stage_transcript_call(logits_list)
+            flat_prefixes = [ids for cur in prefixes for ids in cur]
+            nh = len(flat_prefixes)
+            flat, label_off = self._pack_ids(flat_prefixes)
+            prefix_off = np.zeros(n + 1, dtype=np.int64)
+            prefix_off[1:] = np.cumsum([len(cur) for cur in prefixes])
+            # one [prefixes, V] block of float64: for device tensors the shell makes it and the kernels fill it in place
+            buf, next_ptr = None, None
+            if batch.is_device and nh:
+                import torch
+
+                buf = torch.empty((nh, n_labels), dtype=torch.float64, device=batch.keep[0].device)
+                next_ptr = C.c_void_p(buf.data_ptr())
+            res = C.c_void_p()
+            lib = self._lib
+            lib.check(lib.dll.ctcdec_prefix_batch(
+                self._handle, ptrs.ctypes.data_as(C.POINTER(C.c_void_p)), frames.ctypes.data_as(C.POINTER(C.c_int32)), n,
+                batch.dtype, int(batch.is_device), flat.ctypes.data_as(C.POINTER(C.c_int32)), B.off_ptr(label_off),
+                B.off_ptr(prefix_off), FORWARD_KERNELS.get(kernel_env, 0), next_ptr, C.byref(res)))
+            try:
+                end_p, next_p, np_, nv = C.POINTER(C.c_double)(), C.POINTER(C.c_double)(), C.c_int64(), C.c_int32()
+                lib.check(lib.dll.ctcdec_prefix_scores(res, C.byref(end_p), C.byref(next_p), C.byref(np_), C.byref(nv)))
+                if int(np_.value) != nh or int(nv.value) != n_labels:
+                    raise B.NativeError("the prefix result holds another number of scores than was asked for")
+                end = np.ctypeslib.as_array(end_p, shape=(nh,)).copy() if nh else np.zeros(0, dtype=np.float64)
+                if buf is None:
+                    buf = (np.ctypeslib.as_array(next_p, shape=(nh, n_labels)).copy() if nh
+                           else np.zeros((0, n_labels), dtype=np.float64))
+                ms, launches, launched = (C.c_double * 5)(), (C.c_int32 * 3)(), (C.c_int64 * 2)()
+                lib.dll.ctcdec_prefix_timing(res, ms, launches, launched)
+                # [classification (frame-prune kernels), row_lse, forward kernels with end states, ctc_prefix_extend (HIP
+                # events), whole native call]; prefixes that went to (ctc_forward_wave_ends, ctc_forward_ends)
+                self.last_prefix_timing_ms = tuple(float(v) for v in ms)
+                self.last_prefix_launches = tuple(int(v) for v in launches)
+                self.last_prefix_launched = (int(launched[0]), int(launched[1]))
+            finally:
+                lib.dll.ctcdec_prefix_free(res)
+            if batch.is_device:
+                self.last_prefix_next = buf
+        space = None if self._is_bpe else self._vocab2idx.get(" ")
+        rows = buf.unbind(0) if batch.is_device else list(buf)  # (every row's view in one call)
+        ends = end.tolist()
+        out: List[List[PrefixScores]] = []
+        h = 0
+        for cur in prefixes:
+            got = []
+            for ids in cur:
+                text = self._words_of_target(ids)[0] + (" " if ids and ids[-1] == space else "")
+                got.append(PrefixScores(text, list(ids), ends[h], rows[h]))
+                h += 1
+            out.append(got)
         return out
 
     # -- phrase search (no reference analogue; DESIGN.md, "Phrase search") ----------------------------------

@@ -226,6 +226,11 @@ def decode_greedy_batch_sharded(decoder, logits_list, group=None, **kwargs):
     raise NotImplementedError("decode_greedy_batch is not gathered over ranks: decode each rank's slice with decoder.decode_greedy_batch itself")
 
 
+def prefix_scores_batch_sharded(decoder, logits_list, texts=None, group=None, **kwargs):
+    """Prefix scores are not sharded over ranks: each rank calls decoder.prefix_scores_batch on its own slice."""
+    raise NotImplementedError("prefix_scores_batch is not gathered over ranks: call decoder.prefix_scores_batch on each rank's slice itself")
+
+
 def _device_worker(conn, device: int, decoder_dir: str, library: Optional[str]) -> None:
     """One worker process = one GPU (the native library binds one device per process): loads the saved decoder on its device and
     serves (method, logits, kwargs) requests until it is told to stop."""
@@ -384,6 +389,12 @@ class DevicePool:
         raise NotImplementedError("DevicePool does not shard decode_greedy_batch: call decoder.decode_greedy_batch on the process's own device")
 
     decode_greedy = decode_greedy_batch
+
+    def prefix_scores_batch(self, logits_list, texts=None, **kwargs):
+        """Prefix scores run on the calling process's own device: a pool does not shard them."""
+        raise NotImplementedError("DevicePool does not shard prefix_scores_batch: call decoder.prefix_scores_batch on the process's own device")
+
+    prefix_scores = prefix_scores_batch
 
     def decode_batch(self, logits_list, **kwargs) -> List[str]:
         if kwargs.get("token_frames") or kwargs.get("confidence") is not None:  # (texts, TokenFrames) per slice -> one of each, offsets rebased

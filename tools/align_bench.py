@@ -6,7 +6,7 @@ substituted), each forward kernel forced in turn -- and at 64 utterances, with t
 for scale; then a sweep of target lengths on 256 utterances of random logits, which is what the wave / group threshold of
 ctcdec_score_batch rests on. Kernel times are HIP events on the decode stream (ctcdec_alignment_timing, ctcdec_score_batch,
 ctcdec_posteriors_timing).
-  python tools/align_bench.py [--out profiles/align_bench.txt] [--steps 3] [--legs align,score,posteriors,sweep,gradient,find,gaps,greedy]
+  python tools/align_bench.py [--out profiles/align_bench.txt] [--steps 3] [--legs align,score,posteriors,sweep,gradient,find,gaps,greedy,prefix]
 The gradient leg (not in the default set) times gradient_batch -- ctc_grad_rows alone, next to posteriors_batch(dense=False).
 The find leg (not in the default set either) times find_batch -- ctc_find / ctc_find_wave forced in turn, alternating: at the
 bench shape each utterance searched for 1 and for 8 phrases of 8 labels cut from its own decoded tokens, then 256 and 2048
@@ -16,6 +16,9 @@ row_lse_max against row_lse, ctc_viterbi_gaps on the gap-free targets against ct
 ctc_viterbi_gaps again with a leading gap, a trailing gap and one gap at every word boundary.
 The greedy leg (not in the default set either) times decode_greedy_batch: row_argmax, row_lse_argmax and greedy_collapse,
 next to row_lse_max and decode_batch's frame-prune stage on the same batch in the same rounds, alternating.
+The prefix leg (not in the default set either) times prefix_scores_batch with 1, 8 and 16 prefixes of about 20 labels per
+utterance -- the first 20 of its decoded tokens, and copies with one label substituted --: ctc_prefix_extend, the forward
+kernels with end states next to score_batch's plain ones on the same prefixes in the same rounds, alternating, and row_lse.
 The 4096 utterances are 256 distinct ones repeated: no kernel's time depends on the rows being distinct."""
 import argparse
 import os
@@ -323,6 +326,51 @@ def greedy_lines(dec, dev, targets, n, steps):
     ]
 
 
+def prefix_lines(dec, dev, targets, n, steps):
+    rng = np.random.default_rng(11)
+    blank = dec._alphabet.labels.index("")
+    pool = [c for c in range(V) if c != blank]
+    sixteen = []
+    for t in targets:
+        head = list(t[:20])
+        cur = [head]
+        for _ in range(15):
+            sub = list(head)
+            if sub:
+                sub[int(rng.integers(0, len(sub)))] = pool[int(rng.integers(0, len(pool)))]
+            cur.append(sub)
+        sixteen.append(cur)
+    read = n * T * V * 4
+    lines = ["  prefix scores, prefixes of %.0f labels on average" % np.mean([len(c[0]) for c in sixteen])]
+    ext_of = {}
+    for per_utt in (1, 8, 16):
+        prefixes = [c[:per_utt] for c in sixteen]
+        got = {k: [] for k in ("extend", "ends", "lse", "native", "wall", "plain")}
+        for step in range(steps + 1):
+            t0 = time.perf_counter()
+            out = dec.prefix_scores_batch(dev, tokens=prefixes)
+            wall = (time.perf_counter() - t0) * 1e3
+            ms = dec.last_prefix_timing_ms
+            dec.score_batch(dev, tokens=prefixes)
+            if step:
+                for k, v in (("extend", ms[3]), ("ends", ms[2]), ("lse", ms[1]), ("native", ms[4]), ("wall", wall),
+                             ("plain", dec.last_score_timing_ms[2])):
+                    got[k].append(v)
+        assert all(np.isfinite(g.logp_end) for per in out for g in per)
+        del out
+        m = lambda k: float(np.median(got[k]))  # noqa: E731
+        spread = lambda k: max(got[k]) - min(got[k])  # noqa: E731
+        ext_of[per_utt] = m("extend")
+        lines.append("  %2d prefix(es) per utterance: ctc_prefix_extend %9.3f ms (spread %.3f; %.2f TB/s of the %.2f GB of logits per chunk "
+                     "of 8)  forward with end states %9.3f ms  plain forward (score_batch, same rounds) %9.3f ms  ratio %.3f  (spreads %.3f / %.3f)"
+                     % (per_utt, m("extend"), spread("extend"), -(-per_utt // 8) * read / (m("extend") * 1e-3) / 1e12, read / 1e9,
+                        m("ends"), m("plain"), m("ends") / m("plain"), spread("ends"), spread("plain")))
+        lines.append("      row_lse %9.3f ms  (ctc_prefix_extend / row_lse %.2f)  native call %9.3f ms  Python call %9.3f ms  launches %s"
+                     % (m("lse"), m("extend") / m("lse"), m("native"), m("wall"), dec.last_prefix_launches))
+    lines.append("    ctc_prefix_extend, 8 prefixes / 1 prefix: %.2f   16 / 8: %.2f" % (ext_of[8] / ext_of[1], ext_of[16] / ext_of[8]))
+    return lines
+
+
 def time_forward(dec, dev, hyps, kernels, steps):
     """The forward kernels' time (HIP events) under each forced kernel: one warm-up call each, then `steps` rounds that
     alternate between them (clocks as they come: neither kernel gets the warmer half of the run). -> {kernel: median ms}"""
@@ -463,6 +511,8 @@ def main():
             lines += gaps_lines(dec, dev, targets, args.steps)
         if "greedy" in legs:
             lines += greedy_lines(dec, dev, targets, n, args.steps)
+        if "prefix" in legs:
+            lines += prefix_lines(dec, dev, targets, n, args.steps)
         del dev
     if "sweep" in legs:
         lines += sweep_lines(dec, max(args.steps, 5))
