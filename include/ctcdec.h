@@ -501,6 +501,48 @@ int ctcdec_prefix_scores(const ctcdec_prefix* p, const double** end, const doubl
 int ctcdec_prefix_timing(const ctcdec_prefix* p, double* ms5, int32_t* launches3, int64_t* launched2);
 void ctcdec_prefix_free(ctcdec_prefix* p);
 
+/* ---- prefix sessions: ctcdec_prefix_batch for a decoding loop -- a prefix is extended by one label in O(T) ---------------
+ * A decoding loop's prefixes are each a parent of the step before plus one label. A session keeps, per live prefix, what
+ * ctcdec_prefix_batch's forward pass leaves behind for it -- bc[t] = a_{t-1}[S-1], bc[T + t] = a_{t-1}[S-2] and their
+ * maximum, `scale` -- in a slot of an arena, and forms the child g + [c] from the slot of g alone, by a recursion over the
+ * child's two new states, its last label y and its final blank z:
+ *   y_0 = e(0, c) for the empty g, else -inf;   z_0 = -inf;
+ *   y_t = lse3(y_{t-1}, bc_g[t], c != last(g) ? bc_g[T + t] : -inf) + e(t, c),    z_t = lse2(z_{t-1}, y_{t-1}) + e(t, blank),
+ *   bc[t] = z_{t-1},  bc[T + t] = y_{t-1},  end = lse2(z_{T-1}, y_{T-1})
+ * (kernel ctc_prefix_advance, one launch per extend), followed by ctcdec_prefix_batch's own ctc_prefix_extend over the new
+ * slots. The recursion applies the forward pass' functions to the forward pass' operands in its order, so end and next of
+ * every prefix of a session are, bit for bit, what ctcdec_prefix_batch returns for the same labels on the same input. The
+ * classification and the row log-sum-exps are computed once, by ctcdec_prefix_session_open.
+ * open: logits, frame counts, dtype and is_device as in ctcdec_prefix_batch. The session copies the row log-sum-exps, the
+ * classification and, for host input, the staged matrices into memory of its own; device matrices are read in place by
+ * every later extend and have to outlive the session. `capacity` slots (>= n_utts) of 2 * max(T) doubles plus a scale are
+ * allocated at once and never grow. Utterance u's empty prefix takes slot u for the session's lifetime: its id goes to
+ * root_ids[u], its end to root_end[u], its next to row u of next_out (is_device only: device memory [n_utts][V], written
+ * in place) or of next_host (host memory of that shape); exactly one of the two is given.
+ * extend: child i is parents[i] followed by labels[i]. Checked before anything is launched or taken: every parent a live
+ * id of this session, every label inside the alphabet and not the blank (CTCDEC_ERR_ARG), no child longer than 2047
+ * labels and n free slots (CTCDEC_ERR_LIMIT; the session is unchanged and usable). A parent may appear any number of
+ * times; the ids of a call's children come back with the call, so none of them can be a parent in it. ids_out[n],
+ * end_out[n], and next as for open, [n][V]. A child with fewer frames than labels plus adjacent equal labels has end and
+ * next of -inf throughout, as in ctcdec_prefix_batch.
+ * release: the slots of the ids become free; an id stays dead when its slot is handed out again. Releasing an empty
+ * prefix, a dead id or one id twice is CTCDEC_ERR_ARG, and nothing is released. A prefix stays usable as a parent until it
+ * is released, whatever became of its own parent.
+ * timing, of the last open or extend: ms3 = [0] ctc_prefix_advance, [1] ctc_prefix_extend with ctc_prefix_finish and the
+ * fill (HIP events on the decode stream), [2] the whole native call; launches4 (may be NULL) = kernel launches of [0]
+ * ctc_prefix_advance, [1] ctc_prefix_extend, ctc_prefix_finish and the fill, [2] row_lse, [3] the forward kernels -- the
+ * last two are 0 for an extend.
+ * Every entry takes the device lock. The decoder has to outlive its sessions. decoder.py: prefix_session. */
+typedef struct ctcdec_prefix_session ctcdec_prefix_session; /* opaque */
+int ctcdec_prefix_session_open(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts,
+                               int32_t dtype, int32_t is_device, int64_t capacity, double* next_out, int64_t* root_ids,
+                               double* root_end, double* next_host, ctcdec_prefix_session** out);
+int ctcdec_prefix_session_extend(ctcdec_prefix_session* s, const int64_t* parents, const int32_t* labels, int64_t n,
+                                 double* next_out, int64_t* ids_out, double* end_out, double* next_host);
+int ctcdec_prefix_session_release(ctcdec_prefix_session* s, const int64_t* ids, int64_t n);
+int ctcdec_prefix_session_timing(const ctcdec_prefix_session* s, double* ms3, int32_t* launches4);
+void ctcdec_prefix_session_close(ctcdec_prefix_session* s);
+
 /* ---- frame posteriors: where, under ALL alignments of a label sequence the caller already has, each frame lies ---------
  * No reference analogue: the CTC forward-backward. Utterance u's target is labels[label_off[u] .. label_off[u + 1]) (alphabet
  * indices, never the blank; at most 2047 of them); logits, frame counts, dtype, is_device, the probabilities-or-logits rule

@@ -173,6 +173,13 @@ _PROTOS = {
                                        C.POINTER(C.c_int32)]),
     "ctcdec_prefix_timing": (C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "ctcdec_prefix_free": (None, [_VP]),
+    "ctcdec_prefix_session_open": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int64,
+                                             _VP, C.POINTER(C.c_int64), C.POINTER(C.c_double), _VP, C.POINTER(_VP)]),
+    "ctcdec_prefix_session_extend": (C.c_int, [_VP, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int64, _VP,
+                                               C.POINTER(C.c_int64), C.POINTER(C.c_double), _VP]),
+    "ctcdec_prefix_session_release": (C.c_int, [_VP, C.POINTER(C.c_int64), C.c_int64]),
+    "ctcdec_prefix_session_timing": (C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
+    "ctcdec_prefix_session_close": (None, [_VP]),
     "ctcdec_score_batch": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32,
                                      C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32,
                                      C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

@@ -228,7 +228,8 @@ struct ctcdec_decoder {
   DevBuf w_garg, w_gcnt, w_gtoff, w_glab, w_gspan, w_glogp;
   // prefix scores (ctcdec_prefix_batch): the end states and scales the forward pass stores, their records in launch order
   // and by prefix, the prefixes' last labels, the chunks, a split launch's sums, the rows without a launch and, for host
-  // callers, the result (labels: w_alab, scores: w_ascore, hypothesis records: w_fhyps)
+  // callers, the result (labels: w_alab, scores: w_ascore, hypothesis records: w_fhyps). A prefix session's calls use the
+  // same ones for a step's records, and w_fhyps for its children's
   DevBuf w_xends, w_xscale, w_xrecl, w_xrech, w_xlast, w_xchunks, w_xpart, w_xrows, w_xnext;
   bool slicing = false;  // a time-sliced host ingest is under way (decode_host_sliced): the prune stage notes each slice's side of 1
   uint32_t max_label_bytes = 1;
@@ -3414,6 +3415,413 @@ int ctcdec_prefix_timing(const ctcdec_prefix* p, double* ms5, int32_t* launches3
 }
 
 void ctcdec_prefix_free(ctcdec_prefix* p) { delete p; }
+
+// ---- prefix sessions ("Prefix sessions") ------------------------------------------------------------------------
+}  // extern "C"
+
+// What outlives a call: the batch's row log-sum-exps, classification and (host input) staged matrices, and an arena of
+// `capacity` slots of 2 * T_max end states plus a scale. Slot s < n_utts is the root of utterance s. An id is a slot under
+// the tag it was handed out with; tags come from one counter for all sessions, so a stale id and another session's id
+// both fail the same test.
+struct ctcdec_prefix_session {
+  ctcdec_decoder* dec = nullptr;
+  TranscriptCall tc;
+  int32_t n_utts = 0, dtype = 0, T_max = 0;
+  bool is_device = false;
+  int64_t capacity = 0;
+  std::vector<int32_t> frames;
+  std::vector<const void*> ptrs;  // (device) the utterances' matrices: the caller's tensors, or rows of `logits`
+  std::vector<uint32_t> is_prob;
+  std::vector<int64_t> row0;
+  DevBuf logits, lse, arena, scales;
+  std::vector<uint32_t> tag;      // per slot: 0 while free
+  std::vector<int32_t> utt, last, len;
+  std::vector<int64_t> free_slots;  // taken from the back: the lowest slot first
+  double ms[3] = {0, 0, 0};
+  int32_t launches[4] = {0, 0, 0, 0};
+  double* bc(int64_t slot) const { return (double*)arena.p + (size_t)slot * 2 * (size_t)T_max; }
+  double* scale(int64_t slot) const { return (double*)scales.p + slot; }
+  const double* lse_of(int32_t u) const { return (const double*)lse.p + row0[(size_t)u]; }
+};
+
+static uint32_t g_session_tag = 0;  // (under the device lock)
+static uint32_t session_next_tag() {
+  if (++g_session_tag == 0) ++g_session_tag;
+  return g_session_tag;
+}
+static int64_t session_id(uint32_t tag, int64_t slot) { return (int64_t)(((uint64_t)tag << 31) | (uint64_t)slot); }
+// The slot of a live id, -1 for anything else
+static int64_t session_slot(const ctcdec_prefix_session* s, int64_t id) {
+  if (id < 0) return -1;
+  const int64_t slot = id & (int64_t)0x7FFFFFFF;
+  const uint32_t tag = (uint32_t)((uint64_t)id >> 31);
+  return slot < s->capacity && tag != 0 && s->tag[(size_t)slot] == tag ? slot : -1;
+}
+
+// The second half of an open or an extend: the call's prefixes are slots[i], in the caller's order, their end states and
+// scales in the arena and their `end` in dec->w_ascore[i] (device). Every label's score by ctc_prefix_extend, in chunks of up
+// to PREFIX_K prefixes of one utterance, into next_out (device) or the decoder's block and from there into next_host; `end`
+// into end_out. An utterance without frames launches nothing: its empty prefix has end 0.0, every other -inf, next is -inf.
+static int session_deliver(ctcdec_prefix_session* s, const std::vector<int64_t>& slots, double* next_out, double* end_out,
+                           double* next_host) {
+  ctcdec_decoder* dec = s->dec;
+  const int V = s->tc.V;
+  const double NEG = align_neg_inf();
+  const size_t n = slots.size();
+  if (n == 0) return CTCDEC_OK;
+  std::string err;
+  double* next = next_out;
+  if (!next) {
+    if (dec->w_xnext.ensure(n * (size_t)V * 8, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+    next = (double*)dec->w_xnext.p;
+  }
+  std::vector<PrefixEnds> rec_h(n, PrefixEnds{nullptr, nullptr});
+  std::vector<int32_t> last(n, -1), dead, order;
+  for (size_t i = 0; i < n; ++i) {
+    const int64_t slot = slots[i];
+    last[i] = s->last[(size_t)slot];
+    if (s->frames[(size_t)s->utt[(size_t)slot]] == 0) {
+      dead.push_back((int32_t)i);
+      continue;
+    }
+    rec_h[i] = PrefixEnds{s->bc(slot), s->scale(slot)};
+    order.push_back((int32_t)i);
+  }
+  if (next_out && !dead.empty()) {
+    if (upload(dec->w_xrows, dead, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+#ifdef CTC_SIM
+    for (int32_t h : dead)
+      for (int c = 0; c < V; ++c) next[(size_t)h * (size_t)V + (size_t)c] = NEG;
+#else
+    for (size_t at = 0; at < dead.size(); at += 65535) {
+      const int32_t rows = (int32_t)std::min<size_t>(65535, dead.size() - at);
+      if (be::launch_ctc_prefix_fill(next, (const int32_t*)dec->w_xrows.p + at, rows, V, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+    }
+#endif
+  }
+  if (!order.empty()) {
+    // the chunks: an utterance's prefixes of the call in the caller's order, PREFIX_K at a time
+    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return s->utt[(size_t)slots[(size_t)a]] < s->utt[(size_t)slots[(size_t)b]]; });
+    std::vector<PrefixChunk> chunks;
+    int32_t max_segs = 1;
+    for (size_t at = 0; at < order.size();) {
+      const int32_t u = s->utt[(size_t)slots[(size_t)order[at]]];
+      PrefixChunk ch{};
+      ch.x = s->ptrs[(size_t)u];
+      ch.lse = s->lse_of(u);
+      ch.T = s->frames[(size_t)u];
+      ch.is_prob = s->is_prob[(size_t)u] ? 1 : 0;
+      for (; at < order.size() && s->utt[(size_t)slots[(size_t)order[at]]] == u; ++at) {
+        ch.h[ch.n++] = order[at];
+        if (ch.n == PREFIX_K) chunks.push_back(ch), ch.n = 0;
+      }
+      if (ch.n) chunks.push_back(ch);
+      max_segs = std::max(max_segs, prefix_segments(ch.T));
+    }
+    PrefixExtendArgs xa;
+    xa.n_chunks = (int32_t)chunks.size();
+    xa.n_labels = V;
+    xa.dtype = s->dtype;
+    xa.blank = s->tc.blank;
+    xa.max_segs = max_segs;
+    xa.split = prefix_split((int64_t)chunks.size(), V) ? 1 : 0;
+    xa.clip_lo = s->tc.clip_lo;
+    const size_t part = xa.split ? chunks.size() * (size_t)max_segs * PREFIX_K * (size_t)V : 1;
+    if (dec->w_xpart.ensure(part * 8, &err) || upload(dec->w_xrech, rec_h, &err) || upload(dec->w_xlast, last, &err) ||
+        upload(dec->w_xchunks, chunks, &err))
+      return fail(CTCDEC_ERR_DEVICE, err);
+    xa.chunks = (const PrefixChunk*)dec->w_xchunks.p;
+    xa.ends = (const PrefixEnds*)dec->w_xrech.p;
+    xa.last = (const int32_t*)dec->w_xlast.p;
+    xa.next = next;
+    xa.partial = (double*)dec->w_xpart.p;
+#ifdef CTC_SIM
+    AlignSeqCtx cx;
+    std::vector<double> w((size_t)PREFIX_W_DOUBLES);
+    for (int32_t k = 0; k < xa.n_chunks; ++k) {
+      const int nseg = prefix_segments(chunks[(size_t)k].T);
+      for (int c = 0; c < V; ++c) {
+        for_dtype(s->dtype, [&](auto dt) {
+          if (!xa.split) return ctc_prefix_extend_tile<decltype(dt)::value>(cx, xa, k, c, 0, nseg, w.data());
+          for (int seg = 0; seg < nseg; ++seg) ctc_prefix_extend_tile<decltype(dt)::value>(cx, xa, k, c, seg, seg + 1, w.data());
+        });
+        if (xa.split) ctc_prefix_finish_col(xa, k, c);
+      }
+    }
+#else
+    if (be::launch_ctc_prefix_extend(xa, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+#endif
+  }
+  std::vector<double> got(n, NEG);
+  if (!order.empty() && be::d2h(got.data(), dec->w_ascore.p, n * 8, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+  if (next_host) {
+    if (!order.empty() && be::d2h(next_host, next, n * (size_t)V * 8, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+    for (int32_t h : dead) std::fill(next_host + (size_t)h * (size_t)V, next_host + ((size_t)h + 1) * (size_t)V, NEG);
+  }
+  for (int32_t h : dead) got[(size_t)h] = s->len[(size_t)slots[(size_t)h]] == 0 ? 0.0 : NEG;
+  std::copy(got.begin(), got.end(), end_out);
+  if (be::sync(&err)) return fail(CTCDEC_ERR_DEVICE, err);
+  return CTCDEC_OK;
+}
+
+// The timers and launch counts of the call that ends here (the kernels' event logs since the call's reset)
+static void session_timing(ctcdec_prefix_session* s, Clock::time_point t_begin, int32_t sim_advances) {
+#ifdef CTC_SIM
+  s->ms[0] = s->ms[1] = 0;
+  s->launches[0] = sim_advances;  // (the simulator runs the body over all children once: counted as the one launch it stands for)
+  s->launches[1] = s->launches[2] = s->launches[3] = 0;
+#else
+  (void)sim_advances;
+  s->ms[0] = be::align_kernel_ms(be::K_PREFIX_ADVANCE);
+  s->ms[1] = be::align_kernel_ms(be::K_PREFIX_EXTEND);
+  s->launches[0] = be::align_kernel_launches(be::K_PREFIX_ADVANCE);
+  s->launches[1] = be::align_kernel_launches(be::K_PREFIX_EXTEND);
+  s->launches[2] = be::align_kernel_launches(be::K_ROW_LSE);
+  s->launches[3] = be::align_kernel_launches(be::K_FORWARD);
+#endif
+  s->ms[2] = ms(t_begin, Clock::now());
+}
+
+extern "C" {
+
+int ctcdec_prefix_session_open(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts,
+                               int32_t dtype, int32_t is_device, int64_t capacity, double* next_out, int64_t* root_ids,
+                               double* root_end, double* next_host, ctcdec_prefix_session** out) {
+  TranscriptCall tc;
+  const bool args_ok = dec && out && n_utts >= 0 && (n_utts == 0 || (utt_logits && utt_frames && root_ids && root_end));
+  if (int rc = transcript_open(dec, args_ok, dtype, "", tc)) return rc;
+  const size_t n = (size_t)n_utts;
+  int32_t T_max = 0;
+  for (int32_t u = 0; u < n_utts; ++u) {
+    if (utt_frames[u] < 0) return fail(CTCDEC_ERR_ARG, "utterance " + std::to_string(u) + ": negative frame count");
+    if (utt_frames[u] > 0 && !utt_logits[u]) return fail(CTCDEC_ERR_ARG, "utterance " + std::to_string(u) + ": no logits");
+    T_max = std::max(T_max, utt_frames[u]);
+  }
+  if (capacity < n_utts)
+    return fail(CTCDEC_ERR_ARG, "a session needs a slot for every utterance's empty prefix: capacity " + std::to_string(capacity) +
+                                    " for " + std::to_string(n_utts) + " utterances");
+  if (capacity > (int64_t)0x7FFFFFFF) return fail(CTCDEC_ERR_LIMIT, "more than 2^31 - 1 slots in one session");
+  if (next_out && !is_device) return fail(CTCDEC_ERR_ARG, "a buffer for next is device memory: it goes with device logits");
+  if (n_utts > 0 && !next_out && !next_host) return fail(CTCDEC_ERR_ARG, "no room for the roots' next");
+  const auto t_begin = Clock::now();
+  std::unique_ptr<ctcdec_prefix_session> s(new ctcdec_prefix_session);
+  s->dec = dec, s->tc = tc, s->n_utts = n_utts, s->dtype = dtype, s->T_max = T_max, s->is_device = is_device != 0, s->capacity = capacity;
+  s->frames.assign(utt_frames, utt_frames + n);
+  s->row0 = row_starts(utt_frames, n);
+  const int64_t R = s->row0[n];
+  const int V = tc.V;
+  std::string err;
+  AlignFront fr;
+  if (R > 0) {
+    if (int rc = align_front(dec, utt_logits, utt_frames, n_utts, dtype, is_device, V, s->row0, fr)) return rc;
+  } else {  // (no frames at all: nothing to stage, classify or sum)
+    fr.device_lock = std::unique_lock<std::mutex>(g_device_mu);
+    if (be::bind_thread(&err)) return fail(CTCDEC_ERR_DEVICE, err);
+#ifndef CTC_SIM
+    be::align_timing_reset();
+#endif
+    fr.ptrs.assign(n, nullptr);
+    fr.is_prob.assign(n, 0);
+  }
+  // what must outlive this call leaves the decoder's workspaces
+  const size_t row_bytes = (size_t)V * dtype_size(dtype);
+  if (s->lse.ensure((size_t)std::max<int64_t>(R, 1) * 8, &err) || s->arena.ensure(std::max<size_t>((size_t)capacity * 2 * (size_t)T_max * 8, 16), &err) ||
+      s->scales.ensure(std::max<size_t>((size_t)capacity * 8, 16), &err))
+    return fail(CTCDEC_ERR_DEVICE, err);
+  if (R > 0 && be::d2d(s->lse.p, fr.lse, (size_t)R * 8, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+  s->is_prob = fr.is_prob;
+  s->ptrs = fr.ptrs;
+  if (!is_device && R > 0) {
+    if (s->logits.ensure((size_t)R * row_bytes, &err) || be::d2d(s->logits.p, dec->w_logits.p, (size_t)R * row_bytes, &err))
+      return fail(CTCDEC_ERR_DEVICE, err);
+    for (size_t u = 0; u < n; ++u) s->ptrs[u] = (const char*)s->logits.p + (size_t)s->row0[u] * row_bytes;
+  }
+  s->tag.assign((size_t)capacity, 0);
+  s->utt.assign((size_t)capacity, -1);
+  s->last.assign((size_t)capacity, -1);
+  s->len.assign((size_t)capacity, 0);
+  for (int64_t slot = capacity - 1; slot >= n_utts; --slot) s->free_slots.push_back(slot);
+  std::vector<int64_t> roots(n);
+  for (size_t u = 0; u < n; ++u) {
+    roots[u] = (int64_t)u;
+    s->tag[u] = session_next_tag();
+    s->utt[u] = (int32_t)u;
+    root_ids[u] = session_id(s->tag[u], (int64_t)u);
+  }
+  // the roots' end states: the forward pass of the empty prefix, by the wave kernel
+  std::vector<ForwardHyp> hyps;
+  std::vector<PrefixEnds> rec_l;
+  if (dec->w_alab.ensure(4, &err) || dec->w_ascore.ensure(std::max<size_t>(n * 8, 16), &err) || be::zero(dec->w_ascore.p, std::max<size_t>(n * 8, 16), &err))
+    return fail(CTCDEC_ERR_DEVICE, err);
+  for (size_t u = 0; u < n; ++u) {
+    if (utt_frames[u] == 0) continue;
+    ForwardHyp a;
+    a.x = s->ptrs[u];
+    a.lse = s->lse_of((int32_t)u);
+    a.lab = (const int32_t*)dec->w_alab.p;
+    a.logp = (double*)dec->w_ascore.p + u;
+    a.T = utt_frames[u];
+    a.L = 0;
+    a.is_prob = s->is_prob[u] ? 1 : 0;
+    a.pad = 0;
+    hyps.push_back(a);
+    rec_l.push_back(PrefixEnds{s->bc((int64_t)u), s->scale((int64_t)u)});
+  }
+#ifdef CTC_SIM
+  {
+    std::vector<double> col((size_t)2);
+    AlignSeqCtx cx;
+    for (size_t i = 0; i < hyps.size(); ++i)
+      for_dtype(dtype, [&](auto dt) { ctc_forward_hyp<decltype(dt)::value, true>(cx, hyps[i], V, tc.blank, tc.clip_lo, col.data(), &rec_l[i]); });
+  }
+#else
+  if (!hyps.empty()) {
+    if (upload(dec->w_fhyps, hyps, &err) || upload(dec->w_xrecl, rec_l, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+    be::ForwardArgs fa;
+    fa.hyps = (const ForwardHyp*)dec->w_fhyps.p;
+    fa.n_hyps = (int32_t)hyps.size();
+    fa.n_labels = V;
+    fa.dtype = dtype;
+    fa.blank = tc.blank;
+    fa.max_chunks = 1;
+    fa.pad = 0;
+    fa.clip_lo = tc.clip_lo;
+    if (be::launch_ctc_forward_ends(fa, (const PrefixEnds*)dec->w_xrecl.p, 1, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+  }
+#endif
+  if (int rc = session_deliver(s.get(), roots, next_out, root_end, next_host)) return rc;
+  session_timing(s.get(), t_begin, 0);
+  *out = s.release();
+  return CTCDEC_OK;
+}
+
+int ctcdec_prefix_session_extend(ctcdec_prefix_session* s, const int64_t* parents, const int32_t* labels, int64_t n, double* next_out,
+                                 int64_t* ids_out, double* end_out, double* next_host) {
+  if (!s || n < 0 || (n > 0 && (!parents || !labels || !ids_out || !end_out))) return fail(CTCDEC_ERR_ARG, "bad arguments");
+  if (next_out && !s->is_device) return fail(CTCDEC_ERR_ARG, "a buffer for next is device memory: it goes with device logits");
+  if (n > 0 && !next_out && !next_host) return fail(CTCDEC_ERR_ARG, "no room for next");
+  std::lock_guard<std::mutex> device_lock(g_device_mu);
+  const auto t_begin = Clock::now();
+  ctcdec_decoder* dec = s->dec;
+  const int V = s->tc.V;
+  // everything before anything is launched or taken
+  std::vector<int64_t> pslot((size_t)n);
+  for (int64_t i = 0; i < n; ++i) {
+    const std::string who = "child " + std::to_string(i);
+    const int64_t p = session_slot(s, parents[i]);
+    if (p < 0) return fail(CTCDEC_ERR_ARG, who + ": parent " + std::to_string(parents[i]) + " is not a live prefix of this session");
+    if (labels[i] < 0 || labels[i] >= V) return fail(CTCDEC_ERR_ARG, who + ": label " + std::to_string(labels[i]) + " is outside the alphabet");
+    if (labels[i] == s->tc.blank) return fail(CTCDEC_ERR_ARG, who + ": the blank is not a label to extend by");
+    if (s->len[(size_t)p] + 1 > ALIGN_MAX_LABELS)
+      return fail(CTCDEC_ERR_LIMIT, who + ": " + std::to_string(s->len[(size_t)p] + 1) + " labels, above the limit of " + std::to_string(ALIGN_MAX_LABELS));
+    pslot[(size_t)i] = p;
+  }
+  if ((int64_t)s->free_slots.size() < n)
+    return fail(CTCDEC_ERR_LIMIT, std::to_string(n) + " children for " + std::to_string(s->free_slots.size()) + " free slots of " +
+                                      std::to_string(s->capacity) + ": release prefixes, or open the session with a larger capacity");
+  if (n == 0) {
+    session_timing(s, t_begin, 0);
+    return CTCDEC_OK;
+  }
+  std::string err;
+  if (be::bind_thread(&err)) return fail(CTCDEC_ERR_DEVICE, err);
+#ifndef CTC_SIM
+  be::align_timing_reset();
+#endif
+  // the children's slots (not handed out before the call has succeeded), and their records: an utterance's next to each other
+  std::vector<int64_t> slots((size_t)n);
+  for (int64_t i = 0; i < n; ++i) slots[(size_t)i] = s->free_slots[s->free_slots.size() - 1 - (size_t)i];
+  std::vector<int32_t> order;
+  for (int64_t i = 0; i < n; ++i) {
+    const int64_t slot = slots[(size_t)i], p = pslot[(size_t)i];
+    s->utt[(size_t)slot] = s->utt[(size_t)p];
+    s->last[(size_t)slot] = labels[i];
+    s->len[(size_t)slot] = s->len[(size_t)p] + 1;
+    if (s->frames[(size_t)s->utt[(size_t)p]] > 0) order.push_back((int32_t)i);
+  }
+  std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return s->utt[(size_t)slots[(size_t)a]] < s->utt[(size_t)slots[(size_t)b]]; });
+  std::vector<PrefixChild> kids;
+  kids.reserve(order.size());
+  if (dec->w_ascore.ensure((size_t)n * 8, &err) || be::zero(dec->w_ascore.p, (size_t)n * 8, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+  for (int32_t i : order) {
+    const int64_t slot = slots[(size_t)i], p = pslot[(size_t)i];
+    const int32_t u = s->utt[(size_t)slot];
+    PrefixChild k;
+    k.x = s->ptrs[(size_t)u];
+    k.lse = s->lse_of(u);
+    k.parent = s->bc(p);
+    k.bc = s->bc(slot);
+    k.scale = s->scale(slot);
+    k.end = (double*)dec->w_ascore.p + i;
+    k.T = s->frames[(size_t)u];
+    k.c = labels[i];
+    k.parent_last = s->last[(size_t)p];
+    k.is_prob = s->is_prob[(size_t)u] ? 1 : 0;
+    kids.push_back(k);
+  }
+#ifdef CTC_SIM
+  for_dtype(s->dtype, [&](auto dt) {
+    for (const PrefixChild& k : kids) ctc_prefix_advance_child<decltype(dt)::value>(k, V, s->tc.blank, s->tc.clip_lo);
+  });
+#else
+  if (!kids.empty()) {
+    if (upload(dec->w_fhyps, kids, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+    PrefixAdvanceArgs aa;
+    aa.kids = (const PrefixChild*)dec->w_fhyps.p;
+    aa.n_kids = (int32_t)kids.size();
+    aa.n_labels = V;
+    aa.dtype = s->dtype;
+    aa.blank = s->tc.blank;
+    aa.clip_lo = s->tc.clip_lo;
+    if (be::launch_ctc_prefix_advance(aa, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+  }
+#endif
+  if (int rc = session_deliver(s, slots, next_out, end_out, next_host)) return rc;
+  for (int64_t i = 0; i < n; ++i) {
+    s->tag[(size_t)slots[(size_t)i]] = session_next_tag();
+    ids_out[i] = session_id(s->tag[(size_t)slots[(size_t)i]], slots[(size_t)i]);
+  }
+  s->free_slots.resize(s->free_slots.size() - (size_t)n);
+  session_timing(s, t_begin, kids.empty() ? 0 : 1);
+  return CTCDEC_OK;
+}
+
+int ctcdec_prefix_session_release(ctcdec_prefix_session* s, const int64_t* ids, int64_t n) {
+  if (!s || n < 0 || (n > 0 && !ids)) return fail(CTCDEC_ERR_ARG, "bad arguments");
+  std::lock_guard<std::mutex> device_lock(g_device_mu);
+  std::vector<int64_t> slots((size_t)n);
+  for (int64_t i = 0; i < n; ++i) {
+    const int64_t slot = session_slot(s, ids[i]);
+    if (slot < 0) return fail(CTCDEC_ERR_ARG, "release: " + std::to_string(ids[i]) + " is not a live prefix of this session");
+    if (slot < s->n_utts)
+      return fail(CTCDEC_ERR_ARG, "release: " + std::to_string(ids[i]) + " is the empty prefix of utterance " + std::to_string(slot) +
+                                      ", which lives as long as the session");
+    slots[(size_t)i] = slot;
+  }
+  std::vector<int64_t> sorted = slots;
+  std::sort(sorted.begin(), sorted.end());
+  if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return fail(CTCDEC_ERR_ARG, "release: an id is given twice");
+  for (int64_t slot : slots) {
+    s->tag[(size_t)slot] = 0;
+    s->free_slots.push_back(slot);
+  }
+  return CTCDEC_OK;
+}
+
+int ctcdec_prefix_session_timing(const ctcdec_prefix_session* s, double* ms3, int32_t* launches4) {
+  if (!s || !ms3) return fail(CTCDEC_ERR_ARG, "no prefix session");
+  std::lock_guard<std::mutex> device_lock(g_device_mu);
+  for (int k = 0; k < 3; ++k) ms3[k] = s->ms[k];
+  if (launches4)
+    for (int k = 0; k < 4; ++k) launches4[k] = s->launches[k];
+  return CTCDEC_OK;
+}
+
+void ctcdec_prefix_session_close(ctcdec_prefix_session* s) {
+  if (!s) return;
+  std::lock_guard<std::mutex> device_lock(g_device_mu);
+  delete s;
+}
 
 // ---- frame posteriors ("Frame posteriors") --------------------------------------------------------------------
 }  // extern "C"

@@ -327,12 +327,15 @@ int launch_greedy_collapse(const GreedyArgs& a, std::string* err);
 int launch_ctc_forward_ends(const ForwardArgs& a, const PrefixEnds* ends, int wave, std::string* err);
 int launch_ctc_prefix_extend(const PrefixExtendArgs& a, std::string* err);
 int launch_ctc_prefix_fill(double* next, const int32_t* rows, int32_t n_rows, int32_t V, std::string* err);
+// Prefix sessions (ctc_align.h, "ctc_prefix_advance"): the end states, scale and end of every child of `kids`, each from its
+// parent's end states; all entries validated by the host (PrefixChild), no child's output another's input
+int launch_ctc_prefix_advance(const PrefixAdvanceArgs& a, std::string* err);
 // kernel times (HIP events) of the launches of one of these kernels since the last reset; waits for the kernels.
 // ctc_forward and ctc_forward_wave share a log (with their _ends forms), as do ctc_find and ctc_find_wave, greedy_collapse's
-// two passes, and ctc_prefix_extend, ctc_prefix_finish and ctc_prefix_fill.
+// two passes, and ctc_prefix_extend, ctc_prefix_finish and ctc_prefix_fill; ctc_prefix_advance has its own.
 enum AlignKernel {
   K_ROW_LSE, K_VITERBI, K_FORWARD, K_POSTERIORS, K_GRAD_ROWS, K_FIND, K_ROW_LSE_MAX, K_VITERBI_GAPS, K_ROW_ARGMAX, K_ROW_LSE_ARGMAX,
-  K_GREEDY_COLLAPSE, K_PREFIX_EXTEND, ALIGN_KERNELS
+  K_GREEDY_COLLAPSE, K_PREFIX_EXTEND, K_PREFIX_ADVANCE, ALIGN_KERNELS
 };
 void align_timing_reset();
 double align_kernel_ms(AlignKernel kind);

@@ -589,6 +589,8 @@ int launch_ctc_prefix_fill_on(double* next, const int32_t* rows, int32_t n_rows,
 int launch_ctc_prefix_fill(double* next, const int32_t* rows, int32_t n_rows, int32_t V, std::string* err) {
   return launch_ctc_prefix_fill_on(next, rows, n_rows, V, g_stream, err);
 }
+int launch_ctc_prefix_advance_on(const PrefixAdvanceArgs& a, hipStream_t stream, std::string* err);
+int launch_ctc_prefix_advance(const PrefixAdvanceArgs& a, std::string* err) { return launch_ctc_prefix_advance_on(a, g_stream, err); }
 int launch_greedy_collapse_on(const GreedyArgs& a, hipStream_t stream, std::string* err);
 int launch_greedy_collapse(const GreedyArgs& a, std::string* err) { return launch_greedy_collapse_on(a, g_stream, err); }
 

@@ -13,6 +13,7 @@
 //   greedy_collapse_utt            runs of frame labels to tokens               (greedy_collapse)
 //   ctc_forward_hyp / _wave_hyp <ENDS>  the forward pass that also stores a prefix' end states  (ctc_forward_ends / ctc_forward_wave_ends)
 //   ctc_prefix_extend_tile, ctc_prefix_finish_col   every label's prefix score from them  (ctc_prefix_extend, ctc_prefix_finish)
+//   ctc_prefix_advance_child       a child prefix' end states from its parent's  (ctc_prefix_advance)
 // The shared pieces, and who uses them:
 //   viterbi_backtrace, fold_token_logp                   ctc_viterbi, ctc_viterbi_gaps
 //   group_setup, EntrySource, FrameEntries               ctc_find, ctc_find_wave, ctc_viterbi_gaps
@@ -1620,6 +1621,90 @@ CTC_HD void ctc_prefix_finish_col(const PrefixExtendArgs& a, int chunk, int c) {
     for (int seg = 0; seg < nseg; ++seg) total += a.partial[prefix_partial_at(a, chunk, seg, k, c)];
     prefix_store(a, ch.h[k], c, total);
   }
+}
+
+// ---- ctc_prefix_advance ------------------------------------------------------------------------------------------------------
+// A prefix session ("Prefix sessions"): the PrefixEnds of the child g + [c] from the PrefixEnds of its parent g,
+// without g's other states. Of the child's S = 2 (L + 1) + 1 states only the last label, y = a[S-2], and the final blank,
+// z = a[S-1], are new; what feeds them from below is g's final blank and g's last label, which g's bc holds frame by frame:
+//   y_0 = e(0, c) for the empty g, else -inf;  z_0 = -inf;
+//   y_t = lse3(y_{t-1}, bc_g[t], c != last(g) ? bc_g[T + t] : -inf) + e(t, c),   z_t = lse2(z_{t-1}, y_{t-1}) + e(t, blank),
+//   bc[t] = z_{t-1},  bc[T + t] = y_{t-1},  scale = their running maximum,  end = lse2(z_{T-1}, y_{T-1}).
+// These are forward_step's calls for the child's last group -- the same functions on the same operands in the same order --
+// and forward_window never withholds an operand: its lower edge stays below S - 4 until the last frame, and a state above
+// its upper edge is -inf under the recursion as well. So the child's bc, scale and end are, bit for bit, what the forward
+// bodies with ENDS store for g + [c]. One child of a launch; the host validates every field before it.
+struct PrefixChild {
+  const void* x;         // [T, V] the utterance's matrix, of the launch's dtype
+  const double* lse;     // [T] log-sum-exp of each row (read, not used, when is_prob)
+  const double* parent;  // [2 T] the parent's bc
+  double* bc;            // [2 T] out
+  double* scale;         // [1] out
+  double* end;           // [1] out
+  int32_t T, c, parent_last, is_prob;  // parent_last: -1 for the empty prefix
+};
+struct PrefixAdvanceArgs {
+  const PrefixChild* kids;  // [n_kids] (device), the children of one utterance next to each other
+  int32_t n_kids, n_labels, dtype, blank;
+  double clip_lo;           // ln(MIN_TOKEN_CLIP_P)
+};
+constexpr int32_t PREFIX_ADVANCE_THREADS = 64;  // children of a workgroup: one wavefront
+constexpr int32_t PREFIX_ADVANCE_AHEAD = 4;     // frames whose operands are asked for ahead of their use
+
+// The operands of PREFIX_ADVANCE_AHEAD consecutive frames, kept as loaded. None of their addresses depends on the recursion.
+template <int DT>
+struct AdvanceFrames {
+  typedef typename AlignRaw<DT>::type Raw;
+  Raw vc[PREFIX_ADVANCE_AHEAD], vb[PREFIX_ADVANCE_AHEAD];
+  double lse_t[PREFIX_ADVANCE_AHEAD], pb[PREFIX_ADVANCE_AHEAD], pl[PREFIX_ADVANCE_AHEAD];
+  // frames t0 .. t0 + AHEAD - 1, those past the last frame the last frame again: loads alone, at indices that are always valid
+  CTC_HD void request(const PrefixChild& k, int V, int blank, int t0) {
+    CTC_UNROLL
+    for (int i = 0; i < PREFIX_ADVANCE_AHEAD; ++i) {
+      const int t = t0 + i < k.T ? t0 + i : k.T - 1;
+      const size_t row = (size_t)t * (size_t)V;
+      vc[i] = align_load_raw<DT>(k.x, row + (size_t)k.c);
+      vb[i] = align_load_raw<DT>(k.x, row + (size_t)blank);
+      lse_t[i] = k.lse[t];
+      pb[i] = k.parent[t];
+      pl[i] = k.parent[(size_t)k.T + (size_t)t];
+    }
+  }
+};
+
+template <int DT>
+CTC_HD void ctc_prefix_advance_child(const PrefixChild& k, int V, int blank, double clip_lo) {
+  const int T = k.T;
+  if (T <= 0) return;
+  const double NEG = align_neg_inf();
+  const bool is_prob = k.is_prob != 0, skip = k.parent_last >= 0 && k.parent_last != k.c;
+  double* const bc = k.bc;
+  double y = k.parent_last < 0 ? align_emit(k.x, DT, (size_t)k.c, is_prob ? 0.0 : k.lse[0], is_prob, clip_lo) : NEG;
+  double z = NEG, ends_m = NEG;
+  bc[0] = NEG, bc[T] = NEG;
+  AdvanceFrames<DT> cur, nxt;
+  nxt.request(k, V, blank, 1);
+  for (int t0 = 1; t0 < T; t0 += PREFIX_ADVANCE_AHEAD) {
+    cur = nxt;
+    nxt.request(k, V, blank, t0 + PREFIX_ADVANCE_AHEAD);
+    CTC_UNROLL
+    for (int i = 0; i < PREFIX_ADVANCE_AHEAD; ++i) {
+      const int t = t0 + i;
+      if (t >= T) break;
+      bc[t] = z;
+      bc[(size_t)T + (size_t)t] = y;
+      ends_m = z > ends_m ? z : ends_m;
+      ends_m = y > ends_m ? y : ends_m;
+      const double lse_use = is_prob ? 0.0 : cur.lse_t[i];
+      const double e_blank = align_emit_of_value(align_widen<DT>(cur.vb[i]), lse_use, is_prob, clip_lo);
+      const double e_c = align_emit_of_value(align_widen<DT>(cur.vc[i]), lse_use, is_prob, clip_lo);
+      const double y1 = align_lse3(y, cur.pb[i], skip ? cur.pl[i] : NEG) + e_c;
+      z = align_lse2(z, y) + e_blank;
+      y = y1;
+    }
+  }
+  *k.end = align_lse2(z, y);
+  *k.scale = ends_m;
 }
 
 }  // namespace ctc

@@ -10,6 +10,7 @@
 //   ctc_forward_ends, _wave_ends    ctc_forward / ctc_forward_wave that also store a prefix' end states per frame
 //   ctc_prefix_extend, _finish      a workgroup per (chunk of prefixes, tile of 256 columns[, segment of frames]), a column per thread
 //   ctc_prefix_fill                 -inf into the rows of the prefixes nothing was launched for
+//   ctc_prefix_advance              (prefix sessions) a lane per child: its end states from its parent's
 // The launchers share timed_launch (the event pair of the kernel's log and the launch's error), for_dtype and for_threads.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -597,6 +598,15 @@ __global__ __launch_bounds__(PREFIX_COLS) void ctc_prefix_fill(double* next, con
   if (c < V) next[(size_t)rows[blockIdx.y] * (size_t)V + (size_t)c] = align_neg_inf();
 }
 
+// ctc_prefix_advance (prefix sessions): a lane per child -- the recursion is two states wide --, a wavefront per workgroup so
+// that a launch of a few hundred waves spreads over the compute units; the host orders the children by utterance. Vector
+// loads and stores only, no LDS, no atomics (ctc_align.h).
+template <int DT>
+__global__ __launch_bounds__(PREFIX_ADVANCE_THREADS) void ctc_prefix_advance(PrefixAdvanceArgs a) {
+  const int i = (int)blockIdx.x * PREFIX_ADVANCE_THREADS + (int)threadIdx.x;
+  if (i < a.n_kids) ctc_prefix_advance_child<DT>(a.kids[i], a.n_labels, a.blank, a.clip_lo);
+}
+
 // ---------------------------------------------------------------------------------------------
 // launches. Every launcher validates its arguments, then makes one timed_launch: the kernel's instantiation is picked by
 // for_dtype (ctc_align.h) and, where the kernel has two sizes, for_threads; the row kernels' lanes per row by for_row_lanes.
@@ -821,6 +831,18 @@ int launch_ctc_prefix_fill_on(double* next, const int32_t* rows, int32_t n_rows,
   if (!next || !rows || V < 1 || n_rows > 65535) return bad_launch(err, "ctc_prefix_fill: bad arguments");
   return timed_launch(K_PREFIX_EXTEND, stream, err, [&] {
     hipLaunchKernelGGL(ctc_prefix_fill, dim3((unsigned)prefix_tiles(V), (unsigned)n_rows), dim3(PREFIX_COLS), 0, stream, next, rows, V);
+  });
+}
+
+int launch_ctc_prefix_advance_on(const PrefixAdvanceArgs& a, hipStream_t stream, std::string* err) {
+  if (a.n_kids <= 0) return 0;
+  if (a.dtype < 0 || a.dtype > 3 || a.n_labels < 1 || a.blank < 0 || a.blank >= a.n_labels || !a.kids)
+    return bad_launch(err, "ctc_prefix_advance: bad arguments");
+  const unsigned blocks = (unsigned)((a.n_kids + PREFIX_ADVANCE_THREADS - 1) / PREFIX_ADVANCE_THREADS);
+  return timed_launch(K_PREFIX_ADVANCE, stream, err, [&] {
+    for_dtype(a.dtype, [&](auto dt) {
+      hipLaunchKernelGGL(ctc_prefix_advance<decltype(dt)::value>, dim3(blocks), dim3(PREFIX_ADVANCE_THREADS), 0, stream, a);
+    });
   });
 }
 

@@ -206,6 +206,196 @@ class PrefixScores:
     next_logp: Any
 
 
+@dataclasses.dataclass(frozen=True, eq=False)
+class SessionPrefix:
+    """A live prefix of a PrefixSession: ``id`` is what extend and release take, ``utt`` the utterance it belongs to, and
+    ``text``, ``tokens``, ``logp_end`` and ``next_logp`` are PrefixScores' -- the same bits prefix_scores_batch gives for
+    ``tokens`` on the session's input. For device input ``next_logp`` is a view of the step's ``[n, V]`` tensor."""
+
+    id: int
+    utt: int
+    text: str
+    tokens: List[int]
+    logp_end: float
+    next_logp: Any
+
+
+class PrefixSession:
+    """Prefix scores for a decoding loop (BeamSearchDecoderCTC.prefix_session; DESIGN.md, "Prefix sessions"): the session
+    keeps every live prefix' end states on the device, so that ``extend`` forms a child -- a live prefix followed by one
+    label -- in O(T) (kernel ctc_prefix_advance) instead of a forward pass from label 0, and row_lse and the classification
+    run once, when the session opens. ``roots[u]`` is the empty prefix of utterance u. A context manager; ``close()`` frees
+    the device memory."""
+
+    def __init__(self, decoder: "BeamSearchDecoderCTC", logits_list: Any, capacity: Optional[int] = None):
+        if isinstance(logits_list, (_ResidentBeams, _DeviceStreams)) or (
+                isinstance(logits_list, (list, tuple)) and any(isinstance(x, (_ResidentBeams, _DeviceStreams)) for x in logits_list)):
+            raise NotImplementedError("a prefix session reads an utterance's matrix at every step; the frames a stream has consumed are not kept")
+        if getattr(logits_list, "ndim", 0) != 3:
+            logits_list = list(logits_list)
+        self._decoder, self._lib = decoder, decoder._lib
+        self._handle = None
+        n = len(logits_list)
+        self._n_labels = len(decoder._labels_list)
+        if capacity is None:
+            capacity = 64 * n
+        if isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or capacity < n:
+            raise ValueError("prefix_session: capacity must be an int of at least one slot per utterance (%d), not %r" % (n, capacity))
+        self.capacity = int(capacity)
+        self.last_next = None
+        self.last_timing_ms, self.last_launches = (0.0, 0.0, 0.0), (0, 0, 0, 0)
+        self._nodes: Dict[int, SessionPrefix] = {}
+        self._space = None if decoder._is_bpe else decoder._vocab2idx.get(" ")
+        with decoder._call_lock:
+            batch, frames, ptrs = decoder._stage_transcript_call(logits_list)
+            self._batch = batch  # (device tensors are read in place by every extend: they live as long as the session)
+            self._is_device = bool(batch.is_device)
+            buf, next_dev, next_host = self._room(n)
+            ids, end = np.zeros(max(n, 1), dtype=np.int64), np.zeros(max(n, 1), dtype=np.float64)
+            handle = C.c_void_p()
+            lib = self._lib
+            lib.check(lib.dll.ctcdec_prefix_session_open(
+                decoder._handle, ptrs.ctypes.data_as(C.POINTER(C.c_void_p)), frames.ctypes.data_as(C.POINTER(C.c_int32)), n,
+                batch.dtype, int(batch.is_device), self.capacity, next_dev, B.off_ptr(ids), end.ctypes.data_as(C.POINTER(C.c_double)),
+                next_host, C.byref(handle)))
+            self._handle = handle
+            self._take_timing()
+        if not self._is_device:
+            self._batch = None  # (host matrices were staged into the session's own memory)
+        self.roots: List[SessionPrefix] = self._nodes_of(ids[:n], list(range(n)), [[] for _ in range(n)], end[:n], buf)
+
+    def _room(self, n: int):
+        """-> (block, device pointer or None, host pointer or None): the step's [n, V] float64 block, which the kernels fill in
+        place for device input."""
+        if self._is_device:
+            import torch
+
+            buf = torch.empty((n, self._n_labels), dtype=torch.float64, device=self._batch.keep[0].device if self._batch.keep else "cuda")
+            return buf, (C.c_void_p(buf.data_ptr()) if n else None), None
+        buf = np.empty((n, self._n_labels), dtype=np.float64)
+        return buf, None, C.c_void_p(buf.ctypes.data)
+
+    def _take_timing(self) -> None:
+        ms, launches = (C.c_double * 3)(), (C.c_int32 * 4)()
+        self._lib.dll.ctcdec_prefix_session_timing(self._handle, ms, launches)
+        # [ctc_prefix_advance, ctc_prefix_extend with its finish and fill (HIP events), whole native call]; launches of
+        # (ctc_prefix_advance, ctc_prefix_extend / finish / fill, row_lse, the forward kernels)
+        self.last_timing_ms = tuple(float(v) for v in ms)
+        self.last_launches = tuple(int(v) for v in launches)
+
+    def _nodes_of(self, ids, utts, tokens, end, buf) -> List[SessionPrefix]:
+        if self._is_device:
+            self.last_next = buf
+        rows = buf.unbind(0) if self._is_device else list(buf)
+        out = []
+        for k, (i, u, toks) in enumerate(zip(ids.tolist(), utts, tokens)):
+            text = self._decoder._words_of_target(toks)[0] + (" " if toks and toks[-1] == self._space else "")
+            node = SessionPrefix(i, u, text, toks, float(end[k]), rows[k])
+            self._nodes[i] = node
+            out.append(node)
+        return out
+
+    def _open_handle(self):
+        if self._handle is None:
+            raise ValueError("the prefix session is closed")
+        return self._handle
+
+    def _live(self, what: str, i: Any) -> SessionPrefix:
+        node = self._nodes.get(i) if isinstance(i, (int, np.integer)) and not isinstance(i, bool) else None
+        if node is None:
+            raise ValueError("%s: %r is not the id of a live prefix of this session" % (what, i))
+        return node
+
+    def __len__(self) -> int:
+        return len(self._nodes)
+
+    def extend(self, parents: Sequence[int], labels: Optional[Sequence[int]] = None,
+               texts: Optional[Sequence[str]] = None) -> List[SessionPrefix]:
+        """Child k is the live prefix ``parents[k]`` followed by ``labels[k]`` (or, character alphabets, by the single
+        character ``texts[k]``): one ctc_prefix_advance launch for all of them, then ctc_prefix_extend as in
+        prefix_scores_batch. A parent may be given any number of times. A ValueError -- a dead or foreign id, the blank, a
+        label outside the alphabet, more children than free slots, a child of more than 2047 labels -- leaves the session
+        as it was."""
+        handle = self._open_handle()
+        dec = self._decoder
+        if (labels is None) == (texts is None):
+            raise ValueError("extend: give exactly one of labels and texts")
+        parents = list(parents)
+        if texts is not None:
+            if dec._is_bpe:
+                raise ValueError("a text has many segmentations under a BPE alphabet: give the labels")
+            labels = []
+            for k, t in enumerate(texts):
+                if not isinstance(t, str) or len(t) != 1 or t not in dec._vocab2idx:
+                    raise ValueError("extend: texts[%d] is %r: not a single character of the alphabet" % (k, t))
+                labels.append(dec._vocab2idx[t])
+        labels = list(labels)
+        if len(labels) != len(parents):
+            raise ValueError("extend: %d labels for %d parents" % (len(labels), len(parents)))
+        blank = dec._vocab2idx[""]
+        nodes = [self._live("extend", p) for p in parents]
+        for k, c in enumerate(labels):
+            if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 0 <= int(c) < self._n_labels or int(c) == blank:
+                raise ValueError("extend: labels[%d] is %r: not a label id in [0, %d) other than the blank (%d)" % (k, c, self._n_labels, blank))
+            if len(nodes[k].tokens) + 1 > ALIGN_MAX_LABELS:
+                raise ValueError("extend: child %d has %d labels, above the limit of %d labels per prefix" % (k, len(nodes[k].tokens) + 1, ALIGN_MAX_LABELS))
+        n = len(parents)
+        if len(self._nodes) + n > self.capacity:
+            raise ValueError("extend: %d children, but %d of the session's %d slots are free: release prefixes, or open the session "
+                             "with a larger capacity" % (n, self.capacity - len(self._nodes), self.capacity))
+        if n == 0:
+            return []
+        with dec._call_lock:
+            buf, next_dev, next_host = self._room(n)
+            par = np.ascontiguousarray(parents, dtype=np.int64)
+            lab = np.ascontiguousarray([int(c) for c in labels], dtype=np.int32)
+            ids, end = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.float64)
+            self._lib.check(self._lib.dll.ctcdec_prefix_session_extend(
+                handle, B.off_ptr(par), lab.ctypes.data_as(C.POINTER(C.c_int32)), n, next_dev, B.off_ptr(ids),
+                end.ctypes.data_as(C.POINTER(C.c_double)), next_host))
+            self._take_timing()
+        return self._nodes_of(ids, [p.utt for p in nodes], [p.tokens + [int(c)] for p, c in zip(nodes, labels)], end, buf)
+
+    def release(self, ids: Sequence[int]) -> None:
+        """The prefixes' slots become free for later children; their ids are dead from here on. The empty prefixes stay."""
+        handle = self._open_handle()
+        ids = list(ids)
+        nodes = [self._live("release", i) for i in ids]
+        for node in nodes:
+            if not node.tokens:
+                raise ValueError("release: %d is the empty prefix of utterance %d, which lives as long as the session" % (node.id, node.utt))
+        if len(set(ids)) != len(ids):
+            raise ValueError("release: an id is given twice")
+        if not ids:
+            return
+        arr = np.ascontiguousarray(ids, dtype=np.int64)
+        with self._decoder._call_lock:
+            self._lib.check(self._lib.dll.ctcdec_prefix_session_release(handle, B.off_ptr(arr), len(ids)))
+        for i in ids:
+            del self._nodes[i]
+
+    def close(self) -> None:
+        if self._handle is not None:
+            with self._decoder._call_lock:
+                self._lib.dll.ctcdec_prefix_session_close(self._handle)
+            self._handle = None
+            self._nodes.clear()
+            self._batch = None
+
+    def __enter__(self) -> "PrefixSession":
+        self._open_handle()
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 (interpreter shutdown)
+            pass
+
+
 @dataclasses.dataclass(frozen=True)
 class ScoredText:
     """How probable a transcript is, given the audio (BeamSearchDecoderCTC.score / score_batch): ``logp`` is the CTC forward
@@ -2315,7 +2505,8 @@ class BeamSearchDecoderCTC:
         csrc/ctc_align_hip.hip). ``logits_list`` is what align_batch takes; ``texts[u]`` (character alphabets) is a list of
         str -- whitespace runs collapse and leading whitespace is dropped as everywhere, but trailing whitespace is kept as
         one space label --, ``tokens[u]`` a list of lists of label ids, the only form for BPE alphabets; ``[]`` or ``""`` is
-        the empty prefix. The call is stateless: nothing is carried from one step's prefixes to the next's. Host arrays give
+        the empty prefix. The call is stateless: nothing is carried from one step's prefixes to the next's (a decoding loop,
+        whose prefixes are each a parent plus one label, wants prefix_session: the same bits, O(T) per child). Host arrays give
         numpy arrays; device tensors give torch tensors on the same device, views of ``last_prefix_next``, which the
         kernels write in place."""
         logits_list, prefixes = self._many_targets_each("prefix_scores", "prefix", "prefixes", logits_list, texts, tokens,
@@ -2381,6 +2572,13 @@ class BeamSearchDecoderCTC:
                 h += 1
             out.append(got)
         return out
+
+    def prefix_session(self, logits_list: Any, capacity: Optional[int] = None) -> "PrefixSession":
+        """prefix_scores_batch for a decoding loop: a PrefixSession over the batch, in which a live prefix is extended by one
+        label in O(T) and row_lse runs once. ``logits_list`` is what prefix_scores_batch takes; ``capacity`` is the number
+        of prefixes that can be live at once, the utterances' empty prefixes among them (default: 64 per utterance). Every
+        prefix of the session has the bits prefix_scores_batch gives for its labels ("Prefix sessions")."""
+        return PrefixSession(self, logits_list, capacity)
 
     # -- phrase search (no reference analogue; DESIGN.md, "Phrase search") ----------------------------------
     def find(self, logits: Any, texts: Optional[Sequence[str]] = None, tokens: Optional[Sequence[Sequence[int]]] = None,

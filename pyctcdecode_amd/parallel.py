@@ -231,6 +231,11 @@ def prefix_scores_batch_sharded(decoder, logits_list, texts=None, group=None, **
     raise NotImplementedError("prefix_scores_batch is not gathered over ranks: call decoder.prefix_scores_batch on each rank's slice itself")
 
 
+def prefix_session_sharded(decoder, logits_list, capacity=None, group=None, **kwargs):
+    """Prefix sessions are not sharded over ranks: each rank opens decoder.prefix_session on its own slice."""
+    raise NotImplementedError("a prefix session is not shared between ranks: open decoder.prefix_session on each rank's slice itself")
+
+
 def _device_worker(conn, device: int, decoder_dir: str, library: Optional[str]) -> None:
     """One worker process = one GPU (the native library binds one device per process): loads the saved decoder on its device and
     serves (method, logits, kwargs) requests until it is told to stop."""
@@ -395,6 +400,10 @@ class DevicePool:
         raise NotImplementedError("DevicePool does not shard prefix_scores_batch: call decoder.prefix_scores_batch on the process's own device")
 
     prefix_scores = prefix_scores_batch
+
+    def prefix_session(self, logits_list, capacity=None, **kwargs):
+        """A prefix session lives on the calling process's own device: a pool does not hold one."""
+        raise NotImplementedError("DevicePool does not hold prefix sessions: open decoder.prefix_session on the process's own device")
 
     def decode_batch(self, logits_list, **kwargs) -> List[str]:
         if kwargs.get("token_frames") or kwargs.get("confidence") is not None:  # (texts, TokenFrames) per slice -> one of each, offsets rebased

@@ -6,7 +6,7 @@ substituted), each forward kernel forced in turn -- and at 64 utterances, with t
 for scale; then a sweep of target lengths on 256 utterances of random logits, which is what the wave / group threshold of
 ctcdec_score_batch rests on. Kernel times are HIP events on the decode stream (ctcdec_alignment_timing, ctcdec_score_batch,
 ctcdec_posteriors_timing).
-  python tools/align_bench.py [--out profiles/align_bench.txt] [--steps 3] [--legs align,score,posteriors,sweep,gradient,find,gaps,greedy,prefix]
+  python tools/align_bench.py [--out profiles/align_bench.txt] [--steps 3] [--legs align,score,posteriors,sweep,gradient,find,gaps,greedy,prefix,prefix_session]
 The gradient leg (not in the default set) times gradient_batch -- ctc_grad_rows alone, next to posteriors_batch(dense=False).
 The find leg (not in the default set either) times find_batch -- ctc_find / ctc_find_wave forced in turn, alternating: at the
 bench shape each utterance searched for 1 and for 8 phrases of 8 labels cut from its own decoded tokens, then 256 and 2048
@@ -19,6 +19,9 @@ next to row_lse_max and decode_batch's frame-prune stage on the same batch in th
 The prefix leg (not in the default set either) times prefix_scores_batch with 1, 8 and 16 prefixes of about 20 labels per
 utterance -- the first 20 of its decoded tokens, and copies with one label substituted --: ctc_prefix_extend, the forward
 kernels with end states next to score_batch's plain ones on the same prefixes in the same rounds, alternating, and row_lse.
+The prefix_session leg (not in the default set either) grows a beam of 8 prefixes per utterance to 20 labels in a prefix
+session and times steps 1, 10 and 20 -- ctc_prefix_advance, ctc_prefix_extend, the native call -- next to the stateless
+prefix_scores_batch on the same prefixes in the same rounds.
 The 4096 utterances are 256 distinct ones repeated: no kernel's time depends on the rows being distinct."""
 import argparse
 import os
@@ -371,6 +374,69 @@ def prefix_lines(dec, dev, targets, n, steps):
     return lines
 
 
+def prefix_session_lines(dec, dev, targets, n, steps, beam=8, depth=20, at=(1, 10, 20)):
+    """A beam of `beam` prefixes per utterance grown from the roots to `depth` labels in a prefix session -- beam 0 along the
+    utterance's own decoded tokens, the others along random labels; every prefix one label longer per step, the parents
+    released --, one warm-up round and then `steps` rounds. At the steps `at`: ctc_prefix_advance, ctc_prefix_extend and the
+    native call of the session's extend, and in the same round the stateless prefix_scores_batch on the same prefixes: its
+    forward kernels, row_lse, ctc_prefix_extend and native call. The stateless call is the baseline."""
+    rng = np.random.default_rng(13)
+    blank = dec._alphabet.labels.index("")
+    pool = [c for c in range(V) if c != blank]
+    paths = [[[int(t[k]) if j == 0 and k < len(t) else pool[int(rng.integers(0, len(pool)))] for k in range(depth)]
+              for j in range(beam)] for t in targets]
+    keys = ("advance", "s_extend", "s_native", "s_wall", "forward", "lse", "extend", "native", "wall", "open")
+    got = {step: {k: [] for k in keys} for step in at}
+    launches = {}
+    for rnd in range(steps + 1):
+        t0 = time.perf_counter()
+        s = dec.prefix_session(dev, capacity=n * (1 + 2 * beam))
+        opened = (time.perf_counter() - t0) * 1e3
+        with s:
+            live = [r for r in s.roots for _j in range(beam)]
+            for step in range(1, depth + 1):
+                t0 = time.perf_counter()
+                kids = s.extend([p.id for p in live], [paths[u][j][step - 1] for u in range(n) for j in range(beam)])
+                wall = (time.perf_counter() - t0) * 1e3
+                ms, launches[step] = s.last_timing_ms, s.last_launches
+                if step > 1:
+                    s.release([p.id for p in live])
+                live = kids
+                if step not in at:
+                    continue
+                row = [("advance", ms[0]), ("s_extend", ms[1]), ("s_native", ms[2]), ("s_wall", wall), ("open", opened)]
+                prefixes = [[paths[u][j][:step] for j in range(beam)] for u in range(n)]
+                t0 = time.perf_counter()
+                out = dec.prefix_scores_batch(dev, tokens=prefixes)
+                wall = (time.perf_counter() - t0) * 1e3
+                ms = dec.last_prefix_timing_ms
+                row += [("forward", ms[2]), ("lse", ms[1]), ("extend", ms[3]), ("native", ms[4]), ("wall", wall)]
+                # (the session's bits are the stateless call's: checked here on the first and the last utterance)
+                for u in (0, n - 1):
+                    for j in range(beam):
+                        a, b = kids[u * beam + j], out[u][j]
+                        assert a.tokens == b.tokens and a.logp_end == b.logp_end and bool((a.next_logp == b.next_logp).all())
+                del out
+                if rnd:
+                    for k, v in row:
+                        got[step][k].append(v)
+            del live, kids
+        print("prefix session, %d utterances: round %d of %d done" % (n, rnd, steps), file=sys.stderr, flush=True)
+    lines = ["  prefix session, a beam of %d prefixes per utterance grown to %d labels; the stateless prefix_scores_batch on the same "
+             "prefixes in the same rounds is the baseline (median, spread of the rounds)" % (beam, depth),
+             "  open (classification, row_lse, the roots' forward pass and extension, arena): Python call %9.3f ms" % float(np.median(got[at[0]]["open"]))]
+    cell = lambda step, k: "%9.3f (%.3f)" % (float(np.median(got[step][k])), max(got[step][k]) - min(got[step][k]))  # noqa: E731
+    for step in at:
+        lines.append("  step %2d  session:   ctc_prefix_advance %s ms  ctc_prefix_extend %s ms  native call %s ms  Python call %s ms  launches %s"
+                     % (step, cell(step, "advance"), cell(step, "s_extend"), cell(step, "s_native"), cell(step, "s_wall"), launches[step]))
+        lines.append("           stateless: forward kernels    %s ms  ctc_prefix_extend %s ms  row_lse %s ms  native call %s ms  Python call %s ms"
+                     % (cell(step, "forward"), cell(step, "extend"), cell(step, "lse"), cell(step, "native"), cell(step, "wall")))
+        lines.append("           native call, stateless / session: %.2f   advance / ctc_prefix_extend: %.2f"
+                     % (float(np.median(got[step]["native"])) / float(np.median(got[step]["s_native"])),
+                        float(np.median(got[step]["advance"])) / float(np.median(got[step]["s_extend"]))))
+    return lines
+
+
 def time_forward(dec, dev, hyps, kernels, steps):
     """The forward kernels' time (HIP events) under each forced kernel: one warm-up call each, then `steps` rounds that
     alternate between them (clocks as they come: neither kernel gets the warmer half of the run). -> {kernel: median ms}"""
@@ -513,6 +579,8 @@ def main():
             lines += greedy_lines(dec, dev, targets, n, args.steps)
         if "prefix" in legs:
             lines += prefix_lines(dec, dev, targets, n, args.steps)
+        if "prefix_session" in legs:
+            lines += prefix_session_lines(dec, dev, targets, n, args.steps)
         del dev
     if "sweep" in legs:
         lines += sweep_lines(dec, max(args.steps, 5))
