@@ -9,7 +9,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libctcdec.so")
-SOURCES = ["api.cpp", "host_tables.cpp", "kenlm_binary.cpp", "backend_hip.hip", "frame_prune_hip.hip", "beam_wave_hip.hip",
+SOURCES = ["api.cpp", "api_transcript.cpp", "host_tables.cpp", "kenlm_binary.cpp", "backend_hip.hip", "frame_prune_hip.hip", "beam_wave_hip.hip",
            "beam_group_hip.hip", "ctc_align_hip.hip"]
 # The wave kernel is one loop over the frames with ~18 000 instructions in its body and a budget of 128 registers. LLVM's
 # machine-level loop-invariant code motion hoists every constant and address computation it finds out of that loop and
@@ -28,7 +28,7 @@ HIP_FLAGS = {"backend_hip.hip": _MAX_ILP,
              # (the workgroup kernel: 238 -> 195 registers, 255 -> 138 scalar registers spilled to vector lanes)
              "beam_group_hip.hip": ["-mllvm", "-disable-machine-licm"]}
 HEADERS = ["common.h", "beam_core.h", "beam_wave.h", "set_order.h", "set_order_small.h", "backend.h", "host_tables.h", "np_sum.h",
-           "np_f32.h", "wave_ops_hip.h", "text_wave.h", "token_logp.h", "surv_ledger.h", "ctc_align.h", "hip_try.h", "prune_route.h"]
+           "np_f32.h", "wave_ops_hip.h", "text_wave.h", "token_logp.h", "surv_ledger.h", "ctc_align.h", "hip_try.h", "prune_route.h", "api_internal.h"]
 
 
 def hipcc() -> str:

@@ -1,4 +1,4 @@
-// backend.h -- the narrow device interface api.cpp is written against.
+// backend.h -- the narrow device interface api.cpp and api_transcript.cpp are written against.
 //   * pyctcdecode_amd/csrc/backend_hip.hip : the product (MI355X / gfx950 HIP kernels)
 //   * tests/sim/backend_sim.cpp            : sequential CPU execution of the same beam_core.h,
 //                                            test infrastructure only (never built into the product)

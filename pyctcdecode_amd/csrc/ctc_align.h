@@ -1,6 +1,6 @@
 // ctc_align.h -- what is computed from an utterance's frames and a known label sequence ("Forced alignment" to
 // "Alignment with gaps"), over the states blank / label / blank / ... One body each for the HIP kernels (ctc_align_hip.hip)
-// and for the CPU simulator build, whose "device" memory is host memory (api.cpp under CTC_SIM runs them with a one-thread
+// and for the CPU simulator build, whose "device" memory is host memory (api_transcript.cpp under CTC_SIM runs them with a one-thread
 // context). The bodies:
 //   row_lse_seq, row_lse_max_seq   a row's fp64 log-sum-exp (and maximum): the simulator's; the kernels fold by lanes
 //   ctc_viterbi_utt                the best path, its columns in LDS            (kernel ctc_viterbi)

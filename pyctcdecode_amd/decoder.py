@@ -247,7 +247,7 @@ class PrefixSession:
         self._nodes: Dict[int, SessionPrefix] = {}
         self._space = None if decoder._is_bpe else decoder._vocab2idx.get(" ")
         with decoder._call_lock:
-            batch, frames, ptrs = decoder._stage_transcript_call(logits_list)
+            batch, frames, ptrs, c_utts = decoder._stage_transcript_call(logits_list)
             self._batch = batch  # (device tensors are read in place by every extend: they live as long as the session)
             self._is_device = bool(batch.is_device)
             buf, next_dev, next_host = self._room(n)
@@ -255,7 +255,7 @@ class PrefixSession:
             handle = C.c_void_p()
             lib = self._lib
             lib.check(lib.dll.ctcdec_prefix_session_open(
-                decoder._handle, ptrs.ctypes.data_as(C.POINTER(C.c_void_p)), frames.ctypes.data_as(C.POINTER(C.c_int32)), n,
+                decoder._handle, *c_utts, n,
                 batch.dtype, int(batch.is_device), self.capacity, next_dev, B.off_ptr(ids), end.ctypes.data_as(C.POINTER(C.c_double)),
                 next_host, C.byref(handle)))
             self._handle = handle
@@ -496,6 +496,14 @@ FORWARD_KERNELS = {"wave": 1, "group": 2}  # ctcdec_score_batch's `kernel` from 
 FIND_KERNELS = {"wave": 1, "group": 2}  # ctcdec_find_batch's `kernel` from CTCDEC_FIND_KERNEL (unset: the library chooses)
 FIND_MAX_HITS = 64  # FIND_MAX_HITS of csrc/ctc_align.h: a wavefront keeps the windows taken so far one to a lane
 CONFIDENCE_FOLDS = {"mean": 2, "min": 3, "max": 4}  # ctcdec_params.token_frames: CTCDEC_TOKEN_LOGP_MEAN / _MIN / _MAX
+
+
+def _forced_kernel(env_name: str, kernels: Dict[str, int]) -> int:
+    """A native call's `kernel` argument from the environment variable that forces one (unset: 0, the library chooses)"""
+    name = os.environ.get(env_name, "")
+    if name and name not in kernels:
+        raise ValueError("%s must be wave or group, not %r" % (env_name, name))
+    return kernels.get(name, 0)
 
 
 def _confidence_fold(confidence: Optional[str]) -> int:
@@ -1988,13 +1996,20 @@ class BeamSearchDecoderCTC:
         return logits_list, targets
 
     def _stage_transcript_call(self, logits_list: Any):
-        """-> (batch, frames, ptrs): what every transcript call stages, under the call lock -- the utterances as a _Batch,
-        on this decoder's device if on one, and their frame counts and matrix pointers as arrays for the native call."""
+        """-> (batch, frames, ptrs, c_utts): what every transcript call stages, under the call lock -- the utterances as a _Batch,
+        on this decoder's device if on one, their frame counts and matrix pointers as arrays for the native call, and these
+        as the call's two leading arguments (_c_utts)."""
         batch = _Batch(logits_list, len(self._labels_list))
         if batch.is_device and batch.device_index is not None and batch.device_index != self._device:
             raise ValueError("the logits live on cuda:%d but this decoder was built for cuda:%d (one process per GPU: "
                              "LOCAL_RANK / CTCDEC_DEVICE pick the device)" % (batch.device_index, self._device))
-        return batch, np.ascontiguousarray(batch.frames, dtype=np.int32), np.ascontiguousarray(batch.ptrs, dtype=np.uint64)
+        frames, ptrs = np.ascontiguousarray(batch.frames, dtype=np.int32), np.ascontiguousarray(batch.ptrs, dtype=np.uint64)
+        return batch, frames, ptrs, self._c_utts(ptrs, frames)
+
+    @staticmethod
+    def _c_utts(ptrs: np.ndarray, frames: np.ndarray):
+        """-> the two leading arguments of every native transcript call: the matrix pointers and the frame counts"""
+        return ptrs.ctypes.data_as(C.POINTER(C.c_void_p)), frames.ctypes.data_as(C.POINTER(C.c_int32))
 
     @staticmethod
     def _frames_needed(ids: Sequence[int]) -> int:
@@ -2036,6 +2051,16 @@ class BeamSearchDecoderCTC:
         off[1:] = np.cumsum([len(ids) for ids in seqs])
         return (flat if len(flat) else np.zeros(1, dtype=np.int32)), off
 
+    @classmethod
+    def _pack_items(cls, items: Sequence[Sequence[Sequence[int]]]):
+        """-> (flat, label_off, item_off, n_items): _many_targets_each's id lists of every utterance end to end (_pack_ids),
+        and where each utterance's items start among them."""
+        flat_items = [ids for cur in items for ids in cur]
+        flat, label_off = cls._pack_ids(flat_items)
+        item_off = np.zeros(len(items) + 1, dtype=np.int64)
+        item_off[1:] = np.cumsum([len(cur) for cur in items])
+        return flat, label_off, item_off, len(flat_items)
+
     def align(self, logits: Any, text: Optional[str] = None, tokens: Optional[Sequence[int]] = None,
               confidence: Optional[str] = None) -> "AlignedText":
         """Forced alignment of one utterance: align_batch of a batch of one (a ValueError when no path exists)."""
@@ -2057,7 +2082,7 @@ class BeamSearchDecoderCTC:
         if n == 0:
             return []
         with self._call_lock:
-            batch, frames, ptrs = self._stage_transcript_call(logits_list)
+            batch, frames, ptrs, _ = self._stage_transcript_call(logits_list)
             keep = self._feasible("align", frames, targets, self._bp_table_bytes, int(_bp_budget) or ALIGN_BP_BUDGET, strict,
                                   "back-pointer table", "path")
             out: List[Optional[AlignedText]] = [None] * n
@@ -2069,7 +2094,7 @@ class BeamSearchDecoderCTC:
             res = C.c_void_p()
             lib = self._lib
             lib.check(lib.dll.ctcdec_align_batch(
-                self._handle, k_ptrs.ctypes.data_as(C.POINTER(C.c_void_p)), k_frames.ctypes.data_as(C.POINTER(C.c_int32)),
+                self._handle, *self._c_utts(k_ptrs, k_frames),
                 len(keep), batch.dtype, int(batch.is_device), flat.ctypes.data_as(C.POINTER(C.c_int32)), B.off_ptr(off), fold,
                 int(_bp_budget), C.byref(res)))
             try:
@@ -2186,7 +2211,7 @@ class BeamSearchDecoderCTC:
         if n == 0:
             return []
         with self._call_lock:
-            batch, frames, ptrs = self._stage_transcript_call(logits_list)
+            batch, frames, ptrs, _ = self._stage_transcript_call(logits_list)
             labels_only = [[c for c in items if c != -1] for items in targets]
             keep = self._feasible("align_gaps", frames, labels_only, self._bp_table_bytes, int(_bp_budget) or ALIGN_BP_BUDGET, strict,
                                   "back-pointer table", "path")
@@ -2199,7 +2224,7 @@ class BeamSearchDecoderCTC:
             res = C.c_void_p()
             lib = self._lib
             lib.check(lib.dll.ctcdec_align_gaps_batch(
-                self._handle, k_ptrs.ctypes.data_as(C.POINTER(C.c_void_p)), k_frames.ctypes.data_as(C.POINTER(C.c_int32)),
+                self._handle, *self._c_utts(k_ptrs, k_frames),
                 len(keep), batch.dtype, int(batch.is_device), flat.ctypes.data_as(C.POINTER(C.c_int32)), B.off_ptr(off), fold,
                 int(_bp_budget), C.byref(res)))
             try:
@@ -2270,12 +2295,12 @@ class BeamSearchDecoderCTC:
         token of every utterance (the space label of a character alphabet included) as arrays, utterance u's at
         ``[offsets[u], offsets[u + 1])``; ``logp`` and ``score`` are None without a fold."""
         with self._call_lock:
-            batch, frames, ptrs = self._stage_transcript_call(logits_list)
+            batch, frames, ptrs, c_utts = self._stage_transcript_call(logits_list)
             n = len(frames)
             res = C.c_void_p()
             lib = self._lib
             lib.check(lib.dll.ctcdec_greedy_batch(
-                self._handle, ptrs.ctypes.data_as(C.POINTER(C.c_void_p)), frames.ctypes.data_as(C.POINTER(C.c_int32)), n,
+                self._handle, *c_utts, n,
                 batch.dtype, int(batch.is_device), fold, C.byref(res)))
             try:
                 blob_p, off_p, nu = C.c_void_p(), C.POINTER(C.c_int64)(), C.c_int64()
@@ -2440,22 +2465,17 @@ class BeamSearchDecoderCTC:
         if n == 0:
             self.last_score_timing_ms, self.last_score_launched = (0.0, 0.0, 0.0, 0.0), (0, 0)
             return []
-        kernel_env = os.environ.get("CTCDEC_FORWARD_KERNEL", "")
-        if kernel_env and kernel_env not in FORWARD_KERNELS:
-            raise ValueError("CTCDEC_FORWARD_KERNEL must be wave or group, not %r" % kernel_env)
+        kernel = _forced_kernel("CTCDEC_FORWARD_KERNEL", FORWARD_KERNELS)
         with self._call_lock:
-            batch, frames, ptrs = self._stage_transcript_call(logits_list)
-            flat_hyps = [ids for cur in hyps for ids in cur]
-            flat, target_off = self._pack_ids(flat_hyps)
-            hyp_off = np.zeros(n + 1, dtype=np.int64)
-            hyp_off[1:] = np.cumsum([len(cur) for cur in hyps])
-            logp = np.zeros(max(len(flat_hyps), 1), dtype=np.float64)
+            batch, frames, ptrs, c_utts = self._stage_transcript_call(logits_list)
+            flat, target_off, hyp_off, nh = self._pack_items(hyps)
+            logp = np.zeros(max(nh, 1), dtype=np.float64)
             ms, launched = (C.c_double * 4)(), (C.c_int64 * 2)()
             lib = self._lib
             lib.check(lib.dll.ctcdec_score_batch(
-                self._handle, ptrs.ctypes.data_as(C.POINTER(C.c_void_p)), frames.ctypes.data_as(C.POINTER(C.c_int32)), n,
+                self._handle, *c_utts, n,
                 batch.dtype, int(batch.is_device), flat.ctypes.data_as(C.POINTER(C.c_int32)), B.off_ptr(target_off),
-                B.off_ptr(hyp_off), FORWARD_KERNELS.get(kernel_env, 0), logp.ctypes.data_as(C.POINTER(C.c_double)), ms, launched))
+                B.off_ptr(hyp_off), kernel, logp.ctypes.data_as(C.POINTER(C.c_double)), ms, launched))
             # [classification (frame-prune kernels), row_lse, forward kernels (HIP events), whole native call]; hypotheses that
             # went to (ctc_forward_wave, ctc_forward)
             self.last_score_timing_ms = tuple(float(v) for v in ms)
@@ -2516,16 +2536,10 @@ class BeamSearchDecoderCTC:
         self.last_prefix_next = None
         if n == 0:
             return []
-        kernel_env = os.environ.get("CTCDEC_FORWARD_KERNEL", "")
-        if kernel_env and kernel_env not in FORWARD_KERNELS:
-            raise ValueError("CTCDEC_FORWARD_KERNEL must be wave or group, not %r" % kernel_env)
+        kernel = _forced_kernel("CTCDEC_FORWARD_KERNEL", FORWARD_KERNELS)
         with self._call_lock:
-            batch, frames, ptrs = self._stage_transcript_call(logits_list)
-            flat_prefixes = [ids for cur in prefixes for ids in cur]
-            nh = len(flat_prefixes)
-            flat, label_off = self._pack_ids(flat_prefixes)
-            prefix_off = np.zeros(n + 1, dtype=np.int64)
-            prefix_off[1:] = np.cumsum([len(cur) for cur in prefixes])
+            batch, frames, ptrs, c_utts = self._stage_transcript_call(logits_list)
+            flat, label_off, prefix_off, nh = self._pack_items(prefixes)
             # one [prefixes, V] block of float64: for device tensors the shell makes it and the kernels fill it in place
             buf, next_ptr = None, None
             if batch.is_device and nh:
@@ -2536,9 +2550,9 @@ class BeamSearchDecoderCTC:
             res = C.c_void_p()
             lib = self._lib
             lib.check(lib.dll.ctcdec_prefix_batch(
-                self._handle, ptrs.ctypes.data_as(C.POINTER(C.c_void_p)), frames.ctypes.data_as(C.POINTER(C.c_int32)), n,
+                self._handle, *c_utts, n,
                 batch.dtype, int(batch.is_device), flat.ctypes.data_as(C.POINTER(C.c_int32)), B.off_ptr(label_off),
-                B.off_ptr(prefix_off), FORWARD_KERNELS.get(kernel_env, 0), next_ptr, C.byref(res)))
+                B.off_ptr(prefix_off), kernel, next_ptr, C.byref(res)))
             try:
                 end_p, next_p, np_, nv = C.POINTER(C.c_double)(), C.POINTER(C.c_double)(), C.c_int64(), C.c_int32()
                 lib.check(lib.dll.ctcdec_prefix_scores(res, C.byref(end_p), C.byref(next_p), C.byref(np_), C.byref(nv)))
@@ -2618,34 +2632,29 @@ class BeamSearchDecoderCTC:
         self.last_find_timing_ms, self.last_find_launches, self.last_find_launched = (0.0, 0.0, 0.0, 0.0), 0, (0, 0)
         if n == 0:
             return []
-        kernel_env = os.environ.get("CTCDEC_FIND_KERNEL", "")
-        if kernel_env and kernel_env not in FIND_KERNELS:
-            raise ValueError("CTCDEC_FIND_KERNEL must be wave or group, not %r" % kernel_env)
+        kernel = _forced_kernel("CTCDEC_FIND_KERNEL", FIND_KERNELS)
         with self._call_lock:
-            batch, frames, ptrs = self._stage_transcript_call(logits_list)
+            batch, frames, ptrs, c_utts = self._stage_transcript_call(logits_list)
             budget = int(_trace_budget) or ALIGN_BP_BUDGET
             for u, cur in enumerate(phrases):
                 for j, ids in enumerate(cur):
                     if int(frames[u]) >= self._frames_needed(ids) and 12 * int(frames[u]) > budget:
                         raise ValueError("find: utterance %d, phrase %d needs a trace of %d bytes, above the memory budget of %d "
                                          "bytes of one launch" % (u, j, 12 * int(frames[u]), budget))
-            flat_phrases = [ids for cur in phrases for ids in cur]
-            flat, label_off = self._pack_ids(flat_phrases)
-            hyp_off = np.zeros(n + 1, dtype=np.int64)
-            hyp_off[1:] = np.cumsum([len(cur) for cur in phrases])
+            flat, label_off, hyp_off, n_phrases = self._pack_items(phrases)
             res = C.c_void_p()
             lib = self._lib
             lib.check(lib.dll.ctcdec_find_batch(
-                self._handle, ptrs.ctypes.data_as(C.POINTER(C.c_void_p)), frames.ctypes.data_as(C.POINTER(C.c_int32)), n,
+                self._handle, *c_utts, n,
                 batch.dtype, int(batch.is_device), B.off_ptr(hyp_off), B.off_ptr(label_off), flat.ctypes.data_as(C.POINTER(C.c_int32)),
-                int(max_hits), floor, int(bool(trace)), FIND_KERNELS.get(kernel_env, 0), int(_trace_budget), C.byref(res)))
+                int(max_hits), floor, int(bool(trace)), kernel, int(_trace_budget), C.byref(res)))
             try:
                 ho, ps, pe, pl, nph = (C.POINTER(C.c_int64)(), C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)(),
                                        C.POINTER(C.c_double)(), C.c_int64())
                 lib.check(lib.dll.ctcdec_search_hits(res, C.byref(ho), C.byref(ps), C.byref(pe), C.byref(pl), C.byref(nph)))
-                if int(nph.value) != len(flat_phrases):
+                if int(nph.value) != n_phrases:
                     raise B.NativeError("the search holds another number of phrases than was asked for")
-                hit_off = np.ctypeslib.as_array(ho, shape=(len(flat_phrases) + 1,)).tolist()
+                hit_off = np.ctypeslib.as_array(ho, shape=(n_phrases + 1,)).tolist()
                 nh = hit_off[-1]
                 starts = np.ctypeslib.as_array(ps, shape=(nh,)).tolist() if nh else []
                 ends = np.ctypeslib.as_array(pe, shape=(nh,)).tolist() if nh else []
@@ -2654,7 +2663,7 @@ class BeamSearchDecoderCTC:
                 if trace:
                     to, tl, ts = C.POINTER(C.c_int64)(), C.POINTER(C.c_double)(), C.POINTER(C.c_int32)()
                     lib.check(lib.dll.ctcdec_search_trace(res, C.byref(to), C.byref(tl), C.byref(ts)))
-                    t_off = np.ctypeslib.as_array(to, shape=(len(flat_phrases) + 1,)).tolist()
+                    t_off = np.ctypeslib.as_array(to, shape=(n_phrases + 1,)).tolist()
                     nt = t_off[-1]
                     t_logp = np.ctypeslib.as_array(tl, shape=(nt,)).copy() if nt else np.zeros(0)
                     t_start = np.ctypeslib.as_array(ts, shape=(nt,)).copy() if nt else np.zeros(0, dtype=np.int32)
@@ -2706,7 +2715,7 @@ class BeamSearchDecoderCTC:
         if n == 0:
             return []
         with self._call_lock:
-            batch, frames, ptrs = self._stage_transcript_call(logits_list)
+            batch, frames, ptrs, _ = self._stage_transcript_call(logits_list)
             keep = self._feasible("posteriors", frames, targets, self._state_table_bytes, int(_table_budget) or POSTERIORS_TABLE_BUDGET, strict)
             out: List[Optional[TranscriptPosteriors]] = [None] * n
             if not keep:
@@ -2717,7 +2726,7 @@ class BeamSearchDecoderCTC:
             res = C.c_void_p()
             lib = self._lib
             lib.check(lib.dll.ctcdec_posteriors_batch(
-                self._handle, k_ptrs.ctypes.data_as(C.POINTER(C.c_void_p)), k_frames.ctypes.data_as(C.POINTER(C.c_int32)),
+                self._handle, *self._c_utts(k_ptrs, k_frames),
                 len(keep), batch.dtype, int(batch.is_device), B.off_ptr(off), flat.ctypes.data_as(C.POINTER(C.c_int32)),
                 int(bool(dense)), int(_table_budget), C.byref(res)))
             try:
@@ -2783,7 +2792,7 @@ class BeamSearchDecoderCTC:
         if n == 0:
             return [], None, []
         with self._call_lock:
-            batch, frames, ptrs = self._stage_transcript_call(logits_list)
+            batch, frames, ptrs, _ = self._stage_transcript_call(logits_list)
             keep = self._feasible("gradient", frames, targets, self._state_table_bytes, int(_table_budget) or POSTERIORS_TABLE_BUDGET, strict)
             out: List[Optional[TranscriptGradient]] = [None] * n
             if not keep:
@@ -2809,7 +2818,7 @@ class BeamSearchDecoderCTC:
             ms, launches, launched = (C.c_double * 5)(), C.c_int32(), (C.c_int64 * 2)()
             lib = self._lib
             lib.check(lib.dll.ctcdec_gradient_batch(
-                self._handle, k_ptrs.ctypes.data_as(C.POINTER(C.c_void_p)), k_frames.ctypes.data_as(C.POINTER(C.c_int32)),
+                self._handle, *self._c_utts(k_ptrs, k_frames),
                 len(keep), batch.dtype, int(batch.is_device), B.off_ptr(off), flat.ctypes.data_as(C.POINTER(C.c_int32)),
                 g_ptrs.ctypes.data_as(C.POINTER(C.c_void_p)), 1 if wide else 0, int(_table_budget),
                 logp.ctypes.data_as(C.POINTER(C.c_double)), ms, C.byref(launches), launched))

@@ -11,7 +11,7 @@ SOURCES = [os.path.join(SRC, "api.cpp"), os.path.join(SRC, "host_tables.cpp"), o
            os.path.join(ROOT, "tests", "sim", "backend_sim.cpp")]
 DEPS = SOURCES + [os.path.join(SRC, h) for h in ("common.h", "beam_core.h", "beam_wave.h", "text_wave.h", "set_order.h",
                                                   "np_sum.h", "np_f32.h", "backend.h", "host_tables.h", "ctc_align.h",
-                                                  "token_logp.h")] + [os.path.join(ROOT, "tests", "sim", "wave_fibers.h"), os.path.join(ROOT, "tests", "sim", "group_fibers.h")] + [os.path.join(ROOT, "include", "ctcdec.h")]
+                                                  "token_logp.h", "api_internal.h", "api_transcript.cpp")] + [os.path.join(ROOT, "tests", "sim", "wave_fibers.h"), os.path.join(ROOT, "tests", "sim", "group_fibers.h")] + [os.path.join(ROOT, "include", "ctcdec.h")]
 
 
 def build(force: bool = False) -> str:
