@@ -322,6 +322,15 @@ class OracleState:
         self.text_memo = text_memo
         self.partial_memo = partial_memo
 
+    def refresh_memos(self, hotwords: Optional[Iterable[str]], hotword_weight: float) -> None:
+        """For a caller whose hot-word set changes between chunks: give every memoised text the bonus of the NEW set and forget
+        the partial-word scores. The reference does neither -- texts and partial words met under the old set keep its bonus --;
+        the package scores everything against the new set, which is the reference after this refresh."""
+        hw = HotwordOracle(hotwords, hotword_weight) if hotwords is not None else HotwordOracle([], 0.0)
+        for key, (_, raw, end) in list(self.text_memo.items()):
+            self.text_memo[key] = (raw + hw.score(key[0]), raw, end)
+        self.partial_memo.clear()
+
 
 # Decoders live in a module-level registry so that fork-pool workers find them (and their LM) in
 # inherited memory instead of un-pickling them per task -- the reference does the same with its

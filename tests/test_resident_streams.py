@@ -59,8 +59,10 @@ def _scenario_unread_chunks(build, to_input, beam_width, labels, is_bpe):
 
 
 def _scenario_reads_edits_and_hotwords(build, to_input):
-    """Lists that are read stay valid and can still be handed back; edited lists, lists of another stream and a changed
-    hot-word set go through the host import -- every route equals the oracle."""
+    """Lists that are read stay valid and can still be handed back, with one hot-word scorer for every chunk (a); an edited list
+    goes through the host import (b) and is resident again afterwards, force_next_word included (c); a hot-word set that changes
+    in mid-stream goes through the import too and equals the oracle whose memos are refreshed at the change (d) -- the package's
+    contract there, pinned on the reference itself by tests/test_stream_golden.py. Every route equals the oracle."""
     labels = synth.LIBRI_LABELS
     dec = build(labels, LM.path)
     alpha = Alphabet.build_alphabet(labels)
@@ -98,6 +100,20 @@ def _scenario_reads_edits_and_hotwords(build, to_input):
     with np.errstate(all="ignore"):
         ob = orc.partial_decode_beams(x[75:], st, 75, is_end=True)
     check_beams(_lm_beams(beams), _oracle_beams(ob), what="after force_next_word")
+    # (d) the hot-word set changes after the first chunk and is dropped for the last: every carried beam and every later partial
+    # word is scored against the set of the call that runs = the oracle after OracleState.refresh_memos
+    plan = [(hot, 8.0), (LM.hotwords(3, 2), 3.0), (None, None)]
+    beams, c1, c2 = dec.get_starting_state()
+    st = orc.get_starting_state()
+    for k, (a, b) in enumerate(zip(cuts[:-1], cuts[1:])):
+        words, weight = plan[k]
+        beams = dec.partial_decode_beams(to_input(x[a:b]), c1, c2, beams, a, is_end=(b == 90),
+                                         hotword_scorer=None if words is None else HotwordScorer.build_scorer(words, weight=weight))
+        if k > 0:
+            st.refresh_memos(words, weight)
+        with np.errstate(all="ignore"):
+            ob = orc.partial_decode_beams(x[a:b], st, a, is_end=(b == 90), hotwords=words, hotword_weight=weight)
+        check_beams(_lm_beams(beams), _oracle_beams(ob), what="changed hot words %d:%d" % (a, b))
 
 
 def _scenario_many_streams_long(build, to_input, n_streams, n_chunks, chunk, beam_width):
