@@ -367,6 +367,30 @@ int ctcdec_alignment_tokens(const ctcdec_alignment* a, const int64_t** tok_off, 
 int ctcdec_alignment_timing(const ctcdec_alignment* a, double* ms4, int32_t* launches);
 void ctcdec_alignment_free(ctcdec_alignment* a);
 
+/* ---- forced alignment of long transcripts: a lecture against its script ------------------------------------------------
+ * ctcdec_align_batch without its two limits: at most 1048575 labels per utterance (2 L + 1 states below 2^21) instead of
+ * 2047, and no back-pointer table of all frames. For every input ctcdec_align_batch accepts the result is that call's, bit
+ * for bit -- path, score, token frames and confidences --, however the frames are cut: the recursion, its operands, their
+ * order and the tie rules are the same. Both score columns live in device memory (kernel ctc_viterbi_long, one workgroup
+ * per utterance), so for short targets ctcdec_align_batch is the faster call.
+ * The frames 1 .. T - 1 of an utterance are cut into n = ceil((T - 1) / K) segments of K frames. With nch = ceil((2 L + 1) / 4)
+ * its plan takes  K * nch + (n > 1 ? 32 * nch * n : 0) + 64 * nch  bytes: one segment's back-pointers, the score column every
+ * segment starts from, the two columns. One segment is one pass, as ctcdec_align_batch makes it; more segments are one pass
+ * that keeps the checkpoints and a second, from the last segment to the first, that fills and traces back one table each.
+ * segment_frames: 0 -- one segment (K = T) when that plan fits the budget, else K = min(T, ceil(sqrt(32 T))) --, or > 0 to
+ * force K = min(segment_frames, T). bp_budget: the planned bytes one launch may hold, 0 for 1 GiB; a batch that needs more is
+ * aligned in several launches with the same results.
+ * Validation, before any launch: ctcdec_align_batch's checks with its codes; segment_frames < 0 is CTCDEC_ERR_ARG; more than
+ * 1048575 labels, or one utterance whose plan exceeds the budget, is CTCDEC_ERR_LIMIT and names the utterance.
+ * The result is read by ctcdec_alignment_paths / _tokens / _timing ([2] ctc_viterbi_long) / _plan and freed by
+ * ctcdec_alignment_free. decoder.py: align_long / align_long_batch. */
+int ctcdec_align_long_batch(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts,
+                            int32_t dtype, int32_t is_device, const int32_t* targets, const int64_t* target_off, int32_t fold,
+                            int64_t bp_budget, int32_t segment_frames, ctcdec_alignment** out);
+/* How each utterance's frames were cut: segment_frames[u] = K and n_segments[u] = ceil((T - 1) / K) (0 / 0 without frames). An
+ * alignment made by ctcdec_align_batch or ctcdec_align_gaps_batch reports one segment of all T frames. */
+int ctcdec_alignment_plan(const ctcdec_alignment* a, const int32_t** segment_frames, const int32_t** n_segments, int64_t* n_utts);
+
 /* ---- alignment with gaps: a transcript that does not cover all of the audio ------------------------------------------
  * torchaudio's forced_align tutorials do this with a "star" token. ctcdec_align_batch with one more kind of target item:
  * CTCDEC_ALIGN_GAP stands for "something nobody transcribed". A target is a sequence of items, each a label id (alphabet

@@ -153,6 +153,11 @@ _PROTOS = {
                                           C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.c_int64)]),
     "ctcdec_alignment_timing": (C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
     "ctcdec_alignment_free": (None, [_VP]),
+    "ctcdec_align_long_batch": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32,
+                                          C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_int32, C.c_int64, C.c_int32,
+                                          C.POINTER(_VP)]),
+    "ctcdec_alignment_plan": (C.c_int, [_VP, C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_int32)),
+                                        C.POINTER(C.c_int64)]),
     "ctcdec_align_gaps_batch": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32,
                                           C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_int32, C.c_int64, C.POINTER(_VP)]),
     "ctcdec_alignment_gaps": (C.c_int, [_VP, C.POINTER(C.POINTER(C.c_int64)), C.POINTER(C.POINTER(C.c_int32)),

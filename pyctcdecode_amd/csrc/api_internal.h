@@ -182,6 +182,9 @@ struct ctcdec_decoder {
   // forced alignment (ctcdec_align_batch): row log-sum-exps, targets, paths, token spans, confidences, scores, the launch's
   // back-pointer tables and utterance records
   DevBuf w_alse, w_alab, w_apath, w_atok, w_atlp, w_ascore, w_abp, w_autts;
+  // forced alignment of long transcripts (ctcdec_align_long_batch): a launch's score columns, checkpoints and utterance
+  // records (the segment tables: w_abp; everything else: the alignment's)
+  DevBuf w_lcol, w_lckpt, w_lutts;
   // transcript likelihood (ctcdec_score_batch): the hypothesis records of a launch (labels: w_alab, scores: w_ascore)
   DevBuf w_fhyps;
   // frame posteriors (ctcdec_posteriors_batch): a launch's tables and utterance records, the token sums (labels: w_alab,

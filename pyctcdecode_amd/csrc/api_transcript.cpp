@@ -23,6 +23,8 @@ struct ctcdec_alignment {
   bool has_logp = false;
   int32_t launches = 0;
   double ms[4] = {0, 0, 0, 0};
+  // how each utterance's frames were cut (ctcdec_alignment_plan): one segment of all of them unless ctcdec_align_long_batch cut
+  std::vector<int32_t> seg_frames, n_segs;
   // ctcdec_align_gaps_batch: utterance u's gaps, in target order, are [gap_off[u], gap_off[u + 1])
   bool has_gaps = false;
   std::vector<int64_t> gap_off;
@@ -32,6 +34,31 @@ struct ctcdec_alignment {
 
 // The back-pointer tables of one ctc_viterbi launch (T * align_chunks(L) bytes per utterance) when the caller names no budget
 static const int64_t ALIGN_BP_BUDGET = (int64_t)1 << 30;
+
+// ---- the plan of ctcdec_align_long_batch ("Forced alignment of long transcripts") ----------------------------
+// An utterance's frames in segments of K: a table of K rows, a checkpoint per segment when there is more than one, and the two
+// score columns. A pure function of (T, L, budget, segment_frames); decoder.py's _align_long_plan is the same rule.
+struct LongPlan {
+  int32_t K = 0, n_seg = 0;
+  int64_t bytes = 0;
+};
+static LongPlan long_plan_of(int64_t T, int32_t L, int64_t K) {
+  const int64_t nch = align_chunks(L), n = align_long_segments((int32_t)T, (int32_t)K);
+  return LongPlan{(int32_t)K, (int32_t)n, K * nch + (n > 1 ? 32 * nch * n : 0) + 64 * nch};
+}
+static int64_t long_balanced_frames(int64_t T) {  // ceil(sqrt(32 T)), at most T
+  int64_t K = (int64_t)sqrt(32.0 * (double)T);
+  while (K * K < 32 * T) ++K;
+  while (K > 1 && (K - 1) * (K - 1) >= 32 * T) --K;
+  return std::min(K, T);
+}
+// segment_frames > 0: that many frames (at most T); else one segment when its plan fits the budget, else the balanced K
+static LongPlan long_plan(int32_t T, int32_t L, int64_t budget, int32_t segment_frames) {
+  if (T <= 0) return LongPlan();
+  if (segment_frames > 0) return long_plan_of(T, L, std::min<int64_t>(segment_frames, T));
+  const LongPlan whole = long_plan_of(T, L, T);
+  return whole.bytes <= budget ? whole : long_plan_of(T, L, long_balanced_frames(T));
+}
 
 #ifdef CTC_SIM
 namespace {
@@ -119,16 +146,19 @@ static int check_frames(const void* const* utt_logits, const int32_t* utt_frames
 
 // Everything the kernels index with comes from the caller: checked here, before anything moves.
 static int check_alignment(const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts, const int32_t* targets,
-                           const int64_t* target_off, int64_t budget, const TranscriptCall& tc) {
+                           const int64_t* target_off, int64_t budget, const TranscriptCall& tc, int32_t max_labels = ALIGN_MAX_LABELS,
+                           int32_t segment_frames = -1) {
+  const bool planned = segment_frames >= 0;  // ctcdec_align_long_batch: the budget bounds an utterance's plan, not its whole table
   if (target_off[0] != 0) return fail(CTCDEC_ERR_ARG, "target_off must start at 0");
   std::string infeasible;
   for (int32_t u = 0; u < n_utts; ++u) {
     const int64_t T = utt_frames[u], L = target_off[u + 1] - target_off[u];
     if (T < 0) return fail(CTCDEC_ERR_ARG, "negative frame count");
     if (L < 0) return fail(CTCDEC_ERR_ARG, "target_off must not decrease");
-    if (L > ALIGN_MAX_LABELS)
+    if (L > max_labels)
       return fail(CTCDEC_ERR_LIMIT, "utterance " + std::to_string(u) + ": " + std::to_string(L) + " target labels, above the limit of " +
-                                        std::to_string(ALIGN_MAX_LABELS) + " (two fp64 score columns of 2L + 1 states in LDS)");
+                                        std::to_string(max_labels) +
+                                        (planned ? " (2L + 1 states below 2^21)" : " (two fp64 score columns of 2L + 1 states in LDS)"));
     if (L > 0 && !targets) return fail(CTCDEC_ERR_ARG, "no targets");
     if (T > 0 && !utt_logits[u]) return fail(CTCDEC_ERR_ARG, "utterance " + std::to_string(u) + ": no logits");
     int64_t need = 0;
@@ -136,7 +166,12 @@ static int check_alignment(const void* const* utt_logits, const int32_t* utt_fra
                               "target label", need))
       return rc;
     if (T < need) infeasible += (infeasible.empty() ? "" : ", ") + std::to_string(u);
-    if (T * (int64_t)align_chunks((int32_t)L) > budget)
+    if (planned) {
+      const int64_t bytes = long_plan((int32_t)T, (int32_t)L, budget, segment_frames).bytes;
+      if (bytes > budget)
+        return fail(CTCDEC_ERR_LIMIT, "utterance " + std::to_string(u) + ": segment tables, checkpoints and columns of " + std::to_string(bytes) +
+                                          " bytes, above the budget of " + std::to_string(budget) + " bytes for one launch");
+    } else if (T * (int64_t)align_chunks((int32_t)L) > budget)
       return fail(CTCDEC_ERR_LIMIT, "utterance " + std::to_string(u) + ": a back-pointer table of " +
                                         std::to_string(T * (int64_t)align_chunks((int32_t)L)) + " bytes, above the budget of " +
                                         std::to_string(budget) + " bytes for one launch");
@@ -272,15 +307,20 @@ struct GapSlots {
   std::vector<double> logp;
 };
 
-// The call behind ctcdec_align_batch (Utt = AlignUtt, no slots) and ctcdec_align_gaps_batch (Utt = GapsUtt): the checked
-// labels of every utterance to a result with its paths, spans, scores and, with a fold, confidences.
+// The call behind ctcdec_align_batch (Utt = AlignUtt, no slots), ctcdec_align_gaps_batch (Utt = GapsUtt) and
+// ctcdec_align_long_batch (Utt = AlignLongUtt, with every utterance's plan): the checked labels of every utterance to a
+// result with its paths, spans, scores and, with a fold, confidences.
 template <class Utt>
 static int viterbi_call(ctcdec_decoder* dec, const TranscriptCall& tc, const void* const* utt_logits, const int32_t* utt_frames,
                         int32_t n_utts, int32_t dtype, int32_t is_device, const int32_t* labels, const int64_t* lab_off, int32_t fold,
-                        int64_t budget, GapSlots* slots, std::unique_ptr<ctcdec_alignment>& res) {
-  constexpr bool GAPS = std::is_same<Utt, GapsUtt>::value;
+                        int64_t budget, GapSlots* slots, const std::vector<LongPlan>* plans, std::unique_ptr<ctcdec_alignment>& res) {
+  constexpr bool GAPS = std::is_same<Utt, GapsUtt>::value, LONG = std::is_same<Utt, AlignLongUtt>::value;
   res.reset(new ctcdec_alignment());
   const size_t n = (size_t)n_utts;
+  for (size_t u = 0; u < n; ++u) {
+    res->seg_frames.push_back(LONG ? (*plans)[u].K : utt_frames[u]);
+    res->n_segs.push_back(LONG ? (*plans)[u].n_seg : 1);
+  }
   const int64_t NL = lab_off[n], NS = GAPS ? slots->off[n] : 0;
   const std::vector<int64_t> row0 = row_starts(utt_frames, n);
   const int64_t R = row0[n];
@@ -310,16 +350,30 @@ static int viterbi_call(ctcdec_decoder* dec, const TranscriptCall& tc, const voi
       be::zero(dec->w_atlp.p, nl1 * 8, &err) || be::zero(dec->w_ascore.p, n * 8, &err) ||
       (GAPS && (be::h2d(dec->w_agap.p, slots->gap.data(), (size_t)NS, &err) || be::zero(dec->w_aglp.p, (size_t)NS * 8, &err))))
     return fail(CTCDEC_ERR_DEVICE, err);
-  // launches: utterances in input order until their back-pointer tables fill the budget; longest first inside a launch
+  // launches: utterances in input order until their back-pointer tables (LONG: their planned bytes) fill the budget; longest
+  // first inside a launch
   const auto chunks_of = [&](int32_t u) { return align_chunks((int32_t)(lab_off[u + 1] - lab_off[u])); };
+  // (LONG) the bytes of an utterance's segment table, and the doubles of its two columns and its checkpoints: the plan's terms
+  const auto table_of = [&](int32_t u) { return LONG ? (int64_t)(*plans)[(size_t)u].K * chunks_of(u) : (int64_t)utt_frames[u] * chunks_of(u); };
+  const auto doubles_of = [&](int32_t u) { return LONG ? ((*plans)[(size_t)u].bytes - table_of(u)) / 8 : (int64_t)0; };
   std::vector<std::vector<int32_t>> groups;
-  const int64_t most = budget_groups(n_utts, [&](int32_t u) { return (int64_t)utt_frames[u] * chunks_of(u); }, budget, groups);
+  int64_t most = budget_groups(n_utts, [&](int32_t u) { return LONG ? (*plans)[(size_t)u].bytes : table_of(u); }, budget, groups);
+  if constexpr (LONG) {  // the two workspaces of a launch, each by the launch that needs most of it
+    int64_t most_doubles = 0;
+    most = 0;
+    for (const auto& g : groups) {
+      int64_t tables = 0, doubles = 0;
+      for (int32_t u : g) tables += table_of(u), doubles += doubles_of(u);
+      most = std::max(most, tables), most_doubles = std::max(most_doubles, doubles);
+    }
+    if (dec->w_lcol.ensure((size_t)std::max<int64_t>(most_doubles, 1) * 8, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+  }
   if (dec->w_abp.ensure((size_t)std::max<int64_t>(most, 1), &err)) return fail(CTCDEC_ERR_DEVICE, err);
   std::vector<Utt> utts;
   for (auto& g : groups) {
     std::stable_sort(g.begin(), g.end(), [&](int32_t a, int32_t b) { return utt_frames[a] > utt_frames[b]; });
     utts.clear();
-    int64_t bp_off = 0;
+    int64_t bp_off = 0, col_off = 0;
     int32_t max_chunks = 1;
     for (int32_t u : g) {
       const int64_t lo = lab_off[u];
@@ -336,39 +390,50 @@ static int viterbi_call(ctcdec_decoder* dec, const TranscriptCall& tc, const voi
       a.T = utt_frames[u];
       a.L = (int32_t)(lab_off[u + 1] - lo);
       a.is_prob = fr.is_prob[(size_t)u] ? 1 : 0;
-      a.pad = 0;
+      if constexpr (LONG) {
+        a.K = (*plans)[(size_t)u].K;
+        a.col = (double*)dec->w_lcol.p + col_off;
+        a.ckpt = a.col + 8 * (int64_t)chunks_of(u);  // (read only when there is more than one segment)
+        col_off += doubles_of(u);
+      } else {
+        a.pad = 0;
+      }
       if constexpr (GAPS) {
         a.rmax = fr.rmax + row0[(size_t)u];
         a.gap = (const uint8_t*)dec->w_agap.p + slots->off[(size_t)u];
         a.gap_logp = (double*)dec->w_aglp.p + slots->off[(size_t)u];
       }
       utts.push_back(a);
-      bp_off += (int64_t)utt_frames[u] * chunks_of(u);
+      bp_off += table_of(u);
       max_chunks = std::max(max_chunks, chunks_of(u));
     }
 #ifdef CTC_SIM
-    std::vector<double> col((size_t)(GAPS ? 2 : 8) * (size_t)max_chunks);
+    std::vector<double> col((size_t)(GAPS ? 2 : LONG ? 0 : 8) * (size_t)max_chunks);  // (LONG: the columns are the record's)
     AlignSeqCtx cx;
     for (const Utt& a : utts) {
       if constexpr (GAPS)
         for_dtype(dtype, [&](auto dt) { ctc_viterbi_gaps_utt<decltype(dt)::value>(cx, a, tc.V, tc.blank, fold, tc.clip_lo, col.data()); });
+      else if constexpr (LONG)
+        ctc_viterbi_long_utt(cx, a, tc.V, dtype, tc.blank, fold, tc.clip_lo);
       else
         ctc_viterbi_utt(cx, a, tc.V, dtype, tc.blank, fold, tc.clip_lo, col.data());
     }
 #else
-    DevBuf& records = GAPS ? dec->w_agutts : dec->w_autts;
+    DevBuf& records = GAPS ? dec->w_agutts : LONG ? dec->w_lutts : dec->w_autts;
     if (upload(records, utts, &err)) return fail(CTCDEC_ERR_DEVICE, err);
-    typename std::conditional<GAPS, be::ViterbiGapsArgs, be::ViterbiArgs>::type va;
+    typename std::conditional<GAPS, be::ViterbiGapsArgs, typename std::conditional<LONG, be::ViterbiLongArgs, be::ViterbiArgs>::type>::type va;
     va.utts = (const Utt*)records.p;
     va.n_utts = (int32_t)utts.size();
     va.n_labels = tc.V;
     va.dtype = dtype;
     va.blank = tc.blank;
     va.fold = fold;
-    va.max_chunks = max_chunks;
+    if constexpr (LONG) va.pad = 0;
+    else va.max_chunks = max_chunks;
     va.clip_lo = tc.clip_lo;
     int rc;
     if constexpr (GAPS) rc = be::launch_ctc_viterbi_gaps(va, &err);
+    else if constexpr (LONG) rc = be::launch_ctc_viterbi_long(va, &err);
     else rc = be::launch_ctc_viterbi(va, &err);
     if (rc) return fail(CTCDEC_ERR_DEVICE, err);
 #endif
@@ -383,7 +448,7 @@ static int viterbi_call(ctcdec_decoder* dec, const TranscriptCall& tc, const voi
   if (GAPS && be::d2h(slots->logp.data(), dec->w_aglp.p, (size_t)NS * 8, &err)) return fail(CTCDEC_ERR_DEVICE, err);
 #ifndef CTC_SIM
   res->ms[1] = be::align_kernel_ms(GAPS ? be::K_ROW_LSE_MAX : be::K_ROW_LSE);
-  res->ms[2] = be::align_kernel_ms(GAPS ? be::K_VITERBI_GAPS : be::K_VITERBI);
+  res->ms[2] = be::align_kernel_ms(GAPS ? be::K_VITERBI_GAPS : LONG ? be::K_VITERBI_LONG : be::K_VITERBI);
 #endif
   return CTCDEC_OK;
 }
@@ -401,7 +466,7 @@ int ctcdec_align_batch(ctcdec_decoder* dec, const void* const* utt_logits, const
   const auto t_begin = Clock::now();
   std::unique_ptr<ctcdec_alignment> res;
   if (int rc = viterbi_call<AlignUtt>(dec, tc, utt_logits, utt_frames, n_utts, dtype, is_device, targets, target_off, fold, budget,
-                                      nullptr, res))
+                                      nullptr, nullptr, res))
     return rc;
   res->ms[3] = ms(t_begin, Clock::now());
   *out = res.release();
@@ -438,6 +503,39 @@ int ctcdec_alignment_timing(const ctcdec_alignment* a, double* ms4, int32_t* lau
 }
 
 void ctcdec_alignment_free(ctcdec_alignment* a) { delete a; }
+
+// ---- forced alignment of long transcripts ("Forced alignment of long transcripts") -----------------------------
+int ctcdec_align_long_batch(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts, int32_t dtype,
+                            int32_t is_device, const int32_t* targets, const int64_t* target_off, int32_t fold, int64_t bp_budget,
+                            int32_t segment_frames, ctcdec_alignment** out) {
+  TranscriptCall tc;
+  const bool args_ok = dec && out && n_utts >= 0 && target_off && bp_budget >= 0 && (n_utts == 0 || (utt_logits && utt_frames));
+  const std::string bad_option = !bad_fold(fold).empty() ? bad_fold(fold) : segment_frames < 0 ? "segment_frames must not be negative" : "";
+  if (int rc = transcript_open(dec, args_ok, dtype, bad_option, tc)) return rc;
+  const int64_t budget = bp_budget ? bp_budget : ALIGN_BP_BUDGET;
+  if (int rc = check_alignment(utt_logits, utt_frames, n_utts, targets, target_off, budget, tc, ALIGN_LONG_MAX_LABELS, segment_frames))
+    return rc;
+  std::vector<LongPlan> plans;
+  for (int32_t u = 0; u < n_utts; ++u)
+    plans.push_back(long_plan(utt_frames[u], (int32_t)(target_off[u + 1] - target_off[u]), budget, segment_frames));
+  const auto t_begin = Clock::now();
+  std::unique_ptr<ctcdec_alignment> res;
+  if (int rc = viterbi_call<AlignLongUtt>(dec, tc, utt_logits, utt_frames, n_utts, dtype, is_device, targets, target_off, fold, budget,
+                                          nullptr, &plans, res))
+    return rc;
+  res->ms[3] = ms(t_begin, Clock::now());
+  *out = res.release();
+  return CTCDEC_OK;
+}
+
+int ctcdec_alignment_plan(const ctcdec_alignment* a, const int32_t** segment_frames_out, const int32_t** n_segments_out,
+                          int64_t* n_utts_out) {
+  if (!a || !segment_frames_out || !n_segments_out || !n_utts_out) return fail(CTCDEC_ERR_ARG, "no alignment");
+  *segment_frames_out = a->seg_frames.data();
+  *n_segments_out = a->n_segs.data();
+  *n_utts_out = (int64_t)a->seg_frames.size();
+  return CTCDEC_OK;
+}
 
 // ---- alignment with gaps ("Alignment with gaps") -------------------------------------------------------------
 int ctcdec_align_gaps_batch(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts, int32_t dtype,
@@ -482,7 +580,7 @@ int ctcdec_align_gaps_batch(ctcdec_decoder* dec, const void* const* utt_logits, 
   const auto t_begin = Clock::now();
   std::unique_ptr<ctcdec_alignment> res;
   if (int rc = viterbi_call<GapsUtt>(dec, tc, utt_logits, utt_frames, n_utts, dtype, is_device, labels.data(), lab_off.data(), fold,
-                                     budget, &slots, res))
+                                     budget, &slots, nullptr, res))
     return rc;
   // the gaps, in target order: everything between the end of the label before and the start of the label after
   res->gap_off.assign(n + 1, 0);

@@ -242,6 +242,19 @@ struct ViterbiArgs {
   double clip_lo;      // ln(MIN_TOKEN_CLIP_P)
 };
 int launch_ctc_viterbi(const ViterbiArgs& a, std::string* err);
+// ctc_viterbi_long: one workgroup of 1024 threads per entry of `utts`, all of them validated by the host (AlignLongUtt); the
+// columns, checkpoints and segment tables the entries name are theirs alone
+struct ViterbiLongArgs {
+  const AlignLongUtt* utts;  // [n_utts] (device)
+  int32_t n_utts;
+  int32_t n_labels;
+  int32_t dtype;
+  int32_t blank;
+  int32_t fold;        // 0, LOGP_MEAN / LOGP_MIN / LOGP_MAX
+  int32_t pad;
+  double clip_lo;      // ln(MIN_TOKEN_CLIP_P)
+};
+int launch_ctc_viterbi_long(const ViterbiLongArgs& a, std::string* err);
 // ctc_forward (wave == 0: one workgroup per entry of `hyps`) / ctc_forward_wave (wave != 0: one wavefront per entry, every
 // L <= FORWARD_WAVE_MAX_LABELS), all entries validated by the host (ForwardHyp)
 struct ForwardArgs {
@@ -335,7 +348,7 @@ int launch_ctc_prefix_advance(const PrefixAdvanceArgs& a, std::string* err);
 // two passes, and ctc_prefix_extend, ctc_prefix_finish and ctc_prefix_fill; ctc_prefix_advance has its own.
 enum AlignKernel {
   K_ROW_LSE, K_VITERBI, K_FORWARD, K_POSTERIORS, K_GRAD_ROWS, K_FIND, K_ROW_LSE_MAX, K_VITERBI_GAPS, K_ROW_ARGMAX, K_ROW_LSE_ARGMAX,
-  K_GREEDY_COLLAPSE, K_PREFIX_EXTEND, K_PREFIX_ADVANCE, ALIGN_KERNELS
+  K_GREEDY_COLLAPSE, K_PREFIX_EXTEND, K_PREFIX_ADVANCE, K_VITERBI_LONG, ALIGN_KERNELS
 };
 void align_timing_reset();
 double align_kernel_ms(AlignKernel kind);

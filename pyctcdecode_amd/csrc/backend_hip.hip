@@ -569,6 +569,8 @@ int launch_ctc_find_on(const FindArgs& a, int wave, hipStream_t stream, std::str
 int launch_ctc_find(const FindArgs& a, int wave, std::string* err) { return launch_ctc_find_on(a, wave, g_stream, err); }
 int launch_row_lse(const RowLseArgs& a, std::string* err) { return launch_row_lse_on(a, g_stream, err); }
 int launch_ctc_viterbi(const ViterbiArgs& a, std::string* err) { return launch_ctc_viterbi_on(a, g_stream, err); }
+int launch_ctc_viterbi_long_on(const ViterbiLongArgs& a, hipStream_t stream, std::string* err);
+int launch_ctc_viterbi_long(const ViterbiLongArgs& a, std::string* err) { return launch_ctc_viterbi_long_on(a, g_stream, err); }
 int launch_row_lse_max_on(const RowLseArgs& a, double* rmax, hipStream_t stream, std::string* err);
 int launch_row_lse_max(const RowLseArgs& a, double* rmax, std::string* err) { return launch_row_lse_max_on(a, rmax, g_stream, err); }
 int launch_ctc_viterbi_gaps_on(const ViterbiGapsArgs& a, hipStream_t stream, std::string* err);

@@ -4,6 +4,7 @@
 // context). The bodies:
 //   row_lse_seq, row_lse_max_seq   a row's fp64 log-sum-exp (and maximum): the simulator's; the kernels fold by lanes
 //   ctc_viterbi_utt                the best path, its columns in LDS            (kernel ctc_viterbi)
+//   ctc_viterbi_long_utt           the best path, its columns in device memory, its frames in segments  (ctc_viterbi_long)
 //   ctc_forward_hyp / _wave_hyp    the sum over all paths                       (ctc_forward / ctc_forward_wave)
 //   ctc_posteriors_utt             the forward-backward                         (ctc_posteriors)
 //   ctc_grad_row                   the gradient of the likelihood, row by row   (ctc_grad_rows)
@@ -15,7 +16,9 @@
 //   ctc_prefix_extend_tile, ctc_prefix_finish_col   every label's prefix score from them  (ctc_prefix_extend, ctc_prefix_finish)
 //   ctc_prefix_advance_child       a child prefix' end states from its parent's  (ctc_prefix_advance)
 // The shared pieces, and who uses them:
-//   viterbi_backtrace, fold_token_logp                   ctc_viterbi, ctc_viterbi_gaps
+//   viterbi_backtrace                                    ctc_viterbi, ctc_viterbi_gaps
+//   viterbi_backtrace_span (a segment of it)             ctc_viterbi_long
+//   fold_token_logp                                      ctc_viterbi, ctc_viterbi_gaps, ctc_viterbi_long
 //   group_setup, EntrySource, FrameEntries               ctc_find, ctc_find_wave, ctc_viterbi_gaps
 //   thread_setup                                         ctc_find, ctc_viterbi_gaps
 // ctc_forward_hyp, ctc_forward_wave_hyp and ctc_posteriors_utt keep their loops in raw variables: over FrameEntries
@@ -155,6 +158,30 @@ CTC_HD void viterbi_backtrace(int s, int T, int nch, const uint8_t* bp, const in
     }
   }
 }
+// viterbi_backtrace_span: the frames t_hi down to t_lo of it, from state s of frame t_hi; frame t's back-pointers are row
+// t - row0 of bp. Leaves in s the state of frame t_lo - 1 (of frame 0 when t_lo is 0) and in `open` the label whose span is
+// still open -- a span may go on below t_lo: the next span, over the frames below, takes both over (ctc_viterbi_long).
+// viterbi_backtrace is this over (T - 1, 0, row 0) with nothing open; written as that call, ctc_viterbi and ctc_viterbi_gaps
+// compile to other instructions (tools/kernel_asm_diff.py), so it keeps its own loop.
+template <class SlotValue>
+CTC_HD void viterbi_backtrace_span(int& s, int& open, int t_hi, int t_lo, int row0, int nch, const uint8_t* bp, const int32_t* lab,
+                                   int32_t* path, int32_t* tok_start, int32_t* tok_end, SlotValue slot_value) {
+  for (int t = t_hi; t >= t_lo; --t) {
+    if (s & 1) {
+      const int k = s >> 1;
+      if (k != open) tok_end[k] = t + 1, open = k;
+      tok_start[k] = t;
+      path[t] = lab[k];
+    } else {
+      path[t] = slot_value(s >> 1);
+    }
+    if (t > 0) {
+      const unsigned b = (bp[(size_t)(t - row0) * (size_t)nch + (size_t)(s >> 2)] >> (2 * (s & 3))) & 3u;
+      s -= (int)b;
+      if (s < 0) s = 0;
+    }
+  }
+}
 
 // The confidence fold, a thread per label: the mean, minimum or maximum of the label's log-probability over its span
 template <class Ctx>
@@ -253,6 +280,172 @@ CTC_HD void ctc_viterbi_utt(Ctx& cx, const AlignUtt& u, int V, int dtype, int bl
     *u.score = fin[s];
     viterbi_backtrace(s, T, nch, u.bp, u.lab, u.path, u.tok_start, u.tok_end, [&](int) { return blank; });
   }
+  if (!fold) return;
+  cx.sync();  // (the spans thread 0 wrote are read by every thread)
+  fold_token_logp(cx, u.x, dtype, u.lse, u.lab, u.tok_start, u.tok_end, u.tok_logp, T, L, V, is_prob, fold, clip_lo);
+}
+
+// ---- ctc_viterbi_long ---------------------------------------------------------------------------------------------------------
+// ctc_viterbi's best path for targets whose columns do not fit LDS and whose back-pointer table does not fit memory
+// ("Forced alignment of long transcripts"): the same states, window, operands, order of operations and tie rules,
+// so the same bits. Both score columns live in device memory. The frames 1 .. T - 1 are cut into n = ceil((T - 1) / K)
+// segments; segment j takes the frames j K + 1 .. min((j + 1) K, T - 1) and starts from the column of frame j K.
+//   n == 1: one pass that writes the whole table, then the back-trace -- ctc_viterbi's steps.
+//   n > 1:  a pass without back-pointers that copies the column of every frame j K into a checkpoint and ends with the score
+//           and the end state; then, from the last segment to the first: the checkpoint restored, the segment's frames once
+//           more into a table of K rows, and that segment back-traced from the state the segment above handed down.
+constexpr int32_t ALIGN_LONG_MAX_LABELS = 1048575;  // S = 2 L + 1 < 2^21: every index formed from S stays far inside int32
+constexpr int32_t ALIGN_LONG_THREADS = 1024;
+
+// One utterance of a ctc_viterbi_long launch, validated by the host as an AlignUtt is. col, ckpt and bp are the utterance's
+// own: no other workgroup reads or writes them.
+struct AlignLongUtt {
+  const void* x;       // [T, V] logits or probabilities, of the launch's dtype
+  const double* lse;   // [T] log-sum-exp of each row (not read when is_prob)
+  const int32_t* lab;  // [L] target labels
+  double* col;         // [2 * 4 * align_chunks(L)] the two score columns
+  double* ckpt;        // [n * 4 * align_chunks(L)] (n > 1) the column each segment starts from
+  uint8_t* bp;         // [min(K, T - 1) * align_chunks(L)] one segment's back-pointers, four 2-bit entries per byte
+  int32_t* path;       // [T] out
+  int32_t* tok_start;  // [L] out
+  int32_t* tok_end;    // [L] out
+  double* tok_logp;    // [L] out (fold != 0)
+  double* score;       // [1] out: the last column's value at the end state
+  int32_t T, L, is_prob, K;  // 1 <= K <= T: the frames of a segment
+};
+
+CTC_HD int32_t align_long_segments(int32_t T, int32_t K) { return T > 1 ? (T - 2) / K + 1 : 0; }  // ceil((T - 1) / K)
+CTC_HD int32_t align_long_segment_end(int32_t T, int32_t K, int32_t f) { return T - 1 - f > K ? f + K : T - 1; }
+
+// The frames f + 1 .. e of the recursion, the column of frame f in place (an even frame's in the first column) and the other
+// column -inf above frame f's window. BP: frame t's back-pointers go to row t - f - 1 of bp. The loop and the four-state
+// update are ctc_viterbi_utt's, a second copy: that body indexes LDS and one table of T rows, this one device memory and a
+// table that starts anew with every segment, and shared code would have to leave ctc_viterbi's instructions as they are.
+// The window's bounds are formed without 2 * t or 2 * (T - 1 - t), which leave int32 above 2^30 frames: the same values.
+template <bool BP, class Ctx>
+CTC_HD void viterbi_long_frames(Ctx& cx, const AlignLongUtt& u, int V, int dtype, int blank, double clip_lo, int f, int e, uint8_t* bp) {
+  const int T = u.T, L = u.L;
+  const int S = 2 * L + 1, nch = align_chunks(L);
+  const double NEG = align_neg_inf();
+  const bool is_prob = u.is_prob != 0;
+  double* c0 = u.col;
+  double* c1 = u.col + 4 * nch;
+  // first state of frame f's window, rounded down to its group (before frame 1: 0, as ctc_viterbi_utt starts)
+  int prev_lo4 = f > 0 && T - 1 - f < L ? 4 * ((2 * (L - (T - 1 - f)) - 1) >> 2) : 0;
+  for (int t = f + 1; t <= e; ++t) {
+    const double* prev = (t & 1) ? c0 : c1;
+    double* cur = (t & 1) ? c1 : c0;
+    const int rest = T - 1 - t;  // lo = S - 2 - 2 * rest, hi = 2 * t + 1
+    const int clo = rest < L ? (2 * (L - rest) - 1) >> 2 : 0, chi = (t < L ? 2 * t + 1 : S - 1) >> 2;
+    const double lse_t = is_prob ? 0.0 : u.lse[t];
+    const size_t row = (size_t)t * (size_t)V;
+    const double e_blank = align_emit(u.x, dtype, row + (size_t)blank, lse_t, is_prob, clip_lo);
+    for (int c = clo + cx.tid; c <= chi; c += cx.nt) {
+      const int s0 = 4 * c, k0 = 2 * c, k1 = 2 * c + 1;
+      const int l0 = k0 < L ? u.lab[k0] : -1, l1 = k1 < L ? u.lab[k1] : -1;
+      const int lm1 = k0 > 0 && k0 <= L ? u.lab[k0 - 1] : -1;
+      const double pm1 = s0 - 1 >= prev_lo4 ? prev[s0 - 1] : NEG;
+      const double p0 = prev[s0], p1 = prev[s0 + 1], p2 = prev[s0 + 2], p3 = prev[s0 + 3];
+      // blank s0: stay / step
+      double b0 = p0;
+      unsigned q4 = 0;
+      if (pm1 > b0) b0 = pm1, q4 = 1u;
+      cur[s0] = b0 + e_blank;
+      // label k0: stay / step / skip over the blank when the label before differs
+      double b1 = NEG, b2 = NEG, b3 = NEG;
+      if (l0 >= 0) {
+        unsigned q = 0;
+        b1 = p1;
+        if (p0 > b1) b1 = p0, q = 1u;
+        if (lm1 >= 0 && lm1 != l0 && pm1 > b1) b1 = pm1, q = 2u;
+        q4 |= q << 2;
+        b1 += align_emit(u.x, dtype, row + (size_t)l0, lse_t, is_prob, clip_lo);
+      }
+      if (s0 + 2 < S) {
+        unsigned q = 0;
+        b2 = p2;
+        if (p1 > b2) b2 = p1, q = 1u;
+        q4 |= q << 4;
+        b2 += e_blank;
+      }
+      if (l1 >= 0) {
+        unsigned q = 0;
+        b3 = p3;
+        if (p2 > b3) b3 = p2, q = 1u;
+        if (l1 != l0 && p1 > b3) b3 = p1, q = 2u;
+        q4 |= q << 6;
+        b3 += align_emit(u.x, dtype, row + (size_t)l1, lse_t, is_prob, clip_lo);
+      }
+      cur[s0 + 1] = b1;
+      cur[s0 + 2] = b2;
+      cur[s0 + 3] = b3;
+      if (BP) bp[(size_t)(t - f - 1) * (size_t)nch + (size_t)c] = (uint8_t)q4;
+    }
+    prev_lo4 = 4 * clo;
+    cx.sync();  // the one barrier of a frame: the columns swap roles
+  }
+}
+
+// cx: tid, nt, sync(). A thread loops over its groups of four states as in ctc_viterbi_utt; a workgroup reads from device
+// memory only what it wrote itself, behind a barrier.
+template <class Ctx>
+CTC_HD void ctc_viterbi_long_utt(Ctx& cx, const AlignLongUtt& u, int V, int dtype, int blank, int fold, double clip_lo) {
+  const int T = u.T, L = u.L, K = u.K;
+  if (T <= 0) return;
+  const int S = 2 * L + 1, nch = align_chunks(L), nseg = align_long_segments(T, K);
+  const double NEG = align_neg_inf();
+  const bool is_prob = u.is_prob != 0;
+  double* c0 = u.col;
+  double* c1 = u.col + 4 * nch;
+  for (int i = cx.tid; i < 8 * nch; i += cx.nt) u.col[i] = NEG;
+  cx.sync();
+  if (cx.tid == 0) {
+    const double lse0 = is_prob ? 0.0 : u.lse[0];
+    c0[0] = align_emit(u.x, dtype, (size_t)blank, lse0, is_prob, clip_lo);
+    if (L > 0) c0[1] = align_emit(u.x, dtype, (size_t)u.lab[0], lse0, is_prob, clip_lo);
+  }
+  cx.sync();
+  // the pass over all frames. What lies above a frame's window in either column still holds the -inf written above: a
+  // checkpoint is the whole column, those cells included.
+  for (int j = 0; j < nseg; ++j) {
+    const int f = j * K, e = align_long_segment_end(T, K, f);
+    if (nseg == 1) {
+      viterbi_long_frames<true>(cx, u, V, dtype, blank, clip_lo, f, e, u.bp);
+    } else {
+      const double* at = (f & 1) ? c1 : c0;  // (complete behind frame f's barrier; next written by frame f + 2, behind frame f + 1's)
+      double* keep = u.ckpt + (size_t)j * (size_t)(4 * nch);
+      for (int i = cx.tid; i < 4 * nch; i += cx.nt) keep[i] = at[i];
+      viterbi_long_frames<false>(cx, u, V, dtype, blank, clip_lo, f, e, nullptr);
+    }
+  }
+  // the end state and the score, by the thread that traces back: the last label is preferred over the trailing blank, and
+  // the score is the last column's value -- nothing is summed a second time
+  int s = 0, open = -1;
+  if (cx.tid == 0) {
+    const double* fin = ((T - 1) & 1) ? c1 : c0;
+    s = (L > 0 && fin[S - 2] >= fin[S - 1]) ? S - 2 : S - 1;
+    *u.score = fin[s];
+  }
+  const auto slot = [&](int) { return blank; };
+  if (nseg == 1) {
+    if (cx.tid == 0) viterbi_backtrace_span(s, open, T - 1, 1, 1, nch, u.bp, u.lab, u.path, u.tok_start, u.tok_end, slot);
+  } else {
+    for (int j = nseg - 1; j >= 0; --j) {
+      const int f = j * K, e = align_long_segment_end(T, K, f);
+      double* at = (f & 1) ? c1 : c0;
+      double* other = (f & 1) ? c0 : c1;
+      const double* keep = u.ckpt + (size_t)j * (size_t)(4 * nch);
+      cx.sync();  // (thread 0 has read the last column)
+      // The other column would hold what a later frame left there, above frame f's window too, where frame f + 2 expects
+      // -inf: all of it is reset. Below the window nothing is read, inside it frame f + 1 writes first.
+      for (int i = cx.tid; i < 4 * nch; i += cx.nt) at[i] = keep[i], other[i] = NEG;
+      cx.sync();  // (and thread 0 is through with the table of the segment above)
+      viterbi_long_frames<true>(cx, u, V, dtype, blank, clip_lo, f, e, u.bp);
+      // s and open go on into the segment below: a label's span may cross the boundary
+      if (cx.tid == 0) viterbi_backtrace_span(s, open, e, f + 1, f + 1, nch, u.bp, u.lab, u.path, u.tok_start, u.tok_end, slot);
+    }
+  }
+  if (cx.tid == 0) viterbi_backtrace_span(s, open, 0, 0, 0, nch, u.bp, u.lab, u.path, u.tok_start, u.tok_end, slot);  // frame 0: no step
   if (!fold) return;
   cx.sync();  // (the spans thread 0 wrote are read by every thread)
   fold_token_logp(cx, u.x, dtype, u.lse, u.lab, u.tok_start, u.tok_end, u.tok_logp, T, L, V, is_prob, fold, clip_lo);

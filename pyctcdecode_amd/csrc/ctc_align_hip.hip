@@ -1,6 +1,7 @@
 // ctc_align_hip.hip -- the transcript kernels on gfx950, bodies in ctc_align.h. A translation unit of its own.
 //   row_lse, row_lse_max            G lanes per row; both fold with row_fold
 //   ctc_viterbi                     a workgroup per utterance, score columns in LDS
+//   ctc_viterbi_long                a workgroup of 1024 threads per utterance, score columns and checkpoints in device memory
 //   ctc_forward, ctc_posteriors,    a workgroup per record, a group of four states per thread in registers
 //   ctc_find, ctc_viterbi_gaps        (256 threads up to 511 labels, 1024 above)
 //   ctc_forward_wave, ctc_find_wave a wavefront per record of at most 127 labels
@@ -136,6 +137,15 @@ __global__ __launch_bounds__(ALIGN_THREADS) void ctc_viterbi(ViterbiArgs a) {
   extern __shared__ double align_cols[];
   AlignGpuCtx cx{(int)threadIdx.x, ALIGN_THREADS};
   ctc_viterbi_utt(cx, a.utts[blockIdx.x], a.n_labels, a.dtype, a.blank, a.fold, a.clip_lo, align_cols);
+}
+
+// ---------------------------------------------------------------------------------------------
+// ctc_viterbi_long: 1024 threads per utterance -- sixteen waves on a compute unit, four per SIMD, so at most 128 VGPRs --, both
+// score columns and the checkpoints in device memory, one barrier per frame. No workgroup waits for another (ctc_align.h)
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(ALIGN_LONG_THREADS) void ctc_viterbi_long(ViterbiLongArgs a) {
+  AlignGpuCtx cx{(int)threadIdx.x, ALIGN_LONG_THREADS};
+  ctc_viterbi_long_utt(cx, a.utts[blockIdx.x], a.n_labels, a.dtype, a.blank, a.fold, a.clip_lo);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -747,6 +757,15 @@ int launch_ctc_viterbi_on(const ViterbiArgs& a, hipStream_t stream, std::string*
   const size_t lds = (size_t)2 * 4 * (size_t)a.max_chunks * sizeof(double);  // <= 64 KB
   return timed_launch(K_VITERBI, stream, err, [&] {
     hipLaunchKernelGGL(ctc_viterbi, dim3((unsigned)a.n_utts), dim3(ALIGN_THREADS), lds, stream, a);
+  });
+}
+
+int launch_ctc_viterbi_long_on(const ViterbiLongArgs& a, hipStream_t stream, std::string* err) {
+  if (a.n_utts <= 0) return 0;
+  if (a.dtype < 0 || a.dtype > 3 || !a.utts || a.n_labels < 1 || a.blank < 0 || a.blank >= a.n_labels)
+    return bad_launch(err, "ctc_viterbi_long: bad arguments");
+  return timed_launch(K_VITERBI_LONG, stream, err, [&] {
+    hipLaunchKernelGGL(ctc_viterbi_long, dim3((unsigned)a.n_utts), dim3(ALIGN_LONG_THREADS), 0, stream, a);
   });
 }
 

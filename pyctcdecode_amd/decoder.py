@@ -144,6 +144,7 @@ class ConfidenceOutputBeam(TokenOutputBeam):
     word_logp: List[float]
 
 ALIGN_MAX_LABELS = 2047  # ALIGN_MAX_LABELS of csrc/ctc_align.h: 2 L + 1 states, two fp64 score columns in a workgroup's LDS
+ALIGN_LONG_MAX_LABELS = 1048575  # ALIGN_LONG_MAX_LABELS of csrc/ctc_align.h: 2 L + 1 states below 2^21 (align_long)
 ALIGN_BP_BUDGET = 1 << 30  # bytes of back-pointer tables one ctc_viterbi launch holds by default ("Forced alignment")
 
 
@@ -1486,6 +1487,11 @@ class BeamSearchDecoderCTC:
         # call; kernel launches made)
         self.last_align_gaps_timing_ms = (0.0, 0.0, 0.0, 0.0)
         self.last_align_gaps_launches = 0
+        # ... and of the last align_long / align_long_batch call (ms: classification, row_lse, ctc_viterbi_long, native call;
+        # kernel launches made; (segment_frames, n_segments) of every utterance that was aligned)
+        self.last_align_long_timing_ms = (0.0, 0.0, 0.0, 0.0)
+        self.last_align_long_launches = 0
+        self.last_align_long_plan: List[Tuple[int, int]] = []
         # ... and of the last decode_greedy / decode_greedy_batch call (ms: classification, row_argmax or row_lse_argmax,
         # greedy_collapse, native call; kernel launches made; the part of the row kernel's time that a kernel with a
         # log-sum-exp took: 0 without confidence=...)
@@ -1962,9 +1968,9 @@ class BeamSearchDecoderCTC:
         close()
         return " ".join(w for w, _, _ in words), kept, words
 
-    def _one_target_each(self, what: str, logits_list: Any, texts, tokens):
+    def _one_target_each(self, what: str, logits_list: Any, texts, tokens, max_labels: int = ALIGN_MAX_LABELS):
         """-> (logits_list, targets): the checks align_batch and posteriors_batch make of their arguments before anything is
-        staged -- one target per utterance, as a text (character alphabets) or as label ids."""
+        staged -- one target per utterance, as a text (character alphabets) or as label ids, of at most ``max_labels``."""
         if (texts is None) == (tokens is None):
             raise ValueError("%s: give exactly one of texts and tokens" % what)
         if texts is not None and self._is_bpe:
@@ -1989,9 +1995,9 @@ class BeamSearchDecoderCTC:
                         raise ValueError("%s: tokens[%d] holds %r: not a label id in [0, %d) other than the blank (%d)"
                                          % (what, u, c, n_labels, blank))
                     ids.append(int(c))
-            if len(ids) > ALIGN_MAX_LABELS:
+            if len(ids) > max_labels:
                 raise ValueError("%s: utterance %d has %d target labels, above the limit of %d labels per utterance"
-                                 % (what, u, len(ids), ALIGN_MAX_LABELS))
+                                 % (what, u, len(ids), max_labels))
             targets.append(ids)
         return logits_list, targets
 
@@ -2078,25 +2084,42 @@ class BeamSearchDecoderCTC:
         ValueError that lists them, ``strict=False`` returns None in their place."""
         fold = _confidence_fold(confidence)
         logits_list, targets = self._one_target_each("align", logits_list, texts, tokens)
+        out, stats = self._aligned_texts("align", logits_list, targets, fold, strict, int(_bp_budget), None)
+        if stats is not None:
+            # [classification (frame-prune kernels), row_lse, ctc_viterbi (HIP events), whole native call]; launches made
+            self.last_align_timing_ms, self.last_align_launches, _plan = stats
+        return out
+
+    def _aligned_texts(self, what: str, logits_list: Any, targets: List[List[int]], fold: int, strict: bool, bp_budget: int,
+                       segment_frames: Optional[int]):
+        """-> (the AlignedText of every utterance, None for one without a path; (timing ms, launches, plan) of the native call,
+        None when none was made): the checked targets through ctcdec_align_batch (``segment_frames`` None) or
+        ctcdec_align_long_batch, and the words formed from the result."""
         n = len(targets)
         if n == 0:
-            return []
+            return [], None
+        budget = bp_budget or ALIGN_BP_BUDGET
         with self._call_lock:
             batch, frames, ptrs, _ = self._stage_transcript_call(logits_list)
-            keep = self._feasible("align", frames, targets, self._bp_table_bytes, int(_bp_budget) or ALIGN_BP_BUDGET, strict,
-                                  "back-pointer table", "path")
+            if segment_frames is None:
+                keep = self._feasible(what, frames, targets, self._bp_table_bytes, budget, strict, "back-pointer table", "path")
+            else:
+                keep = self._feasible(what, frames, targets, lambda T, L: self._align_long_plan(T, L, budget, segment_frames)[2],
+                                      budget, strict, "plan (segment table, checkpoints, columns)", "path")
             out: List[Optional[AlignedText]] = [None] * n
             if not keep:
-                return out
+                return out, None
             k_ptrs = np.ascontiguousarray(ptrs[keep])
             k_frames = np.ascontiguousarray(frames[keep])
             flat, off = self._pack_ids([targets[u] for u in keep])
             res = C.c_void_p()
             lib = self._lib
-            lib.check(lib.dll.ctcdec_align_batch(
-                self._handle, *self._c_utts(k_ptrs, k_frames),
-                len(keep), batch.dtype, int(batch.is_device), flat.ctypes.data_as(C.POINTER(C.c_int32)), B.off_ptr(off), fold,
-                int(_bp_budget), C.byref(res)))
+            head = (self._handle, *self._c_utts(k_ptrs, k_frames), len(keep), batch.dtype, int(batch.is_device),
+                    flat.ctypes.data_as(C.POINTER(C.c_int32)), B.off_ptr(off), fold, bp_budget)
+            if segment_frames is None:
+                lib.check(lib.dll.ctcdec_align_batch(*head, C.byref(res)))
+            else:
+                lib.check(lib.dll.ctcdec_align_long_batch(*head, segment_frames, C.byref(res)))
             try:
                 po, pp, ps, nu = C.POINTER(C.c_int64)(), C.POINTER(C.c_int32)(), C.POINTER(C.c_double)(), C.c_int64()
                 lib.check(lib.dll.ctcdec_alignment_paths(res, C.byref(po), C.byref(pp), C.byref(ps), C.byref(nu)))
@@ -2116,9 +2139,10 @@ class BeamSearchDecoderCTC:
                 logp = np.ctypeslib.as_array(tp, shape=(ntok,)).tolist() if ntok and fold else []
                 ms, launches = (C.c_double * 4)(), C.c_int32()
                 lib.dll.ctcdec_alignment_timing(res, ms, C.byref(launches))
-                # [classification (frame-prune kernels), row_lse, ctc_viterbi (HIP events), whole native call]; launches made
-                self.last_align_timing_ms = tuple(float(v) for v in ms)
-                self.last_align_launches = int(launches.value)
+                sf, ns, npl = C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)(), C.c_int64()
+                lib.check(lib.dll.ctcdec_alignment_plan(res, C.byref(sf), C.byref(ns), C.byref(npl)))
+                plan = [(int(sf[j]), int(ns[j])) for j in range(int(npl.value))]
+                stats = (tuple(float(v) for v in ms), int(launches.value), plan)
                 path_off = path_off.tolist()
             finally:
                 lib.dll.ctcdec_alignment_free(res)
@@ -2133,7 +2157,61 @@ class BeamSearchDecoderCTC:
                     tlp = [logp[o + k] for k in kept]
                     wlp = [min(tlp[lo:hi]) for _w, lo, hi in words]
                 out[u] = AlignedText(text, path[path_off[j]:path_off[j + 1]].copy(), float(score[j]), tok, wf, tlp, wlp)
-            return out
+            return out, stats
+
+    # -- forced alignment of long transcripts (no reference analogue; DESIGN.md, "Forced alignment of long transcripts") ------
+    @staticmethod
+    def _align_long_plan(frames: int, n_labels: int, budget: int, segment_frames: int) -> Tuple[int, int, int]:
+        """-> (K, n, bytes): how ctcdec_align_long_batch cuts an utterance (long_plan, csrc/api_transcript.cpp, the same rule):
+        segments of K frames, n = ceil((frames - 1) / K) of them, and the bytes of one segment's back-pointers, a checkpoint
+        per segment when there is more than one, and the two score columns."""
+        nch = (2 * n_labels + 1 + 3) // 4
+
+        def of(K):
+            n = (frames - 2) // K + 1 if frames > 1 else 0
+            return K, n, K * nch + (32 * nch * n if n > 1 else 0) + 64 * nch
+
+        if frames <= 0:
+            return 0, 0, 0
+        if segment_frames > 0:
+            return of(min(segment_frames, frames))
+        whole = of(frames)
+        if whole[2] <= budget:
+            return whole
+        K = math.isqrt(32 * frames)
+        return of(min(K if K * K == 32 * frames else K + 1, frames))
+
+    def align_long(self, logits: Any, text: Optional[str] = None, tokens: Optional[Sequence[int]] = None,
+                   confidence: Optional[str] = None) -> "AlignedText":
+        """Forced alignment of one long utterance: align_long_batch of a batch of one (a ValueError when no path exists)."""
+        if isinstance(logits, (_ResidentBeams, _DeviceStreams)):
+            raise NotImplementedError("align_long reads an utterance's matrix; the frames a stream has consumed are not kept")
+        self._check_logits_dimension(logits)
+        return self.align_long_batch([logits], None if text is None else [text], tokens=None if tokens is None else [tokens],
+                                     confidence=confidence)[0]
+
+    def align_long_batch(self, logits_list: Any, texts: Optional[Sequence[str]] = None,
+                         tokens: Optional[Sequence[Sequence[int]]] = None, confidence: Optional[str] = None, strict: bool = True,
+                         _bp_budget: int = 0, _segment_frames: int = 0) -> List[Optional["AlignedText"]]:
+        """align_batch for a lecture against its script: up to 1048575 target labels per utterance instead of 2047, and no
+        back-pointer table of all frames (row_lse + ctc_viterbi_long, csrc/ctc_align_hip.hip). Arguments, targets, the
+        probabilities-or-logits rule and ``strict`` are align_batch's, and for every input align_batch accepts the result is
+        align_batch's, bit for bit. An utterance whose whole table fits the memory budget of a launch takes one pass; a longer
+        one is cut into segments of about sqrt(32 T) frames and takes two: one that keeps the score column every segment
+        starts from, one that fills and traces back one segment's table at a time, last segment first. The score columns
+        live in device memory, so align_batch stays the faster call for targets it accepts. ``last_align_long_plan`` holds
+        (segment_frames, n_segments) of every utterance aligned."""
+        if isinstance(logits_list, (_ResidentBeams, _DeviceStreams)) or (
+                isinstance(logits_list, (list, tuple)) and any(isinstance(x, (_ResidentBeams, _DeviceStreams)) for x in logits_list)):
+            raise NotImplementedError("align_long_batch reads utterances' matrices; the frames a stream has consumed are not kept")
+        fold = _confidence_fold(confidence)
+        if isinstance(_segment_frames, bool) or not isinstance(_segment_frames, (int, np.integer)) or not 0 <= int(_segment_frames) < 2 ** 31:
+            raise ValueError("align_long: _segment_frames must be an int >= 0 (0: the library plans), not %r" % (_segment_frames,))
+        logits_list, targets = self._one_target_each("align_long", logits_list, texts, tokens, ALIGN_LONG_MAX_LABELS)
+        out, stats = self._aligned_texts("align_long", logits_list, targets, fold, strict, int(_bp_budget), int(_segment_frames))
+        if stats is not None:
+            self.last_align_long_timing_ms, self.last_align_long_launches, self.last_align_long_plan = stats
+        return out
 
     # -- alignment with gaps (no reference analogue; DESIGN.md, "Alignment with gaps") --------------------
     def _gapped_targets(self, what: str, logits_list: Any, texts, tokens, gap: str):

@@ -221,6 +221,11 @@ def align_gaps_batch_sharded(decoder, logits_list, texts=None, group=None, **kwa
     raise NotImplementedError("align_gaps_batch is not gathered over ranks: align each rank's slice with decoder.align_gaps_batch itself")
 
 
+def align_long_batch_sharded(decoder, logits_list, texts=None, group=None, **kwargs):
+    """Forced alignment of long transcripts is not sharded over ranks: each rank calls decoder.align_long_batch on its own slice."""
+    raise NotImplementedError("align_long_batch is not gathered over ranks: align each rank's slice with decoder.align_long_batch itself")
+
+
 def decode_greedy_batch_sharded(decoder, logits_list, group=None, **kwargs):
     """Greedy decoding is not sharded over ranks: each rank calls decoder.decode_greedy_batch on its own slice."""
     raise NotImplementedError("decode_greedy_batch is not gathered over ranks: decode each rank's slice with decoder.decode_greedy_batch itself")
@@ -388,6 +393,12 @@ class DevicePool:
         raise NotImplementedError("DevicePool does not shard align_gaps_batch: call decoder.align_gaps_batch on the process's own device")
 
     align_gaps = align_gaps_batch
+
+    def align_long_batch(self, logits_list, texts=None, **kwargs):
+        """Forced alignment of long transcripts runs on the calling process's own device: a pool does not shard it."""
+        raise NotImplementedError("DevicePool does not shard align_long_batch: call decoder.align_long_batch on the process's own device")
+
+    align_long = align_long_batch
 
     def decode_greedy_batch(self, logits_list, **kwargs):
         """Greedy decoding runs on the calling process's own device: a pool does not shard it."""
