@@ -131,7 +131,10 @@ __global__ __launch_bounds__(256) void utt_sniff_exact(PruneArgs a) {
 }
 
 // per-wave LDS work area of the prune kernels
-constexpr int NP_LEAVES = 64;  // leaves (<= 128 elements each) of numpy's pairwise sum a wave handles: rows up to ~3600 labels
+// leaves (<= 128 elements each) of numpy's pairwise sum a wave lists at a time: those of one 8192-element piece of a row
+// (np_sum.h: at most NP_PIECE_LEAVES = 65), rounded up so that the work area stays a multiple of 16 bytes
+constexpr int NP_LEAVES = 66;
+static_assert(NP_LEAVES >= NP_PIECE_LEAVES, "a wave lists the leaves of a whole piece");
 struct PruneLds {
   double* asc_lp;
   uint16_t *asc_id, *order, *tabA, *tabR, *scratch;
@@ -379,7 +382,9 @@ __device__ __forceinline__ double to_logp_np32(float xv, bool is_prob, float mf,
 // numpy's, and with them the order inside runs of equal scores (tests/test_order_stability.py). Leaves of the recursion
 // (<= 128 elements: eight strided accumulators, then the leftovers) go to groups of eight lanes, eight leaves at a time;
 // lane 0 lists them first and combines their sums last, both by walking the recursion with a small stack in LDS.
-// Returns false for rows of more than NP_LEAVES leaves (the caller then sums in lane order: same value to ~1 ulp).
+// numpy runs that recursion on pieces of NP_PIECE = 8192 elements and adds the pieces' sums to the result one after the other
+// (np_sum.h), so does the loop here: a piece has at most NP_PIECE_LEAVES <= NP_LEAVES leaves and a recursion depth of 7, which
+// is all the work area has to hold for any row up to CTCDEC_MAX_VOCAB = 65535 labels.
 // T = double: the terms are exp(x - m) in fp64; T = float: numpy's float32 exp of the float32 difference, float32 additions
 // (the leaf sums travel through the fp64 LDS words unchanged: every float32 is a double).
 template <typename T>
@@ -388,28 +393,29 @@ template <>
 __device__ __forceinline__ double np_term<double>(const double* x, int i, double m) { return exp(x[i] - m); }
 template <>
 __device__ __forceinline__ float np_term<float>(const float* x, int i, float m) { return np_exp_f32(x[i] - m); }
+// one piece: elements [p0, p0 + pn) of the row, pn <= NP_PIECE (p0 + pn <= 65535: label ids, and so the offsets, are 16 bits wide)
 template <typename T>
-__device__ __forceinline__ bool np_order_exp_sum(const T* x, int V, T m, int lane, const PruneLds& w, T* out) {
+__device__ __forceinline__ T np_order_exp_sum_piece(const T* x, int p0, int pn, T m, int lane, const PruneLds& w) {
   uint16_t* leaf_off = w.np_tab;
   uint16_t* leaf_len = w.np_tab + NP_LEAVES;
   uint16_t* stk_n = w.np_tab + 2 * NP_LEAVES;
   uint16_t* stk_s = stk_n + 16;
   uint16_t* n_leaf = stk_s + 16;
-  if (lane == 0) {  // the leaves, left to right
+  if (lane == 0) {  // the piece's leaves, left to right
     int sp = 0, k = 0;
-    stk_s[0] = 0;
-    stk_n[0] = (uint16_t)V;  // (V <= 65535: label ids are 16 bits wide)
+    stk_s[0] = (uint16_t)p0;
+    stk_n[0] = (uint16_t)pn;
     sp = 1;
-    while (sp > 0 && k <= NP_LEAVES) {
+    while (sp > 0) {
       --sp;
       const int off = stk_s[sp], n = stk_n[sp];
       if (n <= 128) {
-        if (k < NP_LEAVES) {
+        if (k < NP_LEAVES) {  // (always: a piece has at most NP_PIECE_LEAVES of them)
           leaf_off[k] = (uint16_t)off;
           leaf_len[k] = (uint16_t)n;
+          ++k;
         }
-        ++k;
-      } else if (sp + 2 <= 16) {
+      } else if (sp + 2 <= 16) {  // (always: the halves of 8192 reach 128 at depth 6, one pending right half per level)
         int n2 = n / 2;
         n2 -= n2 % 8;
         stk_s[sp] = (uint16_t)(off + n2);  // right half below the left one: the left is listed first
@@ -417,8 +423,6 @@ __device__ __forceinline__ bool np_order_exp_sum(const T* x, int V, T m, int lan
         stk_s[sp + 1] = (uint16_t)off;
         stk_n[sp + 1] = (uint16_t)n2;
         sp += 2;
-      } else {
-        k = NP_LEAVES + 1;
       }
     }
     *n_leaf = (uint16_t)k;
@@ -426,7 +430,6 @@ __device__ __forceinline__ bool np_order_exp_sum(const T* x, int V, T m, int lan
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
   __builtin_amdgcn_wave_barrier();
   const int nl = *n_leaf;
-  if (nl > NP_LEAVES) return false;
   const int g = lane >> 3, j = lane & 7;
   for (int base = 0; base < nl; base += 8) {
     const int k = base + g;
@@ -454,7 +457,7 @@ __device__ __forceinline__ bool np_order_exp_sum(const T* x, int V, T m, int lan
     double* acc = w.np_sum + NP_LEAVES;
     uint16_t* stk_st = stk_s;
     int sp = 1, k = 0;
-    stk_n[0] = (uint16_t)V;
+    stk_n[0] = (uint16_t)pn;
     stk_st[0] = 0;
     T ret = (T)0;
     while (sp > 0) {
@@ -486,16 +489,17 @@ __device__ __forceinline__ bool np_order_exp_sum(const T* x, int V, T m, int lan
   }
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
   __builtin_amdgcn_wave_barrier();
-  *out = (T)w.np_sum[0];
+  const T sum = (T)w.np_sum[0];
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  return true;
+  __builtin_amdgcn_wave_barrier();  // (the next piece, or the caller, writes the work area again)
+  return sum;
 }
 template <typename T>
-__device__ __forceinline__ bool np_order_exp_sum_t(const T*, int, double, int, const PruneLds&, double*) { return false; }
-template <>
-__device__ __forceinline__ bool np_order_exp_sum_t<double>(const double* x, int V, double m, int lane, const PruneLds& w, double* out) {
-  return np_order_exp_sum<double>(x, V, m, lane, w, out);
+__device__ __forceinline__ T np_order_exp_sum(const T* x, int V, T m, int lane, const PruneLds& w) {
+  T out = (T)0;  // (numpy's output element starts at 0, and 0 + s is s: a sum of exponentials is never -0)
+  for (int p0 = 0; p0 < V; p0 += (int)NP_PIECE)
+    out = out + np_order_exp_sum_piece<T>(x, p0, V - p0 < (int)NP_PIECE ? V - p0 : (int)NP_PIECE, m, lane, w);
+  return out;
 }
 
 // Generic frame-prune: one wave per frame row, any V / dtype; the row is swept three times (max and
@@ -511,9 +515,9 @@ __device__ __forceinline__ void prune_row_generic(const PruneArgs& a, int64_t ro
   if (is_prob && a.utt_is_prob[u] != 1u) return;
   const T* x = (const T*)a.utt_logits[u] + (size_t)(row - a.utt_row0[u]) * V;
   double mx = 0.0, lse = 0.0;
-  // float32 rows: the reference's own float32 arithmetic (to_logp_np32); rows of more leaves than a wave lists fall back to fp64
+  // float32 rows: the reference's own float32 arithmetic (to_logp_np32) unless CTCDEC_PRUNE_EXP asks for fp64
   constexpr bool F32 = std::is_same<T, float>::value;
-  bool np32 = F32 && a.f32_np && is_prob;
+  const bool np32 = F32 && a.f32_np;
   float mf = 0.f, l32 = 0.f;
   if (!is_prob) {
     double m = -INFINITY, rs = 0.0;
@@ -527,18 +531,16 @@ __device__ __forceinline__ void prune_row_generic(const PruneArgs& a, int64_t ro
     if (lane == 0) a.row_sum[row] = rs;
     if (!isfinite(m)) m = 0.0;  // decoder.py:186-189
     if constexpr (F32) {
-      if (a.f32_np) {
-        float s32 = 0.f;
+      if (np32) {
         mf = (float)m;  // (exact: the maximum of float32 values)
-        if (np_order_exp_sum<float>((const float*)x, V, mf, lane, w, &s32)) {
-          l32 = np_log_f32(s32);
-          np32 = true;
-        }
+        l32 = np_log_f32(np_order_exp_sum<float>((const float*)x, V, mf, lane, w));
       }
     }
     if (!np32) {
       double s = 0.0;
-      if (!np_order_exp_sum_t<T>(x, V, m, lane, w, &s)) {  // (float64 rows: numpy's own summation order)
+      if constexpr (std::is_same<T, double>::value) {  // float64 rows: numpy's own summation order
+        s = np_order_exp_sum<double>(x, V, m, lane, w);
+      } else {  // 16-bit rows, float32 rows in fp64 mode: the log-softmax of the exact upcast, summed in lane order
         for (int v = lane; v < V; v += 64) s += exp(ld(x, v) - m);
         s = wave_sum(s);
       }
@@ -724,9 +726,9 @@ __device__ __forceinline__ void prune_row_f32x4(const PruneArgs& a, int64_t row,
       // round 6: the reference's float32 arithmetic itself (numpy's float32 exp, its pairwise float32 sum, its float32 log:
       // np_f32.h, np_order_exp_sum<float>; the row is read a second time, from L1 / L2) -- a frame's log-probabilities are the
       // reference's bits. The polynomial variants below stay for CTCDEC_PRUNE_EXP=pk / f64.
-      float l32 = 0.f, s32 = 0.f;
-      const bool np32 = a.f32_np && np_order_exp_sum<float>((const float*)x4, V, mfw, lane, w, &s32);
-      if (np32) l32 = np_log_f32(s32);
+      float l32 = 0.f;
+      const bool np32 = a.f32_np != 0;
+      if (np32) l32 = np_log_f32(np_order_exp_sum<float>((const float*)x4, V, mfw, lane, w));
 #pragma unroll
       for (int k = 0; k < NC; ++k) {
         if (!np32 && k * 64 + lane < n4) {

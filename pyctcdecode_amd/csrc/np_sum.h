@@ -3,16 +3,23 @@
 // The reference decides "probabilities or logits?" with  math.isclose(logits.sum(axis=1).mean(), 1)  (decoder.py:760,
 // rel_tol 1e-9) ON THE INPUT DTYPE. For float32 / float16 inputs the neighbours of 1 are 6e-8 / 5e-4 away, so the test is in
 // effect "does the mean round to exactly 1" -- which depends on the order numpy adds in. That order is pinned here:
-//   * add.reduce over a contiguous axis = pairwise summation (numpy/_core/src/umath/loops_utils.h.src, @TYPE@_pairwise_sum):
+//   * add.reduce over a contiguous axis hands the inner loop PIECES of np.getbufsize() = 8192 elements (NP_PIECE), left to
+//     right; the inner loop adds the pairwise sum of its piece to the output element:  out = out + pairwise(piece), out
+//     starting at 0. Rows of up to 8192 elements are one piece. float16: the pairwise sum is accumulated in float32, added
+//     to the float16 output element widened to float32, and the result rounded back to float16 -- once per PIECE.
+//   * the pairwise sum of a piece (numpy/_core/src/umath/loops_utils.h.src, @TYPE@_pairwise_sum):
 //       n < 8      : plain loop starting from 0
 //       n <= 128   : eight accumulators r[j] over a[j], a[j+8], ...; ((r0+r1)+(r2+r3)) + ((r4+r5)+(r6+r7)); then the
 //                    n % 8 leftover elements one by one
 //       otherwise  : n2 = n/2 rounded down to a multiple of 8; pairwise(a, n2) + pairwise(a + n2, n - n2)
-//     float16 rows are accumulated in float32 by that routine and rounded to float16 once per row;
-//   * ndarray.mean (numpy/_core/_methods.py:_mean): the same reduction (float16: with a float32 accumulator), a true
-//     division by the count in the accumulator type, float16 results rounded back to float16.
-// Checked against numpy 2.2.6 on this container by tests/test_np_sum.py (random C-contiguous arrays, every dtype);
-// for other memory layouts numpy iterates differently and so may the last bit.
+//     A piece has at most NP_PIECE_LEAVES = 65 leaves (n = 7689 is the first length with 65; 8192 has 64).
+//   * ndarray.mean (numpy/_core/_methods.py:_mean): the same reduction (float16: with a float32 accumulator, i.e. the float32
+//     rule), a true division by the count in the accumulator type, float16 results rounded back to float16.
+// Established by experiment, numpy 2.2.6 (oracle/np_sum_pieces.py, profiles/np_sum_pieces.txt: x.sum(axis=1),
+// np.sum(x, axis=1, keepdims=True) and x[t].sum() for float32 / float64 / float16 rows on both sides of every multiple of 8192
+// up to 65535 elements: 0 rows differ from this rule, about half differ from one recursion over the whole row) and checked
+// by tests/test_np_sum.py (random C-contiguous arrays, every dtype); for other memory layouts numpy iterates differently and
+// so may the last bit.
 #pragma once
 #include <stdint.h>
 
@@ -46,15 +53,26 @@ CTC_HD Acc np_pairwise_leaf(Get get, int64_t a, int64_t n) {
   return res;
 }
 
-// the recursion, without recursion: an explicit stack of (offset, length, state, left sum)
+constexpr int64_t NP_PIECE = 8192;      // elements numpy's reduction hands its inner loop at a time (np.getbufsize())
+constexpr int NP_PIECE_LEAVES = 65;     // the most leaves the recursion over a piece has (tests/test_np_sum.py)
+
+// leaves of the pairwise recursion over n elements (host only: what the tests hold NP_PIECE_LEAVES against)
+inline int np_leaf_count(int64_t n) {
+  if (n <= 128) return 1;
+  int64_t n2 = n / 2;
+  n2 -= n2 % 8;
+  return np_leaf_count(n2) + np_leaf_count(n - n2);
+}
+
+// the recursion over one piece [base, base + n), without recursion: an explicit stack of (offset, length, state, left sum)
 template <class Acc, class Get>
-CTC_HD Acc np_pairwise(Get get, int64_t n) {
+CTC_HD Acc np_pairwise_piece(Get get, int64_t base, int64_t n) {
   constexpr int DEPTH = 28;  // lengths halve down to 128: 2^34 elements
   int64_t off[DEPTH], len[DEPTH];
   Acc left[DEPTH];
   int state[DEPTH];  // 0: nothing done, 1: left half done
   int sp = 0;
-  off[0] = 0;
+  off[0] = base;
   len[0] = n;
   state[0] = 0;
   left[0] = (Acc)0;
@@ -92,6 +110,20 @@ CTC_HD Acc np_pairwise(Get get, int64_t n) {
       --sp;
     }
   }
+}
+
+// the reduction of n contiguous elements: out = round(out + pairwise(piece)) over the pieces, left to right. `round` is what
+// storing the running result in the output element does to it (nothing, or the rounding to a 16-bit type)
+struct NpKeep {
+  template <class Acc>
+  CTC_HD Acc operator()(Acc v) const { return v; }
+};
+template <class Acc, class Get, class Round = NpKeep>
+CTC_HD Acc np_pairwise(Get get, int64_t n, Round round = Round()) {
+  Acc out = round(np_pairwise_piece<Acc>(get, 0, n < NP_PIECE ? n : NP_PIECE));
+  for (int64_t base = NP_PIECE; base < n; base += NP_PIECE)
+    out = round(out + np_pairwise_piece<Acc>(get, base, n - base < NP_PIECE ? n - base : NP_PIECE));
+  return out;
 }
 
 // float32 -> float16 / bfloat16 bits, round to nearest even (what numpy's npy_float_to_half does; bfloat16 is not a
@@ -168,12 +200,11 @@ CTC_HD double np_row_sum(const void* x, int dtype, int64_t t, int64_t V) {
     return (double)np_pairwise<float>([p](int64_t i) { return p[i]; }, V);
   }
   const uint16_t* p = (const uint16_t*)x + t * V;
-  if (dtype == 2) {
-    const float s = np_pairwise<float>([p](int64_t i) { return f16_bits_to_f32(p[i]); }, V);
-    return (double)f16_bits_to_f32(f32_to_f16_bits(s));
-  }
-  const float s = np_pairwise<float>([p](int64_t i) { return bf16_bits_to_f32(p[i]); }, V);
-  return (double)bf16_bits_to_f32(f32_to_bf16_bits(s));
+  if (dtype == 2)
+    return (double)np_pairwise<float>([p](int64_t i) { return f16_bits_to_f32(p[i]); }, V,
+                                      [](float s) { return f16_bits_to_f32(f32_to_f16_bits(s)); });
+  return (double)np_pairwise<float>([p](int64_t i) { return bf16_bits_to_f32(p[i]); }, V,
+                                    [](float s) { return bf16_bits_to_f32(f32_to_bf16_bits(s)); });
 }
 // row_sums.mean() of T such sums (held as doubles), as numpy computes it, widened to double; T > 0
 CTC_HD double np_mean_of_sums(const double* rs, int dtype, int64_t T) {

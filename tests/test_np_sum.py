@@ -20,6 +20,9 @@ extern "C" double np_mean_(const double* rs, int dtype, long T) { return ctc::np
 extern "C" int np_is_one_(double m) { return ctc::np_mean_is_one(m) ? 1 : 0; }
 extern "C" unsigned short to_half_(float f) { return ctc::f32_to_f16_bits(f); }
 extern "C" float from_half_(unsigned short h) { return ctc::f16_bits_to_f32(h); }
+extern "C" int np_leaf_count_(long n) { return ctc::np_leaf_count(n); }
+extern "C" long np_piece_() { return ctc::NP_PIECE; }
+extern "C" int np_piece_leaves_() { return ctc::NP_PIECE_LEAVES; }
 ''' % SRC
 
 
@@ -40,6 +43,8 @@ def lib():
     dll.to_half_.argtypes = [C.c_float]
     dll.from_half_.restype = C.c_float
     dll.from_half_.argtypes = [C.c_ushort]
+    dll.np_leaf_count_.argtypes = [C.c_long]
+    dll.np_piece_.restype = C.c_long
     return dll
 
 
@@ -62,6 +67,54 @@ def test_row_sums_and_their_mean_equal_numpy(lib, dtype, code):
             assert bool(lib.np_is_one_(mean)) == math.isclose(want.mean(), 1)
             n_prob += math.isclose(want.mean(), 1)
     assert n_prob > 10
+
+
+def _rows(rng, T, V, dtype):
+    """Half the rows signed values, half the terms of a log-softmax normaliser (exponentials of shifted logits)."""
+    x = rng.standard_normal((T, V)) * 2
+    x[::2] = np.exp(x[::2] - x[::2].max(axis=1, keepdims=True))
+    if dtype == np.float16:
+        x *= 0.05  # (the float16 sums stay finite)
+    return np.ascontiguousarray(x.astype(dtype))
+
+
+@pytest.mark.parametrize("dtype,code", [(np.float32, 0), (np.float64, 1), (np.float16, 2)])
+@pytest.mark.parametrize("V", [7688, 7689, 8191, 8192, 8193, 8200, 16384, 16385, 20000, 65535])
+def test_long_rows_are_summed_in_numpys_pieces(lib, dtype, code, V):
+    """Rows of more than np.getbufsize() = 8192 elements: numpy sums pieces of 8192 pairwise and adds the pieces' sums in
+    order (float16: rounding the running result to float16 after every piece), in every call form the reference uses.
+    One recursion over the whole row differs in the last bit for about half of such rows."""
+    assert np.getbufsize() == lib.np_piece_()
+    rng = np.random.default_rng(1000 * code + V)
+    T = 16  # (few: the per-row ctypes call is the cost; enough that a wrong order shows at every length above 8192)
+    x = _rows(rng, T, V, dtype)
+    want = x.sum(axis=1)
+    assert np.array_equal(want, np.sum(x, axis=1, keepdims=True)[:, 0])
+    assert np.array_equal(want, np.array([x[t].sum() for t in range(T)], dtype=dtype))
+    got = np.array([lib.np_row_sum_(x.ctypes.data, code, t, V) for t in range(T)])
+    assert np.array_equal(got, want.astype(np.float64)), (dtype, V, got - want)
+    mean = lib.np_mean_(got.ctypes.data, code, T)
+    assert mean == float(want.mean())
+
+
+@pytest.mark.parametrize("dtype,code", [(np.float32, 0), (np.float64, 1), (np.float16, 2)])
+@pytest.mark.parametrize("T", [8191, 8193, 20000])
+def test_mean_over_more_frames_than_a_piece(lib, dtype, code, T):
+    """logits.sum(axis=1).mean() of an utterance of more than 8192 frames: the mean's reduction over the T row sums runs in
+    the same pieces (float16: in a float32 accumulator)."""
+    rng = np.random.default_rng(50 * code + T)
+    x = _rows(rng, T, 3, dtype)
+    want = x.sum(axis=1)
+    got = np.array([lib.np_row_sum_(x.ctypes.data, code, t, 3) for t in range(T)])
+    assert np.array_equal(got, want.astype(np.float64))
+    assert lib.np_mean_(got.ctypes.data, code, T) == float(want.mean())
+
+
+def test_a_piece_has_at_most_np_piece_leaves(lib):
+    """The per-row HIP kernels list the leaves of one piece at a time in a table of NP_PIECE_LEAVES entries."""
+    counts = [lib.np_leaf_count_(n) for n in range(1, lib.np_piece_() + 1)]
+    assert max(counts) == lib.np_piece_leaves_() == 65
+    assert counts.index(65) + 1 == 7689 and counts[8192 - 1] == 64 and max(counts[:7688]) == 64
 
 
 def test_non_finite_means_are_never_one(lib):
