@@ -945,19 +945,26 @@ __device__ __forceinline__ float max3_raw(float a, float b, float c) {
   asm("v_max3_f32 %0, %1, %2, %3" : "=v"(o) : "v"(a), "v"(b), "v"(c));
   return o;
 }
-// (lanes a DPP step has no source for keep their value: the destination is the second operand; s_nop 1: the two wait
-// states a DPP read needs after the VALU write of its source -- the compiler cannot see into the asm)
-#define CTC_MAX_DPP(V, CTRL) asm volatile("s_nop 1\n\tv_max_f32_dpp %0, %0, %0 " CTRL : "+v"(V))
-__device__ __forceinline__ float wave_max_f32(float v) {
-  CTC_MAX_DPP(v, "row_shr:1 row_mask:0xf bank_mask:0xf");
-  CTC_MAX_DPP(v, "row_shr:2 row_mask:0xf bank_mask:0xf");
-  CTC_MAX_DPP(v, "row_shr:4 row_mask:0xf bank_mask:0xf");
-  CTC_MAX_DPP(v, "row_shr:8 row_mask:0xf bank_mask:0xf");
-  CTC_MAX_DPP(v, "row_bcast:15 row_mask:0xa bank_mask:0xf");
-  CTC_MAX_DPP(v, "row_bcast:31 row_mask:0xc bank_mask:0xf");
-  asm volatile("s_nop 1" ::: "memory");
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
+// The row maximum and the row sum across the wave: two DPP chains, step by step in ONE block. A DPP read needs two wait states
+// after the VALU write of its source, and the compiler cannot see into the asm: a chain on its own pays `s_nop 1` in front of
+// each of its six steps; here the other chain's step is one of the two states and `s_nop 0` the other -- 19 instructions for
+// the two reductions instead of 31. (Lanes a DPP step has no source for keep their value: the destination is the second
+// operand -- for the sum that is the compiler's own `v + dpp(0, v)`, whose lanes add +0: no partial sum here is -0, each
+// starts from +0. The block ends one wait state after its last write: what a v_readlane of the result needs.)
+#define CTC_MAX_SUM_DPP(CTRL) "v_max_f32_dpp %0, %0, %0 " CTRL "\n\tv_add_f32_dpp %1, %1, %1 " CTRL "\n\ts_nop 0\n\t"
+__device__ __forceinline__ void wave_max_sum_f32(float& mx, float& sm) {
+  asm volatile("s_nop 1\n\t"
+               CTC_MAX_SUM_DPP("row_shr:1 row_mask:0xf bank_mask:0xf")
+               CTC_MAX_SUM_DPP("row_shr:2 row_mask:0xf bank_mask:0xf")
+               CTC_MAX_SUM_DPP("row_shr:4 row_mask:0xf bank_mask:0xf")
+               CTC_MAX_SUM_DPP("row_shr:8 row_mask:0xf bank_mask:0xf")
+               CTC_MAX_SUM_DPP("row_bcast:15 row_mask:0xa bank_mask:0xf")
+               CTC_MAX_SUM_DPP("row_bcast:31 row_mask:0xc bank_mask:0xf")
+               : "+v"(mx), "+v"(sm));
+  mx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mx), 63));
+  sm = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sm), 63));
 }
+#undef CTC_MAX_SUM_DPP
 __device__ __forceinline__ float wave_sum_f32(float v) {
   v += dpp_f32<0x111, 0xf>(0.f, v);
   v += dpp_f32<0x112, 0xf>(0.f, v);
@@ -1119,7 +1126,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NC <= 4 ? PF
   const int64_t row_lo = a.row_base + (int64_t)blockIdx.x * PF_ROWS;
   const int64_t row_end = a.row_base + a.n_rows;
   if (row_lo >= row_end) return;
-  const int nrows = (int)(row_end - row_lo < (int64_t)PF_ROWS ? row_end - row_lo : (int64_t)PF_ROWS);
+  // (wave-uniform, and said so: the 64-bit comparison goes through the vector unit, and everything counted against nrows --
+  // the row loop, the rows' addresses -- would follow it there)
+  const int nrows = __builtin_amdgcn_readfirstlane((int)(row_end - row_lo < (int64_t)PF_ROWS ? row_end - row_lo : (int64_t)PF_ROWS));
   uint16_t* ar_id = (uint16_t*)smem;                       // [PF_CAND][64 rows]
   float* ar_x = (float*)(smem + PF_LDS_IDS);               // [PF_CAND][64 rows]
   uint16_t* tabs = (uint16_t*)(smem + PF_LDS_IDS + PF_LDS_X);  // [SMALL_SET_SLOTS][64 rows]
@@ -1134,6 +1143,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NC <= 4 ? PF
   typedef typename PfRaw<DT>::type Raw;
   const int V = a.n_labels;
   const int n4 = AL ? V / PER : (V + 3) / 4;     // loads (groups of four labels) per row
+  const bool full_row = AL && n4 == NL * 64;     // every lane's loads lie inside the row (wave-uniform)
   const float tminf = (float)a.token_min_logp;
   // label id of element e of group k in this lane; is group k inside the row?
   auto id_of = [&](int k, int e) { return WIDE ? (k * 64 + lane) * 4 + e : ((k >> 1) * 64 + lane) * 8 + (k & 1) * 4 + e; };
@@ -1150,17 +1160,26 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NC <= 4 ? PF
   typedef const Raw __attribute__((address_space(1))) * GlobalRaw;
   const ConstI64 row0_c = (ConstI64)a.utt_row0;
   const ConstPtrs logits_c = (ConstPtrs)a.utt_logits;
+  // The bookkeeping is relative to the block: rows [.., u_end) of its 64 belong to utterance u, and u_row is the address the
+  // block's row 0 would have inside that utterance -- a row's address is then one 32-bit multiply and a 64-bit add, and the
+  // test for the next utterance a 32-bit compare (absolute 64-bit row numbers cost ~30 scalar instructions a row: the
+  // 64-bit compares went through the vector unit, the product through three multiplies).
+  const uint32_t row_bytes = (uint32_t)V * (WIDE ? 4u : 2u);
+  auto rel_end = [&](int64_t r1) {
+    return __builtin_amdgcn_readfirstlane((int)(r1 - row_lo < (int64_t)PF_ROWS ? r1 - row_lo : (int64_t)PF_ROWS));
+  };
   int u = __builtin_amdgcn_readfirstlane(find_utt(a.utt_row0, a.n_utts, row_lo));
-  int64_t u_r0 = row0_c[u], u_r1 = row0_c[u + 1];
-  const char __attribute__((address_space(1))) * u_base = (const char __attribute__((address_space(1)))*)logits_c[u];
-  auto load_row = [&](int64_t row, Raw(&r)[NL]) {
-    while (row >= u_r1) {
+  int64_t u_r1 = row0_c[u + 1];
+  int u_end = rel_end(u_r1);
+  uint64_t u_row = (uint64_t)logits_c[u] + (uint64_t)(row_lo - row0_c[u]) * row_bytes;
+  auto load_row = [&](int i, Raw(&r)[NL]) __attribute__((always_inline)) {  // i: the row's index in the block, never smaller than in the call before
+    while (i >= u_end) {
       ++u;
-      u_r0 = u_r1;
+      u_row = (uint64_t)logits_c[u] + (uint64_t)(row_lo - u_r1) * row_bytes;  // (u_r1: still the row this utterance starts at)
       u_r1 = row0_c[u + 1];
-      u_base = (const char __attribute__((address_space(1)))*)logits_c[u];
+      u_end = rel_end(u_r1);
     }
-    const GlobalRaw x4 = (GlobalRaw)(u_base + (size_t)(row - u_r0) * V * (WIDE ? 4 : 2));
+    const GlobalRaw x4 = (GlobalRaw)(u_row + (uint64_t)((uint32_t)i * row_bytes));
     // Every load is UNCONDITIONAL (a lane past the row's end re-reads the row's first group; `widen` puts -inf there when the
     // row is worked on): a load behind a lane mask is a branch, and at the join the compiler can no longer count how many loads
     // are outstanding -- it waits for all of them, the prefetched rows included.
@@ -1181,7 +1200,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NC <= 4 ? PF
       }
     }
   };
-  auto widen = [&](const Raw(&raw)[NL], float4(&r)[NC]) {
+  // FULL (here and in phase_a): every lane's loads lie inside the row -- 1024 labels in four loads, the usual shape. Compiled
+  // apart from the rows that end inside a load, not tested per row: such a row has no lanes to mask, and where the two cases
+  // meet again the compiler no longer keeps a row in the registers its loads wrote (adjacent pairs, as the packed instructions
+  // want them) -- it paid sixteen selects and two dozen moves per row for a mask that is all ones.
+  auto widen = [&](auto full_c, const Raw(&raw)[NL], float4(&r)[NC]) __attribute__((always_inline)) {
+    constexpr bool FULL = decltype(full_c)::value;
     const float ninf = -INFINITY;
     if constexpr (WIDE) {
 #pragma unroll
@@ -1193,8 +1217,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NC <= 4 ? PF
           if (e0 + 1 >= V) r[k].y = ninf;
           if (e0 + 2 >= V) r[k].z = ninf;
           if (e0 + 3 >= V) r[k].w = ninf;
-        } else if (!in_row(k)) {
-          r[k] = make_float4(ninf, ninf, ninf, ninf);
         }
       }
     } else {
@@ -1204,11 +1226,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NC <= 4 ? PF
                                pf_widen<DT>(raw[k].y >> 16));
         r[2 * k + 1] = make_float4(pf_widen<DT>(raw[k].z & 0xFFFFu), pf_widen<DT>(raw[k].z >> 16), pf_widen<DT>(raw[k].w & 0xFFFFu),
                                    pf_widen<DT>(raw[k].w >> 16));
-        if (!in_row(2 * k)) {
-          r[2 * k] = make_float4(ninf, ninf, ninf, ninf);
-          r[2 * k + 1] = make_float4(ninf, ninf, ninf, ninf);
-        }
       }
+    }
+    if constexpr (AL && !FULL) {  // lanes past the end of the row
+#pragma unroll
+      for (int k = 0; k < NC; ++k)
+        if (!in_row(k)) r[k] = make_float4(ninf, ninf, ninf, ninf);
     }
   };
 
@@ -1228,7 +1251,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NC <= 4 ? PF
       np_len0 = a.np_leaf[2 * leaf + 1];
     }
   }
-  auto np_accumulate = [&](int i) {
+  auto np_accumulate = [&](int i) __attribute__((always_inline)) {
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     __builtin_amdgcn_wave_barrier();
     const int g = lane >> 3, j = lane & 7;
@@ -1268,27 +1291,47 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NC <= 4 ? PF
         if (len < 8) res = 0.f;
         for (int t = body; t < len; ++t) res = res + np_rb[np_pad(off + t)];
       }
-      if (a.np_uniform8) {
-        // up to eight leaves of 128, one per group of eight lanes (every lane of a group holds its leaf's sum; groups without a
-        // leaf hold 0): numpy's tree ((S0+S1)+(S2+S3)) + ((S4+S5)+(S6+S7)) by three cross-lane additions -- partners 8 lanes
-        // apart inside a row of sixteen, then rows 0 -> 1 and 2 -> 3, then row 1 -> row 3 (additions commute) -- and the row's
-        // sum lands in lane i's register: no leaf sums in LDS, which buys the block's two further waves per CU back
-        float t = res + dpp_f32<0x128, 0xf>(0.f, res);  // row_ror:8
-        t = t + dpp_f32<0x142, 0xa>(0.f, t);              // row_bcast:15 into rows 1 and 3
-        t = t + dpp_f32<0x143, 0xc>(0.f, t);              // row_bcast:31 into rows 2 and 3
-        const float total = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t), 63));
-        if (lane == i) my_s32 = total;
-      } else if (mine && j == 0) {
-        np_ls[leaf * PF_ROWS + i] = res;
-      }
+      if (mine && j == 0) np_ls[leaf * PF_ROWS + i] = res;
     }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     __builtin_amdgcn_wave_barrier();  // (the next row's exponentials go to the same buffer)
   };
+  // The same for rows of one, two, four or eight leaves of 128 (a.np_uniform8: 1024 labels among them) with nothing left to
+  // decide per row: one sweep, leaf g at element 128 g, sixteen terms per accumulator from an address that depends on the lane
+  // alone (computed once per block; the per-term part is the instruction's offset), the eight leaf sums combined in registers
+  // and the row's sum left in lane i. The additions and their order are np_accumulate's.
+  const float* np_q8 = np_rb + np_pad(np_off0) + (lane & 7);
+  auto np_accumulate8 = [&](int i) __attribute__((always_inline)) {
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    const float* q = np_q8;
+    float t0 = q[0], t1 = q[8], t2 = q[16], t3 = q[24], t4 = q[32], t5 = q[40], t6 = q[48], t7 = q[56];
+    float t8 = q[64], t9 = q[72], t10 = q[80], t11 = q[88], t12 = q[96], t13 = q[104], t14 = q[112], t15 = q[120];
+    float rr = t0 + t1;
+    rr = rr + t2; rr = rr + t3; rr = rr + t4; rr = rr + t5; rr = rr + t6; rr = rr + t7; rr = rr + t8;
+    rr = rr + t9; rr = rr + t10; rr = rr + t11; rr = rr + t12; rr = rr + t13; rr = rr + t14; rr = rr + t15;
+    float res = rr;
+    res = res + dpp_f32<0xB1, 0xf>(0.f, res);   // quad_perm [1, 0, 3, 2]
+    res = res + dpp_f32<0x4E, 0xf>(0.f, res);   // quad_perm [2, 3, 0, 1]
+    res = res + dpp_f32<0x141, 0xf>(0.f, res);  // row_half_mirror
+    if (a.np_n_leaf < 8) res = np_len0 != 0 ? res : 0.f;  // (groups of eight lanes without a leaf: what they read is not theirs)
+    // every lane of a group holds its leaf's sum: numpy's tree ((S0+S1)+(S2+S3)) + ((S4+S5)+(S6+S7)) by three cross-lane
+    // additions -- partners 8 lanes apart inside a row of sixteen, then rows 0 -> 1 and 2 -> 3, then row 1 -> row 3 (additions
+    // commute) -- and the row's sum lands in lane i's register: no leaf sums in LDS, which buys the block's two further waves
+    // per CU back
+    float t = res + dpp_f32<0x128, 0xf>(0.f, res);  // row_ror:8
+    t = t + dpp_f32<0x142, 0xa>(0.f, t);              // row_bcast:15 into rows 1 and 3
+    t = t + dpp_f32<0x143, 0xc>(0.f, t);              // row_bcast:31 into rows 2 and 3
+    const float total = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t), 63));
+    if (lane == i) my_s32 = total;
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();  // (the next row's exponentials go to the same buffer)
+  };
 
-  auto phase_a = [&](int i, const Raw(&raw)[NL]) -> uint32_t {
+  auto phase_a = [&](auto full_c, int i, const Raw(&raw)[NL]) __attribute__((always_inline)) -> uint32_t {
+    constexpr bool FULL = decltype(full_c)::value;
     float4 r[NC];
-    widen(raw, r);
+    widen(full_c, raw, r);
     float mf = -INFINITY, rsf;
 #pragma unroll
     for (int k = 0; k < NC; ++k) mf = max3_raw(max3_raw(mf, r[k].x, r[k].y), r[k].z, r[k].w);
@@ -1299,7 +1342,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NC <= 4 ? PF
         const int e0 = (k * 64 + lane) * 4;
         rsf += ((e0 < V ? r[k].x : 0.f) + (e0 + 1 < V ? r[k].y : 0.f)) + ((e0 + 2 < V ? r[k].z : 0.f) + (e0 + 3 < V ? r[k].w : 0.f));
       }
-    } else if (n4 == NL * 64) {  // (see prune_row_f32x4 on this sum)
+    } else if (FULL) {  // (see prune_row_f32x4 on this sum)
       f32x2 rs2 = (f32x2)(0.f);
 #pragma unroll
       for (int k = 0; k < NC; ++k) rs2 += (f32x2){r[k].x, r[k].y} + (f32x2){r[k].z, r[k].w};
@@ -1309,8 +1352,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NC <= 4 ? PF
 #pragma unroll
       for (int k = 0; k < NC; ++k) rsf += in_row(k) ? (r[k].x + r[k].y) + (r[k].z + r[k].w) : 0.f;
     }
-    const float m = wave_max_f32(mf);
-    const float rs = wave_sum_f32(rsf);
+    wave_max_sum_f32(mf, rsf);
+    const float m = mf, rs = rsf;
     uint32_t cnt = 0xFFFFu;  // "not a clean row": the per-row kernel takes it
     int first = 0;
     double s = 1.0;
@@ -1320,13 +1363,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NC <= 4 ? PF
       // float32; -inf masks; labels past the row's end do not count) takes the per-row kernel, whose exponential has the
       // underflow rules -- the 16 exponentials below then need neither a clamp nor a select, and scale by an integer add
       float lo = INFINITY;
+      if constexpr (FULL) {
 #pragma unroll
-      for (int k = 0; k < NC; ++k) {
-        if constexpr (AL) {
-          if (n4 == NL * 64 || in_row(k)) lo = min3_raw(min3_raw(lo, r[k].x, r[k].y), r[k].z, r[k].w);
-        } else {
-          const int e0 = (k * 64 + lane) * 4;
-          lo = fminf(lo, fminf(fminf(e0 < V ? r[k].x : lo, e0 + 1 < V ? r[k].y : lo), fminf(e0 + 2 < V ? r[k].z : lo, e0 + 3 < V ? r[k].w : lo)));
+        for (int k = 0; k < NC; ++k) lo = min3_raw(min3_raw(lo, r[k].x, r[k].y), r[k].z, r[k].w);
+      } else {
+#pragma unroll
+        for (int k = 0; k < NC; ++k) {
+          if constexpr (AL) {
+            if (in_row(k)) lo = min3_raw(min3_raw(lo, r[k].x, r[k].y), r[k].z, r[k].w);
+          } else {
+            const int e0 = (k * 64 + lane) * 4;
+            lo = fminf(lo, fminf(fminf(e0 < V ? r[k].x : lo, e0 + 1 < V ? r[k].y : lo), fminf(e0 + 2 < V ? r[k].z : lo, e0 + 3 < V ? r[k].w : lo)));
+          }
         }
       }
       if (clean && __ballot(!(lo - m > -87.0f)) != 0ull) clean = false;
@@ -1357,13 +1405,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NC <= 4 ? PF
           }
         }
 #pragma unroll
-        for (int k = 0; k < NC; ++k) {
-          const f32x2 e01 = ex[k][0], e23 = ex[k][1];
-          bool inside = true;  // (labels past the row's end hold -inf: garbage here, never read by the leaves, kept out of the screen's sum)
-          if constexpr (AL) inside = n4 == NL * 64 || in_row(k);
-          else inside = (k * 64 + lane) * 4 + 3 < V;
-          if (inside) approx += e01 + e23;
-          *(float4*)(np_rb + np_pad((k * 64 + lane) * 4)) = make_float4(e01.x, e01.y, e23.x, e23.y);
+        for (int k = 0; k < NC; ++k)
+          *(float4*)(np_rb + np_pad((k * 64 + lane) * 4)) = make_float4(ex[k][0].x, ex[k][0].y, ex[k][1].x, ex[k][1].y);
+        if constexpr (FULL) {
+#pragma unroll
+          for (int k = 0; k < NC; ++k) approx += ex[k][0] + ex[k][1];
+        } else {
+#pragma unroll
+          for (int k = 0; k < NC; ++k) {
+            bool inside;  // (labels past the row's end hold -inf: garbage here, never read by the leaves, kept out of the screen's sum)
+            if constexpr (AL) inside = in_row(k);
+            else inside = (k * 64 + lane) * 4 + 3 < V;
+            if (inside) approx += ex[k][0] + ex[k][1];
+          }
         }
         s = (double)wave_sum_f32(approx.x + approx.y);
       } else {
@@ -1378,8 +1432,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NC <= 4 ? PF
       s = wave_sum((double)(acc.x + acc.y));
       }
       // candidates: a float32 screen that cannot miss a survivor -- the threshold on the logits from a float32 logarithm
-      // (|error| < 1e-6 (1 + lse)), lowered by a margin two orders above that and above the rounding of the sum
-      const float xthr = (m + __logf((float)s)) + tminf;
+      // (|error| < 1e-6 (1 + lse)), lowered by a margin two orders above that and above the rounding of the sum. The sum is in
+      // [1, 4096): v_log_f32 and one multiply (__logf guards denormal arguments with a dozen instructions more)
+      const float xthr = (m + __builtin_amdgcn_logf((float)s) * 0.693147180559945309f) + tminf;
       const float pre = xthr - 3e-5f * (4.0f + fabsf(xthr));
       cnt = 0;
 #pragma unroll
@@ -1421,12 +1476,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NC <= 4 ? PF
           }
         }
       }
-      if constexpr (NP) np_accumulate(i);
+      if constexpr (NP) {
+        if (a.np_uniform8) np_accumulate8(i);
+        else np_accumulate(i);
+      }
     }
     if (lane == i) {
       my_m = m;
       my_rs = rs;
-      my_s = s;
+      if constexpr (!NP) my_s = s;
       my_first = first;
       my_cnt = cnt;
     }
@@ -1437,39 +1495,46 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NC <= 4 ? PF
   // end the last row is requested again: an L2 hit nobody looks at): the compiler places `s_waitcnt vmcnt(n)` by counting the
   // loads outstanding on every path into a block and keeping the SMALLEST count, so a single path that skips a row's loads
   // (a short block, the loop's last iterations) turned every wait into "all of them" -- the prefetch existed in the source only.
-  const int64_t row_last = row_lo + nrows - 1;
-  auto row_at = [&](int i) { return row_lo + i < row_last ? row_lo + i : row_last; };
-  if constexpr (NC <= 4) {
-    // two rows in flight (three register buffers in rotation): at 13 waves per CU (LDS) and 4 KB a row that is ~100 KB per CU
-    // on its way, what ~6 TB/s times the loaded memory latency asks for
-    Raw ra[NL], rb[NL], rc[NL];
-    load_row(row_at(0), ra);
-    load_row(row_at(1), rb);
-    for (int i = 0; i < nrows; i += 3) {
-      load_row(row_at(i + 2), rc);
-      phase_a(i, ra);
-      load_row(row_at(i + 3), ra);
-      if (i + 1 < nrows) phase_a(i + 1, rb);
-      load_row(row_at(i + 4), rb);
-      if (i + 2 < nrows) phase_a(i + 2, rc);
+  auto row_at = [&](int i) { return i < nrows - 1 ? i : nrows - 1; };
+  auto rows = [&](auto full_c) __attribute__((always_inline)) {
+    if constexpr (NC <= 4) {
+      // two rows in flight (three register buffers in rotation): at 13 waves per CU (LDS) and 4 KB a row that is ~100 KB per CU
+      // on its way, what ~6 TB/s times the loaded memory latency asks for
+      Raw ra[NL], rb[NL], rc[NL];
+      load_row(row_at(0), ra);
+      load_row(row_at(1), rb);
+      for (int i = 0; i < nrows; i += 3) {
+        load_row(row_at(i + 2), rc);
+        phase_a(full_c, i, ra);
+        load_row(row_at(i + 3), ra);
+        if (i + 1 < nrows) phase_a(full_c, i + 1, rb);
+        load_row(row_at(i + 4), rb);
+        if (i + 2 < nrows) phase_a(full_c, i + 2, rc);
+      }
+    } else if constexpr (NC <= 8) {
+      Raw ra[NL], rb[NL];
+      load_row(row_at(0), ra);
+      for (int i = 0; i < nrows; i += 2) {
+        load_row(row_at(i + 1), rb);
+        phase_a(full_c, i, ra);
+        load_row(row_at(i + 2), ra);
+        if (i + 1 < nrows) phase_a(full_c, i + 1, rb);
+      }
+    } else {
+      // 2049 .. 4095 labels (round 5): a row is up to 64 registers per lane, there is no room for a second one in flight --
+      // the other waves of the CU cover the wait (round 5 measured what the rows in flight are worth at V = 1024: 4 %)
+      Raw ra[NL];
+      for (int i = 0; i < nrows; ++i) {
+        load_row(row_at(i), ra);
+        phase_a(full_c, i, ra);
+      }
     }
-  } else if constexpr (NC <= 8) {
-    Raw ra[NL], rb[NL];
-    load_row(row_at(0), ra);
-    for (int i = 0; i < nrows; i += 2) {
-      load_row(row_at(i + 1), rb);
-      phase_a(i, ra);
-      load_row(row_at(i + 2), ra);
-      if (i + 1 < nrows) phase_a(i + 1, rb);
-    }
+  };
+  if constexpr (AL) {
+    if (full_row) rows(std::true_type());
+    else rows(std::false_type());
   } else {
-    // 2049 .. 4095 labels (round 5): a row is up to 64 registers per lane, there is no room for a second one in flight --
-    // the other waves of the CU cover the wait (round 5 measured what the rows in flight are worth at V = 1024: 4 %)
-    Raw ra[NL];
-    for (int i = 0; i < nrows; ++i) {
-      load_row(row_at(i), ra);
-      phase_a(i, ra);
-    }
+    rows(std::false_type());
   }
   __syncthreads();  // (one wave: orders phase A's LDS writes before phase B's reads)
 
