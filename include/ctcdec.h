@@ -427,6 +427,23 @@ int ctcdec_align_gaps_batch(ctcdec_decoder* dec, const void* const* utt_logits, 
 int ctcdec_alignment_gaps(const ctcdec_alignment* a, const int64_t** gap_off, const int32_t** start, const int32_t** end,
                           const double** logp, int64_t* n_gaps);
 
+/* ---- alignment with gaps, long transcripts: a lecture against a script with holes --------------------------------------
+ * ctcdec_align_gaps_batch with the limits and the plan of ctcdec_align_long_batch: at most 1048575 labels per utterance (gaps
+ * do not count) and no back-pointer table of all frames. States, emissions (g(t) included), transitions, tie rules and the
+ * preference at the end are those of ctcdec_align_gaps_batch. For every input that call accepts the result is that call's,
+ * bit for bit -- path, score, token frames, confidences, gaps and their sums --, however the frames are cut; for a target
+ * without gaps it is ctcdec_align_long_batch's. Kernel ctc_viterbi_gaps_long: one workgroup per utterance (256 threads up to
+ * 511 labels, 1024 above), the score columns in device memory, the window of reachable states of ctc_viterbi_long.
+ * The arguments are ctcdec_align_long_batch's, except that targets may hold CTCDEC_ALIGN_GAP; segment_frames, bp_budget and the
+ * plan's bytes are that call's, formula for formula. Validation, before any launch: ctcdec_align_gaps_batch's checks with its
+ * codes, on the labels alone; segment_frames < 0 is CTCDEC_ERR_ARG; more than 1048575 labels, or one utterance whose plan
+ * exceeds the budget, is CTCDEC_ERR_LIMIT and names the utterance.
+ * The result is read by ctcdec_alignment_paths (-1 on gap frames) / _tokens / _gaps / _plan / _timing ([1] row_lse_max,
+ * [2] ctc_viterbi_gaps_long) and freed by ctcdec_alignment_free. decoder.py: align_gaps_long / align_gaps_long_batch. */
+int ctcdec_align_gaps_long_batch(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts,
+                                 int32_t dtype, int32_t is_device, const int32_t* targets, const int64_t* target_off, int32_t fold,
+                                 int64_t bp_budget, int32_t segment_frames, ctcdec_alignment** out);
+
 /* ---- greedy decode: the best path over all texts ----------------------------------------------------------------------
  * No reference analogue (pyctcdecode always searches). Logits, frame counts, dtype and is_device are those of
  * ctcdec_decode_batch. Frame t's label arg[t] is the smallest index among the entries of row t that equal the row's largest

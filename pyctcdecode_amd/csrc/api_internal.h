@@ -198,6 +198,9 @@ struct ctcdec_decoder {
   // alignment with gaps (ctcdec_align_gaps_batch): row maxima, the slots' gap flags, the gaps' sums, a launch's utterance
   // records (everything else: the alignment's)
   DevBuf w_amax, w_agap, w_aglp, w_agutts;
+  // alignment with gaps, long transcripts (ctcdec_align_gaps_long_batch): the groups' records of every target and a launch's
+  // utterance records (columns, checkpoints and tables: the long call's; everything else: the gaps call's)
+  DevBuf w_lgrec, w_lgutts;
   // greedy decode (ctcdec_greedy_batch): the rows' labels, the utterances' token counts and offsets, the tokens' labels, spans
   // and confidences (row maxima: w_amax, scores: w_ascore)
   DevBuf w_garg, w_gcnt, w_gtoff, w_glab, w_gspan, w_glogp;

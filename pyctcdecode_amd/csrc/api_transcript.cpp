@@ -307,14 +307,16 @@ struct GapSlots {
   std::vector<double> logp;
 };
 
-// The call behind ctcdec_align_batch (Utt = AlignUtt, no slots), ctcdec_align_gaps_batch (Utt = GapsUtt) and
-// ctcdec_align_long_batch (Utt = AlignLongUtt, with every utterance's plan): the checked labels of every utterance to a
-// result with its paths, spans, scores and, with a fold, confidences.
+// The call behind ctcdec_align_batch (Utt = AlignUtt, no slots), ctcdec_align_gaps_batch (Utt = GapsUtt),
+// ctcdec_align_long_batch (Utt = AlignLongUtt, with every utterance's plan) and ctcdec_align_gaps_long_batch (Utt =
+// GapsLongUtt: slots and plans): the checked labels of every utterance to a result with its paths, spans, scores and, with a
+// fold, confidences.
 template <class Utt>
 static int viterbi_call(ctcdec_decoder* dec, const TranscriptCall& tc, const void* const* utt_logits, const int32_t* utt_frames,
                         int32_t n_utts, int32_t dtype, int32_t is_device, const int32_t* labels, const int64_t* lab_off, int32_t fold,
                         int64_t budget, GapSlots* slots, const std::vector<LongPlan>* plans, std::unique_ptr<ctcdec_alignment>& res) {
-  constexpr bool GAPS = std::is_same<Utt, GapsUtt>::value, LONG = std::is_same<Utt, AlignLongUtt>::value;
+  constexpr bool GLONG = std::is_same<Utt, GapsLongUtt>::value;  // (both of the following, and the groups' records)
+  constexpr bool GAPS = std::is_same<Utt, GapsUtt>::value || GLONG, LONG = std::is_same<Utt, AlignLongUtt>::value || GLONG;
   res.reset(new ctcdec_alignment());
   const size_t n = (size_t)n_utts;
   for (size_t u = 0; u < n; ++u) {
@@ -350,9 +352,21 @@ static int viterbi_call(ctcdec_decoder* dec, const TranscriptCall& tc, const voi
       be::zero(dec->w_atlp.p, nl1 * 8, &err) || be::zero(dec->w_ascore.p, n * 8, &err) ||
       (GAPS && (be::h2d(dec->w_agap.p, slots->gap.data(), (size_t)NS, &err) || be::zero(dec->w_aglp.p, (size_t)NS * 8, &err))))
     return fail(CTCDEC_ERR_DEVICE, err);
-  // launches: utterances in input order until their back-pointer tables (LONG: their planned bytes) fill the budget; longest
-  // first inside a launch
   const auto chunks_of = [&](int32_t u) { return align_chunks((int32_t)(lab_off[u + 1] - lab_off[u])); };
+  // (GLONG) every group's record, built here next to the labels: target data like them, in no plan
+  std::vector<int64_t> rec_off(n + 1, 0);
+  if constexpr (GLONG) {
+    std::vector<GapGroup> recs;
+    for (size_t u = 0; u < n; ++u) {
+      const int32_t L = (int32_t)(lab_off[u + 1] - lab_off[u]);
+      for (int32_t c = 0; c < chunks_of((int32_t)u); ++c)
+        recs.push_back(gap_group_record(labels + lab_off[u], slots->gap.data() + slots->off[u], L, c));
+      rec_off[u + 1] = (int64_t)recs.size();
+    }
+    if (upload(dec->w_lgrec, recs, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+  }
+  // launches: utterances in input order until their back-pointer tables (LONG: their planned bytes) fill the budget; longest
+  // first inside a launch (GLONG: first among those of at most 256 groups, which run with 256 threads, then among the others)
   // (LONG) the bytes of an utterance's segment table, and the doubles of its two columns and its checkpoints: the plan's terms
   const auto table_of = [&](int32_t u) { return LONG ? (int64_t)(*plans)[(size_t)u].K * chunks_of(u) : (int64_t)utt_frames[u] * chunks_of(u); };
   const auto doubles_of = [&](int32_t u) { return LONG ? ((*plans)[(size_t)u].bytes - table_of(u)) / 8 : (int64_t)0; };
@@ -371,10 +385,13 @@ static int viterbi_call(ctcdec_decoder* dec, const TranscriptCall& tc, const voi
   if (dec->w_abp.ensure((size_t)std::max<int64_t>(most, 1), &err)) return fail(CTCDEC_ERR_DEVICE, err);
   std::vector<Utt> utts;
   for (auto& g : groups) {
-    std::stable_sort(g.begin(), g.end(), [&](int32_t a, int32_t b) { return utt_frames[a] > utt_frames[b]; });
+    const auto small = [&](int32_t u) { return GLONG && chunks_of(u) <= ALIGN_THREADS; };
+    std::stable_sort(g.begin(), g.end(), [&](int32_t a, int32_t b) {
+      return small(a) != small(b) ? small(a) : utt_frames[a] > utt_frames[b];
+    });
     utts.clear();
     int64_t bp_off = 0, col_off = 0;
-    int32_t max_chunks = 1;
+    int32_t max_chunks = 1, n_small = 0;
     for (int32_t u : g) {
       const int64_t lo = lab_off[u];
       Utt a;
@@ -403,15 +420,19 @@ static int viterbi_call(ctcdec_decoder* dec, const TranscriptCall& tc, const voi
         a.gap = (const uint8_t*)dec->w_agap.p + slots->off[(size_t)u];
         a.gap_logp = (double*)dec->w_aglp.p + slots->off[(size_t)u];
       }
+      if constexpr (GLONG) a.rec = (const GapGroup*)dec->w_lgrec.p + rec_off[(size_t)u];
+      n_small += small(u) ? 1 : 0;
       utts.push_back(a);
       bp_off += table_of(u);
       max_chunks = std::max(max_chunks, chunks_of(u));
     }
 #ifdef CTC_SIM
-    std::vector<double> col((size_t)(GAPS ? 2 : LONG ? 0 : 8) * (size_t)max_chunks);  // (LONG: the columns are the record's)
+    std::vector<double> col((size_t)(LONG ? 0 : GAPS ? 2 : 8) * (size_t)max_chunks);  // (LONG: the columns are the record's)
     AlignSeqCtx cx;
     for (const Utt& a : utts) {
-      if constexpr (GAPS)
+      if constexpr (GLONG)
+        for_dtype(dtype, [&](auto dt) { ctc_viterbi_gaps_long_utt<decltype(dt)::value, GAPS_LONG_BATCH>(cx, a, tc.V, tc.blank, fold, tc.clip_lo); });
+      else if constexpr (GAPS)
         for_dtype(dtype, [&](auto dt) { ctc_viterbi_gaps_utt<decltype(dt)::value>(cx, a, tc.V, tc.blank, fold, tc.clip_lo, col.data()); });
       else if constexpr (LONG)
         ctc_viterbi_long_utt(cx, a, tc.V, dtype, tc.blank, fold, tc.clip_lo);
@@ -419,20 +440,23 @@ static int viterbi_call(ctcdec_decoder* dec, const TranscriptCall& tc, const voi
         ctc_viterbi_utt(cx, a, tc.V, dtype, tc.blank, fold, tc.clip_lo, col.data());
     }
 #else
-    DevBuf& records = GAPS ? dec->w_agutts : LONG ? dec->w_lutts : dec->w_autts;
+    DevBuf& records = GLONG ? dec->w_lgutts : GAPS ? dec->w_agutts : LONG ? dec->w_lutts : dec->w_autts;
     if (upload(records, utts, &err)) return fail(CTCDEC_ERR_DEVICE, err);
-    typename std::conditional<GAPS, be::ViterbiGapsArgs, typename std::conditional<LONG, be::ViterbiLongArgs, be::ViterbiArgs>::type>::type va;
+    typename std::conditional<GLONG, be::ViterbiGapsLongArgs, typename std::conditional<GAPS, be::ViterbiGapsArgs,
+        typename std::conditional<LONG, be::ViterbiLongArgs, be::ViterbiArgs>::type>::type>::type va;
     va.utts = (const Utt*)records.p;
     va.n_utts = (int32_t)utts.size();
     va.n_labels = tc.V;
     va.dtype = dtype;
     va.blank = tc.blank;
     va.fold = fold;
-    if constexpr (LONG) va.pad = 0;
+    if constexpr (GLONG) va.n_small = n_small;
+    else if constexpr (LONG) va.pad = 0;
     else va.max_chunks = max_chunks;
     va.clip_lo = tc.clip_lo;
     int rc;
-    if constexpr (GAPS) rc = be::launch_ctc_viterbi_gaps(va, &err);
+    if constexpr (GLONG) rc = be::launch_ctc_viterbi_gaps_long(va, &err);
+    else if constexpr (GAPS) rc = be::launch_ctc_viterbi_gaps(va, &err);
     else if constexpr (LONG) rc = be::launch_ctc_viterbi_long(va, &err);
     else rc = be::launch_ctc_viterbi(va, &err);
     if (rc) return fail(CTCDEC_ERR_DEVICE, err);
@@ -448,7 +472,7 @@ static int viterbi_call(ctcdec_decoder* dec, const TranscriptCall& tc, const voi
   if (GAPS && be::d2h(slots->logp.data(), dec->w_aglp.p, (size_t)NS * 8, &err)) return fail(CTCDEC_ERR_DEVICE, err);
 #ifndef CTC_SIM
   res->ms[1] = be::align_kernel_ms(GAPS ? be::K_ROW_LSE_MAX : be::K_ROW_LSE);
-  res->ms[2] = be::align_kernel_ms(GAPS ? be::K_VITERBI_GAPS : LONG ? be::K_VITERBI_LONG : be::K_VITERBI);
+  res->ms[2] = be::align_kernel_ms(GLONG ? be::K_VITERBI_GAPS_LONG : GAPS ? be::K_VITERBI_GAPS : LONG ? be::K_VITERBI_LONG : be::K_VITERBI);
 #endif
   return CTCDEC_OK;
 }
@@ -538,12 +562,17 @@ int ctcdec_alignment_plan(const ctcdec_alignment* a, const int32_t** segment_fra
 }
 
 // ---- alignment with gaps ("Alignment with gaps") -------------------------------------------------------------
-int ctcdec_align_gaps_batch(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts, int32_t dtype,
-                            int32_t is_device, const int32_t* targets, const int64_t* target_off, int32_t fold, int64_t bp_budget,
-                            ctcdec_alignment** out) {
+}  // extern "C"
+
+// ctcdec_align_gaps_batch, and with segment_frames >= 0 ctcdec_align_gaps_long_batch: that call over the plans of
+// ctcdec_align_long_batch, with that call's limit of labels
+static int align_gaps_call(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts, int32_t dtype,
+                           int32_t is_device, const int32_t* targets, const int64_t* target_off, int32_t fold, int64_t bp_budget,
+                           int32_t segment_frames, const std::string& bad_option, ctcdec_alignment** out) {
+  const bool planned = segment_frames >= 0;
   TranscriptCall tc;
   const bool args_ok = dec && out && n_utts >= 0 && target_off && bp_budget >= 0 && (n_utts == 0 || (utt_logits && utt_frames));
-  if (int rc = transcript_open(dec, args_ok, dtype, bad_fold(fold), tc)) return rc;
+  if (int rc = transcript_open(dec, args_ok, dtype, !bad_fold(fold).empty() ? bad_fold(fold) : bad_option, tc)) return rc;
   const int64_t budget = bp_budget ? bp_budget : ALIGN_BP_BUDGET;
   const size_t n = (size_t)n_utts;
   // the items apart: the labels, with offsets of their own, and one flag per slot (before label 0, between neighbours, after
@@ -573,14 +602,21 @@ int ctcdec_align_gaps_batch(ctcdec_decoder* dec, const void* const* utt_logits, 
     slots.off[u + 1] = (int64_t)slots.gap.size();
   }
   if (labels.empty()) labels.push_back(0);  // (never read: .data() of an empty vector may be null)
-  if (int rc = check_alignment(utt_logits, utt_frames, n_utts, labels.data(), lab_off.data(), budget, tc)) return rc;
+  if (int rc = check_alignment(utt_logits, utt_frames, n_utts, labels.data(), lab_off.data(), budget, tc,
+                               planned ? ALIGN_LONG_MAX_LABELS : ALIGN_MAX_LABELS, segment_frames))
+    return rc;
   for (size_t u = 0; u < n; ++u)
     if (lab_off[u + 1] == lab_off[u])
       return fail(CTCDEC_ERR_ARG, "utterance " + std::to_string(u) + ": a target needs at least one label");
+  std::vector<LongPlan> plans;
+  for (size_t u = 0; planned && u < n; ++u)
+    plans.push_back(long_plan(utt_frames[u], (int32_t)(lab_off[u + 1] - lab_off[u]), budget, segment_frames));
   const auto t_begin = Clock::now();
   std::unique_ptr<ctcdec_alignment> res;
-  if (int rc = viterbi_call<GapsUtt>(dec, tc, utt_logits, utt_frames, n_utts, dtype, is_device, labels.data(), lab_off.data(), fold,
-                                     budget, &slots, nullptr, res))
+  if (int rc = planned ? viterbi_call<GapsLongUtt>(dec, tc, utt_logits, utt_frames, n_utts, dtype, is_device, labels.data(), lab_off.data(),
+                                                   fold, budget, &slots, &plans, res)
+                       : viterbi_call<GapsUtt>(dec, tc, utt_logits, utt_frames, n_utts, dtype, is_device, labels.data(), lab_off.data(),
+                                               fold, budget, &slots, nullptr, res))
     return rc;
   // the gaps, in target order: everything between the end of the label before and the start of the label after
   res->gap_off.assign(n + 1, 0);
@@ -597,6 +633,22 @@ int ctcdec_align_gaps_batch(ctcdec_decoder* dec, const void* const* utt_logits, 
   res->ms[3] = ms(t_begin, Clock::now());
   *out = res.release();
   return CTCDEC_OK;
+}
+
+extern "C" {
+
+int ctcdec_align_gaps_batch(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts, int32_t dtype,
+                            int32_t is_device, const int32_t* targets, const int64_t* target_off, int32_t fold, int64_t bp_budget,
+                            ctcdec_alignment** out) {
+  return align_gaps_call(dec, utt_logits, utt_frames, n_utts, dtype, is_device, targets, target_off, fold, bp_budget, -1, "", out);
+}
+
+// ---- alignment with gaps, long transcripts ("Alignment with gaps, long transcripts") -------------------------
+int ctcdec_align_gaps_long_batch(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts,
+                                 int32_t dtype, int32_t is_device, const int32_t* targets, const int64_t* target_off, int32_t fold,
+                                 int64_t bp_budget, int32_t segment_frames, ctcdec_alignment** out) {
+  return align_gaps_call(dec, utt_logits, utt_frames, n_utts, dtype, is_device, targets, target_off, fold, bp_budget,
+                         segment_frames < 0 ? 0 : segment_frames, segment_frames < 0 ? "segment_frames must not be negative" : "", out);
 }
 
 int ctcdec_alignment_gaps(const ctcdec_alignment* a, const int64_t** gap_off_out, const int32_t** start_out, const int32_t** end_out,

@@ -326,6 +326,21 @@ struct ViterbiGapsArgs {
   double clip_lo;      // ln(MIN_TOKEN_CLIP_P)
 };
 int launch_ctc_viterbi_gaps(const ViterbiGapsArgs& a, std::string* err);
+// ctc_viterbi_gaps_long: one workgroup per entry of `utts`, all of them validated by the host (GapsLongUtt); the columns,
+// checkpoints and segment tables the entries name are theirs alone. The first n_small entries have at most 256 groups of
+// states and run with 256 threads, the others with 1024: two launches, one event pair. CTCDEC_GAPS_LONG_THREADS=256 / 1024
+// (tests) gives every entry that size.
+struct ViterbiGapsLongArgs {
+  const GapsLongUtt* utts;  // [n_utts] (device)
+  int32_t n_utts;
+  int32_t n_labels;
+  int32_t dtype;
+  int32_t blank;
+  int32_t fold;        // 0, LOGP_MEAN / LOGP_MIN / LOGP_MAX
+  int32_t n_small;
+  double clip_lo;      // ln(MIN_TOKEN_CLIP_P)
+};
+int launch_ctc_viterbi_gaps_long(const ViterbiGapsLongArgs& a, std::string* err);
 // Greedy decode. row_argmax: every row's most probable label -- the smallest index of the row's largest entry that is not a
 // NaN, `blank` for a row without an entry above -inf -- in arg[n_rows]; utt_is_prob and lse are not used. row_lse_argmax:
 // row_lse_max (the same bits in a.lse and rmax) that also stores row_argmax's label. greedy_collapse: one wavefront per
@@ -348,7 +363,7 @@ int launch_ctc_prefix_advance(const PrefixAdvanceArgs& a, std::string* err);
 // two passes, and ctc_prefix_extend, ctc_prefix_finish and ctc_prefix_fill; ctc_prefix_advance has its own.
 enum AlignKernel {
   K_ROW_LSE, K_VITERBI, K_FORWARD, K_POSTERIORS, K_GRAD_ROWS, K_FIND, K_ROW_LSE_MAX, K_VITERBI_GAPS, K_ROW_ARGMAX, K_ROW_LSE_ARGMAX,
-  K_GREEDY_COLLAPSE, K_PREFIX_EXTEND, K_PREFIX_ADVANCE, K_VITERBI_LONG, ALIGN_KERNELS
+  K_GREEDY_COLLAPSE, K_PREFIX_EXTEND, K_PREFIX_ADVANCE, K_VITERBI_LONG, K_VITERBI_GAPS_LONG, ALIGN_KERNELS
 };
 void align_timing_reset();
 double align_kernel_ms(AlignKernel kind);

@@ -575,6 +575,8 @@ int launch_row_lse_max_on(const RowLseArgs& a, double* rmax, hipStream_t stream,
 int launch_row_lse_max(const RowLseArgs& a, double* rmax, std::string* err) { return launch_row_lse_max_on(a, rmax, g_stream, err); }
 int launch_ctc_viterbi_gaps_on(const ViterbiGapsArgs& a, hipStream_t stream, std::string* err);
 int launch_ctc_viterbi_gaps(const ViterbiGapsArgs& a, std::string* err) { return launch_ctc_viterbi_gaps_on(a, g_stream, err); }
+int launch_ctc_viterbi_gaps_long_on(const ViterbiGapsLongArgs& a, hipStream_t stream, std::string* err);
+int launch_ctc_viterbi_gaps_long(const ViterbiGapsLongArgs& a, std::string* err) { return launch_ctc_viterbi_gaps_long_on(a, g_stream, err); }
 int launch_row_argmax_on(const RowLseArgs& a, int32_t* arg, int blank, hipStream_t stream, std::string* err);
 int launch_row_argmax(const RowLseArgs& a, int32_t* arg, int blank, std::string* err) { return launch_row_argmax_on(a, arg, blank, g_stream, err); }
 int launch_row_lse_argmax_on(const RowLseArgs& a, double* rmax, int32_t* arg, int blank, hipStream_t stream, std::string* err);

@@ -10,6 +10,7 @@
 //   ctc_grad_row                   the gradient of the likelihood, row by row   (ctc_grad_rows)
 //   ctc_find_phrase / _wave_phrase a phrase's occurrences, free start and end   (ctc_find / ctc_find_wave)
 //   ctc_viterbi_gaps_utt           the best path of a target with gaps          (ctc_viterbi_gaps)
+//   ctc_viterbi_gaps_long_utt      the same, its columns in device memory, its frames in segments  (ctc_viterbi_gaps_long)
 //   row_argmax_seq                 a row's most probable label: the simulator's; the kernels fold by lanes
 //   greedy_collapse_utt            runs of frame labels to tokens               (greedy_collapse)
 //   ctc_forward_hyp / _wave_hyp <ENDS>  the forward pass that also stores a prefix' end states  (ctc_forward_ends / ctc_forward_wave_ends)
@@ -17,8 +18,9 @@
 //   ctc_prefix_advance_child       a child prefix' end states from its parent's  (ctc_prefix_advance)
 // The shared pieces, and who uses them:
 //   viterbi_backtrace                                    ctc_viterbi, ctc_viterbi_gaps
-//   viterbi_backtrace_span (a segment of it)             ctc_viterbi_long
-//   fold_token_logp                                      ctc_viterbi, ctc_viterbi_gaps, ctc_viterbi_long
+//   viterbi_backtrace_span (a segment of it)             ctc_viterbi_long, ctc_viterbi_gaps_long
+//   fold_token_logp                                      ctc_viterbi, ctc_viterbi_gaps, ctc_viterbi_long, ctc_viterbi_gaps_long
+//   gap_step                                             ctc_viterbi_gaps, ctc_viterbi_gaps_long
 //   group_setup, EntrySource, FrameEntries               ctc_find, ctc_find_wave, ctc_viterbi_gaps
 //   thread_setup                                         ctc_find, ctc_viterbi_gaps
 // ctc_forward_hyp, ctc_forward_wave_hyp and ctc_posteriors_utt keep their loops in raw variables: over FrameEntries
@@ -1551,6 +1553,215 @@ CTC_HD void ctc_viterbi_gaps_utt(Ctx& cx, const GapsUtt& utt, int V, int blank, 
     utt.gap_logp[j] = acc;
   }
   if (fold) fold_token_logp(cx, x, DT, lse, lab, utt.tok_start, utt.tok_end, utt.tok_logp, T, L, V, is_prob, fold, clip_lo);
+}
+
+// ---- ctc_viterbi_gaps_long ------------------------------------------------------------------------------------------------------
+// ctc_viterbi_gaps for targets whose columns do not fit LDS and whose back-pointer table does not fit memory (DESIGN.md,
+// "Alignment with gaps, long transcripts"): gap_step on the same operands, so ctc_viterbi_gaps' bits -- and, where no slot is a
+// gap, ctc_viterbi_long's. The columns, segments, checkpoints and two passes are ctc_viterbi_long_utt's, and so is its window
+// of reachable states: transitions do not change with gaps, a state inside frame t's window reads only states inside frame
+// t - 1's, cells above the window are -inf with or without it (every emission is finite), and cells below it are never traced.
+// What differs from ctc_viterbi_long is how a thread goes through its groups (gaps_long_frames).
+
+// What a group of four states keeps for the whole recursion, in 8 bytes (labels fit 16 bits: an alphabet has at most 65536):
+// the ForwardGroup and the gap flags of its two slots. Built once per call by the host, next to the labels.
+struct GapGroup {
+  uint16_t l0, l1;
+  uint32_t flags;
+};
+constexpr uint32_t GG_HAS0 = 1u, GG_HAS1 = 2u, GG_BLANK2 = 4u, GG_SKIP0 = 8u, GG_SKIP1 = 16u, GG_GAP0 = 32u, GG_GAP2 = 64u;
+constexpr int32_t GAP_GROUP_MAX_LABEL = 65535;
+constexpr int GAPS_LONG_BATCH = 2;  // U: the groups a thread takes at a time (profiles/align_kernel_resources.txt)
+
+// gap: [L + 1] the slots' flags
+inline GapGroup gap_group_record(const int32_t* lab, const uint8_t* gap, int L, int c) {
+  const ForwardGroup g = forward_group(lab, L, c);
+  GapGroup r;
+  r.l0 = (uint16_t)(g.l0 >= 0 ? g.l0 : 0);
+  r.l1 = (uint16_t)(g.l1 >= 0 ? g.l1 : 0);
+  r.flags = (g.l0 >= 0 ? GG_HAS0 : 0u) | (g.l1 >= 0 ? GG_HAS1 : 0u) | (g.blank2 ? GG_BLANK2 : 0u) | (g.skip0 ? GG_SKIP0 : 0u) |
+            (g.skip1 ? GG_SKIP1 : 0u) | (2 * c <= L && gap[2 * c] ? GG_GAP0 : 0u) | (2 * c + 1 <= L && gap[2 * c + 1] ? GG_GAP2 : 0u);
+  return r;
+}
+
+// One utterance of a ctc_viterbi_gaps_long launch, validated by the host as a GapsUtt is. col, ckpt and bp are the
+// utterance's own: no other workgroup reads or writes them. col and ckpt lie on 32-byte boundaries.
+struct GapsLongUtt {
+  const void* x;        // [T, V] logits or probabilities, of the launch's dtype
+  const double* lse;    // [T] log-sum-exp of each row (not used when is_prob)
+  const double* rmax;   // [T] largest entry of each row that is not a NaN
+  const int32_t* lab;   // [L] target labels
+  const uint8_t* gap;   // [L + 1] 1: the slot is a gap
+  const GapGroup* rec;  // [align_chunks(L)] gap_group_record of every group
+  double* col;          // [2 * 4 * align_chunks(L)] the two score columns
+  double* ckpt;         // [n * 4 * align_chunks(L)] (n > 1) the column each segment starts from
+  uint8_t* bp;          // [min(K, T - 1) * align_chunks(L)] one segment's back-pointers, four 2-bit entries per byte
+  int32_t* path;        // [T] out: the label taken at each frame, the blank id in a plain slot, -1 in a gap slot
+  int32_t* tok_start;   // [L] out
+  int32_t* tok_end;     // [L] out
+  double* tok_logp;     // [L] out (fold != 0)
+  double* gap_logp;     // [L + 1] out, gap slots only: the sum of g(t) over the slot's frames, in frame order
+  double* score;        // [1] out: the last column's value at the end state
+  int32_t T, L, is_prob, K;  // 1 <= K <= T: the frames of a segment
+};
+
+// Two scores as they lie in a column: a group's four are one 32-byte-aligned run, read and written as two of these
+struct alignas(16) ScorePair {
+  double a, b;
+};
+
+// The frames f + 1 .. e of the recursion, as viterbi_long_frames runs them (the same window, the same role of the two
+// columns, BP: frame t's back-pointers to row t - f - 1 of bp). A thread owns the groups clo + tid + k * nt of a frame's
+// window and takes them U at a time: for a batch it first issues every load -- the U records, each group's four scores as
+// two 16-byte loads and the last score of the group below, then each group's two entries of the row -- and only then runs
+// gap_step on each group and stores its four scores and its byte. A group past the window's end loads what the window's last
+// group loads (always valid) and stores nothing. The row's scalars -- the blank's entry, the log-sum-exp, the maximum -- are
+// asked for one frame ahead, before the frame's arithmetic.
+template <int DT, int U, bool BP, class Ctx>
+CTC_HD void gaps_long_frames(Ctx& cx, const GapsLongUtt& u, int V, int blank, double clip_lo, int f, int e, uint8_t* bp) {
+  typedef typename AlignRaw<DT>::type Raw;
+  const int T = u.T, L = u.L;
+  const int S = 2 * L + 1, nch = align_chunks(L);
+  const double NEG = align_neg_inf();
+  const bool is_prob = u.is_prob != 0;
+  const void* const x = u.x;
+  const double* const lse = u.lse;
+  const double* const rmax = u.rmax;
+  const GapGroup* const rec = u.rec;
+  double* c0 = u.col;
+  double* c1 = u.col + 4 * nch;
+  int prev_lo4 = f > 0 && T - 1 - f < L ? 4 * ((2 * (L - (T - 1 - f)) - 1) >> 2) : 0;
+  if (f + 1 > e) return;
+  Raw vb = align_load_raw<DT>(x, (size_t)(f + 1) * (size_t)V + (size_t)blank);
+  double lse_t = lse[f + 1], max_t = rmax[f + 1];
+  for (int t = f + 1; t <= e; ++t) {
+    const double* prev = (t & 1) ? c0 : c1;
+    double* cur = (t & 1) ? c1 : c0;
+    const int rest = T - 1 - t;  // lo = S - 2 - 2 * rest, hi = 2 * t + 1
+    const int clo = rest < L ? (2 * (L - rest) - 1) >> 2 : 0, chi = (t < L ? 2 * t + 1 : S - 1) >> 2;
+    const size_t row = (size_t)t * (size_t)V;
+    const int tn = t < e ? t + 1 : t;  // (after the segment's last frame: that frame again, never used)
+    const Raw vb_n = align_load_raw<DT>(x, (size_t)tn * (size_t)V + (size_t)blank);
+    const double lse_n = lse[tn], max_n = rmax[tn];
+    const double e_blank = align_emit_of_value(align_widen<DT>(vb), is_prob ? 0.0 : lse_t, is_prob, clip_lo);
+    const double e_gap = align_emit_of_value(max_t, is_prob ? 0.0 : lse_t, is_prob, clip_lo);
+    uint8_t* const bp_row = BP ? bp + (size_t)(t - f - 1) * (size_t)nch : nullptr;
+    for (int cb = clo + cx.tid; cb <= chi; cb += U * cx.nt) {
+      GapGroup r[U];
+      ScorePair lo2[U], hi2[U];
+      double pm1[U];
+      Raw v0[U], v1[U];
+      CTC_UNROLL
+      for (int k = 0; k < U; ++k) {
+        const int c = cb + k * cx.nt;
+        r[k] = rec[c <= chi ? c : chi];
+      }
+      CTC_UNROLL
+      for (int k = 0; k < U; ++k) {
+        const int c = cb + k * cx.nt;
+        const int s0 = 4 * (c <= chi ? c : chi);
+        const ScorePair* at = (const ScorePair*)(prev + s0);
+        lo2[k] = at[0];
+        hi2[k] = at[1];
+        pm1[k] = prev[s0 > 0 ? s0 - 1 : 0];
+      }
+      CTC_UNROLL
+      for (int k = 0; k < U; ++k) {
+        v0[k] = align_load_raw<DT>(x, row + (size_t)((r[k].flags & GG_HAS0) ? (int)r[k].l0 : blank));
+        v1[k] = align_load_raw<DT>(x, row + (size_t)((r[k].flags & GG_HAS1) ? (int)r[k].l1 : blank));
+      }
+      CTC_UNROLL
+      for (int k = 0; k < U; ++k) {
+        const int c = cb + k * cx.nt;
+        if (c > chi) continue;
+        const uint32_t fl = r[k].flags;
+        const ForwardGroup g{(fl & GG_HAS0) ? (int32_t)r[k].l0 : -1, (fl & GG_HAS1) ? (int32_t)r[k].l1 : -1, (fl & GG_SKIP0) != 0,
+                             (fl & GG_SKIP1) != 0, (fl & GG_BLANK2) != 0};
+        double p[4] = {lo2[k].a, lo2[k].b, hi2[k].a, hi2[k].b};
+        const double below = 4 * c - 1 >= prev_lo4 ? pm1[k] : NEG;  // (what lies below the window of the frame before: unreachable)
+        const unsigned b = gap_step(g, (fl & GG_GAP0) != 0, (fl & GG_GAP2) != 0, below, e_blank, e_gap,
+                                    align_emit_of_value(align_widen<DT>(v0[k]), is_prob ? 0.0 : lse_t, is_prob, clip_lo),
+                                    align_emit_of_value(align_widen<DT>(v1[k]), is_prob ? 0.0 : lse_t, is_prob, clip_lo), p);
+        ScorePair* to = (ScorePair*)(cur + 4 * c);
+        to[0] = ScorePair{p[0], p[1]};
+        to[1] = ScorePair{p[2], p[3]};
+        if (BP) bp_row[c] = (uint8_t)b;
+      }
+    }
+    vb = vb_n, lse_t = lse_n, max_t = max_n;
+    prev_lo4 = 4 * clo;
+    cx.sync();  // the one barrier of a frame: the columns swap roles
+  }
+}
+
+// cx: tid, nt, sync(). A workgroup reads from device memory only what it wrote itself, behind a barrier, or input.
+template <int DT, int U, class Ctx>
+CTC_HD void ctc_viterbi_gaps_long_utt(Ctx& cx, const GapsLongUtt& u, int V, int blank, int fold, double clip_lo) {
+  const int T = u.T, L = u.L, K = u.K;
+  if (T <= 0 || L <= 0) return;
+  const int S = 2 * L + 1, nch = align_chunks(L), nseg = align_long_segments(T, K);
+  const double NEG = align_neg_inf();
+  const bool is_prob = u.is_prob != 0;
+  const uint8_t* const gap = u.gap;
+  double* c0 = u.col;
+  double* c1 = u.col + 4 * nch;
+  for (int i = cx.tid; i < 8 * nch; i += cx.nt) u.col[i] = NEG;
+  cx.sync();
+  if (cx.tid == 0) {  // frame 0: states 0 and 1
+    const double lse0 = is_prob ? 0.0 : u.lse[0];
+    c0[0] = gap[0] ? align_emit_of_value(u.rmax[0], lse0, is_prob, clip_lo) : align_emit(u.x, DT, (size_t)blank, lse0, is_prob, clip_lo);
+    c0[1] = align_emit(u.x, DT, (size_t)u.lab[0], lse0, is_prob, clip_lo);
+  }
+  cx.sync();
+  // the pass over all frames; a checkpoint is the whole column, the -inf above the window included
+  for (int j = 0; j < nseg; ++j) {
+    const int f = j * K, e = align_long_segment_end(T, K, f);
+    if (nseg == 1) {
+      gaps_long_frames<DT, U, true>(cx, u, V, blank, clip_lo, f, e, u.bp);
+    } else {
+      const double* at = (f & 1) ? c1 : c0;  // (complete behind frame f's barrier; next written by frame f + 2, behind frame f + 1's)
+      double* keep = u.ckpt + (size_t)j * (size_t)(4 * nch);
+      for (int i = cx.tid; i < 4 * nch; i += cx.nt) keep[i] = at[i];
+      gaps_long_frames<DT, U, false>(cx, u, V, blank, clip_lo, f, e, nullptr);
+    }
+  }
+  // the end state, on >=: the last label is preferred over the trailing slot. The score is the last column's value.
+  int s = 0, open = -1;
+  if (cx.tid == 0) {
+    const double* fin = ((T - 1) & 1) ? c1 : c0;
+    s = fin[S - 2] >= fin[S - 1] ? S - 2 : S - 1;
+    *u.score = fin[s];
+  }
+  const auto slot = [&](int j) { return gap[j] ? -1 : blank; };
+  if (nseg == 1) {
+    if (cx.tid == 0) viterbi_backtrace_span(s, open, T - 1, 1, 1, nch, u.bp, u.lab, u.path, u.tok_start, u.tok_end, slot);
+  } else {
+    for (int j = nseg - 1; j >= 0; --j) {
+      const int f = j * K, e = align_long_segment_end(T, K, f);
+      double* at = (f & 1) ? c1 : c0;
+      double* other = (f & 1) ? c0 : c1;
+      const double* keep = u.ckpt + (size_t)j * (size_t)(4 * nch);
+      cx.sync();  // (thread 0 has read the last column)
+      // the other column is reset: above frame f's window frame f + 2 expects -inf, not what a later frame left there
+      for (int i = cx.tid; i < 4 * nch; i += cx.nt) at[i] = keep[i], other[i] = NEG;
+      cx.sync();  // (and thread 0 is through with the table of the segment above)
+      gaps_long_frames<DT, U, true>(cx, u, V, blank, clip_lo, f, e, u.bp);
+      // s and open go on into the segment below: a label's span may cross the boundary
+      if (cx.tid == 0) viterbi_backtrace_span(s, open, e, f + 1, f + 1, nch, u.bp, u.lab, u.path, u.tok_start, u.tok_end, slot);
+    }
+  }
+  if (cx.tid == 0) viterbi_backtrace_span(s, open, 0, 0, 0, nch, u.bp, u.lab, u.path, u.tok_start, u.tok_end, slot);  // frame 0: no step
+  cx.sync();  // (the spans thread 0 wrote are read by every thread)
+  for (int j = cx.tid; j <= L; j += cx.nt) {
+    if (!gap[j]) continue;
+    int t0 = j > 0 ? u.tok_end[j - 1] : 0, t1 = j < L ? u.tok_start[j] : T;
+    t0 = t0 < 0 ? 0 : t0;
+    t1 = t1 > T ? T : t1;
+    double acc = 0.0;
+    for (int t = t0; t < t1; ++t) acc += align_emit_of_value(u.rmax[t], is_prob ? 0.0 : u.lse[t], is_prob, clip_lo);
+    u.gap_logp[j] = acc;
+  }
+  if (fold) fold_token_logp(cx, u.x, DT, u.lse, u.lab, u.tok_start, u.tok_end, u.tok_logp, T, L, V, is_prob, fold, clip_lo);
 }
 
 // ---- row_argmax / row_lse_argmax / greedy_collapse ---------------------------------------------------------------------------

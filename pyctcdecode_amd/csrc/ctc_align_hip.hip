@@ -2,6 +2,7 @@
 //   row_lse, row_lse_max            G lanes per row; both fold with row_fold
 //   ctc_viterbi                     a workgroup per utterance, score columns in LDS
 //   ctc_viterbi_long                a workgroup of 1024 threads per utterance, score columns and checkpoints in device memory
+//   ctc_viterbi_gaps_long           the same with gaps, 256 or 1024 threads, a thread's groups in batches with the loads first
 //   ctc_forward, ctc_posteriors,    a workgroup per record, a group of four states per thread in registers
 //   ctc_find, ctc_viterbi_gaps        (256 threads up to 511 labels, 1024 above)
 //   ctc_forward_wave, ctc_find_wave a wavefront per record of at most 127 labels
@@ -15,6 +16,7 @@
 // The launchers share timed_launch (the event pair of the kernel's log and the launch's error), for_dtype and for_threads.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include <string>
 #include <vector>
@@ -347,6 +349,18 @@ __global__ __launch_bounds__(NT) void ctc_viterbi_gaps(ViterbiGapsArgs a) {
   extern __shared__ double gaps_cols[];
   ForwardGpuCtx cx{(int)threadIdx.x, NT};
   ctc_viterbi_gaps_utt<DT>(cx, a.utts[blockIdx.x], a.n_labels, a.blank, a.fold, a.clip_lo, gaps_cols);
+}
+
+// ---------------------------------------------------------------------------------------------
+// ctc_viterbi_gaps_long: one workgroup per utterance, 256 threads up to 511 labels and 1024 above; score columns, checkpoints
+// and the groups' records in device memory, a thread's groups GAPS_LONG_BATCH at a time with a batch's loads issued before
+// its arithmetic, one barrier per frame. No LDS, no workgroup waits for another (ctc_align.h). At 1024 threads sixteen waves
+// share a compute unit: at most 128 VGPRs (profiles/align_kernel_resources.txt).
+// ---------------------------------------------------------------------------------------------
+template <int NT, int DT>
+__global__ __launch_bounds__(NT) void ctc_viterbi_gaps_long(ViterbiGapsLongArgs a, int first) {
+  AlignGpuCtx cx{(int)threadIdx.x, NT};
+  ctc_viterbi_gaps_long_utt<DT, GAPS_LONG_BATCH>(cx, a.utts[first + (int)blockIdx.x], a.n_labels, a.blank, a.fold, a.clip_lo);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -780,6 +794,27 @@ int launch_ctc_viterbi_gaps_on(const ViterbiGapsArgs& a, hipStream_t stream, std
         constexpr int NT = decltype(nt)::value, DT = decltype(dt)::value;
         hipLaunchKernelGGL((ctc_viterbi_gaps<NT, DT>), dim3((unsigned)a.n_utts), dim3(NT), lds, stream, a);
       });
+    });
+  });
+}
+
+int launch_ctc_viterbi_gaps_long_on(const ViterbiGapsLongArgs& a, hipStream_t stream, std::string* err) {
+  if (a.n_utts <= 0) return 0;
+  if (a.dtype < 0 || a.dtype > 3 || !a.utts || a.n_labels < 1 || a.n_labels > GAP_GROUP_MAX_LABEL + 1 || a.blank < 0 ||
+      a.blank >= a.n_labels || a.n_small < 0 || a.n_small > a.n_utts)
+    return bad_launch(err, "ctc_viterbi_gaps_long: bad arguments");
+  // (tests: every utterance at one size -- the body takes any number of threads)
+  const char* force = getenv("CTCDEC_GAPS_LONG_THREADS");
+  const int forced = force ? atoi(force) : 0;
+  const int n_small = forced == ALIGN_THREADS ? a.n_utts : forced == ALIGN_LONG_THREADS ? 0 : a.n_small;
+  return timed_launch(K_VITERBI_GAPS_LONG, stream, err, [&] {
+    for_dtype(a.dtype, [&](auto dt) {
+      constexpr int DT = decltype(dt)::value;
+      if (n_small > 0)
+        hipLaunchKernelGGL((ctc_viterbi_gaps_long<ALIGN_THREADS, DT>), dim3((unsigned)n_small), dim3(ALIGN_THREADS), 0, stream, a, 0);
+      if (a.n_utts > n_small)
+        hipLaunchKernelGGL((ctc_viterbi_gaps_long<ALIGN_LONG_THREADS, DT>), dim3((unsigned)(a.n_utts - n_small)), dim3(ALIGN_LONG_THREADS), 0,
+                           stream, a, n_small);
     });
   });
 }

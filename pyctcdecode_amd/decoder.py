@@ -1492,6 +1492,11 @@ class BeamSearchDecoderCTC:
         self.last_align_long_timing_ms = (0.0, 0.0, 0.0, 0.0)
         self.last_align_long_launches = 0
         self.last_align_long_plan: List[Tuple[int, int]] = []
+        # ... and of the last align_gaps_long / align_gaps_long_batch call (ms: classification, row_lse_max,
+        # ctc_viterbi_gaps_long, native call; launches; plan)
+        self.last_align_gaps_long_timing_ms = (0.0, 0.0, 0.0, 0.0)
+        self.last_align_gaps_long_launches = 0
+        self.last_align_gaps_long_plan: List[Tuple[int, int]] = []
         # ... and of the last decode_greedy / decode_greedy_batch call (ms: classification, row_argmax or row_lse_argmax,
         # greedy_collapse, native call; kernel launches made; the part of the row kernel's time that a kernel with a
         # log-sum-exp took: 0 without confidence=...)
@@ -2214,7 +2219,7 @@ class BeamSearchDecoderCTC:
         return out
 
     # -- alignment with gaps (no reference analogue; DESIGN.md, "Alignment with gaps") --------------------
-    def _gapped_targets(self, what: str, logits_list: Any, texts, tokens, gap: str):
+    def _gapped_targets(self, what: str, logits_list: Any, texts, tokens, gap: str, max_labels: int = ALIGN_MAX_LABELS):
         """-> (logits_list, items): the checks align_gaps_batch makes of its arguments before anything is staged -- one
         target per utterance, as a text (character alphabets) or as label ids, -1 standing for a gap; adjacent gaps merged."""
         if not isinstance(gap, str) or gap == "" or gap.split() != [gap]:
@@ -2259,9 +2264,9 @@ class BeamSearchDecoderCTC:
             n_lab = sum(1 for c in ids if c != -1)
             if n_lab == 0:
                 raise ValueError("%s: the target of utterance %d has no label: a gap alone aligns to everything" % (what, u))
-            if n_lab > ALIGN_MAX_LABELS:
+            if n_lab > max_labels:
                 raise ValueError("%s: utterance %d has %d target labels, above the limit of %d labels per utterance"
-                                 % (what, u, n_lab, ALIGN_MAX_LABELS))
+                                 % (what, u, n_lab, max_labels))
             targets.append(ids)
         return logits_list, targets
 
@@ -2285,26 +2290,43 @@ class BeamSearchDecoderCTC:
         result. ``strict`` and the feasibility bound (frames >= labels plus adjacent equal labels) are align_batch's."""
         fold = _confidence_fold(confidence)
         logits_list, targets = self._gapped_targets("align_gaps", logits_list, texts, tokens, gap)
+        out, stats = self._gapped_alignments("align_gaps", logits_list, targets, gap, fold, strict, int(_bp_budget), None)
+        if stats is not None:
+            # [classification (frame-prune kernels), row_lse_max, ctc_viterbi_gaps (HIP events), whole native call]
+            self.last_align_gaps_timing_ms, self.last_align_gaps_launches, _plan = stats
+        return out
+
+    def _gapped_alignments(self, what: str, logits_list: Any, targets: List[List[int]], gap: str, fold: int, strict: bool,
+                           bp_budget: int, segment_frames: Optional[int]):
+        """-> (the GappedAlignment of every utterance, None for one without a path; (timing ms, launches, plan) of the native
+        call, None when none was made): the checked items through ctcdec_align_gaps_batch (``segment_frames`` None) or
+        ctcdec_align_gaps_long_batch, and the words formed from the result."""
         n = len(targets)
         if n == 0:
-            return []
+            return [], None
+        budget = bp_budget or ALIGN_BP_BUDGET
         with self._call_lock:
             batch, frames, ptrs, _ = self._stage_transcript_call(logits_list)
             labels_only = [[c for c in items if c != -1] for items in targets]
-            keep = self._feasible("align_gaps", frames, labels_only, self._bp_table_bytes, int(_bp_budget) or ALIGN_BP_BUDGET, strict,
-                                  "back-pointer table", "path")
+            if segment_frames is None:
+                keep = self._feasible(what, frames, labels_only, self._bp_table_bytes, budget, strict, "back-pointer table", "path")
+            else:
+                keep = self._feasible(what, frames, labels_only, lambda T, L: self._align_long_plan(T, L, budget, segment_frames)[2],
+                                      budget, strict, "plan (segment table, checkpoints, columns)", "path")
             out: List[Optional[GappedAlignment]] = [None] * n
             if not keep:
-                return out
+                return out, None
             k_ptrs = np.ascontiguousarray(ptrs[keep])
             k_frames = np.ascontiguousarray(frames[keep])
             flat, off = self._pack_ids([targets[u] for u in keep])
             res = C.c_void_p()
             lib = self._lib
-            lib.check(lib.dll.ctcdec_align_gaps_batch(
-                self._handle, *self._c_utts(k_ptrs, k_frames),
-                len(keep), batch.dtype, int(batch.is_device), flat.ctypes.data_as(C.POINTER(C.c_int32)), B.off_ptr(off), fold,
-                int(_bp_budget), C.byref(res)))
+            head = (self._handle, *self._c_utts(k_ptrs, k_frames), len(keep), batch.dtype, int(batch.is_device),
+                    flat.ctypes.data_as(C.POINTER(C.c_int32)), B.off_ptr(off), fold, bp_budget)
+            if segment_frames is None:
+                lib.check(lib.dll.ctcdec_align_gaps_batch(*head, C.byref(res)))
+            else:
+                lib.check(lib.dll.ctcdec_align_gaps_long_batch(*head, segment_frames, C.byref(res)))
             try:
                 po, pp, ps, nu = C.POINTER(C.c_int64)(), C.POINTER(C.c_int32)(), C.POINTER(C.c_double)(), C.c_int64()
                 lib.check(lib.dll.ctcdec_alignment_paths(res, C.byref(po), C.byref(pp), C.byref(ps), C.byref(nu)))
@@ -2333,9 +2355,10 @@ class BeamSearchDecoderCTC:
                 g_logp = np.ctypeslib.as_array(gl, shape=(n_gap,)).tolist() if n_gap else []
                 ms, launches = (C.c_double * 4)(), C.c_int32()
                 lib.dll.ctcdec_alignment_timing(res, ms, C.byref(launches))
-                # [classification (frame-prune kernels), row_lse_max, ctc_viterbi_gaps (HIP events), whole native call]
-                self.last_align_gaps_timing_ms = tuple(float(v) for v in ms)
-                self.last_align_gaps_launches = int(launches.value)
+                sf, ns, npl = C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)(), C.c_int64()
+                lib.check(lib.dll.ctcdec_alignment_plan(res, C.byref(sf), C.byref(ns), C.byref(npl)))
+                plan = [(int(sf[j]), int(ns[j])) for j in range(int(npl.value))]
+                stats = (tuple(float(v) for v in ms), int(launches.value), plan)
             finally:
                 lib.dll.ctcdec_alignment_free(res)
             labels = self._labels_list
@@ -2365,7 +2388,39 @@ class BeamSearchDecoderCTC:
                 out[u] = GappedAlignment(" ".join(parts), list(items), path[path_off[j]:path_off[j + 1]].copy(), float(score[j]), tok,
                                          wf, list(zip(g_start[g0:g1], g_end[g0:g1])), g_logp[g0:g1], tlp if fold else None,
                                          wlp if fold else None)
-            return out
+            return out, stats
+
+    # -- alignment with gaps, long transcripts (no reference analogue; DESIGN.md, "Alignment with gaps, long transcripts") ----
+    def align_gaps_long(self, logits: Any, text: Optional[str] = None, tokens: Optional[Sequence[int]] = None, gap: str = "*",
+                        confidence: Optional[str] = None) -> "GappedAlignment":
+        """Alignment of one long utterance to a transcript with gaps: align_gaps_long_batch of a batch of one."""
+        if isinstance(logits, (_ResidentBeams, _DeviceStreams)):
+            raise NotImplementedError("align_gaps_long reads an utterance's matrix; the frames a stream has consumed are not kept")
+        self._check_logits_dimension(logits)
+        return self.align_gaps_long_batch([logits], None if text is None else [text], tokens=None if tokens is None else [tokens],
+                                          gap=gap, confidence=confidence)[0]
+
+    def align_gaps_long_batch(self, logits_list: Any, texts: Optional[Sequence[str]] = None,
+                              tokens: Optional[Sequence[Sequence[int]]] = None, gap: str = "*", confidence: Optional[str] = None,
+                              strict: bool = True, _bp_budget: int = 0, _segment_frames: int = 0) -> List[Optional["GappedAlignment"]]:
+        """align_gaps_batch for a lecture against a script with holes: up to 1048575 target labels per utterance (gaps do not
+        count) instead of 2047, and no back-pointer table of all frames (row_lse_max + ctc_viterbi_gaps_long,
+        csrc/ctc_align_hip.hip). Targets, the gap marker, ``strict`` and the definition of a gap are align_gaps_batch's, and
+        for every input align_gaps_batch accepts the result is that call's, bit for bit; a target without gaps gives
+        align_long_batch's result. The frames are cut as align_long_batch cuts them, under the same budget;
+        ``last_align_gaps_long_plan`` holds (segment_frames, n_segments) of every utterance aligned."""
+        if isinstance(logits_list, (_ResidentBeams, _DeviceStreams)) or (
+                isinstance(logits_list, (list, tuple)) and any(isinstance(x, (_ResidentBeams, _DeviceStreams)) for x in logits_list)):
+            raise NotImplementedError("align_gaps_long_batch reads utterances' matrices; the frames a stream has consumed are not kept")
+        fold = _confidence_fold(confidence)
+        if isinstance(_segment_frames, bool) or not isinstance(_segment_frames, (int, np.integer)) or not 0 <= int(_segment_frames) < 2 ** 31:
+            raise ValueError("align_gaps_long: _segment_frames must be an int >= 0 (0: the library plans), not %r" % (_segment_frames,))
+        logits_list, targets = self._gapped_targets("align_gaps_long", logits_list, texts, tokens, gap, ALIGN_LONG_MAX_LABELS)
+        out, stats = self._gapped_alignments("align_gaps_long", logits_list, targets, gap, fold, strict, int(_bp_budget),
+                                             int(_segment_frames))
+        if stats is not None:
+            self.last_align_gaps_long_timing_ms, self.last_align_gaps_long_launches, self.last_align_gaps_long_plan = stats
+        return out
 
     # -- greedy decode (no reference analogue; DESIGN.md, "Greedy decode") ---------------------------------
     def _greedy_call(self, logits_list: Any, fold: int):

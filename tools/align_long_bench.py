@@ -7,9 +7,13 @@ events on the decode stream (last_align_long_timing_ms), medians of 3 steps afte
             next to the balanced K
   hour      the case the call exists for: one utterance of 180000 frames x 32 labels float32 and 40000 target labels, which
             align refuses
+  gaps*     the same shapes through align_gaps_long_batch (row_lse_max + ctc_viterbi_gaps_long): gap-free targets next to
+            ctc_viterbi_long and ctc_viterbi_gaps, alternating (gaps64, gaps4096, gaps2047, gapssegments), and the hour with a
+            leading gap, a trailing gap and a gap per 500 labels next to align_long on its labels (gapshour)
 Random logits and random targets: no kernel's time depends on the values. Every leg is a process of its own under `timeout`,
 started by this one, which never opens the device; the first leg that fails ends the run.
-  python tools/align_long_bench.py [--out profiles/align_long_bench.txt] [--steps 3] [--legs short64,short4096,short2047,segments,hour]"""
+  python tools/align_long_bench.py [--out profiles/align_long_bench.txt] [--steps 3] [--legs short64,short4096,short2047,segments,hour]
+  python tools/align_long_bench.py --out profiles/align_gaps_long_bench.txt --legs gaps64,gaps4096,gaps2047,gapssegments,gapshour"""
 import argparse
 import math
 import os
@@ -22,7 +26,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-LEG_SECONDS = {"short64": 240, "short4096": 600, "short2047": 300, "segments": 240, "hour": 600}
+LEG_SECONDS = {"short64": 240, "short4096": 600, "short2047": 300, "segments": 240, "hour": 600,
+               "gaps64": 240, "gaps4096": 600, "gaps2047": 300, "gapssegments": 240, "gapshour": 600}
 DISTINCT = 256
 
 
@@ -127,7 +132,109 @@ def leg_hour(steps):
             "  native call       %10.3f ms   align_long_batch %10.3f ms" % (med(native), med(wall))]
 
 
+def alternate_calls(steps, calls):
+    """Every call of {name: f -> (kernel ms, native ms)} in turn, steps + 1 times: -> {name: ([kernel ms], [native ms])}"""
+    out = {name: ([], []) for name in calls}
+    for _ in range(steps + 1):
+        for name, f in calls.items():
+            k, nat = f()
+            out[name][0].append(k), out[name][1].append(nat)
+    return out
+
+
+def gaps_calls(dec, dev, labels, items, kw=None, short=False):
+    """align_long_batch on the labels, align_gaps_long_batch on the items and, for short targets, align_gaps_batch on them"""
+    kw = kw or {}
+    got = {}
+
+    def long():
+        got["long"] = dec.align_long_batch(dev, tokens=labels, **kw)[0]
+        return dec.last_align_long_timing_ms[2:4]
+
+    def gaps_long():
+        got["gaps_long"] = dec.align_gaps_long_batch(dev, tokens=items, **kw)[0]
+        return dec.last_align_gaps_long_timing_ms[2:4]
+
+    def gaps():
+        got["gaps"] = dec.align_gaps_batch(dev, tokens=items)[0]
+        return dec.last_align_gaps_timing_ms[2:4]
+
+    return got, dict([("long", long), ("gaps_long", gaps_long)] + ([("gaps", gaps)] if short else []))
+
+
+def leg_gaps_short(n, T, V, L, steps):
+    from pyctcdecode_amd import build_ctcdecoder
+
+    dec = build_ctcdecoder(labels_of(V))
+    dev, targets = batch(n, T, V, L, 1)
+    got, calls = gaps_calls(dec, dev, targets, targets, short=True)
+    out = alternate_calls(steps, calls)
+    assert np.array_equal(got["long"].path, got["gaps_long"].path) and got["long"].score == got["gaps_long"].score == got["gaps"].score
+    k = {name: med(v[0]) for name, v in out.items()}
+    return ["%d utterances of %d frames x %d labels float32, gap-free targets of %d labels (%d launch(es)):" % (n, T, V, L, dec.last_align_gaps_long_launches),
+            "  ctc_viterbi_long       %10.3f ms  (align_long_batch, 1024 threads)" % k["long"],
+            "  ctc_viterbi_gaps       %10.3f ms  (align_gaps_batch, states in registers)" % k["gaps"],
+            "  ctc_viterbi_gaps_long  %10.3f ms  (align_gaps_long_batch; native call %.3f ms)" % (k["gaps_long"], med(out["gaps_long"][1])),
+            "  ctc_viterbi_gaps_long / ctc_viterbi_long: %.2f   / ctc_viterbi_gaps: %.2f" % (k["gaps_long"] / k["long"], k["gaps_long"] / k["gaps"])]
+
+
+def leg_gaps_segments(steps):
+    from pyctcdecode_amd import build_ctcdecoder
+
+    T, V, L = 20000, 32, 5000
+    K = min(T, math.isqrt(32 * T - 1) + 1)  # ceil(sqrt(32 T))
+    dec = build_ctcdecoder(labels_of(V))
+    dev, targets = batch(1, T, V, L, 2)
+    lines = ["one utterance of %d frames x %d labels float32, %d target labels without gaps:" % (T, V, L)]
+    for name, kw in (("one segment", {}), ("balanced K", {"_segment_frames": K})):
+        got, calls = gaps_calls(dec, dev, targets, targets, kw)
+        out = alternate_calls(steps, calls)
+        assert np.array_equal(got["long"].path, got["gaps_long"].path) and got["long"].score == got["gaps_long"].score
+        a, b = med(out["long"][0]), med(out["gaps_long"][0])
+        lines.append("  %s  plan %-12s ctc_viterbi_long %10.3f ms  ctc_viterbi_gaps_long %10.3f ms  ratio %.2f"
+                     % (name, dec.last_align_gaps_long_plan[0], a, b, b / a))
+    return lines
+
+
+def leg_gaps_hour(steps):
+    from pyctcdecode_amd import build_ctcdecoder
+
+    T, V, L = 180000, 32, 40000
+    dec = build_ctcdecoder(labels_of(V))
+    dev, targets = batch(1, T, V, L, 3)
+    items = [-1]
+    for k, c in enumerate(targets[0]):
+        items += [c, -1] if (k + 1) % 500 == 0 else [c]
+    items = items if items[-1] == -1 else items + [-1]
+    try:
+        dec.align_gaps_batch(dev, tokens=[items])
+        refusal = "align_gaps_batch accepted it"
+    except ValueError as e:
+        refusal = "align_gaps_batch: ValueError: %s" % e
+    got, calls = gaps_calls(dec, dev, targets, [items])
+    out = alternate_calls(steps, calls)
+    a, b = med(out["long"][0]), med(out["gaps_long"][0])
+    K, n = dec.last_align_gaps_long_plan[0]
+    g = got["gaps_long"]
+    assert len(g.path) == T and len(g.gaps) == items.count(-1) and g.score >= got["long"].score
+    return ["one utterance of %d frames x %d labels float32, %d target labels, %d gaps (leading, trailing, one per 500 labels):" % (T, V, L, len(g.gaps)),
+            "  %s" % refusal,
+            "  plan: %d segments of %d frames, %d bytes" % (n, K, dec._align_long_plan(T, L, 1 << 30, 0)[2]),
+            "  ctc_viterbi_long       %10.3f ms  (align_long_batch on the labels: %.2f us per frame and pass)" % (a, a * 1e3 / (2 * T)),
+            "  ctc_viterbi_gaps_long  %10.3f ms  (%.2f us per frame and pass; native call %.3f ms; %d frames in gaps)"
+            % (b, b * 1e3 / (2 * T), med(out["gaps_long"][1]), int((g.path == -1).sum())),
+            "  ctc_viterbi_gaps_long / ctc_viterbi_long: %.2f" % (b / a)]
+
+
 def run_leg(leg, steps):
+    if leg in ("gaps64", "gaps4096"):
+        return leg_gaps_short(int(leg[4:]), 1000, 1024, 408, steps)
+    if leg == "gaps2047":
+        return leg_gaps_short(256, 2100, 1024, 2047, steps)
+    if leg == "gapssegments":
+        return leg_gaps_segments(steps)
+    if leg == "gapshour":
+        return leg_gaps_hour(steps)
     if leg == "short64":
         return leg_short(64, 1000, 1024, 408, steps)
     if leg == "short4096":
