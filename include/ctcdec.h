@@ -505,6 +505,31 @@ int ctcdec_score_batch(ctcdec_decoder* dec, const void* const* utt_logits, const
                        int32_t dtype, int32_t is_device, const int32_t* targets, const int64_t* target_off,
                        const int64_t* hyp_off, int32_t kernel, double* logp_out, double* ms4, int64_t* launched2);
 
+/* ---- transcript likelihood of long transcripts: ctcdec_score_batch for a lecture against its script -------------------
+ * Arguments, hypotheses, the probabilities-or-logits rule, the -inf rule, the empty hypothesis and logp_out are those of
+ * ctcdec_score_batch, with up to 1048575 labels per hypothesis (2 L + 1 states below 2^21). For every input
+ * ctcdec_score_batch accepts, logp_out holds the same bits, and the same bits whatever the tile shape, alone or in a batch,
+ * from host or device memory: the states, the reachable window, the operands and their order are ctc_forward's.
+ * The kernel, ctc_forward_tile: the groups of four states of a hypothesis are cut into state blocks of tile_groups groups
+ * (0: 256, the most), its frames into time blocks of tile_frames frames (0: all of them when there is one state block, else
+ * 64, fewer where the budget asks for it). Tile (i, j) takes state block i through time block j in one workgroup; it needs
+ * what the tiles (i, j - 1), (i - 1, j) and (i - 1, j - 1) left, so the tiles with i + j = d are independent of each other
+ * and one launch takes diagonal d of every hypothesis. The launches follow each other on the decode stream; nothing else
+ * orders them. A tile none of whose states is reachable in any of its frames is not launched.
+ * budget: the bytes of the columns (32 per group) and edge rows (24 tile_frames per boundary between state blocks) of one
+ * launch group; 0: 1 GiB. A batch above it is cut into launch groups; one hypothesis above it is CTCDEC_ERR_LIMIT.
+ * ms4 (may be NULL): milliseconds of [0] the classification, [1] row_lse, [2] the fill and the tile launches (HIP events on
+ * the decode stream), [3] the whole native call. counts5 (may be NULL): [0] diagonals launched, [1] tiles in them, [2] launch
+ * groups, [3] hypotheses launched, [4] the most tiles one diagonal held. plan5 (may be NULL; room for 5 per hypothesis): for each launched hypothesis, in input
+ * order, tile_groups, tile_frames, state blocks, time blocks and bytes.
+ * Everything is validated before anything is launched, as in ctcdec_score_batch; also CTCDEC_ERR_ARG: a negative budget or
+ * tile_frames, tile_groups outside [0, 256]. CTCDEC_ERR_LIMIT names the utterance and the hypothesis. decoder.py:
+ * score_long / score_long_batch. */
+int ctcdec_score_long_batch(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts,
+                            int32_t dtype, int32_t is_device, const int32_t* targets, const int64_t* target_off,
+                            const int64_t* hyp_off, int64_t budget, int32_t tile_groups, int32_t tile_frames, double* logp_out,
+                            double* ms4, int64_t* counts5, int64_t* plan5);
+
 /* ---- prefix scores: how probable it is that the transcript STARTS with a label sequence followed by label c, for every c ---
  * No reference analogue: the CTC prefix score an external decoder asks for at every step (joint CTC / attention decoding,
  * rescoring another model's next-token distribution, constrained decoding). Utterance u owns the prefixes

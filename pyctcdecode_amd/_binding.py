@@ -191,6 +191,10 @@ _PROTOS = {
     "ctcdec_score_batch": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32,
                                      C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32,
                                      C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
+    "ctcdec_score_long_batch": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32,
+                                          C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int64, C.c_int32,
+                                          C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64),
+                                          C.POINTER(C.c_int64)]),
     "ctcdec_posteriors_batch": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32,
                                           C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int32, C.c_int64, C.POINTER(_VP)]),
     "ctcdec_posteriors_scores": (C.c_int, [_VP, C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.POINTER(C.c_double)),

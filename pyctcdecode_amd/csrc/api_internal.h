@@ -187,6 +187,9 @@ struct ctcdec_decoder {
   DevBuf w_lcol, w_lckpt, w_lutts;
   // transcript likelihood (ctcdec_score_batch): the hypothesis records of a launch (labels: w_alab, scores: w_ascore)
   DevBuf w_fhyps;
+  // transcript likelihood of long transcripts (ctcdec_score_long_batch): a launch group's hypothesis records and tile records
+  // (columns and edge rows: w_lcol; labels: w_alab; scores: w_ascore)
+  DevBuf w_sthyps, w_stiles;
   // frame posteriors (ctcdec_posteriors_batch): a launch's tables and utterance records, the token sums (labels: w_alab,
   // score pairs: w_ascore)
   DevBuf w_ptab, w_putts, w_pocc;

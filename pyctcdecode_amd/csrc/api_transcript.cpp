@@ -903,7 +903,7 @@ void ctcdec_greedy_free(ctcdec_greedy* g) { delete g; }
 // phrases with it too: `item` is what a message calls an entry.)
 static int check_scores(const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts, const int32_t* targets,
                         const int64_t* target_off, const int64_t* hyp_off, const TranscriptCall& tc, std::vector<int32_t>& need,
-                        const char* item = "hypothesis") {
+                        const char* item = "hypothesis", int32_t max_labels = ALIGN_MAX_LABELS) {
   if (hyp_off[0] != 0) return fail(CTCDEC_ERR_ARG, "hyp_off must start at 0");
   for (int32_t u = 0; u < n_utts; ++u) {
     if (hyp_off[u + 1] < hyp_off[u]) return fail(CTCDEC_ERR_ARG, "hyp_off must not decrease");
@@ -918,8 +918,8 @@ static int check_scores(const void* const* utt_logits, const int32_t* utt_frames
       const std::string who = "utterance " + std::to_string(u) + ", " + item + " " + std::to_string(h - hyp_off[u]);
       const int64_t L = target_off[h + 1] - target_off[h];
       if (L < 0) return fail(CTCDEC_ERR_ARG, "target_off must not decrease");
-      if (L > ALIGN_MAX_LABELS)
-        return fail(CTCDEC_ERR_LIMIT, who + ": " + std::to_string(L) + " labels, above the limit of " + std::to_string(ALIGN_MAX_LABELS));
+      if (L > max_labels)
+        return fail(CTCDEC_ERR_LIMIT, who + ": " + std::to_string(L) + " labels, above the limit of " + std::to_string(max_labels));
       if (L > 0 && !targets) return fail(CTCDEC_ERR_ARG, "no targets");
       int64_t nd = 0;
       if (int rc = check_labels(targets + target_off[h], L, tc.V, tc.blank, [&] { return who; }, "label", "label to score", nd)) return rc;
@@ -1123,28 +1123,121 @@ int PrefixExtend::launch() {
 #endif
   return CTCDEC_OK;
 }
-}  // namespace
+// ---- the tiles of ctcdec_score_long_batch ("Transcript likelihood of long transcripts") ------------------------
+#ifdef CTC_SIM
+struct TileSeqCtx {  // (ctc_forward_tile_body: the one thread owns every group of a state block)
+  enum { GROUPS = FORWARD_TILE_MAX_GROUPS };
+  int tid = 0, nt = 1;
+  void sync() {}
+};
+#endif
 
-extern "C" {
+// What ctcdec_score_long_batch adds to a score call: its options, the plan of every hypothesis that is launched (bytes 0: not
+// launched) and, out, what the call did
+struct ScoreLong {
+  int64_t budget = 0;
+  int32_t tile_groups = 0, tile_frames = 0;
+  std::vector<ScoreLongPlan> plans;          // [hypotheses]
+  int64_t launches = 0, tiles = 0, groups = 0, widest = 0;  // diagonals launched, tiles in them, launch groups, most tiles in a diagonal
+};
 
-int ctcdec_score_batch(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts, int32_t dtype,
-                       int32_t is_device, const int32_t* targets, const int64_t* target_off, const int64_t* hyp_off, int32_t kernel,
-                       double* logp_out, double* ms4, int64_t* launched2) {
-  TranscriptCall tc;
-  const bool args_ok = dec && n_utts >= 0 && target_off && hyp_off && (n_utts == 0 || (utt_logits && utt_frames));
-  if (int rc = transcript_open(dec, args_ok, dtype, bad_kernel(kernel), tc)) return rc;
-  std::vector<int32_t> need;
-  if (int rc = check_scores(utt_logits, utt_frames, n_utts, targets, target_off, hyp_off, tc, need)) return rc;
+// forward_pass by ctc_forward_tile, for the items `run` in input order: launch groups of hypotheses whose columns and edge
+// rows fill the budget (w_lcol); per group the hypothesis records, and the records of every live tile sorted by diagonal, go
+// over once, then the fill and one launch per diagonal are queued with nothing between them.
+static int forward_tile_pass(ctcdec_decoder* dec, const TranscriptCall& tc, int32_t dtype, const std::vector<UttRows>& utts,
+                             const std::vector<int32_t>& utt_of, const int64_t* label_off, const std::vector<int32_t>& run, ScoreLong& sl) {
+  std::string err;
+  std::vector<std::vector<int32_t>> groups;
+  const int64_t most = budget_groups((int32_t)run.size(), [&](int32_t k) { return sl.plans[(size_t)run[(size_t)k]].bytes; }, sl.budget, groups);
+  if (dec->w_lcol.ensure((size_t)std::max<int64_t>(most, 8), &err)) return fail(CTCDEC_ERR_DEVICE, err);
+  std::vector<ForwardTileHyp> hyps;
+  std::vector<ForwardTile> tiles;
+  std::vector<int32_t> diag_off, at;
+  for (const auto& g : groups) {
+    hyps.clear();
+    int64_t doubles = 0;
+    int32_t n_diags = 0;
+    for (int32_t k : g) {
+      const int32_t h = run[(size_t)k];
+      const UttRows& u = utts[(size_t)utt_of[(size_t)h]];
+      const ScoreLongPlan& pl = sl.plans[(size_t)h];
+      ForwardTileHyp a;
+      a.x = u.x;
+      a.lse = u.lse;
+      a.lab = (const int32_t*)dec->w_alab.p + label_off[h];
+      a.logp = (double*)dec->w_ascore.p + h;
+      a.T = u.T;
+      a.L = (int32_t)(label_off[h + 1] - label_off[h]);
+      a.col = (double*)dec->w_lcol.p + doubles;
+      a.edge = a.col + 4 * (int64_t)align_chunks(a.L);
+      a.is_prob = u.is_prob;
+      a.GB = pl.GB, a.FB = pl.FB, a.pad = 0;
+      hyps.push_back(a);
+      doubles += pl.bytes / 8;
+      n_diags = std::max(n_diags, pl.nI + pl.nJ - 1);
+    }
+    // the live tiles by diagonal: counted, then placed; a diagonal without one takes no launch
+    const auto each_live = [&](auto f) {
+      for (size_t r = 0; r < hyps.size(); ++r) {
+        const ScoreLongPlan& pl = sl.plans[(size_t)run[(size_t)g[r]]];
+        for (int32_t j = 0; j < pl.nJ; ++j)
+          for (int32_t i = 0; i < pl.nI; ++i)
+            if (forward_tile_live(hyps[r].T, hyps[r].L, pl.GB, pl.FB, i, j)) f((int32_t)r, i, j);
+      }
+    };
+    std::vector<int32_t> count((size_t)n_diags, 0);
+    each_live([&](int32_t, int32_t i, int32_t j) { ++count[(size_t)(i + j)]; });
+    at.assign((size_t)n_diags, 0);
+    diag_off.assign(1, 0);
+    for (int32_t d = 0; d < n_diags; ++d) {
+      at[(size_t)d] = diag_off.back();
+      if (count[(size_t)d]) diag_off.push_back(diag_off.back() + count[(size_t)d]);
+      sl.widest = std::max<int64_t>(sl.widest, count[(size_t)d]);
+    }
+    tiles.assign((size_t)diag_off.back(), ForwardTile());
+    each_live([&](int32_t r, int32_t i, int32_t j) { tiles[(size_t)at[(size_t)(i + j)]++] = ForwardTile{r, i, j, 0}; });
+    sl.launches += (int64_t)diag_off.size() - 1;
+    sl.tiles += (int64_t)tiles.size();
+    ++sl.groups;
+#ifdef CTC_SIM
+    std::fill((double*)dec->w_lcol.p, (double*)dec->w_lcol.p + doubles, align_neg_inf());
+    std::vector<double> lds((size_t)2 * FORWARD_TILE_MAX_GROUPS);
+    TileSeqCtx cx;
+    for (const ForwardTile& t : tiles)
+      for_dtype(dtype, [&](auto dt) {
+        ctc_forward_tile_body<decltype(dt)::value>(cx, hyps[(size_t)t.hyp], t.i, t.j, tc.V, tc.blank, tc.clip_lo, lds.data());
+      });
+#else
+    if (upload(dec->w_sthyps, hyps, &err) || upload(dec->w_stiles, tiles, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+    be::ForwardTileArgs ta;
+    ta.hyps = (const ForwardTileHyp*)dec->w_sthyps.p;
+    ta.tiles = (const ForwardTile*)dec->w_stiles.p;
+    ta.diag_off = diag_off.data();
+    ta.fill = (double*)dec->w_lcol.p;
+    ta.n_fill = doubles;
+    ta.n_diags = (int32_t)diag_off.size() - 1;
+    ta.n_labels = tc.V;
+    ta.dtype = dtype;
+    ta.blank = tc.blank;
+    ta.clip_lo = tc.clip_lo;
+    if (be::launch_ctc_forward_tile(ta, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+#endif
+  }
+  return CTCDEC_OK;
+}
+
+// The call behind ctcdec_score_batch (sl null) and ctcdec_score_long_batch, its arguments checked: the scores decided on the
+// host, the front, the forward pass of everything else -- ctc_forward / ctc_forward_wave, or ctc_forward_tile --, the scores
+// back. tms: [0] .. [2] of the entry's ms4; launched: hypotheses by [0] the wave kernel, [1] every other.
+static int score_call(ctcdec_decoder* dec, const TranscriptCall& tc, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts,
+                      int32_t dtype, int32_t is_device, const int32_t* targets, const int64_t* target_off, const int64_t* hyp_off,
+                      const std::vector<int32_t>& need, int32_t kernel, ScoreLong* sl, double* logp_out, double* tms, int64_t* launched) {
   const size_t n = (size_t)n_utts;
   const int64_t NH = hyp_off[n];
-  if (NH > 0 && !logp_out) return fail(CTCDEC_ERR_ARG, "no room for the scores");
-  const auto t_begin = Clock::now();
-  double tms[4] = {0, 0, 0, 0};
-  int64_t launched[2] = {0, 0};
   // A hypothesis with fewer frames than labels plus adjacent equal labels has no alignment: probability 0, decided here.
   // The empty one without frames has the one empty alignment. Everything else goes to a kernel: the wave kernel up to its
-  // limit (unless the group kernel is forced), the group kernel above it.
-  Routed r = route_items(hyp_off, target_off, utt_frames, n_utts, need, kernel == 2 ? -1 : FORWARD_WAVE_MAX_LABELS);
+  // limit (unless the group kernel is forced), the group kernel above it; the tiles take all of them.
+  Routed r = route_items(hyp_off, target_off, utt_frames, n_utts, need, sl || kernel == 2 ? -1 : FORWARD_WAVE_MAX_LABELS);
   for (int64_t h = 0; h < NH; ++h) {
     const int32_t T = utt_frames[r.utt_of[(size_t)h]];
     if (T < need[(size_t)h]) logp_out[h] = align_neg_inf();
@@ -1161,21 +1254,92 @@ int ctcdec_score_batch(ctcdec_decoder* dec, const void* const* utt_logits, const
       return fail(CTCDEC_ERR_DEVICE, err);
     if ((NL && be::h2d(dec->w_alab.p, targets, (size_t)NL * 4, &err)) || be::zero(dec->w_ascore.p, (size_t)NH * 8, &err))
       return fail(CTCDEC_ERR_DEVICE, err);
-    if (int rc = forward_pass(dec, tc, dtype, utt_rows(fr, row0, utt_frames), r.utt_of, target_off, r.run, nullptr)) return rc;
     for (int w = 0; w < 2; ++w) launched[w] = (int64_t)r.run[w].size();
+    const std::vector<UttRows> utts = utt_rows(fr, row0, utt_frames);
+    if (int rc = sl ? forward_tile_pass(dec, tc, dtype, utts, r.utt_of, target_off, r.run[1], *sl)
+                    : forward_pass(dec, tc, dtype, utts, r.utt_of, target_off, r.run, nullptr))
+      return rc;
     std::vector<double> got((size_t)NH);
     if (be::d2h(got.data(), dec->w_ascore.p, (size_t)NH * 8, &err)) return fail(CTCDEC_ERR_DEVICE, err);
     for (int w = 0; w < 2; ++w)
       for (int32_t h : r.run[w]) logp_out[h] = got[(size_t)h];
 #ifndef CTC_SIM
     tms[1] = be::align_kernel_ms(be::K_ROW_LSE);
-    tms[2] = be::align_kernel_ms(be::K_FORWARD);
+    tms[2] = be::align_kernel_ms(sl ? be::K_FORWARD_TILE : be::K_FORWARD);
 #endif
   }
+  return CTCDEC_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int ctcdec_score_batch(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts, int32_t dtype,
+                       int32_t is_device, const int32_t* targets, const int64_t* target_off, const int64_t* hyp_off, int32_t kernel,
+                       double* logp_out, double* ms4, int64_t* launched2) {
+  TranscriptCall tc;
+  const bool args_ok = dec && n_utts >= 0 && target_off && hyp_off && (n_utts == 0 || (utt_logits && utt_frames));
+  if (int rc = transcript_open(dec, args_ok, dtype, bad_kernel(kernel), tc)) return rc;
+  std::vector<int32_t> need;
+  if (int rc = check_scores(utt_logits, utt_frames, n_utts, targets, target_off, hyp_off, tc, need)) return rc;
+  if (hyp_off[n_utts] > 0 && !logp_out) return fail(CTCDEC_ERR_ARG, "no room for the scores");
+  const auto t_begin = Clock::now();
+  double tms[4] = {0, 0, 0, 0};
+  int64_t launched[2] = {0, 0};
+  if (int rc = score_call(dec, tc, utt_logits, utt_frames, n_utts, dtype, is_device, targets, target_off, hyp_off, need, kernel, nullptr,
+                          logp_out, tms, launched))
+    return rc;
   tms[3] = ms(t_begin, Clock::now());
   if (ms4)
     for (int k = 0; k < 4; ++k) ms4[k] = tms[k];
   if (launched2) launched2[0] = launched[0], launched2[1] = launched[1];
+  return CTCDEC_OK;
+}
+
+// ---- transcript likelihood of long transcripts ("Transcript likelihood of long transcripts") -------------------
+int ctcdec_score_long_batch(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts, int32_t dtype,
+                            int32_t is_device, const int32_t* targets, const int64_t* target_off, const int64_t* hyp_off, int64_t budget,
+                            int32_t tile_groups, int32_t tile_frames, double* logp_out, double* ms4, int64_t* counts5, int64_t* plan5) {
+  TranscriptCall tc;
+  const bool args_ok = dec && n_utts >= 0 && target_off && hyp_off && budget >= 0 && (n_utts == 0 || (utt_logits && utt_frames));
+  const std::string bad_option = tile_groups < 0 || tile_groups > FORWARD_TILE_MAX_GROUPS
+                                     ? "tile_groups must be 0 (the library chooses) to " + std::to_string(FORWARD_TILE_MAX_GROUPS)
+                                     : tile_frames < 0 ? "tile_frames must not be negative" : "";
+  if (int rc = transcript_open(dec, args_ok, dtype, bad_option, tc)) return rc;
+  std::vector<int32_t> need;
+  if (int rc = check_scores(utt_logits, utt_frames, n_utts, targets, target_off, hyp_off, tc, need, "hypothesis", ALIGN_LONG_MAX_LABELS))
+    return rc;
+  const int64_t NH = hyp_off[n_utts];
+  if (NH > 0 && !logp_out) return fail(CTCDEC_ERR_ARG, "no room for the scores");
+  ScoreLong sl;
+  sl.budget = budget ? budget : ALIGN_BP_BUDGET;
+  sl.tile_groups = tile_groups, sl.tile_frames = tile_frames;
+  sl.plans.assign((size_t)NH, ScoreLongPlan());
+  for (int32_t u = 0; u < n_utts; ++u)
+    for (int64_t h = hyp_off[u]; h < hyp_off[u + 1]; ++h) {
+      if (utt_frames[u] == 0 || utt_frames[u] < need[(size_t)h]) continue;  // (decided on the host: nothing is launched for it)
+      ScoreLongPlan& pl = sl.plans[(size_t)h];
+      pl = score_long_plan(utt_frames[u], (int32_t)(target_off[h + 1] - target_off[h]), sl.budget, tile_groups, tile_frames);
+      if (pl.bytes > sl.budget)
+        return fail(CTCDEC_ERR_LIMIT, "utterance " + std::to_string(u) + ", hypothesis " + std::to_string(h - hyp_off[u]) +
+                                          ": a column and edge rows of " + std::to_string(pl.bytes) + " bytes, above the budget of " +
+                                          std::to_string(sl.budget) + " bytes for one launch");
+    }
+  const auto t_begin = Clock::now();
+  double tms[4] = {0, 0, 0, 0};
+  int64_t launched[2] = {0, 0};
+  if (int rc = score_call(dec, tc, utt_logits, utt_frames, n_utts, dtype, is_device, targets, target_off, hyp_off, need, 2, &sl, logp_out,
+                          tms, launched))
+    return rc;
+  tms[3] = ms(t_begin, Clock::now());
+  if (ms4)
+    for (int k = 0; k < 4; ++k) ms4[k] = tms[k];
+  if (counts5) counts5[0] = sl.launches, counts5[1] = sl.tiles, counts5[2] = sl.groups, counts5[3] = launched[1], counts5[4] = sl.widest;
+  if (plan5) {
+    int64_t* row = plan5;
+    for (const ScoreLongPlan& pl : sl.plans)
+      if (pl.bytes > 0) row[0] = pl.GB, row[1] = pl.FB, row[2] = pl.nI, row[3] = pl.nJ, row[4] = pl.bytes, row += 5;
+  }
   return CTCDEC_OK;
 }
 

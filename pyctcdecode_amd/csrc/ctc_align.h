@@ -819,6 +819,224 @@ CTC_HD void ctc_forward_wave_hyp(Ctx& cx, const ForwardHyp& hyp, int V, int blan
   }
 }
 
+// ---- ctc_forward_tile ----------------------------------------------------------------------------------------------------------
+// ctc_forward's likelihood for targets whose groups do not fit one workgroup ("Transcript likelihood of long
+// transcripts"): the same states, window, operands and order of operations, so the same bits, whatever the tile shape. The
+// groups of a hypothesis are cut into state blocks of GB consecutive groups, its frames into time blocks of FB frames; tile
+// (i, j) takes state block i through time block j. It needs the column of block i after time block j - 1, which tile
+// (i, j - 1) left in `col`, and, for every frame t of its own, the last state of block i - 1 at frame t - 1, which the tiles
+// (i - 1, j) and, for its first frame, (i - 1, j - 1) left in block i - 1's edge row. All tiles with i + j = d are independent:
+// one launch per diagonal d, in stream order; no workgroup waits for another.
+// An edge row is a ring of FORWARD_TILE_RING time blocks: on diagonal d the reader of time block j also reads the last frame
+// of block j - 1, while tile (i - 1, j + 1) writes block j + 1.
+constexpr int32_t FORWARD_TILE_MAX_GROUPS = 256;  // GB at most: a group per thread of the tile's workgroup
+constexpr int32_t FORWARD_TILE_RING = 3;
+constexpr int32_t FORWARD_TILE_FRAMES = 64;       // FB when the caller names none and there is more than one state block: the
+                                                  // fastest of 64 .. 1024 on the hour shape (profiles/score_long_bench.txt)
+
+// One hypothesis of a ctc_forward_tile call, validated by the host as a ForwardHyp is. col and edge are the hypothesis' own.
+struct ForwardTileHyp {
+  const void* x;       // [T, V] logits or probabilities of the hypothesis' utterance, of the launch's dtype
+  const double* lse;   // [T] log-sum-exp of each row (not read when is_prob)
+  const int32_t* lab;  // [L] the labels scored
+  double* logp;        // [1] out
+  double* col;         // [4 * align_chunks(L)] every group's four states after the last frame a tile took it through; -inf before
+  double* edge;        // [(state blocks - 1) * FORWARD_TILE_RING * FB] block b's last state, frame t at ring slot (t / FB) % 3
+  int32_t T, L, is_prob, GB, FB, pad;
+};
+// One tile of a launch: state block i, time block j of hypothesis hyp
+struct ForwardTile {
+  int32_t hyp, i, j, pad;
+};
+
+// How a hypothesis is cut: a pure function of (T, L, budget, tile_groups, tile_frames); decoder.py's _score_long_plan is the
+// same rule. tile_groups 0: FORWARD_TILE_MAX_GROUPS. tile_frames 0: all frames when there is one state block (one tile, one
+// launch), else FORWARD_TILE_FRAMES, or as many fewer as keep the bytes under the budget (one at least).
+struct ScoreLongPlan {
+  int32_t GB = 0, FB = 0, nI = 0, nJ = 0;
+  int64_t bytes = 0;  // the column and the edge rows
+};
+CTC_HD ScoreLongPlan score_long_plan(int32_t T, int32_t L, int64_t budget, int32_t tile_groups, int32_t tile_frames) {
+  ScoreLongPlan p;
+  if (T <= 0) return p;
+  const int64_t nch = align_chunks(L);
+  p.GB = tile_groups > 0 ? tile_groups : FORWARD_TILE_MAX_GROUPS;
+  p.nI = (int32_t)((nch + p.GB - 1) / p.GB);
+  const int64_t rows = (int64_t)FORWARD_TILE_RING * (p.nI - 1);  // doubles of edge rows per frame of a time block
+  int64_t FB = tile_frames > 0 ? tile_frames : p.nI == 1 ? T : FORWARD_TILE_FRAMES;
+  if (tile_frames <= 0 && rows > 0 && 8 * (4 * nch + rows * FB) > budget) FB = (budget / 8 - 4 * nch) / rows;
+  FB = FB < 1 ? 1 : FB > T ? T : FB;
+  p.FB = (int32_t)FB;
+  p.nJ = (int32_t)((T + FB - 1) / FB);
+  p.bytes = 8 * (4 * nch + rows * FB);
+  return p;
+}
+
+// forward_window's bounds without 2 * t or 2 * (T - 1 - t), which leave int32 above 2^30 frames: the same values
+CTC_HD void forward_tile_window(int t, int T, int L, int* clo, int* chi) {
+  const int rest = T - 1 - t;
+  *clo = rest < L ? (2 * (L - rest) - 1) >> 2 : 0;
+  *chi = (t < L ? 2 * t + 1 : 2 * L) >> 2;
+}
+// Whether any (group, frame) cell of tile (i, j) lies in its frame's window: a tile without one is not launched. Both bounds
+// of the window rise with t, so the first frame at which the window reaches up to the block decides. The tile that writes the
+// result always runs: with as many frames as labels the last blank is never reached, and its group is in no window.
+CTC_HD bool forward_tile_live(int32_t T, int32_t L, int32_t GB, int32_t FB, int32_t i, int32_t j) {
+  const int64_t nch = align_chunks(L), g0 = (int64_t)i * GB, g1 = (g0 + GB < nch ? g0 + GB : nch) - 1;
+  const int64_t t0 = (int64_t)j * FB, t1 = (t0 + FB < T ? t0 + FB : T) - 1;
+  if (t1 == T - 1 && g1 == nch - 1) return true;
+  const int64_t tb = t0 > 2 * g0 ? t0 : 2 * g0;  // chi(t) >= g0 from t = 2 g0 on
+  if (tb > t1) return false;
+  int clo, chi;
+  forward_tile_window((int)tb, T, L, &clo, &chi);
+  return clo <= g1;
+}
+
+// Tile (bi, bj) of a hypothesis of a matrix of dtype DT, by the threads of cx (tid, nt, sync(); Ctx::GROUPS * nt >= GB): thread
+// tid owns group bi * GB + tid (+ k * nt) for the tile's frames. The group's labels and skip flags are read once, its four
+// states are loaded from `col` at entry, stay in registers and are stored at exit. A group's last state goes to the thread
+// above through `lds` (2 * FORWARD_TILE_MAX_GROUPS doubles, the columns of two successive frames), one barrier per frame; the
+// block's first group takes it from the edge row of the block below, the block's last group writes it to the block's own.
+// The entries, the row's log-sum-exp and that edge value are requested one frame ahead, as in ctc_forward_hyp.
+// A reader of a neighbour's state applies both bounds of the frame before: below its window the state is unreachable from the
+// end, above it the state has never been reached -- and a tile wholly above the window never ran, so that its edge row holds
+// nothing of this call there.
+template <int DT, class Ctx>
+CTC_HD void ctc_forward_tile_body(Ctx& cx, const ForwardTileHyp& hyp, int bi, int bj, int V, int blank, double clip_lo, double* lds) {
+  typedef typename AlignRaw<DT>::type Raw;
+  constexpr int G = Ctx::GROUPS, W = FORWARD_TILE_MAX_GROUPS;
+  const void* const x = hyp.x;  // (the record, once: the loop below reads none of it again)
+  const double* const lse = hyp.lse;
+  const int32_t* const lab = hyp.lab;
+  const int T = hyp.T, L = hyp.L, GB = hyp.GB, FB = hyp.FB;
+  const bool is_prob = hyp.is_prob != 0;
+  const int S = 2 * L + 1, nch = align_chunks(L);
+  const double NEG = align_neg_inf();
+  const int c0 = bi * GB, gb = nch - c0 < GB ? nch - c0 : GB;  // the block's first group, and how many it has
+  const int t0 = bj * FB, t1 = (T - t0 < FB ? T : t0 + FB) - 1;  // the tile's frames, both included
+  const int ts = t0 > 0 ? t0 : 1;                                // the first frame of the recursion here
+  // ring slots: frame t of this time block at slot_j + (t - t0), the last frame of the block before at slot_m
+  const size_t ring = (size_t)FORWARD_TILE_RING * (size_t)FB;
+  const int slot_j = (bj % FORWARD_TILE_RING) * FB, slot_m = ((bj + FORWARD_TILE_RING - 1) % FORWARD_TILE_RING) * FB + FB - 1;
+  const double* const edge_in = bi > 0 ? hyp.edge + (size_t)(bi - 1) * ring : nullptr;
+  double* const edge_out = c0 + gb < nch ? hyp.edge + (size_t)bi * ring : nullptr;
+  ForwardGroup g[G];
+  int i0[G], i1[G];  // the columns a group's two labels read (the blank's where the target ends before them)
+  double p[G][4];    // states
+  Raw v0[G], v1[G];  // the entries of the frame in hand at those columns, as loaded
+  CTC_UNROLL
+  for (int k = 0; k < G; ++k) {
+    const int lc = cx.tid + k * cx.nt;
+    if (lc < gb) {
+      g[k] = forward_group(lab, L, c0 + lc);
+      const double* at = hyp.col + 4 * (size_t)(c0 + lc);
+      p[k][0] = at[0], p[k][1] = at[1], p[k][2] = at[2], p[k][3] = at[3];
+    } else {
+      g[k] = ForwardGroup{-1, -1, false, false, false};
+      p[k][0] = p[k][1] = p[k][2] = p[k][3] = NEG;
+    }
+    i0[k] = g[k].l0 >= 0 ? g[k].l0 : blank;
+    i1[k] = g[k].l1 >= 0 ? g[k].l1 : blank;
+  }
+  // (always 0, but per thread as far as the compiler knows: see ctc_forward_hyp)
+  const int per_thread_zero = g[0].l0 == -2 ? 1 : 0;
+  const double* const lse_v = lse + per_thread_zero;
+  if (bi == 0 && bj == 0 && cx.tid == 0) {  // frame 0, by this tile alone
+    const double lse0 = is_prob ? 0.0 : lse[0];
+    p[0][0] = align_emit(x, DT, (size_t)blank, lse0, is_prob, clip_lo);
+    if (L > 0) p[0][1] = align_emit(x, DT, (size_t)lab[0], lse0, is_prob, clip_lo);
+  }
+  // the column of the frame before the first step, as the tile before left it
+  CTC_UNROLL
+  for (int k = 0; k < G; ++k) {
+    const int lc = cx.tid + k * cx.nt;
+    if (lc >= gb) break;
+    lds[((ts - 1) & 1) * W + lc] = p[k][3];
+    if (t0 == 0 && edge_out && lc == gb - 1) edge_out[slot_j] = p[k][3];
+  }
+  cx.sync();
+  // the first step's entries (a tile of frame 0 alone: that frame's again, never used)
+  const bool first_reads_edge = cx.tid == 0 && edge_in != nullptr;
+  const int tf = ts <= t1 ? ts : t1;
+  int clo = 0, chi = -1, clo_prev, chi_prev;
+  forward_tile_window(ts - 1, T, L, &clo_prev, &chi_prev);
+  if (ts <= t1) forward_tile_window(ts, T, L, &clo, &chi);
+  const size_t rowf = (size_t)tf * (size_t)V;
+  Raw vb = align_load_raw<DT>(x, rowf + (size_t)blank);
+  double lse_t = lse_v[tf];
+  double below = first_reads_edge ? edge_in[ts - 1 >= t0 ? slot_j + (ts - 1 - t0) : slot_m] : NEG;
+  CTC_UNROLL
+  for (int k = 0; k < G; ++k) {
+    v0[k] = align_load_raw<DT>(x, rowf + (size_t)i0[k]);
+    v1[k] = align_load_raw<DT>(x, rowf + (size_t)i1[k]);
+  }
+  for (int t = ts; t <= t1; ++t) {
+    const double* prev = lds + ((t - 1) & 1) * W;
+    double* cur = lds + (t & 1) * W;
+    // the neighbours' states first
+    double pm1[G];
+    CTC_UNROLL
+    for (int k = 0; k < G; ++k) {
+      const int lc = cx.tid + k * cx.nt, c = c0 + lc;
+      if (lc >= gb) break;
+      const bool take = c >= clo && c <= chi && c > 0 && c - 1 >= clo_prev && c - 1 <= chi_prev;
+      pm1[k] = take ? (lc > 0 ? prev[lc - 1] : below) : NEG;
+    }
+    // then ask for frame t + 1 (after the tile's last frame: that frame again)
+    const int tn = t + 1 <= t1 ? t + 1 : t;
+    int nlo = 0, nhi = -1;
+    if (t + 1 <= t1) forward_tile_window(tn, T, L, &nlo, &nhi);
+    const size_t row = (size_t)tn * (size_t)V;
+    const Raw nvb = align_load_raw<DT>(x, row + (size_t)blank);
+    const double nlse = lse_v[tn];
+    const double nbelow = first_reads_edge ? edge_in[tn - 1 >= t0 ? slot_j + (tn - 1 - t0) : slot_m] : NEG;
+    Raw n0[G], n1[G];
+    CTC_UNROLL
+    for (int k = 0; k < G; ++k) {
+      n0[k] = align_load_raw<DT>(x, row + (size_t)i0[k]);
+      n1[k] = align_load_raw<DT>(x, row + (size_t)i1[k]);
+    }
+    const double lse_use = is_prob ? 0.0 : lse_t;
+    const double e_blank = align_emit_of_value(align_widen<DT>(vb), lse_use, is_prob, clip_lo);
+    CTC_UNROLL
+    for (int k = 0; k < G; ++k) {
+      const int lc = cx.tid + k * cx.nt, c = c0 + lc;
+      if (lc >= gb) break;
+      if (c < clo || c > chi) continue;
+      const double e0 = align_emit_of_value(align_widen<DT>(v0[k]), lse_use, is_prob, clip_lo);
+      const double e1 = align_emit_of_value(align_widen<DT>(v1[k]), lse_use, is_prob, clip_lo);
+      forward_step(g[k], pm1[k], e_blank, e0, e1, p[k]);
+      cur[lc] = p[k][3];
+      if (edge_out && lc == gb - 1) edge_out[slot_j + (t - t0)] = p[k][3];
+    }
+    clo_prev = clo, chi_prev = chi;
+    clo = nlo, chi = nhi, vb = nvb, lse_t = nlse, below = nbelow;
+    CTC_UNROLL
+    for (int k = 0; k < G; ++k) v0[k] = n0[k], v1[k] = n1[k];
+    cx.sync();  // the one barrier of a frame: the columns swap roles
+  }
+  // the column, for the tile after this one
+  CTC_UNROLL
+  for (int k = 0; k < G; ++k) {
+    const int lc = cx.tid + k * cx.nt;
+    if (lc >= gb) break;
+    double* at = hyp.col + 4 * (size_t)(c0 + lc);
+    at[0] = p[k][0], at[1] = p[k][1], at[2] = p[k][2], at[3] = p[k][3];
+  }
+  // the result, by the tile that holds the last blank at the last frame: read as ctc_forward_hyp reads it
+  const int cf = (S - 1) >> 2, jf = (S - 1) & 3;
+  if (t1 != T - 1 || cf < c0 || cf >= c0 + gb) return;
+  const double* fin = lds + ((T - 1) & 1) * W;
+  CTC_UNROLL
+  for (int k = 0; k < G; ++k) {
+    const int lc = cx.tid + k * cx.nt;
+    if (c0 + lc != cf) continue;
+    const double last = jf == 2 ? p[k][2] : p[k][0];
+    const double before = jf == 2 ? p[k][1] : (cf > 0 ? (lc > 0 ? fin[lc - 1] : edge_in[slot_j + (T - 1 - t0)]) : NEG);
+    *hyp.logp = align_lse2(last, before);
+  }
+}
+
 // ---- ctc_posteriors ----------------------------------------------------------------------------------------------------------
 // The frame posteriors of a label sequence ("Frame posteriors"): the CTC forward-backward over the states and the
 // window of ctc_forward,

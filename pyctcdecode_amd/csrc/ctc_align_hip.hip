@@ -6,6 +6,7 @@
 //   ctc_forward, ctc_posteriors,    a workgroup per record, a group of four states per thread in registers
 //   ctc_find, ctc_viterbi_gaps        (256 threads up to 511 labels, 1024 above)
 //   ctc_forward_wave, ctc_find_wave a wavefront per record of at most 127 labels
+//   ctc_forward_tile                a workgroup per tile of a hypothesis' states and frames, a launch per diagonal of tiles
 //   ctc_grad_rows                   G threads per row of a dense ctc_posteriors launch's tables
 //   row_argmax, row_lse_argmax      G lanes per row; both fold with row_fold_arg
 //   greedy_collapse                 a wavefront per utterance
@@ -184,6 +185,26 @@ __global__ __launch_bounds__(ALIGN_THREADS) void ctc_forward_wave(ForwardArgs a)
   if (i >= a.n_hyps) return;  // (a whole wave: nothing in this kernel waits for another wave)
   ForwardWaveCtx cx{(int)(threadIdx.x & 63u)};
   ctc_forward_wave_hyp<DT>(cx, a.hyps[i], a.n_labels, a.blank, a.clip_lo);
+}
+
+// ---------------------------------------------------------------------------------------------
+// ctc_forward_tile: one workgroup of 256 threads per tile (state block i, time block j) of a hypothesis, thread tid the
+// block's group tid in registers for the tile's frames; the block's column in device memory between tiles, the last state
+// of the block below out of its edge row, the groups' last states in two LDS columns, one barrier per frame. A launch takes
+// the tiles of one diagonal i + j of every hypothesis of the call; stream order is all that orders the diagonals (ctc_align.h).
+// ctc_forward_tile_fill: -inf into the columns and edge rows before the first diagonal.
+// ---------------------------------------------------------------------------------------------
+template <int DT>
+__global__ __launch_bounds__(FORWARD_TILE_MAX_GROUPS) void ctc_forward_tile(const ForwardTileHyp* hyps, const ForwardTile* tiles, int V,
+                                                                            int blank, double clip_lo) {
+  __shared__ double tile_cols[2 * FORWARD_TILE_MAX_GROUPS];
+  const ForwardTile tile = tiles[blockIdx.x];
+  ForwardGpuCtx cx{(int)threadIdx.x, FORWARD_TILE_MAX_GROUPS};
+  ctc_forward_tile_body<DT>(cx, hyps[tile.hyp], tile.i, tile.j, V, blank, clip_lo, tile_cols);
+}
+
+__global__ __launch_bounds__(256) void ctc_forward_tile_fill(double* p, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) p[i] = align_neg_inf();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -835,6 +856,26 @@ int launch_ctc_forward_on(const ForwardArgs& a, int wave, hipStream_t stream, st
         constexpr int NT = decltype(nt)::value;
         hipLaunchKernelGGL((ctc_forward<NT, DT>), dim3((unsigned)a.n_hyps), dim3(NT), lds, stream, a);
       });
+    });
+  });
+}
+
+// The fill, then the diagonals one after another: one pair of events around all of them, nothing copied or awaited between
+int launch_ctc_forward_tile_on(const ForwardTileArgs& a, hipStream_t stream, std::string* err) {
+  if (a.n_diags <= 0) return 0;
+  if (a.dtype < 0 || a.dtype > 3 || !a.hyps || !a.tiles || !a.diag_off || !a.fill || a.n_fill < 1 || a.n_labels < 1 || a.blank < 0 ||
+      a.blank >= a.n_labels || a.diag_off[0] != 0)
+    return bad_launch(err, "ctc_forward_tile: bad arguments");
+  for (int32_t d = 0; d < a.n_diags; ++d)
+    if (a.diag_off[d + 1] <= a.diag_off[d]) return bad_launch(err, "ctc_forward_tile: a diagonal without tiles");
+  return timed_launch(K_FORWARD_TILE, stream, err, [&] {
+    const int64_t fill_blocks = (a.n_fill + 255) / 256;
+    hipLaunchKernelGGL(ctc_forward_tile_fill, dim3((unsigned)(fill_blocks < 4096 ? fill_blocks : 4096)), dim3(256), 0, stream, a.fill, a.n_fill);
+    for_dtype(a.dtype, [&](auto dt) {
+      constexpr int DT = decltype(dt)::value;
+      for (int32_t d = 0; d < a.n_diags; ++d)
+        hipLaunchKernelGGL(ctc_forward_tile<DT>, dim3((unsigned)(a.diag_off[d + 1] - a.diag_off[d])), dim3(FORWARD_TILE_MAX_GROUPS), 0, stream,
+                           a.hyps, a.tiles + a.diag_off[d], a.n_labels, a.blank, a.clip_lo);
     });
   });
 }

@@ -144,7 +144,9 @@ class ConfidenceOutputBeam(TokenOutputBeam):
     word_logp: List[float]
 
 ALIGN_MAX_LABELS = 2047  # ALIGN_MAX_LABELS of csrc/ctc_align.h: 2 L + 1 states, two fp64 score columns in a workgroup's LDS
-ALIGN_LONG_MAX_LABELS = 1048575  # ALIGN_LONG_MAX_LABELS of csrc/ctc_align.h: 2 L + 1 states below 2^21 (align_long)
+ALIGN_LONG_MAX_LABELS = 1048575  # ALIGN_LONG_MAX_LABELS of csrc/ctc_align.h: 2 L + 1 states below 2^21 (align_long, score_long)
+SCORE_LONG_TILE_GROUPS = 256  # FORWARD_TILE_MAX_GROUPS of csrc/ctc_align.h: the groups of four states of a state block, at most
+SCORE_LONG_TILE_FRAMES = 64  # FORWARD_TILE_FRAMES of csrc/ctc_align.h: the frames of a time block when there are several state blocks
 ALIGN_BP_BUDGET = 1 << 30  # bytes of back-pointer tables one ctc_viterbi launch holds by default ("Forced alignment")
 
 
@@ -1492,6 +1494,11 @@ class BeamSearchDecoderCTC:
         self.last_align_long_timing_ms = (0.0, 0.0, 0.0, 0.0)
         self.last_align_long_launches = 0
         self.last_align_long_plan: List[Tuple[int, int]] = []
+        # ... and of the last score_long / score_long_batch call (ms: classification, row_lse, the fill and ctc_forward_tile's
+        # launches, native call; diagonals launched, tiles in them, launch groups; the plan of every hypothesis launched)
+        self.last_score_long_timing_ms = (0.0, 0.0, 0.0, 0.0)
+        self.last_score_long_launches = self.last_score_long_tiles = self.last_score_long_groups = self.last_score_long_widest = 0
+        self.last_score_long_plan: List[Tuple[int, int, int, int, int]] = []
         # ... and of the last align_gaps_long / align_gaps_long_batch call (ms: classification, row_lse_max,
         # ctc_viterbi_gaps_long, native call; launches; plan)
         self.last_align_gaps_long_timing_ms = (0.0, 0.0, 0.0, 0.0)
@@ -2526,7 +2533,8 @@ class BeamSearchDecoderCTC:
             wlp = [min(tlp[lo:hi]) for _w, lo, hi in words]
         return GreedyText(text, ids, tok, wf, tlp, wlp, float(score[0]) if fold else None)
 
-    def _many_targets_each(self, what: str, item: str, items: str, logits_list: Any, texts, tokens, ids_of_text=None):
+    def _many_targets_each(self, what: str, item: str, items: str, logits_list: Any, texts, tokens, ids_of_text=None,
+                           max_labels: int = ALIGN_MAX_LABELS):
         """The label ids of any number of given texts or token lists per utterance, checked: (logits_list, ids[u][j]).
         ``ids_of_text``: how a text becomes label ids (_target_of_text unless given)."""
         ids_of_text = ids_of_text or self._target_of_text
@@ -2567,9 +2575,9 @@ class BeamSearchDecoderCTC:
                                 raise ValueError("%s: %s holds %r: not a label id in [0, %d) other than the blank (%d)"
                                                  % (what, who, c, n_labels, blank))
                             ids[k] = int(c)
-                if len(ids) > ALIGN_MAX_LABELS:
+                if len(ids) > max_labels:
                     raise ValueError("%s: %s has %d labels, above the limit of %d labels per %s"
-                                     % (what, who, len(ids), ALIGN_MAX_LABELS, item))
+                                     % (what, who, len(ids), max_labels, item))
                 cur.append(ids)
             out.append(cur)
         return logits_list, out
@@ -2590,29 +2598,53 @@ class BeamSearchDecoderCTC:
         ``tokens[u]`` a list of lists of label ids, the only form for BPE alphabets. A hypothesis without an alignment --
         fewer frames than labels plus adjacent equal labels -- has ``logp == -inf``; the empty hypothesis scores the all-blank
         path. ``with_lm=True`` adds the language model's score of the text as a finished beam's (no hot words)."""
+        out, stats = self._scored_texts("score", logits_list, texts, tokens, with_lm, None)
+        # [classification (frame-prune kernels), row_lse, forward kernels (HIP events), whole native call]; hypotheses that
+        # went to (ctc_forward_wave, ctc_forward)
+        self.last_score_timing_ms, self.last_score_launched = stats
+        return out
+
+    def _scored_texts(self, what: str, logits_list: Any, texts, tokens, with_lm: bool, tiles: Optional[Tuple[int, int, int]]):
+        """-> (the ScoredText of every hypothesis of every utterance; what the native call did): the checked hypotheses
+        through ctcdec_score_batch (``tiles`` None: (timing ms, hypotheses by kernel)) or ctcdec_score_long_batch (``tiles``
+        its budget, tile_groups and tile_frames: (timing ms, (diagonals, tiles, launch groups, widest diagonal), plans)), and the language
+        model's term."""
         lm = self._language_model
         if with_lm and lm is None:
-            raise ValueError("score: with_lm=True needs a decoder with a language model")
-        logits_list, hyps = self._many_targets_each("score", "hypothesis", "hypotheses", logits_list, texts, tokens)
+            raise ValueError("%s: with_lm=True needs a decoder with a language model" % what)
+        logits_list, hyps = self._many_targets_each(what, "hypothesis", "hypotheses", logits_list, texts, tokens,
+                                                    max_labels=ALIGN_MAX_LABELS if tiles is None else ALIGN_LONG_MAX_LABELS)
+        zeros = (0.0, 0.0, 0.0, 0.0)
         n = len(hyps)
         if n == 0:
-            self.last_score_timing_ms, self.last_score_launched = (0.0, 0.0, 0.0, 0.0), (0, 0)
-            return []
+            return [], ((zeros, (0, 0)) if tiles is None else (zeros, (0, 0, 0, 0), []))
         kernel = _forced_kernel("CTCDEC_FORWARD_KERNEL", FORWARD_KERNELS)
         with self._call_lock:
             batch, frames, ptrs, c_utts = self._stage_transcript_call(logits_list)
+            if tiles is not None:
+                budget = tiles[0] or ALIGN_BP_BUDGET
+                for u, cur in enumerate(hyps):
+                    for k, ids in enumerate(cur):
+                        need = self._score_long_plan(int(frames[u]), len(ids), budget, tiles[1], tiles[2])[4]
+                        if need > budget and int(frames[u]) >= self._frames_needed(ids):
+                            raise ValueError("%s: utterance %d, hypothesis %d needs a column and edge rows of %d bytes, above the "
+                                             "memory budget of %d bytes of one launch" % (what, u, k, need, budget))
             flat, target_off, hyp_off, nh = self._pack_items(hyps)
             logp = np.zeros(max(nh, 1), dtype=np.float64)
-            ms, launched = (C.c_double * 4)(), (C.c_int64 * 2)()
+            ms = (C.c_double * 4)()
             lib = self._lib
-            lib.check(lib.dll.ctcdec_score_batch(
-                self._handle, *c_utts, n,
-                batch.dtype, int(batch.is_device), flat.ctypes.data_as(C.POINTER(C.c_int32)), B.off_ptr(target_off),
-                B.off_ptr(hyp_off), kernel, logp.ctypes.data_as(C.POINTER(C.c_double)), ms, launched))
-            # [classification (frame-prune kernels), row_lse, forward kernels (HIP events), whole native call]; hypotheses that
-            # went to (ctc_forward_wave, ctc_forward)
-            self.last_score_timing_ms = tuple(float(v) for v in ms)
-            self.last_score_launched = (int(launched[0]), int(launched[1]))
+            head = (self._handle, *c_utts, n, batch.dtype, int(batch.is_device), flat.ctypes.data_as(C.POINTER(C.c_int32)),
+                    B.off_ptr(target_off), B.off_ptr(hyp_off))
+            if tiles is None:
+                launched = (C.c_int64 * 2)()
+                lib.check(lib.dll.ctcdec_score_batch(*head, kernel, logp.ctypes.data_as(C.POINTER(C.c_double)), ms, launched))
+                stats = (tuple(float(v) for v in ms), (int(launched[0]), int(launched[1])))
+            else:
+                counts, plan = (C.c_int64 * 5)(), np.zeros((max(nh, 1), 5), dtype=np.int64)
+                lib.check(lib.dll.ctcdec_score_long_batch(*head, *tiles, logp.ctypes.data_as(C.POINTER(C.c_double)), ms, counts,
+                                                          plan.ctypes.data_as(C.POINTER(C.c_int64))))
+                stats = (tuple(float(v) for v in ms), (int(counts[0]), int(counts[1]), int(counts[2]), int(counts[4])),
+                         [tuple(row) for row in plan[:int(counts[3])].tolist()])
         out: List[List[ScoredText]] = []
         h = 0
         for cur in hyps:
@@ -2630,6 +2662,57 @@ class BeamSearchDecoderCTC:
                 res.append(ScoredText(text, list(ids), lp, lm_logp, lp + (lm_logp or 0.0)))
                 h += 1
             out.append(res)
+        return out, stats
+
+    # -- transcript likelihood of long transcripts (no reference analogue; DESIGN.md, "Transcript likelihood of long transcripts")
+    @staticmethod
+    def _score_long_plan(frames: int, n_labels: int, budget: int, tile_groups: int, tile_frames: int) -> Tuple[int, int, int, int, int]:
+        """-> (tile_groups, tile_frames, state_blocks, time_blocks, bytes): how ctcdec_score_long_batch cuts a hypothesis
+        (score_long_plan, csrc/ctc_align.h, the same rule): state blocks of GB groups of four states, time blocks of FB frames,
+        and the bytes of its column and of a ring of three time blocks per boundary between state blocks."""
+        if frames <= 0:
+            return 0, 0, 0, 0, 0
+        nch = (2 * n_labels + 1 + 3) // 4
+        gb = tile_groups if tile_groups > 0 else SCORE_LONG_TILE_GROUPS
+        n_i = -(-nch // gb)
+        rows = 3 * (n_i - 1)
+        fb = tile_frames if tile_frames > 0 else frames if n_i == 1 else SCORE_LONG_TILE_FRAMES
+        if tile_frames <= 0 and rows > 0 and 8 * (4 * nch + rows * fb) > budget:
+            fb = (budget // 8 - 4 * nch) // rows
+        fb = max(1, min(fb, frames))
+        return gb, fb, n_i, -(-frames // fb), 8 * (4 * nch + rows * fb)
+
+    def score_long(self, logits: Any, texts: Optional[Sequence[str]] = None, tokens: Optional[Sequence[Sequence[int]]] = None,
+                   with_lm: bool = False) -> List["ScoredText"]:
+        """The likelihood of each long hypothesis for one utterance: score_long_batch of a batch of one."""
+        if isinstance(logits, (_ResidentBeams, _DeviceStreams)):
+            raise NotImplementedError("score_long reads an utterance's matrix; the frames a stream has consumed are not kept")
+        self._check_logits_dimension(logits)
+        return self.score_long_batch([logits], None if texts is None else [texts], tokens=None if tokens is None else [tokens],
+                                     with_lm=with_lm)[0]
+
+    def score_long_batch(self, logits_list: Any, texts: Optional[Sequence[Sequence[str]]] = None,
+                         tokens: Optional[Sequence[Sequence[Sequence[int]]]] = None, with_lm: bool = False, _budget: int = 0,
+                         _tile_groups: int = 0, _tile_frames: int = 0) -> List[List["ScoredText"]]:
+        """score_batch for a lecture against its script: up to 1048575 labels per hypothesis instead of 2047 (row_lse +
+        ctc_forward_tile, csrc/ctc_align_hip.hip). Arguments, hypotheses, the -inf rule and ``with_lm`` are score_batch's, and
+        for every input score_batch accepts ``logp`` is score_batch's, bit for bit. A hypothesis' states are cut into blocks
+        of 256 groups of four and its frames into blocks of 64; a tile (state block, time block) runs on one workgroup, and
+        one launch takes a diagonal of tiles, so a long hypothesis spreads over many compute units. score_batch stays the
+        faster call for hypotheses it accepts. ``last_score_long_plan`` holds (tile_groups, tile_frames, state_blocks,
+        time_blocks, bytes) of every hypothesis launched, ``last_score_long_launches`` and ``last_score_long_tiles`` the
+        diagonals launched and the tiles in them, ``last_score_long_groups`` the launch groups the budget made, ``last_score_long_widest`` the most tiles one diagonal held."""
+        if isinstance(logits_list, (_ResidentBeams, _DeviceStreams)) or (
+                isinstance(logits_list, (list, tuple)) and any(isinstance(x, (_ResidentBeams, _DeviceStreams)) for x in logits_list)):
+            raise NotImplementedError("score_long_batch reads utterances' matrices; the frames a stream has consumed are not kept")
+        for name, v, top in (("_budget", _budget, 2 ** 63), ("_tile_groups", _tile_groups, SCORE_LONG_TILE_GROUPS + 1),
+                             ("_tile_frames", _tile_frames, 2 ** 31)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < top:
+                raise ValueError("score_long: %s must be an int in [0, %d) (0: the library's rule), not %r" % (name, top, v))
+        out, stats = self._scored_texts("score_long", logits_list, texts, tokens, with_lm,
+                                        (int(_budget), int(_tile_groups), int(_tile_frames)))
+        self.last_score_long_timing_ms, counts, self.last_score_long_plan = stats
+        self.last_score_long_launches, self.last_score_long_tiles, self.last_score_long_groups, self.last_score_long_widest = counts
         return out
 
     # -- prefix scores (no reference analogue; DESIGN.md, "Prefix scores") -----------------------------------
