@@ -391,6 +391,38 @@ int ctcdec_align_long_batch(ctcdec_decoder* dec, const void* const* utt_logits, 
  * alignment made by ctcdec_align_batch or ctcdec_align_gaps_batch reports one segment of all T frames. */
 int ctcdec_alignment_plan(const ctcdec_alignment* a, const int32_t** segment_frames, const int32_t** n_segments, int64_t* n_utts);
 
+/* ---- forced alignment of long transcripts, tiled: one long utterance over many compute units -----------------------------
+ * ctcdec_align_long_batch on the tile scheme of ctcdec_score_long_batch. The result is ctcdec_align_long_batch's, and for
+ * every input ctcdec_align_batch accepts that call's, bit for bit, whatever the tile shape: the states, the window, the
+ * operands of every comparison and addition and their order -- stay, then step, then skip, with strict > --, the preference of
+ * the last label over the trailing blank and the score (the last column's value) are the same.
+ * With nch = ceil((2 L + 1) / 4): state blocks of GB groups of four states (tile_groups, 0 for 256, at most 256; nI =
+ * ceil(nch / GB) of them), time blocks of FB frames (tile_frames, 0 for 64, clamped to [1, min(T, 448)]; nJ = ceil(T / FB)),
+ * segments of KB time blocks (segment_blocks, 0 for the most with KB * FB <= 448), K = KB * FB frames, n = ceil(T / K) of
+ * them; segment j holds the frames j K .. min((j + 1) K, T) - 1. The plan takes
+ *   8 (4 nch + 3 (nI - 1) FB) + 32 nch max(n - 1, 0)  bytes:
+ * the column, a ring of three time blocks per boundary between state blocks, a checkpoint (the column of frame j K - 1) for
+ * every segment but the first.
+ * Pass A, kernel ctc_viterbi_tile: one workgroup per tile (state block, time block), one launch per diagonal of tiles behind
+ * a fill of -inf; no workgroup waits for another. It keeps the checkpoints and ends with the score and the end state. Pass
+ * B, kernel ctc_viterbi_cone: one workgroup per utterance; from the last segment to the first it restores from the checkpoint
+ * the at most K / 2 + 2 groups that can reach the path's state at the segment's end, runs the segment again with
+ * back-pointers in LDS (rows that shrink towards the segment's end: 50848 bytes at K = 448) and traces it back.
+ * budget: the planned bytes one launch group may hold, 0 for 1 GiB; a batch that needs more takes several with the same
+ * results. Validation, before any launch: ctcdec_align_long_batch's checks with its codes; tile_groups outside [0, 256], a
+ * negative tile_frames or segment_blocks, or segments of more than 448 frames are CTCDEC_ERR_ARG; one utterance whose plan
+ * exceeds the budget is CTCDEC_ERR_LIMIT, names the utterance and the bytes (ctcdec_align_long_batch needs less memory: its
+ * checkpoints shrink with longer segments, these do not).
+ * The result is read by ctcdec_alignment_paths / _tokens / _timing ([2] both passes; launches: launch groups) / _plan (K, n)
+ * / _tiled and freed by ctcdec_alignment_free. decoder.py: align_long(tiled=True) / align_long_batch(tiled=True). */
+int ctcdec_align_tiled_batch(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts,
+                             int32_t dtype, int32_t is_device, const int32_t* targets, const int64_t* target_off, int32_t fold,
+                             int64_t budget, int32_t tile_groups, int32_t tile_frames, int32_t segment_blocks, ctcdec_alignment** out);
+/* What a tiled alignment did. counts4: diagonals launched, tiles in them, launch groups, most tiles in one diagonal; ms2: the
+ * kernel time of pass A (fill and diagonals) and of pass B (HIP events); plan6: (GB, FB, nI, nJ, KB, bytes) of every utterance,
+ * zeros for one without frames. All zeros / no rows for an alignment another call made. */
+int ctcdec_alignment_tiled(const ctcdec_alignment* a, int64_t* counts4, double* ms2, const int64_t** plan6, int64_t* n_utts);
+
 /* ---- alignment with gaps: a transcript that does not cover all of the audio ------------------------------------------
  * torchaudio's forced_align tutorials do this with a "star" token. ctcdec_align_batch with one more kind of target item:
  * CTCDEC_ALIGN_GAP stands for "something nobody transcribed". A target is a sequence of items, each a label id (alphabet

@@ -158,6 +158,11 @@ _PROTOS = {
                                           C.POINTER(_VP)]),
     "ctcdec_alignment_plan": (C.c_int, [_VP, C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_int32)),
                                         C.POINTER(C.c_int64)]),
+    "ctcdec_align_tiled_batch": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32,
+                                           C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_int32, C.c_int64, C.c_int32,
+                                           C.c_int32, C.c_int32, C.POINTER(_VP)]),
+    "ctcdec_alignment_tiled": (C.c_int, [_VP, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.POINTER(C.c_int64)),
+                                         C.POINTER(C.c_int64)]),
     "ctcdec_align_gaps_batch": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32,
                                           C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_int32, C.c_int64, C.POINTER(_VP)]),
     "ctcdec_align_gaps_long_batch": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32,

@@ -190,6 +190,9 @@ struct ctcdec_decoder {
   // transcript likelihood of long transcripts (ctcdec_score_long_batch): a launch group's hypothesis records and tile records
   // (columns and edge rows: w_lcol; labels: w_alab; scores: w_ascore)
   DevBuf w_sthyps, w_stiles;
+  // forced alignment of long transcripts, tiled (ctcdec_align_tiled_batch): a launch group's utterance records and the
+  // utterances' end states (tile records: w_stiles; columns, edge rows and checkpoints: w_lcol; everything else: the alignment's)
+  DevBuf w_tutts, w_tend;
   // frame posteriors (ctcdec_posteriors_batch): a launch's tables and utterance records, the token sums (labels: w_alab,
   // score pairs: w_ascore)
   DevBuf w_ptab, w_putts, w_pocc;

@@ -25,6 +25,11 @@ struct ctcdec_alignment {
   double ms[4] = {0, 0, 0, 0};
   // how each utterance's frames were cut (ctcdec_alignment_plan): one segment of all of them unless ctcdec_align_long_batch cut
   std::vector<int32_t> seg_frames, n_segs;
+  // ctcdec_align_tiled_batch (ctcdec_alignment_tiled): diagonals launched, tiles in them, launch groups, most tiles in a
+  // diagonal; the kernel time of pass A and of pass B; (GB, FB, nI, nJ, KB, bytes) of every utterance
+  int64_t tiled_counts[4] = {0, 0, 0, 0};
+  double tiled_ms[2] = {0, 0};
+  std::vector<int64_t> tiled_plan;
   // ctcdec_align_gaps_batch: utterance u's gaps, in target order, are [gap_off[u], gap_off[u + 1])
   bool has_gaps = false;
   std::vector<int64_t> gap_off;
@@ -147,8 +152,9 @@ static int check_frames(const void* const* utt_logits, const int32_t* utt_frames
 // Everything the kernels index with comes from the caller: checked here, before anything moves.
 static int check_alignment(const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts, const int32_t* targets,
                            const int64_t* target_off, int64_t budget, const TranscriptCall& tc, int32_t max_labels = ALIGN_MAX_LABELS,
-                           int32_t segment_frames = -1) {
+                           int32_t segment_frames = -1, const int32_t* tiled = nullptr) {
   const bool planned = segment_frames >= 0;  // ctcdec_align_long_batch: the budget bounds an utterance's plan, not its whole table
+  // tiled (ctcdec_align_tiled_batch): tile_groups, tile_frames, segment_blocks -- the plan is align_tiled_plan's
   if (target_off[0] != 0) return fail(CTCDEC_ERR_ARG, "target_off must start at 0");
   std::string infeasible;
   for (int32_t u = 0; u < n_utts; ++u) {
@@ -166,7 +172,16 @@ static int check_alignment(const void* const* utt_logits, const int32_t* utt_fra
                               "target label", need))
       return rc;
     if (T < need) infeasible += (infeasible.empty() ? "" : ", ") + std::to_string(u);
-    if (planned) {
+    if (tiled) {
+      const AlignTiledPlan pl = align_tiled_plan((int32_t)T, (int32_t)L, budget, tiled[0], tiled[1], tiled[2]);
+      if (pl.K > ALIGN_TILED_MAX_SEGMENT)
+        return fail(CTCDEC_ERR_ARG, "utterance " + std::to_string(u) + ": segments of " + std::to_string(pl.K) + " frames, above the " +
+                                        std::to_string(ALIGN_TILED_MAX_SEGMENT) + " whose back-pointers fit LDS");
+      if (pl.bytes > budget)
+        return fail(CTCDEC_ERR_LIMIT, "utterance " + std::to_string(u) + ": a column, edge rows and checkpoints of " + std::to_string(pl.bytes) +
+                                          " bytes, above the budget of " + std::to_string(budget) +
+                                          " bytes for one launch (align_long without tiled needs less memory)");
+    } else if (planned) {
       const int64_t bytes = long_plan((int32_t)T, (int32_t)L, budget, segment_frames).bytes;
       if (bytes > budget)
         return fail(CTCDEC_ERR_LIMIT, "utterance " + std::to_string(u) + ": segment tables, checkpoints and columns of " + std::to_string(bytes) +
@@ -1132,6 +1147,40 @@ struct TileSeqCtx {  // (ctc_forward_tile_body: the one thread owns every group 
 };
 #endif
 
+// How one record of a launch group is cut into tiles, and the group's live tiles by diagonal: counted, then placed, `hyp` the
+// record's index, `keep` viterbi_tile_keep's; a diagonal without one takes no launch (diag_off has an entry per diagonal that does, and the end). Returns
+// the most tiles one diagonal holds.
+struct TileCut {
+  int32_t T, L, GB, FB, nI, nJ, KB;  // KB: the time blocks of a segment of ctc_viterbi_tile (ForwardTile::keep), 0 for ctc_forward_tile
+};
+static int64_t diagonal_tiles(const std::vector<TileCut>& cuts, std::vector<ForwardTile>& tiles, std::vector<int32_t>& diag_off) {
+  int32_t n_diags = 0;
+  for (const TileCut& c : cuts) n_diags = std::max(n_diags, c.nI + c.nJ - 1);
+  const auto each_live = [&](auto f) {
+    for (size_t r = 0; r < cuts.size(); ++r) {
+      const TileCut& c = cuts[r];
+      for (int32_t j = 0; j < c.nJ; ++j)
+        for (int32_t i = 0; i < c.nI; ++i)
+          if (forward_tile_live(c.T, c.L, c.GB, c.FB, i, j)) f((int32_t)r, i, j);
+    }
+  };
+  std::vector<int32_t> count((size_t)n_diags, 0), at((size_t)n_diags, 0);
+  each_live([&](int32_t, int32_t i, int32_t j) { ++count[(size_t)(i + j)]; });
+  int64_t widest = 0;
+  diag_off.assign(1, 0);
+  for (int32_t d = 0; d < n_diags; ++d) {
+    at[(size_t)d] = diag_off.back();
+    if (count[(size_t)d]) diag_off.push_back(diag_off.back() + count[(size_t)d]);
+    widest = std::max<int64_t>(widest, count[(size_t)d]);
+  }
+  tiles.assign((size_t)diag_off.back(), ForwardTile());
+  each_live([&](int32_t r, int32_t i, int32_t j) {
+    const TileCut& c = cuts[(size_t)r];
+    tiles[(size_t)at[(size_t)(i + j)]++] = ForwardTile{r, i, j, c.KB > 0 ? viterbi_tile_keep(c.T, c.FB, c.KB, j) : 0};
+  });
+  return widest;
+}
+
 // What ctcdec_score_long_batch adds to a score call: its options, the plan of every hypothesis that is launched (bytes 0: not
 // launched) and, out, what the call did
 struct ScoreLong {
@@ -1151,12 +1200,13 @@ static int forward_tile_pass(ctcdec_decoder* dec, const TranscriptCall& tc, int3
   const int64_t most = budget_groups((int32_t)run.size(), [&](int32_t k) { return sl.plans[(size_t)run[(size_t)k]].bytes; }, sl.budget, groups);
   if (dec->w_lcol.ensure((size_t)std::max<int64_t>(most, 8), &err)) return fail(CTCDEC_ERR_DEVICE, err);
   std::vector<ForwardTileHyp> hyps;
+  std::vector<TileCut> cuts;
   std::vector<ForwardTile> tiles;
-  std::vector<int32_t> diag_off, at;
+  std::vector<int32_t> diag_off;
   for (const auto& g : groups) {
     hyps.clear();
+    cuts.clear();
     int64_t doubles = 0;
-    int32_t n_diags = 0;
     for (int32_t k : g) {
       const int32_t h = run[(size_t)k];
       const UttRows& u = utts[(size_t)utt_of[(size_t)h]];
@@ -1173,29 +1223,10 @@ static int forward_tile_pass(ctcdec_decoder* dec, const TranscriptCall& tc, int3
       a.is_prob = u.is_prob;
       a.GB = pl.GB, a.FB = pl.FB, a.pad = 0;
       hyps.push_back(a);
+      cuts.push_back(TileCut{a.T, a.L, pl.GB, pl.FB, pl.nI, pl.nJ, 0});
       doubles += pl.bytes / 8;
-      n_diags = std::max(n_diags, pl.nI + pl.nJ - 1);
     }
-    // the live tiles by diagonal: counted, then placed; a diagonal without one takes no launch
-    const auto each_live = [&](auto f) {
-      for (size_t r = 0; r < hyps.size(); ++r) {
-        const ScoreLongPlan& pl = sl.plans[(size_t)run[(size_t)g[r]]];
-        for (int32_t j = 0; j < pl.nJ; ++j)
-          for (int32_t i = 0; i < pl.nI; ++i)
-            if (forward_tile_live(hyps[r].T, hyps[r].L, pl.GB, pl.FB, i, j)) f((int32_t)r, i, j);
-      }
-    };
-    std::vector<int32_t> count((size_t)n_diags, 0);
-    each_live([&](int32_t, int32_t i, int32_t j) { ++count[(size_t)(i + j)]; });
-    at.assign((size_t)n_diags, 0);
-    diag_off.assign(1, 0);
-    for (int32_t d = 0; d < n_diags; ++d) {
-      at[(size_t)d] = diag_off.back();
-      if (count[(size_t)d]) diag_off.push_back(diag_off.back() + count[(size_t)d]);
-      sl.widest = std::max<int64_t>(sl.widest, count[(size_t)d]);
-    }
-    tiles.assign((size_t)diag_off.back(), ForwardTile());
-    each_live([&](int32_t r, int32_t i, int32_t j) { tiles[(size_t)at[(size_t)(i + j)]++] = ForwardTile{r, i, j, 0}; });
+    sl.widest = std::max(sl.widest, diagonal_tiles(cuts, tiles, diag_off));
     sl.launches += (int64_t)diag_off.size() - 1;
     sl.tiles += (int64_t)tiles.size();
     ++sl.groups;
@@ -1340,6 +1371,169 @@ int ctcdec_score_long_batch(ctcdec_decoder* dec, const void* const* utt_logits, 
     for (const ScoreLongPlan& pl : sl.plans)
       if (pl.bytes > 0) row[0] = pl.GB, row[1] = pl.FB, row[2] = pl.nI, row[3] = pl.nJ, row[4] = pl.bytes, row += 5;
   }
+  return CTCDEC_OK;
+}
+
+// ---- forced alignment of long transcripts, tiled ("Forced alignment of long transcripts, tiled") ----------------
+}  // extern "C"
+
+// The call behind ctcdec_align_tiled_batch, its arguments checked: viterbi_call's result, front and copies back around launch
+// groups of utterances whose columns, edge rows and checkpoints fill the budget (w_lcol); per group the utterance records and
+// the records of every live tile sorted by diagonal go over once, then the fill, one launch per diagonal (pass A) and the
+// cone launch (pass B) are queued with nothing between them.
+static int align_tiled_call(ctcdec_decoder* dec, const TranscriptCall& tc, const void* const* utt_logits, const int32_t* utt_frames,
+                            int32_t n_utts, int32_t dtype, int32_t is_device, const int32_t* labels, const int64_t* lab_off, int32_t fold,
+                            int64_t budget, const std::vector<AlignTiledPlan>& plans, std::unique_ptr<ctcdec_alignment>& res) {
+  res.reset(new ctcdec_alignment());
+  const size_t n = (size_t)n_utts;
+  for (const AlignTiledPlan& pl : plans) {
+    res->seg_frames.push_back((int32_t)pl.K);
+    res->n_segs.push_back((int32_t)pl.n);
+    for (int64_t v : {(int64_t)pl.GB, (int64_t)pl.FB, (int64_t)pl.nI, (int64_t)pl.nJ, (int64_t)pl.KB, pl.bytes}) res->tiled_plan.push_back(v);
+  }
+  const int64_t NL = lab_off[n];
+  const std::vector<int64_t> row0 = row_starts(utt_frames, n);
+  const int64_t R = row0[n];
+  res->path_off = row0;
+  res->tok_off.assign(lab_off, lab_off + n + 1);
+  res->label.assign(labels, labels + NL);
+  res->path.resize((size_t)R);
+  res->start.assign((size_t)NL, 0);
+  res->end.assign((size_t)NL, 0);
+  res->score.assign(n, 0.0);
+  res->has_logp = fold != 0;
+  if (fold) res->logp.assign((size_t)NL, 0.0);
+  if (R == 0) return CTCDEC_OK;
+  std::string err;
+  AlignFront fr;
+  if (int rc = align_front(dec, utt_logits, utt_frames, n_utts, dtype, is_device, tc.V, row0, fr)) return rc;
+  res->ms[0] = fr.sniff_ms;
+  const size_t nl1 = (size_t)std::max<int64_t>(NL, 1);
+  if (dec->w_apath.ensure((size_t)R * 4, &err) || dec->w_alab.ensure(nl1 * 4, &err) || dec->w_atok.ensure(nl1 * 8, &err) ||
+      dec->w_atlp.ensure(nl1 * 8, &err) || dec->w_ascore.ensure(n * 8, &err) || dec->w_tend.ensure(n * 4, &err))
+    return fail(CTCDEC_ERR_DEVICE, err);
+  if ((NL && be::h2d(dec->w_alab.p, labels, (size_t)NL * 4, &err)) || be::zero(dec->w_atok.p, nl1 * 8, &err) ||
+      be::zero(dec->w_atlp.p, nl1 * 8, &err) || be::zero(dec->w_ascore.p, n * 8, &err) || be::zero(dec->w_tend.p, n * 4, &err))
+    return fail(CTCDEC_ERR_DEVICE, err);
+  std::vector<std::vector<int32_t>> groups;
+  const int64_t most = budget_groups(n_utts, [&](int32_t u) { return plans[(size_t)u].bytes; }, budget, groups);
+  if (dec->w_lcol.ensure((size_t)std::max<int64_t>(most, 8), &err)) return fail(CTCDEC_ERR_DEVICE, err);
+  std::vector<AlignTiledUtt> utts;
+  std::vector<TileCut> cuts;
+  std::vector<ForwardTile> tiles;
+  std::vector<int32_t> diag_off;
+  for (const auto& g : groups) {
+    utts.clear();
+    cuts.clear();
+    int64_t doubles = 0;
+    for (int32_t u : g) {
+      const AlignTiledPlan& pl = plans[(size_t)u];
+      const int64_t lo = lab_off[u];
+      AlignTiledUtt a;
+      a.x = fr.ptrs[(size_t)u];
+      a.lse = fr.lse + row0[(size_t)u];
+      a.lab = (const int32_t*)dec->w_alab.p + lo;
+      a.T = utt_frames[u];
+      a.L = (int32_t)(lab_off[u + 1] - lo);
+      a.col = (double*)dec->w_lcol.p + doubles;
+      a.edge = a.col + 4 * (int64_t)align_chunks(a.L);
+      a.ckpt = a.edge + (int64_t)FORWARD_TILE_RING * (pl.nI - 1) * pl.FB;
+      a.s_end = (int32_t*)dec->w_tend.p + u;
+      a.path = (int32_t*)dec->w_apath.p + row0[(size_t)u];
+      a.tok_start = (int32_t*)dec->w_atok.p + lo;
+      a.tok_end = (int32_t*)dec->w_atok.p + NL + lo;
+      a.tok_logp = (double*)dec->w_atlp.p + lo;
+      a.score = (double*)dec->w_ascore.p + u;
+      a.is_prob = fr.is_prob[(size_t)u] ? 1 : 0;
+      a.GB = pl.GB, a.FB = pl.FB, a.KB = pl.KB;
+      utts.push_back(a);
+      cuts.push_back(TileCut{a.T, a.L, pl.GB, pl.FB, pl.nI, pl.nJ, pl.KB});
+      doubles += pl.bytes / 8;
+    }
+    res->tiled_counts[3] = std::max(res->tiled_counts[3], diagonal_tiles(cuts, tiles, diag_off));
+    res->tiled_counts[0] += (int64_t)diag_off.size() - 1;
+    res->tiled_counts[1] += (int64_t)tiles.size();
+    ++res->tiled_counts[2];
+#ifdef CTC_SIM
+    std::fill((double*)dec->w_lcol.p, (double*)dec->w_lcol.p + doubles, align_neg_inf());
+    std::vector<double> lds((size_t)2 * FORWARD_TILE_MAX_GROUPS);
+    std::vector<uint8_t> bp((size_t)ALIGN_TILED_BP_BYTES);
+    int hand = 0;
+    TileSeqCtx cx;
+    for_dtype(dtype, [&](auto dt) {
+      constexpr int DT = decltype(dt)::value;
+      for (const ForwardTile& t : tiles) ctc_viterbi_tile_body<DT>(cx, utts[(size_t)t.hyp], t.i, t.j, t.keep, tc.V, tc.blank, tc.clip_lo, lds.data());
+      for (const AlignTiledUtt& a : utts) ctc_viterbi_cone_utt<DT>(cx, a, tc.V, tc.blank, fold, tc.clip_lo, lds.data(), bp.data(), &hand);
+    });
+#else
+    if (upload(dec->w_tutts, utts, &err) || upload(dec->w_stiles, tiles, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+    be::ViterbiTiledArgs ta;
+    ta.utts = (const AlignTiledUtt*)dec->w_tutts.p;
+    ta.tiles = (const ForwardTile*)dec->w_stiles.p;
+    ta.diag_off = diag_off.data();
+    ta.fill = (double*)dec->w_lcol.p;
+    ta.n_fill = doubles;
+    ta.n_diags = (int32_t)diag_off.size() - 1;
+    ta.n_utts = (int32_t)utts.size();
+    ta.n_labels = tc.V;
+    ta.dtype = dtype;
+    ta.blank = tc.blank;
+    ta.fold = fold;
+    ta.clip_lo = tc.clip_lo;
+    if (be::launch_ctc_viterbi_tiled(ta, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+#endif
+    ++res->launches;
+  }
+  if (be::d2h(res->path.data(), dec->w_apath.p, (size_t)R * 4, &err) || be::d2h(res->score.data(), dec->w_ascore.p, n * 8, &err))
+    return fail(CTCDEC_ERR_DEVICE, err);
+  if (NL && (be::d2h(res->start.data(), dec->w_atok.p, (size_t)NL * 4, &err) ||
+             be::d2h(res->end.data(), (const int32_t*)dec->w_atok.p + NL, (size_t)NL * 4, &err) ||
+             (fold && be::d2h(res->logp.data(), dec->w_atlp.p, (size_t)NL * 8, &err))))
+    return fail(CTCDEC_ERR_DEVICE, err);
+#ifndef CTC_SIM
+  res->ms[1] = be::align_kernel_ms(be::K_ROW_LSE);
+  res->tiled_ms[0] = be::align_kernel_ms(be::K_VITERBI_TILE);
+  res->tiled_ms[1] = be::align_kernel_ms(be::K_VITERBI_CONE);
+  res->ms[2] = res->tiled_ms[0] + res->tiled_ms[1];
+#endif
+  return CTCDEC_OK;
+}
+
+extern "C" {
+
+int ctcdec_align_tiled_batch(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts, int32_t dtype,
+                             int32_t is_device, const int32_t* targets, const int64_t* target_off, int32_t fold, int64_t budget,
+                             int32_t tile_groups, int32_t tile_frames, int32_t segment_blocks, ctcdec_alignment** out) {
+  TranscriptCall tc;
+  const bool args_ok = dec && out && n_utts >= 0 && target_off && budget >= 0 && (n_utts == 0 || (utt_logits && utt_frames));
+  const std::string bad_option = !bad_fold(fold).empty() ? bad_fold(fold)
+                                 : tile_groups < 0 || tile_groups > FORWARD_TILE_MAX_GROUPS
+                                     ? "tile_groups must be 0 (the library chooses) to " + std::to_string(FORWARD_TILE_MAX_GROUPS)
+                                 : tile_frames < 0      ? "tile_frames must not be negative"
+                                 : segment_blocks < 0 ? "segment_blocks must not be negative"
+                                                      : "";
+  if (int rc = transcript_open(dec, args_ok, dtype, bad_option, tc)) return rc;
+  const int64_t limit = budget ? budget : ALIGN_BP_BUDGET;
+  const int32_t cut[3] = {tile_groups, tile_frames, segment_blocks};
+  if (int rc = check_alignment(utt_logits, utt_frames, n_utts, targets, target_off, limit, tc, ALIGN_LONG_MAX_LABELS, 0, cut)) return rc;
+  std::vector<AlignTiledPlan> plans;
+  for (int32_t u = 0; u < n_utts; ++u)
+    plans.push_back(align_tiled_plan(utt_frames[u], (int32_t)(target_off[u + 1] - target_off[u]), limit, tile_groups, tile_frames, segment_blocks));
+  const auto t_begin = Clock::now();
+  std::unique_ptr<ctcdec_alignment> res;
+  if (int rc = align_tiled_call(dec, tc, utt_logits, utt_frames, n_utts, dtype, is_device, targets, target_off, fold, limit, plans, res))
+    return rc;
+  res->ms[3] = ms(t_begin, Clock::now());
+  *out = res.release();
+  return CTCDEC_OK;
+}
+
+int ctcdec_alignment_tiled(const ctcdec_alignment* a, int64_t* counts4, double* ms2, const int64_t** plan6_out, int64_t* n_utts_out) {
+  if (!a || !counts4 || !ms2 || !plan6_out || !n_utts_out) return fail(CTCDEC_ERR_ARG, "no alignment");
+  for (int k = 0; k < 4; ++k) counts4[k] = a->tiled_counts[k];
+  ms2[0] = a->tiled_ms[0], ms2[1] = a->tiled_ms[1];
+  *plan6_out = a->tiled_plan.data();
+  *n_utts_out = (int64_t)a->tiled_plan.size() / 6;
   return CTCDEC_OK;
 }
 

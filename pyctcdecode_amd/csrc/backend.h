@@ -284,6 +284,24 @@ struct ForwardTileArgs {
   double clip_lo;              // ln(MIN_TOKEN_CLIP_P)
 };
 int launch_ctc_forward_tile(const ForwardTileArgs& a, std::string* err);
+// ctc_viterbi_tile, then ctc_viterbi_cone: `tiles` and `diag_off` as for ctc_forward_tile, `hyp` of a tile the index into
+// `utts`; the fill covers the utterances' columns, edge rows and checkpoints. Behind the last diagonal one workgroup per
+// entry of `utts` traces back. All entries validated by the host (AlignTiledUtt: KB * FB <= ALIGN_TILED_MAX_SEGMENT)
+struct ViterbiTiledArgs {
+  const AlignTiledUtt* utts;  // [n_utts] (device)
+  const ForwardTile* tiles;   // [diag_off[n_diags]] (device)
+  const int32_t* diag_off;    // [n_diags + 1] (host)
+  double* fill;               // [n_fill] (device)
+  int64_t n_fill;
+  int32_t n_diags;
+  int32_t n_utts;
+  int32_t n_labels;
+  int32_t dtype;
+  int32_t blank;
+  int32_t fold;               // 0, LOGP_MEAN / LOGP_MIN / LOGP_MAX
+  double clip_lo;             // ln(MIN_TOKEN_CLIP_P)
+};
+int launch_ctc_viterbi_tiled(const ViterbiTiledArgs& a, std::string* err);
 // ctc_posteriors: one workgroup per entry of `utts`, all of them validated by the host (PostUtt); 256 threads when every
 // utterance of the launch has at most 256 groups of states, else 1024
 struct PosteriorsArgs {
@@ -377,10 +395,12 @@ int launch_ctc_prefix_advance(const PrefixAdvanceArgs& a, std::string* err);
 // kernel times (HIP events) of the launches of one of these kernels since the last reset; waits for the kernels.
 // ctc_forward and ctc_forward_wave share a log (with their _ends forms), as do ctc_find and ctc_find_wave, greedy_collapse's
 // two passes, and ctc_prefix_extend, ctc_prefix_finish and ctc_prefix_fill; ctc_prefix_advance has its own. ctc_forward_tile's
-// log holds one pair of events per launch_ctc_forward_tile: the fill and every diagonal.
+// log holds one pair of events per launch_ctc_forward_tile: the fill and every diagonal; ctc_viterbi_tile's likewise, and
+// ctc_viterbi_cone's one pair per launch_ctc_viterbi_tiled.
 enum AlignKernel {
   K_ROW_LSE, K_VITERBI, K_FORWARD, K_POSTERIORS, K_GRAD_ROWS, K_FIND, K_ROW_LSE_MAX, K_VITERBI_GAPS, K_ROW_ARGMAX, K_ROW_LSE_ARGMAX,
-  K_GREEDY_COLLAPSE, K_PREFIX_EXTEND, K_PREFIX_ADVANCE, K_VITERBI_LONG, K_VITERBI_GAPS_LONG, K_FORWARD_TILE, ALIGN_KERNELS
+  K_GREEDY_COLLAPSE, K_PREFIX_EXTEND, K_PREFIX_ADVANCE, K_VITERBI_LONG, K_VITERBI_GAPS_LONG, K_FORWARD_TILE, K_VITERBI_TILE,
+  K_VITERBI_CONE, ALIGN_KERNELS
 };
 void align_timing_reset();
 double align_kernel_ms(AlignKernel kind);

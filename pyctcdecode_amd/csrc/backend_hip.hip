@@ -563,6 +563,8 @@ int launch_ctc_forward_on(const ForwardArgs& a, int wave, hipStream_t stream, st
 int launch_ctc_forward(const ForwardArgs& a, int wave, std::string* err) { return launch_ctc_forward_on(a, wave, g_stream, err); }
 int launch_ctc_forward_tile_on(const ForwardTileArgs& a, hipStream_t stream, std::string* err);
 int launch_ctc_forward_tile(const ForwardTileArgs& a, std::string* err) { return launch_ctc_forward_tile_on(a, g_stream, err); }
+int launch_ctc_viterbi_tiled_on(const ViterbiTiledArgs& a, hipStream_t stream, std::string* err);
+int launch_ctc_viterbi_tiled(const ViterbiTiledArgs& a, std::string* err) { return launch_ctc_viterbi_tiled_on(a, g_stream, err); }
 int launch_ctc_posteriors_on(const PosteriorsArgs& a, hipStream_t stream, std::string* err);
 int launch_ctc_posteriors(const PosteriorsArgs& a, std::string* err) { return launch_ctc_posteriors_on(a, g_stream, err); }
 int launch_ctc_grad_rows_on(const GradRowsArgs& a, hipStream_t stream, std::string* err);

@@ -6,6 +6,9 @@
 //   ctc_viterbi_utt                the best path, its columns in LDS            (kernel ctc_viterbi)
 //   ctc_viterbi_long_utt           the best path, its columns in device memory, its frames in segments  (ctc_viterbi_long)
 //   ctc_forward_hyp / _wave_hyp    the sum over all paths                       (ctc_forward / ctc_forward_wave)
+//   ctc_forward_tile_body          the same sum, a tile of states and frames at a time  (ctc_forward_tile)
+//   ctc_viterbi_tile_body, ctc_viterbi_cone_utt   ctc_viterbi_long's best path on those tiles, then traced back segment by
+//                                  segment inside the cone under the path       (ctc_viterbi_tile, ctc_viterbi_cone)
 //   ctc_posteriors_utt             the forward-backward                         (ctc_posteriors)
 //   ctc_grad_row                   the gradient of the likelihood, row by row   (ctc_grad_rows)
 //   ctc_find_phrase / _wave_phrase a phrase's occurrences, free start and end   (ctc_find / ctc_find_wave)
@@ -19,7 +22,8 @@
 // The shared pieces, and who uses them:
 //   viterbi_backtrace                                    ctc_viterbi, ctc_viterbi_gaps
 //   viterbi_backtrace_span (a segment of it)             ctc_viterbi_long, ctc_viterbi_gaps_long
-//   fold_token_logp                                      ctc_viterbi, ctc_viterbi_gaps, ctc_viterbi_long, ctc_viterbi_gaps_long
+//   fold_token_logp                                      ctc_viterbi, ctc_viterbi_gaps, ctc_viterbi_long, ctc_viterbi_gaps_long, ctc_viterbi_cone
+//   forward_group, forward_tile_window, forward_tile_live  ctc_forward_tile, ctc_viterbi_tile, ctc_viterbi_cone
 //   gap_step                                             ctc_viterbi_gaps, ctc_viterbi_gaps_long
 //   group_setup, EntrySource, FrameEntries               ctc_find, ctc_find_wave, ctc_viterbi_gaps
 //   thread_setup                                         ctc_find, ctc_viterbi_gaps
@@ -844,9 +848,10 @@ struct ForwardTileHyp {
   double* edge;        // [(state blocks - 1) * FORWARD_TILE_RING * FB] block b's last state, frame t at ring slot (t / FB) % 3
   int32_t T, L, is_prob, GB, FB, pad;
 };
-// One tile of a launch: state block i, time block j of hypothesis hyp
+// One tile of a launch: state block i, time block j of hypothesis hyp. keep (ctc_viterbi_tile; 0 for ctc_forward_tile): 1 + the
+// checkpoint the tile also stores its block of the column into, 0 for none
 struct ForwardTile {
-  int32_t hyp, i, j, pad;
+  int32_t hyp, i, j, keep;
 };
 
 // How a hypothesis is cut: a pure function of (T, L, budget, tile_groups, tile_frames); decoder.py's _score_long_plan is the
@@ -1035,6 +1040,403 @@ CTC_HD void ctc_forward_tile_body(Ctx& cx, const ForwardTileHyp& hyp, int bi, in
     const double before = jf == 2 ? p[k][1] : (cf > 0 ? (lc > 0 ? fin[lc - 1] : edge_in[slot_j + (T - 1 - t0)]) : NEG);
     *hyp.logp = align_lse2(last, before);
   }
+}
+
+// ---- ctc_viterbi_tile, ctc_viterbi_cone ----------------------------------------------------------------------------------------
+// ctc_viterbi_long's best path on ctc_forward_tile's scheme ("Forced alignment of long transcripts, tiled"): the
+// same states, window, operands, order of comparisons and additions and tie rules, so the same bits, whatever the tile shape.
+//   pass A, ctc_viterbi_tile: the recursion without back-pointers over tiles (state block i, time block j), one launch per
+//     diagonal. A segment is KB time blocks, K = KB * FB frames; segment j holds the frames j K .. min((j + 1) K, T) - 1. A tile
+//     whose last frame is j K - 1 also stores its block of the column into checkpoint j - 1 (viterbi_tile_keep: the host
+//     decides, in the tile's record). The tile that holds state S - 1 at frame T - 1 writes the score and the end state.
+//   pass B, ctc_viterbi_cone: one workgroup per utterance, the segments from last to first. The best path into state s_e of a
+//     segment's last frame e descends at most two states a frame: at frame t it lies in the cone [s_e - 2 (e - t), s_e]. Only
+//     the groups b_lo = max(0, s_e - 2 (e - (j K - 1))) >> 2 .. b_hi = s_e >> 2 are restored from checkpoint j - 1, a group per
+//     thread, and run through the segment's frames once more, now with back-pointers in LDS; thread 0 traces the segment back
+//     and hands the state of frame j K - 1 and the open span down to the segment below.
+// Below b_lo the cone reads -inf. That value serves the step into state 4 b_lo and the skip into 4 b_lo + 1 alone; at the
+// segment's first frame j K both lie under the cone's lowest state s_e - 2 (e - j K) >= 4 b_lo + 2, and what is wrong at frame
+// t is wrong at most two states higher at frame t + 1, where the cone's lowest state is two higher as well.
+constexpr int32_t ALIGN_TILED_MAX_SEGMENT = 448;  // K at most: a band of K / 2 + 2 = 226 groups, one per thread of 256
+// A segment's back-pointers: the row of the frame r frames before e holds the groups max(0, s_e - 2 r) >> 2 .. s_e >> 2, at most
+// r / 2 + 2 bytes of four 2-bit entries. K rows: 2 K + floor((K - 1)^2 / 4) bytes, 50848 at K = 448, next to 4096 bytes of
+// exchange columns and the state handed down in the 65536 bytes of LDS a workgroup may use.
+CTC_HD int32_t cone_row_off(int32_t r) { return r > 0 ? 2 * r + ((r - 1) * (r - 1)) / 4 : 0; }
+constexpr int32_t ALIGN_TILED_BP_BYTES = 2 * ALIGN_TILED_MAX_SEGMENT + ((ALIGN_TILED_MAX_SEGMENT - 1) * (ALIGN_TILED_MAX_SEGMENT - 1)) / 4;
+static_assert(ALIGN_TILED_BP_BYTES == 50848 && ALIGN_TILED_BP_BYTES + 2 * 8 * FORWARD_TILE_MAX_GROUPS + 16 <= 65536, "a segment's rows fit LDS");
+static_assert(ALIGN_TILED_MAX_SEGMENT / 2 + 2 <= FORWARD_TILE_MAX_GROUPS, "a thread per group of the band");
+
+// One utterance of a tiled alignment, validated by the host as an AlignUtt is. col, edge, ckpt and s_end are its own.
+struct AlignTiledUtt {
+  const void* x;       // [T, V] logits or probabilities, of the launch's dtype
+  const double* lse;   // [T] log-sum-exp of each row (not read when is_prob)
+  const int32_t* lab;  // [L] target labels
+  double* col;         // [4 * align_chunks(L)] every group's four states after the last frame a tile took it through; -inf before
+  double* edge;        // [(state blocks - 1) * FORWARD_TILE_RING * FB] block b's last state, frame t at ring slot (t / FB) % 3
+  double* ckpt;        // [(segments - 1) * 4 * align_chunks(L)] checkpoint j - 1: the column of frame j K - 1; -inf before
+  int32_t* s_end;      // [1] the end state: pass A writes it, pass B starts from it
+  int32_t* path;       // [T] out
+  int32_t* tok_start;  // [L] out
+  int32_t* tok_end;    // [L] out
+  double* tok_logp;    // [L] out (fold != 0)
+  double* score;       // [1] out: the last column's value at the end state
+  int32_t T, L, is_prob, GB, FB, KB;
+};
+
+// How an utterance is cut: a pure function of its arguments; decoder.py's _align_tiled_plan is the same rule. The budget bounds
+// the bytes and never changes the cut: the checkpoints are not shrunk by longer segments than the cone takes.
+struct AlignTiledPlan {
+  int32_t GB = 0, FB = 0, nI = 0, nJ = 0, KB = 0;
+  int64_t K = 0, n = 0, bytes = 0;  // the frames of a segment, the segments, and the column, edge rows and checkpoints
+};
+CTC_HD AlignTiledPlan align_tiled_plan(int32_t T, int32_t L, int64_t budget, int32_t tile_groups, int32_t tile_frames, int32_t segment_blocks) {
+  (void)budget;
+  AlignTiledPlan p;
+  if (T <= 0) return p;
+  const int64_t nch = align_chunks(L);
+  const int32_t cap = T < ALIGN_TILED_MAX_SEGMENT ? T : ALIGN_TILED_MAX_SEGMENT;
+  p.GB = tile_groups > 0 ? tile_groups : FORWARD_TILE_MAX_GROUPS;
+  p.nI = (int32_t)((nch + p.GB - 1) / p.GB);
+  p.FB = tile_frames > 0 ? tile_frames : FORWARD_TILE_FRAMES;
+  p.FB = p.FB > cap ? cap : p.FB;
+  p.nJ = (T + p.FB - 1) / p.FB;
+  p.KB = segment_blocks > 0 ? segment_blocks : ALIGN_TILED_MAX_SEGMENT / p.FB;
+  p.K = (int64_t)p.KB * p.FB;
+  p.n = (T + p.K - 1) / p.K;
+  p.bytes = 8 * (4 * nch + (int64_t)FORWARD_TILE_RING * (p.nI - 1) * p.FB) + 32 * nch * (p.n - 1);
+  return p;
+}
+
+// ForwardTile::keep of tile (., j) of an utterance of T frames: its last frame is the one before segment (j + 1) / KB
+CTC_HD int32_t viterbi_tile_keep(int32_t T, int32_t FB, int32_t KB, int32_t j) {
+  return (j + 1) % KB == 0 && (int64_t)(j + 1) * FB < T ? (j + 1) / KB : 0;
+}
+
+// One frame of one group of the best-path recursion, in place: viterbi_long_frames' comparisons and additions -- stay, then
+// step, then skip, with strict > -- over forward_step's operands. Returns the group's four 2-bit back-pointers.
+CTC_HD unsigned viterbi_step(const ForwardGroup& g, double pm1, double e_blank, double e0, double e1, double* p) {
+  const double NEG = align_neg_inf();
+  const double p0 = p[0], p1 = p[1], p2 = p[2], p3 = p[3];
+  double b0 = p0, b1 = NEG, b2 = NEG, b3 = NEG;
+  unsigned q4 = 0;
+  if (pm1 > b0) b0 = pm1, q4 = 1u;
+  if (g.l0 >= 0) {
+    unsigned q = 0;
+    b1 = p1;
+    if (p0 > b1) b1 = p0, q = 1u;
+    if (g.skip0 && pm1 > b1) b1 = pm1, q = 2u;
+    q4 |= q << 2;
+    b1 += e0;
+  }
+  if (g.blank2) {
+    unsigned q = 0;
+    b2 = p2;
+    if (p1 > b2) b2 = p1, q = 1u;
+    q4 |= q << 4;
+    b2 += e_blank;
+  }
+  if (g.l1 >= 0) {
+    unsigned q = 0;
+    b3 = p3;
+    if (p2 > b3) b3 = p2, q = 1u;
+    if (g.skip1 && p1 > b3) b3 = p1, q = 2u;
+    q4 |= q << 6;
+    b3 += e1;
+  }
+  p[0] = b0 + e_blank, p[1] = b1, p[2] = b2, p[3] = b3;
+  return q4;
+}
+
+// Pass A. Tile (bi, bj) of an utterance of a matrix of dtype DT, by the threads of cx as in ctc_forward_tile_body -- its
+// geometry, its ring of edge rows, its requests a frame ahead, its two-sided bound on a neighbour's state -- with
+// viterbi_step in place of forward_step; a second copy, so that ctc_forward_tile keeps its instructions.
+template <int DT, class Ctx>
+CTC_HD void ctc_viterbi_tile_body(Ctx& cx, const AlignTiledUtt& utt, int bi, int bj, int keep, int V, int blank, double clip_lo, double* lds) {
+  typedef typename AlignRaw<DT>::type Raw;
+  constexpr int G = Ctx::GROUPS, W = FORWARD_TILE_MAX_GROUPS;
+  const void* const x = utt.x;  // (the record, once: the loop below reads none of it again)
+  const double* const lse = utt.lse;
+  const int32_t* const lab = utt.lab;
+  const int T = utt.T, L = utt.L, GB = utt.GB, FB = utt.FB;
+  const bool is_prob = utt.is_prob != 0;
+  const int S = 2 * L + 1, nch = align_chunks(L);
+  const double NEG = align_neg_inf();
+  const int c0 = bi * GB, gb = nch - c0 < GB ? nch - c0 : GB;  // the block's first group, and how many it has
+  const int t0 = bj * FB, t1 = (T - t0 < FB ? T : t0 + FB) - 1;  // the tile's frames, both included
+  const int ts = t0 > 0 ? t0 : 1;                                // the first frame of the recursion here
+  const size_t ring = (size_t)FORWARD_TILE_RING * (size_t)FB;
+  const int slot_j = (bj % FORWARD_TILE_RING) * FB, slot_m = ((bj + FORWARD_TILE_RING - 1) % FORWARD_TILE_RING) * FB + FB - 1;
+  const double* const edge_in = bi > 0 ? utt.edge + (size_t)(bi - 1) * ring : nullptr;
+  double* const edge_out = c0 + gb < nch ? utt.edge + (size_t)bi * ring : nullptr;
+  ForwardGroup g[G];
+  int i0[G], i1[G];  // the columns a group's two labels read (the blank's where the target ends before them)
+  double p[G][4];    // states
+  Raw v0[G], v1[G];  // the entries of the frame in hand at those columns, as loaded
+  CTC_UNROLL
+  for (int k = 0; k < G; ++k) {
+    const int lc = cx.tid + k * cx.nt;
+    if (lc < gb) {
+      g[k] = forward_group(lab, L, c0 + lc);
+      const double* at = utt.col + 4 * (size_t)(c0 + lc);
+      p[k][0] = at[0], p[k][1] = at[1], p[k][2] = at[2], p[k][3] = at[3];
+    } else {
+      g[k] = ForwardGroup{-1, -1, false, false, false};
+      p[k][0] = p[k][1] = p[k][2] = p[k][3] = NEG;
+    }
+    i0[k] = g[k].l0 >= 0 ? g[k].l0 : blank;
+    i1[k] = g[k].l1 >= 0 ? g[k].l1 : blank;
+  }
+  // (always 0, but per thread as far as the compiler knows: see ctc_forward_hyp)
+  const int per_thread_zero = g[0].l0 == -2 ? 1 : 0;
+  const double* const lse_v = lse + per_thread_zero;
+  if (bi == 0 && bj == 0 && cx.tid == 0) {  // frame 0, by this tile alone
+    const double lse0 = is_prob ? 0.0 : lse[0];
+    p[0][0] = align_emit(x, DT, (size_t)blank, lse0, is_prob, clip_lo);
+    if (L > 0) p[0][1] = align_emit(x, DT, (size_t)lab[0], lse0, is_prob, clip_lo);
+  }
+  // the column of the frame before the first step, as the tile before left it
+  CTC_UNROLL
+  for (int k = 0; k < G; ++k) {
+    const int lc = cx.tid + k * cx.nt;
+    if (lc >= gb) break;
+    lds[((ts - 1) & 1) * W + lc] = p[k][3];
+    if (t0 == 0 && edge_out && lc == gb - 1) edge_out[slot_j] = p[k][3];
+  }
+  cx.sync();
+  // the first step's entries (a tile of frame 0 alone: that frame's again, never used)
+  const bool first_reads_edge = cx.tid == 0 && edge_in != nullptr;
+  const int tf = ts <= t1 ? ts : t1;
+  int clo = 0, chi = -1, clo_prev, chi_prev;
+  forward_tile_window(ts - 1, T, L, &clo_prev, &chi_prev);
+  if (ts <= t1) forward_tile_window(ts, T, L, &clo, &chi);
+  const size_t rowf = (size_t)tf * (size_t)V;
+  Raw vb = align_load_raw<DT>(x, rowf + (size_t)blank);
+  double lse_t = lse_v[tf];
+  double below = first_reads_edge ? edge_in[ts - 1 >= t0 ? slot_j + (ts - 1 - t0) : slot_m] : NEG;
+  CTC_UNROLL
+  for (int k = 0; k < G; ++k) {
+    v0[k] = align_load_raw<DT>(x, rowf + (size_t)i0[k]);
+    v1[k] = align_load_raw<DT>(x, rowf + (size_t)i1[k]);
+  }
+  for (int t = ts; t <= t1; ++t) {
+    const double* prev = lds + ((t - 1) & 1) * W;
+    double* cur = lds + (t & 1) * W;
+    // the neighbours' states first
+    double pm1[G];
+    CTC_UNROLL
+    for (int k = 0; k < G; ++k) {
+      const int lc = cx.tid + k * cx.nt, c = c0 + lc;
+      if (lc >= gb) break;
+      const bool take = c >= clo && c <= chi && c > 0 && c - 1 >= clo_prev && c - 1 <= chi_prev;
+      pm1[k] = take ? (lc > 0 ? prev[lc - 1] : below) : NEG;
+    }
+    // then ask for frame t + 1 (after the tile's last frame: that frame again)
+    const int tn = t + 1 <= t1 ? t + 1 : t;
+    int nlo = 0, nhi = -1;
+    if (t + 1 <= t1) forward_tile_window(tn, T, L, &nlo, &nhi);
+    const size_t row = (size_t)tn * (size_t)V;
+    const Raw nvb = align_load_raw<DT>(x, row + (size_t)blank);
+    const double nlse = lse_v[tn];
+    const double nbelow = first_reads_edge ? edge_in[tn - 1 >= t0 ? slot_j + (tn - 1 - t0) : slot_m] : NEG;
+    Raw n0[G], n1[G];
+    CTC_UNROLL
+    for (int k = 0; k < G; ++k) {
+      n0[k] = align_load_raw<DT>(x, row + (size_t)i0[k]);
+      n1[k] = align_load_raw<DT>(x, row + (size_t)i1[k]);
+    }
+    const double lse_use = is_prob ? 0.0 : lse_t;
+    const double e_blank = align_emit_of_value(align_widen<DT>(vb), lse_use, is_prob, clip_lo);
+    CTC_UNROLL
+    for (int k = 0; k < G; ++k) {
+      const int lc = cx.tid + k * cx.nt, c = c0 + lc;
+      if (lc >= gb) break;
+      if (c < clo || c > chi) continue;
+      const double e0 = align_emit_of_value(align_widen<DT>(v0[k]), lse_use, is_prob, clip_lo);
+      const double e1 = align_emit_of_value(align_widen<DT>(v1[k]), lse_use, is_prob, clip_lo);
+      viterbi_step(g[k], pm1[k], e_blank, e0, e1, p[k]);
+      cur[lc] = p[k][3];
+      if (edge_out && lc == gb - 1) edge_out[slot_j + (t - t0)] = p[k][3];
+    }
+    clo_prev = clo, chi_prev = chi;
+    clo = nlo, chi = nhi, vb = nvb, lse_t = nlse, below = nbelow;
+    CTC_UNROLL
+    for (int k = 0; k < G; ++k) v0[k] = n0[k], v1[k] = n1[k];
+    cx.sync();  // the one barrier of a frame: the columns swap roles
+  }
+  // the column, for the tile after this one, and into the checkpoint of the segment that starts behind this tile's last frame
+  double* const kept = keep > 0 ? utt.ckpt + (size_t)(keep - 1) * (size_t)(4 * nch) : nullptr;
+  CTC_UNROLL
+  for (int k = 0; k < G; ++k) {
+    const int lc = cx.tid + k * cx.nt;
+    if (lc >= gb) break;
+    double* at = utt.col + 4 * (size_t)(c0 + lc);
+    at[0] = p[k][0], at[1] = p[k][1], at[2] = p[k][2], at[3] = p[k][3];
+    if (kept) {
+      double* to = kept + 4 * (size_t)(c0 + lc);
+      to[0] = p[k][0], to[1] = p[k][1], to[2] = p[k][2], to[3] = p[k][3];
+    }
+  }
+  // the end, by the tile that holds the last blank at the last frame: the last label is preferred over the trailing blank,
+  // and the score is the last column's value (state S - 2 read as ctc_forward_tile_body reads `before`)
+  const int cf = (S - 1) >> 2, jf = (S - 1) & 3;
+  if (t1 != T - 1 || cf < c0 || cf >= c0 + gb) return;
+  const double* fin = lds + ((T - 1) & 1) * W;
+  CTC_UNROLL
+  for (int k = 0; k < G; ++k) {
+    const int lc = cx.tid + k * cx.nt;
+    if (c0 + lc != cf) continue;
+    const double last = jf == 2 ? p[k][2] : p[k][0];
+    const double before = jf == 2 ? p[k][1] : (cf > 0 ? (lc > 0 ? fin[lc - 1] : edge_in[slot_j + (T - 1 - t0)]) : NEG);
+    const bool label = L > 0 && before >= last;
+    *utt.s_end = label ? S - 2 : S - 1;
+    *utt.score = label ? before : last;
+  }
+}
+
+// The back-trace of one segment out of its triangular rows, by one thread: viterbi_backtrace_span over the frames e down to
+// t_lo, from state s of frame e = s_e. Leaves in s the state of frame t_lo - 1 (of frame 0 when t_lo is 0), in `open` the
+// label whose span is still open and in open_lab its id.
+CTC_HD void viterbi_backtrace_cone(int& s, int& open, int32_t& open_lab, int e, int t_lo, int s_e, const uint8_t* bp, const int32_t* lab,
+                                   int32_t* path, int32_t* tok_start, int32_t* tok_end, int blank) {
+  for (int t = e; t >= t_lo; --t) {
+    if (s & 1) {
+      const int k = s >> 1;
+      if (k != open) tok_end[k] = t + 1, open = k, open_lab = lab[k];
+      tok_start[k] = t;
+      path[t] = open_lab;
+    } else {
+      path[t] = blank;
+    }
+    if (t > 0) {
+      const int r = e - t, low = s_e - 2 * r;
+      const int at = cone_row_off(r) + (s >> 2) - (low > 0 ? low >> 2 : 0);
+      const unsigned b = (bp[at] >> (2 * (s & 3))) & 3u;
+      s -= (int)b;
+      if (s < 0) s = 0;
+    }
+  }
+}
+
+// Pass B, by the threads of cx (tid, nt, sync(); Ctx::GROUPS * nt >= ALIGN_TILED_MAX_SEGMENT / 2 + 2). lds: 2 *
+// FORWARD_TILE_MAX_GROUPS doubles, bp: ALIGN_TILED_BP_BYTES, hand: one int -- all shared by the threads of cx.
+template <int DT, class Ctx>
+CTC_HD void ctc_viterbi_cone_utt(Ctx& cx, const AlignTiledUtt& utt, int V, int blank, int fold, double clip_lo, double* lds, uint8_t* bp,
+                                 int* hand) {
+  typedef typename AlignRaw<DT>::type Raw;
+  constexpr int G = Ctx::GROUPS, W = FORWARD_TILE_MAX_GROUPS;
+  const void* const x = utt.x;
+  const double* const lse = utt.lse;
+  const int32_t* const lab = utt.lab;
+  const int T = utt.T, L = utt.L, K = utt.KB * utt.FB;
+  if (T <= 0) return;
+  const bool is_prob = utt.is_prob != 0;
+  const int nch = align_chunks(L), nseg = (T - 1) / K + 1;
+  const double NEG = align_neg_inf();
+  int s = *utt.s_end, open = -1;
+  int32_t open_lab = blank;
+  for (int j = nseg - 1; j >= 0; --j) {
+    const int f0 = j * K, e = (T - f0 < K ? T : f0 + K) - 1;  // the segment's frames, both included
+    const int ts = f0 > 0 ? f0 : 1;                            // the first frame of the recursion here
+    const int s_e = s, under = s_e - 2 * (e - f0 + 1);
+    const int b_lo = under > 0 ? under >> 2 : 0, nb = (s_e >> 2) - b_lo + 1;  // the band: its first group, and how many it has
+    const double* const from = j > 0 ? utt.ckpt + (size_t)(j - 1) * (size_t)(4 * nch) : nullptr;
+    ForwardGroup g[G];
+    int i0[G], i1[G];
+    double p[G][4];
+    Raw v0[G], v1[G];
+    CTC_UNROLL
+    for (int k = 0; k < G; ++k) {
+      const int lc = cx.tid + k * cx.nt;
+      g[k] = lc < nb ? forward_group(lab, L, b_lo + lc) : ForwardGroup{-1, -1, false, false, false};
+      p[k][0] = p[k][1] = p[k][2] = p[k][3] = NEG;
+      if (lc < nb && from) {
+        const double* at = from + 4 * (size_t)(b_lo + lc);
+        p[k][0] = at[0], p[k][1] = at[1], p[k][2] = at[2], p[k][3] = at[3];
+      }
+      i0[k] = g[k].l0 >= 0 ? g[k].l0 : blank;
+      i1[k] = g[k].l1 >= 0 ? g[k].l1 : blank;
+    }
+    const int per_thread_zero = g[0].l0 == -2 ? 1 : 0;  // (see ctc_forward_hyp)
+    const double* const lse_v = lse + per_thread_zero;
+    if (j == 0 && cx.tid == 0) {  // frame 0
+      const double lse0 = is_prob ? 0.0 : lse[0];
+      p[0][0] = align_emit(x, DT, (size_t)blank, lse0, is_prob, clip_lo);
+      if (L > 0) p[0][1] = align_emit(x, DT, (size_t)lab[0], lse0, is_prob, clip_lo);
+    }
+    CTC_UNROLL
+    for (int k = 0; k < G; ++k) {
+      const int lc = cx.tid + k * cx.nt;
+      if (lc >= nb) break;
+      lds[((ts - 1) & 1) * W + lc] = p[k][3];
+    }
+    cx.sync();
+    const int tf = ts <= e ? ts : e;
+    int clo = 0, chi = -1, clo_prev, chi_prev;
+    forward_tile_window(ts - 1, T, L, &clo_prev, &chi_prev);
+    if (ts <= e) forward_tile_window(ts, T, L, &clo, &chi);
+    const size_t rowf = (size_t)tf * (size_t)V;
+    Raw vb = align_load_raw<DT>(x, rowf + (size_t)blank);
+    double lse_t = lse_v[tf];
+    CTC_UNROLL
+    for (int k = 0; k < G; ++k) {
+      v0[k] = align_load_raw<DT>(x, rowf + (size_t)i0[k]);
+      v1[k] = align_load_raw<DT>(x, rowf + (size_t)i1[k]);
+    }
+    for (int t = ts; t <= e; ++t) {
+      const double* prev = lds + ((t - 1) & 1) * W;
+      double* cur = lds + (t & 1) * W;
+      double pm1[G];
+      CTC_UNROLL
+      for (int k = 0; k < G; ++k) {
+        const int lc = cx.tid + k * cx.nt, c = b_lo + lc;
+        if (lc >= nb) break;
+        const bool take = c >= clo && c <= chi && lc > 0 && c - 1 >= clo_prev && c - 1 <= chi_prev;  // (below the band: -inf)
+        pm1[k] = take ? prev[lc - 1] : NEG;
+      }
+      const int tn = t + 1 <= e ? t + 1 : t;
+      int nlo = 0, nhi = -1;
+      if (t + 1 <= e) forward_tile_window(tn, T, L, &nlo, &nhi);
+      const size_t row = (size_t)tn * (size_t)V;
+      const Raw nvb = align_load_raw<DT>(x, row + (size_t)blank);
+      const double nlse = lse_v[tn];
+      Raw n0[G], n1[G];
+      CTC_UNROLL
+      for (int k = 0; k < G; ++k) {
+        n0[k] = align_load_raw<DT>(x, row + (size_t)i0[k]);
+        n1[k] = align_load_raw<DT>(x, row + (size_t)i1[k]);
+      }
+      const double lse_use = is_prob ? 0.0 : lse_t;
+      const double e_blank = align_emit_of_value(align_widen<DT>(vb), lse_use, is_prob, clip_lo);
+      // this frame's row: the groups the cone has here
+      const int r = e - t, low = s_e - 2 * r, row_lo = low > 0 ? low >> 2 : 0;
+      uint8_t* const bp_row = bp + cone_row_off(r);
+      CTC_UNROLL
+      for (int k = 0; k < G; ++k) {
+        const int lc = cx.tid + k * cx.nt, c = b_lo + lc;
+        if (lc >= nb) break;
+        if (c < clo || c > chi) continue;
+        const double e0 = align_emit_of_value(align_widen<DT>(v0[k]), lse_use, is_prob, clip_lo);
+        const double e1 = align_emit_of_value(align_widen<DT>(v1[k]), lse_use, is_prob, clip_lo);
+        const unsigned q4 = viterbi_step(g[k], pm1[k], e_blank, e0, e1, p[k]);
+        cur[lc] = p[k][3];
+        if (c >= row_lo) bp_row[c - row_lo] = (uint8_t)q4;
+      }
+      clo_prev = clo, chi_prev = chi;
+      clo = nlo, chi = nhi, vb = nvb, lse_t = nlse;
+      CTC_UNROLL
+      for (int k = 0; k < G; ++k) v0[k] = n0[k], v1[k] = n1[k];
+      cx.sync();  // the one barrier of a frame: the columns swap roles (behind the last: the rows are complete)
+    }
+    // s and open go on into the segment below: a label's span may cross the boundary
+    if (cx.tid == 0) {
+      viterbi_backtrace_cone(s, open, open_lab, e, f0, s_e, bp, lab, utt.path, utt.tok_start, utt.tok_end, blank);
+      *hand = s;
+    }
+    cx.sync();  // (thread 0 is through with the rows; every thread takes the state handed down)
+    s = *hand;
+  }
+  if (!fold) return;
+  fold_token_logp(cx, x, DT, lse, lab, utt.tok_start, utt.tok_end, utt.tok_logp, T, L, V, is_prob, fold, clip_lo);
 }
 
 // ---- ctc_posteriors ----------------------------------------------------------------------------------------------------------

@@ -7,6 +7,7 @@
 //   ctc_find, ctc_viterbi_gaps        (256 threads up to 511 labels, 1024 above)
 //   ctc_forward_wave, ctc_find_wave a wavefront per record of at most 127 labels
 //   ctc_forward_tile                a workgroup per tile of a hypothesis' states and frames, a launch per diagonal of tiles
+//   ctc_viterbi_tile, _cone         the best path on the same tiles with checkpoints; then a workgroup per utterance traces back
 //   ctc_grad_rows                   G threads per row of a dense ctc_posteriors launch's tables
 //   row_argmax, row_lse_argmax      G lanes per row; both fold with row_fold_arg
 //   greedy_collapse                 a wavefront per utterance
@@ -205,6 +206,32 @@ __global__ __launch_bounds__(FORWARD_TILE_MAX_GROUPS) void ctc_forward_tile(cons
 
 __global__ __launch_bounds__(256) void ctc_forward_tile_fill(double* p, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) p[i] = align_neg_inf();
+}
+
+// ---------------------------------------------------------------------------------------------
+// ctc_viterbi_tile: ctc_forward_tile's workgroup per tile and launch per diagonal for the best path, behind the same fill
+// (which here covers the checkpoints too); a tile at a segment's end also stores its block of the column into a checkpoint.
+// ctc_viterbi_cone: one workgroup of 256 threads per utterance, one launch behind the last diagonal: per segment, last to
+// first, the band of groups under the path's state in registers, a group per thread, the segment's back-pointers in LDS in
+// triangular rows, and the back-trace by thread 0 out of LDS (ctc_align.h).
+// ---------------------------------------------------------------------------------------------
+template <int DT>
+__global__ __launch_bounds__(FORWARD_TILE_MAX_GROUPS) void ctc_viterbi_tile(const AlignTiledUtt* utts, const ForwardTile* tiles, int V,
+                                                                            int blank, double clip_lo) {
+  __shared__ double tile_cols[2 * FORWARD_TILE_MAX_GROUPS];
+  const ForwardTile tile = tiles[blockIdx.x];
+  ForwardGpuCtx cx{(int)threadIdx.x, FORWARD_TILE_MAX_GROUPS};
+  ctc_viterbi_tile_body<DT>(cx, utts[tile.hyp], tile.i, tile.j, tile.keep, V, blank, clip_lo, tile_cols);
+}
+
+template <int DT>
+__global__ __launch_bounds__(FORWARD_TILE_MAX_GROUPS) void ctc_viterbi_cone(const AlignTiledUtt* utts, int V, int blank, int fold,
+                                                                            double clip_lo) {
+  __shared__ double cone_cols[2 * FORWARD_TILE_MAX_GROUPS];
+  __shared__ uint8_t cone_bp[ALIGN_TILED_BP_BYTES];
+  __shared__ int cone_hand;
+  ForwardGpuCtx cx{(int)threadIdx.x, FORWARD_TILE_MAX_GROUPS};
+  ctc_viterbi_cone_utt<DT>(cx, utts[blockIdx.x], V, blank, fold, clip_lo, cone_cols, cone_bp, &cone_hand);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -876,6 +903,33 @@ int launch_ctc_forward_tile_on(const ForwardTileArgs& a, hipStream_t stream, std
       for (int32_t d = 0; d < a.n_diags; ++d)
         hipLaunchKernelGGL(ctc_forward_tile<DT>, dim3((unsigned)(a.diag_off[d + 1] - a.diag_off[d])), dim3(FORWARD_TILE_MAX_GROUPS), 0, stream,
                            a.hyps, a.tiles + a.diag_off[d], a.n_labels, a.blank, a.clip_lo);
+    });
+  });
+}
+
+// Pass A -- the fill, then the diagonals -- under one pair of events, pass B behind it under another
+int launch_ctc_viterbi_tiled_on(const ViterbiTiledArgs& a, hipStream_t stream, std::string* err) {
+  if (a.n_utts <= 0) return 0;
+  if (a.dtype < 0 || a.dtype > 3 || !a.utts || !a.tiles || !a.diag_off || !a.fill || a.n_fill < 1 || a.n_diags < 1 || a.n_labels < 1 ||
+      a.blank < 0 || a.blank >= a.n_labels || a.diag_off[0] != 0)
+    return bad_launch(err, "ctc_viterbi_tile: bad arguments");
+  for (int32_t d = 0; d < a.n_diags; ++d)
+    if (a.diag_off[d + 1] <= a.diag_off[d]) return bad_launch(err, "ctc_viterbi_tile: a diagonal without tiles");
+  if (timed_launch(K_VITERBI_TILE, stream, err, [&] {
+        const int64_t fill_blocks = (a.n_fill + 255) / 256;
+        hipLaunchKernelGGL(ctc_forward_tile_fill, dim3((unsigned)(fill_blocks < 4096 ? fill_blocks : 4096)), dim3(256), 0, stream, a.fill, a.n_fill);
+        for_dtype(a.dtype, [&](auto dt) {
+          constexpr int DT = decltype(dt)::value;
+          for (int32_t d = 0; d < a.n_diags; ++d)
+            hipLaunchKernelGGL(ctc_viterbi_tile<DT>, dim3((unsigned)(a.diag_off[d + 1] - a.diag_off[d])), dim3(FORWARD_TILE_MAX_GROUPS), 0, stream,
+                               a.utts, a.tiles + a.diag_off[d], a.n_labels, a.blank, a.clip_lo);
+        });
+      }))
+    return -1;
+  return timed_launch(K_VITERBI_CONE, stream, err, [&] {
+    for_dtype(a.dtype, [&](auto dt) {
+      hipLaunchKernelGGL(ctc_viterbi_cone<decltype(dt)::value>, dim3((unsigned)a.n_utts), dim3(FORWARD_TILE_MAX_GROUPS), 0, stream, a.utts,
+                         a.n_labels, a.blank, a.fold, a.clip_lo);
     });
   });
 }

@@ -146,6 +146,7 @@ class ConfidenceOutputBeam(TokenOutputBeam):
 ALIGN_MAX_LABELS = 2047  # ALIGN_MAX_LABELS of csrc/ctc_align.h: 2 L + 1 states, two fp64 score columns in a workgroup's LDS
 ALIGN_LONG_MAX_LABELS = 1048575  # ALIGN_LONG_MAX_LABELS of csrc/ctc_align.h: 2 L + 1 states below 2^21 (align_long, score_long)
 SCORE_LONG_TILE_GROUPS = 256  # FORWARD_TILE_MAX_GROUPS of csrc/ctc_align.h: the groups of four states of a state block, at most
+ALIGN_TILED_MAX_SEGMENT = 448  # ALIGN_TILED_MAX_SEGMENT of csrc/ctc_align.h: the frames of a segment whose back-pointers fit LDS, at most
 SCORE_LONG_TILE_FRAMES = 64  # FORWARD_TILE_FRAMES of csrc/ctc_align.h: the frames of a time block when there are several state blocks
 ALIGN_BP_BUDGET = 1 << 30  # bytes of back-pointer tables one ctc_viterbi launch holds by default ("Forced alignment")
 
@@ -1494,6 +1495,9 @@ class BeamSearchDecoderCTC:
         self.last_align_long_timing_ms = (0.0, 0.0, 0.0, 0.0)
         self.last_align_long_launches = 0
         self.last_align_long_plan: List[Tuple[int, int]] = []
+        self.last_align_tiled_plan: List[Tuple[int, int, int, int, int, int]] = []
+        self.last_align_tiled_launches = self.last_align_tiled_tiles = self.last_align_tiled_groups = self.last_align_tiled_widest = 0
+        self.last_align_tiled_pass_ms = (0.0, 0.0)
         # ... and of the last score_long / score_long_batch call (ms: classification, row_lse, the fill and ctc_forward_tile's
         # launches, native call; diagonals launched, tiles in them, launch groups; the plan of every hypothesis launched)
         self.last_score_long_timing_ms = (0.0, 0.0, 0.0, 0.0)
@@ -2103,17 +2107,21 @@ class BeamSearchDecoderCTC:
         return out
 
     def _aligned_texts(self, what: str, logits_list: Any, targets: List[List[int]], fold: int, strict: bool, bp_budget: int,
-                       segment_frames: Optional[int]):
+                       segment_frames: Optional[int], tiles: Optional[Tuple[int, int, int]] = None):
         """-> (the AlignedText of every utterance, None for one without a path; (timing ms, launches, plan) of the native call,
-        None when none was made): the checked targets through ctcdec_align_batch (``segment_frames`` None) or
-        ctcdec_align_long_batch, and the words formed from the result."""
+        None when none was made): the checked targets through ctcdec_align_batch (``segment_frames`` None),
+        ctcdec_align_long_batch or, with ``tiles`` = (tile_groups, tile_frames, segment_blocks), ctcdec_align_tiled_batch --
+        then (counts, pass ms, tiled plan) follow in the stats --, and the words formed from the result."""
         n = len(targets)
         if n == 0:
             return [], None
         budget = bp_budget or ALIGN_BP_BUDGET
         with self._call_lock:
             batch, frames, ptrs, _ = self._stage_transcript_call(logits_list)
-            if segment_frames is None:
+            if tiles is not None:
+                keep = self._feasible(what, frames, targets, lambda T, L: self._align_tiled_plan(T, L, budget, *tiles)[5], budget, strict,
+                                      "plan (column, edge rows, checkpoints; align_long without tiled needs less memory)", "path")
+            elif segment_frames is None:
                 keep = self._feasible(what, frames, targets, self._bp_table_bytes, budget, strict, "back-pointer table", "path")
             else:
                 keep = self._feasible(what, frames, targets, lambda T, L: self._align_long_plan(T, L, budget, segment_frames)[2],
@@ -2128,7 +2136,9 @@ class BeamSearchDecoderCTC:
             lib = self._lib
             head = (self._handle, *self._c_utts(k_ptrs, k_frames), len(keep), batch.dtype, int(batch.is_device),
                     flat.ctypes.data_as(C.POINTER(C.c_int32)), B.off_ptr(off), fold, bp_budget)
-            if segment_frames is None:
+            if tiles is not None:
+                lib.check(lib.dll.ctcdec_align_tiled_batch(*head, *tiles, C.byref(res)))
+            elif segment_frames is None:
                 lib.check(lib.dll.ctcdec_align_batch(*head, C.byref(res)))
             else:
                 lib.check(lib.dll.ctcdec_align_long_batch(*head, segment_frames, C.byref(res)))
@@ -2155,6 +2165,11 @@ class BeamSearchDecoderCTC:
                 lib.check(lib.dll.ctcdec_alignment_plan(res, C.byref(sf), C.byref(ns), C.byref(npl)))
                 plan = [(int(sf[j]), int(ns[j])) for j in range(int(npl.value))]
                 stats = (tuple(float(v) for v in ms), int(launches.value), plan)
+                if tiles is not None:
+                    counts, ms2, p6 = (C.c_int64 * 4)(), (C.c_double * 2)(), C.POINTER(C.c_int64)()
+                    lib.check(lib.dll.ctcdec_alignment_tiled(res, counts, ms2, C.byref(p6), C.byref(npl)))
+                    stats += (tuple(int(v) for v in counts), tuple(float(v) for v in ms2),
+                              [tuple(int(p6[6 * j + k]) for k in range(6)) for j in range(int(npl.value))])
                 path_off = path_off.tolist()
             finally:
                 lib.dll.ctcdec_alignment_free(res)
@@ -2193,18 +2208,36 @@ class BeamSearchDecoderCTC:
         K = math.isqrt(32 * frames)
         return of(min(K if K * K == 32 * frames else K + 1, frames))
 
+    @staticmethod
+    def _align_tiled_plan(frames: int, n_labels: int, budget: int, tile_groups: int, tile_frames: int,
+                          segment_blocks: int) -> Tuple[int, int, int, int, int, int, int, int]:
+        """-> (GB, FB, nI, nJ, KB, bytes, K, n): how ctcdec_align_tiled_batch cuts an utterance (align_tiled_plan, csrc/ctc_align.h,
+        the same rule): state blocks of GB groups of four states, time blocks of FB frames, segments of KB time blocks -- K =
+        KB * FB frames, n of them --, and the bytes of the column, a ring of three time blocks per boundary between state blocks
+        and a checkpoint for every segment but the first. The budget bounds the bytes and never changes the cut."""
+        if frames <= 0:
+            return 0, 0, 0, 0, 0, 0, 0, 0
+        nch = (2 * n_labels + 1 + 3) // 4
+        gb = tile_groups if tile_groups > 0 else SCORE_LONG_TILE_GROUPS
+        n_i = -(-nch // gb)
+        fb = min(tile_frames if tile_frames > 0 else SCORE_LONG_TILE_FRAMES, frames, ALIGN_TILED_MAX_SEGMENT)
+        kb = segment_blocks if segment_blocks > 0 else ALIGN_TILED_MAX_SEGMENT // fb
+        n = -(-frames // (kb * fb))
+        return gb, fb, n_i, -(-frames // fb), kb, 8 * (4 * nch + 3 * (n_i - 1) * fb) + 32 * nch * (n - 1), kb * fb, n
+
     def align_long(self, logits: Any, text: Optional[str] = None, tokens: Optional[Sequence[int]] = None,
-                   confidence: Optional[str] = None) -> "AlignedText":
+                   confidence: Optional[str] = None, tiled: bool = False) -> "AlignedText":
         """Forced alignment of one long utterance: align_long_batch of a batch of one (a ValueError when no path exists)."""
         if isinstance(logits, (_ResidentBeams, _DeviceStreams)):
             raise NotImplementedError("align_long reads an utterance's matrix; the frames a stream has consumed are not kept")
         self._check_logits_dimension(logits)
         return self.align_long_batch([logits], None if text is None else [text], tokens=None if tokens is None else [tokens],
-                                     confidence=confidence)[0]
+                                     confidence=confidence, tiled=tiled)[0]
 
     def align_long_batch(self, logits_list: Any, texts: Optional[Sequence[str]] = None,
                          tokens: Optional[Sequence[Sequence[int]]] = None, confidence: Optional[str] = None, strict: bool = True,
-                         _bp_budget: int = 0, _segment_frames: int = 0) -> List[Optional["AlignedText"]]:
+                         tiled: bool = False, _bp_budget: int = 0, _segment_frames: int = 0, _tile_groups: int = 0,
+                         _tile_frames: int = 0, _segment_blocks: int = 0) -> List[Optional["AlignedText"]]:
         """align_batch for a lecture against its script: up to 1048575 target labels per utterance instead of 2047, and no
         back-pointer table of all frames (row_lse + ctc_viterbi_long, csrc/ctc_align_hip.hip). Arguments, targets, the
         probabilities-or-logits rule and ``strict`` are align_batch's, and for every input align_batch accepts the result is
@@ -2212,17 +2245,42 @@ class BeamSearchDecoderCTC:
         one is cut into segments of about sqrt(32 T) frames and takes two: one that keeps the score column every segment
         starts from, one that fills and traces back one segment's table at a time, last segment first. The score columns
         live in device memory, so align_batch stays the faster call for targets it accepts. ``last_align_long_plan`` holds
-        (segment_frames, n_segments) of every utterance aligned."""
+        (segment_frames, n_segments) of every utterance aligned.
+
+        ``tiled=True`` spreads one long utterance over many compute units (ctc_viterbi_tile + ctc_viterbi_cone): the states are
+        cut into blocks of 256 groups of four and the frames into blocks of 64, a tile (state block, time block) runs on one
+        workgroup and one launch takes a diagonal of tiles, as in score_long_batch; the column is kept every 448 frames, and a
+        second pass restores, per segment and from the last to the first, only the states that can reach the path, and traces
+        back. The result is the same, bit for bit. It takes more memory than the untiled plan (the checkpoints do not shrink)
+        and is the slower call for a batch of many utterances, which fills the chip already. ``last_align_tiled_plan`` holds
+        (tile_groups, tile_frames, state_blocks, time_blocks, segment_blocks, bytes) of every utterance aligned,
+        ``last_align_tiled_launches`` and ``last_align_tiled_tiles`` the diagonals launched and the tiles in them."""
         if isinstance(logits_list, (_ResidentBeams, _DeviceStreams)) or (
                 isinstance(logits_list, (list, tuple)) and any(isinstance(x, (_ResidentBeams, _DeviceStreams)) for x in logits_list)):
             raise NotImplementedError("align_long_batch reads utterances' matrices; the frames a stream has consumed are not kept")
         fold = _confidence_fold(confidence)
         if isinstance(_segment_frames, bool) or not isinstance(_segment_frames, (int, np.integer)) or not 0 <= int(_segment_frames) < 2 ** 31:
             raise ValueError("align_long: _segment_frames must be an int >= 0 (0: the library plans), not %r" % (_segment_frames,))
+        if not isinstance(tiled, (bool, np.bool_)):
+            raise ValueError("align_long: tiled must be a bool, not %r" % (tiled,))
+        cut = (("_tile_groups", _tile_groups, SCORE_LONG_TILE_GROUPS + 1), ("_tile_frames", _tile_frames, 2 ** 31),
+               ("_segment_blocks", _segment_blocks, 2 ** 31))
+        for name, v, top in cut:
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < top:
+                raise ValueError("align_long: %s must be an int in [0, %d) (0: the library's rule), not %r" % (name, top, v))
+            if v and not tiled:
+                raise ValueError("align_long: %s cuts the tiles of tiled=True; without tiled there are none" % name)
+        if tiled and _segment_frames:
+            raise ValueError("align_long: _segment_frames cuts the untiled call; tiled=True takes _tile_frames and _segment_blocks")
         logits_list, targets = self._one_target_each("align_long", logits_list, texts, tokens, ALIGN_LONG_MAX_LABELS)
-        out, stats = self._aligned_texts("align_long", logits_list, targets, fold, strict, int(_bp_budget), int(_segment_frames))
+        out, stats = self._aligned_texts("align_long", logits_list, targets, fold, strict, int(_bp_budget), int(_segment_frames),
+                                         tuple(int(v) for _name, v, _top in cut) if tiled else None)
         if stats is not None:
-            self.last_align_long_timing_ms, self.last_align_long_launches, self.last_align_long_plan = stats
+            self.last_align_long_timing_ms, self.last_align_long_launches, self.last_align_long_plan = stats[:3]
+        if stats is not None and tiled:
+            counts, self.last_align_tiled_pass_ms, self.last_align_tiled_plan = stats[3:]
+            (self.last_align_tiled_launches, self.last_align_tiled_tiles, self.last_align_tiled_groups,
+             self.last_align_tiled_widest) = counts
         return out
 
     # -- alignment with gaps (no reference analogue; DESIGN.md, "Alignment with gaps") --------------------

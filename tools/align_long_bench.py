@@ -10,10 +10,15 @@ events on the decode stream (last_align_long_timing_ms), medians of 3 steps afte
   gaps*     the same shapes through align_gaps_long_batch (row_lse_max + ctc_viterbi_gaps_long): gap-free targets next to
             ctc_viterbi_long and ctc_viterbi_gaps, alternating (gaps64, gaps4096, gaps2047, gapssegments), and the hour with a
             leading gap, a trailing gap and a gap per 500 labels next to align_long on its labels (gapshour)
+  tiled*    align_long_batch(tiled=True) (ctc_viterbi_tile between events around the fill and the diagonals, ctc_viterbi_cone
+            between events around its launch) next to align_long_batch untiled, alternating in one process on the same device
+            tensors and checked equal: the hour, the 20000-frame utterance and the three batch shapes (tiledhour, tiledsegments,
+            tiled64, tiled4096, tiled2047)
 Random logits and random targets: no kernel's time depends on the values. Every leg is a process of its own under `timeout`,
 started by this one, which never opens the device; the first leg that fails ends the run.
   python tools/align_long_bench.py [--out profiles/align_long_bench.txt] [--steps 3] [--legs short64,short4096,short2047,segments,hour]
-  python tools/align_long_bench.py --out profiles/align_gaps_long_bench.txt --legs gaps64,gaps4096,gaps2047,gapssegments,gapshour"""
+  python tools/align_long_bench.py --out profiles/align_gaps_long_bench.txt --legs gaps64,gaps4096,gaps2047,gapssegments,gapshour
+  python tools/align_long_bench.py --out profiles/align_tiled_bench.txt --legs tiledhour,tiledsegments,tiled64,tiled4096,tiled2047"""
 import argparse
 import math
 import os
@@ -27,7 +32,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 LEG_SECONDS = {"short64": 240, "short4096": 600, "short2047": 300, "segments": 240, "hour": 600,
-               "gaps64": 240, "gaps4096": 600, "gaps2047": 300, "gapssegments": 240, "gapshour": 600}
+               "gaps64": 240, "gaps4096": 600, "gaps2047": 300, "gapssegments": 240, "gapshour": 600,
+               "tiledhour": 600, "tiledsegments": 240, "tiled64": 240, "tiled4096": 600, "tiled2047": 300}
 DISTINCT = 256
 
 
@@ -226,7 +232,46 @@ def leg_gaps_hour(steps):
             "  ctc_viterbi_gaps_long / ctc_viterbi_long: %.2f" % (b / a)]
 
 
+def leg_tiled(n, T, V, L, steps, seed):
+    from pyctcdecode_amd import build_ctcdecoder
+
+    dec = build_ctcdecoder(labels_of(V))
+    dev, targets = batch(n, T, V, L, seed)
+    got = {}
+
+    def untiled():
+        got["untiled"], got["plan"] = dec.align_long_batch(dev, tokens=targets), dec.last_align_long_plan[0]
+        return dec.last_align_long_timing_ms[2:4]
+
+    def tiled():
+        got["tiled"] = dec.align_long_batch(dev, tokens=targets, tiled=True)
+        return dec.last_align_long_timing_ms[2:4] + dec.last_align_tiled_pass_ms
+
+    out = alternate_calls(steps, {"untiled": untiled, "tiled": lambda: tiled()[:2]})
+    passes = [tiled()[2:] for _ in range(3)]  # (the passes apart: three steps more, the process warm)
+    assert all(np.array_equal(a.path, b.path) and a.score == b.score and a.token_frames == b.token_frames
+               for a, b in zip(got["untiled"], got["tiled"]))
+    a, b = med(out["untiled"][0]), med(out["tiled"][0])
+    pa, pb = float(np.median([p[0] for p in passes])), float(np.median([p[1] for p in passes]))
+    return ["%d utterance(s) of %d frames x %d labels float32, targets of %d labels:" % (n, T, V, L),
+            "  untiled  plan %-12s ctc_viterbi_long %12.3f ms  native call %12.3f ms" % (got["plan"], a, med(out["untiled"][1])),
+            "  tiled    plan %s, %d diagonals, %d tiles, at most %d in one, %d launch group(s)"
+            % (dec.last_align_tiled_plan[0], dec.last_align_tiled_launches, dec.last_align_tiled_tiles, dec.last_align_tiled_widest,
+               dec.last_align_tiled_groups),
+            "           pass A (fill + diagonals) %10.3f ms  pass B (cone) %10.3f ms  both %12.3f ms  native call %12.3f ms"
+            % (pa, pb, b, med(out["tiled"][1])),
+            "  tiled / untiled: %.3f" % (b / a)]
+
+
 def run_leg(leg, steps):
+    if leg == "tiledhour":
+        return leg_tiled(1, 180000, 32, 40000, steps, 3)
+    if leg == "tiledsegments":
+        return leg_tiled(1, 20000, 32, 5000, steps, 2)
+    if leg in ("tiled64", "tiled4096"):
+        return leg_tiled(int(leg[5:]), 1000, 1024, 408, steps, 1)
+    if leg == "tiled2047":
+        return leg_tiled(256, 2100, 1024, 2047, steps, 1)
     if leg in ("gaps64", "gaps4096"):
         return leg_gaps_short(int(leg[4:]), 1000, 1024, 408, steps)
     if leg == "gaps2047":
