@@ -743,6 +743,29 @@ int ctcdec_search_trace(const ctcdec_search* s, const int64_t** trace_off, const
 int ctcdec_search_timing(const ctcdec_search* s, double* ms4, int32_t* launches, int64_t* launched2);
 void ctcdec_search_free(ctcdec_search* s);
 
+/* ---- phrase spotting: the probability, summed over every alignment, that a phrase occurs and ends on a given frame -----------
+ * ctcdec_find_batch's arguments, validation and codes, kernel choice (0 / 1 / 2; spot / spot_batch pass CTCDEC_FIND_KERNEL
+ * too), trace budget, launch splitting, phrase order and timing ([2]: the spot kernels); the result is a ctcdec_search read by
+ * the same accessors. With p(t, c) = exp(e(t, c)) and log1mexp(x) = log(1 - exp(x)) (x > -ln 2 ? log(-expm1(x)) :
+ * log1p(-exp(x)); -inf at 0), in a frame-level path pi the window [s, t] is a maximal occurrence of the phrase y when
+ * pi_s = y[0], pi_t = y[L-1], pi_s .. pi_t collapses to exactly y, s = 0 or pi_{s-1} != y[0], and t = T - 1 or
+ * pi_{t+1} != y[L-1]. Over the interior states 1 .. S - 2, from a_{-1}[s] = -inf:
+ *   fresh_t = 0.0 in frame 0, else log1mexp(e(t - 1, y[0]))
+ *   a_t[1] = lse(a_{t-1}[1], fresh_t) + e(t, y[0])
+ *   a_t[s] = lse(stay a_{t-1}[s], step a_{t-1}[s-1], skip a_{t-1}[s-2] (s >= 3, a label that differs from the label before
+ *            it)) + e(t, label of s)                       -- lse: the maximum first, then m + log(sum of exp(x - m)) in that order
+ *   end_logp[t] = a_t[S-2] + right_t, right_t = log1mexp(e(t + 1, y[L-1])), 0.0 in the last frame
+ * exp(end_logp[t]) is the probability that a maximal occurrence ends on frame t. Every state also carries the mean start
+ * frame of its paths, weighted with the weights exp(x - m) of the lse (a fresh start begins at t; an operand of -inf is left
+ * out): end_start[t] = rint of the mean of state S - 2, -1 where end_logp[t] is -inf. The hits are ctcdec_find_batch's
+ * selection on this trace: logp is end_logp[t], the window [end_start[t], t]. ctcdec_search_count: per phrase the sum over t,
+ * ascending, of exp(end_logp[t]), the expected number of maximal occurrences (it can exceed 1); 0.0 for a phrase that was
+ * not launched; NULL after ctcdec_find_batch. The pointer stays valid until ctcdec_search_free. */
+int ctcdec_spot_batch(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts, int32_t dtype,
+                      int32_t is_device, const int64_t* hyp_off, const int64_t* label_off, const int32_t* labels, int32_t max_hits,
+                      double min_logp, int32_t want_trace, int32_t kernel, int64_t trace_budget, ctcdec_search** out);
+int ctcdec_search_count(const ctcdec_search* s, const double** count);
+
 /* timing of the last call's device stages in milliseconds (HIP events on the decode stream):
  * [0] frame-prune kernel, [1] beam kernel, [2] total device time incl. result copy */
 int ctcdec_result_timing(const ctcdec_result* r, double* ms3);

@@ -217,6 +217,10 @@ _PROTOS = {
     "ctcdec_find_batch": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32,
                                     C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int32, C.c_double,
                                     C.c_int32, C.c_int32, C.c_int64, C.POINTER(_VP)]),
+    "ctcdec_spot_batch": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32,
+                                    C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int32, C.c_double,
+                                    C.c_int32, C.c_int32, C.c_int64, C.POINTER(_VP)]),
+    "ctcdec_search_count": (C.c_int, [_VP, C.POINTER(C.POINTER(C.c_double))]),
     "ctcdec_search_hits": (C.c_int, [_VP, C.POINTER(C.POINTER(C.c_int64)), C.POINTER(C.POINTER(C.c_int32)),
                                      C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.c_int64)]),
     "ctcdec_search_trace": (C.c_int, [_VP, C.POINTER(C.POINTER(C.c_int64)), C.POINTER(C.POINTER(C.c_double)),

@@ -199,7 +199,8 @@ struct ctcdec_decoder {
   // transcript gradient (ctcdec_gradient_batch): the labels' occurrence lists, a launch's row records and, for host callers,
   // its gradient rows (tables, labels and scores: the posteriors')
   DevBuf w_gocc, w_gutts, w_grad;
-  // phrase search (ctcdec_find_batch): a launch's traces and phrase records, the call's hits (labels: w_alab)
+  // phrase search and spotting (ctcdec_find_batch, ctcdec_spot_batch): a launch's traces and phrase records, the call's hits
+  // and, for spotting, counts (labels: w_alab)
   DevBuf w_ftrace, w_fphr, w_fhits;
   // alignment with gaps (ctcdec_align_gaps_batch): row maxima, the slots' gap flags, the gaps' sums, a launch's utterance
   // records (everything else: the alignment's)

@@ -2379,6 +2379,7 @@ struct ctcdec_search {
   std::vector<int64_t> hit_off, trace_off;
   std::vector<int32_t> start, end, end_start;
   std::vector<double> logp, end_logp;
+  std::vector<double> count;  // (ctcdec_spot_batch) per phrase; empty after ctcdec_find_batch
   bool has_trace = false;
   int32_t launches = 0;
   int64_t launched[2] = {0, 0};
@@ -2410,11 +2411,14 @@ static_assert(FORWARD_MAX_GROUPS >= find_chunks(ALIGN_MAX_LABELS), "a group per 
 }  // namespace
 #endif
 
-extern "C" {
-
-int ctcdec_find_batch(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts, int32_t dtype,
-                      int32_t is_device, const int64_t* hyp_off, const int64_t* label_off, const int32_t* labels, int32_t max_hits,
-                      double min_logp, int32_t want_trace, int32_t kernel, int64_t trace_budget, ctcdec_search** out) {
+// ctcdec_find_batch (SPOT false: ctc_find / ctc_find_wave over FindPhrase records) and ctcdec_spot_batch (SPOT true: ctc_spot /
+// ctc_spot_wave over SpotPhrase records, and a count per phrase): one validation, routing, trace budget, launch packing and
+// result for both
+template <bool SPOT>
+static int search_batch(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts, int32_t dtype,
+                        int32_t is_device, const int64_t* hyp_off, const int64_t* label_off, const int32_t* labels, int32_t max_hits,
+                        double min_logp, int32_t want_trace, int32_t kernel, int64_t trace_budget, ctcdec_search** out) {
+  typedef typename std::conditional<SPOT, SpotPhrase, FindPhrase>::type Record;
   TranscriptCall tc;
   const bool args_ok = dec && out && n_utts >= 0 && label_off && hyp_off && trace_budget >= 0 && (n_utts == 0 || (utt_logits && utt_frames));
   std::string bad_option = bad_kernel(kernel);
@@ -2450,6 +2454,7 @@ int ctcdec_find_batch(ctcdec_decoder* dec, const void* const* utt_logits, const 
   }
   std::vector<int32_t> n_hits((size_t)NH, 0), h_start, h_end;
   std::vector<double> h_logp;
+  if (SPOT) res->count.assign((size_t)NH, 0.0);  // (a phrase that is not launched is expected 0 times)
   const size_t K = (size_t)max_hits;
   if (routed.any()) {
     const std::vector<int32_t>& use_frames = routed.use_frames;
@@ -2459,13 +2464,16 @@ int ctcdec_find_batch(ctcdec_decoder* dec, const void* const* utt_logits, const 
     AlignFront fr;
     if (int rc = align_front(dec, utt_logits, use_frames.data(), n_utts, dtype, is_device, tc.V, row0, fr)) return rc;
     res->ms[0] = fr.sniff_ms;
-    // the call's hits: per phrase max_hits scores, then as many starts and ends, then the counts
-    const size_t hits_bytes = (size_t)NH * K * 16 + (size_t)NH * 4;
+    // the call's hits: per phrase max_hits scores, (SPOT) the phrases' expected counts, then as many starts and ends as
+    // scores, then the numbers of hits
+    const size_t NC = SPOT ? (size_t)NH : 0;
+    const size_t hits_bytes = (size_t)NH * K * 16 + NC * 8 + (size_t)NH * 4;
     if (dec->w_alab.ensure((size_t)NL * 4, &err) || dec->w_fhits.ensure(hits_bytes, &err)) return fail(CTCDEC_ERR_DEVICE, err);
     if (be::h2d(dec->w_alab.p, labels, (size_t)NL * 4, &err) || be::zero(dec->w_fhits.p, hits_bytes, &err))
       return fail(CTCDEC_ERR_DEVICE, err);
     double* const d_logp = (double*)dec->w_fhits.p;
-    int32_t* const d_start = (int32_t*)(d_logp + (size_t)NH * K);
+    double* const d_expect = d_logp + (size_t)NH * K;
+    int32_t* const d_start = (int32_t*)(d_expect + NC);
     int32_t* const d_end = d_start + (size_t)NH * K;
     int32_t* const d_count = d_end + (size_t)NH * K;
     // launches: the launched phrases in input order until their traces fill the budget
@@ -2476,7 +2484,7 @@ int ctcdec_find_batch(ctcdec_decoder* dec, const void* const* utt_logits, const 
     };
     const int64_t most = budget_groups((int32_t)NH, bytes_of, budget, groups);
     if (dec->w_ftrace.ensure((size_t)most, &err)) return fail(CTCDEC_ERR_DEVICE, err);
-    std::vector<FindPhrase> phrases;
+    std::vector<Record> phrases;
     std::vector<double> t_logp;
     std::vector<int32_t> t_start;
     for (auto& g : groups) {
@@ -2509,26 +2517,28 @@ int ctcdec_find_batch(ctcdec_decoder* dec, const void* const* utt_logits, const 
         a.L = (int32_t)(label_off[h + 1] - label_off[h]);
         a.is_prob = fr.is_prob[(size_t)u] ? 1 : 0;
         a.pad = 0;
-        phrases.push_back(a);
+        if constexpr (SPOT) phrases.push_back(SpotPhrase{a, d_expect + h});
+        else phrases.push_back(a);
         off += a.T;
         const int w = a.L <= wave_max ? 0 : 1;
         max_chunks[w] = std::max(max_chunks[w], find_chunks(a.L));
         ++count[w];
       }
 #ifdef CTC_SIM  // (both kernels are the one body here: a single thread owns every group)
-      std::vector<double> col((size_t)3 * (size_t)std::max(max_chunks[0], max_chunks[1]));
+      std::vector<double> col((size_t)(SPOT ? 4 : 3) * (size_t)std::max(max_chunks[0], max_chunks[1]));
       FindSeqCtx cx;
-      for (const FindPhrase& a : phrases)
+      for (const Record& a : phrases)
         for_dtype(dtype, [&](auto dt) {
-          ctc_find_phrase<decltype(dt)::value>(cx, a, tc.V, tc.blank, tc.clip_lo, max_hits, min_logp, col.data());
+          if constexpr (SPOT) ctc_spot_phrase<decltype(dt)::value>(cx, a, tc.V, tc.blank, tc.clip_lo, max_hits, min_logp, col.data());
+          else ctc_find_phrase<decltype(dt)::value>(cx, a, tc.V, tc.blank, tc.clip_lo, max_hits, min_logp, col.data());
         });
       for (int w = 0; w < 2; ++w) res->launches += count[w] ? 1 : 0;
 #else
       if (upload(dec->w_fphr, phrases, &err)) return fail(CTCDEC_ERR_DEVICE, err);
       for (int w = 0; w < 2; ++w) {
         if (!count[w]) continue;
-        be::FindArgs fa;
-        fa.phrases = (const FindPhrase*)dec->w_fphr.p + (w ? count[0] : 0);
+        typename std::conditional<SPOT, be::SpotArgs, be::FindArgs>::type fa;
+        fa.phrases = (const Record*)dec->w_fphr.p + (w ? count[0] : 0);
         fa.n_phrases = count[w];
         fa.n_labels = tc.V;
         fa.dtype = dtype;
@@ -2537,7 +2547,11 @@ int ctcdec_find_batch(ctcdec_decoder* dec, const void* const* utt_logits, const 
         fa.max_hits = max_hits;
         fa.clip_lo = tc.clip_lo;
         fa.min_logp = min_logp;
-        if (be::launch_ctc_find(fa, w == 0, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+        if constexpr (SPOT) {
+          if (be::launch_ctc_spot(fa, w == 0, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+        } else {
+          if (be::launch_ctc_find(fa, w == 0, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+        }
         ++res->launches;
       }
 #endif
@@ -2563,14 +2577,16 @@ int ctcdec_find_batch(ctcdec_decoder* dec, const void* const* utt_logits, const 
     if (be::d2h(h_logp.data(), d_logp, (size_t)NH * K * 8, &err) || be::d2h(h_start.data(), d_start, (size_t)NH * K * 4, &err) ||
         be::d2h(h_end.data(), d_end, (size_t)NH * K * 4, &err) || be::d2h(n_hits.data(), d_count, (size_t)NH * 4, &err))
       return fail(CTCDEC_ERR_DEVICE, err);
+    if (SPOT && be::d2h(res->count.data(), d_expect, NC * 8, &err)) return fail(CTCDEC_ERR_DEVICE, err);
 #ifndef CTC_SIM
     res->ms[1] = be::align_kernel_ms(be::K_ROW_LSE);
-    res->ms[2] = be::align_kernel_ms(be::K_FIND);
+    res->ms[2] = be::align_kernel_ms(SPOT ? be::K_SPOT : be::K_FIND);
 #endif
   }
   res->hit_off.assign((size_t)NH + 1, 0);
   for (size_t h = 0; h < (size_t)NH; ++h) {
-    if (n_hits[h] < 0 || n_hits[h] > max_hits) return fail(CTCDEC_ERR_DEVICE, "ctc_find returned a hit count outside 0 .. max_hits");
+    if (n_hits[h] < 0 || n_hits[h] > max_hits)
+      return fail(CTCDEC_ERR_DEVICE, std::string(SPOT ? "ctc_spot" : "ctc_find") + " returned a hit count outside 0 .. max_hits");
     res->hit_off[h + 1] = res->hit_off[h] + n_hits[h];
     for (size_t j = 0; j < (size_t)n_hits[h]; ++j) {
       res->start.push_back(h_start[h * K + j]);
@@ -2580,6 +2596,28 @@ int ctcdec_find_batch(ctcdec_decoder* dec, const void* const* utt_logits, const 
   }
   res->ms[3] = ms(t_begin, Clock::now());
   *out = res.release();
+  return CTCDEC_OK;
+}
+
+extern "C" {
+
+int ctcdec_find_batch(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts, int32_t dtype,
+                      int32_t is_device, const int64_t* hyp_off, const int64_t* label_off, const int32_t* labels, int32_t max_hits,
+                      double min_logp, int32_t want_trace, int32_t kernel, int64_t trace_budget, ctcdec_search** out) {
+  return search_batch<false>(dec, utt_logits, utt_frames, n_utts, dtype, is_device, hyp_off, label_off, labels, max_hits, min_logp,
+                             want_trace, kernel, trace_budget, out);
+}
+
+int ctcdec_spot_batch(ctcdec_decoder* dec, const void* const* utt_logits, const int32_t* utt_frames, int32_t n_utts, int32_t dtype,
+                      int32_t is_device, const int64_t* hyp_off, const int64_t* label_off, const int32_t* labels, int32_t max_hits,
+                      double min_logp, int32_t want_trace, int32_t kernel, int64_t trace_budget, ctcdec_search** out) {
+  return search_batch<true>(dec, utt_logits, utt_frames, n_utts, dtype, is_device, hyp_off, label_off, labels, max_hits, min_logp,
+                            want_trace, kernel, trace_budget, out);
+}
+
+int ctcdec_search_count(const ctcdec_search* s, const double** count_out) {
+  if (!s || !count_out) return fail(CTCDEC_ERR_ARG, "no search");
+  *count_out = s->count.empty() ? nullptr : s->count.data();
   return CTCDEC_OK;
 }
 

@@ -344,6 +344,20 @@ struct FindArgs {
   double min_logp;     // a hit's least score (-inf: none)
 };
 int launch_ctc_find(const FindArgs& a, int wave, std::string* err);
+// ctc_spot (wave == 0) / ctc_spot_wave (wave != 0): launch_ctc_find's split, limits and fields over SpotPhrase records;
+// max_chunks sizes ctc_spot's two columns of (score, mean) pairs in LDS
+struct SpotArgs {
+  const SpotPhrase* phrases;  // [n_phrases] (device)
+  int32_t n_phrases;
+  int32_t n_labels;
+  int32_t dtype;
+  int32_t blank;
+  int32_t max_chunks;
+  int32_t max_hits;
+  double clip_lo;
+  double min_logp;
+};
+int launch_ctc_spot(const SpotArgs& a, int wave, std::string* err);
 // Alignment with gaps. row_lse_max: row_lse (the same bits in a.lse) that also stores each row's largest entry that is not a
 // NaN in rmax -- for the rows of probability-like utterances too, which get no log-sum-exp. ctc_viterbi_gaps: one workgroup
 // per entry of `utts`, all of them validated by the host (GapsUtt); 256 threads when every utterance of the launch has at
@@ -393,14 +407,14 @@ int launch_ctc_prefix_fill(double* next, const int32_t* rows, int32_t n_rows, in
 // parent's end states; all entries validated by the host (PrefixChild), no child's output another's input
 int launch_ctc_prefix_advance(const PrefixAdvanceArgs& a, std::string* err);
 // kernel times (HIP events) of the launches of one of these kernels since the last reset; waits for the kernels.
-// ctc_forward and ctc_forward_wave share a log (with their _ends forms), as do ctc_find and ctc_find_wave, greedy_collapse's
+// ctc_forward and ctc_forward_wave share a log (with their _ends forms), as do ctc_find and ctc_find_wave, ctc_spot and ctc_spot_wave, greedy_collapse's
 // two passes, and ctc_prefix_extend, ctc_prefix_finish and ctc_prefix_fill; ctc_prefix_advance has its own. ctc_forward_tile's
 // log holds one pair of events per launch_ctc_forward_tile: the fill and every diagonal; ctc_viterbi_tile's likewise, and
 // ctc_viterbi_cone's one pair per launch_ctc_viterbi_tiled.
 enum AlignKernel {
   K_ROW_LSE, K_VITERBI, K_FORWARD, K_POSTERIORS, K_GRAD_ROWS, K_FIND, K_ROW_LSE_MAX, K_VITERBI_GAPS, K_ROW_ARGMAX, K_ROW_LSE_ARGMAX,
   K_GREEDY_COLLAPSE, K_PREFIX_EXTEND, K_PREFIX_ADVANCE, K_VITERBI_LONG, K_VITERBI_GAPS_LONG, K_FORWARD_TILE, K_VITERBI_TILE,
-  K_VITERBI_CONE, ALIGN_KERNELS
+  K_VITERBI_CONE, K_SPOT, ALIGN_KERNELS
 };
 void align_timing_reset();
 double align_kernel_ms(AlignKernel kind);

@@ -12,6 +12,7 @@
 //   ctc_posteriors_utt             the forward-backward                         (ctc_posteriors)
 //   ctc_grad_row                   the gradient of the likelihood, row by row   (ctc_grad_rows)
 //   ctc_find_phrase / _wave_phrase a phrase's occurrences, free start and end   (ctc_find / ctc_find_wave)
+//   ctc_spot_phrase / _wave_phrase the probability that a phrase ends on each frame  (ctc_spot / ctc_spot_wave)
 //   ctc_viterbi_gaps_utt           the best path of a target with gaps          (ctc_viterbi_gaps)
 //   ctc_viterbi_gaps_long_utt      the same, its columns in device memory, its frames in segments  (ctc_viterbi_gaps_long)
 //   row_argmax_seq                 a row's most probable label: the simulator's; the kernels fold by lanes
@@ -25,11 +26,12 @@
 //   fold_token_logp                                      ctc_viterbi, ctc_viterbi_gaps, ctc_viterbi_long, ctc_viterbi_gaps_long, ctc_viterbi_cone
 //   forward_group, forward_tile_window, forward_tile_live  ctc_forward_tile, ctc_viterbi_tile, ctc_viterbi_cone
 //   gap_step                                             ctc_viterbi_gaps, ctc_viterbi_gaps_long
-//   group_setup, EntrySource, FrameEntries               ctc_find, ctc_find_wave, ctc_viterbi_gaps
-//   thread_setup                                         ctc_find, ctc_viterbi_gaps
+//   group_setup, EntrySource, FrameEntries               ctc_find, ctc_find_wave, ctc_spot, ctc_spot_wave, ctc_viterbi_gaps
+//   thread_setup                                         ctc_find, ctc_spot, ctc_viterbi_gaps
 // ctc_forward_hyp, ctc_forward_wave_hyp and ctc_posteriors_utt keep their loops in raw variables: over FrameEntries
 // ctc_forward took 8 to 13 % and ctc_posteriors 2 % longer on batches of 64 utterances (profiles/align_refactor_check.txt).
-//   find_trace, find_select                              ctc_find, ctc_find_wave
+//   find_trace, find_select                              ctc_find, ctc_find_wave (find_select: ctc_spot, ctc_spot_wave too)
+//   spot_step, spot_ends, spot_trace                     ctc_spot, ctc_spot_wave
 //   for_dtype (host)                                     the launchers and the simulator's calls
 #pragma once
 #include <math.h>
@@ -1987,6 +1989,208 @@ CTC_HD void ctc_find_wave_phrase(Ctx& cx, const FindPhrase& ph, int V, int blank
       if (c == cf) find_trace(end_logp, end_start, t, jf, d, st);
     }
     now = next;
+  }
+  cx.publish();
+  find_select(cx, ph, max_hits, min_logp);
+}
+
+// ---- ctc_spot / ctc_spot_wave -----------------------------------------------------------------------------------------------
+// The probability that a phrase occurs and ends on a given frame ("Phrase spotting"): ctc_find's states -- the
+// interior states 1 .. S - 2, every one in every frame -- under the forward recursion, the sum over alignments where ctc_find
+// takes the best. Every state carries a[s], the log-mass of the paths that began a maximal occurrence and now sit in s, and
+// m[s], their mass-weighted mean start frame (0.0 in a state without mass). State 1 alone may begin: with the weight
+// fresh_t = log(1 - p(t - 1, y[0])) (0.0 in frame 0), the condition that the frame before is no frame of the first label.
+// The trace holds end_logp[t] = a_t[S-2] + right_t with right_t = log(1 - p(t + 1, y[L-1])) (0.0 in the last frame): the
+// frame after is no frame of the last label; end_start[t] = rint(m_t[S-2]), -1 where end_logp[t] is -inf; and the phrase's
+// count is the sum of exp(end_logp[t]) over t, ascending, by the one thread that writes the trace.
+struct SpotPhrase {
+  FindPhrase f;   // find's record: the trace and the hits are laid out, and selected, as ctc_find's
+  double* count;  // [1] out: the expected number of maximal occurrences
+};
+
+// log(1 - exp(x)) for x <= 0: -inf at 0
+CTC_HD double spot_log1mexp(double x) { return x > -0.6931471805599453 ? log(-expm1(x)) : log1p(-exp(x)); }
+
+// N consecutive states of a group at a time, the first of them a blank, stage by stage so that their exp / log chains
+// interleave: x[j] the operands stay, step, skip of state j (a blank has no skip: two operands), u[j] their means, e[j] its
+// emission; exists[j]: the state is one of the phrase's. Every state is align_lse3's form, max first and the weights
+// w = exp(x - max) summed in the order stay, step, skip; the mean is the same weights over the operands' means, by explicit
+// fma in that order and one division: nothing is left for the compiler to contract, and the same operands give the same bits
+// wherever this is inlined. There is no branch and no select around an exp: an operand of -inf has the weight exp(-inf) = 0
+// exactly, and the mean it comes with is the 0.0 every state without mass keeps (the frame number for a fresh start), so its
+// term adds exactly 0 and the mean of a dead state is never a factor of anything else. A state whose operands are all -inf
+// takes 0.0 for the maximum: its weights are 0, its sum's log -inf, and only its mean needs a select.
+template <int N>
+CTC_HD void spot_states(const double (*x)[3], const double (*u)[3], const bool* exists, const double* e, double* a, double* m) {
+  const double NEG = align_neg_inf();
+  double mx[N], w[N][3], s[N], num[N];
+  CTC_UNROLL
+  for (int j = 0; j < N; ++j) {
+    mx[j] = x[j][0] > x[j][1] ? x[j][0] : x[j][1];
+    if (j & 1) mx[j] = x[j][2] > mx[j] ? x[j][2] : mx[j];
+    mx[j] = mx[j] > NEG ? mx[j] : 0.0;
+  }
+  CTC_UNROLL
+  for (int j = 0; j < N; ++j) {
+    CTC_UNROLL
+    for (int i = 0; i < ((j & 1) ? 3 : 2); ++i) w[j][i] = exp(x[j][i] - mx[j]);
+  }
+  CTC_UNROLL
+  for (int j = 0; j < N; ++j) {
+    s[j] = w[j][0];
+    s[j] += w[j][1];
+    num[j] = fma(w[j][1], u[j][1], fma(w[j][0], u[j][0], 0.0));
+    if (j & 1) s[j] += w[j][2], num[j] = fma(w[j][2], u[j][2], num[j]);
+  }
+  CTC_UNROLL
+  for (int j = 0; j < N; ++j) {
+    a[j] = exists[j] ? mx[j] + log(s[j]) + e[j] : NEG;
+    m[j] = exists[j] && s[j] > 0.0 ? num[j] / s[j] : 0.0;
+  }
+}
+
+// One frame of one group (blank, label 2c, blank, label 2c + 1: ForwardGroup), in place: a / m the group's scores and means at
+// the frame before, am1 / mm1 those of the last state of the group below. `first`: the group holds state 1; its state 0 does
+// not exist, so state 1's step operand is free and carries the fresh start (fresh, begun at t) -- the step and skip of the
+// definition are -inf there and add exactly 0, so the sum over stay, step, skip, fresh has the same bits. The four states of
+// a group are independent within a frame; they go through spot_states SPOT_TOGETHER at a time.
+constexpr int SPOT_TOGETHER = 4;  // (2 compiles to the same register counts: the scheduler interleaves the straight-line code itself)
+CTC_HD void spot_step(const ForwardGroup& g, bool first, int t, double fresh, double am1, double mm1, double e_blank, double e0,
+                      double e1, double* a, double* m) {
+  const double NEG = align_neg_inf();
+  const double a0 = a[0], a1 = a[1], a2 = a[2], a3 = a[3];
+  const double m0 = m[0], m1 = m[1], m2 = m[2], m3 = m[3];
+  const double x[4][3] = {{a0, am1, NEG}, {a1, first ? fresh : a0, g.skip0 ? am1 : NEG}, {a2, a1, NEG}, {a3, a2, g.skip1 ? a1 : NEG}};
+  const double u[4][3] = {{m0, mm1, 0.0}, {m1, first ? (double)t : m0, mm1}, {m2, m1, 0.0}, {m3, m2, m1}};
+  // (state 4c of the first group has no finite operand, ever; a group that is stepped holds label 2c)
+  const bool exists[4] = {true, true, g.l1 >= 0, g.l1 >= 0};
+  const double e[4] = {e_blank, e0, e_blank, e1};
+  CTC_UNROLL
+  for (int j = 0; j < 4; j += SPOT_TOGETHER) spot_states<SPOT_TOGETHER>(x + j, u + j, exists + j, e + j, a + j, m + j);
+}
+
+// The trace's entry of frame t, and its share of the count
+CTC_HD void spot_trace(double* end_logp, int32_t* end_start, int t, double v, double mean, double& count) {
+  const bool some = v > align_neg_inf();
+  end_logp[t] = v;
+  end_start[t] = some ? (int32_t)rint(mean) : -1;
+  if (some) count += exp(v);
+}
+// What a frame's entries give the two ends, by the owners of state 1 (group 0) and of state S - 2 (group cf, entry jf) alone,
+// ahead of the frame's step: e(t, y[0]) becomes fresh_{t+1}, and e(t, y[L-1]) becomes right_{t-1}, with which the trace's entry
+// of frame t - 1 is written from the states as they still stand. Both come from the entries in hand, none from the frame
+// requested ahead: nothing here waits for a load. One log1mexp serves a thread unless it owns both ends of two labels (L = 2).
+CTC_HD void spot_ends(int c, int cf, int jf, int t, double e0, double e1, const double* a, const double* m, double* end_logp,
+                      int32_t* end_start, double& fresh_next, double& count) {
+  if (c != 0 && c != cf) return;
+  const bool last1 = c == cf && jf == 3;
+  const double q = spot_log1mexp(last1 ? e1 : e0);
+  if (c == cf && t > 0) spot_trace(end_logp, end_start, t - 1, (jf == 1 ? a[1] : a[3]) + q, jf == 1 ? m[1] : m[3], count);
+  if (c == 0) fresh_next = last1 ? spot_log1mexp(e0) : q;
+}
+
+// ctc_spot: the threads of cx (tid, nt, sync(); Ctx::GROUPS * nt >= find_chunks(L)) share one phrase of a matrix of dtype DT,
+// arranged as ctc_find is: a group's scores and means stay in registers, and only its last state goes through `col` --
+// 2 * find_chunks(L) pairs (score, mean), the columns of two successive frames -- to the thread that owns the group above: one
+// barrier per frame. The thread that owns state S - 2 writes the trace and keeps the count; after the last frame its
+// wavefront alone (cx.same_wave, after cx.publish) selects the hits from what it wrote, with find_select.
+template <int DT, class Ctx>
+CTC_HD void ctc_spot_phrase(Ctx& cx, const SpotPhrase& sp, int V, int blank, double clip_lo, int max_hits, double min_logp, double* col) {
+  constexpr int G = Ctx::GROUPS;
+  const FindPhrase& ph = sp.f;
+  double* const end_logp = ph.end_logp;  // (the record, once: the frame loop reads none of it again)
+  int32_t* const end_start = ph.end_start;
+  double* const count_out = sp.count;
+  const int T = ph.T, L = ph.L;
+  if (T <= 0 || L <= 0) return;
+  const int nch = find_chunks(L);
+  const int cf = (2 * L - 1) >> 2, jf = (2 * L - 1) & 3;  // state S - 2, the last label: entry 1 or 3 of its group
+  const double NEG = align_neg_inf();
+  ForwardGroup g[G];
+  EntrySource<G> src;
+  thread_setup(cx, ph.x, ph.lse, nullptr, ph.lab, L, nch, V, blank, ph.is_prob != 0, clip_lo, g, src);
+  double a[G][4], m[G][4];  // scores and mean start frames
+  CTC_UNROLL
+  for (int k = 0; k < G; ++k) {
+    a[k][0] = a[k][1] = a[k][2] = a[k][3] = NEG;
+    m[k][0] = m[k][1] = m[k][2] = m[k][3] = 0.0;
+  }
+  for (int i = cx.tid; i < 2 * nch; i += cx.nt) col[2 * i] = NEG, col[2 * i + 1] = 0.0;
+  cx.sync();
+  double fresh = 0.0, fresh_next = 0.0, count = 0.0;
+  FrameEntries<DT, G> now, next;
+  now.request(src, 0);
+  for (int t = 0; t < T; ++t) {
+    const int po = ((t + 1) & 1) * nch, co = (t & 1) * nch;
+    double am1[G], mm1[G];
+    CTC_UNROLL
+    for (int k = 0; k < G; ++k) {
+      const int c = cx.tid + k * cx.nt;
+      am1[k] = c > 0 && c < nch ? col[2 * (po + c - 1)] : NEG;
+      mm1[k] = c > 0 && c < nch ? col[2 * (po + c - 1) + 1] : 0.0;
+    }
+    next.request(src, t + 1 < T ? t + 1 : t);  // (after the last frame: the last frame again)
+    const double e_blank = now.emit_blank(src);
+    CTC_UNROLL
+    for (int k = 0; k < G; ++k) {
+      const int c = cx.tid + k * cx.nt;
+      if (c >= nch) continue;
+      const double e0 = now.emit0(src, k), e1 = now.emit1(src, k);
+      spot_ends(c, cf, jf, t, e0, e1, a[k], m[k], end_logp, end_start, fresh_next, count);
+      spot_step(g[k], c == 0, t, fresh, am1[k], mm1[k], e_blank, e0, e1, a[k], m[k]);
+      col[2 * (co + c)] = a[k][3];
+      col[2 * (co + c) + 1] = m[k][3];
+    }
+    fresh = fresh_next;
+    now = next;
+    cx.sync();  // the one barrier of a frame: the columns swap roles
+  }
+  CTC_UNROLL
+  for (int k = 0; k < G; ++k) {
+    if (cx.tid + k * cx.nt != cf) continue;
+    spot_trace(end_logp, end_start, T - 1, jf == 1 ? a[k][1] : a[k][3], jf == 1 ? m[k][1] : m[k][3], count);  // right is 0.0
+    *count_out = count;
+  }
+  if (!cx.same_wave(cf % cx.nt)) return;
+  cx.publish();
+  find_select(cx, ph, max_hits, min_logp);
+}
+
+// ctc_spot_wave: one wavefront per phrase of at most FIND_WAVE_MAX_LABELS labels. Lane c owns group c; the last state of the
+// group below -- a score and a mean -- comes from lane c - 1 by two cx.up(): no LDS, no barrier. The same groups, steps and
+// entries as ctc_spot_phrase, so the same bits. Lane cf writes the trace and keeps the count, the wave selects.
+template <int DT, class Ctx>
+CTC_HD void ctc_spot_wave_phrase(Ctx& cx, const SpotPhrase& sp, int V, int blank, double clip_lo, int max_hits, double min_logp) {
+  const FindPhrase& ph = sp.f;
+  double* const end_logp = ph.end_logp;
+  int32_t* const end_start = ph.end_start;
+  double* const count_out = sp.count;
+  const int T = ph.T, L = ph.L, c = cx.lane();
+  if (T <= 0 || L <= 0) return;
+  const int nch = find_chunks(L);
+  const int cf = (2 * L - 1) >> 2, jf = (2 * L - 1) & 3;
+  const double NEG = align_neg_inf();
+  EntrySource<1> src = {ph.x, ph.lse, nullptr, V, blank, ph.is_prob != 0, clip_lo, {0}, {0}};
+  const ForwardGroup g = group_setup(ph.lab, L, nch, c, blank, &src.i0[0], &src.i1[0]);
+  double a[4] = {NEG, NEG, NEG, NEG}, m[4] = {0.0, 0.0, 0.0, 0.0};
+  double fresh = 0.0, fresh_next = 0.0, count = 0.0;
+  FrameEntries<DT, 1> now, next;
+  now.request(src, 0);
+  for (int t = 0; t < T; ++t) {
+    const double below_a = cx.up(a[3]);  // (every lane takes part)
+    const double below_m = cx.up(m[3]);
+    next.request(src, t + 1 < T ? t + 1 : t);
+    if (c < nch) {
+      const double e0 = now.emit0(src, 0), e1 = now.emit1(src, 0);
+      spot_ends(c, cf, jf, t, e0, e1, a, m, end_logp, end_start, fresh_next, count);
+      spot_step(g, c == 0, t, fresh, c > 0 ? below_a : NEG, c > 0 ? below_m : 0.0, now.emit_blank(src), e0, e1, a, m);
+    }
+    fresh = fresh_next;
+    now = next;
+  }
+  if (c == cf) {
+    spot_trace(end_logp, end_start, T - 1, jf == 1 ? a[1] : a[3], jf == 1 ? m[1] : m[3], count);
+    *count_out = count;
   }
   cx.publish();
   find_select(cx, ph, max_hits, min_logp);

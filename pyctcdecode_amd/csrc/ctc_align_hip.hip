@@ -6,6 +6,7 @@
 //   ctc_forward, ctc_posteriors,    a workgroup per record, a group of four states per thread in registers
 //   ctc_find, ctc_viterbi_gaps        (256 threads up to 511 labels, 1024 above)
 //   ctc_forward_wave, ctc_find_wave a wavefront per record of at most 127 labels
+//   ctc_spot, ctc_spot_wave         ctc_find's two arrangements under the forward recursion: a score and a mean per state
 //   ctc_forward_tile                a workgroup per tile of a hypothesis' states and frames, a launch per diagonal of tiles
 //   ctc_viterbi_tile, _cone         the best path on the same tiles with checkpoints; then a workgroup per utterance traces back
 //   ctc_grad_rows                   G threads per row of a dense ctc_posteriors launch's tables
@@ -352,6 +353,28 @@ __global__ __launch_bounds__(ALIGN_THREADS) void ctc_find_wave(FindArgs a) {
   if (i >= a.n_phrases) return;  // (a whole wave: nothing in this kernel waits for another wave)
   FindWaveCtx cx((int)(threadIdx.x & 63u));
   ctc_find_wave_phrase<DT>(cx, a.phrases[i], a.n_labels, a.blank, a.clip_lo, a.max_hits, a.min_logp);
+}
+
+// ---------------------------------------------------------------------------------------------
+// ctc_spot / ctc_spot_wave: ctc_find's arrangement under the forward recursion (ctc_align.h, "ctc_spot"): per state a score
+// and a mean start frame, both fp64. ctc_spot: a workgroup per phrase, a thread's four scores and means in registers, the
+// groups' last states in two LDS columns of 16 bytes an entry, one barrier per frame. ctc_spot_wave: a wavefront per phrase
+// of at most 127 labels, four to a workgroup that never synchronises; the neighbour's state by two fp64 shuffles per frame,
+// no LDS. The contexts are ctc_find's, and so is the selection.
+// ---------------------------------------------------------------------------------------------
+template <int NT, int DT>
+__global__ __launch_bounds__(NT) void ctc_spot(SpotArgs a) {
+  extern __shared__ double spot_cols[];
+  FindGpuCtx cx((int)threadIdx.x, NT);
+  ctc_spot_phrase<DT>(cx, a.phrases[blockIdx.x], a.n_labels, a.blank, a.clip_lo, a.max_hits, a.min_logp, spot_cols);
+}
+
+template <int DT>
+__global__ __launch_bounds__(ALIGN_THREADS) void ctc_spot_wave(SpotArgs a) {
+  const int i = (int)blockIdx.x * FORWARD_WAVES + (int)(threadIdx.x >> 6);
+  if (i >= a.n_phrases) return;  // (a whole wave: nothing in this kernel waits for another wave)
+  FindWaveCtx cx((int)(threadIdx.x & 63u));
+  ctc_spot_wave_phrase<DT>(cx, a.phrases[i], a.n_labels, a.blank, a.clip_lo, a.max_hits, a.min_logp);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1047,6 +1070,27 @@ int launch_ctc_find_on(const FindArgs& a, int wave, hipStream_t stream, std::str
       for_threads(a.max_chunks, [&](auto nt) {
         constexpr int NT = decltype(nt)::value;
         hipLaunchKernelGGL((ctc_find<NT, DT>), dim3((unsigned)a.n_phrases), dim3(NT), lds, stream, a);
+      });
+    });
+  });
+}
+
+int launch_ctc_spot_on(const SpotArgs& a, int wave, hipStream_t stream, std::string* err) {
+  if (a.n_phrases <= 0) return 0;
+  if (a.dtype < 0 || a.dtype > 3 || a.max_hits < 1 || a.max_hits > FIND_MAX_HITS || a.max_chunks < 1 ||
+      a.max_chunks > (wave ? find_chunks(FIND_WAVE_MAX_LABELS) : find_chunks(ALIGN_MAX_LABELS)))
+    return bad_launch(err, "ctc_spot: more states or hits than the kernel holds");
+  const size_t lds = (size_t)2 * (size_t)a.max_chunks * 2 * sizeof(double);  // (ctc_spot) <= 32 KB
+  return timed_launch(K_SPOT, stream, err, [&] {
+    for_dtype(a.dtype, [&](auto dt) {
+      constexpr int DT = decltype(dt)::value;
+      if (wave) {
+        hipLaunchKernelGGL(ctc_spot_wave<DT>, dim3((unsigned)((a.n_phrases + FORWARD_WAVES - 1) / FORWARD_WAVES)), dim3(ALIGN_THREADS), 0, stream, a);
+        return;
+      }
+      for_threads(a.max_chunks, [&](auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        hipLaunchKernelGGL((ctc_spot<NT, DT>), dim3((unsigned)a.n_phrases), dim3(NT), lds, stream, a);
       });
     });
   });

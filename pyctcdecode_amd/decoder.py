@@ -495,6 +495,42 @@ class PhraseSearch:
     end_start: Optional[np.ndarray] = None
 
 
+@dataclasses.dataclass(frozen=True)
+class SpotHit:
+    """One hit of a phrase spotting (BeamSearchDecoderCTC.spot / spot_batch): ``logp`` is the log-probability, summed over
+    every alignment, that an occurrence of the phrase ends on frame ``end - 1``; ``start`` is the mass-weighted mean first
+    frame of those occurrences, rounded."""
+
+    start: int
+    end: int
+    logp: float
+
+    @property
+    def frames(self) -> int:
+        return self.end - self.start
+
+    @property
+    def prob(self) -> float:
+        return math.exp(self.logp)
+
+
+@dataclasses.dataclass(frozen=True, eq=False)
+class PhraseSpot:
+    """How probably a phrase occurs in an utterance (BeamSearchDecoderCTC.spot / spot_batch): ``text`` and ``tokens`` are
+    ScoredText's; ``hits`` are the end frames taken, most probable first, their windows pairwise disjoint; ``count`` is the
+    expected number of occurrences, the sum over the frames of exp(end_logp) -- 0.0, and no hits, when the utterance has
+    fewer frames than the phrase has labels plus adjacent equal labels. With ``trace=True``, ``end_logp[t]`` (float64) is the
+    log-probability that an occurrence ends on frame ``t`` and ``end_start[t]`` (int32) the rounded mean first frame of
+    those occurrences, ``-inf`` / ``-1`` where none can end; else both are None."""
+
+    text: str
+    tokens: List[int]
+    hits: List[SpotHit]
+    count: float
+    end_logp: Optional[np.ndarray] = None
+    end_start: Optional[np.ndarray] = None
+
+
 POSTERIORS_TABLE_BUDGET = 4 << 30  # bytes of tables one ctc_posteriors launch holds by default (DESIGN.md, "Frame posteriors")
 FORWARD_KERNELS = {"wave": 1, "group": 2}  # ctcdec_score_batch's `kernel` from CTCDEC_FORWARD_KERNEL (unset: the library chooses)
 FIND_KERNELS = {"wave": 1, "group": 2}  # ctcdec_find_batch's `kernel` from CTCDEC_FIND_KERNEL (unset: the library chooses)
@@ -1486,6 +1522,10 @@ class BeamSearchDecoderCTC:
         self.last_find_timing_ms = (0.0, 0.0, 0.0, 0.0)
         self.last_find_launches = 0
         self.last_find_launched = (0, 0)
+        # ... and of the last spot / spot_batch call, as find's (the kernels: ctc_spot_wave, ctc_spot)
+        self.last_spot_timing_ms = (0.0, 0.0, 0.0, 0.0)
+        self.last_spot_launches = 0
+        self.last_spot_launched = (0, 0)
         # ... and of the last align_gaps / align_gaps_batch call (ms: classification, row_lse_max, ctc_viterbi_gaps, native
         # call; kernel launches made)
         self.last_align_gaps_timing_ms = (0.0, 0.0, 0.0, 0.0)
@@ -2878,34 +2918,31 @@ class BeamSearchDecoderCTC:
         return self.find_batch([logits], None if texts is None else [texts], tokens=None if tokens is None else [tokens],
                                max_hits=max_hits, min_logp=min_logp, trace=trace)[0]
 
-    def find_batch(self, logits_list: Any, texts: Optional[Sequence[Sequence[str]]] = None,
-                   tokens: Optional[Sequence[Sequence[Sequence[int]]]] = None, max_hits: int = 1,
-                   min_logp: Optional[float] = None, trace: bool = False, _trace_budget: int = 0) -> List[List["PhraseSearch"]]:
-        """Does each phrase occur somewhere in its utterance, where, and how well, in one native call: per utterance a
-        sequence of phrases, per phrase a PhraseSearch (row_lse once per utterance + ctc_find / ctc_find_wave,
-        csrc/ctc_align_hip.hip). ``logits_list`` is what align_batch takes; ``texts[u]`` (character alphabets) is a list of
-        str, ``tokens[u]`` a list of lists of label ids, the only form for BPE alphabets. An occurrence is a window of frames
-        that begins on the phrase's first label and ends on its last, scored by its best CTC path; per end frame the best
-        window is kept. Up to ``max_hits`` (1 .. 64) pairwise disjoint windows are taken, best first, none below ``min_logp``
-        (None: no threshold); an end frame whose best window overlaps a hit already taken is dropped, even if a worse window
-        ending there would not overlap. ``trace=True`` also returns the per-frame ``end_logp`` / ``end_start``."""
+    def _set_search_stats(self, name: str, timing_ms, launches: int, launched) -> None:
+        setattr(self, "last_%s_timing_ms" % name, timing_ms)
+        setattr(self, "last_%s_launches" % name, launches)
+        setattr(self, "last_%s_launched" % name, launched)
+
+    def _search_batch(self, name: str, logits_list: Any, texts, tokens, max_hits, min_logp, trace, _trace_budget):
+        """What find_batch ("find": ctcdec_find_batch) and spot_batch ("spot": ctcdec_spot_batch) share: the checks, the
+        native call and its flat results (None for an empty batch); spot's also hold the phrases' counts."""
         if isinstance(logits_list, (_ResidentBeams, _DeviceStreams)) or (
                 isinstance(logits_list, (list, tuple)) and any(isinstance(x, (_ResidentBeams, _DeviceStreams)) for x in logits_list)):
-            raise NotImplementedError("find_batch searches utterances' matrices; the frames a stream has consumed are not kept")
-        logits_list, phrases = self._many_targets_each("find", "phrase", "phrases", logits_list, texts, tokens)
+            raise NotImplementedError("%s_batch searches utterances' matrices; the frames a stream has consumed are not kept" % name)
+        logits_list, phrases = self._many_targets_each(name, "phrase", "phrases", logits_list, texts, tokens)
         for u, cur in enumerate(phrases):
             for j, ids in enumerate(cur):
                 if not ids:
-                    raise ValueError("find: utterance %d, phrase %d is empty: it would occur everywhere and nowhere" % (u, j))
+                    raise ValueError("%s: utterance %d, phrase %d is empty: it would occur everywhere and nowhere" % (name, u, j))
         if isinstance(max_hits, bool) or not isinstance(max_hits, (int, np.integer)) or not 1 <= int(max_hits) <= FIND_MAX_HITS:
-            raise ValueError("find: max_hits must be an int in 1 .. %d, not %r" % (FIND_MAX_HITS, max_hits))
+            raise ValueError("%s: max_hits must be an int in 1 .. %d, not %r" % (name, FIND_MAX_HITS, max_hits))
         floor = -math.inf if min_logp is None else float(min_logp)
         if math.isnan(floor):
-            raise ValueError("find: min_logp is not a number")
+            raise ValueError("%s: min_logp is not a number" % name)
         n = len(phrases)
-        self.last_find_timing_ms, self.last_find_launches, self.last_find_launched = (0.0, 0.0, 0.0, 0.0), 0, (0, 0)
+        self._set_search_stats(name, (0.0, 0.0, 0.0, 0.0), 0, (0, 0))
         if n == 0:
-            return []
+            return None
         kernel = _forced_kernel("CTCDEC_FIND_KERNEL", FIND_KERNELS)
         with self._call_lock:
             batch, frames, ptrs, c_utts = self._stage_transcript_call(logits_list)
@@ -2913,12 +2950,12 @@ class BeamSearchDecoderCTC:
             for u, cur in enumerate(phrases):
                 for j, ids in enumerate(cur):
                     if int(frames[u]) >= self._frames_needed(ids) and 12 * int(frames[u]) > budget:
-                        raise ValueError("find: utterance %d, phrase %d needs a trace of %d bytes, above the memory budget of %d "
-                                         "bytes of one launch" % (u, j, 12 * int(frames[u]), budget))
+                        raise ValueError("%s: utterance %d, phrase %d needs a trace of %d bytes, above the memory budget of %d "
+                                         "bytes of one launch" % (name, u, j, 12 * int(frames[u]), budget))
             flat, label_off, hyp_off, n_phrases = self._pack_items(phrases)
             res = C.c_void_p()
             lib = self._lib
-            lib.check(lib.dll.ctcdec_find_batch(
+            lib.check(getattr(lib.dll, "ctcdec_%s_batch" % name)(
                 self._handle, *c_utts, n,
                 batch.dtype, int(batch.is_device), B.off_ptr(hyp_off), B.off_ptr(label_off), flat.ctypes.data_as(C.POINTER(C.c_int32)),
                 int(max_hits), floor, int(bool(trace)), kernel, int(_trace_budget), C.byref(res)))
@@ -2941,15 +2978,35 @@ class BeamSearchDecoderCTC:
                     nt = t_off[-1]
                     t_logp = np.ctypeslib.as_array(tl, shape=(nt,)).copy() if nt else np.zeros(0)
                     t_start = np.ctypeslib.as_array(ts, shape=(nt,)).copy() if nt else np.zeros(0, dtype=np.int32)
+                counts = None
+                if name == "spot":
+                    pc = C.POINTER(C.c_double)()
+                    lib.check(lib.dll.ctcdec_search_count(res, C.byref(pc)))
+                    counts = np.ctypeslib.as_array(pc, shape=(n_phrases,)).tolist() if n_phrases else []
                 ms, launches, launched = (C.c_double * 4)(), C.c_int32(), (C.c_int64 * 2)()
                 lib.dll.ctcdec_search_timing(res, ms, C.byref(launches), launched)
-                # [classification (frame-prune kernels), row_lse, find kernels (HIP events), whole native call]; kernel launches
-                # made; phrases that went to (ctc_find_wave, ctc_find)
-                self.last_find_timing_ms = tuple(float(v) for v in ms)
-                self.last_find_launches = int(launches.value)
-                self.last_find_launched = (int(launched[0]), int(launched[1]))
+                # [classification (frame-prune kernels), row_lse, the call's kernels (HIP events), whole native call]; kernel
+                # launches made; phrases that went to (the wave kernel, the group kernel)
+                self._set_search_stats(name, tuple(float(v) for v in ms), int(launches.value), (int(launched[0]), int(launched[1])))
             finally:
                 lib.dll.ctcdec_search_free(res)
+        return phrases, hit_off, starts, ends, logps, t_off, t_logp, t_start, counts
+
+    def find_batch(self, logits_list: Any, texts: Optional[Sequence[Sequence[str]]] = None,
+                   tokens: Optional[Sequence[Sequence[Sequence[int]]]] = None, max_hits: int = 1,
+                   min_logp: Optional[float] = None, trace: bool = False, _trace_budget: int = 0) -> List[List["PhraseSearch"]]:
+        """Does each phrase occur somewhere in its utterance, where, and how well, in one native call: per utterance a
+        sequence of phrases, per phrase a PhraseSearch (row_lse once per utterance + ctc_find / ctc_find_wave,
+        csrc/ctc_align_hip.hip). ``logits_list`` is what align_batch takes; ``texts[u]`` (character alphabets) is a list of
+        str, ``tokens[u]`` a list of lists of label ids, the only form for BPE alphabets. An occurrence is a window of frames
+        that begins on the phrase's first label and ends on its last, scored by its best CTC path; per end frame the best
+        window is kept. Up to ``max_hits`` (1 .. 64) pairwise disjoint windows are taken, best first, none below ``min_logp``
+        (None: no threshold); an end frame whose best window overlaps a hit already taken is dropped, even if a worse window
+        ending there would not overlap. ``trace=True`` also returns the per-frame ``end_logp`` / ``end_start``."""
+        got = self._search_batch("find", logits_list, texts, tokens, max_hits, min_logp, trace, _trace_budget)
+        if got is None:
+            return []
+        phrases, hit_off, starts, ends, logps, t_off, t_logp, t_start, _ = got
         out: List[List[PhraseSearch]] = []
         h = 0
         for cur in phrases:
@@ -2960,6 +3017,46 @@ class BeamSearchDecoderCTC:
                 if trace:
                     el, es = t_logp[t_off[h]:t_off[h + 1]].copy(), t_start[t_off[h]:t_off[h + 1]].copy()
                 found.append(PhraseSearch(self._words_of_target(ids)[0], list(ids), hits, el, es))
+                h += 1
+            out.append(found)
+        return out
+
+    # -- phrase spotting (no reference analogue; DESIGN.md, "Phrase spotting") ------------------------------
+    def spot(self, logits: Any, texts: Optional[Sequence[str]] = None, tokens: Optional[Sequence[Sequence[int]]] = None,
+             max_hits: int = 1, min_logp: Optional[float] = None, trace: bool = False) -> List["PhraseSpot"]:
+        """The probability that each phrase occurs in one utterance, and where: spot_batch of a batch of one."""
+        if isinstance(logits, (_ResidentBeams, _DeviceStreams)):
+            raise NotImplementedError("spot searches an utterance's matrix; the frames a stream has consumed are not kept")
+        self._check_logits_dimension(logits)
+        return self.spot_batch([logits], None if texts is None else [texts], tokens=None if tokens is None else [tokens],
+                               max_hits=max_hits, min_logp=min_logp, trace=trace)[0]
+
+    def spot_batch(self, logits_list: Any, texts: Optional[Sequence[Sequence[str]]] = None,
+                   tokens: Optional[Sequence[Sequence[Sequence[int]]]] = None, max_hits: int = 1,
+                   min_logp: Optional[float] = None, trace: bool = False, _trace_budget: int = 0) -> List[List["PhraseSpot"]]:
+        """How probable is it that each phrase occurs in its utterance, summed over every alignment, in one native call:
+        find_batch's arguments, per phrase a PhraseSpot (row_lse once per utterance + ctc_spot / ctc_spot_wave,
+        csrc/ctc_align_hip.hip). Per end frame ``t`` the call forms the log-probability that an occurrence of the phrase --
+        a window that begins on a frame of the first label not preceded by that label, collapses to exactly the phrase, and
+        ends on a frame of the last label not followed by that label -- ends on ``t``, and the mass-weighted mean start frame
+        of those occurrences; ``count`` is the sum of the probabilities over the end frames, the expected number of
+        occurrences. The hits are find_batch's selection on that trace: up to ``max_hits`` (1 .. 64) pairwise disjoint
+        windows ``[mean start, t]``, most probable end frame first, none below ``min_logp``. ``trace=True`` also returns
+        the per-frame ``end_logp`` / ``end_start``. ``CTCDEC_FIND_KERNEL=wave|group`` applies as it does to find_batch."""
+        got = self._search_batch("spot", logits_list, texts, tokens, max_hits, min_logp, trace, _trace_budget)
+        if got is None:
+            return []
+        phrases, hit_off, starts, ends, logps, t_off, t_logp, t_start, counts = got
+        out: List[List[PhraseSpot]] = []
+        h = 0
+        for cur in phrases:
+            found = []
+            for ids in cur:
+                hits = [SpotHit(starts[k], ends[k], logps[k]) for k in range(hit_off[h], hit_off[h + 1])]
+                el = es = None
+                if trace:
+                    el, es = t_logp[t_off[h]:t_off[h + 1]].copy(), t_start[t_off[h]:t_off[h + 1]].copy()
+                found.append(PhraseSpot(self._words_of_target(ids)[0], list(ids), hits, counts[h], el, es))
                 h += 1
             out.append(found)
         return out

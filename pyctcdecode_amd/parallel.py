@@ -216,6 +216,11 @@ def find_batch_sharded(decoder, logits_list, texts=None, group=None, **kwargs):
     raise NotImplementedError("find_batch is not gathered over ranks: search each rank's slice with decoder.find_batch itself")
 
 
+def spot_batch_sharded(decoder, logits_list, texts=None, group=None, **kwargs):
+    """Phrase spotting is not sharded over ranks: each rank calls decoder.spot_batch on its own slice."""
+    raise NotImplementedError("spot_batch is not gathered over ranks: spot in each rank's slice with decoder.spot_batch itself")
+
+
 def align_gaps_batch_sharded(decoder, logits_list, texts=None, group=None, **kwargs):
     """Alignment with gaps is not sharded over ranks: each rank calls decoder.align_gaps_batch on its own slice."""
     raise NotImplementedError("align_gaps_batch is not gathered over ranks: align each rank's slice with decoder.align_gaps_batch itself")
@@ -397,6 +402,12 @@ class DevicePool:
         raise NotImplementedError("DevicePool does not shard find_batch: call decoder.find_batch on the process's own device")
 
     find = find_batch
+
+    def spot_batch(self, logits_list, texts=None, **kwargs):
+        """Phrase spotting runs on the calling process's own device: a pool does not shard it."""
+        raise NotImplementedError("DevicePool does not shard spot_batch: call decoder.spot_batch on the process's own device")
+
+    spot = spot_batch
 
     def align_gaps_batch(self, logits_list, texts=None, **kwargs):
         """Alignment with gaps runs on the calling process's own device: a pool does not shard it."""

@@ -6,11 +6,14 @@ substituted), each forward kernel forced in turn -- and at 64 utterances, with t
 for scale; then a sweep of target lengths on 256 utterances of random logits, which is what the wave / group threshold of
 ctcdec_score_batch rests on. Kernel times are HIP events on the decode stream (ctcdec_alignment_timing, ctcdec_score_batch,
 ctcdec_posteriors_timing).
-  python tools/align_bench.py [--out profiles/align_bench.txt] [--steps 3] [--legs align,score,posteriors,sweep,gradient,find,gaps,greedy,prefix,prefix_session]
+  python tools/align_bench.py [--out profiles/align_bench.txt] [--steps 3] [--legs align,score,posteriors,sweep,gradient,find,spot,gaps,greedy,prefix,prefix_session]
 The gradient leg (not in the default set) times gradient_batch -- ctc_grad_rows alone, next to posteriors_batch(dense=False).
 The find leg (not in the default set either) times find_batch -- ctc_find / ctc_find_wave forced in turn, alternating: at the
 bench shape each utterance searched for 1 and for 8 phrases of 8 labels cut from its own decoded tokens, then 256 and 2048
 phrases of 15 / 127 / 511 labels on 256 utterances of random logits, next to ctc_viterbi and ctc_forward on the same batch.
+The spot leg (not in the default set either) times spot_batch -- ctc_spot / ctc_spot_wave -- on the find leg's batches, with
+find_batch and score_batch (ctc_find / ctc_find_wave, ctc_forward / ctc_forward_wave) on the same phrases in the same rounds,
+alternating, each kernel forced in turn.
 The gaps leg (not in the default set either) times align_gaps_batch next to align_batch on the same batch, alternating:
 row_lse_max against row_lse, ctc_viterbi_gaps on the gap-free targets against ctc_viterbi on the same targets, and
 ctc_viterbi_gaps again with a leading gap, a trailing gap and one gap at every word boundary.
@@ -225,6 +228,71 @@ def find_sweep_lines(dec, steps):
         lines.append("  %6d | %s %s %s | %s %s %s | %9.3f ms %9.3f ms | %8.2f %8.2f" % (
             L, cell(one, "wave"), cell(one, "group"), ratio(one), cell(many, "wave"), cell(many, "group"), ratio(many),
             med(vit), fwd, one["group"] / med(vit), one["group"] / fwd))
+    del dev
+    return lines
+
+
+def time_spot(dec, dev, phrases, kernels, steps):
+    """ctc_spot, ctc_find and ctc_forward (HIP events) on the same phrases under each forced kernel: one warm-up round, then
+    `steps` rounds that alternate between the three calls and the kernels. -> {(call, kernel): median kernel ms}"""
+    got = {}
+    for step in range(steps + 1):
+        for k in kernels:
+            os.environ["CTCDEC_FIND_KERNEL"] = os.environ["CTCDEC_FORWARD_KERNEL"] = k
+            out = dec.spot_batch(dev, tokens=phrases)
+            dec.find_batch(dev, tokens=phrases)
+            dec.score_batch(dev, tokens=phrases)
+            if step:
+                for call, ms in (("spot", dec.last_spot_timing_ms[2]), ("find", dec.last_find_timing_ms[2]), ("forward", dec.last_score_timing_ms[2])):
+                    got.setdefault((call, k), []).append(ms)
+    os.environ.pop("CTCDEC_FIND_KERNEL", None), os.environ.pop("CTCDEC_FORWARD_KERNEL", None)
+    assert all(len(g.hits) == 1 and np.isfinite(g.count) for per_utt in out for g in per_utt)
+    return {key: float(np.median(v)) for key, v in got.items()}
+
+
+def spot_row(what, got, kernels):
+    return ["  %-22s %-5s  ctc_spot %9.3f ms  ctc_find %9.3f ms  ctc_forward %9.3f ms  spot/forward %5.2f  spot/find %5.2f" % (
+        what, k, got["spot", k], got["find", k], got["forward", k], got["spot", k] / got["forward", k], got["spot", k] / got["find", k])
+        for k in kernels]
+
+
+def spot_lines(dec, dev, targets, steps, phrase_labels=8):
+    """Each utterance spotted for one phrase of `phrase_labels` labels cut from its own decoded tokens (find_lines' cuts)."""
+    rng = np.random.default_rng(9)
+    phrases = []
+    for t in targets:
+        k = int(rng.integers(0, max(1, len(t) - phrase_labels + 1)))
+        phrases.append([list(t[k:k + phrase_labels])])
+    return spot_row("spot_batch 1 phrase x %d" % phrase_labels, time_spot(dec, dev, phrases, ("wave", "group"), steps), ("wave", "group"))
+
+
+def spot_sweep_lines(dec, steps):
+    """find_sweep_lines' batches: 256 utterances of standard-normal logits x 3, 1 and 8 random phrases without repeats of
+    15 / 127 / 511 labels each."""
+    import torch
+
+    lines = ["spot: sweep of phrase lengths, 256 utterances x %d frames x %d labels float32 (random logits), 1 and 8 phrases per "
+             "utterance; %d alternating steps after one warm-up round, medians (kernels alone, HIP events):" % (T, V, steps)]
+    rng = np.random.default_rng(5)
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(5)
+    blank = dec._alphabet.labels.index("")
+    pool = np.array([c for c in range(V) if c != blank])
+    dev = torch.randn((DISTINCT, T, V), generator=gen, device="cuda", dtype=torch.float32) * 3
+    torch.cuda.synchronize()
+    for L in (15, 127, 511, 15):  # (15 labels twice: what the first row measures may be the first use, not the length)
+        eights = []
+        for _ in range(DISTINCT):
+            cur = []
+            for _k in range(8):
+                t = pool[rng.integers(0, len(pool), size=L)]
+                same = np.flatnonzero(t[1:] == t[:-1]) + 1
+                t[same] = pool[(np.searchsorted(pool, t[same]) + 1) % len(pool)]
+                cur.append(t.tolist())
+            eights.append(cur)
+        kernels = ("wave", "group") if L <= 127 else ("group",)
+        for n, phrases in ((1, [c[:1] for c in eights]), (8, eights)):
+            lines += spot_row("%4d labels x %d" % (L, n), time_spot(dec, dev, phrases, kernels, steps), kernels)
     del dev
     return lines
 
@@ -573,6 +641,8 @@ def main():
             lines += gradient_lines(dec, dev, targets, args.steps)
         if "find" in legs:
             lines += find_lines(dec, dev, targets, args.steps)
+        if "spot" in legs:
+            lines += spot_lines(dec, dev, targets, args.steps)
         if "gaps" in legs:
             lines += gaps_lines(dec, dev, targets, args.steps)
         if "greedy" in legs:
@@ -586,6 +656,8 @@ def main():
         lines += sweep_lines(dec, max(args.steps, 5))
     if "find" in legs:
         lines += find_sweep_lines(dec, args.steps)
+    if "spot" in legs:
+        lines += spot_sweep_lines(dec, args.steps)
     text = "\n".join(lines) + "\n"
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
