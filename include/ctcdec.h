@@ -766,6 +766,36 @@ int ctcdec_spot_batch(ctcdec_decoder* dec, const void* const* utt_logits, const 
                       double min_logp, int32_t want_trace, int32_t kernel, int64_t trace_budget, ctcdec_search** out);
 int ctcdec_search_count(const ctcdec_search* s, const double** count);
 
+/* ---- phrase spotting on streams: ctcdec_spot_batch's trace, chunk by chunk, the states kept on the device ---------------------
+ * A session spots, on each of n_streams live streams, that stream's phrases hyp_off[u] .. hyp_off[u + 1] (ctcdec_spot_batch's
+ * layout and label checks; 1 .. 127 labels per phrase, more is CTCDEC_ERR_LIMIT). max_frames > 0 allocates, once, a device
+ * trace of 12 bytes per frame per phrase, which ctcdec_spot_streams_hits selects from; it never grows, and a feed that would
+ * take a stream past it is CTCDEC_ERR_LIMIT and leaves the session as it was. 0 keeps no trace.
+ * ctcdec_spot_streams_feed takes one chunk per stream ([chunk_frames[u], V] of `dtype`, host or device memory; 0 frames are
+ * allowed, and all a stream that has ended may get, else CTCDEC_ERR_ARG) and advances every phrase by its stream's chunk in one
+ * ctc_spot_chunk launch. Each chunk is classified as probabilities or logits, and gets its row log-sum-exps, on its own.
+ * is_end[u] != 0 ends stream u with this chunk. Entry t of a phrase is final once frame t + 1 has been fed or the stream has
+ * ended: a chunk of n frames after t0 > 0 earlier ones makes the entries t0 - 1 .. t0 + n - 2 final, a stream's first chunk
+ * one fewer (from entry 0), its last one more. Phrase h's new entries are [entry_off[h], entry_off[h + 1]) of end_logp /
+ * end_start, the first of them frame first_frame[h]; count[h] is the running sum of exp(end_logp) over the final entries.
+ * Every entry and count equals, bit for bit, what ctcdec_spot_batch returns for the concatenated chunks, however they are
+ * cut, provided the chunks and the whole classify alike. min_width: 0, or the fewest lanes (8, 16, 32, 64) a phrase takes in a
+ * wavefront -- 64 is one phrase per wavefront. The pointers stay valid until the session's next call.
+ * ctcdec_spot_streams_hits: ctcdec_find_batch's selection over every phrase's final entries; the layout of
+ * ctcdec_search_hits. Needs max_frames > 0, else CTCDEC_ERR_ARG. ctcdec_spot_streams_timing, of the last feed: [0]
+ * classification, [1] row_lse, [2] ctc_spot_chunk (HIP events), [3] the whole call; the wavefronts launched with segments of
+ * 8, 16, 32 and 64 lanes. Every entry takes the device lock. The decoder has to outlive its sessions. decoder.py: spot_streams. */
+typedef struct ctcdec_spot_streams ctcdec_spot_streams; /* opaque */
+int ctcdec_spot_streams_open(ctcdec_decoder* dec, int32_t n_streams, const int64_t* hyp_off, const int64_t* label_off,
+                             const int32_t* labels, int64_t max_frames, ctcdec_spot_streams** out);
+int ctcdec_spot_streams_feed(ctcdec_spot_streams* s, const void* const* chunk_ptrs, const int32_t* chunk_frames, const int32_t* is_end,
+                             int32_t dtype, int32_t is_device, int32_t min_width, const int64_t** entry_off, const int32_t** first_frame,
+                             const double** end_logp, const int32_t** end_start, const double** count);
+int ctcdec_spot_streams_hits(ctcdec_spot_streams* s, int32_t max_hits, double min_logp, const int64_t** hit_off, const int32_t** start,
+                             const int32_t** end, const double** logp, int64_t* n_phrases);
+int ctcdec_spot_streams_timing(const ctcdec_spot_streams* s, double* ms4, int64_t* waves4);
+void ctcdec_spot_streams_close(ctcdec_spot_streams* s);
+
 /* timing of the last call's device stages in milliseconds (HIP events on the decode stream):
  * [0] frame-prune kernel, [1] beam kernel, [2] total device time incl. result copy */
 int ctcdec_result_timing(const ctcdec_result* r, double* ms3);

@@ -2,7 +2,7 @@
 (reference exports: pyctcdecode/__init__.py:2-4)."""
 from .alphabet import Alphabet  # noqa: F401
 from .decoder import (ALIGN_LONG_MAX_LABELS, AlignedText, BeamSearchDecoderCTC, ConfidenceLMBeam, ConfidenceOutputBeam, GappedAlignment, GreedyFrames,  # noqa: F401
-                      GreedyText, PhraseHit, PhraseSearch, PhraseSpot, PrefixScores, PrefixSession, ScoredText, SessionPrefix, SpotHit, TokenFrames,
+                      GreedyText, PhraseHit, PhraseSearch, PhraseSpot, PrefixScores, PrefixSession, ScoredText, SessionPrefix, SpotChunk, SpotHit, SpotStreams, TokenFrames,
                       TokenLMBeam, TokenOutputBeam, TranscriptGradient, TranscriptPosteriors, build_ctcdecoder)
 from .language_model import LanguageModel  # noqa: F401
 

@@ -221,6 +221,16 @@ _PROTOS = {
                                     C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int32, C.c_double,
                                     C.c_int32, C.c_int32, C.c_int64, C.POINTER(_VP)]),
     "ctcdec_search_count": (C.c_int, [_VP, C.POINTER(C.POINTER(C.c_double))]),
+    "ctcdec_spot_streams_open": (C.c_int, [_VP, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int64,
+                                           C.POINTER(_VP)]),
+    "ctcdec_spot_streams_feed": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32,
+                                           C.POINTER(C.POINTER(C.c_int64)), C.POINTER(C.POINTER(C.c_int32)),
+                                           C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.POINTER(C.c_int32)),
+                                           C.POINTER(C.POINTER(C.c_double))]),
+    "ctcdec_spot_streams_hits": (C.c_int, [_VP, C.c_int32, C.c_double, C.POINTER(C.POINTER(C.c_int64)), C.POINTER(C.POINTER(C.c_int32)),
+                                           C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.c_int64)]),
+    "ctcdec_spot_streams_timing": (C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
+    "ctcdec_spot_streams_close": (None, [_VP]),
     "ctcdec_search_hits": (C.c_int, [_VP, C.POINTER(C.POINTER(C.c_int64)), C.POINTER(C.POINTER(C.c_int32)),
                                      C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.c_int64)]),
     "ctcdec_search_trace": (C.c_int, [_VP, C.POINTER(C.POINTER(C.c_int64)), C.POINTER(C.POINTER(C.c_double)),

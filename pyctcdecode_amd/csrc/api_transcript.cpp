@@ -2650,3 +2650,281 @@ int ctcdec_search_timing(const ctcdec_search* s, double* ms4, int32_t* launches_
 
 void ctcdec_search_free(ctcdec_search* s) { delete s; }
 }  // extern "C"
+
+// ---- phrase spotting on streams ("Phrase spotting on streams") ---------------------------------------------------
+// What outlives a feed: the phrases' labels, per phrase the states of every group (64 bytes each) and (fresh, count), with
+// max_frames the phrases' traces; per stream the frames fed so far and whether it has ended (host: every feed is validated
+// with them before anything is launched). The results of the last feed and of the last hits() stay until the next.
+struct ctcdec_spot_streams {
+  ctcdec_decoder* dec = nullptr;
+  TranscriptCall tc;
+  int32_t n_streams = 0;
+  int64_t NH = 0, max_frames = 0;
+  std::vector<int64_t> hyp_off, label_off, group_off;  // (group_off: where each phrase's groups start among all of them)
+  std::vector<int32_t> stream_of, t0;
+  std::vector<uint8_t> ended;
+  DevBuf lab, groups, hdr, trace, out, items, waves, hits;
+  // the last feed
+  std::vector<int64_t> entry_off;
+  std::vector<int32_t> first_frame, end_start;
+  std::vector<double> end_logp, count, hdr_host;
+  double ms[4] = {0, 0, 0, 0};
+  int64_t n_waves[4] = {0, 0, 0, 0};  // wavefronts launched with segments of 8, 16, 32, 64 lanes
+  // the last hits()
+  std::vector<int64_t> hit_off;
+  std::vector<int32_t> hit_start, hit_end;
+  std::vector<double> hit_logp;
+  int32_t L(int64_t h) const { return (int32_t)(label_off[(size_t)h + 1] - label_off[(size_t)h]); }
+  double* tr_logp(int64_t h) const { return (double*)trace.p + (size_t)h * (size_t)max_frames; }
+  int32_t* tr_start(int64_t h) const { return (int32_t*)((double*)trace.p + (size_t)NH * (size_t)max_frames) + (size_t)h * (size_t)max_frames; }
+  // the entries of a stream of t frames that are final: all of them once it has ended, all but the last before
+  static int32_t final_of(int32_t t, bool ended) { return ended ? t : std::max(t - 1, 0); }
+};
+
+extern "C" {
+
+int ctcdec_spot_streams_open(ctcdec_decoder* dec, int32_t n_streams, const int64_t* hyp_off, const int64_t* label_off, const int32_t* labels,
+                             int64_t max_frames, ctcdec_spot_streams** out) {
+  TranscriptCall tc;
+  const bool args_ok = dec && out && n_streams >= 0 && hyp_off && label_off && max_frames >= 0;
+  if (int rc = transcript_open(dec, args_ok, CTCDEC_F32, "", tc)) return rc;
+  if (hyp_off[0] != 0 || label_off[0] != 0) return fail(CTCDEC_ERR_ARG, "hyp_off and label_off must start at 0");
+  if (max_frames > (int64_t)0x7FFFFFFF) return fail(CTCDEC_ERR_LIMIT, "max_frames above 2^31 - 1");
+  for (int32_t u = 0; u < n_streams; ++u)
+    if (hyp_off[u + 1] < hyp_off[u]) return fail(CTCDEC_ERR_ARG, "hyp_off must not decrease");
+  const int64_t NH = hyp_off[n_streams];
+  if (NH > (int64_t)0x7FFFFFFF) return fail(CTCDEC_ERR_LIMIT, "more than 2^31 - 1 phrases in one session");
+  std::unique_ptr<ctcdec_spot_streams> s(new ctcdec_spot_streams);
+  s->dec = dec, s->tc = tc, s->n_streams = n_streams, s->NH = NH, s->max_frames = max_frames;
+  s->group_off.assign((size_t)NH + 1, 0);
+  s->stream_of.resize((size_t)NH);
+  for (int32_t u = 0; u < n_streams; ++u)
+    for (int64_t h = hyp_off[u]; h < hyp_off[u + 1]; ++h) {
+      const std::string who = "stream " + std::to_string(u) + ", phrase " + std::to_string(h - hyp_off[u]);
+      const int64_t L = label_off[h + 1] - label_off[h];
+      if (L < 0) return fail(CTCDEC_ERR_ARG, "label_off must not decrease");
+      if (L == 0) return fail(CTCDEC_ERR_ARG, who + ": an empty phrase occurs everywhere and nowhere");
+      if (L > FIND_WAVE_MAX_LABELS)
+        return fail(CTCDEC_ERR_LIMIT, who + ": " + std::to_string(L) + " labels, above the limit of " + std::to_string(FIND_WAVE_MAX_LABELS) +
+                                          " of a phrase spotted on a stream (a lane per four states)");
+      if (!labels) return fail(CTCDEC_ERR_ARG, "no labels");
+      int64_t need = 0;
+      if (int rc = check_labels(labels + label_off[h], L, tc.V, tc.blank, [&] { return who; }, "label", "label to spot", need)) return rc;
+      s->stream_of[(size_t)h] = u;
+      s->group_off[(size_t)h + 1] = s->group_off[(size_t)h] + find_chunks((int32_t)L);
+    }
+  s->hyp_off.assign(hyp_off, hyp_off + n_streams + 1);
+  s->label_off.assign(label_off, label_off + NH + 1);
+  s->t0.assign((size_t)n_streams, 0);
+  s->ended.assign((size_t)n_streams, 0);
+  s->count.assign((size_t)NH, 0.0);
+  AlignFront fr;
+  if (int rc = device_only_front(fr)) return rc;
+  // the states nothing has been fed to: every score -inf, every mean 0.0, fresh 0.0 (frame 0 is next), count 0.0
+  std::string err;
+  std::vector<double> init((size_t)s->group_off[(size_t)NH] * 8, 0.0);
+  for (size_t i = 0; i < init.size(); ++i)
+    if ((i & 7) < 4) init[i] = align_neg_inf();
+  const std::vector<int32_t> lab(labels, labels + (NH ? label_off[NH] : 0));
+  const size_t hdr_bytes = std::max<size_t>((size_t)NH * 16, 16), trace_bytes = (size_t)NH * (size_t)max_frames * FIND_TRACE_BYTES;
+  if (upload(s->lab, lab, &err) || upload(s->groups, init, &err) || s->hdr.ensure(hdr_bytes, &err) || be::zero(s->hdr.p, hdr_bytes, &err) ||
+      (trace_bytes && s->trace.ensure(trace_bytes, &err)) || be::sync(&err))
+    return fail(CTCDEC_ERR_DEVICE, err);
+  *out = s.release();
+  return CTCDEC_OK;
+}
+
+int ctcdec_spot_streams_feed(ctcdec_spot_streams* s, const void* const* chunk_ptrs, const int32_t* chunk_frames, const int32_t* is_end,
+                             int32_t dtype, int32_t is_device, int32_t min_width, const int64_t** entry_off, const int32_t** first_frame,
+                             const double** end_logp, const int32_t** end_start, const double** count) {
+  if (!s || !entry_off || !first_frame || !end_logp || !end_start || !count || (s->n_streams > 0 && (!chunk_ptrs || !chunk_frames || !is_end)))
+    return fail(CTCDEC_ERR_ARG, "bad arguments");
+  if (dtype < CTCDEC_F32 || dtype > CTCDEC_BF16) return fail(CTCDEC_ERR_ARG, "dtype must be f32, f64, f16 or bf16");
+  if (min_width != 0 && min_width != 8 && min_width != 16 && min_width != 32 && min_width != 64)
+    return fail(CTCDEC_ERR_ARG, "min_width must be 0 (the library packs), 8, 16, 32 or 64 lanes");
+  const int32_t min_shift = min_width == 64 ? 6 : min_width == 32 ? 5 : min_width == 16 ? 4 : 3;
+  const auto t_begin = Clock::now();
+  ctcdec_decoder* dec = s->dec;
+  const size_t n = (size_t)s->n_streams;
+  const int64_t NH = s->NH;
+  // everything before anything is launched or changed
+  int64_t R = 0;
+  for (int32_t u = 0; u < s->n_streams; ++u) {
+    const std::string who = "stream " + std::to_string(u);
+    if (int rc = check_frames(chunk_ptrs, chunk_frames, u)) return rc;
+    if (s->ended[(size_t)u] && chunk_frames[u] > 0) return fail(CTCDEC_ERR_ARG, who + " has ended: it takes no more frames");
+    const int64_t t1 = (int64_t)s->t0[(size_t)u] + chunk_frames[u];
+    if (t1 > (int64_t)0x7FFFFFFF) return fail(CTCDEC_ERR_LIMIT, who + ": more than 2^31 - 1 frames");
+    if (s->max_frames > 0 && t1 > s->max_frames)
+      return fail(CTCDEC_ERR_LIMIT, who + ": " + std::to_string(t1) + " frames, above the session's max_frames of " + std::to_string(s->max_frames));
+    R += chunk_frames[u];
+  }
+  // the entries this feed makes final, phrase by phrase
+  std::vector<int64_t> eoff((size_t)NH + 1, 0);
+  std::vector<int32_t> first((size_t)NH, 0);
+  for (int64_t h = 0; h < NH; ++h) {
+    const size_t u = (size_t)s->stream_of[(size_t)h];
+    const bool ends = s->ended[u] || is_end[u] != 0;
+    first[(size_t)h] = ctcdec_spot_streams::final_of(s->t0[u], s->ended[u] != 0);
+    eoff[(size_t)h + 1] = eoff[(size_t)h] + ctcdec_spot_streams::final_of(s->t0[u] + chunk_frames[u], ends) - first[(size_t)h];
+  }
+  const int64_t E = eoff[(size_t)NH];
+  std::string err;
+  AlignFront fr;
+  const std::vector<int64_t> row0 = row_starts(chunk_frames, n);
+  if (R > 0) {  // every chunk is classified, and gets its row_lse, on its own
+    if (int rc = align_front(dec, chunk_ptrs, chunk_frames, s->n_streams, dtype, is_device, s->tc.V, row0, fr)) return rc;
+  } else {
+    if (int rc = device_only_front(fr)) return rc;
+    fr.ptrs.assign(n, nullptr);
+    fr.is_prob.assign(n, 0);
+  }
+  s->ms[0] = fr.sniff_ms;
+  if (s->out.ensure(std::max<size_t>((size_t)E * 12, 16), &err)) return fail(CTCDEC_ERR_DEVICE, err);
+  double* const d_logp = (double*)s->out.p;
+  int32_t* const d_start = (int32_t*)(d_logp + E);
+  // the items that have a frame to run or an entry to close, by segment width; a wavefront per 64 >> shift of one width
+  std::vector<int32_t> by_shift[4];
+  for (int64_t h = 0; h < NH; ++h)
+    if (chunk_frames[s->stream_of[(size_t)h]] > 0 || eoff[(size_t)h + 1] > eoff[(size_t)h])
+      by_shift[spot_chunk_shift(s->L(h), min_shift) - 3].push_back((int32_t)h);
+  std::vector<SpotChunkItem> items;
+  std::vector<SpotChunkWave> waves;
+  for (int k = 0; k < 4; ++k) {
+    const int32_t per_wave = 64 >> (k + 3);
+    s->n_waves[k] = ((int64_t)by_shift[k].size() + per_wave - 1) / per_wave;
+    for (size_t i = 0; i < by_shift[k].size(); ++i) {
+      const int64_t h = by_shift[k][i];
+      const size_t u = (size_t)s->stream_of[(size_t)h];
+      SpotChunkItem it;
+      it.x = fr.ptrs[u];
+      it.lse = fr.lse ? fr.lse + row0[u] : nullptr;
+      it.lab = (const int32_t*)s->lab.p + s->label_off[(size_t)h];
+      it.groups = (double*)s->groups.p + 8 * s->group_off[(size_t)h];
+      it.hdr = (double*)s->hdr.p + 2 * h;
+      it.out_logp = d_logp + eoff[(size_t)h];
+      it.out_start = d_start + eoff[(size_t)h];
+      it.tr_logp = s->max_frames > 0 ? s->tr_logp(h) : nullptr;
+      it.tr_start = s->max_frames > 0 ? s->tr_start(h) : nullptr;
+      it.L = s->L(h), it.n = chunk_frames[u], it.t0 = s->t0[u], it.out_t0 = first[(size_t)h];
+      it.n_out = (int32_t)(eoff[(size_t)h + 1] - eoff[(size_t)h]);
+      it.is_prob = fr.is_prob[u] ? 1 : 0, it.is_end = is_end[u] != 0 && !s->ended[u], it.pad = 0;
+      if (i % (size_t)per_wave == 0) waves.push_back(SpotChunkWave{(int32_t)items.size(), 0, k + 3, 0});
+      ++waves.back().count;
+      waves.back().n_max = std::max(waves.back().n_max, it.n);
+      items.push_back(it);
+    }
+  }
+#ifdef CTC_SIM  // (the serial body, item by item: a single thread owns every group)
+  for (const SpotChunkItem& it : items)
+    for_dtype(dtype, [&](auto dt) { ctc_spot_chunk_seq<decltype(dt)::value>(it, s->tc.V, s->tc.blank, s->tc.clip_lo); });
+#else
+  if (!items.empty()) {
+    if (upload(s->items, items, &err) || upload(s->waves, waves, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+    be::SpotChunkArgs ca;
+    ca.waves = (const SpotChunkWave*)s->waves.p;
+    ca.items = (const SpotChunkItem*)s->items.p;
+    ca.n_waves = (int32_t)waves.size(), ca.n_items = (int32_t)items.size();
+    ca.n_labels = s->tc.V, ca.dtype = dtype, ca.blank = s->tc.blank, ca.clip_lo = s->tc.clip_lo;
+    if (be::launch_ctc_spot_chunk(ca, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+  }
+#endif
+  s->end_logp.resize((size_t)E);
+  s->end_start.resize((size_t)E);
+  s->hdr_host.resize((size_t)NH * 2);
+  if ((E && (be::d2h(s->end_logp.data(), d_logp, (size_t)E * 8, &err) || be::d2h(s->end_start.data(), d_start, (size_t)E * 4, &err))) ||
+      (NH && be::d2h(s->hdr_host.data(), s->hdr.p, (size_t)NH * 16, &err)) || be::sync(&err))
+    return fail(CTCDEC_ERR_DEVICE, err);
+  for (int64_t h = 0; h < NH; ++h) s->count[(size_t)h] = s->hdr_host[2 * (size_t)h + 1];
+  for (size_t u = 0; u < n; ++u) {
+    s->t0[u] += chunk_frames[u];
+    s->ended[u] = s->ended[u] || is_end[u] != 0;
+  }
+  s->entry_off.swap(eoff);
+  s->first_frame.swap(first);
+#ifndef CTC_SIM
+  s->ms[1] = R > 0 ? be::align_kernel_ms(be::K_ROW_LSE) : 0.0;
+  s->ms[2] = be::align_kernel_ms(be::K_SPOT_CHUNK);
+#endif
+  s->ms[3] = ms(t_begin, Clock::now());
+  *entry_off = s->entry_off.data(), *first_frame = s->first_frame.data();
+  *end_logp = s->end_logp.data(), *end_start = s->end_start.data(), *count = s->count.data();
+  return CTCDEC_OK;
+}
+
+int ctcdec_spot_streams_hits(ctcdec_spot_streams* s, int32_t max_hits, double min_logp, const int64_t** hit_off_out, const int32_t** start_out,
+                             const int32_t** end_out, const double** logp_out, int64_t* n_phrases_out) {
+  if (!s || !hit_off_out || !start_out || !end_out || !logp_out || !n_phrases_out) return fail(CTCDEC_ERR_ARG, "bad arguments");
+  if (s->max_frames <= 0) return fail(CTCDEC_ERR_ARG, "the session keeps no trace to select hits from: open it with max_frames > 0");
+  if (max_hits < 1 || max_hits > FIND_MAX_HITS) return fail(CTCDEC_ERR_ARG, "max_hits must be in 1 .. " + std::to_string(FIND_MAX_HITS));
+  if (min_logp != min_logp) return fail(CTCDEC_ERR_ARG, "min_logp is not a number");
+  AlignFront fr;
+  if (int rc = device_only_front(fr)) return rc;
+  const size_t NH = (size_t)s->NH, K = (size_t)max_hits;
+  std::string err;
+  // per phrase max_hits scores, then as many starts and ends, then the numbers of hits (ctcdec_find_batch's layout)
+  const size_t hits_bytes = std::max<size_t>(NH * K * 16 + NH * 4, 16);
+  if (s->hits.ensure(hits_bytes, &err) || be::zero(s->hits.p, hits_bytes, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+  double* const d_logp = (double*)s->hits.p;
+  int32_t* const d_start = (int32_t*)(d_logp + NH * K);
+  int32_t* const d_end = d_start + NH * K;
+  int32_t* const d_count = d_end + NH * K;
+  std::vector<FindPhrase> phrases(NH);
+  for (size_t h = 0; h < NH; ++h) {
+    const size_t u = (size_t)s->stream_of[h];
+    FindPhrase& a = phrases[h];
+    a.x = nullptr, a.lse = nullptr, a.lab = nullptr;
+    a.end_logp = s->tr_logp((int64_t)h);
+    a.end_start = s->tr_start((int64_t)h);
+    a.hit_logp = d_logp + h * K, a.hit_start = d_start + h * K, a.hit_end = d_end + h * K, a.n_hits = d_count + h;
+    a.T = ctcdec_spot_streams::final_of(s->t0[u], s->ended[u] != 0);
+    a.L = s->L((int64_t)h), a.is_prob = 0, a.pad = 0;
+  }
+#ifdef CTC_SIM
+  FindSeqCtx cx;
+  for (const FindPhrase& a : phrases) find_select(cx, a, max_hits, min_logp);
+#else
+  if (NH) {
+    if (upload(s->dec->w_fphr, phrases, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+    be::SpotSelectArgs sa;
+    sa.phrases = (const FindPhrase*)s->dec->w_fphr.p;
+    sa.n_phrases = (int32_t)NH, sa.max_hits = max_hits, sa.min_logp = min_logp;
+    if (be::launch_spot_select(sa, &err)) return fail(CTCDEC_ERR_DEVICE, err);
+  }
+#endif
+  std::vector<double> h_logp(NH * K);
+  std::vector<int32_t> h_start(NH * K), h_end(NH * K), n_hits(NH, 0);
+  if (NH && (be::d2h(h_logp.data(), d_logp, NH * K * 8, &err) || be::d2h(h_start.data(), d_start, NH * K * 4, &err) ||
+             be::d2h(h_end.data(), d_end, NH * K * 4, &err) || be::d2h(n_hits.data(), d_count, NH * 4, &err) || be::sync(&err)))
+    return fail(CTCDEC_ERR_DEVICE, err);
+  s->hit_off.assign(NH + 1, 0);
+  s->hit_start.clear(), s->hit_end.clear(), s->hit_logp.clear();
+  for (size_t h = 0; h < NH; ++h) {
+    if (n_hits[h] < 0 || n_hits[h] > max_hits) return fail(CTCDEC_ERR_DEVICE, "spot_select returned a hit count outside 0 .. max_hits");
+    s->hit_off[h + 1] = s->hit_off[h] + n_hits[h];
+    for (size_t j = 0; j < (size_t)n_hits[h]; ++j) {
+      s->hit_start.push_back(h_start[h * K + j]);
+      s->hit_end.push_back(h_end[h * K + j]);
+      s->hit_logp.push_back(h_logp[h * K + j]);
+    }
+  }
+  *hit_off_out = s->hit_off.data(), *start_out = s->hit_start.data(), *end_out = s->hit_end.data(), *logp_out = s->hit_logp.data();
+  *n_phrases_out = (int64_t)NH;
+  return CTCDEC_OK;
+}
+
+int ctcdec_spot_streams_timing(const ctcdec_spot_streams* s, double* ms4, int64_t* waves4) {
+  if (!s || !ms4) return fail(CTCDEC_ERR_ARG, "no spotting session");
+  std::lock_guard<std::mutex> device_lock(g_device_mu);
+  for (int k = 0; k < 4; ++k) ms4[k] = s->ms[k];
+  if (waves4)
+    for (int k = 0; k < 4; ++k) waves4[k] = s->n_waves[k];
+  return CTCDEC_OK;
+}
+
+void ctcdec_spot_streams_close(ctcdec_spot_streams* s) {
+  if (!s) return;
+  std::lock_guard<std::mutex> device_lock(g_device_mu);
+  delete s;
+}
+}  // extern "C"

@@ -358,6 +358,26 @@ struct SpotArgs {
   double min_logp;
 };
 int launch_ctc_spot(const SpotArgs& a, int wave, std::string* err);
+// ctc_spot_chunk: one wavefront per entry of `waves`, four to a workgroup; every item and wave record validated by the host
+// (SpotChunkItem, SpotChunkWave: segments of one width, first + count within n_items, n_max the longest chunk among them)
+struct SpotChunkArgs {
+  const SpotChunkWave* waves;  // [n_waves] (device)
+  const SpotChunkItem* items;  // [n_items] (device), sorted by segment width
+  int32_t n_waves, n_items;
+  int32_t n_labels;
+  int32_t dtype;
+  int32_t blank;
+  double clip_lo;
+};
+int launch_ctc_spot_chunk(const SpotChunkArgs& a, std::string* err);
+// spot_select: find_select by one wavefront per record, over a trace that is already there (T: its entries)
+struct SpotSelectArgs {
+  const FindPhrase* phrases;  // [n_phrases] (device)
+  int32_t n_phrases;
+  int32_t max_hits;
+  double min_logp;
+};
+int launch_spot_select(const SpotSelectArgs& a, std::string* err);
 // Alignment with gaps. row_lse_max: row_lse (the same bits in a.lse) that also stores each row's largest entry that is not a
 // NaN in rmax -- for the rows of probability-like utterances too, which get no log-sum-exp. ctc_viterbi_gaps: one workgroup
 // per entry of `utts`, all of them validated by the host (GapsUtt); 256 threads when every utterance of the launch has at
@@ -408,13 +428,14 @@ int launch_ctc_prefix_fill(double* next, const int32_t* rows, int32_t n_rows, in
 int launch_ctc_prefix_advance(const PrefixAdvanceArgs& a, std::string* err);
 // kernel times (HIP events) of the launches of one of these kernels since the last reset; waits for the kernels.
 // ctc_forward and ctc_forward_wave share a log (with their _ends forms), as do ctc_find and ctc_find_wave, ctc_spot and ctc_spot_wave, greedy_collapse's
-// two passes, and ctc_prefix_extend, ctc_prefix_finish and ctc_prefix_fill; ctc_prefix_advance has its own. ctc_forward_tile's
+// two passes, and ctc_prefix_extend, ctc_prefix_finish and ctc_prefix_fill; ctc_prefix_advance, ctc_spot_chunk and spot_select
+// have their own. ctc_forward_tile's
 // log holds one pair of events per launch_ctc_forward_tile: the fill and every diagonal; ctc_viterbi_tile's likewise, and
 // ctc_viterbi_cone's one pair per launch_ctc_viterbi_tiled.
 enum AlignKernel {
   K_ROW_LSE, K_VITERBI, K_FORWARD, K_POSTERIORS, K_GRAD_ROWS, K_FIND, K_ROW_LSE_MAX, K_VITERBI_GAPS, K_ROW_ARGMAX, K_ROW_LSE_ARGMAX,
   K_GREEDY_COLLAPSE, K_PREFIX_EXTEND, K_PREFIX_ADVANCE, K_VITERBI_LONG, K_VITERBI_GAPS_LONG, K_FORWARD_TILE, K_VITERBI_TILE,
-  K_VITERBI_CONE, K_SPOT, ALIGN_KERNELS
+  K_VITERBI_CONE, K_SPOT, K_SPOT_CHUNK, K_SPOT_SELECT, ALIGN_KERNELS
 };
 void align_timing_reset();
 double align_kernel_ms(AlignKernel kind);

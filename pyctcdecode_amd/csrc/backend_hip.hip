@@ -573,6 +573,10 @@ int launch_ctc_find_on(const FindArgs& a, int wave, hipStream_t stream, std::str
 int launch_ctc_find(const FindArgs& a, int wave, std::string* err) { return launch_ctc_find_on(a, wave, g_stream, err); }
 int launch_ctc_spot_on(const SpotArgs& a, int wave, hipStream_t stream, std::string* err);
 int launch_ctc_spot(const SpotArgs& a, int wave, std::string* err) { return launch_ctc_spot_on(a, wave, g_stream, err); }
+int launch_ctc_spot_chunk_on(const SpotChunkArgs& a, hipStream_t stream, std::string* err);
+int launch_ctc_spot_chunk(const SpotChunkArgs& a, std::string* err) { return launch_ctc_spot_chunk_on(a, g_stream, err); }
+int launch_spot_select_on(const SpotSelectArgs& a, hipStream_t stream, std::string* err);
+int launch_spot_select(const SpotSelectArgs& a, std::string* err) { return launch_spot_select_on(a, g_stream, err); }
 int launch_row_lse(const RowLseArgs& a, std::string* err) { return launch_row_lse_on(a, g_stream, err); }
 int launch_ctc_viterbi(const ViterbiArgs& a, std::string* err) { return launch_ctc_viterbi_on(a, g_stream, err); }
 int launch_ctc_viterbi_long_on(const ViterbiLongArgs& a, hipStream_t stream, std::string* err);

@@ -13,6 +13,7 @@
 //   ctc_grad_row                   the gradient of the likelihood, row by row   (ctc_grad_rows)
 //   ctc_find_phrase / _wave_phrase a phrase's occurrences, free start and end   (ctc_find / ctc_find_wave)
 //   ctc_spot_phrase / _wave_phrase the probability that a phrase ends on each frame  (ctc_spot / ctc_spot_wave)
+//   ctc_spot_chunk_wave / _seq     the same over one chunk of a stream, states carried   (ctc_spot_chunk; _seq: the simulator's)
 //   ctc_viterbi_gaps_utt           the best path of a target with gaps          (ctc_viterbi_gaps)
 //   ctc_viterbi_gaps_long_utt      the same, its columns in device memory, its frames in segments  (ctc_viterbi_gaps_long)
 //   row_argmax_seq                 a row's most probable label: the simulator's; the kernels fold by lanes
@@ -30,8 +31,8 @@
 //   thread_setup                                         ctc_find, ctc_spot, ctc_viterbi_gaps
 // ctc_forward_hyp, ctc_forward_wave_hyp and ctc_posteriors_utt keep their loops in raw variables: over FrameEntries
 // ctc_forward took 8 to 13 % and ctc_posteriors 2 % longer on batches of 64 utterances (profiles/align_refactor_check.txt).
-//   find_trace, find_select                              ctc_find, ctc_find_wave (find_select: ctc_spot, ctc_spot_wave too)
-//   spot_step, spot_ends, spot_trace                     ctc_spot, ctc_spot_wave
+//   find_trace, find_select                              ctc_find, ctc_find_wave (find_select: ctc_spot, ctc_spot_wave, spot_select too)
+//   spot_step, spot_ends, spot_trace                     ctc_spot, ctc_spot_wave, ctc_spot_chunk
 //   for_dtype (host)                                     the launchers and the simulator's calls
 #pragma once
 #include <math.h>
@@ -2194,6 +2195,144 @@ CTC_HD void ctc_spot_wave_phrase(Ctx& cx, const SpotPhrase& sp, int V, int blank
   }
   cx.publish();
   find_select(cx, ph, max_hits, min_logp);
+}
+
+// ---- ctc_spot_chunk ---------------------------------------------------------------------------------------------------------
+// Phrase spotting on streams ("Phrase spotting on streams"): ctc_spot_wave's recursion over one chunk of a stream's
+// frames, from the states the chunk before left on the device to the states the chunk after takes up. An item is one phrase
+// of one stream. Between feeds the device keeps, per item, a[4] and m[4] of every group (`groups`: 64 bytes a group) and
+// fresh and count (`hdr`); the stream's frame count t0 is the host's, which validates with it. A feed of n frames runs the
+// global frames t0 .. t0 + n - 1 through spot_ends and spot_step unchanged, so frame t0 finishes the entry of frame t0 - 1
+// from the carried states, and the entries t0 - 1 .. t0 + n - 2 become final; a stream that ends also gets entry t0 + n - 1
+// with right = 0.0, as ctc_spot_wave_phrase writes it after its loop. The same functions on the same operands in the same
+// order as ctc_spot_wave_phrase over the concatenated chunks: the same bits, however the frames are cut.
+struct SpotChunkItem {
+  const void* x;        // [n, V] the chunk, of the launch's dtype (not read when n == 0)
+  const double* lse;    // [n] log-sum-exp of each row of the chunk (not read when is_prob)
+  const int32_t* lab;   // [L]
+  double* groups;       // [find_chunks(L)][8] in / out: a[4], m[4] of every group
+  double* hdr;          // [2] in / out: fresh, count
+  double* out_logp;     // [n_out] out: the entries this feed makes final, from frame out_t0
+  int32_t* out_start;   // [n_out] out
+  double* tr_logp;      // [max_frames] the session's trace of this phrase, or null: the same entries at their frames
+  int32_t* tr_start;    // [max_frames]
+  int32_t L, n, t0, out_t0, n_out, is_prob, is_end, pad;
+};
+// One wavefront's share of a launch: `count` items of one segment width 1 << shift, from items[first]; n_max their longest chunk
+struct SpotChunkWave {
+  int32_t first, count, shift, n_max;
+};
+// The segment of lanes an item takes: the smallest of 8, 16, 32, 64 lanes (log2) that gives every group a lane, at least min_shift
+CTC_HD constexpr int32_t spot_chunk_shift(int32_t L, int32_t min_shift = 3) {
+  return find_chunks(L) <= 8 && min_shift <= 3 ? 3 : find_chunks(L) <= 16 && min_shift <= 4 ? 4 : find_chunks(L) <= 32 && min_shift <= 5 ? 5 : 6;
+}
+
+// What closes an item's chunk, by the owner of state S - 2: the last entry of a stream that ends, and the count
+CTC_HD void spot_chunk_close(const SpotChunkItem& it, int jf, const double* a, const double* m, double* end_logp, int32_t* end_start,
+                             double count) {
+  const int t1 = it.t0 + it.n;
+  if (it.is_end && t1 > 0) spot_trace(end_logp, end_start, t1 - 1, jf == 1 ? a[1] : a[3], jf == 1 ? m[1] : m[3], count);  // right is 0.0
+  it.hdr[1] = count;
+}
+// The feed's entries into the session's trace, entry i by whoever has i % step == first
+CTC_HD void spot_chunk_keep(const SpotChunkItem& it, int first, int step) {
+  for (int i = first; i < it.n_out; i += step) {
+    it.tr_logp[it.out_t0 + i] = it.out_logp[i];
+    it.tr_start[it.out_t0 + i] = it.out_start[i];
+  }
+}
+
+// One wavefront of ctc_spot_chunk: 64 >> shift items side by side, lane c = lane % W of a segment owning group c of the
+// segment's item, W = 1 << shift. Everything an item names -- matrix, lse row, labels, chunk length, frame offset -- is a
+// per-lane value: the items of a wave may belong to different streams. The last state of the group below comes by
+// ctc_spot_wave's two cx.up(), masked at c == 0, so nothing crosses a segment's edge; every lane takes part in them for the
+// n_max frames of the wave's longest chunk, and a segment whose chunk is over (or that has no item) idles. No LDS, no barrier.
+// Frame j + 1 of the chunk is requested before frame j's arithmetic.
+template <int DT, class Ctx>
+CTC_HD void ctc_spot_chunk_wave(Ctx& cx, const SpotChunkWave& w, const SpotChunkItem* items, int V, int blank, double clip_lo) {
+  const int W = 1 << w.shift, seg = cx.lane() >> w.shift, c = cx.lane() & (W - 1);
+  const bool has = seg < w.count;
+  const SpotChunkItem& it = items[w.first + (has ? seg : 0)];
+  const int L = has ? it.L : 0, n = has ? it.n : 0, t0 = it.t0;
+  const int nch = find_chunks(L);
+  const int cf = (2 * L - 1) >> 2, jf = (2 * L - 1) & 3;
+  const bool mine = c < nch;  // (a lane without a group loads, steps and stores nothing)
+  const double NEG = align_neg_inf();
+  double* const end_logp = it.out_logp - it.out_t0;  // (indexed with the recording's frame numbers, from out_t0 on)
+  int32_t* const end_start = it.out_start - it.out_t0;
+  EntrySource<1> src = {it.x, it.lse, nullptr, V, blank, it.is_prob != 0, clip_lo, {0}, {0}};
+  const ForwardGroup g = group_setup(it.lab, L, nch, c, blank, &src.i0[0], &src.i1[0]);
+  double a[4] = {NEG, NEG, NEG, NEG}, m[4] = {0.0, 0.0, 0.0, 0.0};
+  double fresh = 0.0, count = 0.0;
+  if (mine) {
+    const double* const st = it.groups + 8 * c;
+    CTC_UNROLL
+    for (int k = 0; k < 4; ++k) a[k] = st[k], m[k] = st[4 + k];
+    if (c == 0) fresh = it.hdr[0];
+    if (c == cf) count = it.hdr[1];
+  }
+  double fresh_next = fresh;
+  FrameEntries<DT, 1> now = {}, next = {};
+  if (mine && n > 0) now.request(src, 0);
+  for (int j = 0; j < w.n_max; ++j) {
+    const double below_a = cx.up(a[3]);  // (every lane takes part)
+    const double below_m = cx.up(m[3]);
+    if (mine && j < n) {
+      next.request(src, j + 1 < n ? j + 1 : j);  // (after the chunk's last frame: the last frame again)
+      const int t = t0 + j;
+      const double e0 = now.emit0(src, 0), e1 = now.emit1(src, 0);
+      spot_ends(c, cf, jf, t, e0, e1, a, m, end_logp, end_start, fresh_next, count);
+      spot_step(g, c == 0, t, fresh, c > 0 ? below_a : NEG, c > 0 ? below_m : 0.0, now.emit_blank(src), e0, e1, a, m);
+      fresh = fresh_next;
+      now = next;
+    }
+  }
+  if (mine) {
+    if (c == cf) spot_chunk_close(it, jf, a, m, end_logp, end_start, count);
+    double* const st = it.groups + 8 * c;
+    CTC_UNROLL
+    for (int k = 0; k < 4; ++k) st[k] = a[k], st[4 + k] = m[k];
+    if (c == 0) it.hdr[0] = fresh;
+  }
+  if (has && it.tr_logp) {
+    cx.publish();  // (the entries: stored by one lane of this wave, loaded by the segment)
+    spot_chunk_keep(it, c, W);
+  }
+}
+
+// The same item by one thread that owns every group (the simulator's form, as ctc_spot_phrase is ctc_spot_wave_phrase's):
+// the groups from the last down, so that each still finds the state of the group below as the frame before left it
+template <int DT>
+void ctc_spot_chunk_seq(const SpotChunkItem& it, int V, int blank, double clip_lo) {
+  constexpr int G = find_chunks(FIND_WAVE_MAX_LABELS);
+  const int L = it.L, n = it.n, nch = find_chunks(L);
+  const int cf = (2 * L - 1) >> 2, jf = (2 * L - 1) & 3;
+  const double NEG = align_neg_inf();
+  double* const end_logp = it.out_logp - it.out_t0;
+  int32_t* const end_start = it.out_start - it.out_t0;
+  EntrySource<G> src = {it.x, it.lse, nullptr, V, blank, it.is_prob != 0, clip_lo, {0}, {0}};
+  ForwardGroup g[G];
+  for (int c = 0; c < G; ++c) g[c] = group_setup(it.lab, L, nch, c, blank, &src.i0[c], &src.i1[c]);
+  double fresh = it.hdr[0], fresh_next = fresh, count = it.hdr[1];
+  FrameEntries<DT, G> now = {}, next = {};
+  if (n > 0) now.request(src, 0);
+  for (int j = 0; j < n; ++j) {
+    next.request(src, j + 1 < n ? j + 1 : j);
+    const int t = it.t0 + j;
+    const double e_blank = now.emit_blank(src);
+    for (int c = nch - 1; c >= 0; --c) {
+      double* const a = it.groups + 8 * c;
+      double* const m = a + 4;
+      const double e0 = now.emit0(src, c), e1 = now.emit1(src, c);
+      spot_ends(c, cf, jf, t, e0, e1, a, m, end_logp, end_start, fresh_next, count);
+      spot_step(g[c], c == 0, t, fresh, c > 0 ? a[-8 + 3] : NEG, c > 0 ? a[-4 + 3] : 0.0, e_blank, e0, e1, a, m);
+    }
+    fresh = fresh_next;
+    now = next;
+  }
+  spot_chunk_close(it, jf, it.groups + 8 * cf, it.groups + 8 * cf + 4, end_logp, end_start, count);
+  it.hdr[0] = fresh;
+  if (it.tr_logp) spot_chunk_keep(it, 0, 1);
 }
 
 // ---- row_lse_max / ctc_viterbi_gaps ------------------------------------------------------------------------------------------

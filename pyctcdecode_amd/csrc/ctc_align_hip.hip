@@ -7,6 +7,7 @@
 //   ctc_find, ctc_viterbi_gaps        (256 threads up to 511 labels, 1024 above)
 //   ctc_forward_wave, ctc_find_wave a wavefront per record of at most 127 labels
 //   ctc_spot, ctc_spot_wave         ctc_find's two arrangements under the forward recursion: a score and a mean per state
+//   ctc_spot_chunk, spot_select     64 / W stream items per wavefront in segments of W lanes, states carried between launches
 //   ctc_forward_tile                a workgroup per tile of a hypothesis' states and frames, a launch per diagonal of tiles
 //   ctc_viterbi_tile, _cone         the best path on the same tiles with checkpoints; then a workgroup per utterance traces back
 //   ctc_grad_rows                   G threads per row of a dense ctc_posteriors launch's tables
@@ -375,6 +376,29 @@ __global__ __launch_bounds__(ALIGN_THREADS) void ctc_spot_wave(SpotArgs a) {
   if (i >= a.n_phrases) return;  // (a whole wave: nothing in this kernel waits for another wave)
   FindWaveCtx cx((int)(threadIdx.x & 63u));
   ctc_spot_wave_phrase<DT>(cx, a.phrases[i], a.n_labels, a.blank, a.clip_lo, a.max_hits, a.min_logp);
+}
+
+// ---------------------------------------------------------------------------------------------
+// ctc_spot_chunk: phrase spotting on streams (ctc_align.h, "ctc_spot_chunk"). One launch advances every (stream, phrase)
+// item of a feed by its stream's chunk. A wavefront holds 64 / W items of one segment width W = 8, 16, 32 or 64 lanes, lane
+// c of a segment owning group c of its item: a keyword of 8 labels keeps 5 of 8 lanes busy where ctc_spot_wave keeps 5 of
+// 64. Scores and means are carried in device memory between launches (64 bytes a group), the neighbour's state comes by
+// ctc_spot_wave's two fp64 shuffles, masked at a segment's first lane. No LDS, no barrier, four wavefronts to a workgroup.
+// spot_select: a wavefront per phrase runs find_select over the entries a session's trace holds so far.
+// ---------------------------------------------------------------------------------------------
+template <int DT>
+__global__ __launch_bounds__(ALIGN_THREADS) void ctc_spot_chunk(SpotChunkArgs a) {
+  const int i = (int)blockIdx.x * FORWARD_WAVES + (int)(threadIdx.x >> 6);
+  if (i >= a.n_waves) return;  // (a whole wave: nothing in this kernel waits for another wave)
+  FindWaveCtx cx((int)(threadIdx.x & 63u));
+  ctc_spot_chunk_wave<DT>(cx, a.waves[i], a.items, a.n_labels, a.blank, a.clip_lo);
+}
+
+__global__ __launch_bounds__(ALIGN_THREADS) void spot_select(SpotSelectArgs a) {
+  const int i = (int)blockIdx.x * FORWARD_WAVES + (int)(threadIdx.x >> 6);
+  if (i >= a.n_phrases) return;
+  FindWaveCtx cx((int)(threadIdx.x & 63u));
+  find_select(cx, a.phrases[i], a.max_hits, a.min_logp);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1093,6 +1117,25 @@ int launch_ctc_spot_on(const SpotArgs& a, int wave, hipStream_t stream, std::str
         hipLaunchKernelGGL((ctc_spot<NT, DT>), dim3((unsigned)a.n_phrases), dim3(NT), lds, stream, a);
       });
     });
+  });
+}
+
+int launch_ctc_spot_chunk_on(const SpotChunkArgs& a, hipStream_t stream, std::string* err) {
+  if (a.n_waves <= 0) return 0;
+  if (a.dtype < 0 || a.dtype > 3 || !a.waves || !a.items || a.n_items < 1 || a.n_labels < 1) return bad_launch(err, "ctc_spot_chunk: bad arguments");
+  return timed_launch(K_SPOT_CHUNK, stream, err, [&] {
+    for_dtype(a.dtype, [&](auto dt) {
+      hipLaunchKernelGGL(ctc_spot_chunk<decltype(dt)::value>, dim3((unsigned)((a.n_waves + FORWARD_WAVES - 1) / FORWARD_WAVES)),
+                         dim3(ALIGN_THREADS), 0, stream, a);
+    });
+  });
+}
+
+int launch_spot_select_on(const SpotSelectArgs& a, hipStream_t stream, std::string* err) {
+  if (a.n_phrases <= 0) return 0;
+  if (!a.phrases || a.max_hits < 1 || a.max_hits > FIND_MAX_HITS) return bad_launch(err, "spot_select: bad arguments");
+  return timed_launch(K_SPOT_SELECT, stream, err, [&] {
+    hipLaunchKernelGGL(spot_select, dim3((unsigned)((a.n_phrases + FORWARD_WAVES - 1) / FORWARD_WAVES)), dim3(ALIGN_THREADS), 0, stream, a);
   });
 }
 

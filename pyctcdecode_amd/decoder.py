@@ -531,6 +531,176 @@ class PhraseSpot:
     end_start: Optional[np.ndarray] = None
 
 
+SPOT_STREAM_MAX_LABELS = 127  # FIND_WAVE_MAX_LABELS of csrc/ctc_align.h: ctc_spot_chunk gives a lane to every four states
+SPOT_STREAM_WIDTHS = (8, 16, 32, 64)  # CTCDEC_SPOT_STREAM_WIDTH: the fewest lanes of a wavefront a phrase takes (unset: packed)
+
+
+@dataclasses.dataclass(frozen=True, eq=False)
+class SpotChunk:
+    """What one SpotStreams.feed adds to a phrase: the entries of PhraseSpot's trace that became final in this call, frames
+    ``first_frame .. first_frame + len(end_logp) - 1`` of the whole stream (``end_start`` counts from the stream's first
+    frame too), and ``count``, the expected number of occurrences that end on a frame final so far."""
+
+    text: str
+    tokens: List[int]
+    first_frame: int
+    end_logp: np.ndarray
+    end_start: np.ndarray
+    count: float
+
+
+class SpotStreams:
+    """Phrase spotting on live streams (BeamSearchDecoderCTC.spot_streams; DESIGN.md, "Phrase spotting on streams"): the
+    session keeps every phrase's states on the device, so that ``feed`` advances all phrases of all streams by one chunk each
+    in one ctc_spot_chunk launch, and what it returns, chunk after chunk, is float for float the trace spot_batch computes
+    from the concatenated chunks. A context manager; ``close()`` frees the device memory."""
+
+    def __init__(self, decoder: "BeamSearchDecoderCTC", texts, tokens, n_streams: Optional[int], max_frames: Optional[int]):
+        self._decoder, self._lib, self._handle = decoder, decoder._lib, None
+        given = texts if texts is not None else tokens
+        if (texts is None) == (tokens is None):
+            raise ValueError("spot_streams: give exactly one of texts and tokens")
+        given = list(given)
+        if n_streams is not None:  # one flat list of phrases, shared by every stream
+            if isinstance(n_streams, bool) or not isinstance(n_streams, (int, np.integer)) or n_streams < 0:
+                raise ValueError("spot_streams: n_streams must be a non-negative int, not %r" % (n_streams,))
+            given = [given] * int(n_streams)
+        if isinstance(max_frames, bool) or not (max_frames is None or (isinstance(max_frames, (int, np.integer)) and 0 < max_frames < 2 ** 31)):
+            raise ValueError("spot_streams: max_frames must be None or an int in 1 .. 2^31 - 1, not %r" % (max_frames,))
+        n = len(given)
+        placeholder = [np.zeros((0, len(decoder._labels_list)))] * n
+        _, phrases = decoder._many_targets_each("spot_streams", "phrase", "phrases", placeholder, given if texts is not None else None,
+                                                given if tokens is not None else None)
+        for u, cur in enumerate(phrases):
+            for j, ids in enumerate(cur):
+                if not ids:
+                    raise ValueError("spot_streams: stream %d, phrase %d is empty: it would occur everywhere and nowhere" % (u, j))
+                if len(ids) > SPOT_STREAM_MAX_LABELS:
+                    raise ValueError("spot_streams: stream %d, phrase %d has %d labels, above the limit of %d labels of a phrase "
+                                     "spotted on a stream (spot / spot_batch take up to %d on a whole utterance)"
+                                     % (u, j, len(ids), SPOT_STREAM_MAX_LABELS, ALIGN_MAX_LABELS))
+        self._phrases = phrases
+        self._texts = [[decoder._words_of_target(ids)[0] for ids in cur] for cur in phrases]
+        self.n_streams, self.max_frames = n, None if max_frames is None else int(max_frames)
+        self._fed, self._ended = [0] * n, [False] * n  # frames fed to each stream, and whether it has ended
+        flat, label_off, hyp_off, self._n_phrases = decoder._pack_items(phrases)
+        handle = C.c_void_p()
+        with decoder._call_lock:
+            self._lib.check(self._lib.dll.ctcdec_spot_streams_open(
+                decoder._handle, n, B.off_ptr(hyp_off), B.off_ptr(label_off), flat.ctypes.data_as(C.POINTER(C.c_int32)),
+                self.max_frames or 0, C.byref(handle)))
+        self._handle = handle
+
+    def _open_handle(self):
+        if self._handle is None:
+            raise ValueError("the spotting session is closed")
+        return self._handle
+
+    def feed(self, chunks: Any, is_end: Any = False) -> List[List[SpotChunk]]:
+        """One chunk ``[frames, V]`` per stream -- host arrays or device tensors of one dtype, 0 frames allowed -- through
+        every phrase of its stream; ``is_end`` (a bool, or one per stream) ends a stream with this chunk, after which it
+        takes no more frames. Returns per stream, per phrase, a SpotChunk with the entries that became final: entry ``t``
+        is final once frame ``t + 1`` has been fed or the stream has ended. Each chunk is told apart as probabilities or
+        logits on its own, as a chunk given to partial_decode_beams is. A ValueError leaves the session as it was."""
+        handle = self._open_handle()
+        dec, n = self._decoder, self.n_streams
+        if getattr(chunks, "ndim", 0) != 3:
+            chunks = list(chunks)
+        if len(chunks) != n:
+            raise ValueError("feed: %d chunks for %d streams" % (len(chunks), n))
+        ends = [bool(is_end)] * n if isinstance(is_end, (bool, np.bool_)) else [bool(e) for e in is_end]
+        if len(ends) != n:
+            raise ValueError("feed: %d is_end flags for %d streams" % (len(ends), n))
+        width = os.environ.get("CTCDEC_SPOT_STREAM_WIDTH", "")
+        if width and width not in [str(w) for w in SPOT_STREAM_WIDTHS]:
+            raise ValueError("CTCDEC_SPOT_STREAM_WIDTH must be 8, 16, 32 or 64, not %r" % width)
+        lib = self._lib
+        with dec._call_lock:
+            batch, frames, ptrs, c_utts = dec._stage_transcript_call(chunks)
+            for u in range(n):
+                if self._ended[u] and int(frames[u]) > 0:
+                    raise ValueError("feed: stream %d has ended: it takes no more frames" % u)
+                if self.max_frames is not None and self._fed[u] + int(frames[u]) > self.max_frames:
+                    raise ValueError("feed: stream %d would hold %d frames, above the session's max_frames of %d"
+                                     % (u, self._fed[u] + int(frames[u]), self.max_frames))
+            c_end = np.asarray(ends, dtype=np.int32) if n else np.zeros(1, dtype=np.int32)
+            eo, ff, el, es, cn = (C.POINTER(C.c_int64)(), C.POINTER(C.c_int32)(), C.POINTER(C.c_double)(), C.POINTER(C.c_int32)(),
+                                  C.POINTER(C.c_double)())
+            lib.check(lib.dll.ctcdec_spot_streams_feed(
+                handle, *c_utts, c_end.ctypes.data_as(C.POINTER(C.c_int32)), batch.dtype, int(batch.is_device), int(width or 0),
+                C.byref(eo), C.byref(ff), C.byref(el), C.byref(es), C.byref(cn)))
+            for u in range(n):
+                self._fed[u] += int(frames[u])
+                self._ended[u] = self._ended[u] or ends[u]
+            nph = self._n_phrases
+            off = np.ctypeslib.as_array(eo, shape=(nph + 1,)).tolist() if nph else [0]
+            first = np.ctypeslib.as_array(ff, shape=(nph,)).tolist() if nph else []
+            counts = np.ctypeslib.as_array(cn, shape=(nph,)).tolist() if nph else []
+            logp = np.ctypeslib.as_array(el, shape=(off[-1],)).copy() if off[-1] else np.zeros(0)
+            start = np.ctypeslib.as_array(es, shape=(off[-1],)).copy() if off[-1] else np.zeros(0, dtype=np.int32)
+            ms, waves = (C.c_double * 4)(), (C.c_int64 * 4)()
+            lib.dll.ctcdec_spot_streams_timing(handle, ms, waves)
+            dec.last_spot_stream_timing_ms = tuple(float(v) for v in ms)
+            dec.last_spot_stream_launched = tuple(int(v) for v in waves)
+            dec.last_spot_stream_launches = 1 if any(waves) else 0
+        out, h = [], 0
+        for u, cur in enumerate(self._phrases):
+            got = []
+            for j, ids in enumerate(cur):
+                got.append(SpotChunk(self._texts[u][j], list(ids), first[h], logp[off[h]:off[h + 1]], start[off[h]:off[h + 1]], counts[h]))
+                h += 1
+            out.append(got)
+        return out
+
+    def hits(self, max_hits: int = 1, min_logp: Optional[float] = None) -> List[List[List[SpotHit]]]:
+        """spot_batch's hits, per stream and phrase, over the entries final so far: up to ``max_hits`` pairwise disjoint
+        windows, most probable end frame first, none below ``min_logp`` (kernel spot_select: find_batch's selection on the
+        session's device trace). Needs a session opened with ``max_frames``. Once every stream has ended these are
+        spot_batch's hits on the concatenated chunks."""
+        handle = self._open_handle()
+        if self.max_frames is None:
+            raise ValueError("hits: the session keeps no trace to select from: open it with spot_streams(..., max_frames=)")
+        if isinstance(max_hits, bool) or not isinstance(max_hits, (int, np.integer)) or not 1 <= int(max_hits) <= FIND_MAX_HITS:
+            raise ValueError("hits: max_hits must be an int in 1 .. %d, not %r" % (FIND_MAX_HITS, max_hits))
+        floor = -math.inf if min_logp is None else float(min_logp)
+        if math.isnan(floor):
+            raise ValueError("hits: min_logp is not a number")
+        lib = self._lib
+        with self._decoder._call_lock:
+            ho, ps, pe, pl, nph = (C.POINTER(C.c_int64)(), C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)(), C.POINTER(C.c_double)(), C.c_int64())
+            lib.check(lib.dll.ctcdec_spot_streams_hits(handle, int(max_hits), floor, C.byref(ho), C.byref(ps), C.byref(pe), C.byref(pl),
+                                                       C.byref(nph)))
+            n = int(nph.value)
+            off = np.ctypeslib.as_array(ho, shape=(n + 1,)).tolist() if n else [0]
+            nh = off[-1]
+            starts = np.ctypeslib.as_array(ps, shape=(nh,)).tolist() if nh else []
+            ends = np.ctypeslib.as_array(pe, shape=(nh,)).tolist() if nh else []
+            logps = np.ctypeslib.as_array(pl, shape=(nh,)).tolist() if nh else []
+        out, h = [], 0
+        for cur in self._phrases:
+            out.append([[SpotHit(starts[k], ends[k], logps[k]) for k in range(off[h + j], off[h + j + 1])] for j in range(len(cur))])
+            h += len(cur)
+        return out
+
+    def close(self) -> None:
+        if self._handle is not None:
+            with self._decoder._call_lock:
+                self._lib.dll.ctcdec_spot_streams_close(self._handle)
+            self._handle = None
+
+    def __enter__(self) -> "SpotStreams":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 (interpreter shutdown)
+            pass
+
+
 POSTERIORS_TABLE_BUDGET = 4 << 30  # bytes of tables one ctc_posteriors launch holds by default (DESIGN.md, "Frame posteriors")
 FORWARD_KERNELS = {"wave": 1, "group": 2}  # ctcdec_score_batch's `kernel` from CTCDEC_FORWARD_KERNEL (unset: the library chooses)
 FIND_KERNELS = {"wave": 1, "group": 2}  # ctcdec_find_batch's `kernel` from CTCDEC_FIND_KERNEL (unset: the library chooses)
@@ -1526,6 +1696,11 @@ class BeamSearchDecoderCTC:
         self.last_spot_timing_ms = (0.0, 0.0, 0.0, 0.0)
         self.last_spot_launches = 0
         self.last_spot_launched = (0, 0)
+        # ... and of the last SpotStreams.feed (ms: classification, row_lse, ctc_spot_chunk, native call; kernel launches made;
+        # wavefronts launched with segments of 8, 16, 32 and 64 lanes)
+        self.last_spot_stream_timing_ms = (0.0, 0.0, 0.0, 0.0)
+        self.last_spot_stream_launches = 0
+        self.last_spot_stream_launched = (0, 0, 0, 0)
         # ... and of the last align_gaps / align_gaps_batch call (ms: classification, row_lse_max, ctc_viterbi_gaps, native
         # call; kernel launches made)
         self.last_align_gaps_timing_ms = (0.0, 0.0, 0.0, 0.0)
@@ -3060,6 +3235,16 @@ class BeamSearchDecoderCTC:
                 h += 1
             out.append(found)
         return out
+
+    def spot_streams(self, texts: Optional[Sequence[Any]] = None, tokens: Optional[Sequence[Any]] = None,
+                     n_streams: Optional[int] = None, max_frames: Optional[int] = None) -> "SpotStreams":
+        """spot_batch for live audio: a SpotStreams session whose ``feed`` takes one chunk per stream and returns the entries
+        of spot_batch's trace that became final, the states of every phrase kept on the device in between (kernel
+        ctc_spot_chunk, csrc/ctc_align_hip.hip; DESIGN.md, "Phrase spotting on streams"). ``texts`` / ``tokens``: one list of
+        phrases per stream, or, with ``n_streams``, one flat list that every stream shares; 1 .. 127 labels per phrase.
+        ``max_frames`` keeps a device trace of that many frames per phrase for ``hits()``; a stream cannot be fed past it.
+        ``CTCDEC_SPOT_STREAM_WIDTH=64`` gives every phrase a wavefront of its own instead of packing short ones."""
+        return SpotStreams(self, texts, tokens, n_streams, max_frames)
 
     # -- frame posteriors (no reference analogue; DESIGN.md, "Frame posteriors") ---------------------------
     def posteriors(self, logits: Any, text: Optional[str] = None, tokens: Optional[Sequence[int]] = None,

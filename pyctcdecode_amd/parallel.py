@@ -221,6 +221,11 @@ def spot_batch_sharded(decoder, logits_list, texts=None, group=None, **kwargs):
     raise NotImplementedError("spot_batch is not gathered over ranks: spot in each rank's slice with decoder.spot_batch itself")
 
 
+def spot_streams_sharded(decoder, texts=None, group=None, **kwargs):
+    """Spotting sessions are not sharded over ranks: each rank opens decoder.spot_streams for its own streams."""
+    raise NotImplementedError("spot_streams is not gathered over ranks: open decoder.spot_streams for each rank's own streams")
+
+
 def align_gaps_batch_sharded(decoder, logits_list, texts=None, group=None, **kwargs):
     """Alignment with gaps is not sharded over ranks: each rank calls decoder.align_gaps_batch on its own slice."""
     raise NotImplementedError("align_gaps_batch is not gathered over ranks: align each rank's slice with decoder.align_gaps_batch itself")
@@ -408,6 +413,10 @@ class DevicePool:
         raise NotImplementedError("DevicePool does not shard spot_batch: call decoder.spot_batch on the process's own device")
 
     spot = spot_batch
+
+    def spot_streams(self, texts=None, **kwargs):
+        """A spotting session lives on the calling process's own device: a pool does not shard it."""
+        raise NotImplementedError("DevicePool does not shard spot_streams: call decoder.spot_streams on the process's own device")
 
     def align_gaps_batch(self, logits_list, texts=None, **kwargs):
         """Alignment with gaps runs on the calling process's own device: a pool does not shard it."""
