@@ -365,6 +365,51 @@ def split_texts(blob_ptr, nbytes: int, n: int, sep: bytes):
     return C.string_at(blob_ptr, nbytes).decode("utf-8").split(sep.decode("ascii"))
 
 
+_AS_IS, _NUMBER, _NUMBERS = 0, 1, 2  # how read_out hands an out-value back
+# (function name, number of inputs, sizes) -> (the out-values' types, how each is handed back). By name, so every Library
+# loaded in the process shares the plans: all of them take their argtypes from _PROTOS.
+_OUT_PLANS: dict = {}
+
+
+def _out_plan(fn, n_in: int, sizes: Sequence[int]):
+    """What read_out makes for ``fn`` after ``n_in`` inputs, worked out once per function: per remaining ``POINTER(T)``
+    entry of ``fn.argtypes`` a ``T`` -- handed back as a Python number when T is a number, as it is when T is itself a
+    pointer (``void *`` included) --, or, where ``sizes`` gives a length, an array of T handed back as a tuple."""
+    types, how = [], []
+    for k, t in enumerate(fn.argtypes[n_in:]):
+        of = t._type_
+        if k < len(sizes) and sizes[k]:
+            types.append(of * sizes[k]), how.append(_NUMBERS)
+        else:  # (a simple type's own _type_ is its one-letter code; a pointer type's is the type it points to)
+            types.append(of), how.append(_NUMBER if isinstance(of._type_, str) and of is not C.c_void_p else _AS_IS)
+    return tuple(types), tuple(how)
+
+
+def read_out(lib: "Library", fn, *args, sizes: Sequence[int] = ()) -> list:
+    """Calls a getter of the library: ``fn(*args, outs...)`` with one out-value per entry of ``fn.argtypes`` after the
+    inputs ``args``, each of the type that ``POINTER(...)`` entry points to -- an array of ``sizes[k]`` of them where the
+    library fills several (a timing call's milliseconds), else -- ``sizes[k]`` 0 or not given -- one: ``sizes=(4, 0, 2)`` is
+    four values, one value, two values. Checks the status and returns the out-values: numbers
+    as Python numbers, arrays as tuples of them, and the pointers the library set as they are (for ``values``)."""
+    key = (fn.__name__, len(args), sizes)
+    plan = _OUT_PLANS.get(key)
+    if plan is None:
+        plan = _OUT_PLANS[key] = _out_plan(fn, len(args), sizes)
+    outs = [t() for t in plan[0]]
+    lib.check(fn(*args, *outs))  # (ctypes passes a T where POINTER(T) is declared by reference)
+    return [o if h == _AS_IS else o.value if h == _NUMBER else tuple(o) for o, h in zip(outs, plan[1])]
+
+
+def values(ptr, n, copy: bool = False):
+    """The ``n`` values (``n`` may be a shape) an out-pointer of ``read_out`` points to: a list, or with ``copy`` an array
+    of their own, which outlives the library's result. Empty when there are none: the pointer may then be NULL."""
+    shape = n if isinstance(n, tuple) else (n,)
+    if 0 in shape:
+        return np.zeros(shape, dtype=ptr._type_) if copy else []
+    a = np.ctypeslib.as_array(ptr, shape=shape)
+    return a.copy() if copy else a.tolist()
+
+
 def get_library() -> Library:
     global _LIB
     if _LIB is None:
