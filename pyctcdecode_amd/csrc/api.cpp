@@ -950,8 +950,10 @@ static void size_arenas(DecodeCall& c, bool full) {
     const uint64_t T = (uint64_t)c.utt_frames[u];
     const uint64_t n_imp = c.rs ? (uint64_t)c.rs->mirror[(size_t)u].n_carry
                                 : c.stream ? (uint64_t)(c.stream->beam_off[u + 1] - c.stream->beam_off[u]) : 0;
-    c.toff[(size_t)u + 1] = c.toff[(size_t)u] + ((T + 1) * per_frame + 2 * B + 2 + n_imp) * K;
-    c.eoff[(size_t)u + 1] = c.eoff[(size_t)u] + T * per_frame + 2 * B + 2 + n_imp;
+    // (a stream may carry in more beams than this chunk's beam_width: its first frame -- or, in a chunk of no frames, the
+    // closing fold -- advances every one of them, a node each, whatever per_frame says: n_imp for the imports and n_imp more)
+    c.toff[(size_t)u + 1] = c.toff[(size_t)u] + ((T + 1) * per_frame + 2 * B + 2 + 2 * n_imp) * K;
+    c.eoff[(size_t)u + 1] = c.eoff[(size_t)u] + T * per_frame + 2 * B + 2 + 2 * n_imp;
   }
 }
 
@@ -966,6 +968,7 @@ static int stage_resident_input(DecodeCall& c) {
   uint64_t need = 0;
   for (int32_t u = 0; u < n_utts; ++u)
     need = std::max<uint64_t>(need, (uint64_t)rs->mirror[(size_t)u].emit_next + (uint64_t)c.utt_frames[u] * (uint64_t)c.B +
+                                        (uint64_t)rs->mirror[(size_t)u].n_carry +  // (the first frame advances every carried beam)
                                         (uint64_t)ctcdec_stream::CAP + 2);
   if (need <= rs->emit_cap) return CTCDEC_OK;
   // (sized for the worst case -- one node per frame and beam --, of which a real stream uses a few per cent: grow
@@ -1189,7 +1192,7 @@ static int reserve_pay(DecodeCall& c) {
   ba.pay = nullptr;
   ba.pay_stride = 0;
   if (be::wave_kernel_chosen(ba)) {  // reserved only for launches that will use it (2 GB at the bench size)
-    ba.pay_stride = (uint64_t)wave_pay_stride(ba.params);
+    ba.pay_stride = (uint64_t)wave_pay_stride(ba.params, ba.max_import);
     if (c.dec->w_pay.ensure((size_t)c.n_utts * (size_t)ba.pay_stride * sizeof(PoolPay), &c.err)) return fail(CTCDEC_ERR_DEVICE, c.err);
     ba.pay = (PoolPay*)c.dec->w_pay.p;
   }

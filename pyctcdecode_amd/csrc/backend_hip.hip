@@ -354,7 +354,7 @@ int last_beam_kernel() { return g_last_kernel; }
 
 bool beam_kernel_depends_on_input(const BeamArgs& a) {
   return !getenv("CTCDEC_BEAM_KERNEL") && a.n_utts > 0 && a.n_utts <= g_cus && wave_eligible(a.tables, a.params) &&
-         a.max_import <= wave_bucket(a.params.beam_width);
+         a.max_import <= WAVE_MAX_BEAMS;
 }
 
 bool wave_kernel_chosen(const BeamArgs& a) {
@@ -370,8 +370,9 @@ bool wave_kernel_chosen(const BeamArgs& a) {
   bool small_group = true;
   if (a.surv_x16 > 0 && a.n_utts <= g_cus) small_group = a.surv_x16 > 3 * 16;
   const bool want_group = force ? force[0] == 'g' : (a.n_utts <= 2 * g_cus && small_group);
-  // (streaming: a stream may carry in more beams than this call's beam_width -- up to the workgroup kernel's table)
-  return a.n_utts > 0 && !want_group && wave_eligible(a.tables, a.params) && a.max_import <= wave_bucket(a.params.beam_width);
+  // (streaming: a stream may carry in more beams than this call's beam_width; the wave kernel runs on the table that holds
+  // them, beam_wave.h: wave_table, and more than its largest go to the workgroup kernel)
+  return a.n_utts > 0 && !want_group && wave_eligible(a.tables, a.params) && a.max_import <= WAVE_MAX_BEAMS;
 }
 
 // Per-label hot-word view of every set of a call with per-utterance hot words (what HostHotwords::build does on the host for
@@ -498,7 +499,10 @@ int launch_beam(const BeamArgs& a, std::string* err) {
     // 15.2 ms, 64 threads 19.7 ms for this kernel). CTCDEC_GROUP_THREADS=256|512 forces one.
     const char* gt = getenv("CTCDEC_GROUP_THREADS");
     const bool wide = a.tables.n_lms <= 1 && (gt ? gt[0] == '5' : a.n_utts <= g_cus);
-    LdsShape shape = make_shape(a.params.beam_width, a.params.max_surv, group_cand(beam_bucket(a.params.beam_width), wide));
+    // (streaming: the table holds what the streams carry in -- up to the beam_width of their previous chunk, which may be
+    // more than this chunk's)
+    const int table_for = std::max<int>(a.params.beam_width, a.max_import);
+    LdsShape shape = make_shape(table_for, a.params.max_surv, group_cand(beam_bucket(table_for), wide));
     size_t lds = lds_bytes(shape);
     if (lds > 160 * 1024) {
       if (err) *err = "beam table does not fit LDS (" + std::to_string(lds) + " bytes)";

@@ -197,7 +197,11 @@ CTC_HD bool wave_eligible(const DeviceTables& t, const DecodeParams& p) {
 }
 CTC_HD int wave_bucket(int beam_width) { return beam_width <= 64 ? 64 : beam_width <= 100 ? 100 : 128; }
 // payload lines per utterance: one per candidate that can be pushed in a frame
-CTC_HD size_t wave_pay_stride(const DecodeParams& p) { return (size_t)p.max_surv * (size_t)wave_bucket(p.beam_width); }
+// the table a launch runs on: it holds this call's beam_width and what its streams carry in (up to the beam_width of their
+// previous chunk, which may be more); more than 128 carried beams do not fit any (the workgroup kernel takes those)
+constexpr int WAVE_MAX_BEAMS = 128;
+CTC_HD int wave_table(const DecodeParams& p, int max_import) { return wave_bucket(p.beam_width > max_import ? p.beam_width : max_import); }
+CTC_HD size_t wave_pay_stride(const DecodeParams& p, int max_import) { return (size_t)p.max_surv * (size_t)wave_table(p, max_import); }
 
 // ---- wave-wide hash match ---------------------------------------------------------------------------------------
 // rep[j] = the smallest candidate index whose 64-bit key has the same 57-bit tag (key & ~127), for A candidates per lane

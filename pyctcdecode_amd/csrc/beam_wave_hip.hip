@@ -246,7 +246,7 @@ static int launch_wave_bw(const BeamArgs& a, hipStream_t stream, std::string* er
 }
 
 int launch_wave(const BeamArgs& a, hipStream_t stream, std::string* err) {
-  switch (wave_bucket(a.params.beam_width)) {
+  switch (wave_table(a.params, a.max_import)) {
     case 64: return launch_wave_bw<64>(a, stream, err);
     case 100: return launch_wave_bw<100>(a, stream, err);
     default: return launch_wave_bw<128>(a, stream, err);

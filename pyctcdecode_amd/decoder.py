@@ -1532,6 +1532,9 @@ class BeamSearchDecoderCTC(_TranscriptCalls):
             streams.next_frame = [f + int(t) for f, t in zip(frames_in, batch.frames)]
         try:
             if want:
+                # (of this chunk. Only a chunk that is read has a result to ask: one that stays on the device -- not the
+                #  last, lists left unread -- leaves last_beam_kernel as the call before it set it)
+                self.last_beam_kernel = int(self._lib.dll.ctcdec_result_beam_kernel(res))
                 return streams.unpack(res)
         finally:
             if res:

@@ -299,11 +299,11 @@ bool beam_kernel_depends_on_input(const BeamArgs&) { return false; }  // (the si
 bool wave_kernel_chosen(const BeamArgs& a) {
   const char* force = getenv("CTCDEC_BEAM_KERNEL");  // "wave" / "group": same switch as the HIP backend (default here: wave)
   const bool want_group = force && force[0] == 'g';
-  return a.n_utts > 0 && !want_group && wave_eligible(a.tables, a.params) && a.max_import <= wave_bucket(a.params.beam_width);
+  return a.n_utts > 0 && !want_group && wave_eligible(a.tables, a.params) && a.max_import <= WAVE_MAX_BEAMS;
 }
 static int launch_beam_kernels(const BeamArgs& a, std::string*) {
   if (a.pay && wave_kernel_chosen(a)) {
-    switch (wave_bucket(a.params.beam_width)) {
+    switch (wave_table(a.params, a.max_import)) {
       case 64: run_wave<64>(a); break;
       case 100: run_wave<100>(a); break;
       default: run_wave<128>(a); break;
@@ -327,9 +327,10 @@ static int launch_beam_kernels(const BeamArgs& a, std::string*) {
     const int v = atoi(e);
     if (v == 64 || v == 128 || v == 256 || v == 512) group_threads = v;
   }
+  const int table_for = std::max<int>(a.params.beam_width, a.max_import);  // (backend_hip.hip: what the streams carry in)
   if (group_threads == 512 && !getenv("CTCDEC_SIM_CAND") && a.tables.n_lms <= 1)
-    cand = group_cand(beam_bucket(a.params.beam_width), true);
-  LdsShape shape = make_shape(a.params.beam_width, a.params.max_surv, cand);
+    cand = group_cand(beam_bucket(table_for), true);
+  LdsShape shape = make_shape(table_for, a.params.max_surv, cand);
   size_t bytes = lds_bytes(shape);
   std::vector<char> lds(bytes + 64);
   char* base = (char*)(((uintptr_t)lds.data() + 15) & ~(uintptr_t)15);

@@ -364,8 +364,8 @@ def test_hip_bench_n_gt_1_path_rehearsed_on_one_gpu():
 
 def test_more_carried_beams_than_the_wave_table_holds(sim_library, monkeypatch):  # noqa: F811
     """A chunk decoded with beam_width 128 hands on up to 128 beams; the next one asks for beam_width 100, whose one-wave
-    table holds 100 records: the launch has to fall back to the workgroup kernel instead of overrunning the table
-    (round-2 advisor finding), resident and host-imported alike."""
+    table holds 100 records: the launch has to run on a table that holds them all (beam_wave.h: wave_table; once: the
+    workgroup kernel) instead of overrunning that one (round-2 advisor finding), resident and host-imported alike."""
     monkeypatch.setenv("CTCDEC_BEAM_KERNEL", "wave")
     labels = synth.LIBRI_LABELS
     dec = _build()(labels)
